@@ -1,6 +1,7 @@
 """Forward-throughput benchmark of the MI355X path (clips/s), one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload x3d_m|x3d_l|slowfast_r50|mvit_b_32x3]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,10 +14,18 @@ fixed per-GPU batch (weak scaling) and the step ends with the single head collec
 `torch.distributed.run` with N ranks on 127.0.0.1, so `python bench.py --gpus 8` is the same
 job as the explicit launcher line above.
 
-Default workload = BASELINE.json configs[1]: X3D-M, bf16, [32,3,16,224,224] per GPU; the same line carries, under
-"secondary", MViT-B 32x3 (configs[3], the other model BASELINE.json's metric names), SlowFast-R50 8x8 (configs[2]) and
-X3D-L (configs[4]) -- each with its own step percentiles, sustained run and roofline object.  At N > 1 the secondary
-legs are MViT-B (the metric names it at 1/2/4/8 GPUs) and X3D-L (configs[4]: global batch 32 N sharded over the N GPUs).
+Default workload = BASELINE.json configs[1]: X3D-M, bf16, [32,3,16,224,224] per GPU.  A plain run (no --full) builds
+the workload, runs W warm-up steps and K timed steps and prints the line.
+
+`--full` adds everything else the line can carry: a >= 2 s sustained run, the roofline object (per-op profiling of the
+single-plan form), the CPU baseline at N = 1 and, under "secondary", MViT-B 32x3 (configs[3], the other model
+BASELINE.json's metric names), SlowFast-R50 8x8 (configs[2]) and X3D-L (configs[4]) -- each with its own step
+percentiles, sustained run and roofline object.  At N > 1 the secondary legs are MViT-B (the metric names it at
+1/2/4/8 GPUs) and X3D-L (configs[4]: global batch 32 N sharded over the N GPUs).  The --no-* options drop single parts
+of a --full run.
+
+`--dump-outputs DIR` writes what the last timed step returned, the [global batch, 400] logits, to DIR/logits.npy
+(float32).  Weights and inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -379,7 +388,8 @@ def timed_steps(step, steps, world, device):
 
 
 def run_workload(name, args, world, rank, device, steps, warmup, sustained_s=0.0, prewarm_s=0.0):
-    """Build, warm up, time; returns (result dict, deployed model, input).  prewarm_s (secondary legs only): untimed replays
+    """Build, warm up, time; returns (result dict, deployed model, input, step, host copy of the last timed step's output,
+    taken before the sustained run replays the step again).  prewarm_s (secondary legs only): untimed replays
     for that long BEFORE the W warm-up steps -- the host-side conversion of a leg's model leaves the GPU idle for seconds,
     and twice in three default runs the X3D-L leg (the longest conversion, the last leg) had one or two ~25 ms replays
     among its first timed steps behind 5 warm-up replays (p50 5.4 ms; profiles/r6/bench_default_line.json of calls 83 / 91)."""
@@ -423,6 +433,7 @@ def run_workload(name, args, world, rank, device, steps, warmup, sustained_s=0.0
         out = step()
     elapsed, step_ms, out = timed_steps(step, steps, world, device)
     assert out.shape == (batch * world, 400) and torch.isfinite(out).all()
+    last = out.detach().float().cpu()
     pct = lambda q: round(step_ms[min(len(step_ms) - 1, int(q * len(step_ms)))], 4)
     res = {"value": round(batch * world * steps / elapsed, 2), "ms_per_step": round(elapsed / steps * 1e3, 4),
            "step_ms": {"p10": pct(0.1), "p50": pct(0.5), "p90": pct(0.9)}, "steps": steps, "per_gpu_batch": batch,
@@ -432,7 +443,22 @@ def run_workload(name, args, world, rank, device, steps, warmup, sustained_s=0.0
         e2, _, _ = timed_steps(step, n, world, device)
         res["sustained"] = {"seconds": round(e2, 3), "steps": n, "value": round(batch * world * n / e2, 2),
                             "ms_per_step": round(e2 / n * 1e3, 4)}
-    return res, model, x, step
+    return res, model, x, step, last
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each host tensor of `arrays` as out_dir/<name>.npy in float32.  The logits are 1.6 KB per clip, so
+    the whole output always fits the limit at any batch a GPU holds; a larger dump is refused rather than sampled."""
+    import numpy as np
+    total = sum(t.numel() * 4 for t in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 # the head collective of this process: a pv_comm communicator (RCCL driven from C) at N > 1 or with --head-comm
@@ -596,6 +622,8 @@ def dry_host(args, world, rank, stdout_guard):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     assert out.shape == (batch * world, 400)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": out})
     # ---- N-GPU readiness beyond the launcher (round-4 verdict, next #7): everything below runs WITHOUT a GPU ----
     ready = {}
     # (1) the rank -> device / CPU binding the real run makes: cuda:LOCAL_RANK, a disjoint CPU slice per rank
@@ -705,11 +733,15 @@ def _main(out):
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--streams", type=int, default=0,
                     help="sub-batches replayed concurrently on their own HIP streams (0: the workload's default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the MViT-B / SlowFast-R50 / X3D-L legs of the default line")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the >= 2 s sustained run")
+    ap.add_argument("--full", action="store_true",
+                    help="also the sustained run, the roofline object, the secondary legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the logits of the last timed step to DIR/logits.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the MViT-B / SlowFast-R50 / X3D-L legs")
+    ap.add_argument("--no-sustained", action="store_true", help="with --full: skip the >= 2 s sustained run")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="skip the per-op profiling passes (rocprofv3 --pmc runs: only the replays are wanted)")
+                    help="with --full: skip the per-op profiling passes (rocprofv3 --pmc runs: only the replays are wanted)")
     ap.add_argument("--with-h2d", action="store_true",
                     help="also time steps that upload the (pinned) host input first; reported as pcie_inclusive, never as value")
     ap.add_argument("--head-comm", nargs="?", const="on", default="", choices=["", "on", "require"],
@@ -720,6 +752,8 @@ def _main(out):
                     help="with --dry-host: every rank runs the host half of --workload's conversion at its per-GPU batch, timed")
     ap.add_argument("--tune", default="", help="development knobs k=v,... (pytorchvideo_amd.accelerator.mi355x.tuning / pv_tune_set)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         out.restore()                      # the ranks inherit this process's stdout
@@ -752,11 +786,13 @@ def _main(out):
 
     setup_head_collective(args, world)
     wl = WORKLOADS[args.workload]
-    res, model, x, step = run_workload(args.workload, args, world, rank, device, args.steps, args.warmup,
-                                       sustained_s=0.0 if args.no_sustained else 2.0)
+    res, model, x, step, last = run_workload(args.workload, args, world, rank, device, args.steps, args.warmup,
+                                             sustained_s=2.0 if args.full and not args.no_sustained else 0.0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": last})
     batch = res["per_gpu_batch"]
     pcie = pcie_leg(model, x, step, batch, args.steps, device) if args.with_h2d else None
-    if args.no_roofline or rank != 0:
+    if not args.full or args.no_roofline or rank != 0:
         roof, prof, agg = None, [], {}
     else:
         roof, prof, agg = roofline_of(roofline_session(model, args.workload, batch, device, args), args.workload,
@@ -768,15 +804,15 @@ def _main(out):
     # own roofline object.  `value` of the line stays the X3D-M number at every N so that the driver's scaling curve
     # compares like with like.
     secondary = None
-    if not args.no_secondary and not args.no_roofline and args.workload == "x3d_m" and not args.batch:
+    if args.full and not args.no_secondary and not args.no_roofline and args.workload == "x3d_m" and not args.batch:
         del model, x, step
         torch.cuda.empty_cache()
         secondary = {}
         for w2 in (("mvit_b_32x3", "slowfast_r50", "x3d_l") if world == 1 else ("mvit_b_32x3", "x3d_l")):
             # (the same K timed steps and W warm-up steps as the headline leg: with 10 steps behind 3 warm-up replays one slow
             #  replay -- 20 ms among 5.4 ms ones, X3D-L, profiles/r6/bench_default_line.json -- moved a leg's mean by 20 %)
-            r2, m2, x2, _ = run_workload(w2, args, world, rank, device, max(10, args.steps), max(3, args.warmup),
-                                         sustained_s=0.0 if args.no_sustained else 1.0, prewarm_s=0.3)
+            r2, m2, x2, _, _ = run_workload(w2, args, world, rank, device, max(10, args.steps), max(3, args.warmup),
+                                            sustained_s=0.0 if args.no_sustained else 1.0, prewarm_s=0.3)
             roof2 = None
             if rank == 0 or world == 1:
                 roof2, _, _ = roofline_of(roofline_session(m2, w2, r2["per_gpu_batch"], device, args), w2,
@@ -812,7 +848,7 @@ def _main(out):
             line["secondary"] = secondary
         if pcie is not None:
             line["pcie_inclusive"] = pcie
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.workload)
         if os.environ.get("PV_BENCH_VERBOSE") == "2":
             for label, kind, ms, alg_bytes, flops in prof:

@@ -38,6 +38,18 @@ def test_inside_a_torchrun_environment_the_world_size_wins():
     assert line["n_gpus"] == 1
 
 
+def test_dump_outputs_repeat_run_to_run(tmp_path):
+    """--dump-outputs DIR: the [global batch, 400] logits of the last timed step as float32 DIR/logits.npy, the same in a
+    second run with the same arguments (seeded weights and inputs)."""
+    import numpy as np
+    a, b = tmp_path / "a", tmp_path / "b"
+    line = _run(["--dump-outputs", str(a)])
+    _run(["--dump-outputs", str(b)])
+    got = np.load(a / "logits.npy")
+    assert got.dtype == np.float32 and got.shape == (line["config"]["global_batch"], 400) and np.isfinite(got).all()
+    assert np.array_equal(got, np.load(b / "logits.npy"))
+
+
 def test_two_ranks_gather_through_the_c_communicator(tmp_path):
     # the head collective of `bench.py --gpus N`: pv_comm_* with a host-memory double of librccl behind the dlopen
     so = os.path.join(str(tmp_path), "librccl_stub.so")
