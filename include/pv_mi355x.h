@@ -137,10 +137,24 @@ typedef struct pv_conv3d_desc {
   const float* pw2_scale;    /* [pw2_cout] or NULL (=1) */
   const float* pw2_shift;    /* [pw2_cout] or NULL (=0) */
   int32_t pw2_cout, pw2_act;
+  /* The X3D stem reading the CALLER'S clip (round 7), where pv_conv3d_ncdhw_supported(d) is 1 (with dwt_w): instead of
+   * pv_ingest_ncdhw copying the clip into the 4-channel layout before every forward, the stem kernel stages it from the
+   * caller's NCDHW tensor itself.  x_src_slot points at 8 bytes of DEVICE memory that the kernel reads when it starts:
+   *   0     -> the input is `x` in the 4-channel layout, exactly as without this field (an ingest filled it: the uint8 /
+   *            normalising / frame-selecting forms of pytorchvideo_amd.transforms.DevicePacker, fp32 or strided input);
+   *   other -> the address of a contiguous bf16 [B][x_src_c][Ti][Hi][Wi] tensor (any 2-byte alignment), read in place.
+   * A device slot rather than a kernel argument: the captured graph (pv_plan_graph_build / pv_joint_build) keeps its
+   * nodes and the way it is replayed, and follows the input through a stream-ordered 8-byte write of the slot in front
+   * of the replay, made only when the address changes.  The output is bit-identical to ingest + the 4-channel stem.
+   * NULL: no slot (the 4-channel layout only). */
+  const void* x_src_slot;
+  int32_t x_src_c;        /* channel planes of the caller's clip, 1..4 (planes beyond them read as 0) */
 } pv_conv3d_desc;
 int pv_conv3d(const pv_conv3d_desc* d, pv_stream_t stream);
 /* 1 if this geometry (pointers are ignored) can run with the fused temporal conv, else 0 */
 int pv_conv3d_dwt_supported(const pv_conv3d_desc* d);
+/* 1 if this geometry (pointers are ignored; x_src_c > 0) can read the caller's NCDHW clip through x_src_slot, else 0 */
+int pv_conv3d_ncdhw_supported(const pv_conv3d_desc* d);
 /* 1 if this geometry (pointers are ignored; x2_cin > 0) can run with the second K operand, else 0 */
 int pv_conv3d_x2_supported(const pv_conv3d_desc* d);
 /* 1 if this geometry (pointers are ignored; pw2_cout > 0) can run with the pointwise conv behind it, else 0 */

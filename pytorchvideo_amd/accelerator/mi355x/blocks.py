@@ -87,8 +87,7 @@ class Mi355xBlock(EfficientBlockBase):
     def _deploy_forward(self, x):
         sess = self._sess
         sess.finalize()
-        if not sess.matches(x, self._in_ref):
-            sess.ingest(x, self._in_ref)
+        sess.feed(x, self._in_ref)
         sess.launch(*self._op_range)
         out = self._out_ref
         if out.T == out.H == out.W == 1 and out.f32:
@@ -135,8 +134,7 @@ class Mi355xMultiPathBlock(Mi355xBlock):
         sess = self._sess
         sess.finalize()
         for t, ref in zip(x, self._in_ref):
-            if not sess.matches(t, ref):
-                sess.ingest(t, ref)
+            sess.feed(t, ref)
         sess.launch(*self._op_range)
         if getattr(self, "inplace", False) and self._pre_ref is not None:
             for i, r in enumerate(self._pre_ref):  # the reference overwrites the caller's list (net.py:111-118)
@@ -179,8 +177,7 @@ class Mi355xRoIHeadBlock(Mi355xBlock):
     def _deploy_forward(self, x, bboxes):
         sess = self._sess
         sess.finalize()
-        if not sess.matches(x, self._in_ref):
-            sess.ingest(x, self._in_ref)
+        sess.feed(x, self._in_ref)
         sess.load_boxes(bboxes, self._boxes, self._num_boxes)
         sess.launch(*self._op_range)
         return self._result().clone()

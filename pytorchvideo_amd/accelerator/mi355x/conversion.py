@@ -306,10 +306,9 @@ def _ingest_inputs(s, x, first_in, multi):
     if multi:
         assert isinstance(x, list), "input for MultiPathWayWithFuse needs to be a list of tensors"
         for t, ref in zip(x, first_in):
-            if not s.matches(t, ref):
-                s.ingest(t, ref)
-    elif not s.matches(x, first_in):
-        s.ingest(x, first_in)
+            s.feed(t, ref)
+    else:
+        s.feed(x, first_in)
 
 
 def _try_fuse_net(model, lut, batch, sess, dtype, input_tensor=None):
@@ -457,8 +456,7 @@ def _try_fuse_mvit(model, sess, dtype, input_tensor):
             if x.dim() != 4:
                 raise L.PvError("deploy form was converted for images [B,C,H,W], got %s" % (tuple(x.shape),))
             x = x.unsqueeze(2)
-        if not s.matches(x, first_in):
-            s.ingest(x, first_in)
+        s.feed(x, first_in)
         s.launch(use_graph=self._pv_use_graph)
         return s.view_rows(out)[:, 0, :].clone()   # fresh tensor; `_pv_result()` is the zero-copy view
 

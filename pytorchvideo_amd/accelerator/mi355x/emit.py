@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from ... import _lib as L
 from . import tuning
-from .session import pad8
+from .session import Ptr, pad8
 
 
 class Unsupported(Exception):
@@ -269,6 +269,17 @@ def emit_conv(sess, conv, x, norm=None, act=L.ACT_NONE, residual=None, a_gate=No
         taps_t = torch.zeros(dk, pad8(cout), dtype=torch.float32)
         taps_t[:, :cout] = dwt.weight.detach().float().cpu().reshape(cout, dk).t()
         f.update(dwt_w=sess.add_weight(taps_t), dwt_k=dk)
+    if c4:
+        # the library decides whether this stem can read the caller's NCDHW clip (Session.ingest then skips the ingest)
+        d = L.Conv3dDesc(**{k: v for k, v in f.items() if not isinstance(v, Ptr) and v is not None})
+        d.x_src_c = x.C
+        if (dwt is not None and tuning.get("stem_ncdhw") and x.c4_readers == 0
+                and L.lib().pv_conv3d_ncdhw_supported(C.byref(d)) == 1):
+            if x.src_slot is None:
+                x.src_slot = sess.add_weight(torch.zeros(1, dtype=torch.int64))
+            f.update(x_src_slot=x.src_slot, x_src_c=x.C)
+        else:
+            x.c4_readers += 1       # reads the 4-channel buffer: every forward must fill it
     vox_in, vox_out = x.B * x.voxels, y.B * y.voxels
     taps = kt * kh * kw
     reads = vox_out * cin_p if taps == 1 else vox_in * cin_p  # each input voxel once

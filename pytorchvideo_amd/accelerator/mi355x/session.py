@@ -48,13 +48,16 @@ class TRef:
     their (t,h,w) grid and cls-prefix separately."""
 
     __slots__ = ("off", "B", "T", "H", "W", "C", "ld", "bs", "itemsize", "nbytes", "owned", "f32",
-                 "thw", "has_cls", "prenorm")
+                 "thw", "has_cls", "prenorm", "src_slot", "c4_readers")
 
     def __init__(self, off, B, T, H, W, C, ld, bs, itemsize, nbytes, owned=True, f32=False):
         self.off, self.B, self.T, self.H, self.W, self.C = off, B, T, H, W, C
         self.ld, self.bs, self.itemsize, self.nbytes, self.owned, self.f32 = ld, bs, itemsize, nbytes, owned, f32
         self.thw, self.has_cls = None, False
         self.prenorm = None     # (TRef, norm module): LayerNorm of this stream already written by its producer (emit_mvit)
+        # model inputs in the 4-channel layout: the device slot through which the stem reads the caller's NCDHW clip
+        # (x_src_slot, include/pv_mi355x.h), and how many ops read the 4-channel buffer itself (see Session.ingest)
+        self.src_slot, self.c4_readers = None, 0
 
     @property
     def ptr(self):
@@ -159,6 +162,7 @@ class Session:
         self.weights_t = None
         self._graph_ready = False
         self._desc_keep = []
+        self._slot_vals = {}    # weights offset of a source slot -> the address last written into it (0 = the arena buffer)
 
     # ------------------------------------------------------------------ memory
     def alloc_input(self, B, T, H, W, C):
@@ -329,12 +333,39 @@ class Session:
         v = self.view(ref)
         return x.data_ptr() == v.data_ptr() and x.dtype == v.dtype and x.stride() == v.stride() and x.shape == v.shape
 
+    def _point_input(self, ref, addr):
+        """Make the ops that read `ref` through its source slot read the clip at device address `addr` (0: the arena
+        buffer itself).  A stream-ordered 8-byte fill in front of the replay, only when the address changes."""
+        if ref.src_slot is None or self._slot_vals.get(ref.src_slot.off, 0) == addr:
+            return
+        with torch.cuda.device(self.device):
+            self.weights_t[ref.src_slot.off: ref.src_slot.off + 8].view(torch.int64).fill_(addr)
+        self._slot_vals[ref.src_slot.off] = addr
+
+    def feed(self, x, ref):
+        """Model input `x` for the arena buffer `ref`: nothing to do when `x` already is that buffer, else ingest."""
+        if self.matches(x, ref):
+            self._point_input(ref, 0)
+        else:
+            self.ingest(x, ref)
+
     def ingest(self, x, ref, t_index=None, ch_scale=None, ch_shift=None):
         """Copy a user tensor (NCDHW, any strides; fp32, bf16 or uint8) into the channels-last arena
         buffer `ref`.  `t_index` (int32 device tensor, one source frame per destination frame) selects
         frames in the same pass; `ch_scale` / `ch_shift` (fp32 device tensors [C]) apply
-        y = x*scale + shift -- see pytorchvideo_amd.transforms.DevicePacker."""
+        y = x*scale + shift -- see pytorchvideo_amd.transforms.DevicePacker.
+        When every op that reads `ref` is a stem that reads the caller's clip itself (ref.src_slot, decided by the
+        library at conversion: pv_conv3d_ncdhw_supported) and `x` is a plain contiguous bf16 clip on the session's
+        device, nothing is copied: the stem is pointed at `x`, which must then stay alive until the replay has run."""
         lib = L.lib()
+        if (ref.src_slot is not None and ref.c4_readers == 0 and t_index is None and ch_scale is None
+                and x.is_cuda and x.device == self.arena_t.device and x.dtype == torch.bfloat16 and x.dim() == 5
+                and x.is_contiguous()):
+            if tuple(x.shape) != (ref.B, ref.C, ref.T, ref.H, ref.W):
+                raise L.PvError("deploy form was converted for input %s, got %s" %
+                                ((ref.B, ref.C, ref.T, ref.H, ref.W), tuple(x.shape)))
+            self._point_input(ref, x.data_ptr())
+            return
         if not x.is_cuda:
             x = x.to(self.device, non_blocking=True)
         if x.dtype not in (torch.float32, torch.bfloat16, torch.uint8):
@@ -345,6 +376,7 @@ class Session:
         if (B, Cc, T, H, W) != (ref.B, ref.C, ref.T, ref.H, ref.W):
             raise L.PvError("deploy form was converted for input %s, got %s" %
                             ((ref.B, ref.C, ref.T, ref.H, ref.W), (B, Cc, T, H, W)))
+        self._point_input(ref, 0)
         d = L.LayoutDesc()
         d.src, d.dst = x.data_ptr(), self.arena_t.data_ptr() + ref.off
         d.B, d.C, d.T, d.H, d.W = B, Cc, T, H, W

@@ -11,6 +11,7 @@ OPTIONS = {
     "fuse_block": True,          # a whole X3D residual block without squeeze-excitation as ONE launch (pv_bottleneck, round 6)  (emit.can_fuse_bottleneck)
     "fuse_bc": True,             # conv_b (narrow dense conv) -> pointwise conv_c of a ResNet / SlowFast bottleneck as ONE launch (pv_conv3d pw2_*, round 6)  (emit.can_fuse_conv_bc)
     "fuse_stem": True,           # X3D stem (conv_xy + temporal depthwise + BN + ReLU) in one launch
+    "stem_ncdhw": True,          # ... that reads the caller's bf16 NCDHW clip itself: no ingest launch (round 7)  (emit.emit_conv)
     "fuse_kv_pool": True,        # MViT pool_k + pool_v as one depthwise launch                   (emit_mvit)
     "fuse_posenc": True,         # position tables added in the patch-embedding conv's epilogue   (emit_mvit)
     "split_joint_graph": True,   # sub-batches of SplitBatchDeployed as branches of ONE hipGraph  (conversion)

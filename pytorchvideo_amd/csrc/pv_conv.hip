@@ -25,6 +25,7 @@ int pv_gemm9_try(const pv_conv3d_desc& d, bool pw, hipStream_t s);      // pv_ge
 int pv_tapstream_try(const pv_conv3d_desc& d, hipStream_t s, bool dry = false);   // pv_lateral.hip
 int pv_stem_c4(const pv_conv3d_desc& d, hipStream_t s);                 // pv_stem.hip
 int pv_stem_dwt_supported(const pv_conv3d_desc& d);                     // pv_stem.hip
+int pv_stem_ncdhw_supported(const pv_conv3d_desc& d);                   // pv_stem.hip
 int pv_pwconv_x2_supported(const pv_conv3d_desc& d);                    // pv_pwconv.hip
 
 namespace {
@@ -376,6 +377,11 @@ template <typename T> int launch_conv(const pv_conv3d_desc& d, bool pw, hipStrea
 extern "C" int pv_conv3d_dwt_supported(const pv_conv3d_desc* d) {
   if (!d || d->B <= 0 || d->cout <= 0 || d->To <= 0 || d->Ho <= 0 || d->Wo <= 0) return 0;
   return pv_stem_dwt_supported(*d);
+}
+
+extern "C" int pv_conv3d_ncdhw_supported(const pv_conv3d_desc* d) {
+  if (!d || d->B <= 0 || d->cout <= 0 || d->To <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Ti <= 0 || d->Hi <= 0 || d->Wi <= 0) return 0;
+  return pv_stem_ncdhw_supported(*d);
 }
 
 extern "C" int pv_conv3d_pw2_supported(const pv_conv3d_desc* d) {

@@ -893,7 +893,311 @@ template <int NT, int TM, int KS, int DK> int launch_stem_dwt(const pv_conv3d_de
   return PV_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// The X3D stem reading the CALLER'S clip (x_src_slot, include/pv_mi355x.h): 1 x 3 x 3 conv_xy, stride (1,2,2),
+// padding (0,1,1), + the depthwise temporal conv of the kernel above, with the same MFMA K order, register ring,
+// BN and activation -- only the load stage differs.  Without it every forward first ran pv_ingest_ncdhw (NCDHW ->
+// the 4-channel layout: 154 MB read + 205 MB written for X3D-M's 32 clips), and the kernel above then re-read those
+// 205 MB with one small load in flight per wave.
+//
+// A workgroup owns an 8 x 16 output tile of one clip (wave w: output rows 2w, 2w+1 = the TM = 2 MFMA column groups)
+// and walks the T axis.  Each input frame's halo (17 rows x columns [wi0 - 7, wi0 + 41), where wi0 = 2*wo0 - 1 is the
+// first input column of the tile) is staged into LDS in the 4-channel layout, double-buffered: frame t+1's loads are
+// issued before frame t's MFMAs.  One staging task = one row x 8 voxels (a 16-byte-aligned chunk of every channel
+// plane), written as four 16-byte LDS chunks (channel 3 = 0 when the clip has 3).  The B fragment of lane (n, q) is
+// the two voxels at LDS column 7 + 2n + dw, exactly the 16 bytes the kernel above loads -- zeros where it loads zeros
+// (image border: zero-filled halo; the 4th window column and the unused pairs of K step 1: masked in registers) -- so
+// the output is bit-identical.  The slot is read when the kernel starts, so a captured graph follows the input:
+//   0                                 -> the 4-channel buffer `x` (filled by the ingest: uint8 / t_index / ... forms);
+//   a 16-byte-aligned clip, Wi % 8 == 0 -> one 16-byte load per channel plane and task;
+//   any other clip (2-byte aligned)   -> element loads (correct everywhere, slow; no MI355X workload takes it).
+// The kernel waits on one frame's loads per step, so what hides the latency is the number of resident workgroups: the
+// temporal taps and BN live in LDS and the launch bounds ask for three workgroups per CU (168 VGPRs; two at 244 VGPRs
+// took 199 instead of 168 us for X3D-M's 32 clips).  Two frames in flight per workgroup bought nothing: the output
+// stores share vmcnt with the loads and retire out of order with them, so the wait for the older frame is vmcnt(0).
+constexpr int kDirTH = 8, kDirTW = 16;          // output tile
+constexpr int kDirIH = 2 * kDirTH + 1;          // 17 staged input rows
+constexpr int kDirNC = 6;                       // 8-voxel chunks per staged row
+constexpr int kDirIW = kDirNC * 8;              // 48 staged columns (41 used)
+constexpr int kDirTasks = kDirIH * kDirNC;      // 102 (row, chunk) staging tasks per frame
+constexpr int kDirFrame = kDirIH * kDirIW * 4;  // bf16 elements per staged frame
+enum { kSrcC4 = 0, kSrcVec = 1, kSrcScalar = 2 };
+
+template <int MODE, int NCH, int DK, int ACT>
+__device__ __forceinline__ void stem_dir_body(const pv_conv3d_desc& d, const void* src, const bf16_t* w_s, bf16_t* tiles,
+                                              f32x4* ep_s, int b, int ho0, int wo0) {
+  constexpr int NT = 2, TM = 2, KS = 2;
+  constexpr int WLD = KS * 32 + 8;
+  constexpr int HALF = DK / 2;
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  constexpr unsigned kOOB = 0x80000000u;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int n16 = lane & 15, q = lane >> 4;
+  const int cout_p8 = pv_round_up(d.cout, 8);
+  const int Cs = d.x_src_c;
+
+  // ---- staging task of this thread: row r, chunk c of the halo (threads spread over the four waves) ----
+  const int task = lane * 4 + wave;
+  const bool has_task = task < kDirTasks;
+  const int r = task / kDirNC, c = task - r * kDirNC;
+  const int hi = ho0 * 2 - 1 + r, gc = wo0 * 2 - 8 + c * 8;   // gc: first global column of the chunk (multiple of 8)
+  const bool rok = has_task && (unsigned)hi < (unsigned)d.Hi;
+  const unsigned plane = (unsigned)(d.Hi * d.Wi);               // elements per channel plane of one frame
+  __amdgpu_buffer_rsrc_t rx;
+  unsigned t_stride, base;   // element offsets: frame step, and (clip, row, chunk) start
+  if constexpr (MODE == kSrcC4) {
+    rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.x), 0, (int)((unsigned)d.B * (unsigned)d.x_bs * 2u), 0x00020000);
+    t_stride = plane * 4u;
+    base = (unsigned)b * (unsigned)d.x_bs + ((unsigned)hi * d.Wi + gc) * 4u;
+  } else {
+    rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(src), 0,
+                                           (int)((unsigned)d.B * (unsigned)Cs * (unsigned)d.Ti * plane * 2u), 0x00020000);
+    t_stride = plane;
+    base = (unsigned)b * (unsigned)Cs * (unsigned)d.Ti * plane + (unsigned)hi * d.Wi + gc;
+  }
+  // raw loads of one task: C4 = 8 voxels x 8 bytes; Vec / Scalar = 8 elements of each of the 4 channel planes
+  u32x4 rw[4];
+  auto load_frame = [&](int t) {
+    if constexpr (MODE == kSrcC4) {
+#pragma unroll
+      for (int e = 0; e < 8; e += 2) {
+        u32x2 v[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const bool ok = rok && (unsigned)(gc + e + k) < (unsigned)d.Wi;
+          v[k] = __builtin_amdgcn_raw_buffer_load_b64(rx, (int)(ok ? (base + (unsigned)t * t_stride + (e + k) * 4u) * 2u : kOOB), 0, 0);
+        }
+        rw[e / 2] = u32x4{v[0][0], v[0][1], v[1][0], v[1][1]};
+      }
+    } else if constexpr (MODE == kSrcVec) {
+      // Wi % 8 == 0: a chunk is wholly inside or outside.  No branch around a load (planes beyond Cs read out of
+      // range = 0): with a fixed number of loads per frame the compiler waits for exactly the ones it needs, and the
+      // prefetch stays in flight across the MFMAs and the ring update
+      const bool ok = rok && (unsigned)gc < (unsigned)d.Wi;
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch)
+        rw[ch] = __builtin_amdgcn_raw_buffer_load_b128(
+            rx, (int)(ok && ch < Cs ? (base + ((unsigned)ch * d.Ti + t) * plane) * 2u : kOOB), 0, 0);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 4; ++ch) {
+        unsigned e16[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const bool ok = rok && ch < Cs && (unsigned)(gc + e) < (unsigned)d.Wi;
+          e16[e] = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(
+              rx, (int)(ok ? (base + ((unsigned)ch * d.Ti + t) * plane + e) * 2u : kOOB), 0, 0);
+        }
+        rw[ch] = u32x4{e16[0] | (e16[1] << 16), e16[2] | (e16[3] << 16), e16[4] | (e16[5] << 16), e16[6] | (e16[7] << 16)};
+      }
+    }
+  };
+  // -> four 16-byte chunks of the 4-channel layout (two voxels each) at row r, columns 8c .. 8c+7 of the staged frame
+  auto store_frame = [&](int buf) {
+    if (!has_task) return;
+    u32x4* dst = reinterpret_cast<u32x4*>(tiles + (size_t)buf * kDirFrame + (size_t)(r * kDirIW + c * 8) * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if constexpr (MODE == kSrcC4) {
+        dst[j] = rw[j];
+      } else {
+        // plane dword j holds voxels 2j (low half) and 2j+1 (high half)
+        const unsigned p0 = rw[0][j], p1 = rw[1][j], p2 = rw[2][j], p3 = NCH == 4 ? rw[3][j] : 0u;
+        dst[j] = u32x4{(p0 & 0xffffu) | (p1 << 16), (p2 & 0xffffu) | (p3 << 16),
+                       (p0 >> 16) | (p1 & 0xffff0000u), (p2 >> 16) | (p3 & 0xffff0000u)};
+      }
+    }
+  };
+
+  // ---- this lane's B fragments: LDS offset and masks per (row group i, K step) ----
+  int boff[TM][KS];
+  unsigned mlo[KS], mhi[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const int pi = ks * 4 + q;              // voxel pair of the packed K (kw = 3 -> 2 pairs per window row)
+    const int dh = pi >> 1, dw = 2 * (pi & 1);
+    const bool pok = dh < 3;
+    mlo[ks] = pok ? ~0u : 0u;
+    mhi[ks] = pok && dw == 0 ? ~0u : 0u;    // voxel dw + 1 == 3 is outside the 3-wide window
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+      boff[i][ks] = ((2 * (2 * wave + i) + (pok ? dh : 0)) * kDirIW + 7 + 2 * n16 + dw) * 4;
+  }
+  unsigned yo[TM];
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int ho = ho0 + 2 * wave + i, wo = wo0 + n16;
+    yo[i] = (ho < d.Ho && wo < d.Wo) ? (unsigned)((ho * d.Wo + wo) * d.ldy + q * 4) * 2u : kOOB;
+  }
+  __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(d.y, 0, (int)((unsigned)d.B * (unsigned)d.y_bs * 2u), 0x00020000);
+  const unsigned y_frame = (unsigned)(d.Ho * d.Wo * d.ldy) * 2u, y_clip = (unsigned)b * (unsigned)d.y_bs * 2u;
+
+  // ---- temporal taps, folded BN scale, shift of channels a*16 + 4q .. +3 in LDS: ep_s[(e * NT + a) * 4 + q],
+  //      e < DK tap, e = DK scale, e = DK + 1 shift (56 VGPRs a lane less: three workgroups per CU instead of two) ----
+  for (int id = tid; id < (DK + 2) * NT * 4; id += kThreads) {
+    const int qq = id & 3, a = (id >> 2) % NT, e = (id >> 2) / NT;
+    f32x4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int ch = a * 16 + qq * 4 + j;
+      const bool ok = ch < d.cout;
+      v[j] = !ok ? 0.f : e < DK ? d.dwt_w[e * cout_p8 + ch] : e == DK ? (d.scale ? d.scale[ch] : 1.f) : (d.shift ? d.shift[ch] : 0.f);
+    }
+    ep_s[id] = v;
+  }
+  auto ep = [&](int e, int a) { return ep_s[(e * NT + a) * 4 + q]; };
+
+  f32x4 ring[DK][NT][TM];
+#pragma unroll
+  for (int k = 0; k < DK; ++k)
+#pragma unroll
+    for (int a = 0; a < NT; ++a)
+#pragma unroll
+      for (int i = 0; i < TM; ++i) ring[k][a][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  auto step = [&](auto Rc, int t) {
+    constexpr int R = decltype(Rc)::value;   // t mod DK
+    if (t < d.Ti) {
+      if (t + 1 < d.Ti) load_frame(t + 1);   // in flight under this frame's MFMAs and ring update
+      const bf16_t* fr = tiles + (size_t)(t & 1) * kDirFrame;
+      f32x4 h[NT][TM];
+#pragma unroll
+      for (int a = 0; a < NT; ++a)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) h[a][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        bf16x8 bv[TM];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          const u32x2 lo = *reinterpret_cast<const u32x2*>(fr + boff[i][ks]);
+          const u32x2 hi2 = *reinterpret_cast<const u32x2*>(fr + boff[i][ks] + 4);
+          const u32x4 u = {lo[0] & mlo[ks], lo[1] & mlo[ks], hi2[0] & mhi[ks], hi2[1] & mhi[ks]};
+          bv[i] = __builtin_bit_cast(bf16x8, u);
+        }
+#pragma unroll
+        for (int a = 0; a < NT; ++a) {
+          const bf16x8 wf = *reinterpret_cast<const bf16x8*>(w_s + (a * 16 + n16) * WLD + ks * 32 + q * 8);
+#pragma unroll
+          for (int i = 0; i < TM; ++i) h[a][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, bv[i], h[a][i], 0, 0, 0);
+        }
+      }
+      // frame t feeds output t + HALF - k with tap k
+#pragma unroll
+      for (int k = 0; k < DK; ++k) {
+        const int slot = (R + HALF - k + DK) % DK;
+#pragma unroll
+        for (int a = 0; a < NT; ++a)
+#pragma unroll
+          for (int i = 0; i < TM; ++i) ring[slot][a][i] += ep(k, a) * h[a][i];
+      }
+    }
+    // frame t+1 into the other buffer BEFORE this step's output stores: the wait is then for its loads only, and the
+    // stores drain behind the barrier
+    if (t + 1 < d.Ti) store_frame((t + 1) & 1);
+    const int to = t - HALF;
+    constexpr int slot = (R - HALF + DK) % DK;
+    if (to >= 0 && to < d.To) {
+      const unsigned fb = y_clip + (unsigned)to * y_frame;
+#pragma unroll
+      for (int a = 0; a < NT; ++a) {
+        const bool cok = a * 16 + q * 4 < cout_p8;   // padding channels up to the 8-multiple are written as zeros
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          f32x4 v = ring[slot][a][i] * ep(DK, a) + ep(DK + 1, a);
+          if (ACT == PV_ACT_RELU) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+          }
+          const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+          const unsigned off = cok ? yo[i] + a * 32u + fb : kOOB;   // kOOB + anything stays out of range
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), ry, (int)off, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < NT; ++a)
+#pragma unroll
+      for (int i = 0; i < TM; ++i) ring[slot][a][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (t + 1 < d.Ti) __syncthreads();   // uniform; frame t+1 staged, nobody reads buffer t & 1 any more
+  };
+
+  load_frame(0);
+  store_frame(0);
+  __syncthreads();
+  for (int t0 = 0; t0 < d.Ti + HALF; t0 += DK) {
+    step(IntC<0>{}, t0);
+    step(IntC<1>{}, t0 + 1);
+    step(IntC<2>{}, t0 + 2);
+    if (DK > 3) {
+      step(IntC<3 % DK>{}, t0 + 3);
+      step(IntC<4 % DK>{}, t0 + 4);
+    }
+  }
+}
+
+template <int DK, int ACT>
+__global__ __launch_bounds__(kThreads, 3) void stem_dir_dwt_kernel(const pv_conv3d_desc d, int tiles_h, int tiles_w) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  constexpr int NT = 2, Kp = 64, WLD = Kp + 8;
+  bf16_t* w_s = reinterpret_cast<bf16_t*>(smem_raw);
+  bf16_t* tiles = w_s + NT * 16 * WLD;   // [2][kDirIH][kDirIW][4]
+  f32x4* ep_s = reinterpret_cast<f32x4*>(tiles + 2 * kDirFrame);   // [DK + 2][NT][4]
+  const int tid = threadIdx.x;
+  {
+    const bf16_t* __restrict__ Wt = static_cast<const bf16_t*>(d.w);
+    constexpr int K = 3 * 4 * 4, cpr = Kp / 8;   // packed [cout][kh = 3][kw 3 -> 4][4]
+    for (int id = tid; id < NT * 16 * cpr; id += kThreads) {
+      const int rr = id / cpr, kc = id - rr * cpr;
+      bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (rr < d.cout && kc * 8 < K) v = *reinterpret_cast<const bf16x8*>(Wt + (long)rr * K + kc * 8);
+      *reinterpret_cast<bf16x8*>(w_s + rr * WLD + kc * 8) = v;
+    }
+  }
+  // (the weights are visible behind the barrier after the first frame is staged)
+  int bid = blockIdx.x;
+  const int tw = bid % tiles_w; bid /= tiles_w;
+  const int th = bid % tiles_h;
+  const int b = bid / tiles_h;
+  const void* src = *static_cast<const void* const*>(d.x_src_slot);   // uniform: read once per workgroup
+  if (src == nullptr)
+    stem_dir_body<kSrcC4, 4, DK, ACT>(d, src, w_s, tiles, ep_s, b, th * kDirTH, tw * kDirTW);
+  else if (((uintptr_t)src & 15) == 0 && (d.Wi & 7) == 0)   // RGB: three plane loads per task, channel 3 = 0
+    d.x_src_c <= 3 ? stem_dir_body<kSrcVec, 3, DK, ACT>(d, src, w_s, tiles, ep_s, b, th * kDirTH, tw * kDirTW)
+                   : stem_dir_body<kSrcVec, 4, DK, ACT>(d, src, w_s, tiles, ep_s, b, th * kDirTH, tw * kDirTW);
+  else
+    stem_dir_body<kSrcScalar, 4, DK, ACT>(d, src, w_s, tiles, ep_s, b, th * kDirTH, tw * kDirTW);
+}
+
+template <int DK> int launch_stem_dir(const pv_conv3d_desc& d, hipStream_t s) {
+  const int tiles_h = (d.Ho + kDirTH - 1) / kDirTH, tiles_w = (d.Wo + kDirTW - 1) / kDirTW;
+  const long blocks = (long)d.B * tiles_h * tiles_w;
+  if (blocks > 0x7fffffffL) return PV_ERR_UNSUPPORTED;
+  const size_t lds = (size_t)2 * 16 * (64 + 8) * 2 + (size_t)2 * kDirFrame * 2 + (size_t)(DK + 2) * 2 * 4 * 16;
+  dim3 grid((unsigned)blocks), block(kThreads);
+  if (d.act == PV_ACT_RELU) PV_LAUNCH((stem_dir_dwt_kernel<DK, PV_ACT_RELU>), grid, block, lds, s, d, tiles_h, tiles_w);
+  else PV_LAUNCH((stem_dir_dwt_kernel<DK, PV_ACT_NONE>), grid, block, lds, s, d, tiles_h, tiles_w);
+  PV_LAUNCH_CHECK();
+  return PV_OK;
+}
+
 }  // namespace
+
+int pv_stem_dwt_supported(const pv_conv3d_desc& d);
+
+// geometry test for the stem above: X3D's conv_xy (1x3x3, stride (1,2,2), padding (0,1,1)) + temporal conv, reading a
+// contiguous bf16 [B][x_src_c][Ti][Hi][Wi] clip whose element offsets fit 31 bits
+int pv_stem_ncdhw_supported(const pv_conv3d_desc& d) {
+  if (!pv_stem_dwt_supported(d)) return 0;
+  if (d.kh != 3 || d.kw != 3 || d.sh != 2 || d.sw != 2 || d.ph != 1 || d.pw != 1) return 0;
+  if (d.x_src_c < 1 || d.x_src_c > 4 || d.cout > 32) return 0;
+  if ((long)d.B * d.x_src_c * d.Ti * d.Hi * d.Wi * 2 > 0x7fffffffL) return 0;
+  if ((long)d.B * d.x_bs * 2 > 0x7fffffffL || (long)d.B * d.y_bs * 2 > 0x7fffffffL) return 0;
+  return 1;
+}
 
 // geometry test for the fused temporal conv: first-layer 1 x kh x kw conv whose K fits two MFMA steps
 // (3x3 taps), at most 32 output channels, 3 or 5 temporal taps
@@ -919,6 +1223,10 @@ int pv_stem_c4(const pv_conv3d_desc& d, hipStream_t s) {
   const int KWP = (d.kw + (jp - 1) * d.sw + 1) & ~1;
   const int K = d.kt * d.kh * KWP * 4;
   const int ksteps = (K + 31) / 32;
+  if (d.x_src_slot) {   // X3D stem reading the caller's clip (or `x` when the slot holds 0)
+    if (!d.dwt_w || !pv_stem_ncdhw_supported(d)) return PV_ERR_UNSUPPORTED;
+    return d.dwt_k == 5 ? launch_stem_dir<5>(d, s) : launch_stem_dir<3>(d, s);
+  }
   if (d.dwt_w) {   // fused depthwise temporal conv (X3D stem)
     if (!pv_stem_dwt_supported(d)) return PV_ERR_UNSUPPORTED;
     if ((long)d.B * d.y_bs > 0x3fffffffL) return PV_ERR_UNSUPPORTED;
