@@ -320,6 +320,56 @@ typedef struct pv_layout_desc {
 int pv_ingest_ncdhw(const pv_layout_desc* d, pv_stream_t stream);
 int pv_egress_ncdhw(const pv_layout_desc* d, pv_stream_t stream);
 
+/* ---- short-side scale + uniform crop, fused into the ingest ---------------------------
+ * What every model-zoo recipe does to a decoded frame between the frame selection and the forward:
+ * short_side_scale (transforms/functional.py:92-131; module wrapper transforms/transforms.py:100-121) followed by
+ * uniform_crop (functional.py:302-347; transforms.py:153-175), whose spatial_idx 0 / 1 / 2 is the three-crop test
+ * protocol.  pv_resample_crop reads the decoded clip ONCE per view and writes the crop in a layout the first
+ * convolution reads, with pv_layout_desc's frame selection (t_index) and Div255 + Normalize affine (ch_scale /
+ * ch_shift) riding along: bilinear interpolation has weights that sum to 1, so it commutes with a per-channel affine
+ * map, and the kernel interpolates the raw taps in fp32 and applies the affine map to the result.
+ *
+ * The geometry is computed by the caller, so the library is not tied to one scaling or cropping rule: the clip is
+ * (virtually) scaled from Hs x Ws to Hn x Wn, and view v is the Ho x Wo window at (y_off[v], x_off[v]) of that.
+ * The arithmetic is torch.nn.functional.interpolate(size=(Hn, Wn), mode="bilinear", align_corners=False) without
+ * antialiasing, per axis in fp32:
+ *     s  = (float)n_in / (float)n_out
+ *     r  = max(0, s * (d + 0.5) - 0.5)          d = offset + index inside the window
+ *     i0 = (int)r;  i1 = i0 + (i0 < n_in - 1);  l1 = r - i0;  l0 = 1 - l1
+ *     v  = l0y (l0x p[i0y][i0x] + l1x p[i0y][i1x]) + l1y (l0x p[i1y][i0x] + l1x p[i1y][i1x])
+ *     out = v * ch_scale[c] + ch_shift[c], rounded once to dst_dtype
+ * Source:       PV_SRC_NCTHW  planar [B,C,src_T,Hs,Ws], PV_U8 or PV_F32 (what the decoders hand out after their permute)
+ *               PV_SRC_NTHWC  frame-interleaved [B,src_T,Hs,Ws,C], PV_U8 with C == 3 (before that permute)
+ * Destination:  PV_DST_NDHWC  the forms pv_ingest_ncdhw writes: c_p == 4 && ld == 4 (bf16), or c_p a multiple of 8
+ *                             (bf16 / fp32); voxel stride ld, batch stride bs, pad channels written as zeros
+ *               PV_DST_NCTHW  planar contiguous [n_items,C,T,Ho,Wo], bf16 / fp32 (the stem that reads the caller's clip)
+ * Destination batch item b * n_views + v is view v of source clip b.  A launch writes items [item0, item0 + n_items) of
+ * that sequence to positions 0 .. n_items-1 of dst (n_items == 0: all B * n_views of them), so a deploy form whose
+ * batch is split over several plans is filled one plan at a time.
+ * PV_ERR_INVALID: null pointers, C > 4, a window that leaves Hn x Wn, n_views outside 1..3, an interleaved source that
+ * is not uint8 with C == 3, a misaligned destination.  PV_ERR_UNSUPPORTED: any other dtype / layout pair.
+ */
+enum pv_resample_src_layout { PV_SRC_NCTHW = 0, PV_SRC_NTHWC = 1 };
+enum pv_resample_dst_layout { PV_DST_NDHWC = 0, PV_DST_NCTHW = 1 };
+typedef struct pv_resample_desc {
+  const void* src; void* dst;
+  int32_t B, C, T;            /* source clips, channels (<= 4), DESTINATION frames                              */
+  int32_t src_T, Hs, Ws;      /* source frames (used when t_index is given, else = T) and source frame size      */
+  int32_t src_dtype, src_layout;
+  int32_t Hn, Wn;             /* size after scaling                                                              */
+  int32_t Ho, Wo;             /* crop window size                                                                */
+  int32_t n_views;            /* 1..3                                                                            */
+  int32_t y_off[3], x_off[3]; /* per view: the window's origin inside Hn x Wn                                    */
+  int32_t item0, n_items;     /* destination items written by this launch (n_items == 0: all)                    */
+  int32_t dst_layout, dst_dtype;
+  int32_t c_p, ld;            /* PV_DST_NDHWC only, as in pv_layout_desc                                         */
+  int64_t bs;                 /* PV_DST_NDHWC only: batch stride in elements                                     */
+  const int32_t* t_index;     /* [T] source frame of every destination frame, or NULL (identity)                 */
+  const float* ch_scale;      /* [C] or NULL                                                                     */
+  const float* ch_shift;      /* [C] or NULL                                                                     */
+} pv_resample_desc;
+int pv_resample_crop(const pv_resample_desc* d, pv_stream_t stream);
+
 /* ---- row ops on (rows, C) matrices -------------------------------------------------
  * pv_layernorm: nn.LayerNorm(eps) over C (models/vision_transformers.py:333-335,
  *   layers/attention.py:199-205).

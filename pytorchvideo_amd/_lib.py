@@ -71,6 +71,14 @@ LayoutDesc = _struct("LayoutDesc", [
     + [("bs", _i64)] + _ints("src_dtype", "dst_dtype")
     + [("t_index", _p)] + _ints("src_T") + [("ch_scale", _p), ("ch_shift", _p)])
 
+SRC_NCTHW, SRC_NTHWC = 0, 1
+DST_NDHWC, DST_NCTHW = 0, 1
+ResampleDesc = _struct("ResampleDesc", [
+    ("src", _p), ("dst", _p)] + _ints("B", "C", "T", "src_T", "Hs", "Ws", "src_dtype", "src_layout", "Hn", "Wn", "Ho", "Wo",
+                                      "n_views")
+    + [("y_off", _i32 * 3), ("x_off", _i32 * 3)] + _ints("item0", "n_items", "dst_layout", "dst_dtype", "c_p", "ld")
+    + [("bs", _i64), ("t_index", _p), ("ch_scale", _p), ("ch_shift", _p)])
+
 RowsDesc = _struct("RowsDesc", [
     ("x", _p), ("y", _p), ("gamma", _p), ("beta", _p), ("rows", _i64)]
     + _ints("C", "ldx", "ldy", "rows_per_batch") + [("eps", _f32), ("dtype", _i32), ("x_f32", _i32), ("g_period", _i32),
@@ -146,6 +154,7 @@ _SYMBOLS = [
     ("pv_pool3d", C.c_int, [C.POINTER(Pool3dDesc), _p]),
     ("pv_ingest_ncdhw", C.c_int, [C.POINTER(LayoutDesc), _p]),
     ("pv_egress_ncdhw", C.c_int, [C.POINTER(LayoutDesc), _p]),
+    ("pv_resample_crop", C.c_int, [C.POINTER(ResampleDesc), _p]),
     ("pv_layernorm", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_affine_rows", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_softmax_rows", C.c_int, [C.POINTER(RowsDesc), _p]),
@@ -191,7 +200,7 @@ _SYMBOLS = [
     ("pv_forward_gather", C.c_int, [_p, _p, _p, C.POINTER(GatherSrc), C.c_int, _p, _p, _p]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SYMBOLS]
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 _lib = None
 

@@ -391,6 +391,28 @@ class Session:
         with torch.cuda.device(self.device):
             L.check(lib.pv_ingest_ncdhw(C.byref(d), self._stream()), "ingest")
 
+    def resample(self, d, ref, planar=None):
+        """Fill the input `ref` by pv_resample_crop (short-side scale + uniform crop fused into the ingest).  `d` is a
+        ResampleDesc whose source, geometry, views, item range, t_index and affine map the caller (transforms.DevicePacker)
+        has set; the destination is filled in here: the arena buffer in its own layout, or -- `planar`, a contiguous bf16
+        [B,C,T,H,W] tensor the caller keeps alive, for an input whose readers are all stems that read an NCDHW clip
+        themselves -- that tensor, which the stem is then pointed at."""
+        n = d.n_items if d.n_items else d.B * d.n_views
+        if (n, d.C, d.T, d.Ho, d.Wo) != (ref.B, ref.C, ref.T, ref.H, ref.W):
+            raise L.PvError("deploy form was converted for input %s, got %s" %
+                            ((ref.B, ref.C, ref.T, ref.H, ref.W), (n, d.C, d.T, d.Ho, d.Wo)))
+        if planar is not None:
+            d.dst, d.dst_layout, d.dst_dtype = planar.data_ptr(), L.DST_NCTHW, L.PV_BF16
+        else:
+            d.dst, d.dst_layout, d.dst_dtype = self.arena_t.data_ptr() + ref.off, L.DST_NDHWC, self.pv_dtype
+            d.c_p, d.ld, d.bs = (4 if ref.ld == 4 else pad8(ref.C)), ref.ld, ref.bs
+        with torch.cuda.device(self.device):
+            L.check(L.lib().pv_resample_crop(C.byref(d), self._stream()), "resample_crop")
+        if planar is not None:
+            self.ingest(planar, ref)      # repoints the stem; nothing is copied
+        else:
+            self._point_input(ref, 0)
+
     def alloc_boxes(self, count):
         """Persistent [count, 5] fp32 buffer for the box list of a detection head.  It lives beside the
         weights, NOT in the arena: it is filled before the replay starts and read near its end, and every

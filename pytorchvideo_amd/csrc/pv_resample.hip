@@ -1,0 +1,332 @@
+// pv_resample_crop: short_side_scale + uniform_crop (reference transforms/functional.py:92-131,302-347) fused with the
+// ingest's frame selection, Div255 + Normalize affine, dtype conversion and layout change.
+//
+// A bandwidth-bound gather.  One workgroup owns a strip of R output rows of one destination frame of one view:
+//   1. stage: the source span those rows need -- per output row the two source rows i0y, i1y (or, when the strip's source
+//      rows are fewer than 2R, as in upscaling, that contiguous run of rows once), columns [i0x(first), i1x(last)] -- is
+//      copied to LDS in the SOURCE dtype with aligned 16-byte global loads and 16-byte LDS writes.  A row of the span may
+//      start at any byte address (Ws = 340 gives 4-byte-aligned rows, an odd Ws none at all): the loads fetch the aligned
+//      16-byte granules that cover the span, and the LDS image of each row keeps the span's offset inside its first
+//      granule (`addr & 15`), so unaligned rows cost nothing extra.  A granule that covers a byte of the span lies in the
+//      same page as that byte, so the up to 15 bytes fetched in front of and behind the span are never used and never fault.
+//   2. gather: a thread owns G x-adjacent output pixels of one row (G = one 16-byte store per channel row for planar
+//      destinations, 2 = one 16-byte chunk for the 4-channel layout, 1 voxel for channels-last), takes its 4 taps per
+//      channel from LDS, blends in fp32, applies the affine map and stores 16-byte chunks.  Groups cut by the right edge
+//      (Wo not a multiple of G) or not 16-byte aligned in the destination (odd Wo) are stored element by element.
+//      (Eight pixels per thread for the 4-channel layout -- four 16-byte stores 64 bytes apart, as ingest_c4_vec8_kernel
+//      does -- measured up to 17 % slower here: DESIGN.md 4.6.)
+#include "pv_common.h"
+
+namespace {
+
+constexpr int kRsThreads = 256;
+constexpr int kRsMaxRows = 8;            // output rows per workgroup
+constexpr int kRsLdsBudget = 32 * 1024;  // staging bytes per workgroup: 4-5 workgroups per CU (160 KiB)
+constexpr int kRsLdsMax = 64 * 1024;
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+enum { RS_C4 = 0, RS_CL = 1, RS_PLANAR = 2 };
+
+struct RsLaunch {
+  float sy, sx;     // (float)Hs / (float)Hn, (float)Ws / (float)Wn: divided once, on the host
+  int32_t R;        // output rows per workgroup
+  int32_t pitch;    // LDS bytes per staged (row, plane): multiple of 16, >= 15 + widest span
+  int32_t src_T;
+  int32_t item0;
+};
+
+// Source coordinate of destination index d (the pinned formula: every operation rounded on its own, no contraction, so
+// that the host, which sizes the LDS span, and every thread agree on i0 / i1).
+__host__ __device__ __forceinline__ void rs_coord(float s, int d, int n_in, int& i0, int& i1, float& l1) {
+#pragma clang fp contract(off)
+  const float a = (float)d + 0.5f;
+  const float m = s * a;
+  float r = m - 0.5f;
+  r = r < 0.f ? 0.f : r;
+  i0 = (int)r;
+  i0 = i0 < n_in - 1 ? i0 : n_in - 1;   // r < n_in - 0.5 for every d inside the scaled frame; this keeps reads in bounds regardless
+  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
+  l1 = r - (float)i0;
+}
+
+template <typename S> __device__ __forceinline__ float rs_tap(const unsigned char* lds, int off);
+template <> __device__ __forceinline__ float rs_tap<unsigned char>(const unsigned char* lds, int off) { return (float)lds[off]; }
+template <> __device__ __forceinline__ float rs_tap<float>(const unsigned char* lds, int off) {
+  return *reinterpret_cast<const float*>(lds + off);
+}
+
+template <typename D> struct RsVec;   // one 16-byte store of G = 16 / sizeof(D) elements
+template <> struct RsVec<bf16_t> {
+  static constexpr int G = 8;
+  static __device__ __forceinline__ void store(bf16_t* p, const float* f) {
+    bf16x8 v;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (bf16_t)f[i];
+    *reinterpret_cast<bf16x8*>(p) = v;
+  }
+};
+template <> struct RsVec<float> {
+  static constexpr int G = 4;
+  static __device__ __forceinline__ void store(float* p, const float* f) {
+    *reinterpret_cast<f32x4*>(p) = f32x4{f[0], f[1], f[2], f[3]};
+  }
+};
+
+template <int FORM, typename D> struct RsGroup { static constexpr int G = FORM == RS_PLANAR ? RsVec<D>::G : (FORM == RS_C4 ? 2 : 1); };
+
+// S: source element (unsigned char | float); INTER: frame-interleaved [B,T,Hs,Ws,3] source; FORM / D: destination.
+template <typename S, bool INTER, int FORM, typename D>
+__global__ __launch_bounds__(kRsThreads) void resample_crop_kernel(const pv_resample_desc d, const RsLaunch g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char rs_lds[];
+  constexpr int G = RsGroup<FORM, D>::G;
+  constexpr int XB = INTER ? 3 : (int)sizeof(S);   // bytes from one source column to the next
+  const int tid = threadIdx.x;
+  const int R = g.R, pitch = g.pitch;
+  const int t = blockIdx.y;
+  const int zi = blockIdx.z;                       // destination item of this launch
+  const int item = g.item0 + zi;
+  const int b = item / d.n_views, view = item - b * d.n_views;
+  // selected, not indexed: a runtime index into the by-value descriptor would put it in scratch
+  const int yoff = view == 0 ? d.y_off[0] : (view == 1 ? d.y_off[1] : d.y_off[2]);
+  const int xoff = view == 0 ? d.x_off[0] : (view == 1 ? d.x_off[1] : d.x_off[2]);
+  const int row0 = blockIdx.x * R;
+  const int nrows = min(R, d.Ho - row0);
+  const int ts = d.t_index ? d.t_index[t] : t;
+  const int planes = INTER ? 1 : d.C;
+
+  int xs0, xs1, ybase, ylast, unused;
+  float lunused;
+  rs_coord(g.sx, xoff, d.Ws, xs0, unused, lunused);
+  rs_coord(g.sx, xoff + d.Wo - 1, d.Ws, unused, xs1, lunused);
+  rs_coord(g.sy, yoff + row0, d.Hs, ybase, unused, lunused);
+  rs_coord(g.sy, yoff + row0 + nrows - 1, d.Hs, unused, ylast, lunused);
+  const bool dense = ylast - ybase + 1 <= 2 * R;   // the strip's source rows fit the 2R slots as one contiguous run
+  const int nslots = dense ? ylast - ybase + 1 : 2 * nrows;
+  const int span_bytes = (xs1 - xs0 + 1) * XB;
+
+  // byte address of column xs0 of source row y of plane `pl` of the selected frame
+  const uintptr_t src0 = reinterpret_cast<uintptr_t>(d.src);
+  const long row_bytes = (long)d.Ws * XB;
+  const long frame_bytes = (long)d.Hs * row_bytes;
+  const long first = INTER ? ((long)b * g.src_T + ts) * frame_bytes + (long)xs0 * XB
+                           : ((long)b * d.C * g.src_T + ts) * frame_bytes + (long)xs0 * XB;
+  const long plane_bytes = INTER ? 0 : (long)g.src_T * frame_bytes;
+  auto row_addr = [&](int y, int pl) -> uintptr_t { return src0 + first + (long)pl * plane_bytes + (long)y * row_bytes; };
+
+  // ---- stage -------------------------------------------------------------------------------------------------
+  const int cpr = pitch >> 4;                      // 16-byte chunks per staged row
+  const int total = nslots * planes * cpr;
+  for (int base = tid; base < total; base += kRsThreads * 4) {
+    u32x4 val[4];
+    int off[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = base + u * kRsThreads;
+      off[u] = -1;
+      if (idx < total) {
+        const int sp = idx / cpr, ch = idx - sp * cpr;
+        const int slot = sp / planes, pl = sp - slot * planes;
+        int y = ybase + slot;
+        if (!dense) {
+          int i0, i1;
+          rs_coord(g.sy, yoff + row0 + (slot >> 1), d.Hs, i0, i1, lunused);
+          y = (slot & 1) ? i1 : i0;
+        }
+        const uintptr_t a = row_addr(y, pl);
+        if (ch * 16 < (int)(a & 15) + span_bytes) {
+          val[u] = *reinterpret_cast<const u32x4*>((a & ~(uintptr_t)15) + (uintptr_t)ch * 16);
+          off[u] = sp * pitch + ch * 16;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (off[u] >= 0) *reinterpret_cast<u32x4*>(rs_lds + off[u]) = val[u];
+  }
+  __syncthreads();
+
+  // ---- gather ------------------------------------------------------------------------------------------------
+  float sc[4], sh[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    sc[c] = (d.ch_scale && c < d.C) ? d.ch_scale[c] : 1.f;
+    sh[c] = (d.ch_scale && d.ch_shift && c < d.C) ? d.ch_shift[c] : 0.f;
+  }
+  const int gpr = (d.Wo + G - 1) / G;              // groups per output row
+  const int items = nrows * gpr;
+  for (int it = tid; it < items; it += kRsThreads) {
+    const int r = it / gpr, gx = it - r * gpr;
+    const int y = row0 + r;
+    int i0y, i1y;
+    float ly1;
+    rs_coord(g.sy, yoff + y, d.Hs, i0y, i1y, ly1);
+    const float ly0 = 1.f - ly1;
+    const int s0 = dense ? i0y - ybase : 2 * r, s1 = dense ? i1y - ybase : 2 * r + 1;
+    int ro0[4], ro1[4];                            // LDS byte offset of column xs0, channel c, in the two source rows
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (INTER) {
+        ro0[c] = s0 * pitch + (int)(row_addr(i0y, 0) & 15) + c;
+        ro1[c] = s1 * pitch + (int)(row_addr(i1y, 0) & 15) + c;
+      } else {
+        const int cc = c < d.C ? c : 0;
+        ro0[c] = (s0 * planes + cc) * pitch + (int)(row_addr(i0y, cc) & 15);
+        ro1[c] = (s1 * planes + cc) * pitch + (int)(row_addr(i1y, cc) & 15);
+      }
+    }
+    float out[4][G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      const int x = min(gx * G + j, d.Wo - 1);     // a group cut by the right edge recomputes the last column; not stored
+      int i0x, i1x;
+      float lx1;
+      rs_coord(g.sx, xoff + x, d.Ws, i0x, i1x, lx1);
+      const float lx0 = 1.f - lx1;
+      const int o0 = (i0x - xs0) * XB, o1 = (i1x - xs0) * XB;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (c < d.C) {
+          const float p00 = rs_tap<S>(rs_lds, ro0[c] + o0), p01 = rs_tap<S>(rs_lds, ro0[c] + o1);
+          const float p10 = rs_tap<S>(rs_lds, ro1[c] + o0), p11 = rs_tap<S>(rs_lds, ro1[c] + o1);
+          const float v = ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11);
+          out[c][j] = v * sc[c] + sh[c];
+        } else {
+          out[c][j] = 0.f;
+        }
+      }
+    }
+    const int x0 = gx * G;
+    const int nvalid = min(G, d.Wo - x0);
+    if constexpr (FORM == RS_PLANAR) {
+      const long HW = (long)d.Ho * d.Wo;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (c < d.C) {
+          D* p = static_cast<D*>(d.dst) + (((long)zi * d.C + c) * d.T + t) * HW + (long)y * d.Wo + x0;
+          if (nvalid == G && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+            RsVec<D>::store(p, out[c]);
+          } else {
+#pragma unroll
+            for (int j = 0; j < G; ++j)
+              if (j < nvalid) p[j] = (D)out[c][j];
+          }
+        }
+      }
+    } else if constexpr (FORM == RS_C4) {
+      bf16_t* p = static_cast<bf16_t*>(d.dst) + (long)zi * d.bs + ((((long)t * d.Ho + y) * d.Wo) + x0) * 4;
+      if (nvalid == G && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+#pragma unroll
+        for (int j = 0; j < G; j += 2) {           // two voxels = one 16-byte chunk of the first-layer layout
+          const bf16x8 o = {(bf16_t)out[0][j], (bf16_t)out[1][j], (bf16_t)out[2][j], (bf16_t)out[3][j],
+                            (bf16_t)out[0][j + 1], (bf16_t)out[1][j + 1], (bf16_t)out[2][j + 1], (bf16_t)out[3][j + 1]};
+          *reinterpret_cast<bf16x8*>(p + j * 4) = o;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+          if (j < nvalid) {
+            const bf16x4 o = {(bf16_t)out[0][j], (bf16_t)out[1][j], (bf16_t)out[2][j], (bf16_t)out[3][j]};
+            *reinterpret_cast<bf16x4*>(p + j * 4) = o;
+          }
+      }
+    } else {
+      D* p = static_cast<D*>(d.dst) + (long)zi * d.bs + ((((long)t * d.Ho + y) * d.Wo) + x0) * d.ld;
+      const float f[8] = {out[0][0], out[1][0], out[2][0], out[3][0], 0.f, 0.f, 0.f, 0.f};
+      Chunk8<D> o;
+      o.from_f32(f);
+      o.store(p);
+      o.zero();
+      for (int k = 8; k < d.c_p; k += 8) o.store(p + k);
+    }
+  }
+}
+
+template <typename S, bool INTER>
+int rs_launch(const pv_resample_desc& d, const RsLaunch& g, dim3 grid, size_t lds, hipStream_t s) {
+  const dim3 block(kRsThreads);
+  if (d.dst_layout == PV_DST_NCTHW) {
+    if (d.dst_dtype == PV_BF16) PV_LAUNCH((resample_crop_kernel<S, INTER, RS_PLANAR, bf16_t>), grid, block, lds, s, d, g);
+    else PV_LAUNCH((resample_crop_kernel<S, INTER, RS_PLANAR, float>), grid, block, lds, s, d, g);
+  } else if (d.c_p == 4) {
+    PV_LAUNCH((resample_crop_kernel<S, INTER, RS_C4, bf16_t>), grid, block, lds, s, d, g);
+  } else {
+    if (d.dst_dtype == PV_BF16) PV_LAUNCH((resample_crop_kernel<S, INTER, RS_CL, bf16_t>), grid, block, lds, s, d, g);
+    else PV_LAUNCH((resample_crop_kernel<S, INTER, RS_CL, float>), grid, block, lds, s, d, g);
+  }
+  PV_LAUNCH_CHECK();
+  return PV_OK;
+}
+
+}  // namespace
+
+extern "C" int pv_resample_crop(const pv_resample_desc* dp, pv_stream_t stream) {
+  if (!dp || !dp->src || !dp->dst) return PV_ERR_INVALID;
+  pv_resample_desc d = *dp;
+  if (d.B <= 0 || d.C <= 0 || d.T <= 0 || d.Hs <= 0 || d.Ws <= 0 || d.Hn <= 0 || d.Wn <= 0 || d.Ho <= 0 || d.Wo <= 0)
+    return PV_ERR_INVALID;
+  if (d.C > 4) return PV_ERR_INVALID;
+  if (d.n_views < 1 || d.n_views > 3) return PV_ERR_INVALID;
+  for (int v = 0; v < d.n_views; ++v)
+    if (d.y_off[v] < 0 || d.x_off[v] < 0 || (long)d.y_off[v] + d.Ho > d.Hn || (long)d.x_off[v] + d.Wo > d.Wn)
+      return PV_ERR_INVALID;
+  if (d.src_layout != PV_SRC_NCTHW && d.src_layout != PV_SRC_NTHWC) return PV_ERR_INVALID;
+  if (d.src_layout == PV_SRC_NTHWC && (d.src_dtype != PV_U8 || d.C != 3)) return PV_ERR_INVALID;
+  if (d.t_index && d.src_T <= 0) return PV_ERR_INVALID;
+  const long all_items = (long)d.B * d.n_views;
+  if (d.n_items == 0 && d.item0 == 0) d.n_items = (int32_t)all_items;
+  if (d.item0 < 0 || d.n_items <= 0 || (long)d.item0 + d.n_items > all_items) return PV_ERR_INVALID;
+  if (d.T > 65535 || d.n_items > 65535) return PV_ERR_INVALID;   // grid.y / grid.z
+  // the dtype / layout matrix
+  if (d.src_dtype != PV_U8 && d.src_dtype != PV_F32) return PV_ERR_UNSUPPORTED;
+  if (d.dst_dtype != PV_BF16 && d.dst_dtype != PV_F32) return PV_ERR_UNSUPPORTED;
+  const uintptr_t dst = reinterpret_cast<uintptr_t>(d.dst);
+  if (d.dst_layout == PV_DST_NDHWC) {
+    if (d.c_p == 4 && d.ld == 4) {
+      if (d.dst_dtype != PV_BF16) return PV_ERR_UNSUPPORTED;
+      if (d.bs % 4 || dst % 8) return PV_ERR_INVALID;
+    } else if (d.c_p >= 8 && d.c_p % 8 == 0) {
+      if (d.ld % 8 || d.ld < d.c_p || d.bs % 8 || dst % 16) return PV_ERR_INVALID;
+    } else {
+      return PV_ERR_UNSUPPORTED;
+    }
+    if (d.bs < (int64_t)d.T * d.Ho * d.Wo * d.ld) return PV_ERR_INVALID;
+  } else if (d.dst_layout == PV_DST_NCTHW) {
+    if (dst % (d.dst_dtype == PV_BF16 ? 2 : 4)) return PV_ERR_INVALID;
+  } else {
+    return PV_ERR_UNSUPPORTED;
+  }
+  if (d.src_dtype == PV_F32 && reinterpret_cast<uintptr_t>(d.src) % 4) return PV_ERR_INVALID;
+
+  RsLaunch g;
+  g.sy = (float)d.Hs / (float)d.Hn;
+  g.sx = (float)d.Ws / (float)d.Wn;
+  g.src_T = d.t_index ? d.src_T : d.T;
+  g.item0 = d.item0;
+  // the widest column span of any view sizes the staged row
+  const bool inter = d.src_layout == PV_SRC_NTHWC;
+  const int xb = inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1);
+  int span = 0;
+  for (int v = 0; v < d.n_views; ++v) {
+    int a, b, u;
+    float l;
+    rs_coord(g.sx, d.x_off[v], d.Ws, a, u, l);
+    rs_coord(g.sx, d.x_off[v] + d.Wo - 1, d.Ws, u, b, l);
+    span = b - a + 1 > span ? b - a + 1 : span;
+  }
+  g.pitch = pv_round_up(span * xb + 15, 16);
+  const int planes = inter ? 1 : d.C;
+  const long per_row = 2L * planes * g.pitch;      // two source rows per output row
+  long R = kRsLdsBudget / per_row;
+  R = R > kRsMaxRows ? kRsMaxRows : R;
+  R = R > d.Ho ? d.Ho : R;
+  if (R < 1) R = 1;
+  if (R * per_row > kRsLdsMax) return PV_ERR_UNSUPPORTED;
+  g.R = (int)R;
+  const size_t lds = (size_t)(R * per_row);
+  const dim3 grid((unsigned)pv_ceil_div(d.Ho, R), (unsigned)d.T, (unsigned)d.n_items);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (inter) return rs_launch<unsigned char, true>(d, g, grid, lds, s);
+  if (d.src_dtype == PV_U8) return rs_launch<unsigned char, false>(d, g, grid, lds, s);
+  return rs_launch<float, false>(d, g, grid, lds, s);
+}

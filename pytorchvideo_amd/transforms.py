@@ -10,8 +10,15 @@
   or is uploaded once, as the fast-rate clip only -- is frame-subsampled per pathway, scaled,
   normalised, converted to bf16 and laid out channels-last in ONE pass per pathway.  The reference
   does this as index_select + div + sub + div on the host followed by an upload of every pathway.
+
+The spatial half of the eval protocol -- `short_side_scale` then `uniform_crop` (functional.py:92-131,302-347;
+transforms.py:100-121,153-175), with their box variants -- has the same two forms: host mirrors, and
+`DevicePacker(..., short_side=, crop_size=, spatial_idx=)` / `device_scale_crop`, which run it inside the same pass
+(`pv_resample_crop`): the clip may then have any frame size, and one launch per pathway turns it into the crops.
 """
-from typing import Sequence, Tuple
+import copy
+import math
+from typing import Dict, Sequence, Tuple
 
 import torch
 
@@ -62,7 +69,200 @@ class Normalize(torch.nn.Module):
         return (x - mean) / std
 
 
+# --------------------------------------------------------------------------- spatial host mirrors
+def scaled_size(h: int, w: int, size: int) -> Tuple[int, int]:
+    """The (new_h, new_w) short_side_scale resizes an h x w frame to (functional.py:121-126: the long side is floored)."""
+    if w < h:
+        return int(math.floor((float(h) / w) * size)), size
+    return size, int(math.floor((float(w) / h) * size))
+
+
+def crop_offsets(new_h: int, new_w: int, size: int, spatial_idx: int) -> Tuple[int, int]:
+    """The (y, x) origin of uniform_crop's window (functional.py:311-323: centred with ceil; index 0 / 2 move it to the
+    start / end of the LONGER side)."""
+    assert spatial_idx in [0, 1, 2]
+    y = int(math.ceil((new_h - size) / 2))
+    x = int(math.ceil((new_w - size) / 2))
+    if new_h > new_w:
+        if spatial_idx == 0:
+            y = 0
+        elif spatial_idx == 2:
+            y = new_h - size
+    else:
+        if spatial_idx == 0:
+            x = 0
+        elif spatial_idx == 2:
+            x = new_w - size
+    return y, x
+
+
+def short_side_scale(x: torch.Tensor, size: int, interpolation: str = "bilinear", backend: str = "pytorch") -> torch.Tensor:
+    """functional.py:92-131: scale the shorter side of a (C,T,H,W) float32 clip to `size`, keeping the aspect ratio."""
+    assert len(x.shape) == 4
+    assert x.dtype == torch.float32
+    assert backend in ("pytorch", "opencv")
+    if backend != "pytorch":
+        raise NotImplementedError("%s backend not supported." % backend)
+    _, _, h, w = x.shape
+    return torch.nn.functional.interpolate(x, size=scaled_size(h, w, size), mode=interpolation, align_corners=False)
+
+
+def uniform_crop(images: torch.Tensor, size: int, spatial_idx: int) -> torch.Tensor:
+    """functional.py:326-347: the left / centre / right (top / centre / bottom for a portrait clip) size x size crop."""
+    y, x = crop_offsets(images.shape[2], images.shape[3], size, spatial_idx)
+    return images[:, :, y: y + size, x: x + size]
+
+
+def clip_boxes_to_image(boxes: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    """functional.py:407-426: clip [N,4] boxes (x1, y1, x2, y2) to a height x width image."""
+    clipped = copy.deepcopy(boxes)
+    clipped[:, [0, 2]] = torch.clamp(boxes[:, [0, 2]], 0.0, width - 1.0)
+    clipped[:, [1, 3]] = torch.clamp(boxes[:, [1, 3]], 0.0, height - 1.0)
+    return clipped
+
+
+def crop_boxes(boxes: torch.Tensor, x_offset: int, y_offset: int) -> torch.Tensor:
+    """functional.py:429-446: boxes in the coordinates of a crop whose origin is (x_offset, y_offset)."""
+    cropped = copy.deepcopy(boxes)
+    cropped[:, [0, 2]] = boxes[:, [0, 2]] - x_offset
+    cropped[:, [1, 3]] = boxes[:, [1, 3]] - y_offset
+    return cropped
+
+
+def short_side_scale_with_boxes(images: torch.Tensor, boxes: torch.Tensor, size: int, interpolation: str = "bilinear",
+                                backend: str = "pytorch") -> Tuple[torch.Tensor, torch.Tensor]:
+    """functional.py:195-231: short_side_scale, and the boxes scaled by the ratio of the LONGER side (in place, as there)."""
+    _, _, h, w = images.shape
+    images = short_side_scale(images, size, interpolation, backend)
+    _, _, new_h, new_w = images.shape
+    if w < h:
+        boxes *= float(new_h) / h
+    else:
+        boxes *= float(new_w) / w
+    return images, boxes
+
+
+def uniform_crop_with_boxes(images: torch.Tensor, size: int, spatial_idx: int,
+                            boxes: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """functional.py:350-378: uniform_crop, and the boxes moved into the crop and clipped to it."""
+    y, x = crop_offsets(images.shape[2], images.shape[3], size, spatial_idx)
+    cropped = images[:, :, y: y + size, x: x + size]
+    return cropped, clip_boxes_to_image(crop_boxes(boxes, x, y), cropped.shape[-2], cropped.shape[-1])
+
+
+class ShortSideScale(torch.nn.Module):
+    """transforms/transforms.py:100-121."""
+
+    def __init__(self, size: int, interpolation: str = "bilinear", backend: str = "pytorch"):
+        super().__init__()
+        self._size, self._interpolation, self._backend = size, interpolation, backend
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return short_side_scale(x, self._size, self._interpolation, self._backend)
+
+
+class UniformCropVideo(torch.nn.Module):
+    """transforms/transforms.py:153-175: uniform_crop of x[video_key] with the spatial index x[aug_index_key]."""
+
+    def __init__(self, size: int, video_key: str = "video", aug_index_key: str = "aug_index"):
+        super().__init__()
+        self._size, self._video_key, self._aug_index_key = size, video_key, aug_index_key
+
+    def __call__(self, x: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        x[self._video_key] = uniform_crop(x[self._video_key], self._size, x[self._aug_index_key])
+        return x
+
+
 # --------------------------------------------------------------------------- fused device path
+def _affine(mean, std, div255, channels, device):
+    """(ch_scale, ch_shift) of Div255 + Normalize as fp32 device tensors, or (None, None)."""
+    if mean is None and std is None and not div255:
+        return None, None
+    mean_t = torch.tensor(mean if mean is not None else [0.0] * channels, dtype=torch.float64)
+    std_t = torch.tensor(std if std is not None else [1.0] * channels, dtype=torch.float64)
+    if mean_t.numel() != channels or std_t.numel() != channels:
+        raise ValueError("mean/std must have %d entries" % channels)
+    k = 255.0 if div255 else 1.0
+    return (1.0 / (k * std_t)).float().to(device), (-mean_t / std_t).float().to(device)
+
+
+def _views(spatial_idx):
+    views = (spatial_idx,) if isinstance(spatial_idx, int) else tuple(spatial_idx)
+    if not 1 <= len(views) <= 3 or any(v not in (0, 1, 2) for v in views):
+        raise ValueError("spatial_idx is 0, 1 or 2, or a tuple of up to three of them; got %r" % (spatial_idx,))
+    return views
+
+
+def _source_geometry(clip, src_layout):
+    """(B, C, T, Hs, Ws) of a clip in either source layout."""
+    if clip.dim() != 5:
+        raise RuntimeError("expected a 5-d %s clip, got %s" % (src_layout, tuple(clip.shape),))
+    if src_layout == "NCTHW":
+        return tuple(clip.shape)
+    b, t, h, w, c = clip.shape
+    return b, c, t, h, w
+
+
+def _resample_desc(clip, src_layout, short_side, crop_size, views):
+    """A ResampleDesc with the source and the geometry of short_side_scale + uniform_crop filled in (the destination, the
+    frame selection and the affine map are the caller's).  `clip` is contiguous, uint8 or fp32, on the device."""
+    from . import _lib as L
+    b, c, t, hs, ws = _source_geometry(clip, src_layout)
+    hn, wn = scaled_size(hs, ws, short_side)
+    if crop_size > hn or crop_size > wn:
+        raise RuntimeError("a %d crop does not fit the %d x %d frame scaled to %d x %d" % (crop_size, hs, ws, hn, wn))
+    d = L.ResampleDesc()
+    d.src = clip.data_ptr()
+    d.B, d.C, d.T, d.src_T, d.Hs, d.Ws = b, c, t, t, hs, ws
+    d.src_dtype = L.PV_U8 if clip.dtype == torch.uint8 else L.PV_F32
+    d.src_layout = L.SRC_NCTHW if src_layout == "NCTHW" else L.SRC_NTHWC
+    d.Hn, d.Wn, d.Ho, d.Wo, d.n_views = hn, wn, crop_size, crop_size, len(views)
+    for i, v in enumerate(views):
+        d.y_off[i], d.x_off[i] = crop_offsets(hn, wn, crop_size, v)
+    return d
+
+
+def _device_source(clip, device):
+    clip = clip.to(device, non_blocking=True)
+    if clip.dtype not in (torch.uint8, torch.float32):
+        clip = clip.float()
+    return clip.contiguous()
+
+
+@torch.no_grad()
+def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std=None, div255=False, num_frames=None,
+                      dtype=torch.bfloat16, src_layout="NCTHW"):
+    """uniform_crop(short_side_scale(Normalize(Div255(uniform_temporal_subsample(clip, num_frames))))) for every view of
+    `spatial_idx` in one launch of `pv_resample_crop`: a planar [B * n_views, C, T, crop, crop] tensor of `dtype` (bf16 or
+    fp32) on the GPU, item b * n_views + v being view v of clip b.  `clip` is [B,C,T,H,W] ("NCTHW"; uint8 or float) or the
+    decoder's [B,T,H,W,3] uint8 ("NTHWC")."""
+    import ctypes as C
+    from . import _lib as L
+    if src_layout not in ("NCTHW", "NTHWC"):
+        raise ValueError("src_layout is 'NCTHW' or 'NTHWC'")
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("dtype is torch.bfloat16 or torch.float32")
+    views = _views(spatial_idx)
+    _source_geometry(clip, src_layout)
+    device = clip.device if clip.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    clip = _device_source(clip, device)
+    d = _resample_desc(clip, src_layout, short_side, crop_size, views)
+    scale, shift = _affine(mean, std, div255, d.C, device)
+    index = None
+    if num_frames is not None and num_frames != d.src_T:
+        index = temporal_indices(d.src_T, num_frames).to(torch.int32).to(device)
+        d.T, d.t_index = num_frames, index.data_ptr()
+    if scale is not None:
+        d.ch_scale, d.ch_shift = scale.data_ptr(), shift.data_ptr()
+    out = torch.empty((d.B * d.n_views, d.C, d.T, crop_size, crop_size), dtype=dtype, device=device)
+    d.dst, d.dst_layout = out.data_ptr(), L.DST_NCTHW
+    d.dst_dtype = L.PV_BF16 if dtype == torch.bfloat16 else L.PV_F32
+    with torch.cuda.device(device):
+        L.check(L.lib().pv_resample_crop(C.byref(d), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                "resample_crop")
+    return out
+
+
 class DevicePacker:
     """`DevicePacker(deployed, mean, std, div255=True, frame_ratios=(4, 1))(clip)` = the deploy form
     applied to `[Normalize(Div255(subsample_r(clip))) for r in frame_ratios]`, with everything before
@@ -71,15 +271,33 @@ class DevicePacker:
     `deployed` is what `convert_to_deployable_form` returned for a whole model (one graph replay per
     forward); `frame_ratios` must be given for multi-pathway models in the order of the model's
     input list (SlowFast: slow = T/4 frames, fast = T frames), and left None for single-input models.
-    A deployed detection model (DetectionBBoxNetwork) is called as `packer(clip, bboxes)`."""
+    A deployed detection model (DetectionBBoxNetwork) is called as `packer(clip, bboxes)`.
 
-    def __init__(self, deployed, mean=None, std=None, div255=False, frame_ratios=None):
+    With `short_side` and `crop_size` the packer also does `uniform_crop(short_side_scale(., short_side), crop_size, v)`
+    for every v of `spatial_idx` (an int, or a tuple of up to three: the three-crop protocol) in the same pass
+    (`pv_resample_crop`, one launch per pathway): `clip` may have any frame size and be [B,C,T,H,W] (`src_layout="NCTHW"`)
+    or the decoder's uint8 [B,T,H,W,3] ("NTHWC"); the deploy form's batch is B * n_views, item b * n_views + v being view v
+    of clip b (`VideoEnsembler`'s video_index for it is `repeat_interleave(n_views)`), and `crop_size` is the model's
+    H == W.  The boxes of a detection model are given in the pixels of the SOURCE frame and follow the clip through
+    `short_side_scale_with_boxes` and `uniform_crop_with_boxes` on the host (one view only)."""
+
+    def __init__(self, deployed, mean=None, std=None, div255=False, frame_ratios=None, short_side=None, crop_size=None,
+                 spatial_idx=1, src_layout="NCTHW"):
         self.subs = None
+        if (short_side is None) != (crop_size is None):
+            raise ValueError("short_side and crop_size are given together")
+        if src_layout not in ("NCTHW", "NTHWC"):
+            raise ValueError("src_layout is 'NCTHW' or 'NTHWC'")
+        self.short_side, self.crop_size, self.src_layout = short_side, crop_size, src_layout
+        self.views = _views(spatial_idx) if short_side is not None else (1,)
+        if short_side is None and src_layout != "NCTHW":
+            raise ValueError("a frame-interleaved clip is read by the resampling path only: give short_side and crop_size")
         if hasattr(deployed, "parts") and hasattr(deployed, "_pv_launch"):
             # split-batch deploy form (convert_to_deployable_form(..., streams=k)): one packer per sub-batch fills that
             # sub-plan's input buffers, then ONE launch of the joint graph
             self.model = deployed
-            self.subs = [DevicePacker(p, mean, std, div255, frame_ratios) for p in deployed.parts]
+            self.subs = [DevicePacker(p, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout)
+                         for p in deployed.parts]
             self.sess, self.refs = self.subs[0].sess, self.subs[0].refs
             self.frame_ratios = self.subs[0].frame_ratios
             return
@@ -96,18 +314,16 @@ class DevicePacker:
         if len(frame_ratios) != len(self.refs):
             raise ValueError("%d frame ratios for %d input pathways" % (len(frame_ratios), len(self.refs)))
         self.frame_ratios = tuple(int(r) for r in frame_ratios)
-        dev = self.sess.device
-        channels = self.refs[0].C
-        self.scale = self.shift = None
-        if mean is not None or std is not None or div255:
-            mean_t = torch.tensor(mean if mean is not None else [0.0] * channels, dtype=torch.float64)
-            std_t = torch.tensor(std if std is not None else [1.0] * channels, dtype=torch.float64)
-            if mean_t.numel() != channels or std_t.numel() != channels:
-                raise ValueError("mean/std must have %d entries" % channels)
-            k = 255.0 if div255 else 1.0
-            self.scale = (1.0 / (k * std_t)).float().to(dev)
-            self.shift = (-mean_t / std_t).float().to(dev)
+        if crop_size is not None:
+            for ref in self.refs:
+                if (ref.H, ref.W) != (crop_size, crop_size):
+                    raise ValueError("crop_size %d is not the %d x %d input the deploy form was converted for"
+                                     % (crop_size, ref.H, ref.W))
+            if len(self.views) > 1 and getattr(deployed, "_pv_load_boxes", None) is not None:
+                raise ValueError("a detection model takes one view: its boxes belong to one crop")
+        self.scale, self.shift = _affine(mean, std, div255, self.refs[0].C, self.sess.device)
         self._index = {}
+        self._planar = {}
 
     def _t_index(self, t_src, ref):
         key = (t_src, ref.T)
@@ -117,6 +333,31 @@ class DevicePacker:
                 else idx.to(torch.int32).to(self.sess.device)
         return self._index[key]
 
+    def _check_source(self, clip, want):
+        """Everything that can be wrong with a clip for the resampling path, BEFORE any launch."""
+        b, c, t, hs, ws = _source_geometry(clip, self.src_layout)
+        if b * len(self.views) != want:
+            raise RuntimeError("deploy form was converted for a batch of %d = clips x views, got %d clips x %d views"
+                               % (want, b, len(self.views)))
+        hn, wn = scaled_size(hs, ws, self.short_side)
+        if self.crop_size > hn or self.crop_size > wn:
+            raise RuntimeError("a %d crop does not fit the %d x %d frame scaled to %d x %d" % (self.crop_size, hs, ws, hn, wn))
+        if self.src_layout == "NTHWC" and (c != 3 or clip.dtype != torch.uint8):
+            raise RuntimeError("a frame-interleaved clip is uint8 [B,T,H,W,3], got %s %s" % (clip.dtype, tuple(clip.shape)))
+        for ratio, ref in zip(self.frame_ratios, self.subs[0].refs if self.subs is not None else self.refs):
+            if c != ref.C or t // ratio != ref.T:
+                raise RuntimeError("pathway with frame ratio %d expects %d channels x %d frames, the clip gives %d x %d"
+                                   % (ratio, ref.C, ref.T, c, t // ratio))
+        return hs, ws, hn, wn
+
+    def _boxes_to_crop(self, bboxes, hs, ws, hn, wn):
+        """[R,5] boxes (batch index, x1, y1, x2, y2 in source pixels) -> the same in the pixels of the crop."""
+        out = bboxes.detach().to("cpu", torch.float32).clone()
+        out[:, 1:5] *= float(hn) / hs if ws < hs else float(wn) / ws        # short_side_scale_with_boxes
+        y, x = crop_offsets(hn, wn, self.crop_size, self.views[0])
+        out[:, 1:5] = clip_boxes_to_image(crop_boxes(out[:, 1:5], x, y), self.crop_size, self.crop_size)
+        return out
+
     @torch.no_grad()
     def __call__(self, clip, bboxes=None):
         load_boxes = getattr(self.model, "_pv_load_boxes", None)
@@ -124,22 +365,34 @@ class DevicePacker:
             raise RuntimeError("bboxes are given to a detection model and only to a detection model")
         if clip.dim() != 5:
             raise RuntimeError("expected a [B,C,T,H,W] clip, got %s" % (tuple(clip.shape),))
+        resample = self.short_side is not None
         if self.subs is not None:
             # validate BEFORE any ingest: a short batch must not reach the sub-plans' input buffers
             want = sum(self.model._splits)
-            if clip.shape[0] != want:
+            if resample:
+                self._check_source(clip, want)
+            elif clip.shape[0] != want:
                 raise RuntimeError("deploy form was converted for a batch of %d, got %d" % (want, clip.shape[0]))
             if bboxes is not None:
                 raise RuntimeError("bboxes cannot be given to a split-batch deploy form (detection models are converted as one plan)")
-            clip = clip.to(self.sess.device, non_blocking=True)
+            clip = _device_source(clip, self.sess.device) if resample else clip.to(self.sess.device, non_blocking=True)
             lo = 0
             for sub, b in zip(self.subs, self.model._splits):
-                sub._fill(clip[lo:lo + b])
+                if resample:
+                    sub._fill_resampled(clip, lo, b)      # destination items [lo, lo + b) of the clips x views sequence
+                else:
+                    sub._fill(clip[lo:lo + b])
                 lo += b
             self.model._pv_launch()
             return self.model._pv_result()
-        clip = clip.to(self.sess.device, non_blocking=True)
-        self._fill(clip)
+        if resample:
+            hs, ws, hn, wn = self._check_source(clip, self.refs[0].B)
+            if bboxes is not None:
+                bboxes = self._boxes_to_crop(bboxes, hs, ws, hn, wn)
+            self._fill_resampled(_device_source(clip, self.sess.device), 0, self.refs[0].B)
+        else:
+            clip = clip.to(self.sess.device, non_blocking=True)
+            self._fill(clip)
         if load_boxes is not None:
             load_boxes(bboxes)
         self.sess.launch(use_graph=self.model._pv_use_graph)
@@ -151,3 +404,24 @@ class DevicePacker:
             if t_src // ratio != ref.T:
                 raise RuntimeError("pathway with frame ratio %d expects %d frames, the clip gives %d" % (ratio, ref.T, t_src // ratio))
             self.sess.ingest(clip, ref, t_index=self._t_index(t_src, ref), ch_scale=self.scale, ch_shift=self.shift)
+
+    def _fill_resampled(self, clip, item0, n_items):
+        """One pv_resample_crop launch per pathway: items [item0, item0 + n_items) of the clips x views sequence."""
+        from . import _lib as L
+        self._src = clip                                   # alive until the launch has run
+        for i, ref in enumerate(self.refs):
+            d = _resample_desc(clip, self.src_layout, self.short_side, self.crop_size, self.views)
+            d.item0, d.n_items = item0, n_items
+            index = self._t_index(d.src_T, ref)
+            if index is not None:
+                d.T, d.t_index = ref.T, index.data_ptr()
+            if self.scale is not None:
+                d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
+            planar = None
+            if ref.src_slot is not None and ref.c4_readers == 0 and self.sess.pv_dtype == L.PV_BF16:
+                # every reader is a stem that reads an NCDHW clip itself: resample into a clip of our own and point it there
+                if i not in self._planar:
+                    self._planar[i] = torch.empty((ref.B, ref.C, ref.T, ref.H, ref.W), dtype=torch.bfloat16,
+                                                  device=self.sess.device)
+                planar = self._planar[i]
+            self.sess.resample(d, ref, planar=planar)
