@@ -102,6 +102,12 @@ def test_north_star_bench_batch_with_bench_streams_every_row(workload):
           "oracle %.2e | top-1 %d/%d" % (workload, r["batch"], r["streams"], r["bf16_vs_fp32_oracle"], r["bf16_rows_worst_fp32"],
                                          r["storage_floor"], r["bf16_vs_emulated_oracle"], r["top1_agree"], r["batch"]))
     _dump(r, "north star: bench batch, bench streams, every row")
+    assert_every_row_of_a_bench_form(r, workload)
+
+
+def assert_every_row_of_a_bench_form(r, workload):
+    """The assertions of the bench-batch case on a `parity_full.case` record (also used, with the same constants, by the
+    off-bench batches of tests/test_gpu_batch_routing.py): `row_detail` holds the rows the oracle was evaluated for."""
     _well_scaled(r)
     assert r["bf16_replay_equal"]
     # The batch-wide number: 1e-2, or -- where bf16 STORAGE alone (CPU, exact arithmetic, no kernel) already costs that much --
