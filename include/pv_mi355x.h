@@ -364,11 +364,47 @@ typedef struct pv_resample_desc {
   int32_t dst_layout, dst_dtype;
   int32_t c_p, ld;            /* PV_DST_NDHWC only, as in pv_layout_desc                                         */
   int64_t bs;                 /* PV_DST_NDHWC only: batch stride in elements                                     */
-  const int32_t* t_index;     /* [T] source frame of every destination frame, or NULL (identity)                 */
+  const int32_t* t_index;     /* [T] source frame of every destination frame, or NULL (identity); an entry       */
+                              /* outside [0, src_T-1] is clamped into it before an address is formed             */
   const float* ch_scale;      /* [C] or NULL                                                                     */
   const float* ch_shift;      /* [C] or NULL                                                                     */
 } pv_resample_desc;
 int pv_resample_crop(const pv_resample_desc* d, pv_stream_t stream);
+
+/* ---- whole-video ingest: clip sampling fused into pv_resample_crop ---------------------------
+ * What LabeledVideoDataset does to every video before the transforms above: a clip sampler (data/clip_sampling.py)
+ * cuts it into clips, FrameVideo.get_clip (data/frame_video.py:149-200) maps each clip to a frame range and
+ * UniformTemporalSubsample picks T frames of it.  All of that is a table of frame numbers, so pv_video_views reads
+ * ONE decoded video through a table instead of B materialised clips through one shared index:
+ * Source:       PV_SRC_NCTHW  planar [C,N,Hs,Ws], PV_U8 or PV_F32;  PV_SRC_NTHWC  [N,Hs,Ws,3], PV_U8
+ * Frames:       t_index[clip * t_stride + t] (int32, device) is the video frame of destination frame t of clip `clip`;
+ *               rows may overlap and repeat frames.  Every entry is CLAMPED into [0, N-1] before an address is formed,
+ *               so no table can make the kernel read outside the video; reporting a bad table is the caller's job.
+ * Destination item clip * n_views + v is view v of clip `clip`; item0 / n_items select ANY range of that sequence
+ * (n_items == 0 with item0 == 0: all n_clips * n_views), written to positions 0 .. n_items-1 of dst.
+ * Geometry, interpolation, affine map and the destination forms are pv_resample_crop's (the same kernel): a launch writes
+ * bit for bit what pv_resample_crop writes for the clips materialised by index_select.
+ * PV_ERR_INVALID: null src / dst / t_index, n_clips <= 0, T <= 0, N <= 0, t_stride < T, and whatever pv_resample_crop
+ * rejects.  PV_ERR_UNSUPPORTED as there.
+ */
+typedef struct pv_video_views_desc {
+  const void* src; void* dst;
+  const int32_t* t_index;     /* [n_clips][t_stride], the first T of every row used                              */
+  const float* ch_scale;      /* [C] or NULL                                                                     */
+  const float* ch_shift;      /* [C] or NULL                                                                     */
+  int64_t bs;                 /* PV_DST_NDHWC only: batch stride in elements                                     */
+  int32_t n_clips, C, T;      /* table rows, channels (<= 4), DESTINATION frames per clip                        */
+  int32_t N, t_stride;        /* frames in the video; table row stride (>= T)                                    */
+  int32_t Hs, Ws;
+  int32_t src_dtype, src_layout;
+  int32_t Hn, Wn, Ho, Wo;     /* as in pv_resample_desc                                                          */
+  int32_t n_views;            /* 1..3                                                                            */
+  int32_t y_off[3], x_off[3];
+  int32_t item0, n_items;
+  int32_t dst_layout, dst_dtype;
+  int32_t c_p, ld;            /* PV_DST_NDHWC only                                                               */
+} pv_video_views_desc;
+int pv_video_views(const pv_video_views_desc* d, pv_stream_t stream);
 
 /* ---- row ops on (rows, C) matrices -------------------------------------------------
  * pv_layernorm: nn.LayerNorm(eps) over C (models/vision_transformers.py:333-335,

@@ -79,6 +79,11 @@ ResampleDesc = _struct("ResampleDesc", [
     + [("y_off", _i32 * 3), ("x_off", _i32 * 3)] + _ints("item0", "n_items", "dst_layout", "dst_dtype", "c_p", "ld")
     + [("bs", _i64), ("t_index", _p), ("ch_scale", _p), ("ch_shift", _p)])
 
+VideoViewsDesc = _struct("VideoViewsDesc", [
+    ("src", _p), ("dst", _p), ("t_index", _p), ("ch_scale", _p), ("ch_shift", _p), ("bs", _i64)]
+    + _ints("n_clips", "C", "T", "N", "t_stride", "Hs", "Ws", "src_dtype", "src_layout", "Hn", "Wn", "Ho", "Wo", "n_views")
+    + [("y_off", _i32 * 3), ("x_off", _i32 * 3)] + _ints("item0", "n_items", "dst_layout", "dst_dtype", "c_p", "ld"))
+
 RowsDesc = _struct("RowsDesc", [
     ("x", _p), ("y", _p), ("gamma", _p), ("beta", _p), ("rows", _i64)]
     + _ints("C", "ldx", "ldy", "rows_per_batch") + [("eps", _f32), ("dtype", _i32), ("x_f32", _i32), ("g_period", _i32),
@@ -155,6 +160,7 @@ _SYMBOLS = [
     ("pv_ingest_ncdhw", C.c_int, [C.POINTER(LayoutDesc), _p]),
     ("pv_egress_ncdhw", C.c_int, [C.POINTER(LayoutDesc), _p]),
     ("pv_resample_crop", C.c_int, [C.POINTER(ResampleDesc), _p]),
+    ("pv_video_views", C.c_int, [C.POINTER(VideoViewsDesc), _p]),
     ("pv_layernorm", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_affine_rows", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_softmax_rows", C.c_int, [C.POINTER(RowsDesc), _p]),
@@ -200,7 +206,7 @@ _SYMBOLS = [
     ("pv_forward_gather", C.c_int, [_p, _p, _p, C.POINTER(GatherSrc), C.c_int, _p, _p, _p]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SYMBOLS]
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 _lib = None
 

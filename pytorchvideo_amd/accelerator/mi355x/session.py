@@ -401,13 +401,40 @@ class Session:
         if (n, d.C, d.T, d.Ho, d.Wo) != (ref.B, ref.C, ref.T, ref.H, ref.W):
             raise L.PvError("deploy form was converted for input %s, got %s" %
                             ((ref.B, ref.C, ref.T, ref.H, ref.W), (n, d.C, d.T, d.Ho, d.Wo)))
+        self._resample_into(d, ref, planar, "pv_resample_crop")
+
+    def video_views(self, d, ref, planar=None):
+        """Fill the first d.n_items items of the input `ref` by pv_video_views (clip sampling fused into the resampling
+        ingest: `d` is a VideoViewsDesc prepared by transforms.DevicePacker.fill_video) and ZERO the remaining
+        ref.B - d.n_items items -- a ragged last chunk of a video -- so that no result depends on an earlier forward.
+        d.n_items == 0 only zeroes.  Destination and `planar` as in `resample`."""
+        n = d.n_items
+        if not 0 <= n <= ref.B or (d.C, d.T, d.Ho, d.Wo) != (ref.C, ref.T, ref.H, ref.W):
+            raise L.PvError("deploy form was converted for input %s, got %d items of %s" %
+                            ((ref.B, ref.C, ref.T, ref.H, ref.W), n, (d.C, d.T, d.Ho, d.Wo)))
+        if n < ref.B:
+            with torch.cuda.device(self.device):
+                if planar is not None:
+                    planar[n:].zero_()
+                else:
+                    self.arena_t[ref.off + n * ref.bs * ref.itemsize: ref.off + ref.B * ref.bs * ref.itemsize].zero_()
+        if n:
+            self._resample_into(d, ref, planar, "pv_video_views")
+        elif planar is not None:
+            self.ingest(planar, ref)      # nothing to write: only point the stem at the zeroed clip
+        else:
+            self._point_input(ref, 0)
+
+    def _resample_into(self, d, ref, planar, entry):
+        """Set the destination of the resampling descriptor `d` -- `planar`, or the arena buffer `ref` in its own layout --
+        run `entry` on it and point the ops that read `ref` at what was written."""
         if planar is not None:
             d.dst, d.dst_layout, d.dst_dtype = planar.data_ptr(), L.DST_NCTHW, L.PV_BF16
         else:
             d.dst, d.dst_layout, d.dst_dtype = self.arena_t.data_ptr() + ref.off, L.DST_NDHWC, self.pv_dtype
             d.c_p, d.ld, d.bs = (4 if ref.ld == 4 else pad8(ref.C)), ref.ld, ref.bs
         with torch.cuda.device(self.device):
-            L.check(L.lib().pv_resample_crop(C.byref(d), self._stream()), "resample_crop")
+            L.check(getattr(L.lib(), entry)(C.byref(d), self._stream()), entry[3:])
         if planar is not None:
             self.ingest(planar, ref)      # repoints the stem; nothing is copied
         else:

@@ -1,5 +1,7 @@
 // pv_resample_crop: short_side_scale + uniform_crop (reference transforms/functional.py:92-131,302-347) fused with the
 // ingest's frame selection, Div255 + Normalize affine, dtype conversion and layout change.
+// pv_video_views: the same kernel reading ONE video through a frame table with a row per clip -- the clip sampler,
+// FrameVideo.get_clip (data/frame_video.py:149-200) and UniformTemporalSubsample of the reference's data pipeline as data.
 //
 // A bandwidth-bound gather.  One workgroup owns a strip of R output rows of one destination frame of one view:
 //   1. stage: the source span those rows need -- per output row the two source rows i0y, i1y (or, when the strip's source
@@ -32,8 +34,10 @@ struct RsLaunch {
   float sy, sx;     // (float)Hs / (float)Hn, (float)Ws / (float)Wn: divided once, on the host
   int32_t R;        // output rows per workgroup
   int32_t pitch;    // LDS bytes per staged (row, plane): multiple of 16, >= 15 + widest span
-  int32_t src_T;
+  int32_t src_T;    // frames per source plane; every selected frame is clamped into [0, src_T - 1]
   int32_t item0;
+  int32_t tab_stride;   // t_index row stride per clip: 0 = one row shared by all clips (pv_resample_crop)
+  int64_t clip_frames;  // frames from one source clip to the next: 0 = every clip reads the one video (pv_video_views)
 };
 
 // Source coordinate of destination index d (the pinned formula: every operation rounded on its own, no contraction, so
@@ -76,6 +80,8 @@ template <> struct RsVec<float> {
 template <int FORM, typename D> struct RsGroup { static constexpr int G = FORM == RS_PLANAR ? RsVec<D>::G : (FORM == RS_C4 ? 2 : 1); };
 
 // S: source element (unsigned char | float); INTER: frame-interleaved [B,T,Hs,Ws,3] source; FORM / D: destination.
+// Source clip b starts g.clip_frames frames behind clip b - 1 and takes its frames from row b * g.tab_stride of d.t_index:
+// B clips with one shared row (pv_resample_crop), or one video with a row per clip (pv_video_views: clip_frames == 0).
 template <typename S, bool INTER, int FORM, typename D>
 __global__ __launch_bounds__(kRsThreads) void resample_crop_kernel(const pv_resample_desc d, const RsLaunch g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rs_lds[];
@@ -92,7 +98,8 @@ __global__ __launch_bounds__(kRsThreads) void resample_crop_kernel(const pv_resa
   const int xoff = view == 0 ? d.x_off[0] : (view == 1 ? d.x_off[1] : d.x_off[2]);
   const int row0 = blockIdx.x * R;
   const int nrows = min(R, d.Ho - row0);
-  const int ts = d.t_index ? d.t_index[t] : t;
+  // clamped before any address is formed: a malformed table can never read outside the source
+  const int ts = min(max(d.t_index ? d.t_index[(long)b * g.tab_stride + t] : t, 0), g.src_T - 1);
   const int planes = INTER ? 1 : d.C;
 
   int xs0, xs1, ybase, ylast, unused;
@@ -109,8 +116,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_crop_kernel(const pv_resa
   const uintptr_t src0 = reinterpret_cast<uintptr_t>(d.src);
   const long row_bytes = (long)d.Ws * XB;
   const long frame_bytes = (long)d.Hs * row_bytes;
-  const long first = INTER ? ((long)b * g.src_T + ts) * frame_bytes + (long)xs0 * XB
-                           : ((long)b * d.C * g.src_T + ts) * frame_bytes + (long)xs0 * XB;
+  const long first = ((long)b * g.clip_frames + ts) * frame_bytes + (long)xs0 * XB;
   const long plane_bytes = INTER ? 0 : (long)g.src_T * frame_bytes;
   auto row_addr = [&](int y, int pl) -> uintptr_t { return src0 + first + (long)pl * plane_bytes + (long)y * row_bytes; };
 
@@ -258,11 +264,9 @@ int rs_launch(const pv_resample_desc& d, const RsLaunch& g, dim3 grid, size_t ld
   return PV_OK;
 }
 
-}  // namespace
-
-extern "C" int pv_resample_crop(const pv_resample_desc* dp, pv_stream_t stream) {
-  if (!dp || !dp->src || !dp->dst) return PV_ERR_INVALID;
-  pv_resample_desc d = *dp;
+// Validation and launch shared by both entry points.  `one_video`: the source is one video [C,src_T,Hs,Ws] / [src_T,Hs,Ws,3]
+// every clip reads through its own row of t_index (row stride tab_stride); else B clips and one shared t_index row.
+int rs_run(pv_resample_desc d, bool one_video, int tab_stride, pv_stream_t stream) {
   if (d.B <= 0 || d.C <= 0 || d.T <= 0 || d.Hs <= 0 || d.Ws <= 0 || d.Hn <= 0 || d.Wn <= 0 || d.Ho <= 0 || d.Wo <= 0)
     return PV_ERR_INVALID;
   if (d.C > 4) return PV_ERR_INVALID;
@@ -273,6 +277,7 @@ extern "C" int pv_resample_crop(const pv_resample_desc* dp, pv_stream_t stream) 
   if (d.src_layout != PV_SRC_NCTHW && d.src_layout != PV_SRC_NTHWC) return PV_ERR_INVALID;
   if (d.src_layout == PV_SRC_NTHWC && (d.src_dtype != PV_U8 || d.C != 3)) return PV_ERR_INVALID;
   if (d.t_index && d.src_T <= 0) return PV_ERR_INVALID;
+  if (one_video && (!d.t_index || tab_stride < d.T)) return PV_ERR_INVALID;
   const long all_items = (long)d.B * d.n_views;
   if (d.n_items == 0 && d.item0 == 0) d.n_items = (int32_t)all_items;
   if (d.item0 < 0 || d.n_items <= 0 || (long)d.item0 + d.n_items > all_items) return PV_ERR_INVALID;
@@ -303,6 +308,8 @@ extern "C" int pv_resample_crop(const pv_resample_desc* dp, pv_stream_t stream) 
   g.sx = (float)d.Ws / (float)d.Wn;
   g.src_T = d.t_index ? d.src_T : d.T;
   g.item0 = d.item0;
+  g.tab_stride = one_video ? tab_stride : 0;
+  g.clip_frames = one_video ? 0 : (int64_t)(d.src_layout == PV_SRC_NTHWC ? 1 : d.C) * g.src_T;
   // the widest column span of any view sizes the staged row
   const bool inter = d.src_layout == PV_SRC_NTHWC;
   const int xb = inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1);
@@ -329,4 +336,29 @@ extern "C" int pv_resample_crop(const pv_resample_desc* dp, pv_stream_t stream) 
   if (inter) return rs_launch<unsigned char, true>(d, g, grid, lds, s);
   if (d.src_dtype == PV_U8) return rs_launch<unsigned char, false>(d, g, grid, lds, s);
   return rs_launch<float, false>(d, g, grid, lds, s);
+}
+
+}  // namespace
+
+extern "C" int pv_resample_crop(const pv_resample_desc* dp, pv_stream_t stream) {
+  if (!dp || !dp->src || !dp->dst) return PV_ERR_INVALID;
+  return rs_run(*dp, false, 0, stream);
+}
+
+// One video, one frame table: the same kernel with B = n_clips, src_T = N and a table row per clip.
+extern "C" int pv_video_views(const pv_video_views_desc* vp, pv_stream_t stream) {
+  if (!vp || !vp->src || !vp->dst) return PV_ERR_INVALID;   // n_clips, T, N, the table and its stride: rs_run (B, T, src_T)
+  pv_resample_desc d = {};
+  d.src = vp->src; d.dst = vp->dst;
+  d.B = vp->n_clips; d.C = vp->C; d.T = vp->T;
+  d.src_T = vp->N; d.Hs = vp->Hs; d.Ws = vp->Ws;
+  d.src_dtype = vp->src_dtype; d.src_layout = vp->src_layout;
+  d.Hn = vp->Hn; d.Wn = vp->Wn; d.Ho = vp->Ho; d.Wo = vp->Wo;
+  d.n_views = vp->n_views;
+  for (int v = 0; v < 3; ++v) { d.y_off[v] = vp->y_off[v]; d.x_off[v] = vp->x_off[v]; }
+  d.item0 = vp->item0; d.n_items = vp->n_items;
+  d.dst_layout = vp->dst_layout; d.dst_dtype = vp->dst_dtype;
+  d.c_p = vp->c_p; d.ld = vp->ld; d.bs = vp->bs;
+  d.t_index = vp->t_index; d.ch_scale = vp->ch_scale; d.ch_shift = vp->ch_shift;
+  return rs_run(d, true, vp->t_stride, stream);
 }

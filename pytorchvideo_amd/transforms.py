@@ -229,6 +229,32 @@ def _device_source(clip, device):
     return clip.contiguous()
 
 
+def _video_geometry(video, src_layout):
+    """(C, N, Hs, Ws) of ONE video: [C,N,H,W] ("NCTHW") or the decoder's [N,H,W,3] ("NTHWC")."""
+    if video.dim() != 4:
+        raise RuntimeError("expected one 4-d %s video, got %s" % (src_layout, tuple(video.shape),))
+    if src_layout == "NCTHW":
+        return tuple(video.shape)
+    n, h, w, c = video.shape
+    return c, n, h, w
+
+
+def pathway_tables(table, pathway_frames, num_frames):
+    """The frame table of every input pathway from the table of the clip itself (`data.clip_frame_table`): pathway p holds
+    the columns `temporal_indices(T, pathway_frames[p])` of the [n_clips, T] table -- uniform_temporal_subsample_repeated on
+    frame numbers, so SlowFast's slow table is a column subset of the fast one.  Host int32 tensors; the check that every
+    entry names a frame of the video is made HERE (the kernel only clamps), ValueError otherwise."""
+    table = torch.as_tensor(table)
+    if table.dim() != 2 or table.numel() == 0 or table.dtype in (torch.float16, torch.float32, torch.float64, torch.bfloat16):
+        raise ValueError("a frame table is a non-empty integer [n_clips, T] tensor, got %s %s" % (table.dtype, tuple(table.shape)))
+    table = table.to("cpu", torch.int64)
+    if int(table.min()) < 0 or int(table.max()) >= num_frames:
+        raise ValueError("frame table entries %d..%d leave the video's frames [0, %d)"
+                         % (int(table.min()), int(table.max()), num_frames))
+    t = table.shape[1]
+    return [table[:, temporal_indices(t, tp)].to(torch.int32).contiguous() for tp in pathway_frames]
+
+
 @torch.no_grad()
 def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std=None, div255=False, num_frames=None,
                       dtype=torch.bfloat16, src_layout="NCTHW"):
@@ -279,7 +305,12 @@ class DevicePacker:
     or the decoder's uint8 [B,T,H,W,3] ("NTHWC"); the deploy form's batch is B * n_views, item b * n_views + v being view v
     of clip b (`VideoEnsembler`'s video_index for it is `repeat_interleave(n_views)`), and `crop_size` is the model's
     H == W.  The boxes of a detection model are given in the pixels of the SOURCE frame and follow the clip through
-    `short_side_scale_with_boxes` and `uniform_crop_with_boxes` on the host (one view only)."""
+    `short_side_scale_with_boxes` and `uniform_crop_with_boxes` on the host (one view only).
+
+    `fill_video(video, tables, i0, n)` + `launch()` run the resampling packer on ONE decoded video instead of clips: items
+    [i0, i0 + n) of its clips x views sequence, the clips being rows of a frame table (`data.clip_frame_table`, uploaded by
+    `video_tables`) that the ingest kernel reads the video through (`pv_video_views`); `inference.VideoPredictor` is the
+    loop around it."""
 
     def __init__(self, deployed, mean=None, std=None, div255=False, frame_ratios=None, short_side=None, crop_size=None,
                  spatial_idx=1, src_layout="NCTHW"):
@@ -383,8 +414,7 @@ class DevicePacker:
                 else:
                     sub._fill(clip[lo:lo + b])
                 lo += b
-            self.model._pv_launch()
-            return self.model._pv_result()
+            return self.launch()
         if resample:
             hs, ws, hn, wn = self._check_source(clip, self.refs[0].B)
             if bboxes is not None:
@@ -395,8 +425,7 @@ class DevicePacker:
             self._fill(clip)
         if load_boxes is not None:
             load_boxes(bboxes)
-        self.sess.launch(use_graph=self.model._pv_use_graph)
-        return self.model._pv_result()
+        return self.launch()
 
     def _fill(self, clip):
         t_src = clip.shape[2]
@@ -417,11 +446,105 @@ class DevicePacker:
                 d.T, d.t_index = ref.T, index.data_ptr()
             if self.scale is not None:
                 d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
-            planar = None
-            if ref.src_slot is not None and ref.c4_readers == 0 and self.sess.pv_dtype == L.PV_BF16:
-                # every reader is a stem that reads an NCDHW clip itself: resample into a clip of our own and point it there
-                if i not in self._planar:
-                    self._planar[i] = torch.empty((ref.B, ref.C, ref.T, ref.H, ref.W), dtype=torch.bfloat16,
-                                                  device=self.sess.device)
-                planar = self._planar[i]
-            self.sess.resample(d, ref, planar=planar)
+            self.sess.resample(d, ref, planar=self._planar_for(i, ref))
+
+    def _planar_for(self, i, ref):
+        """The packer's own bf16 NCDHW clip for pathway i when every reader of `ref` is a stem that reads such a clip itself
+        (the resampling kernels write it and the stem is pointed there), else None: the arena buffer in its own layout."""
+        from . import _lib as L
+        if ref.src_slot is None or ref.c4_readers != 0 or self.sess.pv_dtype != L.PV_BF16:
+            return None
+        if i not in self._planar:
+            self._planar[i] = torch.empty((ref.B, ref.C, ref.T, ref.H, ref.W), dtype=torch.bfloat16, device=self.sess.device)
+        return self._planar[i]
+
+    # ------------------------------------------------------------------------- whole-video ingest (pv_video_views)
+    @property
+    def batch(self):
+        """Items of one forward of the deploy form (clips x views)."""
+        return sum(self.model._splits) if self.subs is not None else self.refs[0].B
+
+    @property
+    def clip_frames(self):
+        """Frames of the clip the pathways subsample (SlowFast (4, 1): the fast pathway's)."""
+        refs = self.subs[0].refs if self.subs is not None else self.refs
+        t = max(ref.T * r for ref, r in zip(refs, self.frame_ratios))
+        if any(t // r != ref.T for ref, r in zip(refs, self.frame_ratios)):
+            raise ValueError("frame ratios %s do not fit the pathways' frame counts %s" % (self.frame_ratios, [ref.T for ref in refs]))
+        return t
+
+    def video_tables(self, table, num_frames):
+        """Upload (once per video) the per-pathway frame tables of a [n_clips, clip_frames] table: `pathway_tables`."""
+        refs = self.subs[0].refs if self.subs is not None else self.refs
+        table = torch.as_tensor(table)
+        if table.dim() == 2 and table.shape[1] != self.clip_frames:
+            raise ValueError("the deploy form takes clips of %d frames, the table has %d columns" % (self.clip_frames, table.shape[1]))
+        return [t.to(self.sess.device) for t in pathway_tables(table, [ref.T for ref in refs], num_frames)]
+
+    @torch.no_grad()
+    def fill_video(self, video, tables, i0, n):
+        """Fill the deploy form's input buffers with items [i0, i0 + n) of the clips x views sequence of ONE video (item
+        clip * n_views + v is view v of the clip whose frames are row `clip` of `tables`, from `video_tables`), one
+        pv_video_views launch per pathway (and per sub-plan of a split-batch form): no clip is materialised.  n may be
+        smaller than the deploy batch -- the ragged last chunk of a video -- and the rest of the buffers is then zeroed.
+        `video` is [C,N,H,W] ("NCTHW"; uint8 or fp32) or [N,H,W,3] uint8 ("NTHWC"), contiguous and on the device, and must
+        stay alive until the forward has run.  Nothing is launched here but the ingest: run `launch()` next."""
+        if self.short_side is None:
+            raise RuntimeError("fill_video resamples: construct the packer with short_side and crop_size")
+        if getattr(self.model, "_pv_load_boxes", None) is not None:
+            raise RuntimeError("a detection model takes boxes of key frames, not a video")
+        c, nf, hs, ws = _video_geometry(video, self.src_layout)
+        if not video.is_cuda or not video.is_contiguous() or video.dtype not in (torch.uint8, torch.float32):
+            raise RuntimeError("the video is a contiguous uint8 or fp32 tensor on the device")
+        if self.src_layout == "NTHWC" and (c != 3 or video.dtype != torch.uint8):
+            raise RuntimeError("a frame-interleaved video is uint8 [N,H,W,3], got %s %s" % (video.dtype, tuple(video.shape)))
+        hn, wn = scaled_size(hs, ws, self.short_side)
+        if self.crop_size > hn or self.crop_size > wn:
+            raise RuntimeError("a %d crop does not fit the %d x %d frame scaled to %d x %d" % (self.crop_size, hs, ws, hn, wn))
+        refs = self.subs[0].refs if self.subs is not None else self.refs
+        if len(tables) != len(refs):
+            raise RuntimeError("%d frame tables for %d input pathways" % (len(tables), len(refs)))
+        for tab, ref in zip(tables, refs):
+            if (tab.dim() != 2 or tab.dtype != torch.int32 or not tab.is_cuda or not tab.is_contiguous()
+                    or tab.shape[0] != tables[0].shape[0] or tab.shape[1] != ref.T or c != ref.C):
+                raise RuntimeError("pathway expects %d channels and an int32 device table [n_clips, %d]; got %d channels, %s %s"
+                                   % (ref.C, ref.T, c, tab.dtype, tuple(tab.shape)))
+        total = tables[0].shape[0] * len(self.views)
+        if not (0 <= i0 and 0 < n <= self.batch and i0 + n <= total):
+            raise RuntimeError("items [%d, %d) are not a chunk of at most %d of the video's %d clips x views"
+                               % (i0, i0 + n, self.batch, total))
+        if self.subs is None:
+            return self._fill_video(video, tables, i0, n)
+        lo = 0
+        for sub, b in zip(self.subs, self.model._splits):
+            sub._fill_video(video, tables, i0 + lo, max(0, min(b, n - lo)))
+            lo += b
+
+    def launch(self):
+        """One forward on what the input buffers hold; the logits [batch, classes] (an arena view for a one-plan form:
+        valid until the next forward)."""
+        if self.subs is not None:
+            self.model._pv_launch()
+        else:
+            self.sess.launch(use_graph=self.model._pv_use_graph)
+        return self.model._pv_result()
+
+    def _fill_video(self, video, tables, item0, n_items):
+        """One pv_video_views launch per pathway into this plan's buffers; see Session.video_views for the tail."""
+        from . import _lib as L
+        self._src = (video, tables)                        # alive until the launch has run
+        c, nf, hs, ws = _video_geometry(video, self.src_layout)
+        hn, wn = scaled_size(hs, ws, self.short_side)
+        for i, (ref, tab) in enumerate(zip(self.refs, tables)):
+            d = L.VideoViewsDesc()
+            d.src, d.t_index = video.data_ptr(), tab.data_ptr()
+            d.n_clips, d.C, d.T, d.N, d.t_stride, d.Hs, d.Ws = tab.shape[0], c, ref.T, nf, tab.stride(0), hs, ws
+            d.src_dtype = L.PV_U8 if video.dtype == torch.uint8 else L.PV_F32
+            d.src_layout = L.SRC_NCTHW if self.src_layout == "NCTHW" else L.SRC_NTHWC
+            d.Hn, d.Wn, d.Ho, d.Wo, d.n_views = hn, wn, self.crop_size, self.crop_size, len(self.views)
+            for k, v in enumerate(self.views):
+                d.y_off[k], d.x_off[k] = crop_offsets(hn, wn, self.crop_size, v)
+            d.item0, d.n_items = (item0, n_items) if n_items else (0, 0)
+            if self.scale is not None:
+                d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
+            self.sess.video_views(d, ref, planar=self._planar_for(i, ref))
