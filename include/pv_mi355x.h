@@ -406,6 +406,61 @@ typedef struct pv_video_views_desc {
 } pv_video_views_desc;
 int pv_video_views(const pv_video_views_desc* d, pv_stream_t stream);
 
+/* ---- decoder-native sources: YUV 4:2:0 (NV12 / NV21 / I420 / YV12) read by the ingest itself ---------------------------
+ * No decoder hands out RGB: a GPU decoder writes NV12 surfaces (pitched, often with a coded height above the display
+ * height), a CPU decoder planar yuv420p.  pv_yuv_views is pv_video_views on such frames: it takes the four taps of every
+ * output pixel from the luma and chroma planes, converts each TAP to RGB in registers and goes on with the blend, the
+ * affine map and the store above, so neither a colour-conversion pass nor an RGB copy of the video exists, and the
+ * ingest reads 1.5 bytes per source pixel instead of 3.
+ * Source:       N frames of uint8, frame n at src + n * frame_stride (bytes).  Inside a frame
+ *                   Y(y, x) = frame[y * y_pitch + x]                                0 <= y < Hs, 0 <= x < Ws (both even)
+ *                   U(j, i) = frame[u_offset + j * c_pitch + i * c_step]            0 <= j < Hs/2, 0 <= i < Ws/2
+ *                   V(j, i) = frame[v_offset + j * c_pitch + i * c_step]
+ *               c_step 2: one interleaved chroma plane, |v_offset - u_offset| == 1 (NV12: v_offset = u_offset + 1, NV21
+ *               swapped); c_step 1: two planes (I420: U first, YV12: V first).  Rows, planes and src may start at ANY byte
+ *               address: nothing needs alignment.  A coded height above Hs only moves u_offset / v_offset.
+ * Frames:       t_index[clip * t_stride + t], clamped into [0, N-1] before an address is formed, as in pv_video_views.  A
+ *               whole video is one such sequence; a batch of B materialised clips of T' frames is the sequence of B * T'
+ *               frames with table rows b * T' + index.
+ * Arithmetic:   pixel (y, x) of the VIRTUAL RGB frame is, in fp32 and NOT rounded to an integer,
+ *                   rgb[c] = clamp(fma(M[c][2], V, fma(M[c][1], U, fma(M[c][0], Y, M[c][3]))), 0, 255)
+ *               with Y = Y(y, x), U = U(y >> 1, x >> 1), V = V(y >> 1, x >> 1) and M = yuv2rgb, 12 fp32 values on the
+ *               device: a 3 x 4 matrix, rows R, G, B, columns Y, U, V and a constant, composed by the caller -- as the
+ *               caller computes the scaling geometry -- so the library is not tied to one standard or range.  Chroma is
+ *               REPLICATED over its 2 x 2 luma block (the simplest well-defined rule; a filtered-chroma variant -- sited
+ *               chroma, bilinear chroma upsampling -- is out of scope).  On that virtual frame the rest is exactly
+ *               pv_resample_crop's formula above: the same source coordinate, the same blend order, the affine map after
+ *               the blend, one rounding to dst_dtype.  The clamp sits on the taps, not behind the blend: clamping does not
+ *               commute with interpolation, and "convert, then resize" is what the reference pipeline does.
+ * Destination:  as pv_resample_crop (C == 3); items and item0 / n_items as pv_video_views.
+ * PV_ERR_INVALID: null src / dst / t_index / yuv2rgb; n_clips, T, N <= 0; t_stride < T; odd or non-positive Hs / Ws; c_step
+ * not 1 or 2; c_step 2 with |v_offset - u_offset| != 1; y_pitch < Ws; c_pitch < (Ws/2) * c_step; negative offsets; a luma or
+ * chroma plane that leaves [0, frame_stride); and whatever pv_resample_crop rejects (views, windows, item range,
+ * destination alignment).  PV_ERR_UNSUPPORTED: a dtype / layout pair outside pv_resample_crop's destination matrix.
+ */
+typedef struct pv_yuv_views_desc {
+  const void* src; void* dst;
+  const int32_t* t_index;     /* [n_clips][t_stride], the first T of every row used                              */
+  const float* ch_scale;      /* [3] or NULL                                                                     */
+  const float* ch_shift;      /* [3] or NULL                                                                     */
+  const float* yuv2rgb;       /* [3][4] fp32 on the device                                                       */
+  int64_t bs;                 /* PV_DST_NDHWC only: batch stride in elements                                     */
+  int64_t frame_stride;       /* bytes from one frame to the next                                                */
+  int64_t u_offset, v_offset; /* bytes from the start of a frame to its first U / V sample                       */
+  int32_t y_pitch, c_pitch;   /* bytes per luma row (>= Ws) and per chroma row (>= (Ws/2) * c_step)              */
+  int32_t c_step;             /* bytes between x-adjacent samples of one chroma plane: 2 interleaved, 1 planar   */
+  int32_t n_clips, T;         /* table rows, DESTINATION frames per clip                                         */
+  int32_t N, t_stride;        /* frames in the source; table row stride (>= T)                                   */
+  int32_t Hs, Ws;             /* display size of a frame: even                                                   */
+  int32_t Hn, Wn, Ho, Wo;     /* as in pv_resample_desc                                                          */
+  int32_t n_views;            /* 1..3                                                                            */
+  int32_t y_off[3], x_off[3];
+  int32_t item0, n_items;
+  int32_t dst_layout, dst_dtype;
+  int32_t c_p, ld;            /* PV_DST_NDHWC only                                                               */
+} pv_yuv_views_desc;
+int pv_yuv_views(const pv_yuv_views_desc* d, pv_stream_t stream);
+
 /* ---- row ops on (rows, C) matrices -------------------------------------------------
  * pv_layernorm: nn.LayerNorm(eps) over C (models/vision_transformers.py:333-335,
  *   layers/attention.py:199-205).

@@ -84,6 +84,12 @@ VideoViewsDesc = _struct("VideoViewsDesc", [
     + _ints("n_clips", "C", "T", "N", "t_stride", "Hs", "Ws", "src_dtype", "src_layout", "Hn", "Wn", "Ho", "Wo", "n_views")
     + [("y_off", _i32 * 3), ("x_off", _i32 * 3)] + _ints("item0", "n_items", "dst_layout", "dst_dtype", "c_p", "ld"))
 
+YuvViewsDesc = _struct("YuvViewsDesc", [
+    ("src", _p), ("dst", _p), ("t_index", _p), ("ch_scale", _p), ("ch_shift", _p), ("yuv2rgb", _p), ("bs", _i64),
+    ("frame_stride", _i64), ("u_offset", _i64), ("v_offset", _i64)]
+    + _ints("y_pitch", "c_pitch", "c_step", "n_clips", "T", "N", "t_stride", "Hs", "Ws", "Hn", "Wn", "Ho", "Wo", "n_views")
+    + [("y_off", _i32 * 3), ("x_off", _i32 * 3)] + _ints("item0", "n_items", "dst_layout", "dst_dtype", "c_p", "ld"))
+
 RowsDesc = _struct("RowsDesc", [
     ("x", _p), ("y", _p), ("gamma", _p), ("beta", _p), ("rows", _i64)]
     + _ints("C", "ldx", "ldy", "rows_per_batch") + [("eps", _f32), ("dtype", _i32), ("x_f32", _i32), ("g_period", _i32),
@@ -161,6 +167,7 @@ _SYMBOLS = [
     ("pv_egress_ncdhw", C.c_int, [C.POINTER(LayoutDesc), _p]),
     ("pv_resample_crop", C.c_int, [C.POINTER(ResampleDesc), _p]),
     ("pv_video_views", C.c_int, [C.POINTER(VideoViewsDesc), _p]),
+    ("pv_yuv_views", C.c_int, [C.POINTER(YuvViewsDesc), _p]),
     ("pv_layernorm", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_affine_rows", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_softmax_rows", C.c_int, [C.POINTER(RowsDesc), _p]),
@@ -206,7 +213,7 @@ _SYMBOLS = [
     ("pv_forward_gather", C.c_int, [_p, _p, _p, C.POINTER(GatherSrc), C.c_int, _p, _p, _p]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SYMBOLS]
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 _lib = None
 

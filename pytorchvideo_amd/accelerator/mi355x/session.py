@@ -408,10 +408,17 @@ class Session:
         ingest: `d` is a VideoViewsDesc prepared by transforms.DevicePacker.fill_video) and ZERO the remaining
         ref.B - d.n_items items -- a ragged last chunk of a video -- so that no result depends on an earlier forward.
         d.n_items == 0 only zeroes.  Destination and `planar` as in `resample`."""
+        self._views_into(d, d.C, ref, planar, "pv_video_views")
+
+    def yuv_views(self, d, ref, planar=None):
+        """`video_views` for a YuvViewsDesc (YUV 4:2:0 frames converted inside the ingest: pv_yuv_views; 3 channels)."""
+        self._views_into(d, 3, ref, planar, "pv_yuv_views")
+
+    def _views_into(self, d, channels, ref, planar, entry):
         n = d.n_items
-        if not 0 <= n <= ref.B or (d.C, d.T, d.Ho, d.Wo) != (ref.C, ref.T, ref.H, ref.W):
+        if not 0 <= n <= ref.B or (channels, d.T, d.Ho, d.Wo) != (ref.C, ref.T, ref.H, ref.W):
             raise L.PvError("deploy form was converted for input %s, got %d items of %s" %
-                            ((ref.B, ref.C, ref.T, ref.H, ref.W), n, (d.C, d.T, d.Ho, d.Wo)))
+                            ((ref.B, ref.C, ref.T, ref.H, ref.W), n, (channels, d.T, d.Ho, d.Wo)))
         if n < ref.B:
             with torch.cuda.device(self.device):
                 if planar is not None:
@@ -419,7 +426,7 @@ class Session:
                 else:
                     self.arena_t[ref.off + n * ref.bs * ref.itemsize: ref.off + ref.B * ref.bs * ref.itemsize].zero_()
         if n:
-            self._resample_into(d, ref, planar, "pv_video_views")
+            self._resample_into(d, ref, planar, entry)
         elif planar is not None:
             self.ingest(planar, ref)      # nothing to write: only point the stem at the zeroed clip
         else:

@@ -17,18 +17,9 @@
 //      (Wo not a multiple of G) or not 16-byte aligned in the destination (odd Wo) are stored element by element.
 //      (Eight pixels per thread for the 4-channel layout -- four 16-byte stores 64 bytes apart, as ingest_c4_vec8_kernel
 //      does -- measured up to 17 % slower here: DESIGN.md 4.6.)
-#include "pv_common.h"
+#include "pv_rs.h"
 
 namespace {
-
-constexpr int kRsThreads = 256;
-constexpr int kRsMaxRows = 8;            // output rows per workgroup
-constexpr int kRsLdsBudget = 32 * 1024;  // staging bytes per workgroup: 4-5 workgroups per CU (160 KiB)
-constexpr int kRsLdsMax = 64 * 1024;
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-enum { RS_C4 = 0, RS_CL = 1, RS_PLANAR = 2 };
 
 struct RsLaunch {
   float sy, sx;     // (float)Hs / (float)Hn, (float)Ws / (float)Wn: divided once, on the host
@@ -40,44 +31,11 @@ struct RsLaunch {
   int64_t clip_frames;  // frames from one source clip to the next: 0 = every clip reads the one video (pv_video_views)
 };
 
-// Source coordinate of destination index d (the pinned formula: every operation rounded on its own, no contraction, so
-// that the host, which sizes the LDS span, and every thread agree on i0 / i1).
-__host__ __device__ __forceinline__ void rs_coord(float s, int d, int n_in, int& i0, int& i1, float& l1) {
-#pragma clang fp contract(off)
-  const float a = (float)d + 0.5f;
-  const float m = s * a;
-  float r = m - 0.5f;
-  r = r < 0.f ? 0.f : r;
-  i0 = (int)r;
-  i0 = i0 < n_in - 1 ? i0 : n_in - 1;   // r < n_in - 0.5 for every d inside the scaled frame; this keeps reads in bounds regardless
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  l1 = r - (float)i0;
-}
-
 template <typename S> __device__ __forceinline__ float rs_tap(const unsigned char* lds, int off);
 template <> __device__ __forceinline__ float rs_tap<unsigned char>(const unsigned char* lds, int off) { return (float)lds[off]; }
 template <> __device__ __forceinline__ float rs_tap<float>(const unsigned char* lds, int off) {
   return *reinterpret_cast<const float*>(lds + off);
 }
-
-template <typename D> struct RsVec;   // one 16-byte store of G = 16 / sizeof(D) elements
-template <> struct RsVec<bf16_t> {
-  static constexpr int G = 8;
-  static __device__ __forceinline__ void store(bf16_t* p, const float* f) {
-    bf16x8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16_t)f[i];
-    *reinterpret_cast<bf16x8*>(p) = v;
-  }
-};
-template <> struct RsVec<float> {
-  static constexpr int G = 4;
-  static __device__ __forceinline__ void store(float* p, const float* f) {
-    *reinterpret_cast<f32x4*>(p) = f32x4{f[0], f[1], f[2], f[3]};
-  }
-};
-
-template <int FORM, typename D> struct RsGroup { static constexpr int G = FORM == RS_PLANAR ? RsVec<D>::G : (FORM == RS_C4 ? 2 : 1); };
 
 // S: source element (unsigned char | float); INTER: frame-interleaved [B,T,Hs,Ws,3] source; FORM / D: destination.
 // Source clip b starts g.clip_frames frames behind clip b - 1 and takes its frames from row b * g.tab_stride of d.t_index:
@@ -204,47 +162,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_crop_kernel(const pv_resa
     }
     const int x0 = gx * G;
     const int nvalid = min(G, d.Wo - x0);
-    if constexpr (FORM == RS_PLANAR) {
-      const long HW = (long)d.Ho * d.Wo;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        if (c < d.C) {
-          D* p = static_cast<D*>(d.dst) + (((long)zi * d.C + c) * d.T + t) * HW + (long)y * d.Wo + x0;
-          if (nvalid == G && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-            RsVec<D>::store(p, out[c]);
-          } else {
-#pragma unroll
-            for (int j = 0; j < G; ++j)
-              if (j < nvalid) p[j] = (D)out[c][j];
-          }
-        }
-      }
-    } else if constexpr (FORM == RS_C4) {
-      bf16_t* p = static_cast<bf16_t*>(d.dst) + (long)zi * d.bs + ((((long)t * d.Ho + y) * d.Wo) + x0) * 4;
-      if (nvalid == G && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-#pragma unroll
-        for (int j = 0; j < G; j += 2) {           // two voxels = one 16-byte chunk of the first-layer layout
-          const bf16x8 o = {(bf16_t)out[0][j], (bf16_t)out[1][j], (bf16_t)out[2][j], (bf16_t)out[3][j],
-                            (bf16_t)out[0][j + 1], (bf16_t)out[1][j + 1], (bf16_t)out[2][j + 1], (bf16_t)out[3][j + 1]};
-          *reinterpret_cast<bf16x8*>(p + j * 4) = o;
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < G; ++j)
-          if (j < nvalid) {
-            const bf16x4 o = {(bf16_t)out[0][j], (bf16_t)out[1][j], (bf16_t)out[2][j], (bf16_t)out[3][j]};
-            *reinterpret_cast<bf16x4*>(p + j * 4) = o;
-          }
-      }
-    } else {
-      D* p = static_cast<D*>(d.dst) + (long)zi * d.bs + ((((long)t * d.Ho + y) * d.Wo) + x0) * d.ld;
-      const float f[8] = {out[0][0], out[1][0], out[2][0], out[3][0], 0.f, 0.f, 0.f, 0.f};
-      Chunk8<D> o;
-      o.from_f32(f);
-      o.store(p);
-      o.zero();
-      for (int k = 8; k < d.c_p; k += 8) o.store(p + k);
-    }
+    rs_store_group<FORM, D, G>(d.dst, out, d.C, d.T, d.Ho, d.Wo, d.c_p, d.ld, d.bs, zi, t, y, x0, nvalid);
   }
 }
 
@@ -270,37 +188,15 @@ int rs_run(pv_resample_desc d, bool one_video, int tab_stride, pv_stream_t strea
   if (d.B <= 0 || d.C <= 0 || d.T <= 0 || d.Hs <= 0 || d.Ws <= 0 || d.Hn <= 0 || d.Wn <= 0 || d.Ho <= 0 || d.Wo <= 0)
     return PV_ERR_INVALID;
   if (d.C > 4) return PV_ERR_INVALID;
-  if (d.n_views < 1 || d.n_views > 3) return PV_ERR_INVALID;
-  for (int v = 0; v < d.n_views; ++v)
-    if (d.y_off[v] < 0 || d.x_off[v] < 0 || (long)d.y_off[v] + d.Ho > d.Hn || (long)d.x_off[v] + d.Wo > d.Wn)
-      return PV_ERR_INVALID;
+  if (int e = rs_check_views(d.n_views, d.y_off, d.x_off, d.Ho, d.Wo, d.Hn, d.Wn)) return e;
   if (d.src_layout != PV_SRC_NCTHW && d.src_layout != PV_SRC_NTHWC) return PV_ERR_INVALID;
   if (d.src_layout == PV_SRC_NTHWC && (d.src_dtype != PV_U8 || d.C != 3)) return PV_ERR_INVALID;
   if (d.t_index && d.src_T <= 0) return PV_ERR_INVALID;
   if (one_video && (!d.t_index || tab_stride < d.T)) return PV_ERR_INVALID;
-  const long all_items = (long)d.B * d.n_views;
-  if (d.n_items == 0 && d.item0 == 0) d.n_items = (int32_t)all_items;
-  if (d.item0 < 0 || d.n_items <= 0 || (long)d.item0 + d.n_items > all_items) return PV_ERR_INVALID;
-  if (d.T > 65535 || d.n_items > 65535) return PV_ERR_INVALID;   // grid.y / grid.z
+  if (int e = rs_check_items(d.item0, d.n_items, (long)d.B * d.n_views, d.T)) return e;
   // the dtype / layout matrix
   if (d.src_dtype != PV_U8 && d.src_dtype != PV_F32) return PV_ERR_UNSUPPORTED;
-  if (d.dst_dtype != PV_BF16 && d.dst_dtype != PV_F32) return PV_ERR_UNSUPPORTED;
-  const uintptr_t dst = reinterpret_cast<uintptr_t>(d.dst);
-  if (d.dst_layout == PV_DST_NDHWC) {
-    if (d.c_p == 4 && d.ld == 4) {
-      if (d.dst_dtype != PV_BF16) return PV_ERR_UNSUPPORTED;
-      if (d.bs % 4 || dst % 8) return PV_ERR_INVALID;
-    } else if (d.c_p >= 8 && d.c_p % 8 == 0) {
-      if (d.ld % 8 || d.ld < d.c_p || d.bs % 8 || dst % 16) return PV_ERR_INVALID;
-    } else {
-      return PV_ERR_UNSUPPORTED;
-    }
-    if (d.bs < (int64_t)d.T * d.Ho * d.Wo * d.ld) return PV_ERR_INVALID;
-  } else if (d.dst_layout == PV_DST_NCTHW) {
-    if (dst % (d.dst_dtype == PV_BF16 ? 2 : 4)) return PV_ERR_INVALID;
-  } else {
-    return PV_ERR_UNSUPPORTED;
-  }
+  if (int e = rs_check_dst(d.dst, d.dst_layout, d.dst_dtype, d.c_p, d.ld, d.bs, d.T, d.Ho, d.Wo)) return e;
   if (d.src_dtype == PV_F32 && reinterpret_cast<uintptr_t>(d.src) % 4) return PV_ERR_INVALID;
 
   RsLaunch g;

@@ -23,17 +23,21 @@ class VideoPredictor:
 
     `deployed` is a classification model converted as a whole by `convert_to_deployable_form` (one plan or split-batch);
     `frame_ratios` as for `DevicePacker`; `video` is the decoder's uint8 [N,H,W,3] (`src_layout="NTHWC"`) or a uint8 / fp32
-    [C,N,H,W] ("NCTHW").  The frame table is built, range-checked and uploaded on EVERY call (one video per call); to score
+    [C,N,H,W] ("NCTHW") -- or decoder-native YUV 4:2:0, uint8 [N, Hc*3/2, W] with `src_layout` "NV12" / "NV21" / "I420" /
+    "YV12" (`yuv`, `coded_height`, `height` as for `DevicePacker`), read in place with the strides it has and converted by
+    the ingest itself.  The frame table is built, range-checked and uploaded on EVERY call (one video per call); to score
     the same video again without that, keep `packer.video_tables(...)` and drive `packer.fill_video` / `launch` directly.
     After a call `video_ensembler.counts` (and `clip_ensembler.counts`) hold the rows folded."""
 
     def __init__(self, deployed, clip_sampler, mean, std, div255, short_side, crop_size, spatial_idx=(0, 1, 2),
-                 frame_ratios=None, src_layout="NTHWC", method="sum"):
+                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), coded_height=None, height=None):
         if getattr(deployed, "_pv_load_boxes", None) is not None:
-            raise ValueError("VideoPredictor scores videos; a detection model's boxes belong to key frames")
+            raise ValueError("VideoPredictor scores videos; a detection model's boxes belong to key frames"
+                             " (in any source layout, %s included)" % src_layout)
         if method not in ("sum", "max"):
             raise NotImplementedError("ensemble method %r (the reference knows 'sum' and 'max')" % method)
-        self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout)
+        self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout,
+                                   yuv, coded_height, height)
         self.sampler, self.method, self.src_layout = clip_sampler, method, src_layout
         self.video_ensembler = self.clip_ensembler = None
 
@@ -41,15 +45,16 @@ class VideoPredictor:
     def __call__(self, video, fps, return_clip_scores=False):
         p = self.packer
         device = p.sess.device
-        if video.dim() != 4:
-            raise RuntimeError("expected one 4-d %s video, got %s" % (self.src_layout, tuple(video.shape)))
-        num_frames = video.shape[0] if self.src_layout == "NTHWC" else video.shape[1]
+        if video.dim() != (3 if p.is_yuv else 4):
+            raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(video.shape)))
+        num_frames = video.shape[1] if self.src_layout == "NCTHW" else video.shape[0]
         table, _ = clip_frame_table(self.sampler, num_frames, fps, p.clip_frames)
         tables = p.video_tables(table, num_frames)               # the one upload
         video = video.to(device, non_blocking=True)
-        if video.dtype not in (torch.uint8, torch.float32):
-            video = video.float()
-        video = video.contiguous()
+        if not p.is_yuv:                                         # YUV frames are read in place, with the strides they have
+            if video.dtype not in (torch.uint8, torch.float32):
+                video = video.float()
+            video = video.contiguous()
         n_clips, n_views, batch = table.shape[0], len(p.views), p.batch
         total = n_clips * n_views
         clip_of = torch.arange(total, dtype=torch.int32, device=device) // n_views

@@ -15,6 +15,10 @@ The spatial half of the eval protocol -- `short_side_scale` then `uniform_crop` 
 transforms.py:100-121,153-175), with their box variants -- has the same two forms: host mirrors, and
 `DevicePacker(..., short_side=, crop_size=, spatial_idx=)` / `device_scale_crop`, which run it inside the same pass
 (`pv_resample_crop`): the clip may then have any frame size, and one launch per pathway turns it into the crops.
+
+Decoder-native frames -- YUV 4:2:0 as NV12 / NV21 (what a GPU decoder writes) or I420 / YV12 (a CPU decoder's yuv420p) -- are
+a source layout of that same pass (`pv_yuv_views`): `yuv_matrix` composes the conversion, `yuv420_to_rgb` is the host mirror
+of the tap rule, and `device_scale_crop` / `DevicePacker` / `inference.VideoPredictor` take `src_layout="NV12"` and friends.
 """
 import copy
 import math
@@ -173,6 +177,110 @@ class UniformCropVideo(torch.nn.Module):
         return x
 
 
+# --------------------------------------------------------------------------- YUV 4:2:0 sources
+YUV_LAYOUTS = ("NV12", "NV21", "I420", "YV12")
+_YUV_KR_KB = {"bt709": (0.2126, 0.0722), "bt601": (0.299, 0.114)}
+
+
+def yuv_matrix(standard: str = "bt709", full_range: bool = False) -> torch.Tensor:
+    """The 3 x 4 fp64 matrix M with (R, G, B) = M . (Y, U, V, 1) for 8-bit Y'CbCr, RGB in [0, 255]: rows R, G, B, columns
+    Y, U, V and a constant.  Derived from the standard's luma coefficients (Kr, Kb) -- Y' = Kr R' + Kg G' + Kb B',
+    Pb = (B' - Y') / (2 (1 - Kb)), Pr = (R' - Y') / (2 (1 - Kr)) -- and the quantisation: limited range puts Y' in 16..235
+    and Pb, Pr in 16..240 around 128, full range in 0..255 around 128."""
+    if standard not in _YUV_KR_KB:
+        raise ValueError("standard is one of %s, got %r" % (sorted(_YUV_KR_KB), standard))
+    kr, kb = _YUV_KR_KB[standard]
+    kg = 1.0 - kr - kb
+    y_lo, y_span, c_span = (0.0, 255.0, 255.0) if full_range else (16.0, 219.0, 224.0)
+    ys, cs = 255.0 / y_span, 255.0 / c_span
+    m = torch.tensor([[ys, 0.0, 2.0 * (1.0 - kr) * cs],
+                      [ys, -2.0 * kb * (1.0 - kb) / kg * cs, -2.0 * kr * (1.0 - kr) / kg * cs],
+                      [ys, 2.0 * (1.0 - kb) * cs, 0.0]], dtype=torch.float64)
+    const = -(m[:, 0] * y_lo + (m[:, 1] + m[:, 2]) * 128.0)
+    return torch.cat([m, const[:, None]], dim=1)
+
+
+def _yuv_matrix_of(yuv) -> torch.Tensor:
+    """`yuv` as every YUV entry point takes it: (standard, full_range), or an explicit 3 x 4 matrix."""
+    if isinstance(yuv, (tuple, list)) and len(yuv) == 2 and isinstance(yuv[0], str):
+        return yuv_matrix(yuv[0], bool(yuv[1]))
+    m = torch.as_tensor(yuv, dtype=torch.float64).cpu()
+    if tuple(m.shape) != (3, 4):
+        raise ValueError("yuv is (standard, full_range) or a 3 x 4 matrix, got shape %s" % (tuple(m.shape),))
+    return m
+
+
+def yuv_geometry(frames: torch.Tensor, layout: str, coded_height=None, height=None) -> dict:
+    """Where the samples of YUV 4:2:0 frames are, in bytes, read off the tensor's shape and strides (nothing is copied).
+
+    `frames` is uint8 [N, Hc*3/2, W] (a video) or [B, T', Hc*3/2, W] (clips; then N = B * T' and clip b starts at frame
+    b * T'), Hc being the coded height: Hc luma rows, then the chroma.  `height` is the display height Hs <= Hc (default Hc)
+    and `coded_height`, when given, is checked against the shape.  The only stride requirement is stride(-1) == 1: the
+    row pitch P = stride(-2) may exceed W and the frame stride the frame, so a pitched decoder surface is read in place.
+    NV12 / NV21: chroma row j is tensor row Hc + j, U and V (V and U) interleaved.  I420 / YV12: two planes of Hc/2 rows
+    with pitch P/2 behind the luma, U (V) first -- for P == W exactly the contiguous yuv420p frame."""
+    if layout not in YUV_LAYOUTS:
+        raise ValueError("a YUV layout is one of %s, got %r" % (YUV_LAYOUTS, layout))
+    if frames.dim() not in (3, 4) or frames.dtype != torch.uint8:
+        raise RuntimeError("%s frames are uint8 [N, Hc*3/2, W] or [B, T, Hc*3/2, W], got %s %s"
+                           % (layout, frames.dtype, tuple(frames.shape)))
+    rows, w = frames.shape[-2:]
+    hc = rows * 2 // 3
+    if rows == 0 or hc * 3 != rows * 2 or hc % 2 or w % 2 or w == 0:
+        raise RuntimeError("%d x %d is not Hc*3/2 rows of an even width W with an even coded height Hc" % (rows, w))
+    if coded_height is not None and coded_height != hc:
+        raise RuntimeError("coded_height %d, but the frames have %d = %d * 3 / 2 rows" % (coded_height, rows, hc))
+    hs = hc if height is None else int(height)
+    if not 0 < hs <= hc or hs % 2:
+        raise RuntimeError("the display height %d is even and at most the coded height %d" % (hs, hc))
+    pitch = frames.stride(-2)
+    if frames.stride(-1) != 1 or pitch < w:
+        raise RuntimeError("%s frames have stride(-1) == 1 and a row pitch >= W; got strides %s" % (layout, frames.stride()))
+    if frames.dim() == 4 and frames.shape[0] > 1 and frames.shape[1] > 1 and frames.stride(0) != frames.shape[1] * frames.stride(1):
+        raise RuntimeError("clips [B, T, ...] are one sequence of B * T frames: stride(0) == T * stride(1); got %s" % (frames.stride(),))
+    n = frames.shape[0] if frames.dim() == 3 else frames.shape[0] * frames.shape[1]
+    frame_stride = frames.stride(-3) if frames.shape[-3] > 1 else (frames.stride(0) if frames.dim() == 4 and frames.shape[0] > 1 else rows * pitch)
+    if frame_stride < (rows - 1) * pitch + w:
+        raise RuntimeError("frames overlap: frame stride %d for %d rows of pitch %d" % (frame_stride, rows, pitch))
+    first = hc * pitch
+    if layout in ("NV12", "NV21"):
+        c_step, c_pitch = 2, pitch
+        u, v = (first, first + 1) if layout == "NV12" else (first + 1, first)
+    else:
+        if pitch % 2:
+            raise RuntimeError("%s chroma rows have half the luma pitch: the pitch %d must be even" % (layout, pitch))
+        c_step, c_pitch = 1, pitch // 2
+        second = first + (hc // 2) * c_pitch
+        u, v = (first, second) if layout == "I420" else (second, first)
+    return dict(N=n, Hs=hs, Ws=w, Hc=hc, frame_stride=frame_stride, y_pitch=pitch, c_pitch=c_pitch, c_step=c_step,
+                u_offset=u, v_offset=v)
+
+
+def yuv420_to_rgb(frames: torch.Tensor, layout: str, matrix, coded_height=None, height=None) -> torch.Tensor:
+    """The virtual RGB frame `pv_yuv_views` takes its taps from (include/pv_mi355x.h), on the host: fp32 [..., 3, Hs, Ws] with
+    rgb(y, x) = clamp(M . (Y[y][x], U[y >> 1][x >> 1], V[y >> 1][x >> 1], 1), 0, 255), NOT rounded to an integer.  Chroma is
+    replicated over its 2 x 2 luma block.  `frames`, `layout`, `coded_height` and `height` as in `yuv_geometry`; `matrix`
+    is a 3 x 4 matrix (`yuv_matrix`).  The conversion runs in fp64 and is rounded once to fp32."""
+    g = yuv_geometry(frames, layout, coded_height, height)
+    m = torch.as_tensor(matrix, dtype=torch.float64).cpu()
+    if tuple(m.shape) != (3, 4):
+        raise ValueError("matrix is 3 x 4, got %s" % (tuple(m.shape),))
+    frames = frames.cpu() if frames.is_cuda else frames
+    lead, lead_strides = tuple(frames.shape[:-2]), tuple(frames.stride()[:-2])
+    off = frames.storage_offset()
+
+    def plane(rows, cols, pitch, step, start):
+        return torch.as_strided(frames, lead + (rows, cols), lead_strides + (pitch, step), off + start).to(torch.float64)
+
+    y = plane(g["Hs"], g["Ws"], g["y_pitch"], 1, 0)
+    u = plane(g["Hs"] // 2, g["Ws"] // 2, g["c_pitch"], g["c_step"], g["u_offset"])
+    v = plane(g["Hs"] // 2, g["Ws"] // 2, g["c_pitch"], g["c_step"], g["v_offset"])
+    u, v = [c.repeat_interleave(2, -2).repeat_interleave(2, -1) for c in (u, v)]
+    yuv1 = torch.stack([y, u, v, torch.ones_like(y)], dim=-3)                       # [..., 4, Hs, Ws]
+    rgb = torch.einsum("ck,...khw->...chw", m, yuv1)
+    return torch.clamp(rgb, 0.0, 255.0).float()
+
+
 # --------------------------------------------------------------------------- fused device path
 def _affine(mean, std, div255, channels, device):
     """(ch_scale, ch_shift) of Div255 + Normalize as fp32 device tensors, or (None, None)."""
@@ -255,20 +363,76 @@ def pathway_tables(table, pathway_frames, num_frames):
     return [table[:, temporal_indices(t, tp)].to(torch.int32).contiguous() for tp in pathway_frames]
 
 
+def _yuv_desc(frames, geom, table, matrix, short_side, crop_size, views):
+    """A YuvViewsDesc with the source, the frame table, the conversion and the geometry of short_side_scale + uniform_crop
+    filled in (destination, item range and affine map are the caller's).  `frames`, `table` (int32 [n_clips, T]) and
+    `matrix` (fp32 [12]) are on the device and stay alive until the launch has run."""
+    from . import _lib as L
+    hs, ws = geom["Hs"], geom["Ws"]
+    hn, wn = scaled_size(hs, ws, short_side)
+    if crop_size > hn or crop_size > wn:
+        raise RuntimeError("a %d crop does not fit the %d x %d frame scaled to %d x %d" % (crop_size, hs, ws, hn, wn))
+    d = L.YuvViewsDesc()
+    d.src, d.t_index, d.yuv2rgb = frames.data_ptr(), table.data_ptr(), matrix.data_ptr()
+    d.n_clips, d.T, d.N, d.t_stride, d.Hs, d.Ws = table.shape[0], table.shape[1], geom["N"], table.stride(0), hs, ws
+    for k in ("frame_stride", "u_offset", "v_offset", "y_pitch", "c_pitch", "c_step"):
+        setattr(d, k, geom[k])
+    d.Hn, d.Wn, d.Ho, d.Wo, d.n_views = hn, wn, crop_size, crop_size, len(views)
+    for i, v in enumerate(views):
+        d.y_off[i], d.x_off[i] = crop_offsets(hn, wn, crop_size, v)
+    return d
+
+
+def _clip_rows(n_clips, clip_frames, num_frames):
+    """The frame table of B materialised clips of T' frames laid out as one sequence: row b = b * T' + the frames
+    uniform_temporal_subsample picks (int32 [B, num_frames], host)."""
+    idx = temporal_indices(clip_frames, num_frames)
+    return (torch.arange(n_clips)[:, None] * clip_frames + idx[None, :]).to(torch.int32).contiguous()
+
+
+def _device_scale_crop_yuv(frames, short_side, crop_size, views, mean, std, div255, num_frames, dtype, src_layout, yuv,
+                           coded_height, height):
+    import ctypes as C
+    from . import _lib as L
+    device = frames.device if frames.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    frames = frames.to(device, non_blocking=True)
+    geom = yuv_geometry(frames, src_layout, coded_height, height)
+    b, t_src = (1, frames.shape[0]) if frames.dim() == 3 else tuple(frames.shape[:2])
+    table = _clip_rows(b, t_src, num_frames if num_frames is not None else t_src).to(device)
+    matrix = _yuv_matrix_of(yuv).float().reshape(12).to(device)
+    d = _yuv_desc(frames, geom, table, matrix, short_side, crop_size, views)
+    scale, shift = _affine(mean, std, div255, 3, device)
+    if scale is not None:
+        d.ch_scale, d.ch_shift = scale.data_ptr(), shift.data_ptr()
+    out = torch.empty((b * d.n_views, 3, d.T, crop_size, crop_size), dtype=dtype, device=device)
+    d.dst, d.dst_layout = out.data_ptr(), L.DST_NCTHW
+    d.dst_dtype = L.PV_BF16 if dtype == torch.bfloat16 else L.PV_F32
+    with torch.cuda.device(device):
+        L.check(L.lib().pv_yuv_views(C.byref(d), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "yuv_views")
+    return out
+
+
 @torch.no_grad()
 def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std=None, div255=False, num_frames=None,
-                      dtype=torch.bfloat16, src_layout="NCTHW"):
+                      dtype=torch.bfloat16, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None):
     """uniform_crop(short_side_scale(Normalize(Div255(uniform_temporal_subsample(clip, num_frames))))) for every view of
     `spatial_idx` in one launch of `pv_resample_crop`: a planar [B * n_views, C, T, crop, crop] tensor of `dtype` (bf16 or
     fp32) on the GPU, item b * n_views + v being view v of clip b.  `clip` is [B,C,T,H,W] ("NCTHW"; uint8 or float) or the
-    decoder's [B,T,H,W,3] uint8 ("NTHWC")."""
+    decoder's [B,T,H,W,3] uint8 ("NTHWC").
+
+    With `src_layout` "NV12", "NV21", "I420" or "YV12" the clip is decoder-native YUV 4:2:0, uint8 [B, T, Hc*3/2, W] (or
+    [T, Hc*3/2, W]: one clip) with the strides it has (`yuv_geometry`: `coded_height`, `height`), converted tap by tap inside
+    the same launch (`pv_yuv_views`) by `yuv`: (standard, full_range) for `yuv_matrix`, or a 3 x 4 matrix."""
     import ctypes as C
     from . import _lib as L
-    if src_layout not in ("NCTHW", "NTHWC"):
-        raise ValueError("src_layout is 'NCTHW' or 'NTHWC'")
+    if src_layout not in ("NCTHW", "NTHWC") + YUV_LAYOUTS:
+        raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,))
     if dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("dtype is torch.bfloat16 or torch.float32")
     views = _views(spatial_idx)
+    if src_layout in YUV_LAYOUTS:
+        return _device_scale_crop_yuv(clip, short_side, crop_size, views, mean, std, div255, num_frames, dtype, src_layout,
+                                      yuv, coded_height, height)
     _source_geometry(clip, src_layout)
     device = clip.device if clip.is_cuda else torch.device("cuda", torch.cuda.current_device())
     clip = _device_source(clip, device)
@@ -307,30 +471,40 @@ class DevicePacker:
     H == W.  The boxes of a detection model are given in the pixels of the SOURCE frame and follow the clip through
     `short_side_scale_with_boxes` and `uniform_crop_with_boxes` on the host (one view only).
 
+    `src_layout` "NV12" / "NV21" / "I420" / "YV12": the clip is decoder-native YUV 4:2:0, uint8 [B, T, Hc*3/2, W] with the
+    strides it has (`yuv_geometry`; `coded_height`, `height`), or one video [N, Hc*3/2, W] for `fill_video`; `yuv` is
+    (standard, full_range) for `yuv_matrix` or a 3 x 4 matrix.  The ingest converts every tap itself (`pv_yuv_views`): no RGB
+    copy is made, and a pitched decoder surface is read in place.  Classification models only.
+
     `fill_video(video, tables, i0, n)` + `launch()` run the resampling packer on ONE decoded video instead of clips: items
     [i0, i0 + n) of its clips x views sequence, the clips being rows of a frame table (`data.clip_frame_table`, uploaded by
     `video_tables`) that the ingest kernel reads the video through (`pv_video_views`); `inference.VideoPredictor` is the
     loop around it."""
 
     def __init__(self, deployed, mean=None, std=None, div255=False, frame_ratios=None, short_side=None, crop_size=None,
-                 spatial_idx=1, src_layout="NCTHW"):
+                 spatial_idx=1, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None):
         self.subs = None
         if (short_side is None) != (crop_size is None):
             raise ValueError("short_side and crop_size are given together")
-        if src_layout not in ("NCTHW", "NTHWC"):
-            raise ValueError("src_layout is 'NCTHW' or 'NTHWC'")
+        if src_layout not in ("NCTHW", "NTHWC") + YUV_LAYOUTS:
+            raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,))
         self.short_side, self.crop_size, self.src_layout = short_side, crop_size, src_layout
+        self.is_yuv, self.coded_height, self.height = src_layout in YUV_LAYOUTS, coded_height, height
+        if self.is_yuv and (getattr(deployed, "_pv_load_boxes", None) is not None):
+            raise ValueError("a detection model does not take %s frames: its boxes are mapped through the scaling and the crop "
+                             "of an RGB clip on the host, and that path is not built for YUV sources" % src_layout)
         self.views = _views(spatial_idx) if short_side is not None else (1,)
         if short_side is None and src_layout != "NCTHW":
-            raise ValueError("a frame-interleaved clip is read by the resampling path only: give short_side and crop_size")
+            raise ValueError("a frame-interleaved or YUV clip is read by the resampling path only: give short_side and crop_size")
         if hasattr(deployed, "parts") and hasattr(deployed, "_pv_launch"):
             # split-batch deploy form (convert_to_deployable_form(..., streams=k)): one packer per sub-batch fills that
             # sub-plan's input buffers, then ONE launch of the joint graph
             self.model = deployed
-            self.subs = [DevicePacker(p, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout)
-                         for p in deployed.parts]
+            self.subs = [DevicePacker(p, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv,
+                                      coded_height, height) for p in deployed.parts]
             self.sess, self.refs = self.subs[0].sess, self.subs[0].refs
             self.frame_ratios = self.subs[0].frame_ratios
+            self._clip_tables = {}
             return
         inputs = getattr(deployed, "_pv_inputs", None)
         if inputs is None:
@@ -355,6 +529,8 @@ class DevicePacker:
         self.scale, self.shift = _affine(mean, std, div255, self.refs[0].C, self.sess.device)
         self._index = {}
         self._planar = {}
+        self._clip_tables = {}
+        self.yuv_matrix = _yuv_matrix_of(yuv).float().reshape(12).to(self.sess.device) if self.is_yuv else None
 
     def _t_index(self, t_src, ref):
         key = (t_src, ref.T)
@@ -394,6 +570,8 @@ class DevicePacker:
         load_boxes = getattr(self.model, "_pv_load_boxes", None)
         if (bboxes is None) != (load_boxes is None):
             raise RuntimeError("bboxes are given to a detection model and only to a detection model")
+        if self.is_yuv:
+            return self._call_yuv(clip)
         if clip.dim() != 5:
             raise RuntimeError("expected a [B,C,T,H,W] clip, got %s" % (tuple(clip.shape),))
         resample = self.short_side is not None
@@ -425,6 +603,24 @@ class DevicePacker:
             self._fill(clip)
         if load_boxes is not None:
             load_boxes(bboxes)
+        return self.launch()
+
+    def _call_yuv(self, clips):
+        """B materialised YUV clips [B, T', Hc*3/2, W]: the sequence of B * T' frames read through a table whose row b is
+        b * T' + the frames every pathway subsamples -- `fill_video` on that table, then the forward."""
+        if clips.dim() != 4:
+            raise RuntimeError("expected %s clips [B, T, Hc*3/2, W], got %s" % (self.src_layout, tuple(clips.shape),))
+        b, t = clips.shape[:2]
+        if b * len(self.views) != self.batch:
+            raise RuntimeError("deploy form was converted for a batch of %d = clips x views, got %d clips x %d views"
+                               % (self.batch, b, len(self.views)))
+        refs = self.subs[0].refs if self.subs is not None else self.refs
+        for ratio, ref in zip(self.frame_ratios, refs):
+            if t // ratio != ref.T:
+                raise RuntimeError("pathway with frame ratio %d expects %d frames, the clip gives %d" % (ratio, ref.T, t // ratio))
+        if (b, t) not in self._clip_tables:
+            self._clip_tables[(b, t)] = [_clip_rows(b, t, ref.T).to(self.sess.device) for ref in refs]
+        self.fill_video(clips.to(self.sess.device, non_blocking=True), self._clip_tables[(b, t)], 0, self.batch)
         return self.launch()
 
     def _fill(self, clip):
@@ -487,15 +683,22 @@ class DevicePacker:
         clip * n_views + v is view v of the clip whose frames are row `clip` of `tables`, from `video_tables`), one
         pv_video_views launch per pathway (and per sub-plan of a split-batch form): no clip is materialised.  n may be
         smaller than the deploy batch -- the ragged last chunk of a video -- and the rest of the buffers is then zeroed.
-        `video` is [C,N,H,W] ("NCTHW"; uint8 or fp32) or [N,H,W,3] uint8 ("NTHWC"), contiguous and on the device, and must
-        stay alive until the forward has run.  Nothing is launched here but the ingest: run `launch()` next."""
+        `video` is [C,N,H,W] ("NCTHW"; uint8 or fp32) or [N,H,W,3] uint8 ("NTHWC"), contiguous and on the device -- or, for a
+        YUV layout, uint8 [N, Hc*3/2, W] on the device with the strides it has (`yuv_geometry`) -- and must stay alive until
+        the forward has run.  Nothing is launched here but the ingest: run `launch()` next."""
         if self.short_side is None:
             raise RuntimeError("fill_video resamples: construct the packer with short_side and crop_size")
         if getattr(self.model, "_pv_load_boxes", None) is not None:
             raise RuntimeError("a detection model takes boxes of key frames, not a video")
-        c, nf, hs, ws = _video_geometry(video, self.src_layout)
-        if not video.is_cuda or not video.is_contiguous() or video.dtype not in (torch.uint8, torch.float32):
-            raise RuntimeError("the video is a contiguous uint8 or fp32 tensor on the device")
+        if self.is_yuv:
+            if not video.is_cuda:
+                raise RuntimeError("the %s frames are on the device" % self.src_layout)
+            geom = yuv_geometry(video, self.src_layout, self.coded_height, self.height)
+            c, nf, hs, ws = 3, geom["N"], geom["Hs"], geom["Ws"]
+        else:
+            c, nf, hs, ws = _video_geometry(video, self.src_layout)
+            if not video.is_cuda or not video.is_contiguous() or video.dtype not in (torch.uint8, torch.float32):
+                raise RuntimeError("the video is a contiguous uint8 or fp32 tensor on the device")
         if self.src_layout == "NTHWC" and (c != 3 or video.dtype != torch.uint8):
             raise RuntimeError("a frame-interleaved video is uint8 [N,H,W,3], got %s %s" % (video.dtype, tuple(video.shape)))
         hn, wn = scaled_size(hs, ws, self.short_side)
@@ -533,6 +736,15 @@ class DevicePacker:
         """One pv_video_views launch per pathway into this plan's buffers; see Session.video_views for the tail."""
         from . import _lib as L
         self._src = (video, tables)                        # alive until the launch has run
+        if self.is_yuv:
+            geom = yuv_geometry(video, self.src_layout, self.coded_height, self.height)
+            for i, (ref, tab) in enumerate(zip(self.refs, tables)):
+                d = _yuv_desc(video, geom, tab, self.yuv_matrix, self.short_side, self.crop_size, self.views)
+                d.item0, d.n_items = (item0, n_items) if n_items else (0, 0)
+                if self.scale is not None:
+                    d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
+                self.sess.yuv_views(d, ref, planar=self._planar_for(i, ref))
+            return
         c, nf, hs, ws = _video_geometry(video, self.src_layout)
         hn, wn = scaled_size(hs, ws, self.short_side)
         for i, (ref, tab) in enumerate(zip(self.refs, tables)):
