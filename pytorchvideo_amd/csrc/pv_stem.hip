@@ -19,6 +19,59 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxPairs = 1024;   // K <= 8192
+constexpr unsigned kOOB = 0x80000000u;   // buffer addressing: an out-of-range offset loads zero / drops the store
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// Rows [row0, row0 + ROWS) of the host-packed [w_rows][K] filter -> LDS [ROWS][Kp + 8] (16 B x odd: conflict-free
+// ds_read_b128), zero-filled past K and past the last packed row.
+template <int ROWS>
+__device__ __forceinline__ void stage_filter_slab(const pv_conv3d_desc& d, bf16_t* w_s, int row0, int w_rows, int K, int Kp) {
+  const bf16_t* __restrict__ Wt = static_cast<const bf16_t*>(d.w);
+  const int cpr = Kp / 8, WLD = Kp + 8;
+  for (int id = threadIdx.x; id < ROWS * cpr; id += kThreads) {
+    const int r = id / cpr, kc = id - r * cpr;
+    bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (row0 + r < w_rows && kc * 8 < K) v = *reinterpret_cast<const bf16x8*>(Wt + (long)(row0 + r) * K + kc * 8);
+    *reinterpret_cast<bf16x8*>(w_s + r * WLD + kc * 8) = v;
+  }
+}
+
+// Tap table of the packed K: voxel pair -> dt | dh << 8 | dw << 16, -1 for the pairs that pad K to a multiple of 32.
+__device__ __forceinline__ void fill_tap_table(int* tab_s, int npairs, int PPR, int kt, int kh) {
+  for (int pi = threadIdx.x; pi < npairs; pi += kThreads) {
+    const int row = pi / PPR, pv = pi - row * PPR;
+    const int dt = row / kh, dh = row - dt * kh;
+    tab_s[pi] = row < kt * kh ? (dt | (dh << 8) | ((2 * pv) << 16)) : -1;
+  }
+}
+
+// Folded BN (or bias) of channel c < cout: the identity where the descriptor has none.
+__device__ __forceinline__ float bn_scale(const pv_conv3d_desc& d, int c) { return d.scale ? d.scale[c] : 1.f; }
+__device__ __forceinline__ float bn_shift(const pv_conv3d_desc& d, int c) { return d.shift ? d.shift[c] : 0.f; }
+// ... of the four channels c0 .. c0+3 a lane holds; 0 / 0 for the pad channels past cout
+__device__ __forceinline__ void load_bn4(const pv_conv3d_desc& d, int c0, float (&sc)[4], float (&sh)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool ok = c0 + j < d.cout;
+    sc[j] = ok ? bn_scale(d, c0 + j) : 0.f;
+    sh[j] = ok ? bn_shift(d, c0 + j) : 0.f;
+  }
+}
+
+// The epilogue of four channels c0 .. c0+3, always in this order: affine -> activation -> [position tables, added by the
+// caller] -> zero the pad channels -> round.  The store (fp32 / bf16, plain / buffer) is the caller's.
+__device__ __forceinline__ void ep_affine_act(float (&v)[4], const f32x4& acc, const float (&sc)[4], const float (&sh)[4], int act) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = acc[j] * sc[j] + sh[j];
+  pv_apply_act_n<true>(v, act);
+}
+__device__ __forceinline__ void ep_zero_pad(float (&v)[4], int c0, int cout) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (c0 + j >= cout) v[j] = 0.f;
+}
+__device__ __forceinline__ bf16x4 ep_round(const float (&v)[4]) { return bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]}; }
 
 // JP = 2 (c4_wpair): an MFMA column is a PAIR of W-adjacent outputs whose filters -- the same taps shifted
 // by the stride -- occupy rows [0,8) and [8,16) of one filter tile; for an 8-channel layer (SlowFast's
@@ -27,7 +80,7 @@ template <int NT, int TM, int JP = 1>
 __global__ __launch_bounds__(kThreads) void stem_c4_kernel(const pv_conv3d_desc d, int ksteps, int ngroups) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int Kp = ksteps * 32;
-  const int WLD = Kp + 8;   // 16 B x odd: conflict-free ds_read_b128
+  const int WLD = Kp + 8;
   bf16_t* w_s = reinterpret_cast<bf16_t*>(smem_raw);
   int* tab_s = reinterpret_cast<int*>(smem_raw + (size_t)NT * 16 * WLD * 2);   // [ksteps*4] pair -> (dt, dh, dw)
 
@@ -46,28 +99,13 @@ __global__ __launch_bounds__(kThreads) void stem_c4_kernel(const pv_conv3d_desc 
   const int n0 = blockIdx.y * NT * 16;
   const int w_rows = JP == 1 ? d.cout : JP * pv_round_up(d.cout, 8);   // filter rows the host packed
 
-  {
-    const bf16_t* __restrict__ Wt = static_cast<const bf16_t*>(d.w);
-    const int cpr = Kp / 8;
-    for (int id = tid; id < NT * 16 * cpr; id += kThreads) {
-      const int r = id / cpr, kc = id - r * cpr;
-      bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (n0 + r < w_rows && kc * 8 < K) v = *reinterpret_cast<const bf16x8*>(Wt + (long)(n0 + r) * K + kc * 8);
-      *reinterpret_cast<bf16x8*>(w_s + r * WLD + kc * 8) = v;
-    }
-    for (int pi = tid; pi < npairs; pi += kThreads) {
-      const int row = pi / PPR, pv = pi - row * PPR;
-      const int dt = row / d.kh, dh = row - dt * d.kh;
-      tab_s[pi] = row < d.kt * d.kh ? (dt | (dh << 8) | ((2 * pv) << 16)) : -1;
-    }
-  }
+  stage_filter_slab<NT * 16>(d, w_s, n0, w_rows, K, Kp);
+  fill_tap_table(tab_s, npairs, PPR, d.kt, d.kh);
   __syncthreads();
 
   // buffer descriptor over the whole input (31-bit byte offsets, checked on the host)
-  constexpr unsigned kOOB = 0x80000000u;
   __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(d.x), 0, (int)((unsigned)d.B * (unsigned)d.x_bs * 2u), 0x00020000);
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
   for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
     const long m_base = ((long)g * 4 + wave) * (TM * 16);
@@ -124,7 +162,6 @@ __global__ __launch_bounds__(kThreads) void stem_c4_kernel(const pv_conv3d_desc 
         const bf16x8 wf = *reinterpret_cast<const bf16x8*>(w_s + (a * 16 + n16) * WLD + ks * 32 + q * 8);
 #pragma unroll
         for (int t = 0; t < TM; ++t) {
-          typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
           const u32x4 u = {src[t][0][0], src[t][0][1], src[t][1][0], src[t][1][1]};
           acc[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(bf16x8, u), acc[a][t], 0, 0, 0);
         }
@@ -144,24 +181,14 @@ __global__ __launch_bounds__(kThreads) void stem_c4_kernel(const pv_conv3d_desc 
       // ---- epilogue, paired columns: rows 4q..4q+3 of the tile = channels 4(q&1)..+3 of output j = q>>1 ----
       const int co0 = 4 * (q & 1), j = q >> 1;
       float sc[4], sh[4];
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const bool ok = co0 + jj < d.cout;
-        sc[jj] = ok ? (d.scale ? d.scale[co0 + jj] : 1.f) : 0.f;
-        sh[jj] = ok ? (d.shift ? d.shift[co0 + jj] : 0.f) : 0.f;
-      }
+      load_bn4(d, co0, sc, sh);
 #pragma unroll
       for (int t = 0; t < TM; ++t) {
         if (!vok[t] || vwo[t] + j >= d.Wo) continue;
         float v[4];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) v[jj] = acc[0][t][jj] * sc[jj] + sh[jj];
-        pv_apply_act_n<true>(v, d.act);
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-          if (co0 + jj >= d.cout) v[jj] = 0.f;
-        const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-        *reinterpret_cast<bf16x4*>(static_cast<bf16_t*>(d.y) + vy[t] + (long)j * d.ldy + co0) = o;
+        ep_affine_act(v, acc[0][t], sc, sh, d.act);
+        ep_zero_pad(v, co0, d.cout);
+        *reinterpret_cast<bf16x4*>(static_cast<bf16_t*>(d.y) + vy[t] + (long)j * d.ldy + co0) = ep_round(v);
       }
       continue;
     }
@@ -171,19 +198,12 @@ __global__ __launch_bounds__(kThreads) void stem_c4_kernel(const pv_conv3d_desc 
       const int c0 = n0 + a * 16 + q * 4;
       if (c0 >= pv_round_up(d.cout, 8)) continue;   // padding channels up to the 8-multiple are written as zeros
       float sc[4], sh[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool ok = c0 + j < d.cout;
-        sc[j] = ok ? (d.scale ? d.scale[c0 + j] : 1.f) : 0.f;
-        sh[j] = ok ? (d.shift ? d.shift[c0 + j] : 0.f) : 0.f;
-      }
+      load_bn4(d, c0, sc, sh);
 #pragma unroll
       for (int t = 0; t < TM; ++t) {
         if (!vok[t]) continue;
         float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = acc[a][t][j] * sc[j] + sh[j];
-        pv_apply_act_n<true>(v, d.act);
+        ep_affine_act(v, acc[a][t], sc, sh, d.act);
         if (d.pos_spatial != nullptr) {   // position tables of the token stream (fp32 [rows][cout]); wave-uniform branch
 #pragma unroll
           for (int j = 0; j < 4; ++j)
@@ -192,15 +212,9 @@ __global__ __launch_bounds__(kThreads) void stem_c4_kernel(const pv_conv3d_desc 
               if (d.pos_temporal != nullptr) v[j] += d.pos_temporal[(long)vpt[t] * d.cout + c0 + j];
             }
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (c0 + j >= d.cout) v[j] = 0.f;
-        if (d.y_f32) {
-          *reinterpret_cast<f32x4*>(static_cast<float*>(d.y) + vy[t] + c0) = f32x4{v[0], v[1], v[2], v[3]};
-        } else {
-          const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-          *reinterpret_cast<bf16x4*>(static_cast<bf16_t*>(d.y) + vy[t] + c0) = o;
-        }
+        ep_zero_pad(v, c0, d.cout);
+        if (d.y_f32) *reinterpret_cast<f32x4*>(static_cast<float*>(d.y) + vy[t] + c0) = f32x4{v[0], v[1], v[2], v[3]};
+        else *reinterpret_cast<bf16x4*>(static_cast<bf16_t*>(d.y) + vy[t] + c0) = ep_round(v);
       }
     }
   }
@@ -225,6 +239,41 @@ template <int NT, int TM, int JP = 1> int launch_stem(const pv_conv3d_desc& d, i
 
 
 // ---------------------------------------------------------------------------------------
+// Halo-tile staging of the two LDS-tiled kernels below.  Thread tid owns voxels i = tid + n * NTHR of the IH x IW input
+// tile whose corner is (hi0, wi0) of clip b -- the same voxels in every frame, so the geometry is computed once.  Voxels
+// outside the image and whole frames outside the clip (the conv's temporal zero padding) are read at an out-of-range
+// offset, i.e. as zeros.
+template <int IH, int IW, int NTHR>
+struct HaloStage {
+  static constexpr int NVOX = IH * IW;
+  static constexpr int NLD = (NVOX + NTHR - 1) / NTHR;   // 8-byte loads per thread per frame
+  __amdgpu_buffer_rsrc_t rx;
+  unsigned frame_bytes, g_off[NLD];
+  int Ti;
+  __device__ __forceinline__ HaloStage(const pv_conv3d_desc& d, int b, int hi0, int wi0) {
+    const bf16_t* X = static_cast<const bf16_t*>(d.x) + (long)b * d.x_bs;
+    frame_bytes = (unsigned)(d.Hi * d.Wi) * 8u;
+    rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(X), 0, (int)(frame_bytes * (unsigned)d.Ti), 0x00020000);
+    Ti = d.Ti;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int n = 0; n < NLD; ++n) {
+      const int i = tid + n * NTHR;
+      const int ir = i / IW, ic = i - ir * IW;
+      const int hi = hi0 + ir, wi = wi0 + ic;
+      const bool ok = i < NVOX && (unsigned)hi < (unsigned)d.Hi && (unsigned)wi < (unsigned)d.Wi;
+      g_off[n] = ok ? (unsigned)(hi * d.Wi + wi) * 8u : kOOB;
+    }
+  }
+  __device__ __forceinline__ void load(int ti, u32x2 (&st)[NLD]) const {
+    const bool live = (unsigned)ti < (unsigned)Ti;
+#pragma unroll
+    for (int n = 0; n < NLD; ++n)
+      st[n] = __builtin_amdgcn_raw_buffer_load_b64(rx, (int)((live && g_off[n] != kOOB) ? g_off[n] + (unsigned)ti * frame_bytes : kOOB), 0, 0);
+  }
+};
+
+// ---------------------------------------------------------------------------------------
 // 7 x 7 / stride-2 stems with the input tile in LDS: SlowFast's slow (1,7,7) and fast (5,7,7) stems
 // (models/slowfast.py:209-229 -> models/stem.py:80-107).
 //
@@ -246,9 +295,9 @@ __global__ __launch_bounds__(kThreads) void stem7_kernel(const pv_conv3d_desc d,
   constexpr int TH = 8, TW = TM * 16;
   constexpr int IH = (TH - 1) * 2 + 7;       // 21 input rows
   constexpr int IW = (TW - 1) * 2 + 8;       // 70 input columns (even: 16-byte chunks = voxel pairs)
-  constexpr int NVOX = IH * IW;
+  typedef HaloStage<IH, IW, kThreads> Halo;
+  constexpr int NVOX = Halo::NVOX, NLD = Halo::NLD;
   constexpr int FRAME = NVOX * 4;            // bf16 elements per staged frame
-  constexpr int NLD = (NVOX + kThreads - 1) / kThreads;
   constexpr int JR = RP == 2 ? 9 : 7;        // A fragments per temporal tap (row offsets of a row pair / dh)
   constexpr int NA = RP == 2 ? 1 : NT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -290,28 +339,9 @@ __global__ __launch_bounds__(kThreads) void stem7_kernel(const pv_conv3d_desc d,
     }
   }
 
-  // ---- staging geometry: thread -> voxels of the halo tile (fixed for the whole clip) ----
-  constexpr unsigned kOOB = 0x80000000u;
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  const bf16_t* X = static_cast<const bf16_t*>(d.x) + (long)b * d.x_bs;
-  const unsigned frame_bytes = (unsigned)(d.Hi * d.Wi) * 8u;
-  __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(X), 0, (int)(frame_bytes * (unsigned)d.Ti), 0x00020000);
-  unsigned g_off[NLD];
-#pragma unroll
-  for (int n = 0; n < NLD; ++n) {
-    const int i = tid + n * kThreads;
-    const int ir = i / IW, ic = i - ir * IW;
-    const int hi = hi0 + ir, wi = wi0 + ic;
-    const bool ok = i < NVOX && (unsigned)hi < (unsigned)d.Hi && (unsigned)wi < (unsigned)d.Wi;
-    g_off[n] = ok ? (unsigned)(hi * d.Wi + wi) * 8u : kOOB;
-  }
+  const Halo halo(d, b, hi0, wi0);
   u32x2 st[NLD];
-  auto load_frame = [&](int ti) {
-    const bool live = (unsigned)ti < (unsigned)d.Ti;   // frames outside the clip are the conv's temporal zero padding
-#pragma unroll
-    for (int n = 0; n < NLD; ++n)
-      st[n] = __builtin_amdgcn_raw_buffer_load_b64(rx, (int)((live && g_off[n] != kOOB) ? g_off[n] + (unsigned)ti * frame_bytes : kOOB), 0, 0);
-  };
+  auto load_frame = [&](int ti) { halo.load(ti, st); };
   auto slot_of = [&](int ti) { return (ti + 8 * nslot) % nslot; };
   auto store_frame = [&](int ti) {
     bf16_t* dst = ring + (size_t)slot_of(ti) * FRAME;
@@ -323,16 +353,9 @@ __global__ __launch_bounds__(kThreads) void stem7_kernel(const pv_conv3d_desc d,
   };
 
   // ---- epilogue constants ----
-  float sc[RP == 2 ? 1 : NT][4], sh[RP == 2 ? 1 : NT][4];
+  float sc[NA][4], sh[NA][4];
 #pragma unroll
-  for (int a = 0; a < (RP == 2 ? 1 : NT); ++a)
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int c = RP == 2 ? 4 * (q & 1) + jj : a * 16 + 4 * q + jj;
-      const bool ok = c < d.cout;
-      sc[a][jj] = ok ? (d.scale ? d.scale[c] : 1.f) : 0.f;
-      sh[a][jj] = ok ? (d.shift ? d.shift[c] : 0.f) : 0.f;
-    }
+  for (int a = 0; a < NA; ++a) load_bn4(d, RP == 2 ? 4 * (q & 1) : a * 16 + 4 * q, sc[a], sh[a]);
   bf16_t* Y = static_cast<bf16_t*>(d.y) + (long)b * d.y_bs;
   const unsigned y_frame_bytes = (unsigned)(d.Ho * d.Wo * d.ldy) * 2u;
   __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(Y, 0, (int)(y_frame_bytes * (unsigned)d.To), 0x00020000);
@@ -405,16 +428,11 @@ __global__ __launch_bounds__(kThreads) void stem7_kernel(const pv_conv3d_desc d,
       for (int t = 0; t < TM; ++t) {
         const int wo = wo0 + t * 16 + n16;
         float v[4];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) v[jj] = acc[t][jj] * sc[0][jj] + sh[0][jj];
-        pv_apply_act_n<true>(v, d.act);
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-          if (co0 + jj >= d.cout) v[jj] = 0.f;
-        const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+        ep_affine_act(v, acc[t], sc[0], sh[0], d.act);
+        ep_zero_pad(v, co0, d.cout);
         const bool ok = ho < d.Ho && wo < d.Wo && co0 < cout_p8;
         const unsigned off = ok ? (unsigned)to * y_frame_bytes + (unsigned)((ho * d.Wo + wo) * d.ldy + co0) * 2u : kOOB;
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), ry, (int)off, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, ep_round(v)), ry, (int)off, 0, 0);
       }
     } else {
       f32x4 acc[NT][2][TM];
@@ -457,16 +475,11 @@ __global__ __launch_bounds__(kThreads) void stem7_kernel(const pv_conv3d_desc d,
           for (int t = 0; t < TM; ++t) {
             const int wo = wo0 + t * 16 + n16;
             float v[4];
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) v[jj] = acc[a][rr][t][jj] * sc[a][jj] + sh[a][jj];
-            pv_apply_act_n<true>(v, d.act);
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-              if (c0 + jj >= d.cout) v[jj] = 0.f;
-            const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+            ep_affine_act(v, acc[a][rr][t], sc[a], sh[a], d.act);
+            ep_zero_pad(v, c0, d.cout);
             const bool ok = ho < d.Ho && wo < d.Wo && c0 < cout_p8;
             const unsigned off = ok ? (unsigned)to * y_frame_bytes + (unsigned)((ho * d.Wo + wo) * d.ldy + c0) * 2u : kOOB;
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), ry, (int)off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, ep_round(v)), ry, (int)off, 0, 0);
           }
         }
       }
@@ -492,9 +505,9 @@ __global__ __launch_bounds__(NW * 64, 3) void stem_pe_kernel(const pv_conv3d_des
   constexpr int IH = (TH - 1) * S + 7;       // 35 input rows
   constexpr int IW = (TW - 1) * S + 8;       // 68 input columns = 34 voxel pairs
   constexpr int HP = IW / 4;                 // 17 even (or odd) pairs per row
-  constexpr int NVOX = IH * IW;
   constexpr int NTHR = NW * 64;
-  constexpr int NLD = (NVOX + NTHR - 1) / NTHR;   // 8-byte loads per thread per frame
+  typedef HaloStage<IH, IW, NTHR> Halo;
+  constexpr int NVOX = Halo::NVOX, NLD = Halo::NLD;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   // [KT][IH][even pairs 0..16 | odd pairs 0..16][2 voxels][4]: output column n reads pair 2n + q -- with the pairs of
   // one parity stored contiguously the 16 lanes of a ds_read_b128 phase touch 16 consecutive 16-byte chunks (the
@@ -513,32 +526,17 @@ __global__ __launch_bounds__(NW * 64, 3) void stem_pe_kernel(const pv_conv3d_des
   const int ho0 = th * TH, wo0 = tw * TW;
   const int hi0 = ho0 * S - 3, wi0 = wo0 * S - 3, ti0 = to * d.st - d.pt;
 
-  constexpr unsigned kOOB = 0x80000000u;
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  const bf16_t* X = static_cast<const bf16_t*>(d.x) + (long)b * d.x_bs;
-  const unsigned frame_bytes = (unsigned)(d.Hi * d.Wi) * 8u;
-  __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(X), 0, (int)(frame_bytes * (unsigned)d.Ti), 0x00020000);
-  // per-thread staging geometry of one frame (the same for every frame): global byte offset, LDS element index
-  unsigned g_off[NLD];
-  int l_idx[NLD];
+  const Halo halo(d, b, hi0, wi0);
+  int l_idx[NLD];   // LDS element index of each staged voxel (the parity permutation above)
 #pragma unroll
   for (int n = 0; n < NLD; ++n) {
     const int i = tid + n * NTHR;
     const int ir = i / IW, ic = i - ir * IW;
-    const int hi = hi0 + ir, wi = wi0 + ic;
-    const bool ok = i < NVOX && (unsigned)hi < (unsigned)d.Hi && (unsigned)wi < (unsigned)d.Wi;
-    g_off[n] = ok ? (unsigned)(hi * d.Wi + wi) * 8u : kOOB;
     const int pr = ic >> 1;
     l_idx[n] = i < NVOX ? ((ir * (IW / 2) + (pr & 1) * HP + (pr >> 1)) * 2 + (ic & 1)) * 4 : -1;
   }
   u32x2 st[2][NLD];   // two frames in flight
-  auto load_frame = [&](int fr) {
-    const int ti = ti0 + fr;
-    const bool live = (unsigned)ti < (unsigned)d.Ti;
-#pragma unroll
-    for (int n = 0; n < NLD; ++n)
-      st[fr & 1][n] = __builtin_amdgcn_raw_buffer_load_b64(rx, (int)((live && g_off[n] != kOOB) ? g_off[n] + (unsigned)ti * frame_bytes : kOOB), 0, 0);
-  };
+  auto load_frame = [&](int fr) { halo.load(ti0 + fr, st[fr & 1]); };
   auto store_frame = [&](int fr) {
 #pragma unroll
     for (int n = 0; n < NLD; ++n)
@@ -592,12 +590,7 @@ __global__ __launch_bounds__(NW * 64, 3) void stem_pe_kernel(const pv_conv3d_des
   const int wo = wo0 + n16;
   if (c0 >= pv_round_up(d.cout, 8) || wo >= d.Wo) return;
   float sc[4], sh[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const bool ok = c0 + j < d.cout;
-    sc[j] = ok ? (d.scale ? d.scale[c0 + j] : 1.f) : 0.f;
-    sh[j] = ok ? (d.shift ? d.shift[c0 + j] : 0.f) : 0.f;
-  }
+  load_bn4(d, c0, sc, sh);
   // every position-table value of the tile is requested BEFORE the first store: the compiler cannot prove that y does
   // not alias the tables and would otherwise wait for each row's loads behind the previous row's store (8 round trips)
   float pos[TH][4];
@@ -626,21 +619,13 @@ __global__ __launch_bounds__(NW * 64, 3) void stem_pe_kernel(const pv_conv3d_des
     const int ho = ho0 + r;
     if (ho >= d.Ho) break;
     float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = acc[r][j] * sc[j] + sh[j];
-    pv_apply_act_n<true>(v, d.act);
+    ep_affine_act(v, acc[r], sc, sh, d.act);
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] += pos[r][j];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (c0 + j >= d.cout) v[j] = 0.f;
+    ep_zero_pad(v, c0, d.cout);
     const long yo = (long)b * d.y_bs + (((long)to * d.Ho + ho) * d.Wo + wo) * d.ldy + c0;
-    if (d.y_f32) {
-      *reinterpret_cast<f32x4*>(static_cast<float*>(d.y) + yo) = f32x4{v[0], v[1], v[2], v[3]};
-    } else {
-      const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-      *reinterpret_cast<bf16x4*>(static_cast<bf16_t*>(d.y) + yo) = o;
-    }
+    if (d.y_f32) *reinterpret_cast<f32x4*>(static_cast<float*>(d.y) + yo) = f32x4{v[0], v[1], v[2], v[3]};
+    else *reinterpret_cast<bf16x4*>(static_cast<bf16_t*>(d.y) + yo) = ep_round(v);
   }
 }
 
@@ -707,12 +692,106 @@ template <int RP, int NT, int TM, int KT = 0> int launch_stem7(const pv_conv3d_d
 // loop is unrolled DK-fold), so "rotating" the ring costs no moves.
 template <int V> struct IntC { static constexpr int value = V; };
 
+// Constant e of channel c of the fused temporal stage: e < DK = temporal tap e, e = DK = folded-BN scale, e = DK + 1 =
+// shift; 0 for the pad channels past cout.
+template <int DK> __device__ __forceinline__ float dwt_const(const pv_conv3d_desc& d, int e, int c) {
+  const bool ok = c < d.cout;
+  return !ok ? 0.f : e < DK ? d.dwt_w[e * pv_round_up(d.cout, 8) + c] : e == DK ? bn_scale(d, c) : bn_shift(d, c);
+}
+
+// Where a lane's outputs go: buffer descriptor over y, byte offsets of its clip, of one frame, and of (voxel i, channel
+// 4q) inside a frame (kOOB: no such voxel).
+template <int TM> struct DwtOut {
+  __amdgpu_buffer_rsrc_t ry;
+  unsigned clip, frame, yo[TM];
+  __device__ __forceinline__ DwtOut(const pv_conv3d_desc& d, int b) {
+    ry = __builtin_amdgcn_make_buffer_rsrc(d.y, 0, (int)((unsigned)d.B * (unsigned)d.y_bs * 2u), 0x00020000);
+    clip = (unsigned)b * (unsigned)d.y_bs * 2u;
+    frame = (unsigned)(d.Ho * d.Wo * d.ldy) * 2u;
+  }
+};
+
+// The register ring shared by the two X3D stem kernels below, which differ only in how frame t of conv_xy gets into h.
+// `ep(e, a)` returns constant e (dwt_const) of this lane's channels a*16 + 4q .. +3: from registers in one kernel, from
+// LDS in the other.  Every method takes R = t mod DK as a type, so every ring index is a compile-time constant.
+template <int DK, int NT, int TM, int ACT>
+struct DwtRing {
+  static constexpr int HALF = DK / 2;
+  f32x4 ring[DK][NT][TM];
+
+  __device__ __forceinline__ DwtRing() {
+#pragma unroll
+    for (int k = 0; k < DK; ++k)
+#pragma unroll
+      for (int a = 0; a < NT; ++a)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) ring[k][a][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+
+  // frame t feeds output t + HALF - k with tap k
+  template <int R, class Ep>
+  __device__ __forceinline__ void scatter(IntC<R>, const f32x4 (&h)[NT][TM], const Ep& ep) {
+#pragma unroll
+    for (int k = 0; k < DK; ++k) {
+      f32x4 (&part)[NT][TM] = ring[(R + HALF - k + DK) % DK];
+#pragma unroll
+      for (int a = 0; a < NT; ++a)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) part[a][i] += ep(k, a) * h[a][i];
+    }
+  }
+
+  // output t - HALF is complete after frame t: BN, activation, store; its ring slot is recycled for output t + HALF + 1
+  // (also for the "outputs" before the first frame, which only exist as garbage in the ring)
+  template <int R, class Ep>
+  __device__ __forceinline__ void emit(IntC<R>, const pv_conv3d_desc& d, int t, const DwtOut<TM>& out, const Ep& ep) {
+    const int q = (threadIdx.x & 63) >> 4;
+    const int to = t - HALF;
+    constexpr int slot = (R - HALF + DK) % DK;
+    f32x4 (&done)[NT][TM] = ring[slot];
+    if (to >= 0 && to < d.To) {
+      const unsigned fb = out.clip + (unsigned)to * out.frame;
+#pragma unroll
+      for (int a = 0; a < NT; ++a) {
+        const bool cok = a * 16 + q * 4 < pv_round_up(d.cout, 8);   // padding channels up to the 8-multiple are written as zeros
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          f32x4 v = done[a][i] * ep(DK, a) + ep(DK + 1, a);
+          if (ACT == PV_ACT_RELU) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+          }
+          const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+          const unsigned off = cok ? out.yo[i] + a * 32u + fb : kOOB;   // kOOB + anything stays out of range
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), out.ry, (int)off, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < NT; ++a)
+#pragma unroll
+      for (int i = 0; i < TM; ++i) done[a][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+
+  // the walk over T, unrolled DK-fold: step(IntC<t mod DK>, t) for t = 0 .. Ti + HALF - 1 (and up to DK - 1 empty steps)
+  template <class Step> static __device__ __forceinline__ void walk(int Ti, const Step& step) {
+    for (int t0 = 0; t0 < Ti + HALF; t0 += DK) {
+      step(IntC<0>{}, t0);
+      step(IntC<1>{}, t0 + 1);
+      step(IntC<2>{}, t0 + 2);
+      if (DK > 3) {
+        step(IntC<3 % DK>{}, t0 + 3);
+        step(IntC<4 % DK>{}, t0 + 4);
+      }
+    }
+  }
+};
+
 template <int NT, int TM, int KS, int DK, int ACT>
 __global__ __launch_bounds__(kThreads) void stem_c4_dwt_kernel(const pv_conv3d_desc d, int groups_per_clip) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int Kp = KS * 32;
   constexpr int WLD = Kp + 8;
-  constexpr int HALF = DK / 2;
   bf16_t* w_s = reinterpret_cast<bf16_t*>(smem_raw);
   int* tab_s = reinterpret_cast<int*>(smem_raw + (size_t)NT * 16 * WLD * 2);
 
@@ -724,43 +803,25 @@ __global__ __launch_bounds__(kThreads) void stem_c4_dwt_kernel(const pv_conv3d_d
   const int PPR = KWP / 2;
   const int K = d.kh * KWP * 4;
   const int S_sp = d.Ho * d.Wo;
-  const int cout_p8 = pv_round_up(d.cout, 8);
   const int b = blockIdx.x / groups_per_clip, g = blockIdx.x - b * groups_per_clip;
 
-  {
-    const bf16_t* __restrict__ Wt = static_cast<const bf16_t*>(d.w);
-    constexpr int cpr = Kp / 8;
-    for (int id = tid; id < NT * 16 * cpr; id += kThreads) {
-      const int r = id / cpr, kc = id - r * cpr;
-      bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (r < d.cout && kc * 8 < K) v = *reinterpret_cast<const bf16x8*>(Wt + (long)r * K + kc * 8);
-      *reinterpret_cast<bf16x8*>(w_s + r * WLD + kc * 8) = v;
-    }
-    for (int pi = tid; pi < KS * 4; pi += kThreads) {
-      const int dh = pi / PPR, pv = pi - dh * PPR;
-      tab_s[pi] = dh < d.kh ? ((dh << 8) | ((2 * pv) << 16)) : -1;
-    }
-  }
+  stage_filter_slab<NT * 16>(d, w_s, 0, d.cout, K, Kp);
+  fill_tap_table(tab_s, KS * 4, PPR, 1, d.kh);
   __syncthreads();
 
-  constexpr unsigned kOOB = 0x80000000u;
   __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(d.x), 0, (int)((unsigned)d.B * (unsigned)d.x_bs * 2u), 0x00020000);
-  __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-      d.y, 0, (int)((unsigned)d.B * (unsigned)d.y_bs * 2u), 0x00020000);
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
   // ---- this lane's voxels (fixed for the whole clip) and their load / store offsets inside a frame ----
   unsigned xo[TM][KS][2];   // byte offset of the two 8-byte halves of each k-step's fragment, or kOOB
-  unsigned yo[TM];          // byte offset of (voxel, channel 4q) inside an output frame, or kOOB
+  DwtOut<TM> out(d, b);
 #pragma unroll
   for (int t = 0; t < TM; ++t) {
     const int sp = ((g * 4 + wave) * TM + t) * 16 + n16;
     const bool vok = sp < S_sp;
     const int ho = sp / d.Wo, wo = sp - ho * d.Wo;
     const int h0 = ho * d.sh - d.ph, w0 = wo * d.sw - d.pw;
-    yo[t] = vok ? (unsigned)(sp * d.ldy + q * 4) * 2u : kOOB;
+    out.yo[t] = vok ? (unsigned)(sp * d.ldy + q * 4) * 2u : kOOB;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int tp = tab_s[ks * 4 + q];
@@ -774,22 +835,24 @@ __global__ __launch_bounds__(kThreads) void stem_c4_dwt_kernel(const pv_conv3d_d
       }
     }
   }
-  const unsigned x_frame = (unsigned)(d.Hi * d.Wi * 4) * 2u, y_frame = (unsigned)(S_sp * d.ldy) * 2u;
-  const unsigned x_clip = (unsigned)b * (unsigned)d.x_bs * 2u, y_clip = (unsigned)b * (unsigned)d.y_bs * 2u;
+  const unsigned x_frame = (unsigned)(d.Hi * d.Wi * 4) * 2u, x_clip = (unsigned)b * (unsigned)d.x_bs * 2u;
 
-  // ---- temporal taps, folded BN: channels a*16 + 4q .. +3 ----
-  f32x4 wt[DK][NT], sc[NT], sh[NT];
+  // ---- temporal taps, folded BN scale, shift of channels a*16 + 4q .. +3, in registers: ep_r[e][a], e as in dwt_const
+  //      (scale and shift through load_bn4: one bounds test per channel guards both loads) ----
+  f32x4 ep_r[DK + 2][NT];
 #pragma unroll
-  for (int a = 0; a < NT; ++a)
+  for (int a = 0; a < NT; ++a) {
+    float sc[4], sh[4];
+    load_bn4(d, a * 16 + q * 4, sc, sh);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int c = a * 16 + q * 4 + j;
-      const bool ok = c < d.cout;
-      sc[a][j] = ok ? (d.scale ? d.scale[c] : 1.f) : 0.f;
-      sh[a][j] = ok ? (d.shift ? d.shift[c] : 0.f) : 0.f;
+      ep_r[DK][a][j] = sc[j];
+      ep_r[DK + 1][a][j] = sh[j];
 #pragma unroll
-      for (int k = 0; k < DK; ++k) wt[k][a][j] = ok ? d.dwt_w[k * cout_p8 + c] : 0.f;
+      for (int k = 0; k < DK; ++k) ep_r[k][a][j] = dwt_const<DK>(d, k, a * 16 + q * 4 + j);
     }
+  }
+  auto ep = [&](int e, int a) { return ep_r[e][a]; };
 
   u32x2 xr[TM][KS][2];
   auto load_frame = [&](int t) {
@@ -803,16 +866,8 @@ __global__ __launch_bounds__(kThreads) void stem_c4_dwt_kernel(const pv_conv3d_d
           xr[i][ks][e] = __builtin_amdgcn_raw_buffer_load_b64(rx, (int)(xo[i][ks][e] + fb), 0, 0);   // kOOB + fb stays out of range
   };
 
-  f32x4 ring[DK][NT][TM];
-#pragma unroll
-  for (int k = 0; k < DK; ++k)
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-      for (int i = 0; i < TM; ++i) ring[k][a][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  auto step = [&](auto Rc, int t) {
-    constexpr int R = decltype(Rc)::value;   // t mod DK
+  DwtRing<DK, NT, TM, ACT> ring;
+  auto step = [&](auto Rc, int t) {   // Rc: IntC<t mod DK>
     if (t < d.Ti) {
       f32x4 h[NT][TM];
 #pragma unroll
@@ -831,54 +886,24 @@ __global__ __launch_bounds__(kThreads) void stem_c4_dwt_kernel(const pv_conv3d_d
           }
         }
       if (t + 1 < d.Ti) load_frame(t + 1);   // next frame's loads fly under this frame's FMAs and stores
-      // frame t feeds output t + HALF - k with tap k
-#pragma unroll
-      for (int k = 0; k < DK; ++k) {
-        const int slot = (R + HALF - k + DK) % DK;
-#pragma unroll
-        for (int a = 0; a < NT; ++a)
-#pragma unroll
-          for (int i = 0; i < TM; ++i) ring[slot][a][i] += wt[k][a] * h[a][i];
-      }
+      ring.scatter(Rc, h, ep);
     }
-    // output t - HALF is complete after frame t; its ring slot is recycled for output t + HALF + 1
-    // (also for the "outputs" before the first frame, which only exist as garbage in the ring)
-    const int to = t - HALF;
-    constexpr int slot = (R - HALF + DK) % DK;
-    if (to >= 0 && to < d.To) {
-      const unsigned fb = y_clip + (unsigned)to * y_frame;
-#pragma unroll
-      for (int a = 0; a < NT; ++a) {
-        const bool cok = a * 16 + q * 4 < cout_p8;   // padding channels up to the 8-multiple are written as zeros
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          f32x4 v = ring[slot][a][i] * sc[a] + sh[a];
-          if (ACT == PV_ACT_RELU) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-          }
-          const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-          const unsigned off = cok ? yo[i] + a * 32u + fb : kOOB;   // kOOB + anything stays out of range
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), ry, (int)off, 0, 0);
-        }
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-      for (int i = 0; i < TM; ++i) ring[slot][a][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    ring.emit(Rc, d, t, out, ep);
   };
 
   load_frame(0);
-  for (int t0 = 0; t0 < d.Ti + HALF; t0 += DK) {
-    step(IntC<0>{}, t0);
-    step(IntC<1>{}, t0 + 1);
-    step(IntC<2>{}, t0 + 2);
-    if (DK > 3) {
-      step(IntC<3 % DK>{}, t0 + 3);
-      step(IntC<4 % DK>{}, t0 + 4);
-    }
-  }
+  ring.walk(d.Ti, step);
+}
+
+// The ring kernels take the activation as a template constant: launch the RELU or the NONE instantiation (the only two
+// pv_stem_dwt_supported admits).
+template <class... P, class... A>
+int launch_relu_or_none(const char* name, int act, void (*relu)(P...), void (*none)(P...), dim3 grid, size_t lds, hipStream_t s, A... args) {
+  auto kern = act == PV_ACT_RELU ? relu : none;
+  PV_LAUNCH(kern, grid, dim3(kThreads), lds, s, args...);
+  pv_note_kernel(name);   // (launched through a function pointer: PV_LAUNCH saw only the variable)
+  PV_LAUNCH_CHECK();
+  return PV_OK;
 }
 
 template <int NT, int TM, int KS, int DK> int launch_stem_dwt(const pv_conv3d_desc& d, hipStream_t s) {
@@ -886,11 +911,8 @@ template <int NT, int TM, int KS, int DK> int launch_stem_dwt(const pv_conv3d_de
   const long gpc = pv_ceil_div(S_sp, 4 * TM * 16);
   if (gpc * d.B > 0x7fffffffL) return PV_ERR_UNSUPPORTED;
   const size_t lds = (size_t)NT * 16 * (KS * 32 + 8) * 2 + (size_t)KS * 4 * 4;
-  dim3 grid((unsigned)(gpc * d.B)), block(kThreads);
-  if (d.act == PV_ACT_RELU) PV_LAUNCH((stem_c4_dwt_kernel<NT, TM, KS, DK, PV_ACT_RELU>), grid, block, lds, s, d, (int)gpc);
-  else PV_LAUNCH((stem_c4_dwt_kernel<NT, TM, KS, DK, PV_ACT_NONE>), grid, block, lds, s, d, (int)gpc);
-  PV_LAUNCH_CHECK();
-  return PV_OK;
+  return launch_relu_or_none("stem_c4_dwt_kernel", d.act, stem_c4_dwt_kernel<NT, TM, KS, DK, PV_ACT_RELU>,
+                             stem_c4_dwt_kernel<NT, TM, KS, DK, PV_ACT_NONE>, dim3((unsigned)(gpc * d.B)), lds, s, d, (int)gpc);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -928,17 +950,21 @@ __device__ __forceinline__ void stem_dir_body(const pv_conv3d_desc& d, const voi
                                               f32x4* ep_s, int b, int ho0, int wo0) {
   constexpr int NT = 2, TM = 2, KS = 2;
   constexpr int WLD = KS * 32 + 8;
-  constexpr int HALF = DK / 2;
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  constexpr unsigned kOOB = 0x80000000u;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int n16 = lane & 15, q = lane >> 4;
-  const int cout_p8 = pv_round_up(d.cout, 8);
   const int Cs = d.x_src_c;
 
+  // ---- temporal taps, folded BN scale, shift of channels a*16 + 4q .. +3 in LDS: ep_s[(e * NT + a) * 4 + q]
+  //      (56 VGPRs a lane less than in registers: three workgroups per CU instead of two) ----
+  for (int id = tid; id < (DK + 2) * NT * 4; id += kThreads) {
+    const int qq = id & 3, a = (id >> 2) % NT, e = (id >> 2) / NT;
+    f32x4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = dwt_const<DK>(d, e, a * 16 + qq * 4 + j);
+    ep_s[id] = v;
+  }
   // ---- staging task of this thread: row r, chunk c of the halo (threads spread over the four waves) ----
   const int task = lane * 4 + wave;
   const bool has_task = task < kDirTasks;
@@ -1026,40 +1052,17 @@ __device__ __forceinline__ void stem_dir_body(const pv_conv3d_desc& d, const voi
     for (int i = 0; i < TM; ++i)
       boff[i][ks] = ((2 * (2 * wave + i) + (pok ? dh : 0)) * kDirIW + 7 + 2 * n16 + dw) * 4;
   }
-  unsigned yo[TM];
+  DwtOut<TM> out(d, b);
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     const int ho = ho0 + 2 * wave + i, wo = wo0 + n16;
-    yo[i] = (ho < d.Ho && wo < d.Wo) ? (unsigned)((ho * d.Wo + wo) * d.ldy + q * 4) * 2u : kOOB;
+    out.yo[i] = (ho < d.Ho && wo < d.Wo) ? (unsigned)((ho * d.Wo + wo) * d.ldy + q * 4) * 2u : kOOB;
   }
-  __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(d.y, 0, (int)((unsigned)d.B * (unsigned)d.y_bs * 2u), 0x00020000);
-  const unsigned y_frame = (unsigned)(d.Ho * d.Wo * d.ldy) * 2u, y_clip = (unsigned)b * (unsigned)d.y_bs * 2u;
 
-  // ---- temporal taps, folded BN scale, shift of channels a*16 + 4q .. +3 in LDS: ep_s[(e * NT + a) * 4 + q],
-  //      e < DK tap, e = DK scale, e = DK + 1 shift (56 VGPRs a lane less: three workgroups per CU instead of two) ----
-  for (int id = tid; id < (DK + 2) * NT * 4; id += kThreads) {
-    const int qq = id & 3, a = (id >> 2) % NT, e = (id >> 2) / NT;
-    f32x4 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int ch = a * 16 + qq * 4 + j;
-      const bool ok = ch < d.cout;
-      v[j] = !ok ? 0.f : e < DK ? d.dwt_w[e * cout_p8 + ch] : e == DK ? (d.scale ? d.scale[ch] : 1.f) : (d.shift ? d.shift[ch] : 0.f);
-    }
-    ep_s[id] = v;
-  }
   auto ep = [&](int e, int a) { return ep_s[(e * NT + a) * 4 + q]; };
 
-  f32x4 ring[DK][NT][TM];
-#pragma unroll
-  for (int k = 0; k < DK; ++k)
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-      for (int i = 0; i < TM; ++i) ring[k][a][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  auto step = [&](auto Rc, int t) {
-    constexpr int R = decltype(Rc)::value;   // t mod DK
+  DwtRing<DK, NT, TM, ACT> ring;
+  auto step = [&](auto Rc, int t) {   // Rc: IntC<t mod DK>
     if (t < d.Ti) {
       if (t + 1 < d.Ti) load_frame(t + 1);   // in flight under this frame's MFMAs and ring update
       const bf16_t* fr = tiles + (size_t)(t & 1) * kDirFrame;
@@ -1085,78 +1088,29 @@ __device__ __forceinline__ void stem_dir_body(const pv_conv3d_desc& d, const voi
           for (int i = 0; i < TM; ++i) h[a][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, bv[i], h[a][i], 0, 0, 0);
         }
       }
-      // frame t feeds output t + HALF - k with tap k
-#pragma unroll
-      for (int k = 0; k < DK; ++k) {
-        const int slot = (R + HALF - k + DK) % DK;
-#pragma unroll
-        for (int a = 0; a < NT; ++a)
-#pragma unroll
-          for (int i = 0; i < TM; ++i) ring[slot][a][i] += ep(k, a) * h[a][i];
-      }
+      ring.scatter(Rc, h, ep);
     }
     // frame t+1 into the other buffer BEFORE this step's output stores: the wait is then for its loads only, and the
     // stores drain behind the barrier
     if (t + 1 < d.Ti) store_frame((t + 1) & 1);
-    const int to = t - HALF;
-    constexpr int slot = (R - HALF + DK) % DK;
-    if (to >= 0 && to < d.To) {
-      const unsigned fb = y_clip + (unsigned)to * y_frame;
-#pragma unroll
-      for (int a = 0; a < NT; ++a) {
-        const bool cok = a * 16 + q * 4 < cout_p8;   // padding channels up to the 8-multiple are written as zeros
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          f32x4 v = ring[slot][a][i] * ep(DK, a) + ep(DK + 1, a);
-          if (ACT == PV_ACT_RELU) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-          }
-          const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-          const unsigned off = cok ? yo[i] + a * 32u + fb : kOOB;   // kOOB + anything stays out of range
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), ry, (int)off, 0, 0);
-        }
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-      for (int i = 0; i < TM; ++i) ring[slot][a][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    ring.emit(Rc, d, t, out, ep);
     if (t + 1 < d.Ti) __syncthreads();   // uniform; frame t+1 staged, nobody reads buffer t & 1 any more
   };
 
   load_frame(0);
   store_frame(0);
   __syncthreads();
-  for (int t0 = 0; t0 < d.Ti + HALF; t0 += DK) {
-    step(IntC<0>{}, t0);
-    step(IntC<1>{}, t0 + 1);
-    step(IntC<2>{}, t0 + 2);
-    if (DK > 3) {
-      step(IntC<3 % DK>{}, t0 + 3);
-      step(IntC<4 % DK>{}, t0 + 4);
-    }
-  }
+  ring.walk(d.Ti, step);
 }
 
 template <int DK, int ACT>
 __global__ __launch_bounds__(kThreads, 3) void stem_dir_dwt_kernel(const pv_conv3d_desc d, int tiles_h, int tiles_w) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  constexpr int NT = 2, Kp = 64, WLD = Kp + 8;
+  constexpr int NT = 2, Kp = 64;
   bf16_t* w_s = reinterpret_cast<bf16_t*>(smem_raw);
-  bf16_t* tiles = w_s + NT * 16 * WLD;   // [2][kDirIH][kDirIW][4]
+  bf16_t* tiles = w_s + NT * 16 * (Kp + 8);   // [2][kDirIH][kDirIW][4]
   f32x4* ep_s = reinterpret_cast<f32x4*>(tiles + 2 * kDirFrame);   // [DK + 2][NT][4]
-  const int tid = threadIdx.x;
-  {
-    const bf16_t* __restrict__ Wt = static_cast<const bf16_t*>(d.w);
-    constexpr int K = 3 * 4 * 4, cpr = Kp / 8;   // packed [cout][kh = 3][kw 3 -> 4][4]
-    for (int id = tid; id < NT * 16 * cpr; id += kThreads) {
-      const int rr = id / cpr, kc = id - rr * cpr;
-      bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (rr < d.cout && kc * 8 < K) v = *reinterpret_cast<const bf16x8*>(Wt + (long)rr * K + kc * 8);
-      *reinterpret_cast<bf16x8*>(w_s + rr * WLD + kc * 8) = v;
-    }
-  }
+  stage_filter_slab<NT * 16>(d, w_s, 0, d.cout, 3 * 4 * 4, Kp);   // packed [cout][kh = 3][kw 3 -> 4][4]
   // (the weights are visible behind the barrier after the first frame is staged)
   int bid = blockIdx.x;
   const int tw = bid % tiles_w; bid /= tiles_w;
@@ -1177,11 +1131,8 @@ template <int DK> int launch_stem_dir(const pv_conv3d_desc& d, hipStream_t s) {
   const long blocks = (long)d.B * tiles_h * tiles_w;
   if (blocks > 0x7fffffffL) return PV_ERR_UNSUPPORTED;
   const size_t lds = (size_t)2 * 16 * (64 + 8) * 2 + (size_t)2 * kDirFrame * 2 + (size_t)(DK + 2) * 2 * 4 * 16;
-  dim3 grid((unsigned)blocks), block(kThreads);
-  if (d.act == PV_ACT_RELU) PV_LAUNCH((stem_dir_dwt_kernel<DK, PV_ACT_RELU>), grid, block, lds, s, d, tiles_h, tiles_w);
-  else PV_LAUNCH((stem_dir_dwt_kernel<DK, PV_ACT_NONE>), grid, block, lds, s, d, tiles_h, tiles_w);
-  PV_LAUNCH_CHECK();
-  return PV_OK;
+  return launch_relu_or_none("stem_dir_dwt_kernel", d.act, stem_dir_dwt_kernel<DK, PV_ACT_RELU>, stem_dir_dwt_kernel<DK, PV_ACT_NONE>,
+                             dim3((unsigned)blocks), lds, s, d, tiles_h, tiles_w);
 }
 
 }  // namespace
@@ -1234,15 +1185,19 @@ int pv_stem_c4(const pv_conv3d_desc& d, hipStream_t s) {
   }
   if (ksteps * 4 > kMaxPairs || d.kt > 255 || d.kh > 255 || d.kw > 255) return PV_ERR_UNSUPPORTED;
   const int cout_p8 = pv_round_up(d.cout, 8);
-  if (const int nw = pv_tune("stem_pe", 1) ? stem_pe_waves(d) : 0) {   // 7 x 7 / stride 4: filter in registers, tile in LDS
-#define PV_PE(KT_)                                                              \
-    (nw == 6 ? launch_stem_pe<KT_, 6>(d, KWP * 4, s) : nw == 4 ? launch_stem_pe<KT_, 4>(d, KWP * 4, s) \
-             : launch_stem_pe<KT_, 8>(d, KWP * 4, s))
-    const int r = d.kt == 3 ? PV_PE(3) : PV_PE(1);
-#undef PV_PE
+  if (const int nw = stem_pe_waves(d)) {   // 7 x 7 / stride 4: filter in registers, tile in LDS
+    int r = PV_ERR_UNSUPPORTED;
+    switch (d.kt * 10 + nw) {   // kt 1 or 3, 4 / 6 / 8 waves (stem_pe_waves)
+      case 14: r = launch_stem_pe<1, 4>(d, KWP * 4, s); break;
+      case 16: r = launch_stem_pe<1, 6>(d, KWP * 4, s); break;
+      case 18: r = launch_stem_pe<1, 8>(d, KWP * 4, s); break;
+      case 34: r = launch_stem_pe<3, 4>(d, KWP * 4, s); break;
+      case 36: r = launch_stem_pe<3, 6>(d, KWP * 4, s); break;
+      case 38: r = launch_stem_pe<3, 8>(d, KWP * 4, s); break;
+    }
     if (r != PV_ERR_UNSUPPORTED) return r;
   }
-  if (const int v7 = pv_tune("stem7", 1) ? stem7_variant(d) : 0) {   // 7 x 7 / stride 2: input tiles through LDS
+  if (const int v7 = stem7_variant(d)) {   // 7 x 7 / stride 2: input tiles through LDS
     int r;
     if (v7 == 2 && d.kt == 5) r = launch_stem7<2, 1, 2, 5>(d, KWP * 4, s);   // SlowFast's fast stem
     else if (v7 == 2) r = launch_stem7<2, 1, 2>(d, KWP * 4, s);
@@ -1255,12 +1210,8 @@ int pv_stem_c4(const pv_conv3d_desc& d, hipStream_t s) {
   if (jp == 2) return launch_stem<1, 4, 2>(d, ksteps, s);
   if (cout_p8 <= 16) return launch_stem<1, 4>(d, ksteps, s);
   if (cout_p8 <= 32) return launch_stem<2, 4>(d, ksteps, s);
-  const int mid = pv_tune("stem_mid", 4);
-  if (cout_p8 <= 64) return mid == 2 ? launch_stem<2, 4>(d, ksteps, s) : launch_stem<4, 2>(d, ksteps, s);
-  // wider outputs (MViT's 96 patch-embedding channels) split over blockIdx.y: 48 filter rows per workgroup keep
+  if (cout_p8 <= 64) return launch_stem<4, 2>(d, ksteps, s);
+  // wider outputs (MViT's 96 patch-embedding channels) split over blockIdx.y: 32 filter rows per workgroup keep
   // the LDS-resident filter slab (K up to 672) small enough for two workgroups per CU
-  const int wide = pv_tune("stem_wide", 2);
-  if (wide == 6) return launch_stem<6, 1>(d, ksteps, s);
-  if (wide == 2) return launch_stem<2, 2>(d, ksteps, s);
-  return launch_stem<3, 2>(d, ksteps, s);
+  return launch_stem<2, 2>(d, ksteps, s);
 }

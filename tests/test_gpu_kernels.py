@@ -366,30 +366,57 @@ def test_pointwise_conv_with_se_gate_swish_and_residual(dtype, B, S, K, N, gate,
 
 
 # ------------------------------------------------------------------ first-layer conv on the 4-channel layout
-@pytest.mark.parametrize("B,T,H,W,cout,k,s,p,f32out", [
-    (2, 4, 32, 32, 64, (1, 7, 7), (1, 2, 2), (0, 3, 3), False),    # SlowFast slow stem
-    (1, 8, 24, 40, 8, (5, 7, 7), (1, 2, 2), (2, 3, 3), False),     # SlowFast fast stem
-    (2, 4, 18, 22, 24, (1, 3, 3), (1, 2, 2), (0, 1, 1), False),    # X3D stem conv (odd kw: padded pair)
-    (1, 6, 28, 28, 96, (3, 7, 7), (2, 4, 4), (1, 3, 3), True),     # MViT patch embedding (+bias, fp32 out)
-    (1, 3, 9, 11, 20, (3, 2, 4), (1, 1, 3), (1, 0, 2), False),     # odd everything
+_C4_CASES = [   # B, T, H, W, cout, k, s, p, f32out, pos, kernel the library routes it to
+    (2, 4, 32, 32, 64, (1, 7, 7), (1, 2, 2), (0, 3, 3), False, None, "stem7_kernel"),    # SlowFast slow stem
+    (1, 8, 24, 40, 8, (5, 7, 7), (1, 2, 2), (2, 3, 3), False, None, "stem7_kernel"),     # SlowFast fast stem
+    (2, 4, 18, 22, 24, (1, 3, 3), (1, 2, 2), (0, 1, 1), False, None, "stem_c4_kernel"),  # X3D stem conv (odd kw: padded pair)
+    (1, 6, 28, 28, 96, (3, 7, 7), (2, 4, 4), (1, 3, 3), True, None, "stem_pe_kernel"),   # MViT patch embedding (+bias, fp32 out)
+    (1, 3, 9, 11, 20, (3, 2, 4), (1, 1, 3), (1, 0, 2), False, None, "stem_c4_kernel"),   # odd everything
     # 7x7 / stride 2 with the input tile staged in LDS (stem7_kernel): several ragged tiles, frame ring wrapping
-    (1, 9, 70, 150, 64, (1, 7, 7), (1, 2, 2), (0, 3, 3), False),
-    (2, 9, 50, 134, 8, (5, 7, 7), (1, 2, 2), (2, 3, 3), False),
-    (1, 5, 40, 70, 32, (3, 7, 7), (1, 2, 2), (1, 3, 3), False),
-    (1, 3, 21, 37, 6, (7, 7, 7), (1, 2, 2), (3, 3, 3), False),
-    (1, 2, 33, 66, 16, (1, 7, 7), (1, 2, 2), (0, 3, 3), False),
+    (1, 9, 70, 150, 64, (1, 7, 7), (1, 2, 2), (0, 3, 3), False, None, "stem7_kernel"),
+    (2, 9, 50, 134, 8, (5, 7, 7), (1, 2, 2), (2, 3, 3), False, None, "stem7_kernel"),
+    (1, 5, 40, 70, 32, (3, 7, 7), (1, 2, 2), (1, 3, 3), False, None, "stem7_kernel"),
+    (1, 3, 21, 37, 6, (7, 7, 7), (1, 2, 2), (3, 3, 3), False, None, "stem7_kernel"),
+    (1, 2, 33, 66, 16, (1, 7, 7), (1, 2, 2), (0, 3, 3), False, None, "stem7_kernel"),
     # MViT patch embedding geometries on stem_pe_kernel (filter in registers across the waves, input tile in LDS)
-    (2, 5, 30, 50, 96, (3, 7, 7), (2, 4, 4), (1, 3, 3), True),      # ragged tiles, odd T
-    (1, 1, 64, 64, 96, (1, 7, 7), (1, 4, 4), (0, 3, 3), True),      # mvit_base_16: the image model's Conv2d as one frame
-    (1, 4, 36, 68, 64, (3, 7, 7), (2, 4, 4), (1, 3, 3), False),     # 4 waves, bf16 out
-    (1, 3, 40, 40, 120, (3, 7, 7), (1, 4, 4), (1, 3, 3), True),     # 8 waves, channel tail, temporal stride 1
-])
-def test_first_layer_conv_on_c4_layout(B, T, H, W, cout, k, s, p, f32out):
+    (2, 5, 30, 50, 96, (3, 7, 7), (2, 4, 4), (1, 3, 3), True, None, "stem_pe_kernel"),      # ragged tiles, odd T
+    (1, 1, 64, 64, 96, (1, 7, 7), (1, 4, 4), (0, 3, 3), True, None, "stem_pe_kernel"),      # mvit_base_16: the image model's Conv2d as one frame
+    (1, 4, 36, 68, 64, (3, 7, 7), (2, 4, 4), (1, 3, 3), False, None, "stem_pe_kernel"),     # 4 waves, bf16 out
+    (1, 3, 40, 40, 120, (3, 7, 7), (1, 4, 4), (1, 3, 3), True, None, "stem_pe_kernel"),     # 8 waves, channel tail, temporal stride 1
+    # the generic kernel on 7x7 convs the tiled kernels do not take: 40 channels are neither <= 8 nor a multiple of 16
+    # (stem_c4_kernel<4, 2>); 76 channels = 5 tiles are no stem_pe width (stem_c4_kernel<2, 2>: three blockIdx.y slabs,
+    # channel tail inside the last one)
+    (1, 2, 18, 22, 40, (1, 7, 7), (1, 2, 2), (0, 3, 3), False, None, "stem_c4_kernel"),
+    (1, 3, 20, 28, 76, (3, 7, 7), (2, 4, 4), (1, 3, 3), True, None, "stem_c4_kernel"),
+    # position tables added in the fp32 epilogue: spatial [Ho*Wo, cout] + temporal [To, cout], or one full [To*Ho*Wo, cout]
+    (1, 3, 20, 28, 76, (3, 7, 7), (2, 4, 4), (1, 3, 3), True, "split", "stem_c4_kernel"),
+    (1, 3, 20, 28, 76, (3, 7, 7), (2, 4, 4), (1, 3, 3), True, "full", "stem_c4_kernel"),
+    (2, 5, 30, 50, 96, (3, 7, 7), (2, 4, 4), (1, 3, 3), True, "split", "stem_pe_kernel"),
+    (2, 5, 30, 50, 96, (3, 7, 7), (2, 4, 4), (1, 3, 3), True, "full", "stem_pe_kernel"),
+]
+
+
+def _c4_case_id(i, c):
+    """The id pytest gave case i before `pos` and `kern` were parameters (so the earlier cases keep their names), plus pos."""
+    base = "-".join(str(v) for v in c[:5]) + "-k%d-s%d-p%d-%s" % (i, i, i, c[8])
+    return base if c[9] is None else base + "-" + c[9]
+
+
+@pytest.mark.parametrize("B,T,H,W,cout,k,s,p,f32out,pos,kern", _C4_CASES,
+                         ids=[_c4_case_id(i, c) for i, c in enumerate(_C4_CASES)])
+def test_first_layer_conv_on_c4_layout(B, T, H, W, cout, k, s, p, f32out, pos, kern):
     x = _rand((B, 3, T, H, W), 61, torch.bfloat16)
     w = _rand((cout, 3) + k, 62, torch.bfloat16, (3 * k[0] * k[1] * k[2]) ** -0.5)
     bias = _rand((cout,), 63, torch.float32)
     want = F.relu(F.conv3d(x.float(), w.float(), bias, stride=s, padding=p))
     To, Ho, Wo = want.shape[2:]
+    pos_s = pos_t = None
+    if pos == "split":
+        pos_s, pos_t = _rand((Ho * Wo, cout), 64, torch.float32), _rand((To, cout), 65, torch.float32)
+        want = want + (pos_t[:, None, :] + pos_s[None, :, :]).reshape(To, Ho, Wo, cout).permute(3, 0, 1, 2)
+    elif pos == "full":
+        pos_s = _rand((To * Ho * Wo, cout), 64, torch.float32)
+        want = want + pos_s.reshape(To, Ho, Wo, cout).permute(3, 0, 1, 2)
     # NCDHW -> NDHWC with 4 channels per voxel, through the library's own ingest
     x4 = torch.full((B, T, H, W, 4), 9.0, dtype=torch.bfloat16, device="cuda")
     ld = L.LayoutDesc()
@@ -409,9 +436,12 @@ def test_first_layer_conv_on_c4_layout(B, T, H, W, cout, k, s, p, f32out):
     d.B, d.Ti, d.Hi, d.Wi, d.cin, d.To, d.Ho, d.Wo, d.cout = B, T, H, W, 4, To, Ho, Wo, cout
     d.kt, d.kh, d.kw, d.st, d.sh, d.sw, d.pt, d.ph, d.pw = (*k, *s, *p)
     d.act, d.a_act, d.dtype, d.y_f32 = L.ACT_RELU, L.ACT_NONE, L.PV_BF16, int(f32out)
+    d.pos_spatial = pos_s.data_ptr() if pos_s is not None else None
+    d.pos_temporal = pos_t.data_ptr() if pos_t is not None else None
     call("pv_conv3d", d)
     assert rel_err(y[..., :cout].permute(0, 4, 1, 2, 3), want) <= (2e-3 if f32out else 1e-2)
     assert torch.all(y[..., cout:] == 0)
+    assert _routed_kernel(L.OP_CONV3D, d) == kern
 
 
 @pytest.mark.parametrize("B,T,H,W,cout,k,s,p", [
