@@ -461,6 +461,77 @@ typedef struct pv_yuv_views_desc {
 } pv_yuv_views_desc;
 int pv_yuv_views(const pv_yuv_views_desc* d, pv_stream_t stream);
 
+/* ---- many videos per launch: one source per destination item ---------------------------------------------------------
+ * A dataset evaluation scores thousands of videos with a handful of views each (10 clips x 3 crops, 5 x 1, 1 x 3: the model
+ * zoo's test protocols), and the videos differ in length and frame size.  pv_video_views / pv_yuv_views take ONE source and
+ * ONE geometry per launch, so the views of two videos cannot share a launch and a video's views rarely fill the deploy
+ * batch.  pv_batch_views gives every destination item its own source: the geometry that the two entry points above take by
+ * value is a RECORD per video, and an item names its record, its table row and its view.
+ * Sources:      n_sources records (pv_view_source), the same bytes on the host (`sources`: the records that the launch's items
+ *               name are validated, and the launch is sized from them -- a launch is usually a window of a longer sequence,
+ *               and its cost does not grow with the records it does not use) and on the device (`sources_dev`: what the
+ *               kernel reads).  THE CALLER UPLOADS THE VERY
+ *               BUFFER IT PASSES; the library cannot compare the two, and a device copy that differs from the validated one
+ *               is outside every guarantee given here.  sy / sx are (float)Hs / (float)Hn and (float)Ws / (float)Wn, divided
+ *               by the caller in fp32 (the library checks the bits against its own division).
+ *               src_layout PV_SRC_NCTHW: src is a dense [C,N,Hs,Ws] video, PV_U8 or PV_F32; PV_SRC_NTHWC: dense [N,Hs,Ws,3],
+ *               PV_U8; PV_SRC_YUV420: N frames as in pv_yuv_views_desc (frame_stride, u_offset, v_offset, y_pitch, c_pitch).
+ *               One launch has one source form: src_dtype, src_layout, C and c_step belong to the launch.  NV12 and NV21
+ *               sources may share a launch (c_step 2) and so may I420 and YV12 (c_step 1): the order of U and V is the
+ *               record's u_offset / v_offset.  frame_stride .. c_pitch are ignored for the RGB / planar forms.
+ * Items:        n_items records (pv_view_item), likewise on host and device.  Item i of the launch is view items[i].view of
+ *               table row items[i].row of source items[i].source and is written to position i of dst.  Any order, any mix of
+ *               sources; rows and whole items may repeat.  A window of a longer sequence is a pointer offset into both
+ *               copies.  The kernel clamps source / row / view into range before it uses them.
+ * Frames:       ONE device table t_index[n_rows][t_stride], the rows of all videos one after another; the first T entries of
+ *               a row are the video frames of the item's destination frames.  Every entry is clamped into [0, N-1] OF THE
+ *               ITEM'S SOURCE before an address is formed; reporting a bad table is the caller's job.
+ * Arithmetic:   pv_resample_crop's pinned formula and, for PV_SRC_YUV420, pv_yuv_views' rule, tap clamp included.  Item i is
+ *               bit for bit what pv_video_views / pv_yuv_views writes for that video alone with
+ *               item0 = row * n_views + view, n_items = 1.
+ * Destination:  the forms, strides and alignment of pv_resample_crop; ch_scale / ch_shift as there.
+ * PV_ERR_INVALID: null sources / sources_dev / items / items_dev / t_index / dst (yuv2rgb for PV_SRC_YUV420); n_sources,
+ * n_items, n_rows, T, C, Ho, Wo <= 0; t_stride < T; n_items or T > 65535 (the grid); an item whose source, row or view is out
+ * of range; a record named by an item with a null src, non-positive N / Hs / Ws / Hn / Wn, a view window that leaves Hn x Wn,
+ * sy / sx whose bits are not the library's own division, or -- PV_F32 sources -- a src that is no multiple of 4; whatever pv_resample_crop rejects (C > 4, an interleaved source that is not uint8 with C == 3,
+ * destination alignment, n_views outside 1..3); for PV_SRC_YUV420, per such record, the plane checks of pv_yuv_views (odd sizes,
+ * pitches, offsets, planes inside frame_stride) and C != 3.  PV_ERR_UNSUPPORTED: the dtype / layout matrix of
+ * pv_resample_crop, and a staged strip beyond the kernels' LDS limit.
+ */
+enum { PV_SRC_YUV420 = 2 };   /* pv_batch_views_desc.src_layout only, beside pv_resample_src_layout */
+typedef struct pv_view_source {      /* one decoded video; 96 bytes, 8-byte aligned */
+  const void* src;                   /* device address of the video / of frame 0                              */
+  int64_t frame_stride;              /* YUV sources: bytes between frames (RGB / planar sources: dense)       */
+  int64_t u_offset, v_offset;        /* YUV sources, as in pv_yuv_views_desc                                   */
+  int32_t y_pitch, c_pitch;          /* YUV sources                                                            */
+  int32_t N, Hs, Ws;                 /* frames, frame size                                                     */
+  int32_t Hn, Wn;                    /* size after scaling                                                     */
+  int32_t y_off[3], x_off[3];        /* per view: window origin inside Hn x Wn                                 */
+  float   sy, sx;                    /* (float)Hs / (float)Hn, (float)Ws / (float)Wn, set by the caller        */
+  int32_t reserved;
+} pv_view_source;
+typedef struct pv_view_item { int32_t source, row, view, reserved; } pv_view_item;   /* one destination item */
+typedef struct pv_batch_views_desc {
+  const pv_view_source* sources;      /* [n_sources] on the HOST                                               */
+  const pv_view_source* sources_dev;  /* the same bytes on the device                                          */
+  const pv_view_item* items;          /* [n_items] on the HOST                                                 */
+  const pv_view_item* items_dev;      /* the same bytes on the device                                          */
+  const int32_t* t_index;             /* [n_rows][t_stride] on the device, the first T of every row used       */
+  void* dst;
+  const float* ch_scale;              /* [C] or NULL                                                           */
+  const float* ch_shift;              /* [C] or NULL                                                           */
+  const float* yuv2rgb;               /* PV_SRC_YUV420: [3][4] fp32 on the device                              */
+  int64_t bs;                         /* PV_DST_NDHWC only: batch stride in elements                           */
+  int32_t n_sources, n_items, n_rows, t_stride;
+  int32_t C, T;                       /* channels (<= 4; 3 for YUV), DESTINATION frames per item               */
+  int32_t src_dtype, src_layout;      /* pv_dtype; PV_SRC_NCTHW / PV_SRC_NTHWC / PV_SRC_YUV420                 */
+  int32_t c_step;                     /* PV_SRC_YUV420: 2 interleaved chroma, 1 planar                         */
+  int32_t Ho, Wo, n_views;            /* crop window; views per clip, 1..3                                     */
+  int32_t dst_layout, dst_dtype;
+  int32_t c_p, ld;                    /* PV_DST_NDHWC only                                                     */
+} pv_batch_views_desc;
+int pv_batch_views(const pv_batch_views_desc* d, pv_stream_t stream);
+
 /* ---- row ops on (rows, C) matrices -------------------------------------------------
  * pv_layernorm: nn.LayerNorm(eps) over C (models/vision_transformers.py:333-335,
  *   layers/attention.py:199-205).

@@ -90,6 +90,18 @@ YuvViewsDesc = _struct("YuvViewsDesc", [
     + _ints("y_pitch", "c_pitch", "c_step", "n_clips", "T", "N", "t_stride", "Hs", "Ws", "Hn", "Wn", "Ho", "Wo", "n_views")
     + [("y_off", _i32 * 3), ("x_off", _i32 * 3)] + _ints("item0", "n_items", "dst_layout", "dst_dtype", "c_p", "ld"))
 
+SRC_YUV420 = 2   # BatchViewsDesc.src_layout only
+ViewSource = _struct("ViewSource", [
+    ("src", _p), ("frame_stride", _i64), ("u_offset", _i64), ("v_offset", _i64)]
+    + _ints("y_pitch", "c_pitch", "N", "Hs", "Ws", "Hn", "Wn") + [("y_off", _i32 * 3), ("x_off", _i32 * 3), ("sy", _f32), ("sx", _f32)]
+    + _ints("reserved"))
+ViewItem = _struct("ViewItem", _ints("source", "row", "view", "reserved"))
+BatchViewsDesc = _struct("BatchViewsDesc", [
+    ("sources", _p), ("sources_dev", _p), ("items", _p), ("items_dev", _p), ("t_index", _p), ("dst", _p), ("ch_scale", _p),
+    ("ch_shift", _p), ("yuv2rgb", _p), ("bs", _i64)]
+    + _ints("n_sources", "n_items", "n_rows", "t_stride", "C", "T", "src_dtype", "src_layout", "c_step", "Ho", "Wo", "n_views",
+            "dst_layout", "dst_dtype", "c_p", "ld"))
+
 RowsDesc = _struct("RowsDesc", [
     ("x", _p), ("y", _p), ("gamma", _p), ("beta", _p), ("rows", _i64)]
     + _ints("C", "ldx", "ldy", "rows_per_batch") + [("eps", _f32), ("dtype", _i32), ("x_f32", _i32), ("g_period", _i32),
@@ -168,6 +180,7 @@ _SYMBOLS = [
     ("pv_resample_crop", C.c_int, [C.POINTER(ResampleDesc), _p]),
     ("pv_video_views", C.c_int, [C.POINTER(VideoViewsDesc), _p]),
     ("pv_yuv_views", C.c_int, [C.POINTER(YuvViewsDesc), _p]),
+    ("pv_batch_views", C.c_int, [C.POINTER(BatchViewsDesc), _p]),
     ("pv_layernorm", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_affine_rows", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_softmax_rows", C.c_int, [C.POINTER(RowsDesc), _p]),

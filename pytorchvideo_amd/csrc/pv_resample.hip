@@ -31,12 +31,6 @@ struct RsLaunch {
   int64_t clip_frames;  // frames from one source clip to the next: 0 = every clip reads the one video (pv_video_views)
 };
 
-template <typename S> __device__ __forceinline__ float rs_tap(const unsigned char* lds, int off);
-template <> __device__ __forceinline__ float rs_tap<unsigned char>(const unsigned char* lds, int off) { return (float)lds[off]; }
-template <> __device__ __forceinline__ float rs_tap<float>(const unsigned char* lds, int off) {
-  return *reinterpret_cast<const float*>(lds + off);
-}
-
 // S: source element (unsigned char | float); INTER: frame-interleaved [B,T,Hs,Ws,3] source; FORM / D: destination.
 // Source clip b starts g.clip_frames frames behind clip b - 1 and takes its frames from row b * g.tab_stride of d.t_index:
 // B clips with one shared row (pv_resample_crop), or one video with a row per clip (pv_video_views: clip_frames == 0).

@@ -1,6 +1,7 @@
-// What the resampling ingest kernels share (pv_resample.hip: RGB / planar sources; pv_yuv.hip: YUV 4:2:0 sources): the
-// pinned source coordinate, the blend, the destination forms with their stores, and the host-side checks of views, item
-// range and destination.  Everything is inline in an anonymous namespace: each translation unit keeps its own kernels.
+// What the resampling ingest kernels share (pv_resample.hip: RGB / planar sources; pv_yuv.hip: YUV 4:2:0 sources;
+// pv_batch.hip: either, with one source per destination item): the pinned source coordinate, the taps of a staged row, the
+// YUV tap conversion and blend, the destination forms with their stores, and the host-side checks of views, item range,
+// destination and YUV planes.  Everything is inline in an anonymous namespace: each translation unit keeps its own kernels.
 #pragma once
 #include "pv_common.h"
 
@@ -97,6 +98,38 @@ __device__ __forceinline__ void rs_store_group(void* dst, const float (&out)[4][
   }
 }
 
+// ---- taps and blends shared by the one-source kernels and the per-item kernels (pv_batch.hip) ------------------------
+// One tap of a staged RGB / planar row, in the source dtype.
+template <typename S> __device__ __forceinline__ float rs_tap(const unsigned char* lds, int off);
+template <> __device__ __forceinline__ float rs_tap<unsigned char>(const unsigned char* lds, int off) { return (float)lds[off]; }
+template <> __device__ __forceinline__ float rs_tap<float>(const unsigned char* lds, int off) {
+  return *reinterpret_cast<const float*>(lds + off);
+}
+
+__device__ __forceinline__ f32x2 yuv_splat(float v) { return f32x2{v, v}; }
+
+// Two taps of the virtual RGB frame -- the same column of the two source rows -- as packed fp32 pairs (v_pk_fma_f32 does
+// both for the price of one): per channel three fused multiply-adds in the header's order, then the clamp.
+__device__ __forceinline__ void yuv_tap2(const float (&m)[12], const unsigned char* lds, int oy0, int ou0, int ov0, int oy1, int ou1,
+                                         int ov1, f32x2 (&rgb)[3]) {
+  const f32x2 Y = {(float)lds[oy0], (float)lds[oy1]}, U = {(float)lds[ou0], (float)lds[ou1]}, V = {(float)lds[ov0], (float)lds[ov1]};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const f32x2 v = __builtin_elementwise_fma(yuv_splat(m[c * 4 + 2]), V, __builtin_elementwise_fma(yuv_splat(m[c * 4 + 1]), U,
+                        __builtin_elementwise_fma(yuv_splat(m[c * 4]), Y, yuv_splat(m[c * 4 + 3]))));
+    rgb[c] = f32x2{fminf(fmaxf(v[0], 0.f), 255.f), fminf(fmaxf(v[1], 0.f), 255.f)};
+  }
+}
+
+// The pinned blend and the affine map with the contraction spelled out, so that every instantiation gives the same bits:
+// p0 / p1 hold column i0x / i1x of the rows (i0y, i1y); h = {top, bottom} = lx1 p1 + (lx0 p0), v = ly1 bottom + (ly0 top).
+__device__ __forceinline__ float yuv_blend(float ly0, float ly1, float lx0, float lx1, f32x2 p0, f32x2 p1, float sc, float sh) {
+#pragma clang fp contract(off)
+  const f32x2 h = __builtin_elementwise_fma(yuv_splat(lx1), p1, yuv_splat(lx0) * p0);
+  const float v = fmaf(ly1, h[1], ly0 * h[0]);
+  return fmaf(v, sc, sh);
+}
+
 // ---- host-side checks shared by the entry points ------------------------------------------------------------------
 // The crop windows of every view lie inside the scaled frame.
 inline int rs_check_views(int n_views, const int32_t* y_off, const int32_t* x_off, int Ho, int Wo, int Hn, int Wn) {
@@ -133,6 +166,25 @@ inline int rs_check_dst(const void* dstp, int dst_layout, int dst_dtype, int c_p
   } else {
     return PV_ERR_UNSUPPORTED;
   }
+  return PV_OK;
+}
+
+// Bytes [off, off + (rows - 1) * pitch + (cols - 1) * step] of a plane lie inside [0, frame_stride).
+inline bool plane_inside(int64_t off, int64_t rows, int64_t pitch, int64_t cols, int64_t step, int64_t frame_stride) {
+  return off >= 0 && off + (rows - 1) * pitch + (cols - 1) * step < frame_stride;
+}
+
+// The planes of one YUV 4:2:0 frame of Hs x Ws (both positive): even sizes, the chroma form, pitches that hold a row, and
+// luma and chroma planes inside [0, frame_stride).
+inline int rs_check_yuv_planes(int Hs, int Ws, int c_step, int y_pitch, int c_pitch, int64_t frame_stride, int64_t u_offset,
+                               int64_t v_offset) {
+  if ((Hs | Ws) & 1) return PV_ERR_INVALID;
+  if (c_step != 1 && c_step != 2) return PV_ERR_INVALID;
+  if (y_pitch < Ws || c_pitch < (Ws / 2) * c_step || frame_stride <= 0) return PV_ERR_INVALID;
+  if (c_step == 2 && v_offset - u_offset != 1 && u_offset - v_offset != 1) return PV_ERR_INVALID;
+  if (!plane_inside(0, Hs, y_pitch, Ws, 1, frame_stride) || !plane_inside(u_offset, Hs / 2, c_pitch, Ws / 2, c_step, frame_stride) ||
+      !plane_inside(v_offset, Hs / 2, c_pitch, Ws / 2, c_step, frame_stride))
+    return PV_ERR_INVALID;
   return PV_OK;
 }
 

@@ -28,30 +28,6 @@ struct YuvLaunch {
   int64_t c_off_a, c_off_b; // byte offset inside a frame of staged chroma plane 0 / 1 (c_step 2: only plane 0, min(u, v))
 };
 
-__device__ __forceinline__ f32x2 yuv_splat(float v) { return f32x2{v, v}; }
-
-// Two taps of the virtual RGB frame -- the same column of the two source rows -- as packed fp32 pairs (v_pk_fma_f32 does
-// both for the price of one): per channel three fused multiply-adds in the header's order, then the clamp.
-__device__ __forceinline__ void yuv_tap2(const float (&m)[12], const unsigned char* lds, int oy0, int ou0, int ov0, int oy1, int ou1,
-                                         int ov1, f32x2 (&rgb)[3]) {
-  const f32x2 Y = {(float)lds[oy0], (float)lds[oy1]}, U = {(float)lds[ou0], (float)lds[ou1]}, V = {(float)lds[ov0], (float)lds[ov1]};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const f32x2 v = __builtin_elementwise_fma(yuv_splat(m[c * 4 + 2]), V, __builtin_elementwise_fma(yuv_splat(m[c * 4 + 1]), U,
-                        __builtin_elementwise_fma(yuv_splat(m[c * 4]), Y, yuv_splat(m[c * 4 + 3]))));
-    rgb[c] = f32x2{fminf(fmaxf(v[0], 0.f), 255.f), fminf(fmaxf(v[1], 0.f), 255.f)};
-  }
-}
-
-// The pinned blend and the affine map with the contraction spelled out, so that every instantiation gives the same bits:
-// p0 / p1 hold column i0x / i1x of the rows (i0y, i1y); h = {top, bottom} = lx1 p1 + (lx0 p0), v = ly1 bottom + (ly0 top).
-__device__ __forceinline__ float yuv_blend(float ly0, float ly1, float lx0, float lx1, f32x2 p0, f32x2 p1, float sc, float sh) {
-#pragma clang fp contract(off)
-  const f32x2 h = __builtin_elementwise_fma(yuv_splat(lx1), p1, yuv_splat(lx0) * p0);
-  const float v = fmaf(ly1, h[1], ly0 * h[0]);
-  return fmaf(v, sc, sh);
-}
-
 // CSTEP: bytes between x-adjacent samples of one chroma plane (2: U and V interleaved in ONE staged plane; 1: two planes).
 template <int CSTEP, int FORM, typename D>
 __global__ __launch_bounds__(kRsThreads) void yuv_views_kernel(const pv_yuv_views_desc d, const YuvLaunch g) {
@@ -195,23 +171,11 @@ int yuv_launch(const pv_yuv_views_desc& d, const YuvLaunch& g, dim3 grid, size_t
   return PV_OK;
 }
 
-// Bytes [off, off + (rows - 1) * pitch + (cols - 1) * step] of a plane lie inside [0, frame_stride).
-bool plane_inside(int64_t off, int64_t rows, int64_t pitch, int64_t cols, int64_t step, int64_t frame_stride) {
-  return off >= 0 && off + (rows - 1) * pitch + (cols - 1) * step < frame_stride;
-}
-
 int yuv_run(pv_yuv_views_desc d, pv_stream_t stream) {
   if (d.n_clips <= 0 || d.T <= 0 || d.N <= 0 || d.Hs <= 0 || d.Ws <= 0 || d.Hn <= 0 || d.Wn <= 0 || d.Ho <= 0 || d.Wo <= 0)
     return PV_ERR_INVALID;
   if (d.t_stride < d.T) return PV_ERR_INVALID;
-  if ((d.Hs | d.Ws) & 1) return PV_ERR_INVALID;
-  if (d.c_step != 1 && d.c_step != 2) return PV_ERR_INVALID;
-  if (d.y_pitch < d.Ws || d.c_pitch < (d.Ws / 2) * d.c_step || d.frame_stride <= 0) return PV_ERR_INVALID;
-  if (d.c_step == 2 && d.v_offset - d.u_offset != 1 && d.u_offset - d.v_offset != 1) return PV_ERR_INVALID;
-  if (!plane_inside(0, d.Hs, d.y_pitch, d.Ws, 1, d.frame_stride) ||
-      !plane_inside(d.u_offset, d.Hs / 2, d.c_pitch, d.Ws / 2, d.c_step, d.frame_stride) ||
-      !plane_inside(d.v_offset, d.Hs / 2, d.c_pitch, d.Ws / 2, d.c_step, d.frame_stride))
-    return PV_ERR_INVALID;
+  if (int e = rs_check_yuv_planes(d.Hs, d.Ws, d.c_step, d.y_pitch, d.c_pitch, d.frame_stride, d.u_offset, d.v_offset)) return e;
   if (int e = rs_check_views(d.n_views, d.y_off, d.x_off, d.Ho, d.Wo, d.Hn, d.Wn)) return e;
   if (int e = rs_check_items(d.item0, d.n_items, (long)d.n_clips * d.n_views, d.T)) return e;
   if (int e = rs_check_dst(d.dst, d.dst_layout, d.dst_dtype, d.c_p, d.ld, d.bs, d.T, d.Ho, d.Wo)) return e;

@@ -7,12 +7,16 @@ Nothing is materialised between the video and the first convolution: the sampler
 on the host (`data.clip_frame_table`), the table is uploaded once, and the ingest kernel (`pv_video_views`) reads the video
 through it, one launch per pathway per forward.  The clips x views sequence is walked in chunks of the deploy form's batch;
 the last chunk may be short, so a video of any length runs on a form converted for any batch.
+
+`VideoBatchPredictor` scores MANY videos per call -- a dataset evaluation -- with every forward filled by views of as many
+videos as it takes (`pv_batch_views`: one source per item of the deploy batch), one table upload and at most one short chunk
+per call instead of one of each per video.
 """
 import torch
 
 from .data.clip_sampling import clip_frame_table
 from .ensemble import VideoEnsembler
-from .transforms import DevicePacker
+from .transforms import DevicePacker, batch_chunks
 
 
 class VideoPredictor:
@@ -71,3 +75,61 @@ class VideoPredictor:
                 self.clip_ensembler.update(logits, clip_of[i0:i0 + n])
         scores = self.video_ensembler.result()[0]
         return (scores, self.clip_ensembler.result()) if return_clip_scores else scores
+
+
+class VideoBatchPredictor:
+    """`VideoBatchPredictor(deployed, clip_sampler, mean, std, div255, short_side, crop_size)(videos, fps)` = [V, num_classes]
+    fp32 scores of a list of V videos, each folded as `VideoPredictor` folds one.  The videos are device tensors of ANY
+    lengths and frame sizes in the one `src_layout` (for a YUV layout `height` / `coded_height` of the call are one number or
+    one per video); `fps` is one number or one per video.  The views of all videos form one video-major sequence that is
+    walked in chunks of the deploy batch, so a forward holds views of several videos and only the LAST forward of a call can
+    be short; the frame tables of all videos are built, range-checked and uploaded once per call.
+    `return_clip_scores=True` adds a list of V tensors [n_clips_j, num_classes].  After a call `video_ensembler.counts`
+    holds the views folded per video (and `clip_ensembler.counts` per clip, all videos' clips one after another)."""
+
+    def __init__(self, deployed, clip_sampler, mean, std, div255, short_side, crop_size, spatial_idx=(0, 1, 2),
+                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False)):
+        if getattr(deployed, "_pv_load_boxes", None) is not None:
+            raise ValueError("VideoBatchPredictor scores videos; a detection model's boxes belong to key frames"
+                             " (in any source layout, %s included)" % src_layout)
+        if method not in ("sum", "max"):
+            raise NotImplementedError("ensemble method %r (the reference knows 'sum' and 'max')" % method)
+        self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv)
+        self.sampler, self.method, self.src_layout = clip_sampler, method, src_layout
+        self.video_ensembler = self.clip_ensembler = None
+        self.forwards = 0                                        # forwards of the last call
+
+    @torch.no_grad()
+    def __call__(self, videos, fps, return_clip_scores=False, height=None, coded_height=None):
+        p = self.packer
+        device = p.sess.device
+        videos = list(videos)
+        if not videos:
+            raise ValueError("no videos")
+        rates = list(fps) if isinstance(fps, (list, tuple)) else [fps] * len(videos)
+        if len(rates) != len(videos):
+            raise ValueError("fps is one number or one per video: %d for %d videos" % (len(rates), len(videos)))
+        dims = 3 if p.is_yuv else 4
+        tables = []
+        for j, (video, rate) in enumerate(zip(videos, rates)):
+            if video.dim() != dims:
+                raise RuntimeError("video %d: expected a %d-d %s video, got %s" % (j, dims, self.src_layout, tuple(video.shape)))
+            num_frames = video.shape[1] if self.src_layout == "NCTHW" else video.shape[0]
+            tables.append(clip_frame_table(self.sampler, num_frames, rate, p.clip_frames)[0])
+        batch = p.video_batch(videos, tables, height, coded_height)      # every check, and the one upload
+        self.forwards = 0
+        for i0, n in batch_chunks(batch.total, p.batch):
+            p.fill_batch(batch, i0, n)
+            logits = p.launch()[:n]                              # rows of the zero-filled tail are never folded
+            if i0 == 0:
+                self.video_ensembler = VideoEnsembler(len(videos), logits.shape[1], self.method, device)
+                self.clip_ensembler = VideoEnsembler(batch.n_rows, logits.shape[1], self.method, device) if return_clip_scores else None
+            self.video_ensembler.update(logits, batch.video_of[i0:i0 + n])
+            if return_clip_scores:
+                self.clip_ensembler.update(logits, batch.clip_of[i0:i0 + n])
+            self.forwards += 1
+        p.release_batch()                                        # the videos are the caller's again
+        scores = self.video_ensembler.result()
+        if not return_clip_scores:
+            return scores
+        return scores, list(torch.split(self.clip_ensembler.result(), batch.clips))

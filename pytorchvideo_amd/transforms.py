@@ -19,6 +19,9 @@ transforms.py:100-121,153-175), with their box variants -- has the same two form
 Decoder-native frames -- YUV 4:2:0 as NV12 / NV21 (what a GPU decoder writes) or I420 / YV12 (a CPU decoder's yuv420p) -- are
 a source layout of that same pass (`pv_yuv_views`): `yuv_matrix` composes the conversion, `yuv420_to_rgb` is the host mirror
 of the tap rule, and `device_scale_crop` / `DevicePacker` / `inference.VideoPredictor` take `src_layout="NV12"` and friends.
+
+Many videos per forward: `DevicePacker.video_batch` + `fill_batch` give every item of the deploy batch a source of its own
+(`pv_batch_views`), so that the views of videos of any lengths and frame sizes share a forward (`inference.VideoBatchPredictor`).
 """
 import copy
 import math
@@ -412,6 +415,123 @@ def _device_scale_crop_yuv(frames, short_side, crop_size, views, mean, std, div2
     return out
 
 
+# --------------------------------------------------------------------------- many videos per forward (pv_batch_views)
+def batch_items(clips_per_video, n_views):
+    """The video-major item sequence of a batch of videos: video j, then `clip * n_views + v`.  Returns (items, video_of,
+    clip_of, row0): `items` int32 [total, 4] = (source, row, view, 0) as `pv_view_item` holds them, `row` counting the rows
+    of the CONCATENATED frame table; `video_of` / `clip_of` int32 [total] = the video and the concatenated-table row of
+    every item; `row0[j]` = the first row of video j."""
+    counts = [int(c) for c in clips_per_video]
+    if not counts or any(c <= 0 for c in counts) or n_views < 1:
+        raise ValueError("a batch holds at least one video, and every video at least one clip; got %s clips x %d views" % (counts, n_views))
+    row0 = [0]
+    for c in counts[:-1]:
+        row0.append(row0[-1] + c)
+    video_of = torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int32), torch.tensor(counts) * n_views)
+    clip_of = torch.arange(sum(counts), dtype=torch.int32).repeat_interleave(n_views)
+    view = torch.arange(n_views, dtype=torch.int32).repeat(sum(counts))
+    items = torch.stack([video_of, clip_of, view, torch.zeros_like(view)], dim=1).contiguous()
+    return items, video_of, clip_of, row0
+
+
+def batch_chunks(total, batch):
+    """[(i0, n)] of the forwards that walk `total` items in chunks of the deploy batch; only the last one may be short."""
+    return [(i0, min(batch, total - i0)) for i0 in range(0, total, batch)]
+
+
+def batch_tables(tables, pathway_frames, nums_frames):
+    """The per-pathway frame tables of a batch of videos, the videos' rows one after another: `pathway_tables` of every
+    video's [n_clips_j, T] table -- checked against THAT video's frame count -- concatenated per pathway (host int32)."""
+    if len(tables) != len(nums_frames) or not tables:
+        raise ValueError("%d frame tables for %d videos" % (len(tables), len(nums_frames)))
+    per_video = [pathway_tables(t, pathway_frames, n) for t, n in zip(tables, nums_frames)]
+    return [torch.cat([pv[p] for pv in per_video]).contiguous() for p in range(len(pathway_frames))]
+
+
+class VideoBatch:
+    """What `DevicePacker.video_batch` uploaded for a list of videos: the `pv_view_source` records and the `pv_view_item`
+    sequence (host copies and the device copies of the same bytes), the concatenated per-pathway frame tables, and the
+    videos themselves, kept alive.  `total` items; `video_of` / `clip_of` (int32, device) = the video and the row of the
+    concatenated table behind every item; `clips[j]` / `row0[j]` = the clips of video j and its first row."""
+
+    def __init__(self, videos, sources, items, items_t, tables, video_of, clip_of, clips, row0, n_views, src_dtype, upload):
+        self.videos, self.sources, self.items = list(videos), sources, items
+        self.n_views, self.src_dtype, self.clips, self.row0 = n_views, src_dtype, list(clips), list(row0)
+        self.total, self.n_rows = len(items), sum(clips)
+        # the very buffers the descriptors point at are the ones uploaded
+        self.sources_dev = upload(torch.frombuffer(sources, dtype=torch.uint8))
+        self.items_dev = upload(torch.frombuffer(items, dtype=torch.uint8))
+        self.tables = [upload(t) for t in tables]
+        self.video_of, self.clip_of = upload(video_of), upload(clip_of)
+        self.item_rows = items_t                   # host int32 [total, 4]: (source, row, view, 0)
+
+
+def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, pathway_frames, channels, device, upload,
+                      height=None, coded_height=None):
+    """The host half of `DevicePacker.video_batch` (see there): validate every video, build the records, the item sequence
+    and the concatenated tables, and hand them to `upload` (host tensor -> device tensor) once."""
+    from . import _lib as L
+    videos = list(videos)
+    if not videos or len(tables) != len(videos):
+        raise ValueError("%d frame tables for %d videos" % (len(tables), len(videos)))
+    is_yuv = src_layout in YUV_LAYOUTS
+
+    def per_video(x, what):
+        if x is None or not isinstance(x, (list, tuple)):
+            return [None if x is None else int(x)] * len(videos)         # any integer type: int, numpy, a 0-d tensor
+        x = list(x)
+        if len(x) != len(videos):
+            raise ValueError("%s is one number or one per video: %d for %d videos" % (what, len(x), len(videos)))
+        return x
+
+    heights, coded = per_video(height, "height"), per_video(coded_height, "coded_height")
+    sources = (L.ViewSource * len(videos))()
+    nums_frames, dtype = [], videos[0].dtype
+    for j, video in enumerate(videos):
+        if video.device.type != device.type or (device.index is not None and video.device.index != device.index):
+            raise RuntimeError("video %d is on %s, the deploy form on %s" % (j, video.device, device))
+        rec = sources[j]
+        if is_yuv:
+            if video.dim() != 3:
+                raise RuntimeError("video %d: expected one 3-d %s video, got %s" % (j, src_layout, tuple(video.shape)))
+            geom = yuv_geometry(video, src_layout, coded[j], heights[j])
+            c, nf, hs, ws = 3, geom["N"], geom["Hs"], geom["Ws"]
+            for k in ("frame_stride", "u_offset", "v_offset", "y_pitch", "c_pitch"):
+                setattr(rec, k, geom[k])
+        else:
+            c, nf, hs, ws = _video_geometry(video, src_layout)
+            if not video.is_contiguous() or video.dtype not in (torch.uint8, torch.float32):
+                raise RuntimeError("video %d is not a contiguous uint8 or fp32 tensor" % j)
+            if video.dtype != dtype:
+                raise RuntimeError("the videos of one batch have one dtype: video %d is %s, video 0 %s" % (j, video.dtype, dtype))
+            if src_layout == "NTHWC" and (c != 3 or video.dtype != torch.uint8):
+                raise RuntimeError("a frame-interleaved video is uint8 [N,H,W,3], got %s %s" % (video.dtype, tuple(video.shape)))
+        if c != channels:
+            raise RuntimeError("video %d has %d channels, the deploy form takes %d" % (j, c, channels))
+        hn, wn = scaled_size(hs, ws, short_side)
+        if crop_size > hn or crop_size > wn:
+            raise RuntimeError("video %d: a %d crop does not fit the %d x %d frame scaled to %d x %d" % (j, crop_size, hs, ws, hn, wn))
+        rec.src, rec.N, rec.Hs, rec.Ws, rec.Hn, rec.Wn = video.data_ptr(), nf, hs, ws, hn, wn
+        for k, v in enumerate(views):
+            rec.y_off[k], rec.x_off[k] = crop_offsets(hn, wn, crop_size, v)
+        # (float)Hs / (float)Hn: sizes are exact in fp32, and a double quotient rounded once more to fp32 IS the fp32 quotient
+        rec.sy, rec.sx = hs / hn, ws / wn
+        nums_frames.append(nf)
+    clip_frames = None
+    for j, t in enumerate(tables):
+        t = torch.as_tensor(t)
+        if t.dim() == 2 and clip_frames is None:
+            clip_frames = t.shape[1]
+        if t.dim() != 2 or t.shape[1] != clip_frames:
+            raise ValueError("video %d: a frame table is [n_clips, %s], got %s" % (j, clip_frames, tuple(t.shape)))
+    cat = batch_tables(tables, pathway_frames, nums_frames)       # range-checks every table against ITS video
+    clips = [int(torch.as_tensor(t).shape[0]) for t in tables]
+    items_t, video_of, clip_of, row0 = batch_items(clips, len(views))
+    items = (L.ViewItem * items_t.shape[0]).from_buffer_copy(items_t.numpy().tobytes())
+    src_dtype = L.PV_U8 if (is_yuv or dtype == torch.uint8) else L.PV_F32
+    return VideoBatch(videos, sources, items, items_t, cat, video_of, clip_of, clips, row0, len(views), src_dtype, upload)
+
+
 @torch.no_grad()
 def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std=None, div255=False, num_frames=None,
                       dtype=torch.bfloat16, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None):
@@ -479,7 +599,11 @@ class DevicePacker:
     `fill_video(video, tables, i0, n)` + `launch()` run the resampling packer on ONE decoded video instead of clips: items
     [i0, i0 + n) of its clips x views sequence, the clips being rows of a frame table (`data.clip_frame_table`, uploaded by
     `video_tables`) that the ingest kernel reads the video through (`pv_video_views`); `inference.VideoPredictor` is the
-    loop around it."""
+    loop around it.
+
+    `video_batch(videos, tables)` + `fill_batch(batch, i0, n)` + `launch()` do the same for MANY videos of any lengths and
+    frame sizes at once: every item of the deploy batch has a source of its own (`pv_batch_views`), so a forward is filled
+    with views of as many videos as it takes; `inference.VideoBatchPredictor` is the loop around it."""
 
     def __init__(self, deployed, mean=None, std=None, div255=False, frame_ratios=None, short_side=None, crop_size=None,
                  spatial_idx=1, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None):
@@ -760,3 +884,71 @@ class DevicePacker:
             if self.scale is not None:
                 d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
             self.sess.video_views(d, ref, planar=self._planar_for(i, ref))
+
+    # ------------------------------------------------------------------------- many videos per forward (pv_batch_views)
+    def video_batch(self, videos, tables, height=None, coded_height=None):
+        """Prepare a list of decoded videos -- any lengths, any frame sizes, all in the packer's source layout and on the
+        device -- for `fill_batch`: `tables[j]` is the [n_clips_j, clip_frames] frame table of video j
+        (`data.clip_frame_table`).  Every video is validated as `fill_video` validates one (device, dtype, contiguity of the
+        RGB / planar forms, `yuv_geometry` of the YUV forms with `height` / `coded_height` as one number or one per video,
+        the crop fits the scaled frame, every table entry names a frame of ITS video), then the per-video records, the
+        video-major item sequence (video j, then clip * n_views + v) and the concatenated per-pathway tables are uploaded
+        ONCE.  Returns a `VideoBatch`, which keeps the videos alive."""
+        if self.short_side is None:
+            raise RuntimeError("video_batch resamples: construct the packer with short_side and crop_size")
+        if getattr(self.model, "_pv_load_boxes", None) is not None:
+            raise RuntimeError("a detection model takes boxes of key frames, not videos")
+        refs = self.subs[0].refs if self.subs is not None else self.refs
+        for t in tables:
+            t = torch.as_tensor(t)
+            if t.dim() == 2 and t.shape[1] != self.clip_frames:
+                raise ValueError("the deploy form takes clips of %d frames, the table has %d columns" % (self.clip_frames, t.shape[1]))
+        device = torch.device(self.sess.device)
+        return build_video_batch(videos, tables, self.src_layout, self.short_side, self.crop_size, self.views,
+                                 [ref.T for ref in refs], refs[0].C, device, lambda t: t.to(device),
+                                 self.height if height is None else height,
+                                 self.coded_height if coded_height is None else coded_height)
+
+    @torch.no_grad()
+    def fill_batch(self, batch, i0, n):
+        """Fill the deploy form's input buffers with items [i0, i0 + n) of the sequence of `batch` (`video_batch`), n at most
+        the deploy batch: one pv_batch_views launch per pathway (and per sub-plan of a split-batch form -- a sub-plan's window
+        is a pointer offset into the item sequence).  A short chunk zeroes the rest of the buffers, as `fill_video` does.
+        Nothing is launched here but the ingest: run `launch()` next."""
+        if not isinstance(batch, VideoBatch) or batch.n_views != len(self.views):
+            raise RuntimeError("fill_batch takes what video_batch of this packer returned")
+        if not (0 <= i0 and 0 < n <= self.batch and i0 + n <= batch.total):
+            raise RuntimeError("items [%d, %d) are not a chunk of at most %d of the batch's %d items" % (i0, i0 + n, self.batch, batch.total))
+        if self.subs is None:
+            return self._fill_batch(batch, i0, n)
+        lo = 0
+        for sub, b in zip(self.subs, self.model._splits):
+            sub._fill_batch(batch, i0 + lo, max(0, min(b, n - lo)))
+            lo += b
+
+    def release_batch(self):
+        """Drop the packer's reference to the last `VideoBatch` (and with it to all its videos); call once the last forward
+        on it has been launched.  Work already queued stays valid: the memory is reused in stream order."""
+        for p in (self.subs if self.subs is not None else [self]):
+            p._src = None
+
+    def _fill_batch(self, batch, item0, n_items):
+        """One pv_batch_views launch per pathway into this plan's buffers; see Session.video_views for the tail."""
+        import ctypes as C
+        from . import _lib as L
+        self._src = batch                                  # alive until the launch has run
+        for i, (ref, tab) in enumerate(zip(self.refs, batch.tables)):
+            d = L.BatchViewsDesc()
+            d.sources, d.sources_dev = C.addressof(batch.sources), batch.sources_dev.data_ptr()
+            first = min(item0, batch.total - 1) * C.sizeof(L.ViewItem)      # n_items == 0: any valid address, never read
+            d.items, d.items_dev = C.addressof(batch.items) + first, batch.items_dev.data_ptr() + first
+            d.t_index, d.n_rows, d.t_stride = tab.data_ptr(), tab.shape[0], tab.stride(0)
+            d.n_sources, d.n_items, d.C, d.T = len(batch.sources), n_items, ref.C, ref.T
+            d.src_dtype = batch.src_dtype
+            d.src_layout = L.SRC_YUV420 if self.is_yuv else (L.SRC_NCTHW if self.src_layout == "NCTHW" else L.SRC_NTHWC)
+            if self.is_yuv:
+                d.c_step, d.yuv2rgb = (2 if self.src_layout in ("NV12", "NV21") else 1), self.yuv_matrix.data_ptr()
+            d.Ho, d.Wo, d.n_views = self.crop_size, self.crop_size, len(self.views)
+            if self.scale is not None:
+                d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
+            self.sess.batch_views(d, ref, planar=self._planar_for(i, ref))
