@@ -23,3 +23,495 @@ def call(fn_name, desc):
 def rel_err(got, want):
     want = want.float().cpu()
     return (got.float().cpu() - want).abs().max().item() / max(want.abs().max().item(), 1e-6)
+
+
+def _routed_kernel(op, d):
+    """Symbol of the kernel the library routes descriptor `d` to under the current knobs (a one-op plan, profiled once)."""
+    lib = L.lib()
+    plan = lib.pv_plan_create()
+    try:
+        L.check(lib.pv_plan_add(plan, op, C.byref(d), C.sizeof(d)), "pv_plan_add")
+        ms = (C.c_float * 1)()
+        L.check(lib.pv_plan_profile(plan, C.c_void_p(torch.cuda.current_stream().cuda_stream), 1, ms), "pv_plan_profile")
+        return (lib.pv_plan_op_kernel(plan, 0) or b"").decode()
+    finally:
+        lib.pv_plan_destroy(plan)
+
+
+# ------------------------------------------------------------------ pv_misc.hip family: float64 references and checks
+# Everything below runs on the CPU (tests/test_misc_kernel_checks.py feeds the checks their own reference and defective
+# copies of it); tests/test_gpu_misc_kernels.py feeds them what the kernels left on the device.
+#
+# A buffer is a (B, bs) tensor: item b holds R rows of `ld` elements from its start, the rest of the item is the gap behind
+# it.  A launch owns channels [0, written) of the rows it owns; every other element must come back as it went in (the
+# canary, or the input of an in-place launch).
+CANARY = 7.0
+TOL = {torch.float32: 1e-3, torch.bfloat16: 1e-2}
+BF16_ROUND = 2.0 ** -8          # one bf16 rounding, relative (tests/test_transforms.py)
+
+
+def round_up8(c):
+    return (c + 7) // 8 * 8
+
+
+def randn(shape, seed, scale=1.0, shift=0.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(shape, generator=g) * scale + shift
+
+
+def rows_buf(data, ld, dtype, bs=None, written=None):
+    """(B, R, C) values -> (B, bs) buffer: channels [C, written) zero, everything else the canary."""
+    B, R, Cc = data.shape
+    written = round_up8(Cc) if written is None else written
+    buf = torch.full((B, bs or R * ld), CANARY, dtype=dtype)
+    rows = buf[:, :R * ld].view(B, R, ld)
+    rows[..., :Cc] = data.to(dtype)
+    rows[..., Cc:written] = 0
+    return buf
+
+
+def rows_of(buf, R, ld, Cc):
+    return buf[:, :R * ld].view(buf.shape[0], R, ld)[..., :Cc]
+
+
+def canary_buf(B, bs, dtype):
+    return torch.full((B, bs), CANARY, dtype=dtype)
+
+
+def _abs_rel(got, want):
+    want, got = want.double(), got.double()
+    return (got - want).abs().max().item() / max(want.abs().max().item(), 1e-6) if want.numel() else 0.0
+
+
+class Expect:
+    """What one launch must leave in its output buffer.
+
+    want    (B, R, C) reference values (float64; float32 where the kernel's own fp32 order is the reference)
+    before  (B, bs) the buffer as it was handed to the launch
+    tol     bound on max|got - want| / max|want|; None: every owned row is bit-equal to `want` cast to the buffer's dtype
+    per_elem  instead of tol: |got - want| <= per_elem * |want| for every element
+    exact   (B, R) bool: rows that are bit-equal even where `tol` is given
+    owned   (B, R) bool: rows the launch writes (default all)
+    written channels of an owned row the launch writes; [C, written) must be zero (default round_up(C, 8))
+    """
+
+    def __init__(self, want, before, ld, tol=None, per_elem=None, exact=None, owned=None, written=None):
+        self.want, self.before, self.ld, self.tol, self.per_elem = want.cpu(), before.cpu().clone(), ld, tol, per_elem
+        self.B, self.R, self.C = want.shape
+        self.written = round_up8(self.C) if written is None else written
+        full = torch.ones(self.B, self.R, dtype=torch.bool)
+        self.owned = full if owned is None else owned
+        self.exact = (full if tol is None and per_elem is None else ~full) if exact is None else exact
+        assert self.R * ld <= self.before.shape[1] and self.written <= ld and self.before.shape[0] == self.B
+
+    def _rows(self, buf):
+        return buf[:, :self.R * self.ld].view(self.B, self.R, self.ld)
+
+    def ideal(self):
+        """The buffer a kernel that computes the reference exactly leaves."""
+        buf = self.before.clone()
+        rows = self._rows(buf)
+        rows[..., :self.C][self.owned] = self.want.to(buf.dtype)[self.owned]
+        rows[..., self.C:self.written][self.owned] = 0
+        return buf
+
+    def check(self, got, what=""):
+        got = got.detach().cpu()
+        assert got.shape == self.before.shape and got.dtype == self.before.dtype, what
+        g = self._rows(got)
+        data, want, ex = g[..., :self.C][self.owned], self.want[self.owned], self.exact[self.owned]
+        if ex.any():
+            bad = (data[ex] != want[ex].to(got.dtype)).sum().item()
+            assert bad == 0, "%s: %d elements of rows that must be bit-exact differ from the reference" % (what, bad)
+        err = 0.0
+        if (~ex).any():
+            d, w = data[~ex].double(), want[~ex].double()
+            if self.per_elem is not None:
+                err = ((d - w).abs() / w.abs().clamp_min(1e-30)).max().item()
+                assert ((d - w).abs() <= self.per_elem * w.abs()).all(), \
+                    "%s: worst element-wise relative error %.3e > %.3e" % (what, err, self.per_elem)
+            else:
+                err = _abs_rel(d, w)
+                assert err <= self.tol, "%s: error %.3e of the reference abs-max > %.1e" % (what, err, self.tol)
+        pads = g[..., self.C:self.written][self.owned]
+        assert (pads == 0).all(), "%s: %d padding channels of written rows are not zero" % (what, (pads != 0).sum().item())
+        rest_got, rest_before = got.clone(), self.before.clone()
+        self._rows(rest_got)[..., :self.written][self.owned] = 0
+        self._rows(rest_before)[..., :self.written][self.owned] = 0
+        bad = (rest_got != rest_before).sum().item()
+        assert bad == 0, "%s: %d elements the launch does not own (beyond the padding, other rows, gaps) changed" % (what, bad)
+        return err
+
+
+def ref_act(v, act):
+    v = v.double()
+    if act == L.ACT_RELU:
+        return v.clamp_min(0)
+    if act == L.ACT_SWISH:
+        return v * torch.sigmoid(v)
+    if act == L.ACT_GELU:
+        return 0.5 * v * (1 + torch.erf(v * 0.5 ** 0.5))
+    if act == L.ACT_SIGMOID:
+        return torch.sigmoid(v)
+    return v
+
+
+# ---- pv_softmax_rows: p = rows, C, ldx, ldy; i = x (1, rows*ldx), y0 (x itself when in place)
+def expect_softmax(i, p):
+    want = torch.softmax(rows_of(i["x"].cpu(), p["rows"], p["ldx"], p["C"]).double(), -1)
+    return Expect(want, i["y0"], p["ldy"], tol=TOL[i["y0"].dtype], written=p["C"])
+
+
+def check_softmax(got, i, p):
+    err = expect_softmax(i, p).check(got, "pv_softmax_rows")
+    sums = rows_of(got.cpu(), p["rows"], p["ldy"], p["C"]).double().sum(-1)
+    worst = (sums - 1).abs().max().item()
+    assert worst <= TOL[got.dtype], "pv_softmax_rows: a row sums to 1 %+.3e" % worst
+    return err
+
+
+# ---- pv_mean_rows: p = rows, rows_per_batch, C, ldx, ldy; i = x (1, rows*ldx), y0 (1, B*ldy) fp32
+def expect_mean(i, p):
+    x = rows_of(i["x"].cpu(), p["rows"], p["ldx"], p["C"]).double()
+    want = x.reshape(-1, p["rows_per_batch"], p["C"]).mean(1)[None]
+    return Expect(want, i["y0"], p["ldy"], tol=TOL[i["x"].dtype], written=p["C"])
+
+
+def check_mean(got, i, p):
+    return expect_mean(i, p).check(got, "pv_mean_rows")
+
+
+# ---- pv_add_posenc: p = B, T, HW, C, ld, cls_only; i = x (1, B*rows*ld) in place, cls_token | None, pos_spatial,
+# pos_temporal | None (None: pos_spatial is the full table), pos_class | None
+def expect_posenc(i, p):
+    B, T, HW, Cc, ld = p["B"], p["T"], p["HW"], p["C"], p["ld"]
+    x0 = i["x"].cpu()
+    cls, ps, pt, pc = (None if i[k] is None else i[k].cpu() for k in ("cls_token", "pos_spatial", "pos_temporal", "pos_class"))
+    has_cls = int(cls is not None)
+    R = T * HW + has_cls
+    # fp32: one or two fp32 adds in the kernel's order, x + (pos_spatial + pos_temporal), bit for bit; bf16: float64
+    wide = torch.float32 if x0.dtype == torch.float32 else torch.float64
+    x = rows_of(x0, B * R, ld, Cc).to(wide).reshape(B, R, Cc).clone()
+    ps, pt, pc, clsw = (None if t is None else t.to(wide) for t in (ps, pt, pc, cls))
+    if pt is not None:
+        table = (ps[None, :, :] + pt[:, None, :]).reshape(T * HW, Cc)
+        cls_row = None if cls is None else (clsw + pc if pc is not None else clsw)
+    else:
+        table = ps[has_cls:]
+        cls_row = None if cls is None else clsw + ps[0]
+    x[:, has_cls:] = x[:, has_cls:] + table
+    if has_cls:
+        x[:, 0] = cls_row
+    owned = torch.ones(B, R, dtype=torch.bool)
+    if p["cls_only"]:
+        owned[:, 1:] = False
+    tol = None if x0.dtype == torch.float32 else TOL[x0.dtype]
+    return Expect(x.view(1, B * R, Cc), x0, ld, tol=tol, owned=owned.view(1, B * R))
+
+
+def check_posenc(got, i, p):
+    return expect_posenc(i, p).check(got, "pv_add_posenc")
+
+
+# ---- pv_add_act: p = rows, C, lda, ldb, ldy, act; i = a, b, y0 (a itself when y aliases a)
+def expect_add_act(i, p):
+    a = rows_of(i["a"].cpu(), p["rows"], p["lda"], p["C"]).double()
+    b = rows_of(i["b"].cpu(), p["rows"], p["ldb"], p["C"]).double()
+    return Expect(ref_act(a + b, p["act"]), i["y0"], p["ldy"], tol=TOL[i["y0"].dtype])
+
+
+def check_add_act(got, i, p):
+    return expect_add_act(i, p).check(got, "pv_add_act")
+
+
+# ---- pv_pool3d: p = B, T, H, W, C, k, s, p (pad), mode, n_prefix, ldx, ldy; i = x (B, x_bs), y0 (B, y_bs)
+def pool_out_dims(p):
+    return tuple((n + 2 * pd - k) // s + 1 for n, k, s, pd in zip((p["T"], p["H"], p["W"]), p["k"], p["s"], p["p"]))
+
+
+def ref_pool(grid, k, s, pad, mode, drop=None):
+    """MaxPool3d / AvgPool3d (count_include_pad) of a (B, T, H, W, C) float64 grid, one window tap at a time.
+    drop = (b, to, ho, wo, (dt, dh, dw)): that tap is left out of that one window (a defect for the checks' own test)."""
+    is_max = mode == L.POOL_MAX
+    fill = float("-inf") if is_max else 0.0
+    B, T, H, W, Cc = grid.shape
+    xp = torch.full((B, T + 2 * pad[0], H + 2 * pad[1], W + 2 * pad[2], Cc), fill, dtype=torch.float64)
+    xp[:, pad[0]:pad[0] + T, pad[1]:pad[1] + H, pad[2]:pad[2] + W] = grid
+    To, Ho, Wo = ((n + 2 * pd - kk) // ss + 1 for n, kk, ss, pd in zip((T, H, W), k, s, pad))
+    out = torch.full((B, To, Ho, Wo, Cc), fill, dtype=torch.float64)
+    for dt in range(k[0]):
+        for dh in range(k[1]):
+            for dw in range(k[2]):
+                tap = xp[:, dt:dt + (To - 1) * s[0] + 1:s[0], dh:dh + (Ho - 1) * s[1] + 1:s[1], dw:dw + (Wo - 1) * s[2] + 1:s[2]]
+                if drop is not None and drop[4] == (dt, dh, dw):
+                    tap = tap.clone()
+                    tap[drop[0], drop[1], drop[2], drop[3]] = fill
+                out = torch.maximum(out, tap) if is_max else out + tap
+    return out if is_max else out / (k[0] * k[1] * k[2])
+
+
+def expect_pool(i, p, drop=None):
+    B, T, H, W, Cc, npre = p["B"], p["T"], p["H"], p["W"], p["C"], p["n_prefix"]
+    x = rows_of(i["x"].cpu(), npre + T * H * W, p["ldx"], Cc).double()
+    To, Ho, Wo = pool_out_dims(p)
+    pooled = ref_pool(x[:, npre:].reshape(B, T, H, W, Cc), p["k"], p["s"], p["p"], p["mode"], drop)
+    want = torch.cat([x[:, :npre], pooled.reshape(B, To * Ho * Wo, Cc)], 1)
+    exact = torch.ones(B, want.shape[1], dtype=torch.bool)      # prefix rows are copies; a maximum does no arithmetic
+    if p["mode"] != L.POOL_MAX:
+        exact[:, npre:] = False
+    return Expect(want, i["y0"], p["ldy"], tol=TOL[i["y0"].dtype], exact=exact)
+
+
+def check_pool(got, i, p):
+    return expect_pool(i, p).check(got, "pv_pool3d")
+
+
+# ---- pv_layernorm: p = rows, C, ldx, ldy, eps, g_period; i = x (1, rows*ldx; fp32 when x_f32), gamma, beta
+# ((max(g_period, 1), C) or None), y0
+def ref_layernorm(x, gamma, beta, eps, period, wrong_row=None):
+    """wrong_row = r: row r takes its gamma / beta from the neighbouring period (table row (r + 1) % period)."""
+    x = x.double()
+    mean = x.mean(-1, keepdim=True)
+    var = ((x - mean) ** 2).mean(-1, keepdim=True)
+    y = (x - mean) / torch.sqrt(var + eps)
+    idx = torch.arange(x.shape[0]) % max(period, 1)
+    if wrong_row is not None:
+        idx[wrong_row] = (idx[wrong_row] + 1) % max(period, 1)
+    if gamma is not None:
+        y = y * gamma.double()[idx]
+    if beta is not None:
+        y = y + beta.double()[idx]
+    return y
+
+
+def expect_layernorm(i, p, wrong_row=None):
+    x = rows_of(i["x"].cpu(), p["rows"], p["ldx"], p["C"])[0]
+    g, b = (None if i[k] is None else i[k].cpu().view(max(p["g_period"], 1), p["C"]) for k in ("gamma", "beta"))
+    want = ref_layernorm(x, g, b, p["eps"], p["g_period"], wrong_row)[None]
+    return Expect(want, i["y0"], p["ldy"], tol=TOL[i["y0"].dtype])
+
+
+def check_layernorm(got, i, p):
+    return expect_layernorm(i, p).check(got, "pv_layernorm")
+
+
+# ---- pv_affine_rows: p = rows, C, ldx, ldy, act, n_prefix, rows_per_batch; i = x, gamma, beta, y0 (x itself in place)
+def expect_affine(i, p):
+    x = rows_of(i["x"].cpu(), p["rows"], p["ldx"], p["C"])[0].double()
+    v = x
+    if i["gamma"] is not None:
+        v = v * i["gamma"].cpu().double()
+    if i["beta"] is not None:
+        v = v + i["beta"].cpu().double()
+    want = ref_act(v, p["act"])
+    owned = torch.ones(1, p["rows"], dtype=torch.bool)
+    exact = ~owned
+    if p["rows_per_batch"] > 0 and p["n_prefix"] > 0:
+        skip = (torch.arange(p["rows"]) % p["rows_per_batch"]) < p["n_prefix"]
+        want[skip] = x[skip]                       # out of place the prefix rows are copied through
+        exact[0, skip] = i["y0"].dtype == i["x"].dtype
+        if p["inplace"]:
+            owned[0, skip] = False                 # in place they are not touched at all
+    return Expect(want[None], i["y0"], p["ldy"], tol=TOL[i["y0"].dtype], exact=exact, owned=owned)
+
+
+def check_affine(got, i, p):
+    return expect_affine(i, p).check(got, "pv_affine_rows")
+
+
+# ---- pv_se_gate: p = B, C, c_p, cr, nblk, inv_count; i = psum (B, nblk, c_p), w1, b1, w2, b2, y0 (B, c_p)
+def expect_se_gate(i, p):
+    Cc = p["C"]
+    mean = i["psum"].cpu().double().sum(1)[:, :Cc] * p["inv_count"]
+    hid = (mean @ i["w1"].cpu().double().t() + i["b1"].cpu().double()).clamp_min(0)
+    want = torch.sigmoid(hid @ i["w2"].cpu().double().t() + i["b2"].cpu().double())
+    return Expect(want[:, None], i["y0"], p["c_p"], tol=1e-5, written=p["c_p"])
+
+
+def check_se_gate(got, i, p):
+    return expect_se_gate(i, p).check(got, "pv_se_gate")
+
+
+# ---- pv_ingest_ncdhw: p = B, C, T, H, W, c_p, ld; i = src (B, C, src_T, H, W), t_index | None, ch_scale | None,
+# ch_shift | None, y0 (B, bs)
+def _layout_bound(src_dtype, dst_dtype, affine):
+    """Keyword arguments of Expect for a layout change: exact where nothing rounds, one bf16 rounding where it narrows."""
+    if affine:
+        return dict(tol=TOL[torch.float32] if dst_dtype == torch.float32 else BF16_ROUND)
+    if src_dtype == torch.float32 and dst_dtype == torch.bfloat16:
+        return dict(per_elem=BF16_ROUND)
+    return dict()
+
+
+def expect_ingest(i, p):
+    src = i["src"].cpu().double()
+    if i["t_index"] is not None:
+        src = src[:, :, i["t_index"].cpu().long()]
+    if i["ch_scale"] is not None:
+        src = src * i["ch_scale"].cpu().double().view(1, -1, 1, 1, 1)
+        if i["ch_shift"] is not None:
+            src = src + i["ch_shift"].cpu().double().view(1, -1, 1, 1, 1)
+    want = src.permute(0, 2, 3, 4, 1).reshape(p["B"], p["T"] * p["H"] * p["W"], p["C"])
+    return Expect(want, i["y0"], p["ld"], written=p["c_p"],
+                  **_layout_bound(i["src"].dtype, i["y0"].dtype, i["ch_scale"] is not None))
+
+
+def check_ingest(got, i, p):
+    return expect_ingest(i, p).check(got, "pv_ingest_ncdhw")
+
+
+# ---- pv_egress_ncdhw: p = B, C, T, H, W, c_p, ld; i = src (B, bs) NDHWC rows, y0 (1, B*C*T*H*W + tail) contiguous NCDHW
+def expect_egress(i, p):
+    S3 = p["T"] * p["H"] * p["W"]
+    rows = rows_of(i["src"].cpu(), S3, p["ld"], p["C"]).double()
+    want = rows.permute(0, 2, 1).reshape(1, p["B"] * p["C"] * S3, 1)
+    return Expect(want, i["y0"], 1, written=1, **_layout_bound(i["src"].dtype, i["y0"].dtype, False))
+
+
+def check_egress(got, i, p):
+    return expect_egress(i, p).check(got, "pv_egress_ncdhw")
+
+
+# ---- pv_ensemble_scores: p = N, C, ld, V, mode; i = logits (1, N*ld), video_index (N), accum0 (V, C), counts0 (V)
+# got = (accum, counts)
+def expect_ensemble(i, p):
+    x = rows_of(i["logits"].cpu(), p["N"], p["ld"], p["C"])[0].double()
+    acc, cnt = i["accum0"].cpu().double().clone(), i["counts0"].cpu().clone()
+    seen = torch.zeros(p["V"], dtype=torch.bool)
+    for n, v in enumerate(i["video_index"].cpu().tolist()):
+        if v < 0 or v >= p["V"]:
+            continue
+        pr = torch.softmax(x[n], -1)
+        acc[v] = torch.maximum(acc[v], pr) if p["mode"] == 1 else acc[v] + pr
+        cnt[v] += 1
+        seen[v] = True
+    return Expect(acc[None], i["accum0"].cpu().view(1, -1), p["C"], tol=TOL[torch.float32], exact=~seen[None], written=p["C"]), cnt
+
+
+def check_ensemble(got, i, p):
+    e, cnt = expect_ensemble(i, p)
+    err = e.check(got[0].view(1, -1), "pv_ensemble_scores")
+    assert torch.equal(got[1].cpu(), cnt), "pv_ensemble_scores: counts %s, want %s" % (got[1].cpu().tolist(), cnt.tolist())
+    return err
+
+
+# ---- case builders (CPU tensors; the GPU tests move them to the device) ----------------------------------------------
+def make_softmax(dtype, rows, Cc, inplace, seed=701):
+    x = randn((1, rows, Cc), seed, 3.0).to(dtype).float()
+    x[0, 0] = torch.where(torch.arange(Cc) % 2 == 0, 80.0, -80.0)      # the max subtraction matters
+    if rows > 1:
+        x[0, rows - 1] = 1.25                                           # a row of equal values
+    ldx = round_up8(Cc) + 8
+    ldy = ldx if inplace else ldx + 16
+    xb = rows_buf(x, ldx, dtype)
+    return dict(x=xb, y0=xb if inplace else canary_buf(1, rows * ldy, dtype)), dict(rows=rows, C=Cc, ldx=ldx, ldy=ldy)
+
+
+def make_mean(dtype, B, rpb, Cc, seed=711):
+    ldx, ldy = round_up8(Cc) + 8, round_up8(Cc) + 16
+    x = rows_buf(randn((1, B * rpb, Cc), seed, 1.0, 0.5), ldx, dtype)
+    return dict(x=x, y0=canary_buf(1, B * ldy, torch.float32)), dict(rows=B * rpb, rows_per_batch=rpb, C=Cc, ldx=ldx, ldy=ldy)
+
+
+POSENC_FORMS = {          # form: (cls token, separable tables, pos_class)
+    "sep_cls_posclass": (True, True, True), "sep_cls": (True, True, False), "sep_nocls": (False, True, False),
+    "full_cls": (True, False, False), "full_nocls": (False, False, False),
+}
+
+
+def make_posenc(dtype, form, Cc, ld, cls_only=0, B=2, T=3, HW=5, seed=721):
+    cls, sep, pc = POSENC_FORMS[form]
+    R = T * HW + int(cls)
+    x = rows_buf(randn((1, B * R, Cc), seed), ld, dtype)
+    i = dict(x=x, cls_token=randn((Cc,), seed + 1) if cls else None,
+             pos_spatial=randn((HW if sep else R, Cc), seed + 2), pos_temporal=randn((T, Cc), seed + 3) if sep else None,
+             pos_class=randn((Cc,), seed + 4) if pc else None)
+    return i, dict(B=B, T=T, HW=HW, C=Cc, ld=ld, cls_only=cls_only)
+
+
+def make_add_act(dtype, rows, Cc, act, alias, seed=731):
+    lda, ldb, ldy = round_up8(Cc) + 8, round_up8(Cc), round_up8(Cc) + 16
+    if alias:
+        ldy = lda
+    a = rows_buf(randn((1, rows, Cc), seed, 2.0), lda, dtype)
+    b = rows_buf(randn((1, rows, Cc), seed + 1, 2.0), ldb, dtype)
+    return dict(a=a, b=b, y0=a if alias else canary_buf(1, rows * ldy, dtype)), dict(rows=rows, C=Cc, lda=lda, ldb=ldb, ldy=ldy, act=act)
+
+
+def make_pool(dtype, B, T, H, W, Cc, k, s, pad, mode, n_prefix=0, gap=0, seed=741):
+    p = dict(B=B, T=T, H=H, W=W, C=Cc, k=tuple(k), s=tuple(s), p=tuple(pad), mode=mode, n_prefix=n_prefix)
+    cp = round_up8(Cc)
+    p["ldx"], p["ldy"] = cp + (8 if gap else 0), cp + (16 if gap else 0)
+    To, Ho, Wo = pool_out_dims(p)
+    Rx, Ry = n_prefix + T * H * W, n_prefix + To * Ho * Wo
+    p["x_bs"], p["y_bs"] = Rx * p["ldx"] + gap, Ry * p["ldy"] + 2 * gap
+    x = rows_buf(randn((B, Rx, Cc), seed), p["ldx"], dtype, bs=p["x_bs"])
+    return dict(x=x, y0=canary_buf(B, p["y_bs"], dtype)), p
+
+
+def make_layernorm(dtype, rows, Cc, x_f32=False, g_period=0, gamma=True, beta=True, ramp=False, seed=751):
+    ldx, ldy = round_up8(Cc) + 8, round_up8(Cc) + 16
+    x = rows_buf(randn((1, rows, Cc), seed, 2.0, 0.5), ldx, torch.float32 if x_f32 else dtype)
+    P = max(g_period, 1)
+    g = randn((P, Cc), seed + 1, 0.3, 1.0) if gamma else None
+    if ramp:                                  # table rows a wrong period cannot be mistaken for: gamma row i = 1 + i
+        g = (1.0 + torch.arange(P, dtype=torch.float32))[:, None].repeat(1, Cc)
+    b = randn((P, Cc), seed + 2, 0.5) if beta else None
+    return (dict(x=x, gamma=g, beta=b, y0=canary_buf(1, rows * ldy, dtype)),
+            dict(rows=rows, C=Cc, ldx=ldx, ldy=ldy, eps=1e-6, g_period=g_period, x_f32=int(x_f32)))
+
+
+def make_affine(dtype, rows, Cc, x_f32, inplace, act, n_prefix=0, rpb=0, seed=761):
+    ldx = round_up8(Cc) + 8
+    ldy = ldx if inplace else ldx + 8
+    x = rows_buf(randn((1, rows, Cc), seed), ldx, torch.float32 if x_f32 else dtype)
+    g, b = randn((Cc,), seed + 1, 0.3, 1.0), randn((Cc,), seed + 2, 0.4)
+    return (dict(x=x, gamma=g, beta=b, y0=x if inplace else canary_buf(1, rows * ldy, dtype)),
+            dict(rows=rows, C=Cc, ldx=ldx, ldy=ldy, act=act, n_prefix=n_prefix, rows_per_batch=rpb, x_f32=int(x_f32), inplace=inplace))
+
+
+def make_se_gate(B, Cc, cr, nblk, extra_pad=0, seed=771):
+    cp = round_up8(Cc) + extra_pad
+    psum = torch.zeros(B, nblk, cp)
+    psum[..., :Cc] = randn((B, nblk, Cc), seed, 3.0)
+    i = dict(psum=psum, w1=randn((cr, Cc), seed + 1, Cc ** -0.5), b1=randn((cr,), seed + 2),
+             w2=randn((Cc, cr), seed + 3, cr ** -0.5), b2=randn((Cc,), seed + 4), y0=canary_buf(B, cp, torch.float32))
+    return i, dict(B=B, C=Cc, c_p=cp, cr=cr, nblk=nblk, inv_count=1.0 / 777.0)
+
+
+def _src_values(shape, dtype, seed):
+    if dtype == torch.uint8:
+        return torch.randint(0, 256, shape, generator=torch.Generator().manual_seed(seed), dtype=torch.uint8)
+    return randn(shape, seed, 2.0).to(dtype)
+
+
+def make_ingest(src_dtype, dst_dtype, Cc, H, W, c_p, ld, affine, shift=True, misalign=False, B=2, T=3, src_T=5, gap=16, seed=781):
+    """affine: frame selection (t_index) and the per-channel map ride along, as the data pipeline uses them."""
+    Ts = src_T if affine else T
+    n = B * Cc * Ts * H * W
+    flat = _src_values((n + 1,), src_dtype, seed)
+    src = (flat[1:] if misalign else flat[:n]).view(B, Cc, Ts, H, W)      # misalign: one element past the allocation's start
+    bs = T * H * W * ld + gap
+    i = dict(src=src, t_index=None, ch_scale=None, ch_shift=None, y0=canary_buf(B, bs, dst_dtype))
+    if affine:
+        i["t_index"] = torch.tensor([4, 0, 2], dtype=torch.int32)[:T]
+        i["ch_scale"] = randn((Cc,), seed + 1, 0.1, 1.0) / (255.0 if src_dtype == torch.uint8 else 1.0)
+        i["ch_shift"] = randn((Cc,), seed + 2, 0.5) if shift else None
+    return i, dict(B=B, C=Cc, T=T, H=H, W=W, c_p=c_p, ld=ld, bs=bs, src_T=Ts)
+
+
+def make_egress(src_dtype, dst_dtype, Cc=11, c_p=16, ld=24, B=2, T=3, H=5, W=7, gap=16, seed=791):
+    S3 = T * H * W
+    bs = S3 * ld + gap
+    src = rows_buf(randn((B, S3, Cc), seed, 2.0), ld, src_dtype, bs=bs, written=c_p)
+    return dict(src=src, y0=canary_buf(1, B * Cc * S3 + 16, dst_dtype)), dict(B=B, C=Cc, T=T, H=H, W=W, c_p=c_p, ld=ld, bs=bs)
+
+
+def make_ensemble(mode, seed=801):
+    N, Cc, V = 11, 13, 4
+    ld = Cc + 8
+    idx = torch.tensor([0, 1, 2, 0, -1, 1, 2, V, 0, 1, 2], dtype=torch.int32)     # video 3 gets no clip; -1 and V are ignored
+    logits = rows_buf(randn((1, N, Cc), seed, 3.0), ld, torch.float32, written=Cc)
+    accum0 = torch.rand((V, Cc), generator=torch.Generator().manual_seed(seed + 1)) * (0.2 if mode == 1 else 1.0)
+    return (dict(logits=logits, video_index=idx, accum0=accum0, counts0=torch.tensor([3, 0, 5, 2], dtype=torch.int32)),
+            dict(N=N, C=Cc, ld=ld, V=V, mode=mode))

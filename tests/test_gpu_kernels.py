@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from pytorchvideo_amd import _lib as L
-from gpu_util import call, pv_dtype, rel_err
+from gpu_util import _routed_kernel, call, pv_dtype, rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = {torch.float32: 1e-3, torch.bfloat16: 1e-2}
@@ -947,20 +947,6 @@ def test_lateral_fusion_writes_the_slow_buffers_channel_slice(dtype, B, Ti, H, W
 
 
 # ------------------------------------------------------------------ large-tile GEMM (256-voxel tiles, 4-stage LDS ring)
-def _routed_kernel(op, d):
-    """Symbol of the kernel the library routes descriptor `d` to under the current knobs (a one-op plan, profiled once)."""
-    import ctypes as C
-    lib = L.lib()
-    plan = lib.pv_plan_create()
-    try:
-        L.check(lib.pv_plan_add(plan, op, C.byref(d), C.sizeof(d)), "pv_plan_add")
-        ms = (C.c_float * 1)()
-        L.check(lib.pv_plan_profile(plan, C.c_void_p(torch.cuda.current_stream().cuda_stream), 1, ms), "pv_plan_profile")
-        return (lib.pv_plan_op_kernel(plan, 0) or b"").decode()
-    finally:
-        lib.pv_plan_destroy(plan)
-
-
 def _gemm8_case(ct, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, knob="gemm8"):
     """pv_conv3d forced onto a large-tile kernel (pv_tune gemm8 = 2 | 4, or gemm9 = 2) vs torch on the same bf16-rounded data."""
     dtype = torch.bfloat16
