@@ -532,6 +532,46 @@ typedef struct pv_batch_views_desc {
 } pv_batch_views_desc;
 int pv_batch_views(const pv_batch_views_desc* d, pv_stream_t stream);
 
+/* ---- key-frame detection: the boxes of a forward mapped into its views, on the device ---------------------------------
+ * A detection forward built by pv_batch_views holds one clip per key frame, and every key frame has person boxes given in the
+ * pixels of ITS source frame.  pv_box_views fills the RoI head's persistent [capacity][5] fp32 box buffer (what pv_roi_align
+ * reads at replay time) for one forward from the box list of the whole call, which was uploaded once: one launch, one thread
+ * per destination row, no host arithmetic and no host-to-device copy per forward.
+ * Boxes:        boxes[n_boxes][4] fp32 (x1, y1, x2, y2) in source pixels, FINITE (a NaN is not propagated the way
+ *               torch.clamp propagates it); box_item[n_boxes] int32, non-decreasing: the position, in the call's item
+ *               sequence items_dev[n_seq], of the key frame the box belongs to.
+ * Window:       the launch maps boxes [box0, box0 + n_launch) for the forward that holds items [item0, item0 + n_items) of
+ *               the sequence -- the window pv_batch_views was given for the same forward, read through the same
+ *               sources_dev / items_dev records (Hs, Ws, Hn, Wn, y_off[view], x_off[view]); source and view are clamped
+ *               into range before they are used, as pv_batch_views clamps them.
+ * Rows:         i < n_launch: {box_item - item0, x1', y1', x2', y2'}; a box whose box_item - item0 is outside [0, n_items)
+ *               gets {-1, 0, 0, 0, 0} and nothing is read through it.  n_launch <= i < capacity: {-1, 0, 0, 0, 0}
+ *               (pv_roi_align answers zeros for a clip index outside the batch).  dst_box[capacity], when given: box0 + i,
+ *               and -1 on the tail.  Nothing beyond `capacity` rows is touched.
+ * Arithmetic:   per coordinate, every operation rounded on its own in fp32 (no contraction), shown for x (y: Hs, Hn, y_off,
+ *               Ho):  clip_to_source ? v = min(max(v, 0), Ws - 1) : v;
+ *                     v = v * r,  r = Ws < Hs ? (float)((double)Hn / (double)Hs) : (float)((double)Wn / (double)Ws);
+ *                     v = v - (float)x_off;   v = min(max(v, 0), Wo - 1)
+ *               -- clip_boxes_to_image, short_side_scale_with_boxes (ONE ratio, the longer side's, for x and y),
+ *               crop_boxes and clip_boxes_to_image of the reference (transforms/functional.py:195-231,407-446), bit for
+ *               bit what transforms.boxes_to_view gives on the host.
+ * PV_ERR_INVALID: null boxes / box_item / sources_dev / items_dev / dst; capacity, n_items, Ho, Wo, n_sources <= 0;
+ * n_views outside 1..3; n_launch < 0 or > capacity; box0 < 0 or box0 + n_launch > n_boxes; item0 < 0 or
+ * item0 + n_items > n_seq.  n_launch == 0 is valid and writes only the tail.  Validation precedes every HIP call.
+ */
+typedef struct pv_box_views_desc {
+  const float* boxes;                 /* [n_boxes][4] on the device                                            */
+  const int32_t* box_item;            /* [n_boxes] on the device                                               */
+  const pv_view_source* sources_dev;  /* [n_sources] on the device: the records pv_batch_views reads           */
+  const pv_view_item* items_dev;      /* [n_seq] on the device: the call's WHOLE item sequence                 */
+  float* dst;                         /* [capacity][5] on the device                                           */
+  int32_t* dst_box;                   /* [capacity] on the device, or NULL                                     */
+  int32_t n_boxes, n_seq, n_sources, n_views;
+  int32_t box0, n_launch, item0, n_items;
+  int32_t Ho, Wo, capacity, clip_to_source;
+} pv_box_views_desc;
+int pv_box_views(const pv_box_views_desc* d, pv_stream_t stream);
+
 /* ---- row ops on (rows, C) matrices -------------------------------------------------
  * pv_layernorm: nn.LayerNorm(eps) over C (models/vision_transformers.py:333-335,
  *   layers/attention.py:199-205).

@@ -145,7 +145,9 @@ class Mi355xMultiPathBlock(Mi355xBlock):
 
 class Mi355xRoIHeadBlock(Mi355xBlock):
     """ResNetRoIHead (models/head.py:394-482): forward(x, bboxes).  The deploy form is specialised to the
-    feature size AND the number of boxes; the box values are read on the device at every replay."""
+    feature size AND the number of boxes; the box values are read on the device at every replay.  forward(x, bboxes) takes
+    exactly that number; the key-frame path (transforms.DevicePacker.fill_boxes -> Session.box_views) treats it as the CAPACITY
+    of the buffer and fills the rows it does not use with clip index -1, which pv_roi_align answers with zeros."""
 
     def convert(self, input_blob_size, *args, session=None, input_ref=None, dtype=None, num_boxes=None, **kwargs):
         assert self.convert_flag is False, "already converted, cannot be converted again"

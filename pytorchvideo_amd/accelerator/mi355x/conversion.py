@@ -382,6 +382,9 @@ def _convert_detection(model, inputs, dtype, use_graph, kwargs):
         converted.__dict__["_pv_inputs"] = first_in   # transforms.DevicePacker: packed clip + boxes -> one replay
         converted.__dict__["_pv_load_boxes"] = lambda b: sess.load_boxes(b, head._boxes, head._num_boxes)
         converted.__dict__["_pv_result"] = lambda: head._result().reshape(head._num_boxes, -1)
+        # the key-frame path (transforms.DevicePacker.fill_boxes): the box buffer is filled on the device, up to its capacity
+        converted.__dict__["_pv_box_ptr"] = head._boxes
+        converted.__dict__["_pv_box_capacity"] = head._num_boxes
     else:
         _convert_children(converted, lut, batch, "", sess, dtype, kwargs)
     sess.finalize()

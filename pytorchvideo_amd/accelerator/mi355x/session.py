@@ -418,6 +418,15 @@ class Session:
         """`video_views` for a BatchViewsDesc (one source per item: pv_batch_views; transforms.DevicePacker.fill_batch)."""
         self._views_into(d, d.C, ref, planar, "pv_batch_views")
 
+    def box_views(self, d, ptr):
+        """Fill a detection head's box buffer `ptr` (`alloc_boxes`) by pv_box_views: `d` is a BoxViewsDesc whose boxes, item
+        window, records and capacity the caller (transforms.DevicePacker.fill_boxes) has set; the destination is filled in
+        here.  Like the ingest it runs on the launch stream in front of the replay, outside the captured graph."""
+        assert ptr.space == "weights"
+        d.dst = self.weights_t.data_ptr() + ptr.off
+        with torch.cuda.device(self.device):
+            L.check(L.lib().pv_box_views(C.byref(d), self._stream()), "box_views")
+
     def _views_into(self, d, channels, ref, planar, entry):
         n = d.n_items
         if not 0 <= n <= ref.B or (channels, d.T, d.Ho, d.Wo) != (ref.C, ref.T, ref.H, ref.W):

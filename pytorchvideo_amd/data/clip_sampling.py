@@ -119,6 +119,23 @@ class ConstantClipsPerVideoSampler(ClipSampler):
         self._current_aug_index = 0
 
 
+class TimeStampClipSampler:
+    """data/ava.py:282-318: the clip of `clip_sampler`'s duration CENTRED on the time stamp `annotation["clip_index"]` --
+    [t - d/2, t - d/2 + d) -- for datasets such as AVA where only key frames are annotated.  clip_index, aug_index and
+    is_last_clip are always 0, 0 and True.  As there, d is halved by the float 2.0, so the times are floats."""
+
+    def __init__(self, clip_sampler: ClipSampler) -> None:
+        self.clip_sampler = clip_sampler
+
+    def __call__(self, last_clip_time, video_duration, annotation: Dict[str, Any]) -> ClipInfo:
+        center_frame_sec = annotation["clip_index"]          # a.k.a. the time stamp
+        clip_start_sec = center_frame_sec - self.clip_sampler._clip_duration / 2.0
+        return ClipInfo(clip_start_sec, clip_start_sec + self.clip_sampler._clip_duration, 0, 0, True)
+
+    def reset(self) -> None:
+        pass
+
+
 def make_clip_sampler(sampling_type: str, *args) -> ClipSampler:
     """"uniform" -> UniformClipSampler(*args); "constant_clips_per_video" -> ConstantClipsPerVideoSampler(*args)."""
     if sampling_type == "uniform":
@@ -143,6 +160,19 @@ def sample_clips(sampler: ClipSampler, video_duration) -> List[ClipInfo]:
             return clips
 
 
+def clip_frame_range(start_sec, end_sec, num_frames: int, fps: Fraction, what: str = "clip") -> Tuple[int, int]:
+    """The frames range(first, stop) of an N-frame video that the clip [start_sec, end_sec) covers (frame_video.py:149-200):
+    first = ceil(fps * start), stop = min(ceil(fps * min(end, duration)), N) with duration = N / fps -- a window that ends
+    past the video is cut.  ValueError when the window starts before 0 or behind the video, or holds no frame."""
+    duration = Fraction(num_frames) / fps
+    start, end = Fraction(start_sec), min(Fraction(end_sec), duration)
+    first = math.ceil(fps * start)
+    stop = min(math.ceil(fps * end), num_frames)
+    if start < 0 or start > duration or stop <= first:
+        raise ValueError("%s [%s, %s) s holds no frame of a %d-frame video at %s fps" % (what, start_sec, end_sec, num_frames, fps))
+    return first, stop
+
+
 def clip_frame_table(sampler: ClipSampler, num_frames: int, fps, frames_per_clip: int):
     """(int32 [n_clips, frames_per_clip] tensor, [ClipInfo]): row i holds the frames of the video that clip i of `sampler`
     consists of.  A clip [start, end) covers frames range(ceil(fps * start), min(ceil(fps * min(end, duration)), N)) with
@@ -159,15 +189,36 @@ def clip_frame_table(sampler: ClipSampler, num_frames: int, fps, frames_per_clip
     for info in sample_clips(sampler, duration):
         if infos and info.clip_index == infos[-1].clip_index and info.aug_index != 0:
             continue
-        start, end = Fraction(info.clip_start_sec), min(Fraction(info.clip_end_sec), duration)
-        first = math.ceil(fps * start)
-        stop = min(math.ceil(fps * end), num_frames)
-        if start < 0 or start > duration or stop <= first:
-            raise ValueError("clip %d [%s, %s) s holds no frame of a %d-frame video at %s fps"
-                             % (info.clip_index, info.clip_start_sec, info.clip_end_sec, num_frames, fps))
+        first, stop = clip_frame_range(info.clip_start_sec, info.clip_end_sec, num_frames, fps, "clip %d" % info.clip_index)
         rows.append(first + temporal_indices(stop - first, frames_per_clip))
         infos.append(info)
     table = torch.stack(rows).to(torch.int32)
     if int(table.min()) < 0 or int(table.max()) >= num_frames:
         raise ValueError("frame table leaves the video [0, %d)" % num_frames)
     return table, infos
+
+
+def keyframe_frame_table(timestamps, clip_duration, num_frames: int, fps, frames_per_clip: int):
+    """(int32 [K, frames_per_clip] tensor, centre_frames [K]): row k holds the frames of the clip that `TimeStampClipSampler`
+    cuts around key-frame time stamp `timestamps[k]` (seconds) -- the window [t - d/2, t - d/2 + d) of data/ava.py:310-315
+    under the frame rule of `clip_frame_table` (a window that ends past the video is cut), the window computed in exact
+    `Fraction` arithmetic on the numbers given (the sampler itself divides by the float 2.0, which can move a window edge
+    that falls exactly on a frame by one frame) -- and `centre_frames[k]` the middle
+    frame of that window, frames[len(frames) // 2]: the one the detection tutorial hands to the person detector
+    (inp_imgs[:, shape[1] // 2]).  ValueError for a window that starts before 0 or holds no frame."""
+    import torch
+    from ..transforms import temporal_indices
+    if num_frames <= 0 or frames_per_clip <= 0 or fps <= 0:
+        raise ValueError("num_frames, fps and frames_per_clip are positive")
+    stamps = list(timestamps)
+    if not stamps:
+        raise ValueError("no time stamps")
+    fps = Fraction(fps)
+    duration = Fraction(clip_duration)
+    rows, centres = [], []
+    for k, t in enumerate(stamps):
+        start = Fraction(t) - duration / 2
+        first, stop = clip_frame_range(start, start + duration, num_frames, fps, "key frame %d (t = %s s):" % (k, t))
+        rows.append(first + temporal_indices(stop - first, frames_per_clip))
+        centres.append(first + (stop - first) // 2)
+    return torch.stack(rows).to(torch.int32), centres

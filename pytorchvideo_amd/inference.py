@@ -11,10 +11,15 @@ the last chunk may be short, so a video of any length runs on a form converted f
 `VideoBatchPredictor` scores MANY videos per call -- a dataset evaluation -- with every forward filled by views of as many
 videos as it takes (`pv_batch_views`: one source per item of the deploy batch), one table upload and at most one short chunk
 per call instead of one of each per video.
+
+`KeyframeDetector` is the same for the detection models: the reference's AVA recipe (the detection tutorial with
+data/ava.py's `TimeStampClipSampler`) -- a clip around every key-frame time stamp, a variable number of person boxes per key
+frame given in the pixels of the source frame -- with the boxes mapped into the view on the device (`pv_box_views`) and as many
+key frames per forward as the deploy batch and the box capacity hold.
 """
 import torch
 
-from .data.clip_sampling import clip_frame_table
+from .data.clip_sampling import clip_frame_table, keyframe_frame_table
 from .ensemble import VideoEnsembler
 from .transforms import DevicePacker, batch_chunks
 
@@ -133,3 +138,131 @@ class VideoBatchPredictor:
         if not return_clip_scores:
             return scores
         return scores, list(torch.split(self.clip_ensembler.result(), batch.clips))
+
+
+def keyframe_chunks(counts, batch, capacity):
+    """The forwards of a key-frame sequence whose key frame k has `counts[k]` boxes, for a deploy form of `batch` items
+    and `capacity` box rows: a list of chunks, each the list of key-frame indices of one forward.  Key frames without a box
+    are skipped (the tutorial skips them); the others are walked greedily in order -- a chunk takes key frames while it
+    holds at most `batch` of them and at most `capacity` boxes, and a key frame is never split.  ValueError for a key frame
+    with more than `capacity` boxes."""
+    if batch < 1 or capacity < 1:
+        raise ValueError("batch and capacity are positive")
+    chunks, cur, used = [], [], 0
+    for k, c in enumerate(int(c) for c in counts):
+        if c < 0:
+            raise ValueError("key frame %d has %d boxes" % (k, c))
+        if c > capacity:
+            raise ValueError("key frame %d has %d boxes, the deploy form was converted for at most %d" % (k, c, capacity))
+        if c == 0:
+            continue
+        if cur and (len(cur) == batch or used + c > capacity):
+            chunks.append(cur)
+            cur, used = [], 0
+        cur.append(k)
+        used += c
+    if cur:
+        chunks.append(cur)
+    return chunks
+
+
+class KeyframeDetector:
+    """`KeyframeDetector(deployed, clip_duration, mean, std, div255, short_side)(video, fps, timestamps, boxes)` =
+    [sum r_k, num_classes] fp32 action scores, one row per person box, rows in the order of the concatenated box list.
+
+    `deployed` is a detection model (`slow_r50_detection`, `slowfast_r50_detection`) converted as a whole by
+    `convert_to_deployable_form(det, (x, bboxes))`: its batch is the number of key frames of one forward and its box count
+    the CAPACITY of one forward.  `timestamps` are the key frames in seconds; around each a clip of `clip_duration` seconds is
+    cut (`data.keyframe_frame_table`).  `boxes` holds one [r_k, 4] tensor (x1, y1, x2, y2 in the pixels of the SOURCE frame,
+    finite; host or device) per time stamp, r_k >= 0; key frames without a box are skipped.  `crop_size=None` is the
+    tutorial's protocol: boxes clipped to the frame, short side scaled to `short_side`, NO crop, boxes clipped again -- every
+    video must then scale to the deploy form's H x W (256 x 455 for 720p at short_side 256).  With `crop_size` the view is the
+    `spatial_idx` crop and the boxes follow it as `DevicePacker(dm)(clip, bboxes)` moves them.  `video`, `src_layout`, `yuv`,
+    `coded_height`, `height` as for `VideoPredictor` (YUV 4:2:0 included); `video` may also be a LIST of videos, with
+    `timestamps` and `boxes` given per video and `fps` one number or one per video.
+
+    Frame tables, the box list and its key-frame index are uploaded once per call; per forward there are only the ingest,
+    one `pv_box_views` launch and the replay.  The key frames are walked by `keyframe_chunks`.  Everything is validated
+    before the first launch.  After a call `forwards` holds the number of forwards and `chunks` the key frames (numbered
+    over all videos of the call, in order) of each."""
+
+    def __init__(self, deployed, clip_duration, mean, std, div255, short_side, crop_size=None, spatial_idx=1,
+                 frame_ratios=None, src_layout="NTHWC", yuv=("bt709", False), coded_height=None, height=None):
+        if getattr(deployed, "_pv_load_boxes", None) is None or getattr(deployed, "_pv_box_capacity", None) is None:
+            raise ValueError("KeyframeDetector scores the boxes of key frames with a detection model converted as a whole "
+                             "by convert_to_deployable_form(det, (x, bboxes)); a classification model scores videos: "
+                             "VideoPredictor / VideoBatchPredictor")
+        if short_side is None:
+            raise ValueError("short_side is required (crop_size=None: no crop)")
+        if not isinstance(spatial_idx, int):
+            raise ValueError("a detection model takes one view: its boxes belong to one crop")
+        self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout,
+                                   yuv, coded_height, height, keyframes=True)
+        self.clip_duration, self.src_layout = clip_duration, src_layout
+        self.forwards, self.chunks = 0, []
+
+    @torch.no_grad()
+    def __call__(self, video, fps, timestamps, boxes, height=None, coded_height=None):
+        p = self.packer
+        device = torch.device(p.sess.device)
+        if isinstance(video, (list, tuple)):
+            videos, stamps, box_lists = list(video), list(timestamps), list(boxes)
+            rates = list(fps) if isinstance(fps, (list, tuple)) else [fps] * len(videos)
+        else:
+            videos, stamps, box_lists, rates = [video], [timestamps], [boxes], [fps]
+        if not videos or not (len(stamps) == len(box_lists) == len(rates) == len(videos)):
+            raise ValueError("timestamps, boxes and fps are given per video: %d, %d and %d for %d videos"
+                             % (len(stamps), len(box_lists), len(rates), len(videos)))
+        dims = 3 if p.is_yuv else 4
+
+        def per_video(x):
+            return list(x) if isinstance(x, (list, tuple)) else [x] * len(videos)
+
+        heights, coded = per_video(height), per_video(coded_height)
+        kept, tables, counts, flat = [], [], [], []
+        for j, (vid, rate, ts, bl) in enumerate(zip(videos, rates, stamps, box_lists)):
+            if vid.dim() != dims:
+                raise RuntimeError("video %d: expected a %d-d %s video, got %s" % (j, dims, self.src_layout, tuple(vid.shape)))
+            ts, bl = list(ts), list(bl)
+            if len(ts) != len(bl) or not ts:
+                raise ValueError("video %d: %d box tensors for %d time stamps" % (j, len(bl), len(ts)))
+            num_frames = vid.shape[1] if self.src_layout == "NCTHW" else vid.shape[0]
+            table, _ = keyframe_frame_table(ts, self.clip_duration, num_frames, rate, p.clip_frames)
+            for k, b in enumerate(bl):
+                if not isinstance(b, torch.Tensor) or b.dim() != 2 or b.shape[1] != 4:
+                    raise ValueError("video %d, key frame %d: boxes are an [r, 4] tensor (x1, y1, x2, y2)" % (j, k))
+            own = [int(b.shape[0]) for b in bl]
+            counts.extend(own)
+            rows = [k for k, c in enumerate(own) if c > 0]
+            if not rows:
+                continue                                         # no key frame of this video has a box
+            vid = vid.to(device, non_blocking=True)
+            if not p.is_yuv:
+                if vid.dtype not in (torch.uint8, torch.float32):
+                    vid = vid.float()
+                vid = vid.contiguous()
+            kept.append((vid, heights[j], coded[j]))
+            tables.append(table[rows])
+            flat.extend(bl[k] for k in rows)
+        chunks = keyframe_chunks(counts, p.batch, p.box_capacity)    # ValueError before any launch
+        self.forwards, self.chunks = 0, chunks
+        classes = p.model._pv_result().shape[1]
+        out = torch.zeros((sum(counts), classes), dtype=torch.float32, device=device)
+        if not chunks:
+            return out
+        batch = p.video_batch([v for v, _, _ in kept], tables, [h for _, h, _ in kept] if height is not None else None,
+                              [c for _, _, c in kept] if coded_height is not None else None)   # every check, one upload
+        full = [c for c in counts if c > 0]                      # boxes per item of the sequence
+        boxes_dev = torch.cat([b.detach().to(device=device, dtype=torch.float32) for b in flat]).contiguous()
+        box_item = torch.repeat_interleave(torch.arange(len(full), dtype=torch.int32), torch.tensor(full)).to(device)
+        item0 = box0 = 0
+        for chunk in chunks:
+            n_items = len(chunk)
+            n = sum(counts[k] for k in chunk)
+            p.fill_batch(batch, item0, n_items)
+            p.fill_boxes(batch, boxes_dev, box_item, box0, n, item0, n_items)
+            out[box0:box0 + n] = p.launch()[:n]                  # rows behind the n-th are padding
+            item0, box0 = item0 + n_items, box0 + n
+            self.forwards += 1
+        p.release_batch()                                        # the videos are the caller's again
+        return out

@@ -22,6 +22,11 @@ of the tap rule, and `device_scale_crop` / `DevicePacker` / `inference.VideoPred
 
 Many videos per forward: `DevicePacker.video_batch` + `fill_batch` give every item of the deploy batch a source of its own
 (`pv_batch_views`), so that the views of videos of any lengths and frame sizes share a forward (`inference.VideoBatchPredictor`).
+
+Key-frame detection: a detection form takes the same batch path (`keyframes=True`) -- rectangular and uncropped with
+`short_side` alone, the detection tutorial's protocol -- and `DevicePacker.fill_boxes` maps the boxes of a forward from the
+pixels of their source frames into the views on the device (`pv_box_views`); `boxes_to_view` is the host mirror, composed of
+the box mirrors above, and `inference.KeyframeDetector` the loop around it.
 """
 import copy
 import math
@@ -155,6 +160,28 @@ def uniform_crop_with_boxes(images: torch.Tensor, size: int, spatial_idx: int,
     y, x = crop_offsets(images.shape[2], images.shape[3], size, spatial_idx)
     cropped = images[:, :, y: y + size, x: x + size]
     return cropped, clip_boxes_to_image(crop_boxes(boxes, x, y), cropped.shape[-2], cropped.shape[-1])
+
+
+def boxes_to_view(boxes: torch.Tensor, height: int, width: int, short_side: int, crop_size=None, spatial_idx: int = 1,
+                  clip_to_source: bool = False) -> torch.Tensor:
+    """The host mirror of `pv_box_views` (include/pv_mi355x.h): fp32 [N,4] boxes (x1, y1, x2, y2) in the pixels of a
+    height x width SOURCE frame -> the same boxes in the pixels of the view the ingest cuts from that frame, composed from the
+    mirrors above in the reference's order: `clip_boxes_to_image` to the source (`clip_to_source`: the detection tutorial's
+    first step), `short_side_scale_with_boxes`, then `crop_boxes` to the origin of the `crop_size` window of `spatial_idx`
+    -- `crop_size=None`: no crop, the window is the whole scaled frame -- and `clip_boxes_to_image` to the window.  The
+    input is not modified.  Boxes are finite."""
+    out = boxes.detach().to("cpu", torch.float32).clone()
+    if clip_to_source:
+        out = clip_boxes_to_image(out, height, width)
+    frame = torch.zeros(1, dtype=torch.float32).expand(1, 1, height, width)          # only its size is used
+    scaled, out = short_side_scale_with_boxes(frame, out, short_side)
+    hn, wn = scaled.shape[-2:]
+    if crop_size is None:
+        return clip_boxes_to_image(out, hn, wn)
+    if crop_size > hn or crop_size > wn:
+        raise RuntimeError("a %d crop does not fit the %d x %d frame scaled to %d x %d" % (crop_size, height, width, hn, wn))
+    y, x = crop_offsets(hn, wn, crop_size, spatial_idx)
+    return clip_boxes_to_image(crop_boxes(out, x, y), crop_size, crop_size)
 
 
 class ShortSideScale(torch.nn.Module):
@@ -469,12 +496,16 @@ class VideoBatch:
 def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, pathway_frames, channels, device, upload,
                       height=None, coded_height=None):
     """The host half of `DevicePacker.video_batch` (see there): validate every video, build the records, the item sequence
-    and the concatenated tables, and hand them to `upload` (host tensor -> device tensor) once."""
+    and the concatenated tables, and hand them to `upload` (host tensor -> device tensor) once.  `crop_size` is the side of
+    the square crop, or a pair (Ho, Wo): NO crop -- the window is the whole scaled frame, and every video must scale to
+    exactly Ho x Wo."""
     from . import _lib as L
     videos = list(videos)
     if not videos or len(tables) != len(videos):
         raise ValueError("%d frame tables for %d videos" % (len(tables), len(videos)))
     is_yuv = src_layout in YUV_LAYOUTS
+    no_crop = isinstance(crop_size, (tuple, list))
+    ho, wo = (int(crop_size[0]), int(crop_size[1])) if no_crop else (crop_size, crop_size)
 
     def per_video(x, what):
         if x is None or not isinstance(x, (list, tuple)):
@@ -509,11 +540,14 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
         if c != channels:
             raise RuntimeError("video %d has %d channels, the deploy form takes %d" % (j, c, channels))
         hn, wn = scaled_size(hs, ws, short_side)
-        if crop_size > hn or crop_size > wn:
+        if no_crop and (hn, wn) != (ho, wo):
+            raise RuntimeError("video %d: the %d x %d frame scales to %d x %d, the deploy form takes %d x %d and nothing is cropped"
+                               % (j, hs, ws, hn, wn, ho, wo))
+        if not no_crop and (crop_size > hn or crop_size > wn):
             raise RuntimeError("video %d: a %d crop does not fit the %d x %d frame scaled to %d x %d" % (j, crop_size, hs, ws, hn, wn))
         rec.src, rec.N, rec.Hs, rec.Ws, rec.Hn, rec.Wn = video.data_ptr(), nf, hs, ws, hn, wn
         for k, v in enumerate(views):
-            rec.y_off[k], rec.x_off[k] = crop_offsets(hn, wn, crop_size, v)
+            rec.y_off[k], rec.x_off[k] = (0, 0) if no_crop else crop_offsets(hn, wn, crop_size, v)
         # (float)Hs / (float)Hn: sizes are exact in fp32, and a double quotient rounded once more to fp32 IS the fp32 quotient
         rec.sy, rec.sx = hs / hn, ws / wn
         nums_frames.append(nf)
@@ -603,21 +637,33 @@ class DevicePacker:
 
     `video_batch(videos, tables)` + `fill_batch(batch, i0, n)` + `launch()` do the same for MANY videos of any lengths and
     frame sizes at once: every item of the deploy batch has a source of its own (`pv_batch_views`), so a forward is filled
-    with views of as many videos as it takes; `inference.VideoBatchPredictor` is the loop around it."""
+    with views of as many videos as it takes; `inference.VideoBatchPredictor` is the loop around it.
+
+    `keyframes=True` with `short_side` and WITHOUT `crop_size`: no crop -- the window is the whole scaled frame, which must be the deploy form's H x W
+    (rectangular for a rectangular source: 256 x 455 for 720p); this mode runs through `video_batch` / `fill_batch` only.
+    `keyframes=True` in general makes the packer the ingest of key-frame detection: `video_batch` / `fill_batch` accept a detection form
+    (one view; every item is the clip around one key frame), any source layout is legal -- the boxes no longer pass through
+    the host -- and `fill_boxes(batch, boxes_dev, box_item_dev, box0, n, item0, n_items)` fills the form's box buffer for the
+    forward `fill_batch(batch, item0, n_items)` filled (`pv_box_views`); `inference.KeyframeDetector` is the loop around it.
+    The clip-at-a-time `packer(clip, bboxes)` keeps mapping the boxes on the host and keeps refusing YUV clips."""
 
     def __init__(self, deployed, mean=None, std=None, div255=False, frame_ratios=None, short_side=None, crop_size=None,
-                 spatial_idx=1, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None):
+                 spatial_idx=1, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None, keyframes=False):
         self.subs = None
-        if (short_side is None) != (crop_size is None):
-            raise ValueError("short_side and crop_size are given together")
+        if (short_side is None) != (crop_size is None) and not (keyframes and crop_size is None):
+            raise ValueError("short_side and crop_size are given together (short_side alone -- no crop -- is a mode of the "
+                             "key-frame path: keyframes=True)")
+        # keyframes=True and short_side alone: no crop (the detection tutorial's protocol) -- the window is the whole scaled frame
+        self.no_crop, self.keyframes = short_side is not None and crop_size is None, bool(keyframes)
         if src_layout not in ("NCTHW", "NTHWC") + YUV_LAYOUTS:
             raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,))
         self.short_side, self.crop_size, self.src_layout = short_side, crop_size, src_layout
         self.is_yuv, self.coded_height, self.height = src_layout in YUV_LAYOUTS, coded_height, height
-        if self.is_yuv and (getattr(deployed, "_pv_load_boxes", None) is not None):
+        if self.is_yuv and not self.keyframes and (getattr(deployed, "_pv_load_boxes", None) is not None):
             raise ValueError("a detection model does not take %s frames: its boxes are mapped through the scaling and the crop "
-                             "of an RGB clip on the host, and that path is not built for YUV sources" % src_layout)
-        self.views = _views(spatial_idx) if short_side is not None else (1,)
+                             "of an RGB clip on the host, and that path is not built for YUV sources (the key-frame path, "
+                             "keyframes=True / inference.KeyframeDetector, maps them on the device for any layout)" % src_layout)
+        self.views = _views(spatial_idx) if crop_size is not None else (1,)
         if short_side is None and src_layout != "NCTHW":
             raise ValueError("a frame-interleaved or YUV clip is read by the resampling path only: give short_side and crop_size")
         if hasattr(deployed, "parts") and hasattr(deployed, "_pv_launch"):
@@ -625,7 +671,8 @@ class DevicePacker:
             # sub-plan's input buffers, then ONE launch of the joint graph
             self.model = deployed
             self.subs = [DevicePacker(p, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv,
-                                      coded_height, height) for p in deployed.parts]
+                                      coded_height, height, keyframes) for p in deployed.parts]
+            self.window = self.subs[0].window
             self.sess, self.refs = self.subs[0].sess, self.subs[0].refs
             self.frame_ratios = self.subs[0].frame_ratios
             self._clip_tables = {}
@@ -650,6 +697,11 @@ class DevicePacker:
                                      % (crop_size, ref.H, ref.W))
             if len(self.views) > 1 and getattr(deployed, "_pv_load_boxes", None) is not None:
                 raise ValueError("a detection model takes one view: its boxes belong to one crop")
+        if any((ref.H, ref.W) != (self.refs[0].H, self.refs[0].W) for ref in self.refs):
+            raise ValueError("the input pathways of one deploy form have one frame size")
+        # (Ho, Wo) of the window every resampling launch writes: the crop, or -- no crop -- the deploy form's own H x W, which
+        # every source must then scale to (checked per video, with both sizes named)
+        self.window = (self.refs[0].H, self.refs[0].W) if crop_size is None else (crop_size, crop_size)
         self.scale, self.shift = _affine(mean, std, div255, self.refs[0].C, self.sess.device)
         self._index = {}
         self._planar = {}
@@ -694,6 +746,12 @@ class DevicePacker:
         load_boxes = getattr(self.model, "_pv_load_boxes", None)
         if (bboxes is None) != (load_boxes is None):
             raise RuntimeError("bboxes are given to a detection model and only to a detection model")
+        if self.is_yuv and load_boxes is not None:
+            raise ValueError("a detection model does not take %s frames a clip at a time: its boxes are mapped on the host "
+                             "there; use video_batch / fill_batch / fill_boxes (inference.KeyframeDetector)" % self.src_layout)
+        if self.no_crop:
+            raise RuntimeError("the no-crop mode (short_side without crop_size) runs through video_batch / fill_batch / "
+                               "fill_boxes; a clip at a time takes short_side and crop_size")
         if self.is_yuv:
             return self._call_yuv(clip)
         if clip.dim() != 5:
@@ -810,7 +868,7 @@ class DevicePacker:
         `video` is [C,N,H,W] ("NCTHW"; uint8 or fp32) or [N,H,W,3] uint8 ("NTHWC"), contiguous and on the device -- or, for a
         YUV layout, uint8 [N, Hc*3/2, W] on the device with the strides it has (`yuv_geometry`) -- and must stay alive until
         the forward has run.  Nothing is launched here but the ingest: run `launch()` next."""
-        if self.short_side is None:
+        if self.short_side is None or self.no_crop:
             raise RuntimeError("fill_video resamples: construct the packer with short_side and crop_size")
         if getattr(self.model, "_pv_load_boxes", None) is not None:
             raise RuntimeError("a detection model takes boxes of key frames, not a video")
@@ -896,15 +954,17 @@ class DevicePacker:
         ONCE.  Returns a `VideoBatch`, which keeps the videos alive."""
         if self.short_side is None:
             raise RuntimeError("video_batch resamples: construct the packer with short_side and crop_size")
-        if getattr(self.model, "_pv_load_boxes", None) is not None:
-            raise RuntimeError("a detection model takes boxes of key frames, not videos")
+        if getattr(self.model, "_pv_load_boxes", None) is not None and not self.keyframes:
+            raise RuntimeError("a detection model takes boxes of key frames, not videos: construct the packer with "
+                               "keyframes=True and fill the boxes with fill_boxes (inference.KeyframeDetector)")
         refs = self.subs[0].refs if self.subs is not None else self.refs
         for t in tables:
             t = torch.as_tensor(t)
             if t.dim() == 2 and t.shape[1] != self.clip_frames:
                 raise ValueError("the deploy form takes clips of %d frames, the table has %d columns" % (self.clip_frames, t.shape[1]))
         device = torch.device(self.sess.device)
-        return build_video_batch(videos, tables, self.src_layout, self.short_side, self.crop_size, self.views,
+        return build_video_batch(videos, tables, self.src_layout, self.short_side,
+                                 self.window if self.no_crop else self.crop_size, self.views,
                                  [ref.T for ref in refs], refs[0].C, device, lambda t: t.to(device),
                                  self.height if height is None else height,
                                  self.coded_height if coded_height is None else coded_height)
@@ -931,6 +991,7 @@ class DevicePacker:
         on it has been launched.  Work already queued stays valid: the memory is reused in stream order."""
         for p in (self.subs if self.subs is not None else [self]):
             p._src = None
+        self._boxes_src = None
 
     def _fill_batch(self, batch, item0, n_items):
         """One pv_batch_views launch per pathway into this plan's buffers; see Session.video_views for the tail."""
@@ -948,7 +1009,54 @@ class DevicePacker:
             d.src_layout = L.SRC_YUV420 if self.is_yuv else (L.SRC_NCTHW if self.src_layout == "NCTHW" else L.SRC_NTHWC)
             if self.is_yuv:
                 d.c_step, d.yuv2rgb = (2 if self.src_layout in ("NV12", "NV21") else 1), self.yuv_matrix.data_ptr()
-            d.Ho, d.Wo, d.n_views = self.crop_size, self.crop_size, len(self.views)
+            d.Ho, d.Wo, d.n_views = self.window[0], self.window[1], len(self.views)
             if self.scale is not None:
                 d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
             self.sess.batch_views(d, ref, planar=self._planar_for(i, ref))
+
+    # ------------------------------------------------------------------------- key-frame detection (pv_box_views)
+    @property
+    def box_capacity(self):
+        """Rows of the detection form's box buffer: the box count it was converted for."""
+        cap = getattr(self.model, "_pv_box_capacity", None)
+        if cap is None:
+            raise RuntimeError("fill_boxes needs a detection model converted as a whole by convert_to_deployable_form")
+        return cap
+
+    @torch.no_grad()
+    def fill_boxes(self, batch, boxes_dev, box_item_dev, box0, n, item0, n_items, clip_to_source=None, dst_box=None):
+        """Fill the detection form's box buffer for the forward that `fill_batch(batch, item0, n_items)` filled: boxes
+        [box0, box0 + n) of `boxes_dev` (fp32 [N,4] on the device, x1 y1 x2 y2 in the pixels of each key frame's SOURCE frame)
+        are mapped into the view of their item -- `box_item_dev` (int32 [N], non-decreasing, on the device) names it by its
+        position in the sequence of `batch` -- by ONE `pv_box_views` launch; rows [n, capacity) get clip index -1.  Both
+        tensors are uploaded once per call, not per forward.  `clip_to_source` (default: the no-crop mode) clips the boxes to
+        the source frame first, as the detection tutorial does.  `dst_box`: an int32 [capacity] device tensor that receives
+        the box number of every row (-1 behind the n-th)."""
+        import ctypes as C
+        from . import _lib as L
+        if self.subs is not None:
+            raise RuntimeError("fill_boxes needs a one-plan detection form")
+        cap = self.box_capacity
+        if not isinstance(batch, VideoBatch) or batch.n_views != len(self.views):
+            raise RuntimeError("fill_boxes takes what video_batch of this packer returned")
+        for t, dt, shape in ((boxes_dev, torch.float32, (boxes_dev.shape[0], 4)), (box_item_dev, torch.int32, (boxes_dev.shape[0],))):
+            if not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise RuntimeError("boxes are a contiguous fp32 [N,4] and box_item an int32 [N] tensor on the device; got %s %s"
+                                   % (t.dtype, tuple(t.shape)))
+        if dst_box is not None and (not dst_box.is_cuda or dst_box.dtype != torch.int32 or dst_box.numel() < cap
+                                    or not dst_box.is_contiguous()):
+            raise RuntimeError("dst_box is a contiguous int32 device tensor of at least %d entries" % cap)
+        if not (0 <= box0 and 0 <= n <= cap and box0 + n <= boxes_dev.shape[0]):
+            raise RuntimeError("boxes [%d, %d) are not a window of at most %d of the call's %d boxes" % (box0, box0 + n, cap, boxes_dev.shape[0]))
+        if not (0 <= item0 and 0 < n_items <= self.batch and item0 + n_items <= batch.total):
+            raise RuntimeError("items [%d, %d) are not a chunk of at most %d of the batch's %d items" % (item0, item0 + n_items, self.batch, batch.total))
+        d = L.BoxViewsDesc()
+        d.boxes, d.box_item = boxes_dev.data_ptr(), box_item_dev.data_ptr()
+        d.sources_dev, d.items_dev = batch.sources_dev.data_ptr(), batch.items_dev.data_ptr()
+        d.dst_box = dst_box.data_ptr() if dst_box is not None else None
+        d.n_boxes, d.n_seq, d.n_sources, d.n_views = boxes_dev.shape[0], batch.total, len(batch.sources), len(self.views)
+        d.box0, d.n_launch, d.item0, d.n_items = box0, n, item0, n_items
+        d.Ho, d.Wo, d.capacity = self.window[0], self.window[1], cap
+        d.clip_to_source = int(self.no_crop if clip_to_source is None else clip_to_source)
+        self._boxes_src = (boxes_dev, box_item_dev, dst_box)       # alive until the launch has run
+        self.sess.box_views(d, self.model._pv_box_ptr)
