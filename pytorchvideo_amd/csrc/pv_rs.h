@@ -1,7 +1,10 @@
-// What the resampling ingest kernels share (pv_resample.hip: RGB / planar sources; pv_yuv.hip: YUV 4:2:0 sources;
-// pv_batch.hip: either, with one source per destination item): the pinned source coordinate, the taps of a staged row, the
-// YUV tap conversion and blend, the destination forms with their stores, and the host-side checks of views, item range,
-// destination and YUV planes.  Everything is inline in an anonymous namespace: each translation unit keeps its own kernels.
+// The resampling ingest (pv_resample.hip: RGB / planar sources; pv_yuv.hip: YUV 4:2:0 sources; pv_batch.hip: either, with
+// one source per destination item).  What the entry points compute with is here, once: the pinned source coordinate, the
+// destination forms with their stores, the taps and blends, the two staged-strip bodies that the four kernels wrap
+// (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather), the launch arithmetic (widest span, rows per strip, destination-form
+// dispatch) and the host-side checks of views, item range, destination and YUV planes.  The three files keep what differs:
+// where a workgroup's geometry comes from, and the validation of their descriptors.
+// Everything is inline in an anonymous namespace: each translation unit keeps its own kernels.
 #pragma once
 #include "pv_common.h"
 
@@ -98,7 +101,7 @@ __device__ __forceinline__ void rs_store_group(void* dst, const float (&out)[4][
   }
 }
 
-// ---- taps and blends shared by the one-source kernels and the per-item kernels (pv_batch.hip) ------------------------
+// ---- taps and blends ------------------------------------------------------------------------------------------------
 // One tap of a staged RGB / planar row, in the source dtype.
 template <typename S> __device__ __forceinline__ float rs_tap(const unsigned char* lds, int off);
 template <> __device__ __forceinline__ float rs_tap<unsigned char>(const unsigned char* lds, int off) { return (float)lds[off]; }
@@ -129,6 +132,360 @@ __device__ __forceinline__ float yuv_blend(float ly0, float ly1, float lx0, floa
   const float v = fmaf(ly1, h[1], ly0 * h[0]);
   return fmaf(v, sc, sh);
 }
+
+// ---- the staged strip ---------------------------------------------------------------------------------------------
+// A bandwidth-bound gather.  One workgroup owns a strip of R output rows (blockIdx.x) of one destination frame t of one
+// destination item zi:
+//   1. stage: the source span those rows need -- per output row the two source rows i0y, i1y (or, when the strip's source
+//      rows are at most 2R, as in upscaling, that contiguous run of rows once), columns [i0x(first), i1x(last)] -- is
+//      copied to LDS in the SOURCE dtype with aligned 16-byte global loads, a batch of four per thread, and 16-byte LDS
+//      writes.  YUV stages the luma span and the chroma span behind it: chroma rows (y >> 1) of the same rows, columns
+//      [xs0 >> 1, xs1 >> 1]; in the contiguous case every chroma row once, so half as many as luma rows.  A row of a span
+//      may start at any byte address (Ws = 340 gives 4-byte-aligned rows, an odd Ws, a pitched surface, an odd base or the
+//      +1 of the second interleaved sample none at all): the loads fetch the aligned 16-byte granules that cover the span,
+//      and the LDS image of each row keeps the span's offset inside its first granule (`addr & 15`), so unaligned rows cost
+//      nothing extra.  A granule that covers a byte of the span lies in the same page as that byte, so the up to 15 bytes
+//      fetched in front of and behind the span are never used and never fault.
+//   2. gather: a thread owns G x-adjacent output pixels of one row (G = one 16-byte store per channel row for planar
+//      destinations, 2 = one 16-byte chunk for the 4-channel layout, 1 voxel for channels-last), takes its 4 taps per
+//      channel from LDS (YUV: the four Y taps and the (U, V) pair behind each, converted and clamped per tap), blends in
+//      fp32, applies the affine map and hands the group to rs_store_group.  Groups cut by the right edge (Wo not a multiple
+//      of G) or not 16-byte aligned in the destination (odd Wo) are stored element by element.  (Eight pixels per thread
+//      for the 4-channel layout -- four 16-byte stores 64 bytes apart, as ingest_c4_vec8_kernel does -- measured up to 17 %
+//      slower here: DESIGN.md 4.6.)
+// The launch sizes R and the LDS pitch(es) of a staged row; the geometry is a struct of workgroup-uniform scalars that the
+// kernel fills from its descriptor or from the item's record.  The view's window origin arrives selected (rs_view_off):
+// a runtime index into a by-value descriptor would put the descriptor in scratch.  check_span: the source is a per-item
+// record, which the launch may not have been sized for; a workgroup whose span exceeds the pitch then stages nothing and
+// writes nothing.  The host sizes a one-source launch from the very values the kernel sees, so those kernels skip the test.
+
+// What the gather writes, and the affine map in front of the store.
+struct RsDst {
+  void* dst;
+  int C, T, Ho, Wo, c_p, ld;
+  int64_t bs;
+  const float* ch_scale;
+  const float* ch_shift;
+};
+template <typename Desc> __device__ __forceinline__ RsDst rs_dst(const Desc& d, int C) {
+  return RsDst{d.dst, C, d.T, d.Ho, d.Wo, d.c_p, d.ld, d.bs, d.ch_scale, d.ch_shift};
+}
+
+// Selected, not indexed -- and from values the caller has loaded, not through a reference to the three: the compiler keeps
+// conditional loads as branches.
+__device__ __forceinline__ int rs_view_off(int view, int off0, int off1, int off2) {
+  return view == 0 ? off0 : (view == 1 ? off1 : off2);
+}
+
+// An RGB / planar source: clip `clip_frame0 / (planes * N)` of [.., C, N, Hs, Ws] or [.., N, Hs, Ws, 3].
+struct RsRgbSrc {
+  uintptr_t src;
+  int Hs, Ws, N;        // N: frames per source plane, which is the plane stride in frames
+  float sy, sx;         // (float)Hs / (float)Hn, (float)Ws / (float)Wn: divided once, on the host
+  int yoff, xoff;       // the view's window origin inside Hn x Wn
+  int ts;               // the selected frame, clamped into [0, N - 1] before any address is formed
+  long clip_frame0;     // frames from `src` to frame 0 of the clip
+};
+
+// S: source element (unsigned char | float); INTER: frame-interleaved [.., Hs, Ws, 3] source; FORM / D: destination.
+template <typename S, bool INTER, int FORM, typename D>
+__device__ __forceinline__ void rs_strip_rgb(unsigned char* lds, int R, int pitch, const RsRgbSrc& s, const RsDst& d, int zi, int t,
+                                             bool check_span) {
+  constexpr int G = RsGroup<FORM, D>::G;
+  constexpr int XB = INTER ? 3 : (int)sizeof(S);   // bytes from one source column to the next
+  const int tid = threadIdx.x;
+  const int row0 = blockIdx.x * R;
+  const int nrows = min(R, d.Ho - row0);
+  const int planes = INTER ? 1 : d.C;
+
+  int xs0, xs1, ybase, ylast, unused;
+  float lunused;
+  rs_coord(s.sx, s.xoff, s.Ws, xs0, unused, lunused);
+  rs_coord(s.sx, s.xoff + d.Wo - 1, s.Ws, unused, xs1, lunused);
+  rs_coord(s.sy, s.yoff + row0, s.Hs, ybase, unused, lunused);
+  rs_coord(s.sy, s.yoff + row0 + nrows - 1, s.Hs, unused, ylast, lunused);
+  const bool dense = ylast - ybase + 1 <= 2 * R;   // the strip's source rows fit the 2R slots as one contiguous run
+  const int nslots = dense ? ylast - ybase + 1 : 2 * nrows;
+  const int span_bytes = (xs1 - xs0 + 1) * XB;
+  if (check_span && span_bytes + 15 > pitch) return;
+
+  // byte address of column xs0 of source row y of plane `pl` of the selected frame
+  const long row_bytes = (long)s.Ws * XB;
+  const long frame_bytes = (long)s.Hs * row_bytes;
+  const long first = (s.clip_frame0 + s.ts) * frame_bytes + (long)xs0 * XB;
+  const long plane_bytes = INTER ? 0 : (long)s.N * frame_bytes;
+  auto row_addr = [&](int y, int pl) -> uintptr_t { return s.src + first + (long)pl * plane_bytes + (long)y * row_bytes; };
+
+  // ---- stage -------------------------------------------------------------------------------------------------
+  const int cpr = pitch >> 4;                      // 16-byte chunks per staged row
+  const int total = nslots * planes * cpr;
+  for (int base = tid; base < total; base += kRsThreads * 4) {
+    u32x4 val[4];
+    int off[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = base + u * kRsThreads;
+      off[u] = -1;
+      if (idx < total) {
+        const int sp = idx / cpr, ch = idx - sp * cpr;
+        const int slot = sp / planes, pl = sp - slot * planes;
+        int y = ybase + slot;
+        if (!dense) {
+          int i0, i1;
+          rs_coord(s.sy, s.yoff + row0 + (slot >> 1), s.Hs, i0, i1, lunused);
+          y = (slot & 1) ? i1 : i0;
+        }
+        const uintptr_t a = row_addr(y, pl);
+        if (ch * 16 < (int)(a & 15) + span_bytes) {
+          val[u] = *reinterpret_cast<const u32x4*>((a & ~(uintptr_t)15) + (uintptr_t)ch * 16);
+          off[u] = sp * pitch + ch * 16;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (off[u] >= 0) *reinterpret_cast<u32x4*>(lds + off[u]) = val[u];
+  }
+  __syncthreads();
+
+  // ---- gather ------------------------------------------------------------------------------------------------
+  float sc[4], sh[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    sc[c] = (d.ch_scale && c < d.C) ? d.ch_scale[c] : 1.f;
+    sh[c] = (d.ch_scale && d.ch_shift && c < d.C) ? d.ch_shift[c] : 0.f;
+  }
+  const int gpr = (d.Wo + G - 1) / G;              // groups per output row
+  const int items = nrows * gpr;
+  for (int it = tid; it < items; it += kRsThreads) {
+    const int r = it / gpr, gx = it - r * gpr;
+    const int y = row0 + r;
+    int i0y, i1y;
+    float ly1;
+    rs_coord(s.sy, s.yoff + y, s.Hs, i0y, i1y, ly1);
+    const float ly0 = 1.f - ly1;
+    const int s0 = dense ? i0y - ybase : 2 * r, s1 = dense ? i1y - ybase : 2 * r + 1;
+    int ro0[4], ro1[4];                            // LDS byte offset of column xs0, channel c, in the two source rows
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (INTER) {
+        ro0[c] = s0 * pitch + (int)(row_addr(i0y, 0) & 15) + c;
+        ro1[c] = s1 * pitch + (int)(row_addr(i1y, 0) & 15) + c;
+      } else {
+        const int cc = c < d.C ? c : 0;
+        ro0[c] = (s0 * planes + cc) * pitch + (int)(row_addr(i0y, cc) & 15);
+        ro1[c] = (s1 * planes + cc) * pitch + (int)(row_addr(i1y, cc) & 15);
+      }
+    }
+    float out[4][G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      const int x = min(gx * G + j, d.Wo - 1);     // a group cut by the right edge recomputes the last column; not stored
+      int i0x, i1x;
+      float lx1;
+      rs_coord(s.sx, s.xoff + x, s.Ws, i0x, i1x, lx1);
+      const float lx0 = 1.f - lx1;
+      const int o0 = (i0x - xs0) * XB, o1 = (i1x - xs0) * XB;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (c < d.C) {
+          const float p00 = rs_tap<S>(lds, ro0[c] + o0), p01 = rs_tap<S>(lds, ro0[c] + o1);
+          const float p10 = rs_tap<S>(lds, ro1[c] + o0), p11 = rs_tap<S>(lds, ro1[c] + o1);
+          const float v = ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11);
+          out[c][j] = v * sc[c] + sh[c];
+        } else {
+          out[c][j] = 0.f;
+        }
+      }
+    }
+    const int x0 = gx * G;
+    const int nvalid = min(G, d.Wo - x0);
+    rs_store_group<FORM, D, G>(d.dst, out, d.C, d.T, d.Ho, d.Wo, d.c_p, d.ld, d.bs, zi, t, y, x0, nvalid);
+  }
+}
+
+// A YUV 4:2:0 source: the planes of the selected frame.
+struct RsYuvSrc {
+  uintptr_t src;
+  long frame_off;           // bytes from `src` to the selected frame, its index clamped before the product
+  int Hs, Ws;
+  float sy, sx;             // as in RsRgbSrc
+  int yoff, xoff;
+  int y_pitch, c_pitch;     // bytes per luma / chroma row of the source
+  long c_off_a, c_off_b;    // byte offset inside a frame of staged chroma plane 0 / 1 (c_step 2: only plane 0, min(u, v))
+  int u_byte, v_byte;       // c_step 2: which byte of an interleaved pair is U / V; c_step 1: 0
+};
+// The staged chroma planes behind a frame's u_offset / v_offset; `inter`: c_step 2.
+__host__ __device__ __forceinline__ void rs_chroma_planes(bool inter, int64_t u_off, int64_t v_off, RsYuvSrc& s) {
+  const int64_t c_min = u_off < v_off ? u_off : v_off;
+  s.c_off_a = inter ? c_min : u_off;
+  s.c_off_b = inter ? c_min : v_off;
+  s.u_byte = inter ? (int)(u_off - c_min) : 0;
+  s.v_byte = inter ? (int)(v_off - c_min) : 0;
+}
+
+// CSTEP: bytes between x-adjacent samples of one chroma plane (2: U and V interleaved in ONE staged plane; 1: two planes).
+// pitch_y / pitch_c: LDS bytes per staged luma row / chroma (row, plane); c_base: LDS offset of the chroma image.
+template <int CSTEP, int FORM, typename D>
+__device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitch_y, int pitch_c, int c_base, const RsYuvSrc& s,
+                                             const RsDst& d, const float* yuv2rgb, int zi, int t, bool check_span) {
+  constexpr int G = RsGroup<FORM, D>::G;
+  constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
+  const int tid = threadIdx.x;
+  const int row0 = blockIdx.x * R;
+  const int nrows = min(R, d.Ho - row0);
+
+  int xs0, xs1, ybase, ylast, unused;
+  float lunused;
+  rs_coord(s.sx, s.xoff, s.Ws, xs0, unused, lunused);
+  rs_coord(s.sx, s.xoff + d.Wo - 1, s.Ws, unused, xs1, lunused);
+  rs_coord(s.sy, s.yoff + row0, s.Hs, ybase, unused, lunused);
+  rs_coord(s.sy, s.yoff + row0 + nrows - 1, s.Hs, unused, ylast, lunused);
+  const bool dense = ylast - ybase + 1 <= 2 * R;   // the strip's source rows fit the 2R slots as one contiguous run
+  const int nslots = dense ? ylast - ybase + 1 : 2 * nrows;
+  const int cxs0 = xs0 >> 1, cybase = ybase >> 1;
+  const int ncslots = dense ? (ylast >> 1) - cybase + 1 : 2 * nrows;   // dense: <= R + 1 <= 2R
+  const int span_y = xs1 - xs0 + 1;
+  const int span_c = ((xs1 >> 1) - cxs0 + 1) * CSTEP;
+  if (check_span && (span_y + 15 > pitch_y || span_c + 15 > pitch_c)) return;
+
+  const uintptr_t frame = s.src + s.frame_off;
+  auto y_addr = [&](int y) -> uintptr_t { return frame + (long)y * s.y_pitch + xs0; };
+  auto c_addr = [&](int cy, int pl) -> uintptr_t {
+    return frame + (pl == 0 ? s.c_off_a : s.c_off_b) + (long)cy * s.c_pitch + (long)cxs0 * CSTEP;
+  };
+
+  // ---- stage -------------------------------------------------------------------------------------------------
+  const int cpr_y = pitch_y >> 4, cpr_c = pitch_c >> 4;   // 16-byte chunks per staged row
+  const int total_y = nslots * cpr_y;
+  const int total = total_y + ncslots * CP * cpr_c;
+  for (int base = tid; base < total; base += kRsThreads * 4) {
+    u32x4 val[4];
+    int off[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = base + u * kRsThreads;
+      off[u] = -1;
+      if (idx < total) {
+        const bool luma = idx < total_y;
+        const int j = luma ? idx : idx - total_y;
+        const int cpr = luma ? cpr_y : cpr_c;
+        const int sp = j / cpr, ch = j - sp * cpr;             // luma: sp = slot; chroma: sp = slot * CP + plane
+        const int slot = luma ? sp : sp / CP, pl = luma ? 0 : sp - slot * CP;
+        int y = ybase + slot, cy = cybase + slot;
+        if (!dense) {
+          int i0, i1;
+          rs_coord(s.sy, s.yoff + row0 + (slot >> 1), s.Hs, i0, i1, lunused);
+          y = (slot & 1) ? i1 : i0;
+          cy = y >> 1;
+        }
+        const uintptr_t a = luma ? y_addr(y) : c_addr(cy, pl);
+        if (ch * 16 < (int)(a & 15) + (luma ? span_y : span_c)) {
+          val[u] = *reinterpret_cast<const u32x4*>((a & ~(uintptr_t)15) + (uintptr_t)ch * 16);
+          off[u] = (luma ? sp * pitch_y : c_base + sp * pitch_c) + ch * 16;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (off[u] >= 0) *reinterpret_cast<u32x4*>(lds + off[u]) = val[u];
+  }
+  __syncthreads();
+
+  // ---- gather ------------------------------------------------------------------------------------------------
+  float m[12], sc[3], sh[3];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) m[i] = yuv2rgb[i];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    sc[c] = d.ch_scale ? d.ch_scale[c] : 1.f;
+    sh[c] = (d.ch_scale && d.ch_shift) ? d.ch_shift[c] : 0.f;
+  }
+  const int gpr = (d.Wo + G - 1) / G;              // groups per output row
+  const int items = nrows * gpr;
+  for (int it = tid; it < items; it += kRsThreads) {
+    const int r = it / gpr, gx = it - r * gpr;
+    const int y = row0 + r;
+    int i0y, i1y;
+    float ly1;
+    rs_coord(s.sy, s.yoff + y, s.Hs, i0y, i1y, ly1);
+    const float ly0 = 1.f - ly1;
+    const int s0 = dense ? i0y - ybase : 2 * r, s1 = dense ? i1y - ybase : 2 * r + 1;
+    const int cs0 = dense ? (i0y >> 1) - cybase : 2 * r, cs1 = dense ? (i1y >> 1) - cybase : 2 * r + 1;
+    // LDS byte offset of column xs0 (luma) / cxs0 (U, V) in the two source rows
+    const int yo0 = s0 * pitch_y + (int)(y_addr(i0y) & 15), yo1 = s1 * pitch_y + (int)(y_addr(i1y) & 15);
+    const int uo0 = c_base + cs0 * CP * pitch_c + (int)(c_addr(i0y >> 1, 0) & 15) + s.u_byte;
+    const int uo1 = c_base + cs1 * CP * pitch_c + (int)(c_addr(i1y >> 1, 0) & 15) + s.u_byte;
+    const int vo0 = c_base + (cs0 * CP + CP - 1) * pitch_c + (int)(c_addr(i0y >> 1, CP - 1) & 15) + s.v_byte;
+    const int vo1 = c_base + (cs1 * CP + CP - 1) * pitch_c + (int)(c_addr(i1y >> 1, CP - 1) & 15) + s.v_byte;
+    float out[4][G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      const int x = min(gx * G + j, d.Wo - 1);     // a group cut by the right edge recomputes the last column; not stored
+      int i0x, i1x;
+      float lx1;
+      rs_coord(s.sx, s.xoff + x, s.Ws, i0x, i1x, lx1);
+      const float lx0 = 1.f - lx1;
+      const int o0 = i0x - xs0, o1 = i1x - xs0;
+      const int c0 = ((i0x >> 1) - cxs0) * CSTEP, c1 = ((i1x >> 1) - cxs0) * CSTEP;
+      f32x2 p0[3], p1[3];                          // {row i0y, row i1y} of column i0x / i1x, per channel
+      yuv_tap2(m, lds, yo0 + o0, uo0 + c0, vo0 + c0, yo1 + o0, uo1 + c0, vo1 + c0, p0);
+      yuv_tap2(m, lds, yo0 + o1, uo0 + c1, vo0 + c1, yo1 + o1, uo1 + c1, vo1 + c1, p1);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) out[c][j] = yuv_blend(ly0, ly1, lx0, lx1, p0[c], p1[c], sc[c], sh[c]);
+      out[3][j] = 0.f;
+      // finish this pixel before the next one starts: left alone, the compiler blends all G pixels together at the end and
+      // keeps every converted tap alive until then (170+ VGPRs for G = 8: two waves per SIMD)
+      asm volatile("" : "+v"(out[0][j]), "+v"(out[1][j]), "+v"(out[2][j]));
+    }
+    const int x0 = gx * G;
+    rs_store_group<FORM, D, G>(d.dst, out, 3, d.T, d.Ho, d.Wo, d.c_p, d.ld, d.bs, zi, t, y, x0, min(G, d.Wo - x0));
+  }
+}
+
+// ---- the launch arithmetic shared by the entry points ---------------------------------------------------------------
+// Folds the widest source column span of a record's views into `span`, and the chroma span behind it into `span_c`: they
+// size the staged rows.
+inline void rs_widest_span(float sx, const int32_t* x_off, int n_views, int Wo, int Ws, int& span, int& span_c) {
+  for (int v = 0; v < n_views; ++v) {
+    int a, b, u;
+    float l;
+    rs_coord(sx, x_off[v], Ws, a, u, l);
+    rs_coord(sx, x_off[v] + Wo - 1, Ws, u, b, l);
+    span = b - a + 1 > span ? b - a + 1 : span;
+    const int c = (b >> 1) - (a >> 1) + 1;
+    span_c = c > span_c ? c : span_c;
+  }
+}
+
+// R output rows per workgroup and the LDS bytes they stage; per_row: LDS bytes of the two source rows of one output row.
+inline int rs_strip_rows(long per_row, int Ho, int32_t& R_out, size_t& lds) {
+  long R = kRsLdsBudget / per_row;
+  R = R > kRsMaxRows ? kRsMaxRows : R;
+  R = R > Ho ? Ho : R;
+  if (R < 1) R = 1;
+  if (R * per_row > kRsLdsMax) return PV_ERR_UNSUPPORTED;
+  R_out = (int32_t)R;
+  lds = (size_t)(R * per_row);
+  return PV_OK;
+}
+
+// The destination-form dispatch: KERNEL<leading template arguments..., FORM, D>(d, g) over a grid of strips x d.T frames x
+// d.n_items destination items; expects d, g (g.R set), lds and stream in scope.
+#define RS_DISPATCH(KERNEL, ...)                                                                                         \
+  do {                                                                                                                   \
+    const dim3 grid((unsigned)pv_ceil_div(d.Ho, g.R), (unsigned)d.T, (unsigned)d.n_items), block(kRsThreads);            \
+    hipStream_t s = static_cast<hipStream_t>(stream);                                                                    \
+    if (d.dst_layout == PV_DST_NCTHW) {                                                                                  \
+      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, bf16_t>), grid, block, lds, s, d, g);        \
+      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, float>), grid, block, lds, s, d, g);                                \
+    } else if (d.c_p == 4) {                                                                                             \
+      PV_LAUNCH((KERNEL<__VA_ARGS__, RS_C4, bf16_t>), grid, block, lds, s, d, g);                                        \
+    } else {                                                                                                             \
+      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, bf16_t>), grid, block, lds, s, d, g);            \
+      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, float>), grid, block, lds, s, d, g);                                    \
+    }                                                                                                                    \
+  } while (0)
 
 // ---- host-side checks shared by the entry points ------------------------------------------------------------------
 // The crop windows of every view lie inside the scaled frame.
