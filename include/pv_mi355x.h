@@ -532,6 +532,39 @@ typedef struct pv_batch_views_desc {
 } pv_batch_views_desc;
 int pv_batch_views(const pv_batch_views_desc* d, pv_stream_t stream);
 
+/* ---- frame-list sources: every frame individually addressed ------------------------------------------------------------
+ * pv_batch_views reads a video as ONE allocation with a constant frame stride.  A hardware decoder hands out surfaces from a
+ * pool -- one allocation per frame, uniform geometry and pitch, any order, reused -- and a live stream never is one tensor.
+ * pv_frame_views is pv_batch_views with a source given as a list of frame addresses: nothing is copied together first.
+ * Launch:       `batch`, a whole pv_batch_views_desc with the meaning it has there, except sources[i].src.
+ * Frames:       ONE table frame_ptrs[n_frame_ptrs] of 64-bit device addresses for the launch, on the host (`frame_ptrs`:
+ *               validated) and the same bytes on the device (`frame_ptrs_dev`: what the kernel reads), under the rule of
+ *               sources / sources_dev: THE CALLER UPLOADS THE VERY BUFFER IT PASSES.  The `src` of a record is the DEVICE
+ *               address of the record's slice of the table, frame_ptrs_dev + k (8-byte aligned); the slice's N entries are the
+ *               base addresses of frames 0 .. N-1.  An address may appear any number of times, in any slice.  The record
+ *               keeps its 96 bytes and pv_box_views reads the same records (it never follows `src`).
+ * One frame:    PV_SRC_NTHWC: dense [Hs,Ws,3], PV_U8.  PV_SRC_NCTHW: dense [C,Hs,Ws] -- the plane stride is that of ONE
+ *               frame --, PV_U8 or PV_F32.  PV_SRC_YUV420: one surface as in pv_yuv_views_desc (u_offset, v_offset, y_pitch,
+ *               c_pitch from the frame's base); frame_stride keeps its meaning as the extent of one frame, for the plane
+ *               checks.  uint8 frames may start at any byte; fp32 frames at a multiple of 4.  One launch has one form.
+ * Table entry:  clamped into [0, N-1] OF THE ITEM'S SOURCE before the slice is indexed, as pv_batch_views clamps it before
+ *               the multiply.  Only the aligned 16-byte granules that cover a byte of a staged span are fetched, so a frame
+ *               that ends at the end of its allocation is read safely.
+ * Arithmetic:   item i is bit for bit what pv_batch_views writes for the same frames laid out as one video.
+ * PV_ERR_INVALID: whatever pv_batch_views rejects; a null frame_ptrs or frame_ptrs_dev, a frame_ptrs_dev that is no multiple
+ * of 8, n_frame_ptrs <= 0; a record named by an item whose src is not frame_ptrs_dev + 8 k with 0 <= k and
+ * k + N <= n_frame_ptrs; a null frame address in such a slice (read from the host copy); PV_F32 sources with a frame address
+ * that is no multiple of 4.  PV_ERR_UNSUPPORTED: as pv_batch_views.  Validation precedes every HIP call.
+ */
+typedef struct pv_frame_views_desc {
+  pv_batch_views_desc batch;          /* as for pv_batch_views; sources[i].src = frame_ptrs_dev + first_i       */
+  const uint64_t* frame_ptrs;         /* [n_frame_ptrs] on the HOST: device addresses of frames                */
+  const uint64_t* frame_ptrs_dev;     /* the same bytes on the device                                          */
+  int32_t n_frame_ptrs;
+  int32_t reserved;
+} pv_frame_views_desc;
+int pv_frame_views(const pv_frame_views_desc* d, pv_stream_t stream);
+
 /* ---- key-frame detection: the boxes of a forward mapped into its views, on the device ---------------------------------
  * A detection forward built by pv_batch_views holds one clip per key frame, and every key frame has person boxes given in the
  * pixels of ITS source frame.  pv_box_views fills the RoI head's persistent [capacity][5] fp32 box buffer (what pv_roi_align

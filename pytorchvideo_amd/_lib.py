@@ -101,6 +101,8 @@ BatchViewsDesc = _struct("BatchViewsDesc", [
     ("ch_shift", _p), ("yuv2rgb", _p), ("bs", _i64)]
     + _ints("n_sources", "n_items", "n_rows", "t_stride", "C", "T", "src_dtype", "src_layout", "c_step", "Ho", "Wo", "n_views",
             "dst_layout", "dst_dtype", "c_p", "ld"))
+FrameViewsDesc = _struct("FrameViewsDesc", [
+    ("batch", BatchViewsDesc), ("frame_ptrs", _p), ("frame_ptrs_dev", _p)] + _ints("n_frame_ptrs", "reserved"))
 BoxViewsDesc = _struct("BoxViewsDesc", [
     ("boxes", _p), ("box_item", _p), ("sources_dev", _p), ("items_dev", _p), ("dst", _p), ("dst_box", _p)]
     + _ints("n_boxes", "n_seq", "n_sources", "n_views", "box0", "n_launch", "item0", "n_items", "Ho", "Wo", "capacity",
@@ -185,6 +187,7 @@ _SYMBOLS = [
     ("pv_video_views", C.c_int, [C.POINTER(VideoViewsDesc), _p]),
     ("pv_yuv_views", C.c_int, [C.POINTER(YuvViewsDesc), _p]),
     ("pv_batch_views", C.c_int, [C.POINTER(BatchViewsDesc), _p]),
+    ("pv_frame_views", C.c_int, [C.POINTER(FrameViewsDesc), _p]),
     ("pv_box_views", C.c_int, [C.POINTER(BoxViewsDesc), _p]),
     ("pv_layernorm", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_affine_rows", C.c_int, [C.POINTER(RowsDesc), _p]),

@@ -418,6 +418,11 @@ class Session:
         """`video_views` for a BatchViewsDesc (one source per item: pv_batch_views; transforms.DevicePacker.fill_batch)."""
         self._views_into(d, d.C, ref, planar, "pv_batch_views")
 
+    def frame_views(self, f, ref, planar=None):
+        """`batch_views` for a FrameViewsDesc (every frame individually addressed: pv_frame_views); the destination goes
+        into the BatchViewsDesc it embeds."""
+        self._views_into(f.batch, f.batch.C, ref, planar, "pv_frame_views", outer=f)
+
     def box_views(self, d, ptr):
         """Fill a detection head's box buffer `ptr` (`alloc_boxes`) by pv_box_views: `d` is a BoxViewsDesc whose boxes, item
         window, records and capacity the caller (transforms.DevicePacker.fill_boxes) has set; the destination is filled in
@@ -427,7 +432,7 @@ class Session:
         with torch.cuda.device(self.device):
             L.check(L.lib().pv_box_views(C.byref(d), self._stream()), "box_views")
 
-    def _views_into(self, d, channels, ref, planar, entry):
+    def _views_into(self, d, channels, ref, planar, entry, outer=None):
         n = d.n_items
         if not 0 <= n <= ref.B or (channels, d.T, d.Ho, d.Wo) != (ref.C, ref.T, ref.H, ref.W):
             raise L.PvError("deploy form was converted for input %s, got %d items of %s" %
@@ -439,22 +444,23 @@ class Session:
                 else:
                     self.arena_t[ref.off + n * ref.bs * ref.itemsize: ref.off + ref.B * ref.bs * ref.itemsize].zero_()
         if n:
-            self._resample_into(d, ref, planar, entry)
+            self._resample_into(d, ref, planar, entry, outer)
         elif planar is not None:
             self.ingest(planar, ref)      # nothing to write: only point the stem at the zeroed clip
         else:
             self._point_input(ref, 0)
 
-    def _resample_into(self, d, ref, planar, entry):
+    def _resample_into(self, d, ref, planar, entry, outer=None):
         """Set the destination of the resampling descriptor `d` -- `planar`, or the arena buffer `ref` in its own layout --
-        run `entry` on it and point the ops that read `ref` at what was written."""
+        run `entry` on it (on `outer`, the descriptor that embeds `d`, when given) and point the ops that read `ref` at what
+        was written."""
         if planar is not None:
             d.dst, d.dst_layout, d.dst_dtype = planar.data_ptr(), L.DST_NCTHW, L.PV_BF16
         else:
             d.dst, d.dst_layout, d.dst_dtype = self.arena_t.data_ptr() + ref.off, L.DST_NDHWC, self.pv_dtype
             d.c_p, d.ld, d.bs = (4 if ref.ld == 4 else pad8(ref.C)), ref.ld, ref.bs
         with torch.cuda.device(self.device):
-            L.check(getattr(L.lib(), entry)(C.byref(d), self._stream()), entry[3:])
+            L.check(getattr(L.lib(), entry)(C.byref(d if outer is None else outer), self._stream()), entry[3:])
         if planar is not None:
             self.ingest(planar, ref)      # repoints the stem; nothing is copied
         else:

@@ -222,3 +222,29 @@ def keyframe_frame_table(timestamps, clip_duration, num_frames: int, fps, frames
         rows.append(first + temporal_indices(stop - first, frames_per_clip))
         centres.append(first + (stop - first) // 2)
     return torch.stack(rows).to(torch.int32), centres
+
+
+def stream_windows(clip_duration, stride, fps, frames_seen: int, first_window: int = 0):
+    """The windows of a live stream that are COMPLETE once `frames_seen` frames have arrived, from window `first_window`
+    on: a list of (k, start_sec, first, stop).  Window k covers [k * stride, k * stride + clip_duration) seconds under the
+    frame rule of `clip_frame_range` -- frames range(ceil(fps * start), ceil(fps * end)) -- in exact `Fraction` arithmetic,
+    and is complete when its last frame has been seen: ceil(fps * end) <= frames_seen.  Its frame-table row is
+    first + temporal_indices(stop - first, clip_frames).  A pure function of its arguments.
+
+    For frames_seen / fps >= clip_duration these are exactly the clips `clip_frame_table(UniformClipSampler(clip_duration,
+    stride), frames_seen, fps, T)` cuts from a video of `frames_seen` frames (for numbers that are exact fractions the
+    sampler's eps never matters); a stream shorter than one clip has no complete window, where the sampler cuts one short
+    clip."""
+    d, step, fps = Fraction(clip_duration), Fraction(stride), Fraction(fps)
+    if d <= 0 or step <= 0 or fps <= 0 or frames_seen < 0 or first_window < 0:
+        raise ValueError("clip_duration, stride and fps are positive, frames_seen and first_window not negative")
+    out, k = [], int(first_window)
+    while True:
+        start = k * step
+        first, stop = math.ceil(fps * start), math.ceil(fps * (start + d))
+        if stop > frames_seen:
+            return out
+        if stop <= first:
+            raise ValueError("a window of %s s holds no frame at %s fps" % (d, fps))
+        out.append((k, start, first, stop))
+        k += 1

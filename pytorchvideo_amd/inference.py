@@ -16,12 +16,19 @@ per call instead of one of each per video.
 data/ava.py's `TimeStampClipSampler`) -- a clip around every key-frame time stamp, a variable number of person boxes per key
 frame given in the pixels of the source frame -- with the boxes mapped into the view on the device (`pv_box_views`) and as many
 key frames per forward as the deploy batch and the box capacity hold.
+
+Every predictor also takes a video as a `transforms.FrameList` -- one device tensor per frame, as a hardware decoder's
+surface pool hands them out -- and reads each frame where it lies (`pv_frame_views`); `StreamPredictor` scores a live
+stream, whose frames arrive a few at a time, as its windows complete.
 """
+import math
+from fractions import Fraction
+
 import torch
 
-from .data.clip_sampling import clip_frame_table, keyframe_frame_table
+from .data.clip_sampling import clip_frame_table, keyframe_frame_table, stream_windows
 from .ensemble import VideoEnsembler
-from .transforms import DevicePacker, batch_chunks
+from .transforms import DevicePacker, FrameList, batch_chunks, temporal_indices
 
 
 class VideoPredictor:
@@ -36,6 +43,8 @@ class VideoPredictor:
     "YV12" (`yuv`, `coded_height`, `height` as for `DevicePacker`), read in place with the strides it has and converted by
     the ingest itself.  The frame table is built, range-checked and uploaded on EVERY call (one video per call); to score
     the same video again without that, keep `packer.video_tables(...)` and drive `packer.fill_video` / `launch` directly.
+    `video` may also be a `transforms.FrameList` (one device tensor per frame): it is walked as a one-video batch
+    (`packer.video_batch` / `fill_batch`, `pv_frame_views`), the same items at the same batch positions.
     After a call `video_ensembler.counts` (and `clip_ensembler.counts`) hold the rows folded."""
 
     def __init__(self, deployed, clip_sampler, mean, std, div255, short_side, crop_size, spatial_idx=(0, 1, 2),
@@ -54,6 +63,8 @@ class VideoPredictor:
     def __call__(self, video, fps, return_clip_scores=False):
         p = self.packer
         device = p.sess.device
+        if isinstance(video, FrameList):
+            return self._call_frames(video, fps, return_clip_scores)
         if video.dim() != (3 if p.is_yuv else 4):
             raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(video.shape)))
         num_frames = video.shape[1] if self.src_layout == "NCTHW" else video.shape[0]
@@ -81,12 +92,32 @@ class VideoPredictor:
         scores = self.video_ensembler.result()[0]
         return (scores, self.clip_ensembler.result()) if return_clip_scores else scores
 
+    def _call_frames(self, frames, fps, return_clip_scores):
+        """A FrameList: the loop of `__call__` over a one-video batch."""
+        p = self.packer
+        device = p.sess.device
+        table, _ = clip_frame_table(self.sampler, len(frames), fps, p.clip_frames)
+        batch = p.video_batch([frames], [table])                 # every check, and the one upload
+        zeros = torch.zeros(p.batch, dtype=torch.int32, device=device)
+        for i0, n in batch_chunks(batch.total, p.batch):
+            p.fill_batch(batch, i0, n)
+            logits = p.launch()[:n]                              # rows of the zero-filled tail are never folded
+            if i0 == 0:
+                self.video_ensembler = VideoEnsembler(1, logits.shape[1], self.method, device)
+                self.clip_ensembler = VideoEnsembler(batch.n_rows, logits.shape[1], self.method, device) if return_clip_scores else None
+            self.video_ensembler.update(logits, zeros[:n])
+            if return_clip_scores:
+                self.clip_ensembler.update(logits, batch.clip_of[i0:i0 + n])
+        p.release_batch()                                        # the frames are the caller's again
+        scores = self.video_ensembler.result()[0]
+        return (scores, self.clip_ensembler.result()) if return_clip_scores else scores
+
 
 class VideoBatchPredictor:
     """`VideoBatchPredictor(deployed, clip_sampler, mean, std, div255, short_side, crop_size)(videos, fps)` = [V, num_classes]
-    fp32 scores of a list of V videos, each folded as `VideoPredictor` folds one.  The videos are device tensors of ANY
-    lengths and frame sizes in the one `src_layout` (for a YUV layout `height` / `coded_height` of the call are one number or
-    one per video); `fps` is one number or one per video.  The views of all videos form one video-major sequence that is
+    fp32 scores of a list of V videos, each folded as `VideoPredictor` folds one.  The videos are device tensors -- or ALL
+    `transforms.FrameList`s, one device tensor per frame -- of ANY lengths and frame sizes in the one `src_layout` (for a
+    YUV layout `height` / `coded_height` of the call are one number or one per video); `fps` is one number or one per video.  The views of all videos form one video-major sequence that is
     walked in chunks of the deploy batch, so a forward holds views of several videos and only the LAST forward of a call can
     be short; the frame tables of all videos are built, range-checked and uploaded once per call.
     `return_clip_scores=True` adds a list of V tensors [n_clips_j, num_classes].  After a call `video_ensembler.counts`
@@ -117,6 +148,9 @@ class VideoBatchPredictor:
         dims = 3 if p.is_yuv else 4
         tables = []
         for j, (video, rate) in enumerate(zip(videos, rates)):
+            if isinstance(video, FrameList):                     # its frames are checked by video_batch
+                tables.append(clip_frame_table(self.sampler, len(video), rate, p.clip_frames)[0])
+                continue
             if video.dim() != dims:
                 raise RuntimeError("video %d: expected a %d-d %s video, got %s" % (j, dims, self.src_layout, tuple(video.shape)))
             num_frames = video.shape[1] if self.src_layout == "NCTHW" else video.shape[0]
@@ -178,8 +212,8 @@ class KeyframeDetector:
     tutorial's protocol: boxes clipped to the frame, short side scaled to `short_side`, NO crop, boxes clipped again -- every
     video must then scale to the deploy form's H x W (256 x 455 for 720p at short_side 256).  With `crop_size` the view is the
     `spatial_idx` crop and the boxes follow it as `DevicePacker(dm)(clip, bboxes)` moves them.  `video`, `src_layout`, `yuv`,
-    `coded_height`, `height` as for `VideoPredictor` (YUV 4:2:0 included); `video` may also be a LIST of videos, with
-    `timestamps` and `boxes` given per video and `fps` one number or one per video.
+    `coded_height`, `height` as for `VideoPredictor` (YUV 4:2:0 and `transforms.FrameList` included); `video` may also be a
+    LIST of videos, with `timestamps` and `boxes` given per video and `fps` one number or one per video.
 
     Frame tables, the box list and its key-frame index are uploaded once per call; per forward there are only the ingest,
     one `pv_box_views` launch and the replay.  The key frames are walked by `keyframe_chunks`.  Everything is validated
@@ -221,12 +255,13 @@ class KeyframeDetector:
         heights, coded = per_video(height), per_video(coded_height)
         kept, tables, counts, flat = [], [], [], []
         for j, (vid, rate, ts, bl) in enumerate(zip(videos, rates, stamps, box_lists)):
-            if vid.dim() != dims:
+            as_frames = isinstance(vid, FrameList)               # its frames are checked by video_batch, and never moved
+            if not as_frames and vid.dim() != dims:
                 raise RuntimeError("video %d: expected a %d-d %s video, got %s" % (j, dims, self.src_layout, tuple(vid.shape)))
             ts, bl = list(ts), list(bl)
             if len(ts) != len(bl) or not ts:
                 raise ValueError("video %d: %d box tensors for %d time stamps" % (j, len(bl), len(ts)))
-            num_frames = vid.shape[1] if self.src_layout == "NCTHW" else vid.shape[0]
+            num_frames = len(vid) if as_frames else (vid.shape[1] if self.src_layout == "NCTHW" else vid.shape[0])
             table, _ = keyframe_frame_table(ts, self.clip_duration, num_frames, rate, p.clip_frames)
             for k, b in enumerate(bl):
                 if not isinstance(b, torch.Tensor) or b.dim() != 2 or b.shape[1] != 4:
@@ -236,8 +271,9 @@ class KeyframeDetector:
             rows = [k for k, c in enumerate(own) if c > 0]
             if not rows:
                 continue                                         # no key frame of this video has a box
-            vid = vid.to(device, non_blocking=True)
-            if not p.is_yuv:
+            if not as_frames:
+                vid = vid.to(device, non_blocking=True)
+            if not as_frames and not p.is_yuv:
                 if vid.dtype not in (torch.uint8, torch.float32):
                     vid = vid.float()
                 vid = vid.contiguous()
@@ -265,4 +301,124 @@ class KeyframeDetector:
             item0, box0 = item0 + n_items, box0 + n
             self.forwards += 1
         p.release_batch()                                        # the videos are the caller's again
+        return out
+
+
+class StreamState:
+    """The host bookkeeping of `StreamPredictor`, no device involved: which windows of a stream a push completes
+    (`data.stream_windows`) and which frames may be dropped afterwards.  Absolute frame numbers are Python ints; `base` is
+    the absolute number of the oldest frame still held and `next_window` the first window not yet emitted."""
+
+    def __init__(self, clip_duration, stride, fps):
+        self.duration, self.stride, self.fps = Fraction(clip_duration), Fraction(stride), Fraction(fps)
+        if self.duration <= 0 or self.stride <= 0 or self.fps <= 0:
+            raise ValueError("clip_duration, stride and fps are positive")
+        self.seen = self.base = self.next_window = 0
+
+    @property
+    def held(self):
+        return self.seen - self.base
+
+    @property
+    def bound(self):
+        """`held` after a push of n frames is at most ceil(fps * clip_duration) + n: the first unemitted window is incomplete,
+        so fewer than ceil(fps * d) + 1 of its frames had arrived before the push ended."""
+        return math.ceil(self.fps * self.duration)
+
+    def push(self, n):
+        """`n` more frames have arrived: the windows (k, start_sec, first, stop) they complete, frames in ABSOLUTE numbers.
+        The caller scores them -- every frame from `base` on is still held -- and then calls `drop()`."""
+        if n < 0:
+            raise ValueError("a push adds frames")
+        self.seen += n
+        windows = stream_windows(self.duration, self.stride, self.fps, self.seen, self.next_window)
+        if windows:
+            self.next_window = windows[-1][0] + 1
+        return windows
+
+    def drop(self):
+        """Frames below the first frame of the first unemitted window are no longer needed: returns how many of the oldest
+        held frames to let go, and moves `base` behind them."""
+        keep_from = min(math.ceil(self.fps * (self.next_window * self.stride)), self.seen)
+        n = max(0, keep_from - self.base)
+        self.base += n
+        return n
+
+
+class StreamPredictor:
+    """`StreamPredictor(deployed, clip_duration, stride, fps, mean, std, div255, short_side, crop_size).push(frames)` scores
+    ONE live stream as its windows complete: window k covers [k * stride, k * stride + clip_duration) seconds of the stream
+    (`data.stream_windows`: for a stream of at least one clip exactly the clips `UniformClipSampler(clip_duration, stride)`
+    cuts from the frames seen so far), and `push` returns one (k, start_sec, scores) per window the pushed frames complete,
+    `scores` a [num_classes] fp32 device tensor: the fold (`method`) over the window's views, the row `VideoPredictor`
+    returns for that clip with `return_clip_scores=True`.
+
+    `frames` is an iterable of per-frame device tensors in the forms of `transforms.FrameList` for `src_layout`; they are
+    NOT copied -- the ingest reads each where it lies (`pv_frame_views`) -- and are held until no unemitted window needs
+    them: after every push the frames in front of the first unemitted window are let go, so `frames_held` is at most
+    ceil(fps * clip_duration) plus the size of the push.  The windows one push completes, times the views, are walked in
+    chunks of the deploy batch from position 0; a short chunk zeroes the tail.  `push` enqueues its work on the launch stream
+    and returns without waiting.  A decoder may therefore recycle a surface once the scores of the LAST window that contains
+    it have been read on the host, or after a synchronise on the launch stream -- not when `push` returns.
+
+    `deployed` is a classification form; one object scores one stream; `reset()` starts a new one.  Windows are scored
+    independently: nothing is smoothed or voted over windows."""
+
+    def __init__(self, deployed, clip_duration, stride, fps, mean, std, div255, short_side, crop_size, spatial_idx=(1,),
+                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False)):
+        if getattr(deployed, "_pv_load_boxes", None) is not None:
+            raise ValueError("StreamPredictor scores the windows of a stream with a classification form; a detection model's "
+                             "boxes belong to key frames: KeyframeDetector")
+        if method not in ("sum", "max"):
+            raise NotImplementedError("ensemble method %r (the reference knows 'sum' and 'max')" % method)
+        self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv)
+        self.method, self.src_layout = method, src_layout
+        self.state = StreamState(clip_duration, stride, fps)
+        self._frames = []
+        self.forwards = 0                                        # forwards of the last push
+
+    def reset(self):
+        """Forget the stream: the next frame pushed is frame 0 of a new one."""
+        self.state = StreamState(self.state.duration, self.state.stride, self.state.fps)
+        self._frames = []
+
+    @property
+    def frames_held(self):
+        return len(self._frames)
+
+    @torch.no_grad()
+    def push(self, frames):
+        p = self.packer
+        device = torch.device(p.sess.device)
+        new = list(frames)
+        self.forwards = 0
+        if not new:
+            return []
+        held = FrameList(self._frames + new)                     # one form over the whole stream; refused before any change
+        held.geometry(self.src_layout)
+        if held.device.type != device.type or (device.index is not None and held.device.index != device.index):
+            raise RuntimeError("the frames are on %s, the deploy form on %s" % (held.device, device))
+        st = self.state
+        base, batch = st.base, None
+        windows = stream_windows(st.duration, st.stride, st.fps, st.seen + len(new), st.next_window)
+        if windows:
+            t = p.clip_frames
+            table = torch.stack([first - base + temporal_indices(stop - first, t) for _, _, first, stop in windows]).to(torch.int32)
+            batch = p.video_batch([held], [table])               # every check, and the one upload: entries count from `base`
+        self._frames = held.frames                               # nothing was refused: the push counts
+        st.push(len(new))                                        # the same windows: stream_windows is pure
+        out = []
+        if windows:
+            clips = None
+            for i0, n in batch_chunks(batch.total, p.batch):
+                p.fill_batch(batch, i0, n)
+                logits = p.launch()[:n]                          # rows of the zero-filled tail are never folded
+                if clips is None:
+                    clips = VideoEnsembler(len(windows), logits.shape[1], self.method, device)
+                clips.update(logits, batch.clip_of[i0:i0 + n])
+                self.forwards += 1
+            p.release_batch()
+            scores = clips.result()
+            out = [(k, start, scores[i]) for i, (k, start, _, _) in enumerate(windows)]
+        del self._frames[:st.drop()]
         return out

@@ -442,6 +442,71 @@ def _device_scale_crop_yuv(frames, short_side, crop_size, views, mean, std, div2
     return out
 
 
+# --------------------------------------------------------------------------- frame-list sources (pv_frame_views)
+class FrameList:
+    """One video as a sequence of per-frame device tensors -- a decoder's surface pool, or the frames of a live stream --
+    for `DevicePacker.video_batch` and the predictors of `inference`: the ingest reads every frame where it lies
+    (`pv_frame_views`), nothing is stacked first.
+
+    The frames share one device, dtype, shape and set of strides.  Per frame, by the packer's source layout: "NTHWC" a
+    contiguous uint8 [H, W, 3]; "NCTHW" a contiguous uint8 or fp32 [C, H, W]; the YUV layouts a uint8 2-d [Hc*3/2, W] with
+    stride(1) == 1 and any row pitch P >= W (`yuv_geometry` of a one-frame view: the surface is the Hc*3/2 * P bytes from
+    its first sample -- the half-pitch chroma rows of I420 / YV12 lie partly behind column W).  `src_layout`, when given,
+    checks that form at construction; `video_batch` checks it in any case.  A frame may be a view at any offset inside a
+    larger buffer and appear more than once, and the frames may have been allocated in any order.  The list keeps its
+    tensors alive; `len()` is the frame count; `stack(src_layout)` is the contiguous video the frames make up."""
+
+    def __init__(self, frames, src_layout=None):
+        frames = list(frames)
+        if not frames:
+            raise ValueError("a FrameList holds at least one frame")
+        f0 = frames[0]
+        for i, f in enumerate(frames):
+            if not isinstance(f, torch.Tensor):
+                raise TypeError("frame %d is a %s, not a tensor" % (i, type(f).__name__))
+            for what, a, b in (("device", f.device, f0.device), ("dtype", f.dtype, f0.dtype),
+                               ("shape", tuple(f.shape), tuple(f0.shape)), ("strides", f.stride(), f0.stride())):
+                if a != b:
+                    raise RuntimeError("the frames of a FrameList share one device, dtype, shape and set of strides: "
+                                       "frame %d has %s %s, frame 0 %s" % (i, what, a, b))
+        self.frames = frames
+        self.device, self.dtype, self.shape = f0.device, f0.dtype, tuple(f0.shape)
+        if src_layout is not None:
+            self.geometry(src_layout)
+
+    def __len__(self):
+        return len(self.frames)
+
+    def geometry(self, src_layout, coded_height=None, height=None):
+        """(C, Hs, Ws, geom) of one frame in `src_layout`, `geom` being `yuv_geometry` of a one-frame view for the YUV
+        layouts (frame_stride: the extent of one frame) and None otherwise.  RuntimeError for a frame of another form."""
+        f = self.frames[0]
+        if src_layout in YUV_LAYOUTS:
+            if f.dim() != 2:
+                raise RuntimeError("a %s frame is uint8 [Hc*3/2, W], got %s %s" % (src_layout, f.dtype, tuple(f.shape)))
+            geom = yuv_geometry(f[None], src_layout, coded_height, height)
+            return 3, geom["Hs"], geom["Ws"], geom
+        if src_layout not in ("NCTHW", "NTHWC"):
+            raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,))
+        if f.dim() != 3 or not f.is_contiguous() or f.dtype not in (torch.uint8, torch.float32):
+            raise RuntimeError("a frame of a FrameList is a contiguous uint8 or fp32 [H,W,3] / [C,H,W] tensor, got %s %s with "
+                               "strides %s" % (f.dtype, tuple(f.shape), f.stride()))
+        if src_layout == "NCTHW":
+            return f.shape[0], f.shape[1], f.shape[2], None
+        if f.shape[2] != 3 or f.dtype != torch.uint8:
+            raise RuntimeError("a frame-interleaved frame is uint8 [H,W,3], got %s %s" % (f.dtype, tuple(f.shape)))
+        return 3, f.shape[0], f.shape[1], None
+
+    def stack(self, src_layout="NTHWC"):
+        """The contiguous video: [N,H,W,3], [C,N,H,W] ("NCTHW") or [N, Hc*3/2, W] (a YUV layout, pitch W)."""
+        return torch.stack(self.frames, dim=1 if src_layout == "NCTHW" else 0)
+
+
+def _refuse_frames(video, what):
+    if isinstance(video, FrameList):
+        raise RuntimeError("%s takes one tensor; a FrameList goes through video_batch / fill_batch" % what)
+
+
 # --------------------------------------------------------------------------- many videos per forward (pv_batch_views)
 def batch_items(clips_per_video, n_views):
     """The video-major item sequence of a batch of videos: video j, then `clip * n_views + v`.  Returns (items, video_of,
@@ -479,9 +544,14 @@ class VideoBatch:
     """What `DevicePacker.video_batch` uploaded for a list of videos: the `pv_view_source` records and the `pv_view_item`
     sequence (host copies and the device copies of the same bytes), the concatenated per-pathway frame tables, and the
     videos themselves, kept alive.  `total` items; `video_of` / `clip_of` (int32, device) = the video and the row of the
-    concatenated table behind every item; `clips[j]` / `row0[j]` = the clips of video j and its first row."""
+    concatenated table behind every item; `clips[j]` / `row0[j]` = the clips of video j and its first row.  For videos
+    given as `FrameList`s `frame_ptrs` (host int64, video-major: the frame addresses of video j from `frame_first[j]` on)
+    and `frame_ptrs_dev`, the same bytes on the device, are the pointer table of `pv_frame_views`, and the `src` of record j
+    is the device address of its slice; for tensors they are None."""
 
-    def __init__(self, videos, sources, items, items_t, tables, video_of, clip_of, clips, row0, n_views, src_dtype, upload):
+    def __init__(self, videos, sources, items, items_t, tables, video_of, clip_of, clips, row0, n_views, src_dtype, upload,
+                 frame_ptrs=None, frame_ptrs_dev=None, frame_first=None):
+        self.frame_ptrs, self.frame_ptrs_dev, self.frame_first = frame_ptrs, frame_ptrs_dev, frame_first
         self.videos, self.sources, self.items = list(videos), sources, items
         self.n_views, self.src_dtype, self.clips, self.row0 = n_views, src_dtype, list(clips), list(row0)
         self.total, self.n_rows = len(items), sum(clips)
@@ -498,11 +568,16 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
     """The host half of `DevicePacker.video_batch` (see there): validate every video, build the records, the item sequence
     and the concatenated tables, and hand them to `upload` (host tensor -> device tensor) once.  `crop_size` is the side of
     the square crop, or a pair (Ho, Wo): NO crop -- the window is the whole scaled frame, and every video must scale to
-    exactly Ho x Wo."""
+    exactly Ho x Wo.  The videos are all tensors or all `FrameList`s; for `FrameList`s ONE int64 table of frame addresses,
+    video-major, is uploaded in front of the records, and record j points at its slice of the device copy."""
     from . import _lib as L
     videos = list(videos)
     if not videos or len(tables) != len(videos):
         raise ValueError("%d frame tables for %d videos" % (len(tables), len(videos)))
+    as_frames = isinstance(videos[0], FrameList)
+    if any(isinstance(v, FrameList) != as_frames for v in videos):
+        raise ValueError("the videos of one call are all tensors or all FrameLists, not a mix of tensors and FrameLists "
+                         "(wrap a tensor: FrameList(video.unbind(0)))")
     is_yuv = src_layout in YUV_LAYOUTS
     no_crop = isinstance(crop_size, (tuple, list))
     ho, wo = (int(crop_size[0]), int(crop_size[1])) if no_crop else (crop_size, crop_size)
@@ -522,7 +597,14 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
         if video.device.type != device.type or (device.index is not None and video.device.index != device.index):
             raise RuntimeError("video %d is on %s, the deploy form on %s" % (j, video.device, device))
         rec = sources[j]
-        if is_yuv:
+        if as_frames:
+            c, hs, ws, geom = video.geometry(src_layout, coded[j], heights[j])
+            nf = len(video)
+            if video.dtype != dtype:
+                raise RuntimeError("the videos of one batch have one dtype: video %d is %s, video 0 %s" % (j, video.dtype, dtype))
+            for k in ("frame_stride", "u_offset", "v_offset", "y_pitch", "c_pitch") if is_yuv else ():
+                setattr(rec, k, geom[k])
+        elif is_yuv:
             if video.dim() != 3:
                 raise RuntimeError("video %d: expected one 3-d %s video, got %s" % (j, src_layout, tuple(video.shape)))
             geom = yuv_geometry(video, src_layout, coded[j], heights[j])
@@ -545,7 +627,7 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
                                % (j, hs, ws, hn, wn, ho, wo))
         if not no_crop and (crop_size > hn or crop_size > wn):
             raise RuntimeError("video %d: a %d crop does not fit the %d x %d frame scaled to %d x %d" % (j, crop_size, hs, ws, hn, wn))
-        rec.src, rec.N, rec.Hs, rec.Ws, rec.Hn, rec.Wn = video.data_ptr(), nf, hs, ws, hn, wn
+        rec.src, rec.N, rec.Hs, rec.Ws, rec.Hn, rec.Wn = (None if as_frames else video.data_ptr()), nf, hs, ws, hn, wn
         for k, v in enumerate(views):
             rec.y_off[k], rec.x_off[k] = (0, 0) if no_crop else crop_offsets(hn, wn, crop_size, v)
         # (float)Hs / (float)Hn: sizes are exact in fp32, and a double quotient rounded once more to fp32 IS the fp32 quotient
@@ -563,7 +645,18 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
     items_t, video_of, clip_of, row0 = batch_items(clips, len(views))
     items = (L.ViewItem * items_t.shape[0]).from_buffer_copy(items_t.numpy().tobytes())
     src_dtype = L.PV_U8 if (is_yuv or dtype == torch.uint8) else L.PV_F32
-    return VideoBatch(videos, sources, items, items_t, cat, video_of, clip_of, clips, row0, len(views), src_dtype, upload)
+    if not as_frames:
+        return VideoBatch(videos, sources, items, items_t, cat, video_of, clip_of, clips, row0, len(views), src_dtype, upload)
+    # the pointer table of the call: the frame addresses of video j from first[j] on; the records point into the DEVICE copy
+    ptrs = torch.tensor([f.data_ptr() for video in videos for f in video.frames], dtype=torch.int64)
+    first = [0]
+    for n in nums_frames[:-1]:
+        first.append(first[-1] + n)
+    ptrs_dev = upload(ptrs)
+    for rec, k in zip(sources, first):
+        rec.src = ptrs_dev.data_ptr() + 8 * k
+    return VideoBatch(videos, sources, items, items_t, cat, video_of, clip_of, clips, row0, len(views), src_dtype, upload,
+                      ptrs, ptrs_dev, first)
 
 
 @torch.no_grad()
@@ -749,6 +842,7 @@ class DevicePacker:
         if self.is_yuv and load_boxes is not None:
             raise ValueError("a detection model does not take %s frames a clip at a time: its boxes are mapped on the host "
                              "there; use video_batch / fill_batch / fill_boxes (inference.KeyframeDetector)" % self.src_layout)
+        _refuse_frames(clip, "a clip-at-a-time call")
         if self.no_crop:
             raise RuntimeError("the no-crop mode (short_side without crop_size) runs through video_batch / fill_batch / "
                                "fill_boxes; a clip at a time takes short_side and crop_size")
@@ -868,6 +962,7 @@ class DevicePacker:
         `video` is [C,N,H,W] ("NCTHW"; uint8 or fp32) or [N,H,W,3] uint8 ("NTHWC"), contiguous and on the device -- or, for a
         YUV layout, uint8 [N, Hc*3/2, W] on the device with the strides it has (`yuv_geometry`) -- and must stay alive until
         the forward has run.  Nothing is launched here but the ingest: run `launch()` next."""
+        _refuse_frames(video, "fill_video")
         if self.short_side is None or self.no_crop:
             raise RuntimeError("fill_video resamples: construct the packer with short_side and crop_size")
         if getattr(self.model, "_pv_load_boxes", None) is not None:
@@ -951,7 +1046,10 @@ class DevicePacker:
         RGB / planar forms, `yuv_geometry` of the YUV forms with `height` / `coded_height` as one number or one per video,
         the crop fits the scaled frame, every table entry names a frame of ITS video), then the per-video records, the
         video-major item sequence (video j, then clip * n_views + v) and the concatenated per-pathway tables are uploaded
-        ONCE.  Returns a `VideoBatch`, which keeps the videos alive."""
+        ONCE.  The videos may instead ALL be `FrameList`s -- one device tensor per frame, as a decoder's surface pool hands
+        them out: one table of frame addresses is then uploaded with the records, and `fill_batch` reads every frame where
+        it lies (`pv_frame_views`); a mix of tensors and FrameLists is a ValueError.  Returns a `VideoBatch`, which keeps
+        the videos alive."""
         if self.short_side is None:
             raise RuntimeError("video_batch resamples: construct the packer with short_side and crop_size")
         if getattr(self.model, "_pv_load_boxes", None) is not None and not self.keyframes:
@@ -994,12 +1092,14 @@ class DevicePacker:
         self._boxes_src = None
 
     def _fill_batch(self, batch, item0, n_items):
-        """One pv_batch_views launch per pathway into this plan's buffers; see Session.video_views for the tail."""
+        """One pv_batch_views launch per pathway into this plan's buffers -- pv_frame_views, the same descriptor with the
+        call's pointer table beside it, for a batch of FrameLists; see Session.video_views for the tail."""
         import ctypes as C
         from . import _lib as L
         self._src = batch                                  # alive until the launch has run
         for i, (ref, tab) in enumerate(zip(self.refs, batch.tables)):
-            d = L.BatchViewsDesc()
+            f = L.FrameViewsDesc() if batch.frame_ptrs is not None else None
+            d = L.BatchViewsDesc() if f is None else f.batch
             d.sources, d.sources_dev = C.addressof(batch.sources), batch.sources_dev.data_ptr()
             first = min(item0, batch.total - 1) * C.sizeof(L.ViewItem)      # n_items == 0: any valid address, never read
             d.items, d.items_dev = C.addressof(batch.items) + first, batch.items_dev.data_ptr() + first
@@ -1012,7 +1112,12 @@ class DevicePacker:
             d.Ho, d.Wo, d.n_views = self.window[0], self.window[1], len(self.views)
             if self.scale is not None:
                 d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
-            self.sess.batch_views(d, ref, planar=self._planar_for(i, ref))
+            if f is None:
+                self.sess.batch_views(d, ref, planar=self._planar_for(i, ref))
+                continue
+            f.frame_ptrs, f.frame_ptrs_dev = batch.frame_ptrs.data_ptr(), batch.frame_ptrs_dev.data_ptr()
+            f.n_frame_ptrs = batch.frame_ptrs.numel()
+            self.sess.frame_views(f, ref, planar=self._planar_for(i, ref))
 
     # ------------------------------------------------------------------------- key-frame detection (pv_box_views)
     @property
