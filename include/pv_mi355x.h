@@ -39,7 +39,8 @@ enum pv_status {
   PV_ERR_HIP = -3          /* a HIP runtime call failed; see pv_last_error()          */
 };
 
-enum pv_dtype { PV_F32 = 0, PV_BF16 = 1, PV_U8 = 2 /* source of pv_ingest_ncdhw only: decoded video frames */ };
+enum pv_dtype { PV_F32 = 0, PV_BF16 = 1, PV_U8 = 2 /* source of pv_ingest_ncdhw only: decoded video frames */,
+                PV_U16 = 3 /* source of the YUV 4:2:0 ingest only: 16-bit little-endian samples (pv_yuv16_views) */ };
 
 enum pv_act {
   PV_ACT_NONE = 0,
@@ -448,7 +449,7 @@ typedef struct pv_yuv_views_desc {
   int64_t frame_stride;       /* bytes from one frame to the next                                                */
   int64_t u_offset, v_offset; /* bytes from the start of a frame to its first U / V sample                       */
   int32_t y_pitch, c_pitch;   /* bytes per luma row (>= Ws) and per chroma row (>= (Ws/2) * c_step)              */
-  int32_t c_step;             /* bytes between x-adjacent samples of one chroma plane: 2 interleaved, 1 planar   */
+  int32_t c_step;             /* SAMPLES between x-adjacent samples of one chroma plane: 2 interleaved, 1 planar */
   int32_t n_clips, T;         /* table rows, DESTINATION frames per clip                                         */
   int32_t N, t_stride;        /* frames in the source; table row stride (>= T)                                   */
   int32_t Hs, Ws;             /* display size of a frame: even                                                   */
@@ -460,6 +461,40 @@ typedef struct pv_yuv_views_desc {
   int32_t c_p, ld;            /* PV_DST_NDHWC only                                                               */
 } pv_yuv_views_desc;
 int pv_yuv_views(const pv_yuv_views_desc* d, pv_stream_t stream);
+
+/* ---- 10- to 16-bit YUV 4:2:0 (P010 / P012 / P016, yuv420p10le and kin) read by the ingest itself ---------------------------
+ * A hardware decoder given HEVC Main10, AV1 10-bit or VP9 profile 2 hands out P010: the NV12 arrangement with 16-bit
+ * little-endian samples, the value in the HIGH bits; a CPU decoder hands out yuv420p10le: the I420 arrangement, the value in
+ * the LOW bits.  pv_yuv16_views is pv_yuv_views on such frames -- the same descriptor, unchanged in size -- so that no
+ * narrowing pass and no RGB copy stands between the decoder and the ingest.
+ * Source:       N frames of 16-bit samples, frame n at src + n * frame_stride.  frame_stride, u_offset, v_offset, y_pitch and
+ *               c_pitch stay in BYTES; c_step is the distance in SAMPLES (2 interleaved, 1 planar; for pv_yuv_views samples
+ *               are bytes, so nothing changes there).  With s(a) the unsigned 16-bit little-endian code at byte address a,
+ *                   Y(y, x) = s(frame + y * y_pitch + 2 * x)                        0 <= y < Hs, 0 <= x < Ws (both even)
+ *                   U(j, i) = s(frame + u_offset + j * c_pitch + 2 * i * c_step)    0 <= j < Hs/2, 0 <= i < Ws/2
+ *                   V(j, i) = s(frame + v_offset + j * c_pitch + 2 * i * c_step)
+ *               c_step 2: |v_offset - u_offset| == 2 bytes (P010: v_offset = u_offset + 2; the V-first form swapped).
+ *               src, frame_stride, u_offset, v_offset, y_pitch and c_pitch are EVEN: every sample lies at an even address,
+ *               which is all the alignment there is (a row may start at any even byte).
+ * Arithmetic:   a sample is read whole and converted exactly to fp32; it is never sign-extended, shifted or masked.  From
+ *               there on the rule is pv_yuv_views' rule unchanged,
+ *                   rgb[c] = clamp(fma(M[c][2], V, fma(M[c][1], U, fma(M[c][0], Y, M[c][3]))), 0, 255)
+ *               per tap, chroma replicated over its 2 x 2 luma block, then pv_resample_crop's blend, affine map and single
+ *               rounding to dst_dtype.  Bit depth and bit alignment are NOT the library's business: they go into M, which the
+ *               caller composes, as standard and range do.  P010, P012 and P016 carry the value MSB-aligned, so their
+ *               limited-range matrix is the 8-bit matrix with its Y, U, V columns scaled by 2^-8 (an exact scaling: a P016
+ *               surface holding `nv12_sample << 8` gives the bits pv_yuv_views gives for the NV12 surface); an LSB-aligned
+ *               10-bit stream scales them by 2^-2 around 64 / 512.  Low bits that a non-conforming decoder leaves set in an
+ *               MSB-aligned sample are therefore part of the sample, worth less than one code of the stream's depth.
+ * PV_ERR_INVALID: everything pv_yuv_views rejects, with row and plane extents counted at 2 bytes per sample (y_pitch < 2 Ws,
+ * c_pitch < 2 (Ws/2) c_step, a last sample whose second byte leaves [0, frame_stride), c_step 2 with
+ * |v_offset - u_offset| != 2); an odd src, frame_stride, u_offset, v_offset, y_pitch or c_pitch.  PV_ERR_UNSUPPORTED: as
+ * pv_yuv_views; a staged strip beyond the kernels' LDS limit (two source rows of the widest window with their chroma, 64 KiB:
+ * a window some 8000 columns wide).  Validation precedes every HIP call.
+ * Out of scope: 4:2:2 and 4:4:4, filtered or sited chroma, transfer functions and tone mapping (PQ / HLG to SDR is the
+ * caller's decision), big-endian samples, 16-bit RGB.
+ */
+int pv_yuv16_views(const pv_yuv_views_desc* d, pv_stream_t stream);
 
 /* ---- many videos per launch: one source per destination item ---------------------------------------------------------
  * A dataset evaluation scores thousands of videos with a handful of views each (10 clips x 3 crops, 5 x 1, 1 x 3: the model
@@ -479,6 +514,9 @@ int pv_yuv_views(const pv_yuv_views_desc* d, pv_stream_t stream);
  *               One launch has one source form: src_dtype, src_layout, C and c_step belong to the launch.  NV12 and NV21
  *               sources may share a launch (c_step 2) and so may I420 and YV12 (c_step 1): the order of U and V is the
  *               record's u_offset / v_offset.  frame_stride .. c_pitch are ignored for the RGB / planar forms.
+ *               src_dtype PV_U16 with PV_SRC_YUV420: every record is a source of pv_yuv16_views (16-bit samples, byte
+ *               pitches and offsets, all even, src even); item i is then bit for bit what pv_yuv16_views writes.  One launch
+ *               has one sample width.  PV_U16 with an RGB / planar layout is PV_ERR_UNSUPPORTED.
  * Items:        n_items records (pv_view_item), likewise on host and device.  Item i of the launch is view items[i].view of
  *               table row items[i].row of source items[i].source and is written to position i of dst.  Any order, any mix of
  *               sources; rows and whole items may repeat.  A window of a longer sequence is a pointer offset into both
@@ -546,7 +584,9 @@ int pv_batch_views(const pv_batch_views_desc* d, pv_stream_t stream);
  * One frame:    PV_SRC_NTHWC: dense [Hs,Ws,3], PV_U8.  PV_SRC_NCTHW: dense [C,Hs,Ws] -- the plane stride is that of ONE
  *               frame --, PV_U8 or PV_F32.  PV_SRC_YUV420: one surface as in pv_yuv_views_desc (u_offset, v_offset, y_pitch,
  *               c_pitch from the frame's base); frame_stride keeps its meaning as the extent of one frame, for the plane
- *               checks.  uint8 frames may start at any byte; fp32 frames at a multiple of 4.  One launch has one form.
+ *               checks.  uint8 frames may start at any byte; fp32 frames at a multiple of 4; the frames of a PV_U16
+ *               launch (PV_SRC_YUV420 only, as in pv_batch_views) at an even address, read from the host copy.  One launch
+ *               has one form.
  * Table entry:  clamped into [0, N-1] OF THE ITEM'S SOURCE before the slice is indexed, as pv_batch_views clamps it before
  *               the multiply.  Only the aligned 16-byte granules that cover a byte of a staged span are fetched, so a frame
  *               that ends at the end of its allocation is read safely.

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("PV_MI355X_LIB") or os.path.join(_HERE, "_lib", "libpv
 
 PV_OK, PV_ERR_UNSUPPORTED, PV_ERR_INVALID, PV_ERR_HIP = 0, -1, -2, -3
 PV_F32, PV_BF16, PV_U8 = 0, 1, 2
+PV_U16 = 3     # 16-bit samples: the source dtype of the YUV 4:2:0 ingest only (pv_yuv16_views, BatchViewsDesc.src_dtype)
 ACT_NONE, ACT_RELU, ACT_SWISH, ACT_GELU, ACT_SIGMOID = 0, 1, 2, 3, 4
 POOL_MAX, POOL_AVG = 0, 1
 (OP_CONV3D, OP_DWCONV3D, OP_SE_GATE, OP_POOL3D, OP_LAYERNORM, OP_SOFTMAX_ROWS, OP_MEAN_ROWS,
@@ -186,6 +187,7 @@ _SYMBOLS = [
     ("pv_resample_crop", C.c_int, [C.POINTER(ResampleDesc), _p]),
     ("pv_video_views", C.c_int, [C.POINTER(VideoViewsDesc), _p]),
     ("pv_yuv_views", C.c_int, [C.POINTER(YuvViewsDesc), _p]),
+    ("pv_yuv16_views", C.c_int, [C.POINTER(YuvViewsDesc), _p]),
     ("pv_batch_views", C.c_int, [C.POINTER(BatchViewsDesc), _p]),
     ("pv_frame_views", C.c_int, [C.POINTER(FrameViewsDesc), _p]),
     ("pv_box_views", C.c_int, [C.POINTER(BoxViewsDesc), _p]),

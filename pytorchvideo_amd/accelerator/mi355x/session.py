@@ -414,6 +414,10 @@ class Session:
         """`video_views` for a YuvViewsDesc (YUV 4:2:0 frames converted inside the ingest: pv_yuv_views; 3 channels)."""
         self._views_into(d, 3, ref, planar, "pv_yuv_views")
 
+    def yuv16_views(self, d, ref, planar=None):
+        """`yuv_views` on 16-bit samples (P010 / yuv420p10le and kin: pv_yuv16_views; the same descriptor, byte geometry)."""
+        self._views_into(d, 3, ref, planar, "pv_yuv16_views")
+
     def batch_views(self, d, ref, planar=None):
         """`video_views` for a BatchViewsDesc (one source per item: pv_batch_views; transforms.DevicePacker.fill_batch)."""
         self._views_into(d, d.C, ref, planar, "pv_batch_views")

@@ -85,6 +85,28 @@ __global__ __launch_bounds__(kRsThreads) void batch_yuv_kernel(const pv_batch_vi
   rs_strip_yuv<CSTEP, FORM, D>(by_lds, g.R, g.pitch, g.pitch_c, g.c_base, s, rs_dst(d, 3), d.yuv2rgb, zi, t, true);
 }
 
+// The same on two-byte samples (PV_U16 / pv_yuv16_views).  A kernel of its own, spelled out rather than sharing a wrapper
+// with the one above: routed through a common inline function the 8-bit kernels come out with other instructions than
+// they had (commuted scalar adds), and their code is pinned.
+template <int CSTEP, int FORM, typename D>
+__global__ __launch_bounds__(kRsThreads) void batch_yuv16_kernel(const pv_batch_views_desc d, const BvLaunch g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char by_lds[];
+  const int t = blockIdx.y;
+  const int zi = blockIdx.z;                       // destination item of this launch
+  const BvItem item = bv_item(d, zi, t);
+  const pv_view_source* __restrict__ V = item.S;
+  RsYuvSrc s;
+  s.src = reinterpret_cast<uintptr_t>(V->src);
+  s.frame_off = (long)item.ts * V->frame_stride;
+  s.Hs = V->Hs, s.Ws = V->Ws;
+  s.sy = V->sy, s.sx = V->sx;
+  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
+  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
+  s.y_pitch = V->y_pitch, s.c_pitch = V->c_pitch;
+  rs_chroma_planes(CSTEP == 2, V->u_offset, V->v_offset, s);
+  rs_strip_yuv<CSTEP, FORM, D, unsigned short>(by_lds, g.R, g.pitch, g.pitch_c, g.c_base, s, rs_dst(d, 3), d.yuv2rgb, zi, t, true);
+}
+
 bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof(float)) == 0; }
 
 // One record of a launch: a source, positive sizes, windows inside the scaled frame, sy / sx the library's own division, and
@@ -93,7 +115,12 @@ int bv_check_record(const pv_batch_views_desc& d, const pv_view_source& v, bool 
   if (!v.src || v.N <= 0 || v.Hs <= 0 || v.Ws <= 0 || v.Hn <= 0 || v.Wn <= 0) return PV_ERR_INVALID;
   if (int e = rs_check_views(d.n_views, v.y_off, v.x_off, d.Ho, d.Wo, v.Hn, v.Wn)) return e;
   if (!same_bits(v.sy, (float)v.Hs / (float)v.Hn) || !same_bits(v.sx, (float)v.Ws / (float)v.Wn)) return PV_ERR_INVALID;
-  if (yuv) return rs_check_yuv_planes(v.Hs, v.Ws, d.c_step, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset);
+  if (yuv) {
+    const int sb = d.src_dtype == PV_U16 ? 2 : 1;
+    if (int e = rs_check_yuv_planes(v.Hs, v.Ws, d.c_step, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset, sb)) return e;
+    return sb == 2 ? rs_check_yuv16_even(reinterpret_cast<uintptr_t>(v.src), v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset)
+                   : PV_OK;
+  }
   if (d.src_dtype == PV_F32 && reinterpret_cast<uintptr_t>(v.src) % 4) return PV_ERR_INVALID;
   return PV_OK;
 }
@@ -105,10 +132,12 @@ int bv_run(const pv_batch_views_desc& d, pv_stream_t stream) {
   if (d.C > 4 || d.n_views < 1 || d.n_views > 3) return PV_ERR_INVALID;
   const bool yuv = d.src_layout == PV_SRC_YUV420;
   if (!yuv && d.src_layout != PV_SRC_NCTHW && d.src_layout != PV_SRC_NTHWC) return PV_ERR_INVALID;
+  if (!yuv && d.src_dtype == PV_U16) return PV_ERR_UNSUPPORTED;   // 16-bit samples are a YUV 4:2:0 source only
   if (d.src_layout == PV_SRC_NTHWC && (d.src_dtype != PV_U8 || d.C != 3)) return PV_ERR_INVALID;
   if (yuv && (!d.yuv2rgb || d.C != 3 || (d.c_step != 1 && d.c_step != 2))) return PV_ERR_INVALID;
   // the dtype / layout matrix
-  if (yuv ? d.src_dtype != PV_U8 : (d.src_dtype != PV_U8 && d.src_dtype != PV_F32)) return PV_ERR_UNSUPPORTED;
+  if (yuv ? (d.src_dtype != PV_U8 && d.src_dtype != PV_U16) : (d.src_dtype != PV_U8 && d.src_dtype != PV_F32)) return PV_ERR_UNSUPPORTED;
+  const int sb = d.src_dtype == PV_U16 ? 2 : 1;     // bytes per YUV sample
   if (int e = rs_check_dst(d.dst, d.dst_layout, d.dst_dtype, d.c_p, d.ld, d.bs, d.T, d.Ho, d.Wo)) return e;
   // the items, the record behind each of them -- a launch is a window of a longer sequence and reads only the records its
   // items name (the kernel clamps `source` into range and the items are the validated ones), so the cost of a launch does
@@ -128,9 +157,7 @@ int bv_run(const pv_batch_views_desc& d, pv_stream_t stream) {
   const bool inter = d.src_layout == PV_SRC_NTHWC;
   long per_row;                                    // LDS bytes of the two source rows of one output row
   if (yuv) {
-    g.pitch = pv_round_up(span + 15, 16);
-    g.pitch_c = pv_round_up(span_c * d.c_step + 15, 16);
-    per_row = 2L * (g.pitch + (long)(d.c_step == 2 ? 1 : 2) * g.pitch_c);
+    per_row = rs_yuv_pitches(span, span_c, d.c_step, sb, g.pitch, g.pitch_c);
   } else {
     g.pitch = pv_round_up(span * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
     per_row = 2L * (inter ? 1 : d.C) * g.pitch;
@@ -138,7 +165,10 @@ int bv_run(const pv_batch_views_desc& d, pv_stream_t stream) {
   size_t lds;
   if (int e = rs_strip_rows(per_row, d.Ho, g.R, lds)) return e;
   g.c_base = 2 * g.R * g.pitch;
-  if (yuv) {
+  if (yuv && sb == 2) {
+    if (d.c_step == 2) RS_DISPATCH(batch_yuv16_kernel, 2);
+    else RS_DISPATCH(batch_yuv16_kernel, 1);
+  } else if (yuv) {
     if (d.c_step == 2) RS_DISPATCH(batch_yuv_kernel, 2);
     else RS_DISPATCH(batch_yuv_kernel, 1);
   } else if (inter) {

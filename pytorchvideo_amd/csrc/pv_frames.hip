@@ -15,40 +15,14 @@
 // What stays per launch -- R, the LDS pitch(es) -- is sized as pv_batch_views sizes it, from the host copies of the records
 // the items name.  The descriptor embeds a whole pv_batch_views_desc; its checks are repeated here (pv_batch.hip keeps its
 // own in its anonymous namespace) with the record's `src` read as a table slice.
+//
+// PV_U16 sources (16-bit YUV samples) are validated and sized here and launched from pv_frames16.hip, which holds their
+// kernels: this translation unit keeps exactly its 25.
 #include <cstring>
 
-#include "pv_rs.h"
+#include "pv_frames.h"
 
 namespace {
-
-struct FvLaunch {
-  int32_t R;          // output rows per workgroup
-  int32_t pitch;      // LDS bytes per staged (row, plane) -- YUV: per staged luma row; multiple of 16, >= 15 + widest span
-  int32_t pitch_c;    // YUV: LDS bytes per staged chroma (row, plane)
-  int32_t c_base;     // YUV: LDS offset of the chroma image: 2 R pitch
-};
-
-// The item of this workgroup, clamped into range before anything is addressed through it, and the base address of the
-// frame its table row selects: the entry is clamped into [0, N-1] of the item's source before the slice is indexed, so a
-// malformed table can never read outside the item's slice.
-struct FvItem {
-  const pv_view_source* __restrict__ S;
-  int view;
-  uintptr_t frame;
-};
-__device__ __forceinline__ FvItem fv_item(const pv_batch_views_desc& d, int zi, int t) {
-  const pv_view_item* __restrict__ it = d.items_dev + zi;
-  FvItem r;
-  r.S = d.sources_dev + min(max(it->source, 0), d.n_sources - 1);
-  r.view = min(max(it->view, 0), d.n_views - 1);
-  const int row = min(max(it->row, 0), d.n_rows - 1);
-  const int ts = min(max(d.t_index[(long)row * d.t_stride + t], 0), r.S->N - 1);
-  // `src` is a generic pointer loaded from memory: read through it the entry would be a per-lane flat load.  The table is
-  // global memory that nothing writes while the kernel runs, so it is read as constant memory: one scalar load.
-  typedef const uint64_t __attribute__((address_space(4))) * table_ptr;
-  r.frame = (uintptr_t) reinterpret_cast<table_ptr>(reinterpret_cast<uintptr_t>(r.S->src))[ts];
-  return r;
-}
 
 // S / INTER / FORM / D: as rs_strip_rgb.  One frame is a dense [C, Hs, Ws] (plane stride of ONE frame) or [Hs, Ws, 3].
 template <typename S, bool INTER, int FORM, typename D>
@@ -101,14 +75,18 @@ int fv_check_record(const pv_frame_views_desc& f, const pv_view_source& v, bool 
   if (at < base || (at - base) % 8) return PV_ERR_INVALID;
   const uint64_t k = (at - base) / 8;
   if (k + (uint64_t)v.N > (uint64_t)f.n_frame_ptrs) return PV_ERR_INVALID;
-  const bool f32 = !yuv && d.src_dtype == PV_F32;
+  const bool f32 = !yuv && d.src_dtype == PV_F32, u16 = yuv && d.src_dtype == PV_U16;
   for (int i = 0; i < v.N; ++i) {
     const uint64_t p = f.frame_ptrs[k + i];
-    if (!p || (f32 && p % 4)) return PV_ERR_INVALID;
+    if (!p || (f32 && p % 4) || (u16 && !rs_yuv16_even((uintptr_t)p))) return PV_ERR_INVALID;
   }
   if (int e = rs_check_views(d.n_views, v.y_off, v.x_off, d.Ho, d.Wo, v.Hn, v.Wn)) return e;
   if (!same_bits(v.sy, (float)v.Hs / (float)v.Hn) || !same_bits(v.sx, (float)v.Ws / (float)v.Wn)) return PV_ERR_INVALID;
-  if (yuv) return rs_check_yuv_planes(v.Hs, v.Ws, d.c_step, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset);
+  if (yuv) {
+    if (int e = rs_check_yuv_planes(v.Hs, v.Ws, d.c_step, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset, u16 ? 2 : 1))
+      return e;
+    if (u16) return rs_check_yuv16_even(0, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset);   // frames: above
+  }
   return PV_OK;
 }
 
@@ -122,10 +100,12 @@ int fv_run(const pv_frame_views_desc& f, pv_stream_t stream) {
   if (d.C > 4 || d.n_views < 1 || d.n_views > 3) return PV_ERR_INVALID;
   const bool yuv = d.src_layout == PV_SRC_YUV420;
   if (!yuv && d.src_layout != PV_SRC_NCTHW && d.src_layout != PV_SRC_NTHWC) return PV_ERR_INVALID;
+  if (!yuv && d.src_dtype == PV_U16) return PV_ERR_UNSUPPORTED;   // 16-bit samples are a YUV 4:2:0 source only
   if (d.src_layout == PV_SRC_NTHWC && (d.src_dtype != PV_U8 || d.C != 3)) return PV_ERR_INVALID;
   if (yuv && (!d.yuv2rgb || d.C != 3 || (d.c_step != 1 && d.c_step != 2))) return PV_ERR_INVALID;
   // the dtype / layout matrix
-  if (yuv ? d.src_dtype != PV_U8 : (d.src_dtype != PV_U8 && d.src_dtype != PV_F32)) return PV_ERR_UNSUPPORTED;
+  if (yuv ? (d.src_dtype != PV_U8 && d.src_dtype != PV_U16) : (d.src_dtype != PV_U8 && d.src_dtype != PV_F32)) return PV_ERR_UNSUPPORTED;
+  const int sb = d.src_dtype == PV_U16 ? 2 : 1;     // bytes per YUV sample
   if (int e = rs_check_dst(d.dst, d.dst_layout, d.dst_dtype, d.c_p, d.ld, d.bs, d.T, d.Ho, d.Wo)) return e;
   // the items and the record behind each of them, as pv_batch_views: only the records the launch's items name are read,
   // a video-major sequence names the record just checked, and the widest column span(s) size the staged rows
@@ -143,9 +123,7 @@ int fv_run(const pv_frame_views_desc& f, pv_stream_t stream) {
   const bool inter = d.src_layout == PV_SRC_NTHWC;
   long per_row;                                    // LDS bytes of the two source rows of one output row
   if (yuv) {
-    g.pitch = pv_round_up(span + 15, 16);
-    g.pitch_c = pv_round_up(span_c * d.c_step + 15, 16);
-    per_row = 2L * (g.pitch + (long)(d.c_step == 2 ? 1 : 2) * g.pitch_c);
+    per_row = rs_yuv_pitches(span, span_c, d.c_step, sb, g.pitch, g.pitch_c);
   } else {
     g.pitch = pv_round_up(span * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
     per_row = 2L * (inter ? 1 : d.C) * g.pitch;
@@ -153,7 +131,9 @@ int fv_run(const pv_frame_views_desc& f, pv_stream_t stream) {
   size_t lds;
   if (int e = rs_strip_rows(per_row, d.Ho, g.R, lds)) return e;
   g.c_base = 2 * g.R * g.pitch;
-  if (yuv) {
+  if (yuv && sb == 2) {
+    return pv_frame_yuv16_launch(&d, g.R, g.pitch, g.pitch_c, g.c_base, lds, stream);   // pv_frames16.hip
+  } else if (yuv) {
     if (d.c_step == 2) RS_DISPATCH(frame_yuv_kernel, 2);
     else RS_DISPATCH(frame_yuv_kernel, 1);
   } else if (inter) {

@@ -1,0 +1,38 @@
+// The 16-bit YUV 4:2:0 kernels of pv_frame_views (PV_U16 sources: P010 / yuv420p10le surfaces from a decoder's pool), in a
+// translation unit of their own; pv_frames.hip validates the descriptor, sizes the launch and calls pv_frame_yuv16_launch.
+#include "pv_frames.h"
+
+namespace {
+
+// CSTEP / FORM / D: as rs_strip_yuv.  frame_yuv_kernel (pv_frames.hip) on two-byte samples: one frame is one surface, the
+// record's byte offsets and pitches from the frame's (even) base.
+template <int CSTEP, int FORM, typename D>
+__global__ __launch_bounds__(kRsThreads) void frame_yuv16_kernel(const pv_batch_views_desc d, const FvLaunch g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char fy_lds[];
+  const int t = blockIdx.y;
+  const int zi = blockIdx.z;                       // destination item of this launch
+  const FvItem item = fv_item(d, zi, t);
+  const pv_view_source* __restrict__ V = item.S;
+  RsYuvSrc s;
+  s.src = item.frame;
+  s.frame_off = 0;
+  s.Hs = V->Hs, s.Ws = V->Ws;
+  s.sy = V->sy, s.sx = V->sx;
+  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
+  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
+  s.y_pitch = V->y_pitch, s.c_pitch = V->c_pitch;
+  rs_chroma_planes(CSTEP == 2, V->u_offset, V->v_offset, s);
+  rs_strip_yuv<CSTEP, FORM, D, unsigned short>(fy_lds, g.R, g.pitch, g.pitch_c, g.c_base, s, rs_dst(d, 3), d.yuv2rgb, zi, t, true);
+}
+
+}  // namespace
+
+int pv_frame_yuv16_launch(const pv_batch_views_desc* dp, int32_t R, int32_t pitch, int32_t pitch_c, int32_t c_base, size_t lds,
+                          pv_stream_t stream) {
+  const pv_batch_views_desc& d = *dp;
+  const FvLaunch g = {R, pitch, pitch_c, c_base};
+  if (d.c_step == 2) RS_DISPATCH(frame_yuv16_kernel, 2);
+  else RS_DISPATCH(frame_yuv16_kernel, 1);
+  PV_LAUNCH_CHECK();
+  return PV_OK;
+}

@@ -2,7 +2,8 @@
 // one source per destination item).  What the entry points compute with is here, once: the pinned source coordinate, the
 // destination forms with their stores, the taps and blends, the two staged-strip bodies that the four kernels wrap
 // (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather), the launch arithmetic (widest span, rows per strip, destination-form
-// dispatch) and the host-side checks of views, item range, destination and YUV planes.  The three files keep what differs:
+// dispatch) and the host-side checks of views, item range, destination and YUV planes.  rs_strip_yuv takes the sample type:
+// bytes, or the 16-bit codes of P010 / yuv420p10le (pv_yuv16_views, PV_U16 sources).  The three files keep what differs:
 // where a workgroup's geometry comes from, and the validation of their descriptors.
 // Everything is inline in an anonymous namespace: each translation unit keeps its own kernels.
 #pragma once
@@ -111,11 +112,20 @@ template <> __device__ __forceinline__ float rs_tap<float>(const unsigned char* 
 
 __device__ __forceinline__ f32x2 yuv_splat(float v) { return f32x2{v, v}; }
 
+// One staged YUV sample at LDS byte offset `off`, read whole and unsigned: a byte, or a 16-bit little-endian code (the
+// offset is then even: the entry points refuse odd source addresses, and the LDS image keeps a row's `addr & 15`).
+template <typename SMP> __device__ __forceinline__ float yuv_sample(const unsigned char* lds, int off) {
+  if constexpr (sizeof(SMP) == 1) return (float)lds[off];
+  else return (float)*reinterpret_cast<const unsigned short*>(lds + off);
+}
+
 // Two taps of the virtual RGB frame -- the same column of the two source rows -- as packed fp32 pairs (v_pk_fma_f32 does
 // both for the price of one): per channel three fused multiply-adds in the header's order, then the clamp.
+template <typename SMP = unsigned char>
 __device__ __forceinline__ void yuv_tap2(const float (&m)[12], const unsigned char* lds, int oy0, int ou0, int ov0, int oy1, int ou1,
                                          int ov1, f32x2 (&rgb)[3]) {
-  const f32x2 Y = {(float)lds[oy0], (float)lds[oy1]}, U = {(float)lds[ou0], (float)lds[ou1]}, V = {(float)lds[ov0], (float)lds[ov1]};
+  const f32x2 Y = {yuv_sample<SMP>(lds, oy0), yuv_sample<SMP>(lds, oy1)}, U = {yuv_sample<SMP>(lds, ou0), yuv_sample<SMP>(lds, ou1)},
+              V = {yuv_sample<SMP>(lds, ov0), yuv_sample<SMP>(lds, ov1)};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const f32x2 v = __builtin_elementwise_fma(yuv_splat(m[c * 4 + 2]), V, __builtin_elementwise_fma(yuv_splat(m[c * 4 + 1]), U,
@@ -313,7 +323,7 @@ struct RsYuvSrc {
   int yoff, xoff;
   int y_pitch, c_pitch;     // bytes per luma / chroma row of the source
   long c_off_a, c_off_b;    // byte offset inside a frame of staged chroma plane 0 / 1 (c_step 2: only plane 0, min(u, v))
-  int u_byte, v_byte;       // c_step 2: which byte of an interleaved pair is U / V; c_step 1: 0
+  int u_byte, v_byte;       // c_step 2: the byte offset of U / V inside an interleaved pair (0 or one sample); c_step 1: 0
 };
 // The staged chroma planes behind a frame's u_offset / v_offset; `inter`: c_step 2.
 __host__ __device__ __forceinline__ void rs_chroma_planes(bool inter, int64_t u_off, int64_t v_off, RsYuvSrc& s) {
@@ -324,13 +334,19 @@ __host__ __device__ __forceinline__ void rs_chroma_planes(bool inter, int64_t u_
   s.v_byte = inter ? (int)(v_off - c_min) : 0;
 }
 
-// CSTEP: bytes between x-adjacent samples of one chroma plane (2: U and V interleaved in ONE staged plane; 1: two planes).
+// CSTEP: samples between x-adjacent samples of one chroma plane (2: U and V interleaved in ONE staged plane; 1: two planes).
 // pitch_y / pitch_c: LDS bytes per staged luma row / chroma (row, plane); c_base: LDS offset of the chroma image.
-template <int CSTEP, int FORM, typename D>
+// SMP: the sample, unsigned char or unsigned short (16-bit little-endian codes: P010 / yuv420p10le and their 12- and 16-bit
+// kin).  Spans, source addresses and LDS offsets count SB = sizeof(SMP) bytes per luma column and CSTEP * SB per chroma
+// column; pitches and plane offsets are bytes in either case.  Two-byte samples need even source addresses (checked on the
+// host: rs_check_yuv16_even), which makes every 16-bit LDS read naturally aligned.
+template <int CSTEP, int FORM, typename D, typename SMP = unsigned char>
 __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitch_y, int pitch_c, int c_base, const RsYuvSrc& s,
                                              const RsDst& d, const float* yuv2rgb, int zi, int t, bool check_span) {
   constexpr int G = RsGroup<FORM, D>::G;
   constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
+  constexpr int SB = (int)sizeof(SMP);             // bytes from one luma column to the next
+  constexpr int CB = CSTEP * SB;                   // bytes from one chroma column to the next
   const int tid = threadIdx.x;
   const int row0 = blockIdx.x * R;
   const int nrows = min(R, d.Ho - row0);
@@ -345,14 +361,14 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
   const int nslots = dense ? ylast - ybase + 1 : 2 * nrows;
   const int cxs0 = xs0 >> 1, cybase = ybase >> 1;
   const int ncslots = dense ? (ylast >> 1) - cybase + 1 : 2 * nrows;   // dense: <= R + 1 <= 2R
-  const int span_y = xs1 - xs0 + 1;
-  const int span_c = ((xs1 >> 1) - cxs0 + 1) * CSTEP;
+  const int span_y = (xs1 - xs0 + 1) * SB;
+  const int span_c = ((xs1 >> 1) - cxs0 + 1) * CB;
   if (check_span && (span_y + 15 > pitch_y || span_c + 15 > pitch_c)) return;
 
   const uintptr_t frame = s.src + s.frame_off;
-  auto y_addr = [&](int y) -> uintptr_t { return frame + (long)y * s.y_pitch + xs0; };
+  auto y_addr = [&](int y) -> uintptr_t { return frame + (long)y * s.y_pitch + xs0 * SB; };
   auto c_addr = [&](int cy, int pl) -> uintptr_t {
-    return frame + (pl == 0 ? s.c_off_a : s.c_off_b) + (long)cy * s.c_pitch + (long)cxs0 * CSTEP;
+    return frame + (pl == 0 ? s.c_off_a : s.c_off_b) + (long)cy * s.c_pitch + (long)cxs0 * CB;
   };
 
   // ---- stage -------------------------------------------------------------------------------------------------
@@ -426,11 +442,11 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
       float lx1;
       rs_coord(s.sx, s.xoff + x, s.Ws, i0x, i1x, lx1);
       const float lx0 = 1.f - lx1;
-      const int o0 = i0x - xs0, o1 = i1x - xs0;
-      const int c0 = ((i0x >> 1) - cxs0) * CSTEP, c1 = ((i1x >> 1) - cxs0) * CSTEP;
+      const int o0 = (i0x - xs0) * SB, o1 = (i1x - xs0) * SB;
+      const int c0 = ((i0x >> 1) - cxs0) * CB, c1 = ((i1x >> 1) - cxs0) * CB;
       f32x2 p0[3], p1[3];                          // {row i0y, row i1y} of column i0x / i1x, per channel
-      yuv_tap2(m, lds, yo0 + o0, uo0 + c0, vo0 + c0, yo1 + o0, uo1 + c0, vo1 + c0, p0);
-      yuv_tap2(m, lds, yo0 + o1, uo0 + c1, vo0 + c1, yo1 + o1, uo1 + c1, vo1 + c1, p1);
+      yuv_tap2<SMP>(m, lds, yo0 + o0, uo0 + c0, vo0 + c0, yo1 + o0, uo1 + c0, vo1 + c0, p0);
+      yuv_tap2<SMP>(m, lds, yo0 + o1, uo0 + c1, vo0 + c1, yo1 + o1, uo1 + c1, vo1 + c1, p1);
 #pragma unroll
       for (int c = 0; c < 3; ++c) out[c][j] = yuv_blend(ly0, ly1, lx0, lx1, p0[c], p1[c], sc[c], sh[c]);
       out[3][j] = 0.f;
@@ -444,8 +460,8 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
 }
 
 // ---- the launch arithmetic shared by the entry points ---------------------------------------------------------------
-// Folds the widest source column span of a record's views into `span`, and the chroma span behind it into `span_c`: they
-// size the staged rows.
+// Folds the widest source column span of a record's views into `span`, and the chroma span behind it into `span_c`, both in
+// columns: times the bytes of a column (rs_yuv_pitches for YUV) they size the staged rows.
 inline void rs_widest_span(float sx, const int32_t* x_off, int n_views, int Wo, int Ws, int& span, int& span_c) {
   for (int v = 0; v < n_views; ++v) {
     int a, b, u;
@@ -456,6 +472,14 @@ inline void rs_widest_span(float sx, const int32_t* x_off, int n_views, int Wo, 
     const int c = (b >> 1) - (a >> 1) + 1;
     span_c = c > span_c ? c : span_c;
   }
+}
+
+// The LDS pitches of a staged luma row and a staged chroma (row, plane) for the widest spans (columns) of a launch whose
+// samples have `sb` bytes, and the LDS bytes of the two source rows of one output row with their chroma.
+inline long rs_yuv_pitches(int span, int span_c, int c_step, int sb, int32_t& pitch_y, int32_t& pitch_c) {
+  pitch_y = pv_round_up(span * sb + 15, 16);
+  pitch_c = pv_round_up(span_c * c_step * sb + 15, 16);
+  return 2L * (pitch_y + (long)(c_step == 2 ? 1 : 2) * pitch_c);
 }
 
 // R output rows per workgroup and the LDS bytes they stage; per_row: LDS bytes of the two source rows of one output row.
@@ -526,22 +550,32 @@ inline int rs_check_dst(const void* dstp, int dst_layout, int dst_dtype, int c_p
   return PV_OK;
 }
 
-// Bytes [off, off + (rows - 1) * pitch + (cols - 1) * step] of a plane lie inside [0, frame_stride).
-inline bool plane_inside(int64_t off, int64_t rows, int64_t pitch, int64_t cols, int64_t step, int64_t frame_stride) {
-  return off >= 0 && off + (rows - 1) * pitch + (cols - 1) * step < frame_stride;
+// Bytes [off, off + (rows - 1) * pitch + (cols - 1) * step + sb) of a plane of sb-byte samples lie inside [0, frame_stride).
+inline bool plane_inside(int64_t off, int64_t rows, int64_t pitch, int64_t cols, int64_t step, int64_t frame_stride, int64_t sb = 1) {
+  return off >= 0 && off + (rows - 1) * pitch + (cols - 1) * step + (sb - 1) < frame_stride;
 }
 
-// The planes of one YUV 4:2:0 frame of Hs x Ws (both positive): even sizes, the chroma form, pitches that hold a row, and
-// luma and chroma planes inside [0, frame_stride).
+// The planes of one YUV 4:2:0 frame of Hs x Ws (both positive) of sb-byte samples: even sizes, the chroma form (c_step counts
+// samples), pitches that hold a row, and luma and chroma planes inside [0, frame_stride).  Pitches, offsets and the frame
+// stride are bytes.
 inline int rs_check_yuv_planes(int Hs, int Ws, int c_step, int y_pitch, int c_pitch, int64_t frame_stride, int64_t u_offset,
-                               int64_t v_offset) {
+                               int64_t v_offset, int sb = 1) {
   if ((Hs | Ws) & 1) return PV_ERR_INVALID;
   if (c_step != 1 && c_step != 2) return PV_ERR_INVALID;
-  if (y_pitch < Ws || c_pitch < (Ws / 2) * c_step || frame_stride <= 0) return PV_ERR_INVALID;
-  if (c_step == 2 && v_offset - u_offset != 1 && u_offset - v_offset != 1) return PV_ERR_INVALID;
-  if (!plane_inside(0, Hs, y_pitch, Ws, 1, frame_stride) || !plane_inside(u_offset, Hs / 2, c_pitch, Ws / 2, c_step, frame_stride) ||
-      !plane_inside(v_offset, Hs / 2, c_pitch, Ws / 2, c_step, frame_stride))
+  if (y_pitch < (int64_t)Ws * sb || c_pitch < (int64_t)(Ws / 2) * c_step * sb || frame_stride <= 0) return PV_ERR_INVALID;
+  if (c_step == 2 && v_offset - u_offset != sb && u_offset - v_offset != sb) return PV_ERR_INVALID;
+  if (!plane_inside(0, Hs, y_pitch, Ws, sb, frame_stride, sb) ||
+      !plane_inside(u_offset, Hs / 2, c_pitch, Ws / 2, (int64_t)c_step * sb, frame_stride, sb) ||
+      !plane_inside(v_offset, Hs / 2, c_pitch, Ws / 2, (int64_t)c_step * sb, frame_stride, sb))
     return PV_ERR_INVALID;
+  return PV_OK;
+}
+
+// Two-byte samples: every sample address is even, so that the 16-bit LDS reads of the gather are naturally aligned (the LDS
+// image of a staged row keeps the row's `addr & 15`).  `base` is the source or, for a frame list, a frame's address.
+inline bool rs_yuv16_even(uintptr_t base) { return (base & 1) == 0; }
+inline int rs_check_yuv16_even(uintptr_t base, int y_pitch, int c_pitch, int64_t frame_stride, int64_t u_offset, int64_t v_offset) {
+  if (!rs_yuv16_even(base) || ((y_pitch | c_pitch) & 1) || ((frame_stride | u_offset | v_offset) & 1)) return PV_ERR_INVALID;
   return PV_OK;
 }
 

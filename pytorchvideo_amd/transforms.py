@@ -209,31 +209,56 @@ class UniformCropVideo(torch.nn.Module):
 
 # --------------------------------------------------------------------------- YUV 4:2:0 sources
 YUV_LAYOUTS = ("NV12", "NV21", "I420", "YV12")
+# 16-bit little-endian samples.  P0xx: the NV12 arrangement with the value in the HIGH bits (what a hardware decoder writes for
+# 10- / 12- / 16-bit streams); I0xx: the I420 arrangement with the value in the LOW bits (yuv420p10le and friends).
+YUV16_LAYOUTS = ("P010", "P012", "P016", "I010", "I012", "I016")
+_YUV_ANY = YUV_LAYOUTS + YUV16_LAYOUTS
+_YUV_INTERLEAVED = ("NV12", "NV21", "P010", "P012", "P016")
+_YUV16_DEPTH = {"P010": (10, True), "P012": (12, True), "P016": (16, True), "I010": (10, False), "I012": (12, False),
+                "I016": (16, False)}                       # layout -> (bit depth, MSB-aligned)
 _YUV_KR_KB = {"bt709": (0.2126, 0.0722), "bt601": (0.299, 0.114)}
+_YUV_KR_KB_DEEP = {"bt2020": (0.2627, 0.0593)}             # Rec. 2020 defines 10- and 12-bit quantisation only: no 8-bit form
 
 
-def yuv_matrix(standard: str = "bt709", full_range: bool = False) -> torch.Tensor:
+def yuv_matrix(standard: str = "bt709", full_range: bool = False, bit_depth: int = 8, msb_aligned: bool = False) -> torch.Tensor:
     """The 3 x 4 fp64 matrix M with (R, G, B) = M . (Y, U, V, 1) for 8-bit Y'CbCr, RGB in [0, 255]: rows R, G, B, columns
     Y, U, V and a constant.  Derived from the standard's luma coefficients (Kr, Kb) -- Y' = Kr R' + Kg G' + Kb B',
     Pb = (B' - Y') / (2 (1 - Kb)), Pr = (R' - Y') / (2 (1 - Kr)) -- and the quantisation: limited range puts Y' in 16..235
-    and Pb, Pr in 16..240 around 128, full range in 0..255 around 128."""
-    if standard not in _YUV_KR_KB:
-        raise ValueError("standard is one of %s, got %r" % (sorted(_YUV_KR_KB), standard))
-    kr, kb = _YUV_KR_KB[standard]
+    and Pb, Pr in 16..240 around 128, full range in 0..255 around 128.
+
+    `bit_depth` d in 8..16 (RGB stays in [0, 255]): limited range puts Y' in 16 * 2^(d-8) .. 235 * 2^(d-8) and gives Pb, Pr a
+    span of 224 * 2^(d-8); full range is 0 .. 2^d - 1; the chroma centre is 2^(d-1) for both.  `msb_aligned`: the value sits in
+    the high bits of a 16-bit code (P010 / P012 / P016), so the Y, U, V columns are scaled by 2^-(16-d) -- exactly.  The ingest
+    applies no shift and no mask of its own: depth and alignment live here.  The defaults give the 8-bit matrix bit for bit.
+    "bt2020" (Kr 0.2627, Kb 0.0593; what 10-bit streams usually signal) takes a `bit_depth` of 10 or more: the standard
+    defines no 8-bit quantisation."""
+    deep = standard in _YUV_KR_KB_DEEP
+    if standard not in _YUV_KR_KB and not (deep and isinstance(bit_depth, int) and bit_depth >= 10):
+        raise ValueError("standard is one of %s, got %r" % (sorted(_YUV_KR_KB), standard)
+                         + (" (bt2020 takes bit_depth >= 10, got %r)" % (bit_depth,) if deep else ""))
+    if not isinstance(bit_depth, int) or not 8 <= bit_depth <= 16:
+        raise ValueError("bit_depth is an integer in 8..16, got %r" % (bit_depth,))
+    kr, kb = _YUV_KR_KB_DEEP[standard] if deep else _YUV_KR_KB[standard]
     kg = 1.0 - kr - kb
-    y_lo, y_span, c_span = (0.0, 255.0, 255.0) if full_range else (16.0, 219.0, 224.0)
+    k = float(1 << (bit_depth - 8))                        # codes per 8-bit code: a power of two, so the products with it are exact
+    top = float((1 << bit_depth) - 1)
+    y_lo, y_span, c_span = (0.0, top, top) if full_range else (16.0 * k, 219.0 * k, 224.0 * k)
     ys, cs = 255.0 / y_span, 255.0 / c_span
     m = torch.tensor([[ys, 0.0, 2.0 * (1.0 - kr) * cs],
                       [ys, -2.0 * kb * (1.0 - kb) / kg * cs, -2.0 * kr * (1.0 - kr) / kg * cs],
                       [ys, 2.0 * (1.0 - kb) * cs, 0.0]], dtype=torch.float64)
-    const = -(m[:, 0] * y_lo + (m[:, 1] + m[:, 2]) * 128.0)
+    const = -(m[:, 0] * y_lo + (m[:, 1] + m[:, 2]) * (128.0 * k))
+    if msb_aligned:
+        m = m * (1.0 / float(1 << (16 - bit_depth)))
     return torch.cat([m, const[:, None]], dim=1)
 
 
-def _yuv_matrix_of(yuv) -> torch.Tensor:
-    """`yuv` as every YUV entry point takes it: (standard, full_range), or an explicit 3 x 4 matrix."""
+def _yuv_matrix_of(yuv, layout=None) -> torch.Tensor:
+    """`yuv` as every YUV entry point takes it: (standard, full_range) -- composed with the depth and the bit alignment of a
+    16-bit `layout` --, or an explicit 3 x 4 matrix, taken as it is."""
     if isinstance(yuv, (tuple, list)) and len(yuv) == 2 and isinstance(yuv[0], str):
-        return yuv_matrix(yuv[0], bool(yuv[1]))
+        depth, msb = _YUV16_DEPTH.get(layout, (8, False))
+        return yuv_matrix(yuv[0], bool(yuv[1]), depth, msb)
     m = torch.as_tensor(yuv, dtype=torch.float64).cpu()
     if tuple(m.shape) != (3, 4):
         raise ValueError("yuv is (standard, full_range) or a 3 x 4 matrix, got shape %s" % (tuple(m.shape),))
@@ -248,12 +273,18 @@ def yuv_geometry(frames: torch.Tensor, layout: str, coded_height=None, height=No
     and `coded_height`, when given, is checked against the shape.  The only stride requirement is stride(-1) == 1: the
     row pitch P = stride(-2) may exceed W and the frame stride the frame, so a pitched decoder surface is read in place.
     NV12 / NV21: chroma row j is tensor row Hc + j, U and V (V and U) interleaved.  I420 / YV12: two planes of Hc/2 rows
-    with pitch P/2 behind the luma, U (V) first -- for P == W exactly the contiguous yuv420p frame."""
-    if layout not in YUV_LAYOUTS:
-        raise ValueError("a YUV layout is one of %s, got %r" % (YUV_LAYOUTS, layout))
-    if frames.dim() not in (3, 4) or frames.dtype != torch.uint8:
-        raise RuntimeError("%s frames are uint8 [N, Hc*3/2, W] or [B, T, Hc*3/2, W], got %s %s"
-                           % (layout, frames.dtype, tuple(frames.shape)))
+    with pitch P/2 behind the luma, U (V) first -- for P == W exactly the contiguous yuv420p frame.
+
+    The layouts of `YUV16_LAYOUTS` hold 16-bit samples: P010 / P012 / P016 are NV12's arrangement, I010 / I012 / I016 are
+    I420's (yuv420p10le).  `frames` is then torch.uint16 or torch.int16 (the same bits; decoder bindings differ) with the
+    same shape and stride rules IN ELEMENTS, and the returned frame_stride, pitches and offsets are BYTES, as the
+    descriptors take them (c_step stays 2 / 1: samples)."""
+    if layout not in _YUV_ANY:
+        raise ValueError("a YUV layout is one of %s, got %r" % (YUV_LAYOUTS, layout) + " (16-bit samples: %s)" % (YUV16_LAYOUTS,))
+    wide = layout in YUV16_LAYOUTS
+    if frames.dim() not in (3, 4) or (frames.dtype not in (torch.uint16, torch.int16) if wide else frames.dtype != torch.uint8):
+        raise RuntimeError("%s frames are %s [N, Hc*3/2, W] or [B, T, Hc*3/2, W], got %s %s"
+                           % (layout, "uint16 or int16" if wide else "uint8", frames.dtype, tuple(frames.shape)))
     rows, w = frames.shape[-2:]
     hc = rows * 2 // 3
     if rows == 0 or hc * 3 != rows * 2 or hc % 2 or w % 2 or w == 0:
@@ -273,34 +304,40 @@ def yuv_geometry(frames: torch.Tensor, layout: str, coded_height=None, height=No
     if frame_stride < (rows - 1) * pitch + w:
         raise RuntimeError("frames overlap: frame stride %d for %d rows of pitch %d" % (frame_stride, rows, pitch))
     first = hc * pitch
-    if layout in ("NV12", "NV21"):
+    if layout in _YUV_INTERLEAVED:
         c_step, c_pitch = 2, pitch
-        u, v = (first, first + 1) if layout == "NV12" else (first + 1, first)
+        u, v = (first + 1, first) if layout == "NV21" else (first, first + 1)
     else:
         if pitch % 2:
             raise RuntimeError("%s chroma rows have half the luma pitch: the pitch %d must be even" % (layout, pitch))
         c_step, c_pitch = 1, pitch // 2
         second = first + (hc // 2) * c_pitch
-        u, v = (first, second) if layout == "I420" else (second, first)
-    return dict(N=n, Hs=hs, Ws=w, Hc=hc, frame_stride=frame_stride, y_pitch=pitch, c_pitch=c_pitch, c_step=c_step,
-                u_offset=u, v_offset=v)
+        u, v = (second, first) if layout == "YV12" else (first, second)
+    sb = 2 if wide else 1                                   # elements -> bytes
+    return dict(N=n, Hs=hs, Ws=w, Hc=hc, frame_stride=frame_stride * sb, y_pitch=pitch * sb, c_pitch=c_pitch * sb, c_step=c_step,
+                u_offset=u * sb, v_offset=v * sb)
 
 
 def yuv420_to_rgb(frames: torch.Tensor, layout: str, matrix, coded_height=None, height=None) -> torch.Tensor:
     """The virtual RGB frame `pv_yuv_views` takes its taps from (include/pv_mi355x.h), on the host: fp32 [..., 3, Hs, Ws] with
     rgb(y, x) = clamp(M . (Y[y][x], U[y >> 1][x >> 1], V[y >> 1][x >> 1], 1), 0, 255), NOT rounded to an integer.  Chroma is
     replicated over its 2 x 2 luma block.  `frames`, `layout`, `coded_height` and `height` as in `yuv_geometry`; `matrix`
-    is a 3 x 4 matrix (`yuv_matrix`).  The conversion runs in fp64 and is rounded once to fp32."""
+    is a 3 x 4 matrix (`yuv_matrix`).  The conversion runs in fp64 and is rounded once to fp32.  The 16-bit codes of a
+    `YUV16_LAYOUTS` layout are read UNSIGNED, whichever of uint16 / int16 the tensor is (`pv_yuv16_views`)."""
     g = yuv_geometry(frames, layout, coded_height, height)
     m = torch.as_tensor(matrix, dtype=torch.float64).cpu()
     if tuple(m.shape) != (3, 4):
         raise ValueError("matrix is 3 x 4, got %s" % (tuple(m.shape),))
     frames = frames.cpu() if frames.is_cuda else frames
+    sb = 2 if layout in YUV16_LAYOUTS else 1                # the geometry is bytes, as_strided counts elements
+    if frames.dtype == torch.uint16:
+        frames = frames.view(torch.int16)                   # the same bits, in the type every CPU operator has
     lead, lead_strides = tuple(frames.shape[:-2]), tuple(frames.stride()[:-2])
     off = frames.storage_offset()
 
     def plane(rows, cols, pitch, step, start):
-        return torch.as_strided(frames, lead + (rows, cols), lead_strides + (pitch, step), off + start).to(torch.float64)
+        p = torch.as_strided(frames, lead + (rows, cols), lead_strides + (pitch // sb, step), off + start // sb).to(torch.float64)
+        return torch.where(p < 0, p + 65536.0, p) if sb == 2 else p
 
     y = plane(g["Hs"], g["Ws"], g["y_pitch"], 1, 0)
     u = plane(g["Hs"] // 2, g["Ws"] // 2, g["c_pitch"], g["c_step"], g["u_offset"])
@@ -429,7 +466,7 @@ def _device_scale_crop_yuv(frames, short_side, crop_size, views, mean, std, div2
     geom = yuv_geometry(frames, src_layout, coded_height, height)
     b, t_src = (1, frames.shape[0]) if frames.dim() == 3 else tuple(frames.shape[:2])
     table = _clip_rows(b, t_src, num_frames if num_frames is not None else t_src).to(device)
-    matrix = _yuv_matrix_of(yuv).float().reshape(12).to(device)
+    matrix = _yuv_matrix_of(yuv, src_layout).float().reshape(12).to(device)
     d = _yuv_desc(frames, geom, table, matrix, short_side, crop_size, views)
     scale, shift = _affine(mean, std, div255, 3, device)
     if scale is not None:
@@ -438,7 +475,8 @@ def _device_scale_crop_yuv(frames, short_side, crop_size, views, mean, std, div2
     d.dst, d.dst_layout = out.data_ptr(), L.DST_NCTHW
     d.dst_dtype = L.PV_BF16 if dtype == torch.bfloat16 else L.PV_F32
     with torch.cuda.device(device):
-        L.check(L.lib().pv_yuv_views(C.byref(d), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "yuv_views")
+        entry = L.lib().pv_yuv16_views if src_layout in YUV16_LAYOUTS else L.lib().pv_yuv_views
+        L.check(entry(C.byref(d), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "yuv_views")
     return out
 
 
@@ -449,8 +487,8 @@ class FrameList:
     (`pv_frame_views`), nothing is stacked first.
 
     The frames share one device, dtype, shape and set of strides.  Per frame, by the packer's source layout: "NTHWC" a
-    contiguous uint8 [H, W, 3]; "NCTHW" a contiguous uint8 or fp32 [C, H, W]; the YUV layouts a uint8 2-d [Hc*3/2, W] with
-    stride(1) == 1 and any row pitch P >= W (`yuv_geometry` of a one-frame view: the surface is the Hc*3/2 * P bytes from
+    contiguous uint8 [H, W, 3]; "NCTHW" a contiguous uint8 or fp32 [C, H, W]; the YUV layouts a uint8 (`YUV16_LAYOUTS`:
+    uint16 or int16) 2-d [Hc*3/2, W] with stride(1) == 1 and any row pitch P >= W (`yuv_geometry` of a one-frame view: the surface is the Hc*3/2 * P bytes from
     its first sample -- the half-pitch chroma rows of I420 / YV12 lie partly behind column W).  `src_layout`, when given,
     checks that form at construction; `video_batch` checks it in any case.  A frame may be a view at any offset inside a
     larger buffer and appear more than once, and the frames may have been allocated in any order.  The list keeps its
@@ -481,13 +519,13 @@ class FrameList:
         """(C, Hs, Ws, geom) of one frame in `src_layout`, `geom` being `yuv_geometry` of a one-frame view for the YUV
         layouts (frame_stride: the extent of one frame) and None otherwise.  RuntimeError for a frame of another form."""
         f = self.frames[0]
-        if src_layout in YUV_LAYOUTS:
+        if src_layout in _YUV_ANY:
             if f.dim() != 2:
                 raise RuntimeError("a %s frame is uint8 [Hc*3/2, W], got %s %s" % (src_layout, f.dtype, tuple(f.shape)))
             geom = yuv_geometry(f[None], src_layout, coded_height, height)
             return 3, geom["Hs"], geom["Ws"], geom
         if src_layout not in ("NCTHW", "NTHWC"):
-            raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,))
+            raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
         if f.dim() != 3 or not f.is_contiguous() or f.dtype not in (torch.uint8, torch.float32):
             raise RuntimeError("a frame of a FrameList is a contiguous uint8 or fp32 [H,W,3] / [C,H,W] tensor, got %s %s with "
                                "strides %s" % (f.dtype, tuple(f.shape), f.stride()))
@@ -578,7 +616,7 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
     if any(isinstance(v, FrameList) != as_frames for v in videos):
         raise ValueError("the videos of one call are all tensors or all FrameLists, not a mix of tensors and FrameLists "
                          "(wrap a tensor: FrameList(video.unbind(0)))")
-    is_yuv = src_layout in YUV_LAYOUTS
+    is_yuv = src_layout in _YUV_ANY
     no_crop = isinstance(crop_size, (tuple, list))
     ho, wo = (int(crop_size[0]), int(crop_size[1])) if no_crop else (crop_size, crop_size)
 
@@ -644,7 +682,7 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
     clips = [int(torch.as_tensor(t).shape[0]) for t in tables]
     items_t, video_of, clip_of, row0 = batch_items(clips, len(views))
     items = (L.ViewItem * items_t.shape[0]).from_buffer_copy(items_t.numpy().tobytes())
-    src_dtype = L.PV_U8 if (is_yuv or dtype == torch.uint8) else L.PV_F32
+    src_dtype = L.PV_U16 if src_layout in YUV16_LAYOUTS else (L.PV_U8 if (is_yuv or dtype == torch.uint8) else L.PV_F32)
     if not as_frames:
         return VideoBatch(videos, sources, items, items_t, cat, video_of, clip_of, clips, row0, len(views), src_dtype, upload)
     # the pointer table of the call: the frame addresses of video j from first[j] on; the records point into the DEVICE copy
@@ -669,15 +707,17 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
 
     With `src_layout` "NV12", "NV21", "I420" or "YV12" the clip is decoder-native YUV 4:2:0, uint8 [B, T, Hc*3/2, W] (or
     [T, Hc*3/2, W]: one clip) with the strides it has (`yuv_geometry`: `coded_height`, `height`), converted tap by tap inside
-    the same launch (`pv_yuv_views`) by `yuv`: (standard, full_range) for `yuv_matrix`, or a 3 x 4 matrix."""
+    the same launch (`pv_yuv_views`) by `yuv`: (standard, full_range) for `yuv_matrix`, or a 3 x 4 matrix.  With a layout of
+    `YUV16_LAYOUTS` ("P010", "I010", ...) the clip is uint16 or int16 and read by `pv_yuv16_views`; a (standard, full_range)
+    pair is composed with the layout's depth and bit alignment: `src_layout="P010", yuv=("bt2020", False)`."""
     import ctypes as C
     from . import _lib as L
-    if src_layout not in ("NCTHW", "NTHWC") + YUV_LAYOUTS:
-        raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,))
+    if src_layout not in ("NCTHW", "NTHWC") + _YUV_ANY:
+        raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
     if dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("dtype is torch.bfloat16 or torch.float32")
     views = _views(spatial_idx)
-    if src_layout in YUV_LAYOUTS:
+    if src_layout in _YUV_ANY:
         return _device_scale_crop_yuv(clip, short_side, crop_size, views, mean, std, div255, num_frames, dtype, src_layout,
                                       yuv, coded_height, height)
     _source_geometry(clip, src_layout)
@@ -721,7 +761,10 @@ class DevicePacker:
     `src_layout` "NV12" / "NV21" / "I420" / "YV12": the clip is decoder-native YUV 4:2:0, uint8 [B, T, Hc*3/2, W] with the
     strides it has (`yuv_geometry`; `coded_height`, `height`), or one video [N, Hc*3/2, W] for `fill_video`; `yuv` is
     (standard, full_range) for `yuv_matrix` or a 3 x 4 matrix.  The ingest converts every tap itself (`pv_yuv_views`): no RGB
-    copy is made, and a pitched decoder surface is read in place.  Classification models only.
+    copy is made, and a pitched decoder surface is read in place.  Classification models only.  The layouts of
+    `YUV16_LAYOUTS` ("P010" / "P012" / "P016" / "I010" / "I012" / "I016": uint16 or int16 tensors, what a decoder hands out
+    for 10- to 16-bit streams) go through every one of these paths the same way (`pv_yuv16_views`, `PV_U16`); a
+    (standard, full_range) pair is composed with the layout's depth and bit alignment, and no narrowing pass exists.
 
     `fill_video(video, tables, i0, n)` + `launch()` run the resampling packer on ONE decoded video instead of clips: items
     [i0, i0 + n) of its clips x views sequence, the clips being rows of a frame table (`data.clip_frame_table`, uploaded by
@@ -748,10 +791,11 @@ class DevicePacker:
                              "key-frame path: keyframes=True)")
         # keyframes=True and short_side alone: no crop (the detection tutorial's protocol) -- the window is the whole scaled frame
         self.no_crop, self.keyframes = short_side is not None and crop_size is None, bool(keyframes)
-        if src_layout not in ("NCTHW", "NTHWC") + YUV_LAYOUTS:
-            raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,))
+        if src_layout not in ("NCTHW", "NTHWC") + _YUV_ANY:
+            raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
         self.short_side, self.crop_size, self.src_layout = short_side, crop_size, src_layout
-        self.is_yuv, self.coded_height, self.height = src_layout in YUV_LAYOUTS, coded_height, height
+        self.is_yuv, self.coded_height, self.height = src_layout in _YUV_ANY, coded_height, height
+        self.is_yuv16 = src_layout in YUV16_LAYOUTS            # 16-bit samples: pv_yuv16_views / PV_U16
         if self.is_yuv and not self.keyframes and (getattr(deployed, "_pv_load_boxes", None) is not None):
             raise ValueError("a detection model does not take %s frames: its boxes are mapped through the scaling and the crop "
                              "of an RGB clip on the host, and that path is not built for YUV sources (the key-frame path, "
@@ -799,7 +843,7 @@ class DevicePacker:
         self._index = {}
         self._planar = {}
         self._clip_tables = {}
-        self.yuv_matrix = _yuv_matrix_of(yuv).float().reshape(12).to(self.sess.device) if self.is_yuv else None
+        self.yuv_matrix = _yuv_matrix_of(yuv, src_layout).float().reshape(12).to(self.sess.device) if self.is_yuv else None
 
     def _t_index(self, t_src, ref):
         key = (t_src, ref.T)
@@ -1020,7 +1064,7 @@ class DevicePacker:
                 d.item0, d.n_items = (item0, n_items) if n_items else (0, 0)
                 if self.scale is not None:
                     d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
-                self.sess.yuv_views(d, ref, planar=self._planar_for(i, ref))
+                (self.sess.yuv16_views if self.is_yuv16 else self.sess.yuv_views)(d, ref, planar=self._planar_for(i, ref))
             return
         c, nf, hs, ws = _video_geometry(video, self.src_layout)
         hn, wn = scaled_size(hs, ws, self.short_side)
@@ -1108,7 +1152,7 @@ class DevicePacker:
             d.src_dtype = batch.src_dtype
             d.src_layout = L.SRC_YUV420 if self.is_yuv else (L.SRC_NCTHW if self.src_layout == "NCTHW" else L.SRC_NTHWC)
             if self.is_yuv:
-                d.c_step, d.yuv2rgb = (2 if self.src_layout in ("NV12", "NV21") else 1), self.yuv_matrix.data_ptr()
+                d.c_step, d.yuv2rgb = (2 if self.src_layout in _YUV_INTERLEAVED else 1), self.yuv_matrix.data_ptr()
             d.Ho, d.Wo, d.n_views = self.window[0], self.window[1], len(self.views)
             if self.scale is not None:
                 d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
