@@ -184,7 +184,76 @@ __global__ __launch_bounds__(kThreads) void pool_window_kernel(const pv_pool3d_d
           ((long)(to * d.Ho + ho) * d.Wo + wo) * d.ldy + cg * 8);
 }
 
-// large windows: one block per output voxel (and chunk slab), taps split over threads
+// large windows: one block per output voxel (and chunk slab), taps split over threads.
+// A thread's taps sp, sp + splits, ... go out kPoolBatch at a time as straight-line code, all loads of a batch ahead of
+// its additions, and are accumulated in tap order.  Nothing is divided or multiplied per tap: the tap's byte offset steps
+// with it -- by a constant where the window is a run of whole input planes (WHOLE: the head pools, tap t is voxel
+// t0 * Hi * Wi + t), with (dt, dh, dw) and their carries otherwise.  A tap outside the input loads the item's first voxel
+// instead and contributes the neutral element; so does, in the thread's last batch, a tap past the window's end.
+constexpr int kPoolBatch = 8;
+template <bool B> struct BoolC { static constexpr bool value = B; };
+template <typename T, bool MAX, bool WHOLE>
+__device__ __forceinline__ void pool_reduce_taps(const pv_pool3d_desc& d, const T* X, int t0, int h0, int w0, int sp,
+                                                 int splits, int taps, float (&a)[8]) {
+  const long vox = (long)d.ldx * (long)sizeof(T), row = vox * d.Wi, plane = row * d.Hi;   // bytes
+  int dt = 0, dh = 0, dw = 0, s_t = 0, s_h = 0, s_w = 0;
+  long off, step, wrap_w = 0, wrap_h = 0;
+  if (WHOLE) {
+    off = t0 * plane + sp * vox;
+    step = splits * vox;
+  } else {
+    const int khw = d.kh * d.kw;
+    s_t = splits / khw;
+    s_h = (splits - s_t * khw) / d.kw;
+    s_w = splits - s_t * khw - s_h * d.kw;
+    dt = sp / khw;
+    dh = (sp - dt * khw) / d.kw;
+    dw = sp - dt * khw - dh * d.kw;
+    off = (t0 + dt) * plane + (h0 + dh) * row + (w0 + dw) * vox;
+    step = s_t * plane + s_h * row + s_w * vox;
+    wrap_w = row - d.kw * vox;       // dw -= kw, ++dh
+    wrap_h = plane - d.kh * row;     // dh -= kh, ++dt
+  }
+  const char* Xb = reinterpret_cast<const char*>(X);
+  const float neutral = MAX ? -FLT_MAX : 0.f;
+  int t = sp;
+  auto batch = [&](auto full) {
+    constexpr bool FULL = decltype(full)::value;     // every tap of the batch is inside the window
+    Chunk8<T> c[kPoolBatch];
+    bool ok[kPoolBatch];
+#pragma unroll
+    for (int i = 0; i < kPoolBatch; ++i) {
+      ok[i] = FULL || t + i * splits < taps;
+      if (!WHOLE)
+        ok[i] = ok[i] && (unsigned)(t0 + dt) < (unsigned)d.Ti && (unsigned)(h0 + dh) < (unsigned)d.Hi &&
+                (unsigned)(w0 + dw) < (unsigned)d.Wi;
+      c[i].load(reinterpret_cast<const T*>(Xb + (ok[i] ? off : 0L)));
+      off += step;
+      if (!WHOLE) {
+        dw += s_w;
+        if (dw >= d.kw) { dw -= d.kw; ++dh; off += wrap_w; }
+        dh += s_h;
+        if (dh >= d.kh) { dh -= d.kh; ++dt; off += wrap_h; }
+        dt += s_t;
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keep the batch's loads together: sunk to their uses, each is waited for alone
+#pragma unroll
+    for (int i = 0; i < kPoolBatch; ++i) {
+      float f[8];
+      c[i].to_f32(f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = ok[i] ? f[j] : neutral;
+        a[j] = MAX ? fmaxf(a[j], v) : a[j] + v;
+      }
+    }
+    t += kPoolBatch * splits;
+  };
+  while (t + (kPoolBatch - 1) * splits < taps) batch(BoolC<true>());
+  if (t < taps) batch(BoolC<false>());
+}
+
 template <typename T>
 __global__ __launch_bounds__(kThreads) void pool_reduce_kernel(const pv_pool3d_desc d, int cgb) {
   __shared__ float s_red[kThreads * 8];
@@ -205,19 +274,14 @@ __global__ __launch_bounds__(kThreads) void pool_reduce_kernel(const pv_pool3d_d
   const int taps = d.kt * d.kh * d.kw;
   if (cg < CG && sp < splits) {
     const T* X = static_cast<const T*>(d.x) + (long)b * d.x_bs + (long)d.n_prefix * d.ldx + cg * 8;
-    for (int t = sp; t < taps; t += splits) {
-      const int dt = t / (d.kh * d.kw);
-      const int r = t - dt * d.kh * d.kw;
-      const int dh = r / d.kw, dw = r - dh * d.kw;
-      const int ti = to * d.st - d.pt + dt, hi = ho * d.sh - d.ph + dh, wi = wo * d.sw - d.pw + dw;
-      if ((unsigned)ti >= (unsigned)d.Ti || (unsigned)hi >= (unsigned)d.Hi || (unsigned)wi >= (unsigned)d.Wi)
-        continue;
-      Chunk8<T> c;
-      c.load(X + ((long)(ti * d.Hi + hi) * d.Wi + wi) * d.ldx);
-      float f[8];
-      c.to_f32(f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a[j] = is_max ? fmaxf(a[j], f[j]) : a[j] + f[j];
+    const int t0 = to * d.st - d.pt, h0 = ho * d.sh - d.ph, w0 = wo * d.sw - d.pw;
+    const bool whole = t0 >= 0 && t0 + d.kt <= d.Ti && h0 == 0 && d.kh == d.Hi && w0 == 0 && d.kw == d.Wi;
+    if (is_max) {
+      if (whole) pool_reduce_taps<T, true, true>(d, X, t0, h0, w0, sp, splits, taps, a);
+      else pool_reduce_taps<T, true, false>(d, X, t0, h0, w0, sp, splits, taps, a);
+    } else {
+      if (whole) pool_reduce_taps<T, false, true>(d, X, t0, h0, w0, sp, splits, taps, a);
+      else pool_reduce_taps<T, false, false>(d, X, t0, h0, w0, sp, splits, taps, a);
     }
   }
 #pragma unroll
@@ -723,26 +787,62 @@ __global__ __launch_bounds__(kThreads) void add_act_kernel(const pv_add_desc d, 
 }
 
 // The same gate for the sizes X3D uses (C <= 448, reduced width <= 32): this kernel is a chain of four
-// dependent phases on a handful of bytes, so its duration is the sum of their memory latencies.  Every
-// FC weight a thread will need is requested at kernel entry, together with the partial sums, so the
-// phases after the first run out of registers.
-constexpr int kSeMaxCh = 2;     // channels per thread: c_p <= 512
+// dependent phases on a handful of bytes, so its duration is the sum of their memory latencies and of the
+// instructions one wave has to issue between them.  Every FC weight a thread will need is requested at kernel
+// entry, together with the first partial sums, so the phases after the first run out of registers and LDS.
+// fc2's matrix is [C][cr], and thread = channel would fetch it with one dword load per hidden unit, the 64
+// lanes of a wave in 64 different lines (at C = 432, cr = 32 about 16 k line requests per workgroup for
+// 55 KB that are contiguous in memory).  The block therefore fetches w2 as the flat array it is, 16 bytes
+// per lane, and spreads it into an LDS image [C][cr | 1]: the odd pitch puts the rows that the lanes of a
+// wave read in fc2 on different banks.
+// The wider stages run more waves (se_threads): the mean keeps the 256-thread split of the rows, on which the
+// order of its sum depends; fc1 (one wave per hidden unit), fc2 (one thread per channel) and the staging of w2
+// do the same arithmetic whichever wave does it, and each wave has a quarter of the instructions to issue.
+constexpr int kSeMaxCp = 512;   // channels (padded) the fast kernel covers
+__host__ __device__ constexpr int se_threads(int cj, int crp) { return cj * crp > 64 ? 1024 : cj * crp > 16 ? 512 : kThreads; }
+__host__ __device__ __forceinline__ int se_w2_pitch(int cr) { return cr | 1; }
+// floats of dynamic LDS: s_mean[c_p], s_hid[32], s_part[groups][c_p], s_w2[C][pitch] + 32 (fc2 reads CRP <= 32
+// columns of every row unconditionally, so the last row's reads end inside the allocation)
+__host__ __device__ __forceinline__ int se_w2_lds_off(int c_p, int groups) { return c_p + 32 + groups * c_p; }
 // CJ: 64-channel strides covering C (<= 7); CRP: reduced width rounded up to 8 / 16 / 32
 template <int CJ, int CRP>
-__global__ __launch_bounds__(kThreads) void se_gate_fast_kernel(const pv_se_gate_desc d) {
+__global__ __launch_bounds__(se_threads(CJ, CRP)) void se_gate_fast_kernel(const pv_se_gate_desc d) {
+  constexpr int NT = se_threads(CJ, CRP);
   constexpr int kSeMaxC64 = CJ;
-  constexpr int kSeMaxR = CRP / 4;   // hidden units per wave (4 waves)
+  constexpr int kSeMaxR = CRP / (NT / 64);                          // hidden units per wave
+  constexpr int kSeMaxCh = kSeMaxCp / NT > 0 ? kSeMaxCp / NT : 1;   // channels per thread
+  constexpr int kW2Q = (CJ * 64 * CRP / 4 + NT - 1) / NT;           // 16-byte pieces of w2 per thread
   extern __shared__ float s[];
   float* s_mean = s;                 // [c_p]
   float* s_hid = s + d.c_p;          // [32]
   float* s_part = s + d.c_p + 32;    // [groups][c_p]
   const int b = blockIdx.x, tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
-  // ---- prefetch: fc1 rows (wave = hidden unit), fc2 rows (thread = channel), biases ----
+  const int cw = d.c_p < kThreads ? d.c_p : kThreads;
+  const int groups = kThreads / cw;
+  float* s_w2 = s + se_w2_lds_off(d.c_p, groups);   // [C][pitch]
+  // ---- prefetch: fc2 matrix (flat, to LDS below), fc1 rows (wave = hidden unit), biases ----
+  // w2 = `head` leading floats up to the first 16-byte boundary, nq aligned 16-byte pieces, a tail of < 4 floats
+  const int n2 = d.C * d.cr;
+  int head = (int)((16u - (unsigned)((size_t)d.w2 & 15u)) & 15u) >> 2;
+  head = head < n2 ? head : n2;
+  const int nq = (n2 - head) >> 2;
+  const int ntail = n2 - head - 4 * nq;
+  f32x4 w2q[kW2Q];
+#pragma unroll
+  for (int i = 0; i < kW2Q; ++i) {
+    const int q = tid + i * NT;
+    w2q[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (q < nq) w2q[i] = *reinterpret_cast<const f32x4*>(d.w2 + head + 4 * q);
+  }
+  // the ragged ends: threads 0..2 take the head, threads 4..6 the tail
+  const int e_rag = tid < 4 ? (tid < head ? tid : -1) : (tid - 4 < ntail ? head + 4 * nq + tid - 4 : -1);
+  float w2rag = 0.f;
+  if (e_rag >= 0) w2rag = d.w2[e_rag];
   float w1r[kSeMaxR][kSeMaxC64], b1r[kSeMaxR];
 #pragma unroll
   for (int i = 0; i < kSeMaxR; ++i) {
-    const int r = wave + i * 4;
+    const int r = wave + i * (NT / 64);
     const bool rok = r < d.cr;
     b1r[i] = (rok && d.b1) ? d.b1[r] : 0.f;
 #pragma unroll
@@ -753,23 +853,14 @@ __global__ __launch_bounds__(kThreads) void se_gate_fast_kernel(const pv_se_gate
       w1r[i][j] = ok ? v : 0.f;
     }
   }
-  float w2r[kSeMaxCh][CRP], b2r[kSeMaxCh];
+  float b2r[kSeMaxCh];
 #pragma unroll
   for (int i = 0; i < kSeMaxCh; ++i) {
-    const int c = tid + i * kThreads;
-    const bool cok = c < d.C;
-    b2r[i] = (cok && d.b2) ? d.b2[c] : 0.f;
-#pragma unroll
-    for (int r = 0; r < CRP; ++r) {
-      const bool ok = cok && r < d.cr;
-      const float v = d.w2[ok ? (long)c * d.cr + r : 0];
-      w2r[i][r] = ok ? v : 0.f;
-    }
+    const int c = tid + i * NT;
+    b2r[i] = (c < d.C && d.b2) ? d.b2[c] : 0.f;
   }
-  // ---- mean over T,H,W from the per-tile partial sums ----
+  // ---- mean over T,H,W from the per-tile partial sums: the first kThreads threads, as the generic kernel ----
   const float* ps = d.psum + (long)b * d.nblk * d.c_p;
-  const int cw = d.c_p < kThreads ? d.c_p : kThreads;
-  const int groups = kThreads / cw;
   const int g = tid / cw, cl = tid - g * cw;
   for (int c0 = 0; c0 < d.c_p; c0 += cw) {
     const int c = c0 + cl;
@@ -786,8 +877,32 @@ __global__ __launch_bounds__(kThreads) void se_gate_fast_kernel(const pv_se_gate
       s_part[g * d.c_p + c] = (a0 + a1) + (a2 + a3);
     }
   }
+  // ---- w2 into its LDS image: element e of the flat array is row e / cr, column e % cr; a thread's
+  // pieces are 4 * NT elements apart, so it divides once and steps (row, column) from piece to piece ----
+  {
+    const int pitch = se_w2_pitch(d.cr);
+    const int e0 = head + 4 * tid;
+    int row = e0 / d.cr, col = e0 - row * d.cr;
+    const int srow = 4 * NT / d.cr, scol = 4 * NT - srow * d.cr;
+#pragma unroll
+    for (int i = 0; i < kW2Q; ++i) {
+      int r = row, c = col;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (tid + i * NT < nq) s_w2[r * pitch + c] = w2q[i][k];
+        if (++c == d.cr) { c = 0; ++r; }
+      }
+      row += srow;
+      col += scol;
+      if (col >= d.cr) { col -= d.cr; ++row; }
+    }
+    if (e_rag >= 0) {
+      const int r = e_rag / d.cr;
+      s_w2[r * pitch + (e_rag - r * d.cr)] = w2rag;
+    }
+  }
   __syncthreads();
-  for (int c = tid; c < d.c_p; c += kThreads) {
+  for (int c = tid; c < d.c_p; c += NT) {
     float a = 0.f;
     for (int gg = 0; gg < groups; ++gg) a += s_part[gg * d.c_p + c];
     s_mean[c] = a * d.inv_count;
@@ -799,11 +914,12 @@ __global__ __launch_bounds__(kThreads) void se_gate_fast_kernel(const pv_se_gate
   for (int j = 0; j < kSeMaxC64; ++j) mj[j] = lane + j * 64 < d.C ? s_mean[lane + j * 64] : 0.f;
 #pragma unroll
   for (int i = 0; i < kSeMaxR; ++i) {
+    const int r = wave + i * (NT / 64);
     float a = 0.f;
 #pragma unroll
     for (int j = 0; j < kSeMaxC64; ++j) a += w1r[i][j] * mj[j];
     a = pv_wave_sum(a);
-    if (lane == 0 && wave + i * 4 < 32) s_hid[wave + i * 4] = wave + i * 4 < d.cr ? fmaxf(a + b1r[i], 0.f) : 0.f;
+    if (lane == 0 && r < 32) s_hid[r] = r < d.cr ? fmaxf(a + b1r[i], 0.f) : 0.f;
   }
   __syncthreads();
   // ---- fc2 + sigmoid ----
@@ -812,11 +928,15 @@ __global__ __launch_bounds__(kThreads) void se_gate_fast_kernel(const pv_se_gate
   for (int r = 0; r < CRP; ++r) hid[r] = s_hid[r];
 #pragma unroll
   for (int i = 0; i < kSeMaxCh; ++i) {
-    const int c = tid + i * kThreads;
+    const int c = tid + i * NT;
     if (c < d.c_p) {
+      const float* wrow = s_w2 + (c < d.C ? c : d.C - 1) * se_w2_pitch(d.cr);
+      float w2r[CRP];
+#pragma unroll
+      for (int r = 0; r < CRP; ++r) w2r[r] = wrow[r];
       float a = b2r[i];
 #pragma unroll
-      for (int r = 0; r < CRP; ++r) a += w2r[i][r] * hid[r];
+      for (int r = 0; r < CRP; ++r) a = __builtin_fmaf(r < d.cr ? w2r[r] : 0.f, hid[r], a);   // fused, as `a += w * h` always compiled here
       d.gate[(long)b * d.c_p + c] = c < d.C ? pv_sigmoid(a) : 0.f;
     }
   }
@@ -831,15 +951,16 @@ extern "C" int pv_se_gate(const pv_se_gate_desc* d, pv_stream_t stream) {
   if (!d || !d->psum || !d->gate || !d->w1 || !d->w2) return PV_ERR_INVALID;
   if (d->B <= 0 || d->C <= 0 || d->cr <= 0 || d->nblk <= 0 || d->c_p < d->C || d->c_p % 8) return PV_ERR_INVALID;
   const int cw = d->c_p < kThreads ? d->c_p : kThreads;
-  if (d->C <= 448 && d->cr <= 32 && d->c_p <= kThreads * kSeMaxCh) {
-    const size_t lds_f = sizeof(float) * ((size_t)d->c_p + 32 + (size_t)(kThreads / cw) * d->c_p);
+  if (d->C <= 448 && d->cr <= 32 && d->c_p <= kSeMaxCp) {
+    // at most (512 + 32 + 512) + (448 * 33 + 32) floats = 63488 bytes: inside the 64 KB a launch gets without opting in
+    const size_t lds_f = sizeof(float) * ((size_t)se_w2_lds_off(d->c_p, kThreads / cw) + (size_t)d->C * se_w2_pitch(d->cr) + 32);
     const int cj = (d->C + 63) / 64;
-    dim3 grid(d->B), block(kThreads);
+    dim3 grid(d->B);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (cj <= 1 && d->cr <= 8) PV_LAUNCH((se_gate_fast_kernel<1, 8>), grid, block, lds_f, st, *d);
-    else if (cj <= 2 && d->cr <= 8) PV_LAUNCH((se_gate_fast_kernel<2, 8>), grid, block, lds_f, st, *d);
-    else if (cj <= 4 && d->cr <= 16) PV_LAUNCH((se_gate_fast_kernel<4, 16>), grid, block, lds_f, st, *d);
-    else PV_LAUNCH((se_gate_fast_kernel<7, 32>), grid, block, lds_f, st, *d);
+    if (cj <= 1 && d->cr <= 8) PV_LAUNCH((se_gate_fast_kernel<1, 8>), grid, dim3(se_threads(1, 8)), lds_f, st, *d);
+    else if (cj <= 2 && d->cr <= 8) PV_LAUNCH((se_gate_fast_kernel<2, 8>), grid, dim3(se_threads(2, 8)), lds_f, st, *d);
+    else if (cj <= 4 && d->cr <= 16) PV_LAUNCH((se_gate_fast_kernel<4, 16>), grid, dim3(se_threads(4, 16)), lds_f, st, *d);
+    else PV_LAUNCH((se_gate_fast_kernel<7, 32>), grid, dim3(se_threads(7, 32)), lds_f, st, *d);
     PV_LAUNCH_CHECK();
     return PV_OK;
   }
