@@ -1,20 +1,12 @@
-// What pv_frames.hip and pv_frames16.hip share: the launch geometry of pv_frame_views and the item of a workgroup.
+// What pv_frames.hip and pv_frames16.hip share: the item of a workgroup of pv_frame_views and the launch of its 16-bit kernels.
 #pragma once
 #include "pv_rs.h"
 
 // The 16-bit YUV kernels of pv_frame_views (frame_yuv16_kernel, pv_frames16.hip) on a launch that fv_run (pv_frames.hip) has
-// validated and sized: R, the LDS pitches, the chroma base and the LDS bytes are FvLaunch's and rs_strip_rows'.
-int pv_frame_yuv16_launch(const pv_batch_views_desc* d, int32_t R, int32_t pitch, int32_t pitch_c, int32_t c_base, size_t lds,
-                          pv_stream_t stream);
+// validated and sized: g and lds are rs_item_launch's.
+int pv_frame_yuv16_launch(const pv_batch_views_desc& d, const RsItemLaunch& g, size_t lds, pv_stream_t stream);
 
 namespace {
-
-struct FvLaunch {
-  int32_t R;          // output rows per workgroup
-  int32_t pitch;      // LDS bytes per staged (row, plane) -- YUV: per staged luma row; multiple of 16, >= 15 + widest span
-  int32_t pitch_c;    // YUV: LDS bytes per staged chroma (row, plane)
-  int32_t c_base;     // YUV: LDS offset of the chroma image: 2 R pitch
-};
 
 // The item of this workgroup, clamped into range before anything is addressed through it, and the base address of the
 // frame its table row selects: the entry is clamped into [0, N-1] of the item's source before the slice is indexed, so a

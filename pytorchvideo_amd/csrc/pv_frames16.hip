@@ -7,7 +7,7 @@ namespace {
 // CSTEP / FORM / D: as rs_strip_yuv.  frame_yuv_kernel (pv_frames.hip) on two-byte samples: one frame is one surface, the
 // record's byte offsets and pitches from the frame's (even) base.
 template <int CSTEP, int FORM, typename D>
-__global__ __launch_bounds__(kRsThreads) void frame_yuv16_kernel(const pv_batch_views_desc d, const FvLaunch g) {
+__global__ __launch_bounds__(kRsThreads) void frame_yuv16_kernel(const pv_batch_views_desc d, const RsItemLaunch g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fy_lds[];
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
@@ -27,10 +27,7 @@ __global__ __launch_bounds__(kRsThreads) void frame_yuv16_kernel(const pv_batch_
 
 }  // namespace
 
-int pv_frame_yuv16_launch(const pv_batch_views_desc* dp, int32_t R, int32_t pitch, int32_t pitch_c, int32_t c_base, size_t lds,
-                          pv_stream_t stream) {
-  const pv_batch_views_desc& d = *dp;
-  const FvLaunch g = {R, pitch, pitch_c, c_base};
+int pv_frame_yuv16_launch(const pv_batch_views_desc& d, const RsItemLaunch& g, size_t lds, pv_stream_t stream) {
   if (d.c_step == 2) RS_DISPATCH(frame_yuv16_kernel, 2);
   else RS_DISPATCH(frame_yuv16_kernel, 1);
   PV_LAUNCH_CHECK();

@@ -1,13 +1,32 @@
-// The resampling ingest (pv_resample.hip: RGB / planar sources; pv_yuv.hip: YUV 4:2:0 sources; pv_batch.hip: either, with
-// one source per destination item).  What the entry points compute with is here, once: the pinned source coordinate, the
-// destination forms with their stores, the taps and blends, the two staged-strip bodies that the four kernels wrap
-// (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather), the launch arithmetic (widest span, rows per strip, destination-form
-// dispatch) and the host-side checks of views, item range, destination and YUV planes.  rs_strip_yuv takes the sample type:
-// bytes, or the 16-bit codes of P010 / yuv420p10le (pv_yuv16_views, PV_U16 sources).  The three files keep what differs:
-// where a workgroup's geometry comes from, and the validation of their descriptors.
-// Everything is inline in an anonymous namespace: each translation unit keeps its own kernels.
+// The resampling ingest: six entry points in five translation units.
+//   pv_resample.hip   pv_resample_crop, pv_video_views    RGB / planar sources, one source per launch
+//   pv_yuv.hip        pv_yuv_views, pv_yuv16_views        YUV 4:2:0 sources of 8- / 16-bit samples, one source per launch
+//   pv_batch.hip      pv_batch_views                      either, one source per destination item
+//   pv_frames.hip     pv_frame_views                      the same with every frame addressed through a pointer table
+//   pv_frames16.hip   (launched from pv_frames.hip)       the 16-bit YUV kernels of pv_frame_views
+// What they compute with is here, once: the pinned source coordinate, the destination forms with their stores, the taps and
+// blends, the two staged-strip bodies (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather) that the nine kernel templates
+// wrap (resample_crop_kernel; yuv_views_kernel, yuv16_views_kernel; batch_views_kernel, batch_yuv_kernel,
+// batch_yuv16_kernel; frame_views_kernel, frame_yuv_kernel; frame_yuv16_kernel), the launch arithmetic (widest span, rows
+// per strip, destination-form dispatch), the host-side checks of views, item range, destination and YUV planes, and the
+// whole validation and sizing of an item-sourced launch (rs_item_launch).  rs_strip_yuv takes the sample type: bytes, or the
+// 16-bit codes of P010 / yuv420p10le (PV_U16 sources).  The files keep what differs: where a workgroup's geometry comes
+// from (the kernel wrappers), the validation of the one-source descriptors (rs_run, yuv_run) and, for the item-sourced two,
+// what a record's `src` must be.
+// Everything but RsItemLaunch is inline in an anonymous namespace: each translation unit keeps its own kernels.
 #pragma once
+#include <cstring>
+
 #include "pv_common.h"
+
+// What stays per launch of an item-sourced kernel (pv_batch.hip, pv_frames.hip, pv_frames16.hip): filled by rs_item_launch.
+// It crosses translation units (pv_frame_yuv16_launch), so it is the one type here with external linkage.
+struct RsItemLaunch {
+  int32_t R;          // output rows per workgroup
+  int32_t pitch;      // LDS bytes per staged (row, plane) -- YUV: per staged luma row; multiple of 16, >= 15 + widest span
+  int32_t pitch_c;    // YUV: LDS bytes per staged chroma (row, plane)
+  int32_t c_base;     // YUV: LDS offset of the chroma image: 2 R pitch
+};
 
 namespace {
 
@@ -576,6 +595,67 @@ inline int rs_check_yuv_planes(int Hs, int Ws, int c_step, int y_pitch, int c_pi
 inline bool rs_yuv16_even(uintptr_t base) { return (base & 1) == 0; }
 inline int rs_check_yuv16_even(uintptr_t base, int y_pitch, int c_pitch, int64_t frame_stride, int64_t u_offset, int64_t v_offset) {
   if (!rs_yuv16_even(base) || ((y_pitch | c_pitch) & 1) || ((frame_stride | u_offset | v_offset) & 1)) return PV_ERR_INVALID;
+  return PV_OK;
+}
+
+// ---- an item-sourced launch (pv_batch_views, pv_frame_views): validated and sized here, once -----------------------------
+inline bool rs_same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof(float)) == 0; }
+
+// One record of such a launch: positive sizes, windows inside the scaled frame, sy / sx the library's own division, for YUV
+// the planes inside a frame, at even bytes for two-byte samples, and what its `src` points to (check_src: see below).
+template <typename CheckSrc>
+inline int rs_check_record(const pv_batch_views_desc& d, const pv_view_source& v, bool yuv, const CheckSrc& check_src) {
+  if (!v.src || v.N <= 0 || v.Hs <= 0 || v.Ws <= 0 || v.Hn <= 0 || v.Wn <= 0) return PV_ERR_INVALID;
+  if (int e = rs_check_views(d.n_views, v.y_off, v.x_off, d.Ho, d.Wo, v.Hn, v.Wn)) return e;
+  if (!rs_same_bits(v.sy, (float)v.Hs / (float)v.Hn) || !rs_same_bits(v.sx, (float)v.Ws / (float)v.Wn)) return PV_ERR_INVALID;
+  if (yuv) {
+    const int sb = d.src_dtype == PV_U16 ? 2 : 1;
+    if (int e = rs_check_yuv_planes(v.Hs, v.Ws, d.c_step, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset, sb)) return e;
+    if (sb == 2 && rs_check_yuv16_even(0, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset)) return PV_ERR_INVALID;
+  }
+  return check_src(v);
+}
+
+// The descriptor, the items and the record behind each of them, then R, the LDS pitch(es) and the LDS bytes of the launch.
+// check_src(record) is the entry point's own part: whether the record's `src` is a source of d.src_dtype (PV_ERR_INVALID if
+// not).  A launch is a window of a longer sequence and reads only the records its items name (the kernel clamps `source`
+// into range and the items are the validated ones), so its cost does not grow with the number of videos of the whole
+// sequence; a video-major sequence names the record just checked, which is not checked again, and any other record named
+// again is, which is cheaper than remembering.  The widest column span(s) of any such record x view size the staged rows.
+template <typename CheckSrc>
+inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_src, RsItemLaunch& g, size_t& lds) {
+  if (!d.sources || !d.sources_dev || !d.items || !d.items_dev || !d.t_index || !d.dst) return PV_ERR_INVALID;
+  if (d.n_sources <= 0 || d.n_items <= 0 || d.n_rows <= 0 || d.T <= 0 || d.C <= 0 || d.Ho <= 0 || d.Wo <= 0) return PV_ERR_INVALID;
+  if (d.t_stride < d.T || d.n_items > 65535 || d.T > 65535) return PV_ERR_INVALID;   // grid.y / grid.z
+  if (d.C > 4 || d.n_views < 1 || d.n_views > 3) return PV_ERR_INVALID;
+  const bool yuv = d.src_layout == PV_SRC_YUV420, inter = d.src_layout == PV_SRC_NTHWC;
+  if (!yuv && !inter && d.src_layout != PV_SRC_NCTHW) return PV_ERR_INVALID;
+  if (!yuv && d.src_dtype == PV_U16) return PV_ERR_UNSUPPORTED;   // 16-bit samples are a YUV 4:2:0 source only
+  if (inter && (d.src_dtype != PV_U8 || d.C != 3)) return PV_ERR_INVALID;
+  if (yuv && (!d.yuv2rgb || d.C != 3 || (d.c_step != 1 && d.c_step != 2))) return PV_ERR_INVALID;
+  // the dtype / layout matrix
+  if (yuv ? (d.src_dtype != PV_U8 && d.src_dtype != PV_U16) : (d.src_dtype != PV_U8 && d.src_dtype != PV_F32)) return PV_ERR_UNSUPPORTED;
+  if (int e = rs_check_dst(d.dst, d.dst_layout, d.dst_dtype, d.c_p, d.ld, d.bs, d.T, d.Ho, d.Wo)) return e;
+  int span = 0, span_c = 0;
+  for (int i = 0; i < d.n_items; ++i) {
+    const pv_view_item& it = d.items[i];
+    if (it.source < 0 || it.source >= d.n_sources || it.row < 0 || it.row >= d.n_rows || it.view < 0 || it.view >= d.n_views)
+      return PV_ERR_INVALID;
+    const pv_view_source& v = d.sources[it.source];
+    if (i == 0 || it.source != d.items[i - 1].source)   // a video-major sequence names the record just checked
+      if (int e = rs_check_record(d, v, yuv, check_src)) return e;
+    rs_widest_span(v.sx, v.x_off, d.n_views, d.Wo, v.Ws, span, span_c);
+  }
+  g = {};
+  long per_row;                                    // LDS bytes of the two source rows of one output row
+  if (yuv) {
+    per_row = rs_yuv_pitches(span, span_c, d.c_step, d.src_dtype == PV_U16 ? 2 : 1, g.pitch, g.pitch_c);
+  } else {
+    g.pitch = pv_round_up(span * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
+    per_row = 2L * (inter ? 1 : d.C) * g.pitch;
+  }
+  if (int e = rs_strip_rows(per_row, d.Ho, g.R, lds)) return e;
+  g.c_base = 2 * g.R * g.pitch;
   return PV_OK;
 }
 

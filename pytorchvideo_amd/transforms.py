@@ -214,6 +214,7 @@ YUV_LAYOUTS = ("NV12", "NV21", "I420", "YV12")
 YUV16_LAYOUTS = ("P010", "P012", "P016", "I010", "I012", "I016")
 _YUV_ANY = YUV_LAYOUTS + YUV16_LAYOUTS
 _YUV_INTERLEAVED = ("NV12", "NV21", "P010", "P012", "P016")
+_YUV_PLANE_FIELDS = ("frame_stride", "u_offset", "v_offset", "y_pitch", "c_pitch")   # of `yuv_geometry`, a descriptor, a record
 _YUV16_DEPTH = {"P010": (10, True), "P012": (12, True), "P016": (16, True), "I010": (10, False), "I012": (12, False),
                 "I016": (16, False)}                       # layout -> (bit depth, MSB-aligned)
 _YUV_KR_KB = {"bt709": (0.2126, 0.0722), "bt601": (0.299, 0.114)}
@@ -378,22 +379,60 @@ def _source_geometry(clip, src_layout):
     return b, c, t, h, w
 
 
+def _view_geometry(hs, ws, short_side, crop, views, what=""):
+    """(Hn, Wn, [(y_off, x_off) per view]) of the views of an Hs x Ws source: short_side_scale, then uniform_crop.  `crop` is
+    the side of the square crop, or a pair (Ho, Wo): NO crop -- the window is the whole scaled frame, which must then be
+    exactly Ho x Wo.  RuntimeError, its message behind `what`, if the window does not fit."""
+    hn, wn = scaled_size(hs, ws, short_side)
+    if isinstance(crop, (tuple, list)):
+        if (hn, wn) != (int(crop[0]), int(crop[1])):
+            raise RuntimeError("%sthe %d x %d frame scales to %d x %d, the deploy form takes %d x %d and nothing is cropped"
+                               % (what, hs, ws, hn, wn, crop[0], crop[1]))
+        return hn, wn, [(0, 0)] * len(views)
+    if crop > hn or crop > wn:
+        raise RuntimeError("%sa %d crop does not fit the %d x %d frame scaled to %d x %d" % (what, crop, hs, ws, hn, wn))
+    return hn, wn, [crop_offsets(hn, wn, crop, v) for v in views]
+
+
+def _set_views(d, hn, wn, offsets, crop_size=None):
+    """The view fields of a descriptor, or (`crop_size` None) of a ViewSource record, whose window is its launch's."""
+    d.Hn, d.Wn = hn, wn
+    for i, (y, x) in enumerate(offsets):
+        d.y_off[i], d.x_off[i] = y, x
+    if crop_size is not None:
+        d.Ho, d.Wo, d.n_views = crop_size, crop_size, len(offsets)
+
+
+def _set_affine(d, scale, shift):
+    """The affine pair of `_affine` into a descriptor; (None, None) leaves the null pointers: no map."""
+    if scale is not None:
+        d.ch_scale, d.ch_shift = scale.data_ptr(), shift.data_ptr()
+
+
+def _src_codes(src_layout, dtype):
+    """(src_layout, src_dtype) as the descriptors code them; `dtype` is the tensors' and decides for RGB / planar sources."""
+    from . import _lib as L
+    if src_layout in _YUV_ANY:
+        return L.SRC_YUV420, L.PV_U16 if src_layout in YUV16_LAYOUTS else L.PV_U8
+    return L.SRC_NCTHW if src_layout == "NCTHW" else L.SRC_NTHWC, L.PV_U8 if dtype == torch.uint8 else L.PV_F32
+
+
+def _rgb_source(d, src, src_layout, c, hs, ws, geo, crop_size):
+    """What a ResampleDesc and a VideoViewsDesc share: the RGB / planar source `src` of C x Hs x Ws frames and the views
+    (`geo`: `_view_geometry`) of short_side_scale + uniform_crop.  Returns `d`."""
+    d.src, d.C, d.Hs, d.Ws = src.data_ptr(), c, hs, ws
+    d.src_layout, d.src_dtype = _src_codes(src_layout, src.dtype)
+    _set_views(d, *geo, crop_size)
+    return d
+
+
 def _resample_desc(clip, src_layout, short_side, crop_size, views):
     """A ResampleDesc with the source and the geometry of short_side_scale + uniform_crop filled in (the destination, the
     frame selection and the affine map are the caller's).  `clip` is contiguous, uint8 or fp32, on the device."""
     from . import _lib as L
     b, c, t, hs, ws = _source_geometry(clip, src_layout)
-    hn, wn = scaled_size(hs, ws, short_side)
-    if crop_size > hn or crop_size > wn:
-        raise RuntimeError("a %d crop does not fit the %d x %d frame scaled to %d x %d" % (crop_size, hs, ws, hn, wn))
-    d = L.ResampleDesc()
-    d.src = clip.data_ptr()
-    d.B, d.C, d.T, d.src_T, d.Hs, d.Ws = b, c, t, t, hs, ws
-    d.src_dtype = L.PV_U8 if clip.dtype == torch.uint8 else L.PV_F32
-    d.src_layout = L.SRC_NCTHW if src_layout == "NCTHW" else L.SRC_NTHWC
-    d.Hn, d.Wn, d.Ho, d.Wo, d.n_views = hn, wn, crop_size, crop_size, len(views)
-    for i, v in enumerate(views):
-        d.y_off[i], d.x_off[i] = crop_offsets(hn, wn, crop_size, v)
+    d = _rgb_source(L.ResampleDesc(), clip, src_layout, c, hs, ws, _view_geometry(hs, ws, short_side, crop_size, views), crop_size)
+    d.B, d.T, d.src_T = b, t, t
     return d
 
 
@@ -414,6 +453,27 @@ def _video_geometry(video, src_layout):
     return c, n, h, w
 
 
+def _on_device(video, device, what):
+    if video.device.type != device.type or (device.index is not None and video.device.index != device.index):
+        raise RuntimeError("%s is on %s, the deploy form on %s" % (what, video.device, device))
+
+
+def _video_source(video, src_layout, device, coded_height=None, height=None, what="the video"):
+    """What a legal video tensor is for `src_layout`, for `fill_video` and `video_batch` alike: on `device`, and either
+    contiguous uint8 / fp32 [C,N,H,W], contiguous uint8 [N,H,W,3], or YUV frames with the strides `yuv_geometry` accepts.
+    Returns (C, N, Hs, Ws, geom), `geom` being `yuv_geometry` of the frames, or None.  RuntimeError, naming `what`, if not."""
+    _on_device(video, device, what)
+    if src_layout in _YUV_ANY:
+        geom = yuv_geometry(video, src_layout, coded_height, height)
+        return 3, geom["N"], geom["Hs"], geom["Ws"], geom
+    c, nf, hs, ws = _video_geometry(video, src_layout)
+    if not video.is_contiguous() or video.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError("%s is not a contiguous uint8 or fp32 tensor" % what)
+    if src_layout == "NTHWC" and (c != 3 or video.dtype != torch.uint8):
+        raise RuntimeError("a frame-interleaved video is uint8 [N,H,W,3], got %s %s" % (video.dtype, tuple(video.shape)))
+    return c, nf, hs, ws, None
+
+
 def pathway_tables(table, pathway_frames, num_frames):
     """The frame table of every input pathway from the table of the clip itself (`data.clip_frame_table`): pathway p holds
     the columns `temporal_indices(T, pathway_frames[p])` of the [n_clips, T] table -- uniform_temporal_subsample_repeated on
@@ -430,23 +490,18 @@ def pathway_tables(table, pathway_frames, num_frames):
     return [table[:, temporal_indices(t, tp)].to(torch.int32).contiguous() for tp in pathway_frames]
 
 
-def _yuv_desc(frames, geom, table, matrix, short_side, crop_size, views):
+def _yuv_desc(frames, geom, table, matrix, short_side, crop_size, views, geo=None):
     """A YuvViewsDesc with the source, the frame table, the conversion and the geometry of short_side_scale + uniform_crop
     filled in (destination, item range and affine map are the caller's).  `frames`, `table` (int32 [n_clips, T]) and
-    `matrix` (fp32 [12]) are on the device and stay alive until the launch has run."""
+    `matrix` (fp32 [12]) are on the device and stay alive until the launch has run.  `geo`: the `_view_geometry` of the
+    source, where the caller has it already."""
     from . import _lib as L
-    hs, ws = geom["Hs"], geom["Ws"]
-    hn, wn = scaled_size(hs, ws, short_side)
-    if crop_size > hn or crop_size > wn:
-        raise RuntimeError("a %d crop does not fit the %d x %d frame scaled to %d x %d" % (crop_size, hs, ws, hn, wn))
     d = L.YuvViewsDesc()
+    _set_views(d, *(geo or _view_geometry(geom["Hs"], geom["Ws"], short_side, crop_size, views)), crop_size)
     d.src, d.t_index, d.yuv2rgb = frames.data_ptr(), table.data_ptr(), matrix.data_ptr()
-    d.n_clips, d.T, d.N, d.t_stride, d.Hs, d.Ws = table.shape[0], table.shape[1], geom["N"], table.stride(0), hs, ws
-    for k in ("frame_stride", "u_offset", "v_offset", "y_pitch", "c_pitch", "c_step"):
+    d.n_clips, d.T, d.N, d.t_stride = table.shape[0], table.shape[1], geom["N"], table.stride(0)
+    for k in ("Hs", "Ws") + _YUV_PLANE_FIELDS + ("c_step",):
         setattr(d, k, geom[k])
-    d.Hn, d.Wn, d.Ho, d.Wo, d.n_views = hn, wn, crop_size, crop_size, len(views)
-    for i, v in enumerate(views):
-        d.y_off[i], d.x_off[i] = crop_offsets(hn, wn, crop_size, v)
     return d
 
 
@@ -457,10 +512,22 @@ def _clip_rows(n_clips, clip_frames, num_frames):
     return (torch.arange(n_clips)[:, None] * clip_frames + idx[None, :]).to(torch.int32).contiguous()
 
 
-def _device_scale_crop_yuv(frames, short_side, crop_size, views, mean, std, div255, num_frames, dtype, src_layout, yuv,
-                           coded_height, height):
+def _scale_crop_launch(d, entry, what, b, c, affine, dtype, device):
+    """The tail of `device_scale_crop` for either kind of source: the planar [b * n_views, c, T, Ho, Wo] destination of
+    `dtype`, the affine map (`affine`: mean, std, div255) and the launch of `entry` on `device`'s current stream."""
     import ctypes as C
     from . import _lib as L
+    scale, shift = _affine(*affine, c, device)
+    _set_affine(d, scale, shift)
+    out = torch.empty((b * d.n_views, c, d.T, d.Ho, d.Wo), dtype=dtype, device=device)
+    d.dst, d.dst_layout = out.data_ptr(), L.DST_NCTHW
+    d.dst_dtype = L.PV_BF16 if dtype == torch.bfloat16 else L.PV_F32
+    with torch.cuda.device(device):
+        L.check(getattr(L.lib(), entry)(C.byref(d), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), what)
+    return out
+
+
+def _device_scale_crop_yuv(frames, short_side, crop_size, views, affine, num_frames, dtype, src_layout, yuv, coded_height, height):
     device = frames.device if frames.is_cuda else torch.device("cuda", torch.cuda.current_device())
     frames = frames.to(device, non_blocking=True)
     geom = yuv_geometry(frames, src_layout, coded_height, height)
@@ -468,16 +535,8 @@ def _device_scale_crop_yuv(frames, short_side, crop_size, views, mean, std, div2
     table = _clip_rows(b, t_src, num_frames if num_frames is not None else t_src).to(device)
     matrix = _yuv_matrix_of(yuv, src_layout).float().reshape(12).to(device)
     d = _yuv_desc(frames, geom, table, matrix, short_side, crop_size, views)
-    scale, shift = _affine(mean, std, div255, 3, device)
-    if scale is not None:
-        d.ch_scale, d.ch_shift = scale.data_ptr(), shift.data_ptr()
-    out = torch.empty((b * d.n_views, 3, d.T, crop_size, crop_size), dtype=dtype, device=device)
-    d.dst, d.dst_layout = out.data_ptr(), L.DST_NCTHW
-    d.dst_dtype = L.PV_BF16 if dtype == torch.bfloat16 else L.PV_F32
-    with torch.cuda.device(device):
-        entry = L.lib().pv_yuv16_views if src_layout in YUV16_LAYOUTS else L.lib().pv_yuv_views
-        L.check(entry(C.byref(d), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "yuv_views")
-    return out
+    entry = "pv_yuv16_views" if src_layout in YUV16_LAYOUTS else "pv_yuv_views"
+    return _scale_crop_launch(d, entry, "yuv_views", b, 3, affine, dtype, device)
 
 
 # --------------------------------------------------------------------------- frame-list sources (pv_frame_views)
@@ -617,8 +676,6 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
         raise ValueError("the videos of one call are all tensors or all FrameLists, not a mix of tensors and FrameLists "
                          "(wrap a tensor: FrameList(video.unbind(0)))")
     is_yuv = src_layout in _YUV_ANY
-    no_crop = isinstance(crop_size, (tuple, list))
-    ho, wo = (int(crop_size[0]), int(crop_size[1])) if no_crop else (crop_size, crop_size)
 
     def per_video(x, what):
         if x is None or not isinstance(x, (list, tuple)):
@@ -632,42 +689,23 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
     sources = (L.ViewSource * len(videos))()
     nums_frames, dtype = [], videos[0].dtype
     for j, video in enumerate(videos):
-        if video.device.type != device.type or (device.index is not None and video.device.index != device.index):
-            raise RuntimeError("video %d is on %s, the deploy form on %s" % (j, video.device, device))
-        rec = sources[j]
+        what, rec = "video %d" % j, sources[j]
         if as_frames:
-            c, hs, ws, geom = video.geometry(src_layout, coded[j], heights[j])
-            nf = len(video)
-            if video.dtype != dtype:
-                raise RuntimeError("the videos of one batch have one dtype: video %d is %s, video 0 %s" % (j, video.dtype, dtype))
-            for k in ("frame_stride", "u_offset", "v_offset", "y_pitch", "c_pitch") if is_yuv else ():
-                setattr(rec, k, geom[k])
-        elif is_yuv:
-            if video.dim() != 3:
-                raise RuntimeError("video %d: expected one 3-d %s video, got %s" % (j, src_layout, tuple(video.shape)))
-            geom = yuv_geometry(video, src_layout, coded[j], heights[j])
-            c, nf, hs, ws = 3, geom["N"], geom["Hs"], geom["Ws"]
-            for k in ("frame_stride", "u_offset", "v_offset", "y_pitch", "c_pitch"):
-                setattr(rec, k, geom[k])
+            _on_device(video, device, what)
+            (c, hs, ws, geom), nf = video.geometry(src_layout, coded[j], heights[j]), len(video)
         else:
-            c, nf, hs, ws = _video_geometry(video, src_layout)
-            if not video.is_contiguous() or video.dtype not in (torch.uint8, torch.float32):
-                raise RuntimeError("video %d is not a contiguous uint8 or fp32 tensor" % j)
-            if video.dtype != dtype:
-                raise RuntimeError("the videos of one batch have one dtype: video %d is %s, video 0 %s" % (j, video.dtype, dtype))
-            if src_layout == "NTHWC" and (c != 3 or video.dtype != torch.uint8):
-                raise RuntimeError("a frame-interleaved video is uint8 [N,H,W,3], got %s %s" % (video.dtype, tuple(video.shape)))
+            if is_yuv and video.dim() != 3:
+                raise RuntimeError("video %d: expected one 3-d %s video, got %s" % (j, src_layout, tuple(video.shape)))
+            c, nf, hs, ws, geom = _video_source(video, src_layout, device, coded[j], heights[j], what)
+        if (as_frames or not is_yuv) and video.dtype != dtype:
+            raise RuntimeError("the videos of one batch have one dtype: video %d is %s, video 0 %s" % (j, video.dtype, dtype))
         if c != channels:
             raise RuntimeError("video %d has %d channels, the deploy form takes %d" % (j, c, channels))
-        hn, wn = scaled_size(hs, ws, short_side)
-        if no_crop and (hn, wn) != (ho, wo):
-            raise RuntimeError("video %d: the %d x %d frame scales to %d x %d, the deploy form takes %d x %d and nothing is cropped"
-                               % (j, hs, ws, hn, wn, ho, wo))
-        if not no_crop and (crop_size > hn or crop_size > wn):
-            raise RuntimeError("video %d: a %d crop does not fit the %d x %d frame scaled to %d x %d" % (j, crop_size, hs, ws, hn, wn))
-        rec.src, rec.N, rec.Hs, rec.Ws, rec.Hn, rec.Wn = (None if as_frames else video.data_ptr()), nf, hs, ws, hn, wn
-        for k, v in enumerate(views):
-            rec.y_off[k], rec.x_off[k] = (0, 0) if no_crop else crop_offsets(hn, wn, crop_size, v)
+        for k in _YUV_PLANE_FIELDS if is_yuv else ():
+            setattr(rec, k, geom[k])
+        hn, wn, offsets = _view_geometry(hs, ws, short_side, crop_size, views, what + ": ")
+        _set_views(rec, hn, wn, offsets)
+        rec.src, rec.N, rec.Hs, rec.Ws = (None if as_frames else video.data_ptr()), nf, hs, ws
         # (float)Hs / (float)Hn: sizes are exact in fp32, and a double quotient rounded once more to fp32 IS the fp32 quotient
         rec.sy, rec.sx = hs / hn, ws / wn
         nums_frames.append(nf)
@@ -682,7 +720,7 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
     clips = [int(torch.as_tensor(t).shape[0]) for t in tables]
     items_t, video_of, clip_of, row0 = batch_items(clips, len(views))
     items = (L.ViewItem * items_t.shape[0]).from_buffer_copy(items_t.numpy().tobytes())
-    src_dtype = L.PV_U16 if src_layout in YUV16_LAYOUTS else (L.PV_U8 if (is_yuv or dtype == torch.uint8) else L.PV_F32)
+    src_dtype = _src_codes(src_layout, dtype)[1]
     if not as_frames:
         return VideoBatch(videos, sources, items, items_t, cat, video_of, clip_of, clips, row0, len(views), src_dtype, upload)
     # the pointer table of the call: the frame addresses of video j from first[j] on; the records point into the DEVICE copy
@@ -710,34 +748,22 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
     the same launch (`pv_yuv_views`) by `yuv`: (standard, full_range) for `yuv_matrix`, or a 3 x 4 matrix.  With a layout of
     `YUV16_LAYOUTS` ("P010", "I010", ...) the clip is uint16 or int16 and read by `pv_yuv16_views`; a (standard, full_range)
     pair is composed with the layout's depth and bit alignment: `src_layout="P010", yuv=("bt2020", False)`."""
-    import ctypes as C
-    from . import _lib as L
     if src_layout not in ("NCTHW", "NTHWC") + _YUV_ANY:
         raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
     if dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("dtype is torch.bfloat16 or torch.float32")
     views = _views(spatial_idx)
     if src_layout in _YUV_ANY:
-        return _device_scale_crop_yuv(clip, short_side, crop_size, views, mean, std, div255, num_frames, dtype, src_layout,
+        return _device_scale_crop_yuv(clip, short_side, crop_size, views, (mean, std, div255), num_frames, dtype, src_layout,
                                       yuv, coded_height, height)
     _source_geometry(clip, src_layout)
     device = clip.device if clip.is_cuda else torch.device("cuda", torch.cuda.current_device())
     clip = _device_source(clip, device)
     d = _resample_desc(clip, src_layout, short_side, crop_size, views)
-    scale, shift = _affine(mean, std, div255, d.C, device)
-    index = None
     if num_frames is not None and num_frames != d.src_T:
         index = temporal_indices(d.src_T, num_frames).to(torch.int32).to(device)
         d.T, d.t_index = num_frames, index.data_ptr()
-    if scale is not None:
-        d.ch_scale, d.ch_shift = scale.data_ptr(), shift.data_ptr()
-    out = torch.empty((d.B * d.n_views, d.C, d.T, crop_size, crop_size), dtype=dtype, device=device)
-    d.dst, d.dst_layout = out.data_ptr(), L.DST_NCTHW
-    d.dst_dtype = L.PV_BF16 if dtype == torch.bfloat16 else L.PV_F32
-    with torch.cuda.device(device):
-        L.check(L.lib().pv_resample_crop(C.byref(d), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
-                "resample_crop")
-    return out
+    return _scale_crop_launch(d, "pv_resample_crop", "resample_crop", d.B, d.C, (mean, std, div255), dtype, device)
 
 
 class DevicePacker:
@@ -859,9 +885,7 @@ class DevicePacker:
         if b * len(self.views) != want:
             raise RuntimeError("deploy form was converted for a batch of %d = clips x views, got %d clips x %d views"
                                % (want, b, len(self.views)))
-        hn, wn = scaled_size(hs, ws, self.short_side)
-        if self.crop_size > hn or self.crop_size > wn:
-            raise RuntimeError("a %d crop does not fit the %d x %d frame scaled to %d x %d" % (self.crop_size, hs, ws, hn, wn))
+        hn, wn, _ = _view_geometry(hs, ws, self.short_side, self.crop_size, self.views)
         if self.src_layout == "NTHWC" and (c != 3 or clip.dtype != torch.uint8):
             raise RuntimeError("a frame-interleaved clip is uint8 [B,T,H,W,3], got %s %s" % (clip.dtype, tuple(clip.shape)))
         for ratio, ref in zip(self.frame_ratios, self.subs[0].refs if self.subs is not None else self.refs):
@@ -960,8 +984,7 @@ class DevicePacker:
             index = self._t_index(d.src_T, ref)
             if index is not None:
                 d.T, d.t_index = ref.T, index.data_ptr()
-            if self.scale is not None:
-                d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
+            _set_affine(d, self.scale, self.shift)
             self.sess.resample(d, ref, planar=self._planar_for(i, ref))
 
     def _planar_for(self, i, ref):
@@ -1011,20 +1034,8 @@ class DevicePacker:
             raise RuntimeError("fill_video resamples: construct the packer with short_side and crop_size")
         if getattr(self.model, "_pv_load_boxes", None) is not None:
             raise RuntimeError("a detection model takes boxes of key frames, not a video")
-        if self.is_yuv:
-            if not video.is_cuda:
-                raise RuntimeError("the %s frames are on the device" % self.src_layout)
-            geom = yuv_geometry(video, self.src_layout, self.coded_height, self.height)
-            c, nf, hs, ws = 3, geom["N"], geom["Hs"], geom["Ws"]
-        else:
-            c, nf, hs, ws = _video_geometry(video, self.src_layout)
-            if not video.is_cuda or not video.is_contiguous() or video.dtype not in (torch.uint8, torch.float32):
-                raise RuntimeError("the video is a contiguous uint8 or fp32 tensor on the device")
-        if self.src_layout == "NTHWC" and (c != 3 or video.dtype != torch.uint8):
-            raise RuntimeError("a frame-interleaved video is uint8 [N,H,W,3], got %s %s" % (video.dtype, tuple(video.shape)))
-        hn, wn = scaled_size(hs, ws, self.short_side)
-        if self.crop_size > hn or self.crop_size > wn:
-            raise RuntimeError("a %d crop does not fit the %d x %d frame scaled to %d x %d" % (self.crop_size, hs, ws, hn, wn))
+        c, nf, hs, ws, geom = _video_source(video, self.src_layout, torch.device(self.sess.device), self.coded_height, self.height)
+        source = (c, nf, hs, ws, geom, _view_geometry(hs, ws, self.short_side, self.crop_size, self.views))
         refs = self.subs[0].refs if self.subs is not None else self.refs
         if len(tables) != len(refs):
             raise RuntimeError("%d frame tables for %d input pathways" % (len(tables), len(refs)))
@@ -1038,10 +1049,10 @@ class DevicePacker:
             raise RuntimeError("items [%d, %d) are not a chunk of at most %d of the video's %d clips x views"
                                % (i0, i0 + n, self.batch, total))
         if self.subs is None:
-            return self._fill_video(video, tables, i0, n)
+            return self._fill_video(video, source, tables, i0, n)
         lo = 0
         for sub, b in zip(self.subs, self.model._splits):
-            sub._fill_video(video, tables, i0 + lo, max(0, min(b, n - lo)))
+            sub._fill_video(video, source, tables, i0 + lo, max(0, min(b, n - lo)))
             lo += b
 
     def launch(self):
@@ -1053,34 +1064,24 @@ class DevicePacker:
             self.sess.launch(use_graph=self.model._pv_use_graph)
         return self.model._pv_result()
 
-    def _fill_video(self, video, tables, item0, n_items):
-        """One pv_video_views launch per pathway into this plan's buffers; see Session.video_views for the tail."""
+    def _fill_video(self, video, source, tables, item0, n_items):
+        """One pv_video_views (YUV: pv_yuv_views / pv_yuv16_views) launch per pathway into this plan's buffers; `source` is
+        what `fill_video` found out about the video: `_video_source` and `_view_geometry`.  See Session.video_views for the
+        tail."""
         from . import _lib as L
         self._src = (video, tables)                        # alive until the launch has run
-        if self.is_yuv:
-            geom = yuv_geometry(video, self.src_layout, self.coded_height, self.height)
-            for i, (ref, tab) in enumerate(zip(self.refs, tables)):
-                d = _yuv_desc(video, geom, tab, self.yuv_matrix, self.short_side, self.crop_size, self.views)
-                d.item0, d.n_items = (item0, n_items) if n_items else (0, 0)
-                if self.scale is not None:
-                    d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
-                (self.sess.yuv16_views if self.is_yuv16 else self.sess.yuv_views)(d, ref, planar=self._planar_for(i, ref))
-            return
-        c, nf, hs, ws = _video_geometry(video, self.src_layout)
-        hn, wn = scaled_size(hs, ws, self.short_side)
+        c, nf, hs, ws, geom, geo = source
         for i, (ref, tab) in enumerate(zip(self.refs, tables)):
-            d = L.VideoViewsDesc()
-            d.src, d.t_index = video.data_ptr(), tab.data_ptr()
-            d.n_clips, d.C, d.T, d.N, d.t_stride, d.Hs, d.Ws = tab.shape[0], c, ref.T, nf, tab.stride(0), hs, ws
-            d.src_dtype = L.PV_U8 if video.dtype == torch.uint8 else L.PV_F32
-            d.src_layout = L.SRC_NCTHW if self.src_layout == "NCTHW" else L.SRC_NTHWC
-            d.Hn, d.Wn, d.Ho, d.Wo, d.n_views = hn, wn, self.crop_size, self.crop_size, len(self.views)
-            for k, v in enumerate(self.views):
-                d.y_off[k], d.x_off[k] = crop_offsets(hn, wn, self.crop_size, v)
+            if self.is_yuv:
+                d = _yuv_desc(video, geom, tab, self.yuv_matrix, self.short_side, self.crop_size, self.views, geo)
+                fill = self.sess.yuv16_views if self.is_yuv16 else self.sess.yuv_views
+            else:
+                d = _rgb_source(L.VideoViewsDesc(), video, self.src_layout, c, hs, ws, geo, self.crop_size)
+                d.t_index, d.n_clips, d.T, d.N, d.t_stride = tab.data_ptr(), tab.shape[0], ref.T, nf, tab.stride(0)
+                fill = self.sess.video_views
             d.item0, d.n_items = (item0, n_items) if n_items else (0, 0)
-            if self.scale is not None:
-                d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
-            self.sess.video_views(d, ref, planar=self._planar_for(i, ref))
+            _set_affine(d, self.scale, self.shift)
+            fill(d, ref, planar=self._planar_for(i, ref))
 
     # ------------------------------------------------------------------------- many videos per forward (pv_batch_views)
     def video_batch(self, videos, tables, height=None, coded_height=None):
@@ -1149,13 +1150,11 @@ class DevicePacker:
             d.items, d.items_dev = C.addressof(batch.items) + first, batch.items_dev.data_ptr() + first
             d.t_index, d.n_rows, d.t_stride = tab.data_ptr(), tab.shape[0], tab.stride(0)
             d.n_sources, d.n_items, d.C, d.T = len(batch.sources), n_items, ref.C, ref.T
-            d.src_dtype = batch.src_dtype
-            d.src_layout = L.SRC_YUV420 if self.is_yuv else (L.SRC_NCTHW if self.src_layout == "NCTHW" else L.SRC_NTHWC)
+            d.src_layout, d.src_dtype = _src_codes(self.src_layout, None)[0], batch.src_dtype
             if self.is_yuv:
                 d.c_step, d.yuv2rgb = (2 if self.src_layout in _YUV_INTERLEAVED else 1), self.yuv_matrix.data_ptr()
             d.Ho, d.Wo, d.n_views = self.window[0], self.window[1], len(self.views)
-            if self.scale is not None:
-                d.ch_scale, d.ch_shift = self.scale.data_ptr(), self.shift.data_ptr()
+            _set_affine(d, self.scale, self.shift)
             if f is None:
                 self.sess.batch_views(d, ref, planar=self._planar_for(i, ref))
                 continue

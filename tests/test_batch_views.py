@@ -126,6 +126,8 @@ def test_batch_views_rejects_invalid_launch_fields(pv_lib):
             assert _bad(keep, **{field: val}) == INV, (field, val)
     assert _bad(keep, T=2, t_stride=1) == INV                    # a row stride shorter than the row
     assert _bad(keep, n_items=65536) == INV                      # refused by the count, before any item is read
+    assert _bad(keep, T=65536, t_stride=65536) == INV            # more frames than grid.y holds
+    assert _bad(keep, T=65535, t_stride=65535) == UNS            # the positive control: the last count that fits
     # whatever pv_resample_crop rejects
     assert _bad(keep, C=5) == INV
     assert _bad(keep, C=0) == INV
