@@ -535,6 +535,30 @@ int pv_yuv16_views(const pv_yuv_views_desc* d, pv_stream_t stream);
  * destination alignment, n_views outside 1..3); for PV_SRC_YUV420, per such record, the plane checks of pv_yuv_views (odd sizes,
  * pitches, offsets, planes inside frame_stride) and C != 3.  PV_ERR_UNSUPPORTED: the dtype / layout matrix of
  * pv_resample_crop, and a staged strip beyond the kernels' LDS limit.
+ * Orientation:  a phone video recorded upright is STORED as landscape frames plus a display matrix ("rotate 90"), a front
+ *               camera adds a mirror, and a decoder hands out the stored frames.  pv_view_source.orient (the field that used
+ *               to be `reserved`: same offset and size, 0 in every record built before) = rot | (mirror << 2), rot 0..3,
+ *               mirror 0 / 1.  Hs, Ws, pitches, offsets and frame_stride keep describing the STORED frame S -- addresses
+ *               depend on them.  The DISPLAYED frame D is Hd x Wd = (rot & 1) ? Ws x Hs : Hs x Ws and, with
+ *               x' = mirror ? Wd-1-x : x,
+ *                   rot 0: D(y,x) = S(y, x')             the stored frame as it lies
+ *                   rot 1: D(y,x) = S(Hs-1-x', y)        turned 90 degrees clockwise: a decoder's "rotation 90"
+ *                   rot 2: D(y,x) = S(Hs-1-y, Ws-1-x')   turned 180 degrees
+ *                   rot 3: D(y,x) = S(x', Ws-1-y)        turned 270 degrees clockwise
+ *               -- torch.rot90(S, -rot, (h, w)), then .flip(w) if mirror.  Everything downstream is defined ON D: Hn, Wn
+ *               and the view windows are displayed coordinates, sy = (float)Hd / (float)Hn and sx = (float)Wd / (float)Wn
+ *               (the bit check uses these); the pinned coordinate, the blend order, the tap clamp of YUV, the affine map
+ *               and the single rounding are unchanged.  For YUV 4:2:0 the chroma of displayed pixel (y,x) is the chroma
+ *               sample of the stored pixel it maps to; Hs and Ws are even, so that is the Y, U and V planes oriented
+ *               separately.  Hence: AN ITEM OF AN ORIENTED RECORD HOLDS, BIT FOR BIT, WHAT THE SAME LAUNCH WRITES FOR A
+ *               DENSE COPY OF THE VIDEO THAT WAS ORIENTED BEFOREHAND, WITH orient = 0.  Honoured by pv_batch_views and
+ *               pv_frame_views in every source form, and by pv_box_views; one launch may mix orientations freely.  Items
+ *               of upright records run the staged-strip kernels exactly as before; items of oriented records run a tile
+ *               kernel (a workgroup stages the stored footprint of a tile of displayed rows x columns), each maximal run
+ *               of items of one kind as one kernel launch.  The one-source entry points (pv_resample_crop, pv_video_views,
+ *               pv_yuv_views, pv_yuv16_views) have no field for it.  PV_ERR_INVALID: orient outside 0..7; sy / sx whose
+ *               bits are not the displayed-size quotient; a window that leaves Hn x Wn.  PV_ERR_UNSUPPORTED: a staged
+ *               tile footprint beyond the LDS limit.
  */
 enum { PV_SRC_YUV420 = 2 };   /* pv_batch_views_desc.src_layout only, beside pv_resample_src_layout */
 typedef struct pv_view_source {      /* one decoded video; 96 bytes, 8-byte aligned */
@@ -545,8 +569,8 @@ typedef struct pv_view_source {      /* one decoded video; 96 bytes, 8-byte alig
   int32_t N, Hs, Ws;                 /* frames, frame size                                                     */
   int32_t Hn, Wn;                    /* size after scaling                                                     */
   int32_t y_off[3], x_off[3];        /* per view: window origin inside Hn x Wn                                 */
-  float   sy, sx;                    /* (float)Hs / (float)Hn, (float)Ws / (float)Wn, set by the caller        */
-  int32_t reserved;
+  float   sy, sx;                    /* (float)Hd / (float)Hn, (float)Wd / (float)Wn of the DISPLAYED frame    */
+  int32_t orient;                    /* rot | (mirror << 2): see "orientation" above; 0 = the stored frame    */
 } pv_view_source;
 typedef struct pv_view_item { int32_t source, row, view, reserved; } pv_view_item;   /* one destination item */
 typedef struct pv_batch_views_desc {
@@ -628,6 +652,14 @@ int pv_frame_views(const pv_frame_views_desc* d, pv_stream_t stream);
  *               -- clip_boxes_to_image, short_side_scale_with_boxes (ONE ratio, the longer side's, for x and y),
  *               crop_boxes and clip_boxes_to_image of the reference (transforms/functional.py:195-231,407-446), bit for
  *               bit what transforms.boxes_to_view gives on the host.
+ * Orientation:  boxes stay pixels of the STORED frame (what a detector that ran on decoder surfaces produces).  For a record
+ *               with orient != 0 the box is, after the optional clip_to_source, mapped into the displayed frame D in fp32,
+ *               every operation rounded on its own: a mirrored coordinate along an axis of stored length n is
+ *               t = (float)n - v; t = t - 1.0f (the reference's `width - boxes - 1` of horizontal_flip_with_boxes,
+ *               transforms/functional.py:380-404); rot 1: (x, y) -> (mirror_Hs(y), x); rot 2: (mirror_Ws(x), mirror_Hs(y));
+ *               rot 3: (y, mirror_Ws(x)); then the mirror bit: x -> mirror_Wd(x); the corners are re-ordered so that
+ *               x1' <= x2' and y1' <= y2'.  The three steps behind run with the displayed Hd / Wd.  Bit for bit
+ *               transforms.boxes_to_view(..., orientation=).  An orient outside 0..7 is read as orient & 7.
  * PV_ERR_INVALID: null boxes / box_item / sources_dev / items_dev / dst; capacity, n_items, Ho, Wo, n_sources <= 0;
  * n_views outside 1..3; n_launch < 0 or > capacity; box0 < 0 or box0 + n_launch > n_boxes; item0 < 0 or
  * item0 + n_items > n_seq.  n_launch == 0 is valid and writes only the tail.  Validation precedes every HIP call.

@@ -96,6 +96,9 @@ ViewSource = _struct("ViewSource", [
     ("src", _p), ("frame_stride", _i64), ("u_offset", _i64), ("v_offset", _i64)]
     + _ints("y_pitch", "c_pitch", "N", "Hs", "Ws", "Hn", "Wn") + [("y_off", _i32 * 3), ("x_off", _i32 * 3), ("sy", _f32), ("sx", _f32)]
     + _ints("reserved"))
+# pv_view_source.orient -- rot | (mirror << 2), the header's "Orientation" -- lies where `reserved` lay; the ctypes field keeps
+# its name (records built before hold 0 there) and `orient` reads and writes it.
+ViewSource.orient = property(lambda self: self.reserved, lambda self, code: setattr(self, "reserved", int(code)))
 ViewItem = _struct("ViewItem", _ints("source", "row", "view", "reserved"))
 BatchViewsDesc = _struct("BatchViewsDesc", [
     ("sources", _p), ("sources_dev", _p), ("items", _p), ("items_dev", _p), ("t_index", _p), ("dst", _p), ("ch_scale", _p),

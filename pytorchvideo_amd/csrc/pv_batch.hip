@@ -104,28 +104,35 @@ __global__ __launch_bounds__(kRsThreads) void batch_yuv16_kernel(const pv_batch_
 
 // Validation and sizing are rs_item_launch's (pv_rs.h); this entry point's own part is the record's `src`, one allocation:
 // 4-byte aligned for fp32, even for 16-bit samples (either dtype outside its layouts is refused before a record is read).
-int bv_run(const pv_batch_views_desc& d, pv_stream_t stream) {
+// Items of oriented records (orient != 0) are not for these kernels: rs_item_runs hands each run of them to the tile kernels.
+int bv_run(const pv_batch_views_desc& desc, pv_stream_t stream) {
   RsItemLaunch g;
-  size_t lds;
-  const uintptr_t misaligned = d.src_dtype == PV_F32 ? 3 : (d.src_dtype == PV_U16 ? 1 : 0);   // address bits `src` may not have
+  RsTileLaunch tg;
+  size_t lds, lds_t;
+  const uintptr_t misaligned = desc.src_dtype == PV_F32 ? 3 : (desc.src_dtype == PV_U16 ? 1 : 0);   // address bits `src` may not have
   auto check_src = [=](const pv_view_source& v) { return reinterpret_cast<uintptr_t>(v.src) & misaligned ? PV_ERR_INVALID : PV_OK; };
-  if (int e = rs_item_launch(d, check_src, g, lds)) return e;
-  const bool yuv = d.src_layout == PV_SRC_YUV420;
-  if (yuv && d.src_dtype == PV_U16) {
-    if (d.c_step == 2) RS_DISPATCH(batch_yuv16_kernel, 2);
-    else RS_DISPATCH(batch_yuv16_kernel, 1);
-  } else if (yuv) {
-    if (d.c_step == 2) RS_DISPATCH(batch_yuv_kernel, 2);
-    else RS_DISPATCH(batch_yuv_kernel, 1);
-  } else if (d.src_layout == PV_SRC_NTHWC) {
-    RS_DISPATCH(batch_views_kernel, unsigned char, true);
-  } else if (d.src_dtype == PV_U8) {
-    RS_DISPATCH(batch_views_kernel, unsigned char, false);
-  } else {
-    RS_DISPATCH(batch_views_kernel, float, false);
-  }
-  PV_LAUNCH_CHECK();
-  return PV_OK;
+  if (int e = rs_item_launch(desc, check_src, g, lds, tg, lds_t)) return e;
+  // the strips of a run of upright items: the whole launch when no record is oriented
+  auto upright = [&](const pv_batch_views_desc& d) -> int {
+    const bool yuv = d.src_layout == PV_SRC_YUV420;
+    if (yuv && d.src_dtype == PV_U16) {
+      if (d.c_step == 2) RS_DISPATCH(batch_yuv16_kernel, 2);
+      else RS_DISPATCH(batch_yuv16_kernel, 1);
+    } else if (yuv) {
+      if (d.c_step == 2) RS_DISPATCH(batch_yuv_kernel, 2);
+      else RS_DISPATCH(batch_yuv_kernel, 1);
+    } else if (d.src_layout == PV_SRC_NTHWC) {
+      RS_DISPATCH(batch_views_kernel, unsigned char, true);
+    } else if (d.src_dtype == PV_U8) {
+      RS_DISPATCH(batch_views_kernel, unsigned char, false);
+    } else {
+      RS_DISPATCH(batch_views_kernel, float, false);
+    }
+    PV_LAUNCH_CHECK();
+    return PV_OK;
+  };
+  auto oriented = [&](const pv_batch_views_desc& d) -> int { return pv_orient_launch(d, false, tg, lds_t, stream); };   // pv_orient.hip
+  return rs_item_runs(desc, upright, oriented);
 }
 
 }  // namespace

@@ -86,23 +86,29 @@ int fv_run(const pv_frame_views_desc& f, pv_stream_t stream) {
     return PV_OK;
   };
   RsItemLaunch g;
-  size_t lds;
-  if (int e = rs_item_launch(d, check_src, g, lds)) return e;
-  const bool yuv = d.src_layout == PV_SRC_YUV420;
-  if (yuv && d.src_dtype == PV_U16) {
-    return pv_frame_yuv16_launch(d, g, lds, stream);   // pv_frames16.hip
-  } else if (yuv) {
-    if (d.c_step == 2) RS_DISPATCH(frame_yuv_kernel, 2);
-    else RS_DISPATCH(frame_yuv_kernel, 1);
-  } else if (d.src_layout == PV_SRC_NTHWC) {
-    RS_DISPATCH(frame_views_kernel, unsigned char, true);
-  } else if (d.src_dtype == PV_U8) {
-    RS_DISPATCH(frame_views_kernel, unsigned char, false);
-  } else {
-    RS_DISPATCH(frame_views_kernel, float, false);
-  }
-  PV_LAUNCH_CHECK();
-  return PV_OK;
+  RsTileLaunch tg;
+  size_t lds, lds_t;
+  if (int e = rs_item_launch(f.batch, check_src, g, lds, tg, lds_t)) return e;
+  // the strips of a run of upright items: the whole launch when no record is oriented
+  auto upright = [&](const pv_batch_views_desc& d) -> int {
+    const bool yuv = d.src_layout == PV_SRC_YUV420;
+    if (yuv && d.src_dtype == PV_U16) {
+      return pv_frame_yuv16_launch(d, g, lds, stream);   // pv_frames16.hip
+    } else if (yuv) {
+      if (d.c_step == 2) RS_DISPATCH(frame_yuv_kernel, 2);
+      else RS_DISPATCH(frame_yuv_kernel, 1);
+    } else if (d.src_layout == PV_SRC_NTHWC) {
+      RS_DISPATCH(frame_views_kernel, unsigned char, true);
+    } else if (d.src_dtype == PV_U8) {
+      RS_DISPATCH(frame_views_kernel, unsigned char, false);
+    } else {
+      RS_DISPATCH(frame_views_kernel, float, false);
+    }
+    PV_LAUNCH_CHECK();
+    return PV_OK;
+  };
+  auto oriented = [&](const pv_batch_views_desc& d) -> int { return pv_orient_launch(d, true, tg, lds_t, stream); };   // pv_orient.hip
+  return rs_item_runs(f.batch, upright, oriented);
 }
 
 }  // namespace

@@ -4,6 +4,7 @@
 //   pv_batch.hip      pv_batch_views                      either, one source per destination item
 //   pv_frames.hip     pv_frame_views                      the same with every frame addressed through a pointer table
 //   pv_frames16.hip   (launched from pv_frames.hip)       the 16-bit YUV kernels of pv_frame_views
+//   pv_orient.hip     (launched from pv_batch.hip and pv_frames.hip)   the tile kernels of oriented records (orient != 0)
 // What they compute with is here, once: the pinned source coordinate, the destination forms with their stores, the taps and
 // blends, the two staged-strip bodies (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather) that the nine kernel templates
 // wrap (resample_crop_kernel; yuv_views_kernel, yuv16_views_kernel; batch_views_kernel, batch_yuv_kernel,
@@ -13,9 +14,13 @@
 // 16-bit codes of P010 / yuv420p10le (PV_U16 sources).  The files keep what differs: where a workgroup's geometry comes
 // from (the kernel wrappers), the validation of the one-source descriptors (rs_run, yuv_run) and, for the item-sourced two,
 // what a record's `src` must be.
-// Everything but RsItemLaunch is inline in an anonymous namespace: each translation unit keeps its own kernels.
+// Records with orient != 0 -- a video stored turned and / or mirrored -- have two bodies of their own, the staged tiles
+// (rs_tile_rgb, rs_tile_yuv), sized by rs_tile_size; rs_item_runs hands every run of items of one kind to its kernels.
+// Everything but RsItemLaunch, RsTileLaunch and pv_orient_launch is inline in an anonymous namespace: each translation unit
+// keeps its own kernels.
 #pragma once
 #include <cstring>
+#include <vector>
 
 #include "pv_common.h"
 
@@ -27,6 +32,18 @@ struct RsItemLaunch {
   int32_t pitch_c;    // YUV: LDS bytes per staged chroma (row, plane)
   int32_t c_base;     // YUV: LDS offset of the chroma image: 2 R pitch
 };
+
+// What stays per launch of a tile kernel (pv_orient.hip: items of oriented records): filled by rs_tile_size.
+struct RsTileLaunch {
+  int32_t TR, TC;       // displayed rows x columns per workgroup; TC a multiple of 8
+  int32_t tiles_x;      // tiles per window row
+  int32_t rows, pitch;  // staged stored rows, LDS bytes per staged (row, plane) -- YUV: luma
+  int32_t rows_c, pitch_c, c_base;   // YUV: staged chroma rows, LDS bytes per chroma (row, plane), LDS offset of the chroma image
+};
+
+// The tile kernels (pv_orient.hip) over the items of `d`, all of oriented records, on a launch rs_item_launch has validated
+// and sized; frames: `src` of a record is a slice of the pointer table of pv_frame_views.
+int pv_orient_launch(const pv_batch_views_desc& d, bool frames, const RsTileLaunch& g, size_t lds, pv_stream_t stream);
 
 namespace {
 
@@ -478,6 +495,281 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
   }
 }
 
+// ---- the staged tile: oriented records ---------------------------------------------------------------------------------
+// A record with orient != 0 (include/pv_mi355x.h: rot | mirror << 2) is resampled ON ITS DISPLAYED FRAME D: rs_coord runs on
+// Hd x Wd, and a tap at displayed (y, x) is stored pixel (r, c) = (r0 + ry y + rx x, c0 + cy y + cx x), one of y / x per
+// coordinate (rs_orient_map).  For rot & 1 an output row is a source COLUMN, so the strip's whole-row spans would degenerate
+// to a few bytes per staged row; the bodies below own a TILE instead: TR displayed rows x TC displayed columns (blockIdx.x,
+// row-major over the window) of one frame of one item.
+//   1. stage: the displayed rows / columns the tile's taps touch are contiguous ranges, and the map is monotone in each, so
+//      the stored footprint is one rectangle [sr0, sr1] x [sc0, sc1].  Its rows are copied to LDS in the source dtype as
+//      the strip copies a contiguous run: the aligned 16-byte granules that cover each row's span, the LDS image keeping the
+//      span's `addr & 15`.  YUV stages the chroma rectangle [sr0 >> 1, sr1 >> 1] x [sc0 >> 1, sc1 >> 1] behind the luma one.
+//      A square-ish tile keeps the staged rows of a transposing record several granules long.
+//   2. one barrier.
+//   3. gather: as in the strip a thread owns G x-adjacent displayed pixels of one row -- TC is a multiple of 8, so a group
+//      starts where the strip's groups start -- takes its taps from LDS through the map, every stored coordinate clamped
+//      into the staged rectangle, blends with the strip's own expressions and hands the group to rs_store_group.
+// The host sizes TR, TC, the staged rows and the LDS pitch(es) from the widest footprint over the records the launch's
+// oriented items name (rs_tile_size); a workgroup whose footprint exceeds them stages nothing and writes nothing.
+struct RsOrient { int r0, ry, rx, c0, cy, cx; };
+__host__ __device__ __forceinline__ RsOrient rs_orient_map(int orient, int Hs, int Ws) {
+  const int rot = orient & 3;
+  const int Wd = (rot & 1) ? Hs : Ws;
+  const int m0 = (orient & 4) ? Wd - 1 : 0, mx = (orient & 4) ? -1 : 1;   // x' = m0 + mx x
+  if (rot == 0) return RsOrient{0, 1, 0, m0, 0, mx};                       // S(y, x')
+  if (rot == 1) return RsOrient{Hs - 1 - m0, 0, -mx, 0, 1, 0};             // S(Hs-1-x', y)
+  if (rot == 2) return RsOrient{Hs - 1, -1, 0, Ws - 1 - m0, 0, -mx};       // S(Hs-1-y, Ws-1-x')
+  return RsOrient{m0, 0, mx, Ws - 1, -1, 0};                               // S(x', Ws-1-y)
+}
+
+__device__ __forceinline__ int rs_clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// The stored rectangle behind displayed rows [dy0, dy1] x columns [dx0, dx1], clamped into the stored frame.
+__host__ __device__ __forceinline__ void rs_tile_rect(const RsOrient& o, int dy0, int dy1, int dx0, int dx1, int Hs, int Ws, int& sr0,
+                                                      int& sr1, int& sc0, int& sc1) {
+  const int ra = o.r0 + o.ry * dy0 + o.rx * dx0, rb = o.r0 + o.ry * dy1 + o.rx * dx1;
+  const int ca = o.c0 + o.cy * dy0 + o.cx * dx0, cb = o.c0 + o.cy * dy1 + o.cx * dx1;
+  sr0 = ra < rb ? ra : rb, sr1 = ra < rb ? rb : ra, sc0 = ca < cb ? ca : cb, sc1 = ca < cb ? cb : ca;
+  sr0 = sr0 < 0 ? 0 : sr0, sc0 = sc0 < 0 ? 0 : sc0;
+  sr1 = sr1 > Hs - 1 ? Hs - 1 : sr1, sc1 = sc1 > Ws - 1 ? Ws - 1 : sc1;
+}
+
+// The displayed rows / columns [d0, d1] the taps of outputs [first, first + n) touch.
+__host__ __device__ __forceinline__ void rs_tile_range(float s, int first, int n, int n_in, int& d0, int& d1) {
+  int unused;
+  float lunused;
+  rs_coord(s, first, n_in, d0, unused, lunused);
+  rs_coord(s, first + n - 1, n_in, unused, d1, lunused);
+}
+
+// S / INTER / FORM / D: as rs_strip_rgb.
+template <typename S, bool INTER, int FORM, typename D>
+__device__ __forceinline__ void rs_tile_rgb(unsigned char* lds, const RsTileLaunch& g, const RsRgbSrc& s, int orient, const RsDst& d,
+                                            int zi, int t) {
+  constexpr int G = RsGroup<FORM, D>::G;
+  constexpr int XB = INTER ? 3 : (int)sizeof(S);   // bytes from one source column to the next
+  const int tid = threadIdx.x;
+  const int tile_y = blockIdx.x / g.tiles_x, tile_x = blockIdx.x - tile_y * g.tiles_x;
+  const int row0 = tile_y * g.TR, col0 = tile_x * g.TC;
+  const int nrows = min(g.TR, d.Ho - row0), ncols = min(g.TC, d.Wo - col0);
+  if (nrows <= 0 || ncols <= 0) return;
+  const int planes = INTER ? 1 : d.C;
+  const int pitch = g.pitch;
+  const int Hd = (orient & 1) ? s.Ws : s.Hs, Wd = (orient & 1) ? s.Hs : s.Ws;
+  const RsOrient o = rs_orient_map(orient, s.Hs, s.Ws);
+
+  int dy0, dy1, dx0, dx1, sr0, sr1, sc0, sc1;
+  rs_tile_range(s.sy, s.yoff + row0, nrows, Hd, dy0, dy1);
+  rs_tile_range(s.sx, s.xoff + col0, ncols, Wd, dx0, dx1);
+  rs_tile_rect(o, dy0, dy1, dx0, dx1, s.Hs, s.Ws, sr0, sr1, sc0, sc1);
+  const int nslots = sr1 - sr0 + 1;
+  const int span_bytes = (sc1 - sc0 + 1) * XB;
+  if (nslots > g.rows || span_bytes + 15 > pitch) return;
+
+  // byte address of column sc0 of stored row r of plane `pl` of the selected frame
+  const long row_bytes = (long)s.Ws * XB;
+  const long frame_bytes = (long)s.Hs * row_bytes;
+  const long first = (s.clip_frame0 + s.ts) * frame_bytes + (long)sc0 * XB;
+  const long plane_bytes = INTER ? 0 : (long)s.N * frame_bytes;
+  auto row_addr = [&](int r, int pl) -> uintptr_t { return s.src + first + (long)pl * plane_bytes + (long)r * row_bytes; };
+
+  // ---- stage -------------------------------------------------------------------------------------------------
+  const int cpr = pitch >> 4;                      // 16-byte chunks per staged row
+  const int total = nslots * planes * cpr;
+  for (int base = tid; base < total; base += kRsThreads * 4) {
+    u32x4 val[4];
+    int off[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = base + u * kRsThreads;
+      off[u] = -1;
+      if (idx < total) {
+        const int sp = idx / cpr, ch = idx - sp * cpr;
+        const int slot = sp / planes, pl = sp - slot * planes;
+        const uintptr_t a = row_addr(sr0 + slot, pl);
+        if (ch * 16 < (int)(a & 15) + span_bytes) {
+          val[u] = *reinterpret_cast<const u32x4*>((a & ~(uintptr_t)15) + (uintptr_t)ch * 16);
+          off[u] = sp * pitch + ch * 16;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (off[u] >= 0) *reinterpret_cast<u32x4*>(lds + off[u]) = val[u];
+  }
+  __syncthreads();
+
+  // ---- gather ------------------------------------------------------------------------------------------------
+  float sc[4], sh[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    sc[c] = (d.ch_scale && c < d.C) ? d.ch_scale[c] : 1.f;
+    sh[c] = (d.ch_scale && d.ch_shift && c < d.C) ? d.ch_shift[c] : 0.f;
+  }
+  // the low address bits of a staged row: 32-bit arithmetic keeps `addr & 15`
+  const unsigned rb32 = (unsigned)row_bytes, pb32 = (unsigned)plane_bytes, a32 = (unsigned)(s.src + first);
+  // LDS byte offset of the tap at displayed (iy, ix), plane pl (INTER: channel 0)
+  auto tap = [&](int iy, int ix, int pl) -> int {
+    const int r = rs_clampi(o.r0 + o.ry * iy + o.rx * ix, sr0, sr1), c = rs_clampi(o.c0 + o.cy * iy + o.cx * ix, sc0, sc1);
+    const int lo = (int)((a32 + (unsigned)pl * pb32 + (unsigned)r * rb32) & 15u);
+    return ((r - sr0) * planes + pl) * pitch + lo + (c - sc0) * XB;
+  };
+  const int gpr = (ncols + G - 1) / G;             // groups per tile row
+  const int items = nrows * gpr;
+  for (int it = tid; it < items; it += kRsThreads) {
+    const int r = it / gpr, gx = it - r * gpr;
+    const int y = row0 + r;
+    int i0y, i1y;
+    float ly1;
+    rs_coord(s.sy, s.yoff + y, Hd, i0y, i1y, ly1);
+    const float ly0 = 1.f - ly1;
+    const int x0 = col0 + gx * G;
+    float out[4][G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      const int x = min(x0 + j, d.Wo - 1);         // a group cut by the right edge recomputes the last column; not stored
+      int i0x, i1x;
+      float lx1;
+      rs_coord(s.sx, s.xoff + x, Wd, i0x, i1x, lx1);
+      const float lx0 = 1.f - lx1;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (c < d.C) {
+          const int pl = INTER ? 0 : c, cb = INTER ? c : 0;
+          const float p00 = rs_tap<S>(lds, tap(i0y, i0x, pl) + cb), p01 = rs_tap<S>(lds, tap(i0y, i1x, pl) + cb);
+          const float p10 = rs_tap<S>(lds, tap(i1y, i0x, pl) + cb), p11 = rs_tap<S>(lds, tap(i1y, i1x, pl) + cb);
+          const float v = ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11);
+          out[c][j] = v * sc[c] + sh[c];
+        } else {
+          out[c][j] = 0.f;
+        }
+      }
+    }
+    const int nvalid = min(G, d.Wo - x0);
+    rs_store_group<FORM, D, G>(d.dst, out, d.C, d.T, d.Ho, d.Wo, d.c_p, d.ld, d.bs, zi, t, y, x0, nvalid);
+  }
+}
+
+// CSTEP / FORM / D / SMP: as rs_strip_yuv.
+template <int CSTEP, int FORM, typename D, typename SMP>
+__device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaunch& g, const RsYuvSrc& s, int orient, const RsDst& d,
+                                            const float* yuv2rgb, int zi, int t) {
+  constexpr int G = RsGroup<FORM, D>::G;
+  constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
+  constexpr int SB = (int)sizeof(SMP);             // bytes from one luma column to the next
+  constexpr int CB = CSTEP * SB;                   // bytes from one chroma column to the next
+  const int tid = threadIdx.x;
+  const int tile_y = blockIdx.x / g.tiles_x, tile_x = blockIdx.x - tile_y * g.tiles_x;
+  const int row0 = tile_y * g.TR, col0 = tile_x * g.TC;
+  const int nrows = min(g.TR, d.Ho - row0), ncols = min(g.TC, d.Wo - col0);
+  if (nrows <= 0 || ncols <= 0) return;
+  const int pitch_y = g.pitch, pitch_c = g.pitch_c, c_base = g.c_base;
+  const int Hd = (orient & 1) ? s.Ws : s.Hs, Wd = (orient & 1) ? s.Hs : s.Ws;
+  const RsOrient o = rs_orient_map(orient, s.Hs, s.Ws);
+
+  int dy0, dy1, dx0, dx1, sr0, sr1, sc0, sc1;
+  rs_tile_range(s.sy, s.yoff + row0, nrows, Hd, dy0, dy1);
+  rs_tile_range(s.sx, s.xoff + col0, ncols, Wd, dx0, dx1);
+  rs_tile_rect(o, dy0, dy1, dx0, dx1, s.Hs, s.Ws, sr0, sr1, sc0, sc1);
+  const int cr0 = sr0 >> 1, cc0 = sc0 >> 1;
+  const int nslots = sr1 - sr0 + 1, ncslots = (sr1 >> 1) - cr0 + 1;
+  const int span_y = (sc1 - sc0 + 1) * SB;
+  const int span_c = ((sc1 >> 1) - cc0 + 1) * CB;
+  if (nslots > g.rows || ncslots > g.rows_c || span_y + 15 > pitch_y || span_c + 15 > pitch_c) return;
+
+  const uintptr_t frame = s.src + s.frame_off;
+  auto y_addr = [&](int r) -> uintptr_t { return frame + (long)r * s.y_pitch + sc0 * SB; };
+  auto c_addr = [&](int cr, int pl) -> uintptr_t {
+    return frame + (pl == 0 ? s.c_off_a : s.c_off_b) + (long)cr * s.c_pitch + (long)cc0 * CB;
+  };
+
+  // ---- stage -------------------------------------------------------------------------------------------------
+  const int cpr_y = pitch_y >> 4, cpr_c = pitch_c >> 4;   // 16-byte chunks per staged row
+  const int total_y = nslots * cpr_y;
+  const int total = total_y + ncslots * CP * cpr_c;
+  for (int base = tid; base < total; base += kRsThreads * 4) {
+    u32x4 val[4];
+    int off[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = base + u * kRsThreads;
+      off[u] = -1;
+      if (idx < total) {
+        const bool luma = idx < total_y;
+        const int j = luma ? idx : idx - total_y;
+        const int cpr = luma ? cpr_y : cpr_c;
+        const int sp = j / cpr, ch = j - sp * cpr;             // luma: sp = slot; chroma: sp = slot * CP + plane
+        const int slot = luma ? sp : sp / CP, pl = luma ? 0 : sp - slot * CP;
+        const uintptr_t a = luma ? y_addr(sr0 + slot) : c_addr(cr0 + slot, pl);
+        if (ch * 16 < (int)(a & 15) + (luma ? span_y : span_c)) {
+          val[u] = *reinterpret_cast<const u32x4*>((a & ~(uintptr_t)15) + (uintptr_t)ch * 16);
+          off[u] = (luma ? sp * pitch_y : c_base + sp * pitch_c) + ch * 16;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (off[u] >= 0) *reinterpret_cast<u32x4*>(lds + off[u]) = val[u];
+  }
+  __syncthreads();
+
+  // ---- gather ------------------------------------------------------------------------------------------------
+  float m[12], sc[3], sh[3];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) m[i] = yuv2rgb[i];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    sc[c] = d.ch_scale ? d.ch_scale[c] : 1.f;
+    sh[c] = (d.ch_scale && d.ch_shift) ? d.ch_shift[c] : 0.f;
+  }
+  // the low address bits of a staged row: 32-bit arithmetic keeps `addr & 15`
+  const unsigned ya32 = (unsigned)(frame + sc0 * SB), yp32 = (unsigned)s.y_pitch, cp32 = (unsigned)s.c_pitch;
+  const unsigned ua32 = (unsigned)(frame + s.c_off_a + (long)cc0 * CB), va32 = (unsigned)(frame + s.c_off_b + (long)cc0 * CB);
+  // LDS byte offsets of the Y, U and V samples of the tap at displayed (iy, ix)
+  auto tap = [&](int iy, int ix, int& oy, int& ou, int& ov) {
+    const int r = rs_clampi(o.r0 + o.ry * iy + o.rx * ix, sr0, sr1), c = rs_clampi(o.c0 + o.cy * iy + o.cx * ix, sc0, sc1);
+    oy = (r - sr0) * pitch_y + (int)((ya32 + (unsigned)r * yp32) & 15u) + (c - sc0) * SB;
+    const int cr = r >> 1, co = ((c >> 1) - cc0) * CB, crow = c_base + (cr - cr0) * CP * pitch_c;
+    ou = crow + (int)((ua32 + (unsigned)cr * cp32) & 15u) + s.u_byte + co;
+    ov = crow + (CP - 1) * pitch_c + (int)((va32 + (unsigned)cr * cp32) & 15u) + s.v_byte + co;
+  };
+  const int gpr = (ncols + G - 1) / G;             // groups per tile row
+  const int items = nrows * gpr;
+  for (int it = tid; it < items; it += kRsThreads) {
+    const int r = it / gpr, gx = it - r * gpr;
+    const int y = row0 + r;
+    int i0y, i1y;
+    float ly1;
+    rs_coord(s.sy, s.yoff + y, Hd, i0y, i1y, ly1);
+    const float ly0 = 1.f - ly1;
+    const int x0 = col0 + gx * G;
+    float out[4][G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      const int x = min(x0 + j, d.Wo - 1);         // a group cut by the right edge recomputes the last column; not stored
+      int i0x, i1x;
+      float lx1;
+      rs_coord(s.sx, s.xoff + x, Wd, i0x, i1x, lx1);
+      const float lx0 = 1.f - lx1;
+      int y00, u00, v00, y10, u10, v10, y01, u01, v01, y11, u11, v11;   // (displayed row, column) of the tap
+      tap(i0y, i0x, y00, u00, v00);
+      tap(i1y, i0x, y10, u10, v10);
+      tap(i0y, i1x, y01, u01, v01);
+      tap(i1y, i1x, y11, u11, v11);
+      f32x2 p0[3], p1[3];                          // {row i0y, row i1y} of column i0x / i1x, per channel
+      yuv_tap2<SMP>(m, lds, y00, u00, v00, y10, u10, v10, p0);
+      yuv_tap2<SMP>(m, lds, y01, u01, v01, y11, u11, v11, p1);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) out[c][j] = yuv_blend(ly0, ly1, lx0, lx1, p0[c], p1[c], sc[c], sh[c]);
+      out[3][j] = 0.f;
+      // finish this pixel before the next one starts (as in rs_strip_yuv)
+      asm volatile("" : "+v"(out[0][j]), "+v"(out[1][j]), "+v"(out[2][j]));
+    }
+    rs_store_group<FORM, D, G>(d.dst, out, 3, d.T, d.Ho, d.Wo, d.c_p, d.ld, d.bs, zi, t, y, x0, min(G, d.Wo - x0));
+  }
+}
+
 // ---- the launch arithmetic shared by the entry points ---------------------------------------------------------------
 // Folds the widest source column span of a record's views into `span`, and the chroma span behind it into `span_c`, both in
 // columns: times the bytes of a column (rs_yuv_pitches for YUV) they size the staged rows.
@@ -606,8 +898,10 @@ inline bool rs_same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof(f
 template <typename CheckSrc>
 inline int rs_check_record(const pv_batch_views_desc& d, const pv_view_source& v, bool yuv, const CheckSrc& check_src) {
   if (!v.src || v.N <= 0 || v.Hs <= 0 || v.Ws <= 0 || v.Hn <= 0 || v.Wn <= 0) return PV_ERR_INVALID;
+  if (v.orient < 0 || v.orient > 7) return PV_ERR_INVALID;
   if (int e = rs_check_views(d.n_views, v.y_off, v.x_off, d.Ho, d.Wo, v.Hn, v.Wn)) return e;
-  if (!rs_same_bits(v.sy, (float)v.Hs / (float)v.Hn) || !rs_same_bits(v.sx, (float)v.Ws / (float)v.Wn)) return PV_ERR_INVALID;
+  const int Hd = (v.orient & 1) ? v.Ws : v.Hs, Wd = (v.orient & 1) ? v.Hs : v.Ws;   // the displayed frame: Hn, Wn and the windows are its
+  if (!rs_same_bits(v.sy, (float)Hd / (float)v.Hn) || !rs_same_bits(v.sx, (float)Wd / (float)v.Wn)) return PV_ERR_INVALID;
   if (yuv) {
     const int sb = d.src_dtype == PV_U16 ? 2 : 1;
     if (int e = rs_check_yuv_planes(v.Hs, v.Ws, d.c_step, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset, sb)) return e;
@@ -622,8 +916,70 @@ inline int rs_check_record(const pv_batch_views_desc& d, const pv_view_source& v
 // into range and the items are the validated ones), so its cost does not grow with the number of videos of the whole
 // sequence; a video-major sequence names the record just checked, which is not checked again, and any other record named
 // again is, which is cheaper than remembering.  The widest column span(s) of any such record x view size the staged rows.
+// The widest stored footprint of a TR x TC tile of oriented record v over its views: stored rows x columns, and the chroma
+// rows x columns behind them.  The map takes displayed rows to one stored axis and displayed columns to the other, so the
+// bands of tile rows and of tile columns are walked separately, with the very calls the kernel makes.
+inline void rs_tile_footprint(const pv_view_source& v, int n_views, int Ho, int Wo, int TR, int TC, int (&n)[4]) {
+  const bool turned = v.orient & 1;
+  const int Hd = turned ? v.Ws : v.Hs, Wd = turned ? v.Hs : v.Ws;
+  const RsOrient o = rs_orient_map(v.orient, v.Hs, v.Ws);
+  auto fold = [&](int lo, int hi, bool rows) {     // a stored interval of rows / of columns
+    const int a = hi - lo + 1, c = (hi >> 1) - (lo >> 1) + 1;
+    int& na = n[rows ? 0 : 1];
+    int& nc = n[rows ? 2 : 3];
+    na = a > na ? a : na, nc = c > nc ? c : nc;
+  };
+  for (int view = 0; view < n_views; ++view) {
+    int d0, d1, sr0, sr1, sc0, sc1;
+    for (int row0 = 0; row0 < Ho; row0 += TR) {
+      rs_tile_range(v.sy, v.y_off[view] + row0, TR < Ho - row0 ? TR : Ho - row0, Hd, d0, d1);
+      rs_tile_rect(o, d0, d1, 0, 0, v.Hs, v.Ws, sr0, sr1, sc0, sc1);
+      turned ? fold(sc0, sc1, false) : fold(sr0, sr1, true);
+    }
+    for (int col0 = 0; col0 < Wo; col0 += TC) {
+      rs_tile_range(v.sx, v.x_off[view] + col0, TC < Wo - col0 ? TC : Wo - col0, Wd, d0, d1);
+      rs_tile_rect(o, 0, 0, d0, d1, v.Hs, v.Ws, sr0, sr1, sc0, sc1);
+      turned ? fold(sr0, sr1, true) : fold(sc0, sc1, false);
+    }
+  }
+}
+
+// TR x TC, the staged rows and the LDS pitch(es) of a tile launch over `records` (the oriented records the launch's items
+// name): the largest tile of the list whose widest footprint fits the staging budget, else the smallest one if it fits the
+// LDS limit.  Tiles are square-ish so that the staged rows of a transposing record stay several 16-byte granules long.
+inline int rs_tile_size(const pv_batch_views_desc& d, const pv_view_source* const* records, size_t n_records, RsTileLaunch& g,
+                        size_t& lds) {
+  static const int tiles[][2] = {{32, 32}, {16, 32}, {16, 16}, {8, 16}, {8, 8}, {4, 8}, {2, 8}, {1, 8}};
+  const bool yuv = d.src_layout == PV_SRC_YUV420, inter = d.src_layout == PV_SRC_NTHWC;
+  const int sb = d.src_dtype == PV_U16 ? 2 : 1;
+  for (size_t k = 0; k < sizeof(tiles) / sizeof(tiles[0]); ++k) {
+    const int TR = tiles[k][0], TC = tiles[k][1];
+    int n[4] = {0, 0, 0, 0};
+    for (size_t i = 0; i < n_records; ++i) rs_tile_footprint(*records[i], d.n_views, d.Ho, d.Wo, TR, TC, n);
+    g = {};
+    g.TR = TR, g.TC = TC, g.tiles_x = (int32_t)pv_ceil_div(d.Wo, TC);
+    g.rows = n[0], g.rows_c = n[2];
+    long bytes;
+    if (yuv) {
+      rs_yuv_pitches(n[1], n[3], d.c_step, sb, g.pitch, g.pitch_c);
+      g.c_base = g.rows * g.pitch;
+      bytes = (long)g.c_base + (long)g.rows_c * (d.c_step == 2 ? 1 : 2) * g.pitch_c;
+    } else {
+      g.pitch = pv_round_up(n[1] * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
+      bytes = (long)g.rows * (inter ? 1 : d.C) * g.pitch;
+    }
+    lds = (size_t)bytes;
+    if (bytes <= kRsLdsBudget) return PV_OK;
+    if (k + 1 == sizeof(tiles) / sizeof(tiles[0])) return bytes <= kRsLdsMax ? PV_OK : PV_ERR_UNSUPPORTED;
+  }
+  return PV_ERR_UNSUPPORTED;
+}
+
+// Items of upright records (orient == 0) run the staged strip, items of oriented records the staged tile: g / lds size the
+// first kind exactly as before (g.R == 0: the launch has none), tg / lds_t the second (tg.TR == 0: none).
 template <typename CheckSrc>
-inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_src, RsItemLaunch& g, size_t& lds) {
+inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_src, RsItemLaunch& g, size_t& lds, RsTileLaunch& tg,
+                          size_t& lds_t) {
   if (!d.sources || !d.sources_dev || !d.items || !d.items_dev || !d.t_index || !d.dst) return PV_ERR_INVALID;
   if (d.n_sources <= 0 || d.n_items <= 0 || d.n_rows <= 0 || d.T <= 0 || d.C <= 0 || d.Ho <= 0 || d.Wo <= 0) return PV_ERR_INVALID;
   if (d.t_stride < d.T || d.n_items > 65535 || d.T > 65535) return PV_ERR_INVALID;   // grid.y / grid.z
@@ -636,17 +992,28 @@ inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_sr
   // the dtype / layout matrix
   if (yuv ? (d.src_dtype != PV_U8 && d.src_dtype != PV_U16) : (d.src_dtype != PV_U8 && d.src_dtype != PV_F32)) return PV_ERR_UNSUPPORTED;
   if (int e = rs_check_dst(d.dst, d.dst_layout, d.dst_dtype, d.c_p, d.ld, d.bs, d.T, d.Ho, d.Wo)) return e;
-  int span = 0, span_c = 0;
+  int span = 0, span_c = 0, n_upright = 0;
+  std::vector<const pv_view_source*> oriented;     // the oriented records the items name, a video-major run once
   for (int i = 0; i < d.n_items; ++i) {
     const pv_view_item& it = d.items[i];
     if (it.source < 0 || it.source >= d.n_sources || it.row < 0 || it.row >= d.n_rows || it.view < 0 || it.view >= d.n_views)
       return PV_ERR_INVALID;
     const pv_view_source& v = d.sources[it.source];
-    if (i == 0 || it.source != d.items[i - 1].source)   // a video-major sequence names the record just checked
+    const bool again = i > 0 && it.source == d.items[i - 1].source;   // a video-major sequence names the record just checked
+    if (!again)
       if (int e = rs_check_record(d, v, yuv, check_src)) return e;
+    if (v.orient != 0) {
+      if (!again) oriented.push_back(&v);
+      continue;
+    }
+    ++n_upright;
     rs_widest_span(v.sx, v.x_off, d.n_views, d.Wo, v.Ws, span, span_c);
   }
-  g = {};
+  g = {}, tg = {};
+  lds = lds_t = 0;
+  if (!oriented.empty())
+    if (int e = rs_tile_size(d, oriented.data(), oriented.size(), tg, lds_t)) return e;
+  if (n_upright == 0) return PV_OK;
   long per_row;                                    // LDS bytes of the two source rows of one output row
   if (yuv) {
     per_row = rs_yuv_pitches(span, span_c, d.c_step, d.src_dtype == PV_U16 ? 2 : 1, g.pitch, g.pitch_c);
@@ -656,6 +1023,25 @@ inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_sr
   }
   if (int e = rs_strip_rows(per_row, d.Ho, g.R, lds)) return e;
   g.c_base = 2 * g.R * g.pitch;
+  return PV_OK;
+}
+
+// The launches of a validated item sequence: every maximal run of items of one kind -- upright records, oriented records --
+// is one call of `upright` / `oriented` with a descriptor whose items, item count and destination are the run's (item i of a
+// launch is written to position i of dst).  A launch of upright records only is one call with the descriptor itself.
+template <typename Upright, typename Oriented>
+inline int rs_item_runs(const pv_batch_views_desc& d, const Upright& upright, const Oriented& oriented) {
+  const long item_bytes = (d.dst_dtype == PV_BF16 ? 2L : 4L) * (d.dst_layout == PV_DST_NCTHW ? (long)d.C * d.T * d.Ho * d.Wo : (long)d.bs);
+  for (int i = 0; i < d.n_items;) {
+    const bool turned = d.sources[d.items[i].source].orient != 0;
+    int j = i + 1;
+    while (j < d.n_items && (d.sources[d.items[j].source].orient != 0) == turned) ++j;
+    pv_batch_views_desc r = d;
+    r.items += i, r.items_dev += i, r.n_items = j - i;
+    r.dst = static_cast<unsigned char*>(d.dst) + (long)i * item_bytes;
+    if (int e = turned ? oriented(r) : upright(r)) return e;
+    i = j;
+  }
   return PV_OK;
 }
 

@@ -31,6 +31,16 @@ from .ensemble import VideoEnsembler
 from .transforms import DevicePacker, FrameList, batch_chunks, temporal_indices
 
 
+def _resident(video, device, is_yuv):
+    """The video on the device in a dtype the ingest reads: YUV frames are read in place, with the strides they have."""
+    video = video.to(device, non_blocking=True)
+    if is_yuv:
+        return video
+    if video.dtype not in (torch.uint8, torch.float32):
+        video = video.float()
+    return video.contiguous()
+
+
 class VideoPredictor:
     """`VideoPredictor(deployed, clip_sampler, mean, std, div255, short_side, crop_size)(video, fps)` = [num_classes] fp32
     scores of the video: softmax of every view of every clip, summed (`method="sum"`) or maxed ("max") and divided by the
@@ -45,6 +55,8 @@ class VideoPredictor:
     the same video again without that, keep `packer.video_tables(...)` and drive `packer.fill_video` / `launch` directly.
     `video` may also be a `transforms.FrameList` (one device tensor per frame): it is walked as a one-video batch
     (`packer.video_batch` / `fill_batch`, `pv_frame_views`), the same items at the same batch positions.
+    `orientation` (`transforms.orientation_code`): the video is STORED turned and / or mirrored, as a decoder hands out a
+    portrait phone clip; a non-zero code walks it as a one-video batch too and reads it in place.
     After a call `video_ensembler.counts` (and `clip_ensembler.counts`) hold the rows folded."""
 
     def __init__(self, deployed, clip_sampler, mean, std, div255, short_side, crop_size, spatial_idx=(0, 1, 2),
@@ -60,11 +72,11 @@ class VideoPredictor:
         self.video_ensembler = self.clip_ensembler = None
 
     @torch.no_grad()
-    def __call__(self, video, fps, return_clip_scores=False):
+    def __call__(self, video, fps, return_clip_scores=False, orientation=0):
         p = self.packer
         device = p.sess.device
-        if isinstance(video, FrameList):
-            return self._call_frames(video, fps, return_clip_scores)
+        if isinstance(video, FrameList) or orientation:
+            return self._call_frames(video, fps, return_clip_scores, orientation)
         if video.dim() != (3 if p.is_yuv else 4):
             raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(video.shape)))
         num_frames = video.shape[1] if self.src_layout == "NCTHW" else video.shape[0]
@@ -92,12 +104,20 @@ class VideoPredictor:
         scores = self.video_ensembler.result()[0]
         return (scores, self.clip_ensembler.result()) if return_clip_scores else scores
 
-    def _call_frames(self, frames, fps, return_clip_scores):
-        """A FrameList: the loop of `__call__` over a one-video batch."""
+    def _call_frames(self, frames, fps, return_clip_scores, orientation=0):
+        """A FrameList, or a video stored turned / mirrored (the one-source ingest has no orientation): the loop of `__call__`
+        over a one-video batch."""
         p = self.packer
         device = p.sess.device
-        table, _ = clip_frame_table(self.sampler, len(frames), fps, p.clip_frames)
-        batch = p.video_batch([frames], [table])                 # every check, and the one upload
+        if isinstance(frames, FrameList):
+            num_frames = len(frames)
+        else:
+            if frames.dim() != (3 if p.is_yuv else 4):
+                raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(frames.shape)))
+            num_frames = frames.shape[1] if self.src_layout == "NCTHW" else frames.shape[0]
+            frames = _resident(frames, device, p.is_yuv)
+        table, _ = clip_frame_table(self.sampler, num_frames, fps, p.clip_frames)
+        batch = p.video_batch([frames], [table], orientation=orientation)    # every check, and the one upload
         zeros = torch.zeros(p.batch, dtype=torch.int32, device=device)
         for i0, n in batch_chunks(batch.total, p.batch):
             p.fill_batch(batch, i0, n)
@@ -120,8 +140,9 @@ class VideoBatchPredictor:
     YUV layout `height` / `coded_height` of the call are one number or one per video); `fps` is one number or one per video.  The views of all videos form one video-major sequence that is
     walked in chunks of the deploy batch, so a forward holds views of several videos and only the LAST forward of a call can
     be short; the frame tables of all videos are built, range-checked and uploaded once per call.
-    `return_clip_scores=True` adds a list of V tensors [n_clips_j, num_classes].  After a call `video_ensembler.counts`
-    holds the views folded per video (and `clip_ensembler.counts` per clip, all videos' clips one after another)."""
+    `return_clip_scores=True` adds a list of V tensors [n_clips_j, num_classes].  `orientation` is one code
+    (`transforms.orientation_code`) or one per video: videos stored turned and / or mirrored are read in place.  After a call
+    `video_ensembler.counts` holds the views folded per video (and `clip_ensembler.counts` per clip, all videos' clips one after another)."""
 
     def __init__(self, deployed, clip_sampler, mean, std, div255, short_side, crop_size, spatial_idx=(0, 1, 2),
                  frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False)):
@@ -136,7 +157,7 @@ class VideoBatchPredictor:
         self.forwards = 0                                        # forwards of the last call
 
     @torch.no_grad()
-    def __call__(self, videos, fps, return_clip_scores=False, height=None, coded_height=None):
+    def __call__(self, videos, fps, return_clip_scores=False, height=None, coded_height=None, orientation=None):
         p = self.packer
         device = p.sess.device
         videos = list(videos)
@@ -155,7 +176,7 @@ class VideoBatchPredictor:
                 raise RuntimeError("video %d: expected a %d-d %s video, got %s" % (j, dims, self.src_layout, tuple(video.shape)))
             num_frames = video.shape[1] if self.src_layout == "NCTHW" else video.shape[0]
             tables.append(clip_frame_table(self.sampler, num_frames, rate, p.clip_frames)[0])
-        batch = p.video_batch(videos, tables, height, coded_height)      # every check, and the one upload
+        batch = p.video_batch(videos, tables, height, coded_height, orientation)    # every check, and the one upload
         self.forwards = 0
         for i0, n in batch_chunks(batch.total, p.batch):
             p.fill_batch(batch, i0, n)
@@ -213,7 +234,9 @@ class KeyframeDetector:
     video must then scale to the deploy form's H x W (256 x 455 for 720p at short_side 256).  With `crop_size` the view is the
     `spatial_idx` crop and the boxes follow it as `DevicePacker(dm)(clip, bboxes)` moves them.  `video`, `src_layout`, `yuv`,
     `coded_height`, `height` as for `VideoPredictor` (YUV 4:2:0 and `transforms.FrameList` included); `video` may also be a
-    LIST of videos, with `timestamps` and `boxes` given per video and `fps` one number or one per video.
+    LIST of videos, with `timestamps` and `boxes` given per video and `fps` one number or one per video.  `orientation` is one
+    code (`transforms.orientation_code`) or one per video: the video is stored turned and / or mirrored and the boxes are
+    pixels of the STORED frame (a detector that ran on the decoder's surfaces); `pv_box_views` takes them into the view.
 
     Frame tables, the box list and its key-frame index are uploaded once per call; per forward there are only the ingest,
     one `pv_box_views` launch and the replay.  The key frames are walked by `keyframe_chunks`.  Everything is validated
@@ -236,7 +259,7 @@ class KeyframeDetector:
         self.forwards, self.chunks = 0, []
 
     @torch.no_grad()
-    def __call__(self, video, fps, timestamps, boxes, height=None, coded_height=None):
+    def __call__(self, video, fps, timestamps, boxes, height=None, coded_height=None, orientation=None):
         p = self.packer
         device = torch.device(p.sess.device)
         if isinstance(video, (list, tuple)):
@@ -252,7 +275,9 @@ class KeyframeDetector:
         def per_video(x):
             return list(x) if isinstance(x, (list, tuple)) else [x] * len(videos)
 
-        heights, coded = per_video(height), per_video(coded_height)
+        heights, coded, orients = per_video(height), per_video(coded_height), per_video(orientation)
+        if not (len(heights) == len(coded) == len(orients) == len(videos)):
+            raise ValueError("height, coded_height and orientation are one value or one per video")
         kept, tables, counts, flat = [], [], [], []
         for j, (vid, rate, ts, bl) in enumerate(zip(videos, rates, stamps, box_lists)):
             as_frames = isinstance(vid, FrameList)               # its frames are checked by video_batch, and never moved
@@ -277,7 +302,7 @@ class KeyframeDetector:
                 if vid.dtype not in (torch.uint8, torch.float32):
                     vid = vid.float()
                 vid = vid.contiguous()
-            kept.append((vid, heights[j], coded[j]))
+            kept.append((vid, heights[j], coded[j], orients[j]))
             tables.append(table[rows])
             flat.extend(bl[k] for k in rows)
         chunks = keyframe_chunks(counts, p.batch, p.box_capacity)    # ValueError before any launch
@@ -286,8 +311,9 @@ class KeyframeDetector:
         out = torch.zeros((sum(counts), classes), dtype=torch.float32, device=device)
         if not chunks:
             return out
-        batch = p.video_batch([v for v, _, _ in kept], tables, [h for _, h, _ in kept] if height is not None else None,
-                              [c for _, _, c in kept] if coded_height is not None else None)   # every check, one upload
+        batch = p.video_batch([k[0] for k in kept], tables, [k[1] for k in kept] if height is not None else None,
+                              [k[2] for k in kept] if coded_height is not None else None,
+                              [k[3] for k in kept] if orientation is not None else None)   # every check, one upload
         full = [c for c in counts if c > 0]                      # boxes per item of the sequence
         boxes_dev = torch.cat([b.detach().to(device=device, dtype=torch.float32) for b in flat]).contiguous()
         box_item = torch.repeat_interleave(torch.arange(len(full), dtype=torch.int32), torch.tensor(full)).to(device)
@@ -361,18 +387,19 @@ class StreamPredictor:
     and returns without waiting.  A decoder may therefore recycle a surface once the scores of the LAST window that contains
     it have been read on the host, or after a synchronise on the launch stream -- not when `push` returns.
 
+    `orientation` (`transforms.orientation_code`): the frames are stored turned and / or mirrored and are read in place.
     `deployed` is a classification form; one object scores one stream; `reset()` starts a new one.  Windows are scored
     independently: nothing is smoothed or voted over windows."""
 
     def __init__(self, deployed, clip_duration, stride, fps, mean, std, div255, short_side, crop_size, spatial_idx=(1,),
-                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False)):
+                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), orientation=0):
         if getattr(deployed, "_pv_load_boxes", None) is not None:
             raise ValueError("StreamPredictor scores the windows of a stream with a classification form; a detection model's "
                              "boxes belong to key frames: KeyframeDetector")
         if method not in ("sum", "max"):
             raise NotImplementedError("ensemble method %r (the reference knows 'sum' and 'max')" % method)
         self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv)
-        self.method, self.src_layout = method, src_layout
+        self.method, self.src_layout, self.orientation = method, src_layout, orientation   # a stream has one orientation
         self.state = StreamState(clip_duration, stride, fps)
         self._frames = []
         self.forwards = 0                                        # forwards of the last push
@@ -404,7 +431,7 @@ class StreamPredictor:
         if windows:
             t = p.clip_frames
             table = torch.stack([first - base + temporal_indices(stop - first, t) for _, _, first, stop in windows]).to(torch.int32)
-            batch = p.video_batch([held], [table])               # every check, and the one upload: entries count from `base`
+            batch = p.video_batch([held], [table], orientation=self.orientation)   # every check, the one upload: entries count from `base`
         self._frames = held.frames                               # nothing was refused: the push counts
         st.push(len(new))                                        # the same windows: stream_windows is pure
         out = []

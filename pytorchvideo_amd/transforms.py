@@ -30,6 +30,7 @@ the box mirrors above, and `inference.KeyframeDetector` the loop around it.
 """
 import copy
 import math
+import operator
 from typing import Dict, Sequence, Tuple
 
 import torch
@@ -162,17 +163,88 @@ def uniform_crop_with_boxes(images: torch.Tensor, size: int, spatial_idx: int,
     return cropped, clip_boxes_to_image(crop_boxes(boxes, x, y), cropped.shape[-2], cropped.shape[-1])
 
 
+def orientation_code(rotation: int = 0, mirror: bool = False) -> int:
+    """The `orient` code of a `pv_view_source` record (include/pv_mi355x.h): `rotation` is the clockwise turn the stream's
+    metadata asks for -- 0, 90, 180 or 270 degrees, a decoder's "rotate 90" -- and `mirror` the horizontal flip of the turned
+    frame (a front camera): rot | (mirror << 2)."""
+    if isinstance(rotation, bool) or rotation not in (0, 90, 180, 270):
+        raise ValueError("rotation is 0, 90, 180 or 270 degrees clockwise, got %r" % (rotation,))
+    return int(rotation) // 90 | (4 if mirror else 0)
+
+
+def _orient(code, what="orientation"):
+    try:
+        if isinstance(code, bool):
+            raise TypeError
+        code = operator.index(code)                  # any integer type: int, numpy, a 0-d tensor
+    except TypeError:
+        raise ValueError("%s is a code 0..7 (orientation_code), got %r" % (what, code)) from None
+    if not 0 <= code <= 7:
+        raise ValueError("%s is a code 0..7 (orientation_code), got %d" % (what, code))
+    return code
+
+
+def displayed_size(height: int, width: int, orient: int) -> Tuple[int, int]:
+    """(Hd, Wd) of a stored height x width frame under `orient`: a quarter turn swaps the two."""
+    return (width, height) if _orient(orient) & 1 else (height, width)
+
+
+def oriented(x: torch.Tensor, orient: int, h_dim: int = -2, w_dim: int = -1) -> torch.Tensor:
+    """The displayed frame(s) of stored frame(s) `x` under `orient`, the host mirror of the ingest's rule:
+    `torch.rot90(x, -rot, (h_dim, w_dim))`, then `.flip(w_dim)` if the mirror bit is set.  The result is a view or a copy as
+    torch decides; call `.contiguous()` for a dense one."""
+    orient = _orient(orient)
+    if orient & 3:
+        x = torch.rot90(x, -(orient & 3), (h_dim, w_dim))
+    return x.flip(w_dim) if orient & 4 else x
+
+
+def orient_boxes(boxes: torch.Tensor, height: int, width: int, orient: int) -> torch.Tensor:
+    """fp32 [N,4] boxes (x1, y1, x2, y2) in the pixels of a STORED height x width frame -> the same boxes in the pixels of the
+    displayed frame, the host mirror of `pv_box_views`: every operation rounded on its own in fp32.  A mirrored coordinate
+    along an axis of stored length n is `n - v - 1` in that order (the reference's `horizontal_flip_with_boxes`,
+    functional.py:380-404, which code 4 equals), a quarter turn swaps x and y, and the corners are re-ordered so that
+    x1 <= x2 and y1 <= y2.  The input is not modified."""
+    orient = _orient(orient)
+    b = boxes.detach().to("cpu", torch.float32).clone()
+    if orient == 0:
+        return b
+    x, y = b[:, [0, 2]], b[:, [1, 3]]
+
+    def mirror(v, n):
+        return (float(n) - v) - 1.0
+
+    rot = orient & 3
+    if rot == 1:
+        x, y = mirror(y, height), x
+    elif rot == 2:
+        x, y = mirror(x, width), mirror(y, height)
+    elif rot == 3:
+        x, y = y, mirror(x, width)
+    if orient & 4:
+        x = mirror(x, displayed_size(height, width, orient)[1])
+    out = torch.empty_like(b)
+    out[:, 0], out[:, 2] = torch.minimum(x[:, 0], x[:, 1]), torch.maximum(x[:, 0], x[:, 1])
+    out[:, 1], out[:, 3] = torch.minimum(y[:, 0], y[:, 1]), torch.maximum(y[:, 0], y[:, 1])
+    return out
+
+
 def boxes_to_view(boxes: torch.Tensor, height: int, width: int, short_side: int, crop_size=None, spatial_idx: int = 1,
-                  clip_to_source: bool = False) -> torch.Tensor:
+                  clip_to_source: bool = False, orientation: int = 0) -> torch.Tensor:
     """The host mirror of `pv_box_views` (include/pv_mi355x.h): fp32 [N,4] boxes (x1, y1, x2, y2) in the pixels of a
     height x width SOURCE frame -> the same boxes in the pixels of the view the ingest cuts from that frame, composed from the
     mirrors above in the reference's order: `clip_boxes_to_image` to the source (`clip_to_source`: the detection tutorial's
     first step), `short_side_scale_with_boxes`, then `crop_boxes` to the origin of the `crop_size` window of `spatial_idx`
     -- `crop_size=None`: no crop, the window is the whole scaled frame -- and `clip_boxes_to_image` to the window.  The
-    input is not modified.  Boxes are finite."""
+    input is not modified.  Boxes are finite.  `orientation` (`orientation_code`): `height` x `width` and the boxes are the
+    STORED frame's; behind the first clip the boxes go into the displayed frame (`orient_boxes`), whose size the scale and
+    the crop then see."""
     out = boxes.detach().to("cpu", torch.float32).clone()
     if clip_to_source:
         out = clip_boxes_to_image(out, height, width)
+    if _orient(orientation):
+        out = orient_boxes(out, height, width, orientation)
+        height, width = displayed_size(height, width, orientation)
     frame = torch.zeros(1, dtype=torch.float32).expand(1, 1, height, width)          # only its size is used
     scaled, out = short_side_scale_with_boxes(frame, out, short_side)
     hn, wn = scaled.shape[-2:]
@@ -599,6 +671,13 @@ class FrameList:
         return torch.stack(self.frames, dim=1 if src_layout == "NCTHW" else 0)
 
 
+def _refuse_orientation(orientation, what):
+    if _orient(0 if orientation is None else orientation):
+        raise RuntimeError("%s reads materialised clips through the one-source entry points, which have no orientation; a "
+                           "turned or mirrored video is read in place by DevicePacker.video_batch(..., orientation=) / "
+                           "fill_batch (inference.VideoPredictor and its kin take orientation= too)" % what)
+
+
 def _refuse_frames(video, what):
     if isinstance(video, FrameList):
         raise RuntimeError("%s takes one tensor; a FrameList goes through video_batch / fill_batch" % what)
@@ -661,12 +740,14 @@ class VideoBatch:
 
 
 def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, pathway_frames, channels, device, upload,
-                      height=None, coded_height=None):
+                      height=None, coded_height=None, orientation=None):
     """The host half of `DevicePacker.video_batch` (see there): validate every video, build the records, the item sequence
     and the concatenated tables, and hand them to `upload` (host tensor -> device tensor) once.  `crop_size` is the side of
     the square crop, or a pair (Ho, Wo): NO crop -- the window is the whole scaled frame, and every video must scale to
     exactly Ho x Wo.  The videos are all tensors or all `FrameList`s; for `FrameList`s ONE int64 table of frame addresses,
-    video-major, is uploaded in front of the records, and record j points at its slice of the device copy."""
+    video-major, is uploaded in front of the records, and record j points at its slice of the device copy.
+    `orientation`: one code (`orientation_code`) or one per video, None = 0 -- the videos are the STORED frames, as a decoder
+    hands them out; the record keeps the stored sizes and carries the code, and the views are cut from the displayed frame."""
     from . import _lib as L
     videos = list(videos)
     if not videos or len(tables) != len(videos):
@@ -686,6 +767,7 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
         return x
 
     heights, coded = per_video(height, "height"), per_video(coded_height, "coded_height")
+    orients = [_orient(0 if o is None else o) for o in per_video(orientation, "orientation")]
     sources = (L.ViewSource * len(videos))()
     nums_frames, dtype = [], videos[0].dtype
     for j, video in enumerate(videos):
@@ -703,11 +785,14 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
             raise RuntimeError("video %d has %d channels, the deploy form takes %d" % (j, c, channels))
         for k in _YUV_PLANE_FIELDS if is_yuv else ():
             setattr(rec, k, geom[k])
-        hn, wn, offsets = _view_geometry(hs, ws, short_side, crop_size, views, what + ": ")
+        hd, wd = displayed_size(hs, ws, orients[j])               # the views are cut from the displayed frame
+        hn, wn, offsets = _view_geometry(hd, wd, short_side, crop_size, views, what + ": ")
         _set_views(rec, hn, wn, offsets)
         rec.src, rec.N, rec.Hs, rec.Ws = (None if as_frames else video.data_ptr()), nf, hs, ws
-        # (float)Hs / (float)Hn: sizes are exact in fp32, and a double quotient rounded once more to fp32 IS the fp32 quotient
-        rec.sy, rec.sx = hs / hn, ws / wn
+        if orients[j]:                                            # default records keep the zero they were built with
+            rec.orient = orients[j]
+        # (float)Hd / (float)Hn: sizes are exact in fp32, and a double quotient rounded once more to fp32 IS the fp32 quotient
+        rec.sy, rec.sx = hd / hn, wd / wn
         nums_frames.append(nf)
     clip_frames = None
     for j, t in enumerate(tables):
@@ -737,7 +822,8 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
 
 @torch.no_grad()
 def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std=None, div255=False, num_frames=None,
-                      dtype=torch.bfloat16, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None):
+                      dtype=torch.bfloat16, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None,
+                      orientation=0):
     """uniform_crop(short_side_scale(Normalize(Div255(uniform_temporal_subsample(clip, num_frames))))) for every view of
     `spatial_idx` in one launch of `pv_resample_crop`: a planar [B * n_views, C, T, crop, crop] tensor of `dtype` (bf16 or
     fp32) on the GPU, item b * n_views + v being view v of clip b.  `clip` is [B,C,T,H,W] ("NCTHW"; uint8 or float) or the
@@ -747,7 +833,11 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
     [T, Hc*3/2, W]: one clip) with the strides it has (`yuv_geometry`: `coded_height`, `height`), converted tap by tap inside
     the same launch (`pv_yuv_views`) by `yuv`: (standard, full_range) for `yuv_matrix`, or a 3 x 4 matrix.  With a layout of
     `YUV16_LAYOUTS` ("P010", "I010", ...) the clip is uint16 or int16 and read by `pv_yuv16_views`; a (standard, full_range)
-    pair is composed with the layout's depth and bit alignment: `src_layout="P010", yuv=("bt2020", False)`."""
+    pair is composed with the layout's depth and bit alignment: `src_layout="P010", yuv=("bt2020", False)`.
+
+    Materialised clips go through the one-source entry points, whose descriptors have no orientation: a non-zero
+    `orientation` is refused; `DevicePacker.video_batch` reads turned and mirrored videos in place."""
+    _refuse_orientation(orientation, "device_scale_crop")
     if src_layout not in ("NCTHW", "NTHWC") + _YUV_ANY:
         raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
     if dtype not in (torch.bfloat16, torch.float32):
@@ -903,7 +993,8 @@ class DevicePacker:
         return out
 
     @torch.no_grad()
-    def __call__(self, clip, bboxes=None):
+    def __call__(self, clip, bboxes=None, orientation=0):
+        _refuse_orientation(orientation, "a clip-at-a-time call")
         load_boxes = getattr(self.model, "_pv_load_boxes", None)
         if (bboxes is None) != (load_boxes is None):
             raise RuntimeError("bboxes are given to a detection model and only to a detection model")
@@ -1084,7 +1175,7 @@ class DevicePacker:
             fill(d, ref, planar=self._planar_for(i, ref))
 
     # ------------------------------------------------------------------------- many videos per forward (pv_batch_views)
-    def video_batch(self, videos, tables, height=None, coded_height=None):
+    def video_batch(self, videos, tables, height=None, coded_height=None, orientation=None):
         """Prepare a list of decoded videos -- any lengths, any frame sizes, all in the packer's source layout and on the
         device -- for `fill_batch`: `tables[j]` is the [n_clips_j, clip_frames] frame table of video j
         (`data.clip_frame_table`).  Every video is validated as `fill_video` validates one (device, dtype, contiguity of the
@@ -1093,8 +1184,10 @@ class DevicePacker:
         video-major item sequence (video j, then clip * n_views + v) and the concatenated per-pathway tables are uploaded
         ONCE.  The videos may instead ALL be `FrameList`s -- one device tensor per frame, as a decoder's surface pool hands
         them out: one table of frame addresses is then uploaded with the records, and `fill_batch` reads every frame where
-        it lies (`pv_frame_views`); a mix of tensors and FrameLists is a ValueError.  Returns a `VideoBatch`, which keeps
-        the videos alive."""
+        it lies (`pv_frame_views`); a mix of tensors and FrameLists is a ValueError.  `orientation`: one code
+        (`orientation_code`) or one per video for videos STORED turned and / or mirrored -- a portrait phone clip is landscape
+        frames plus "rotate 90": the ingest reads them in place and cuts the views from the displayed frame, and
+        `fill_boxes` takes boxes given in stored pixels along.  Returns a `VideoBatch`, which keeps the videos alive."""
         if self.short_side is None:
             raise RuntimeError("video_batch resamples: construct the packer with short_side and crop_size")
         if getattr(self.model, "_pv_load_boxes", None) is not None and not self.keyframes:
@@ -1110,7 +1203,7 @@ class DevicePacker:
                                  self.window if self.no_crop else self.crop_size, self.views,
                                  [ref.T for ref in refs], refs[0].C, device, lambda t: t.to(device),
                                  self.height if height is None else height,
-                                 self.coded_height if coded_height is None else coded_height)
+                                 self.coded_height if coded_height is None else coded_height, orientation)
 
     @torch.no_grad()
     def fill_batch(self, batch, i0, n):
