@@ -515,3 +515,221 @@ def make_ensemble(mode, seed=801):
     accum0 = torch.rand((V, Cc), generator=torch.Generator().manual_seed(seed + 1)) * (0.2 if mode == 1 else 1.0)
     return (dict(logits=logits, video_index=idx, accum0=accum0, counts0=torch.tensor([3, 0, 5, 2], dtype=torch.int32)),
             dict(N=N, C=Cc, ld=ld, V=V, mode=mode))
+
+
+# ------------------------------------------------------------------ stencil family (pv_dwconv.hip, pv_pwdw.hip, pv_tokpool.hip)
+# float64 references and checks of pv_dwconv3d (depthwise / grouped, psum, cls prefix, w_mod, fused pointwise producer) and
+# pv_token_pool.  tests/test_stencil_kernel_checks.py feeds the checks their own reference and defective copies of it;
+# tests/test_gpu_stencil_kernels.py feeds them what the kernels left on the device.
+PSUM_TOL, PSUM_TOL_FUSED = 1e-3, 2e-3      # mean over T,H,W taken from psum (tests/test_gpu_kernels.py)
+
+
+def round_up32(c):
+    return (c + 31) // 32 * 32
+
+
+def conv_out_dims(p):
+    return tuple((n + 2 * pd - k) // s + 1 for n, k, s, pd in zip((p["T"], p["H"], p["W"]), p["k"], p["s"], p["p"]))
+
+
+def ref_stencil(grid, w, s, pad, gw=1, halo=None, drop=None):
+    """nn.Conv3d(C, C, k, s, pad, groups=C // gw, bias=False) of a (B, T, H, W, C) float64 grid; w (C, gw, kt, kh, kw).
+    halo: (C,) value the padding is filled with instead of zero; drop = (b, to, ho, wo, (dt, dh, dw)): that tap is left out
+    of that one output voxel (both are defects for the checks' own test)."""
+    import torch.nn.functional as F
+    B, T, H, W, Cc = grid.shape
+    xp = torch.zeros(B, T + 2 * pad[0], H + 2 * pad[1], W + 2 * pad[2], Cc, dtype=torch.float64)
+    if halo is not None:
+        xp[:] = halo.double()
+    xp[:, pad[0]:pad[0] + T, pad[1]:pad[1] + H, pad[2]:pad[2] + W] = grid
+    out = F.conv3d(xp.permute(0, 4, 1, 2, 3), w.double(), None, stride=s, padding=0, groups=Cc // gw).permute(0, 2, 3, 4, 1).contiguous()
+    if drop is not None:
+        assert gw == 1
+        b, to, ho, wo, (dt, dh, dw) = drop
+        out[b, to, ho, wo] -= xp[b, to * s[0] + dt, ho * s[1] + dh, wo * s[2] + dw] * w.double()[:, 0, dt, dh, dw]
+    return out
+
+
+def pack_dw_weights(w, w_p):
+    """(Cw, gw, kt, kh, kw) -> the library's [taps][gw][w_p] fp32 block, zero padded."""
+    Cw, gw = w.shape[:2]
+    taps = w[0, 0].numel()
+    wp = torch.zeros(taps, gw, w_p, dtype=torch.float32)
+    wp[:, :, :Cw] = w.reshape(Cw, gw, taps).permute(2, 1, 0)
+    return wp
+
+
+def fill_dw_geometry(d, p, dtype):
+    """Every field of a DwConv3dDesc that is not a pointer."""
+    To, Ho, Wo = conv_out_dims(p)
+    d.x_bs, d.y_bs, d.ldx, d.ldy = p["x_bs"], p["y_bs"], p["ldx"], p["ldy"]
+    d.B, d.Ti, d.Hi, d.Wi, d.C, d.To, d.Ho, d.Wo = p["B"], p["T"], p["H"], p["W"], p["C"], To, Ho, Wo
+    d.kt, d.kh, d.kw, d.st, d.sh, d.sw, d.pt, d.ph, d.pw = (*p["k"], *p["s"], *p["p"])
+    d.w_mod, d.act, d.n_prefix, d.gw = p["w_mod"], p["act"], p["n_prefix"], p["gw"]
+    d.dtype = L.PV_BF16 if dtype == torch.bfloat16 else L.PV_F32
+    d.pw_cin, d.pw_act = p.get("pw_cin", 0), p.get("pw_act", 0)
+    return d
+
+
+# ---- pv_dwconv3d: p = B, T, H, W, C, k, s, p (pad), act, gw, w_mod, n_prefix, ldx, ldy, x_bs, y_bs, x_off, psum;
+# i = x (B, x_bs; the grid's channels start at column x_off of every row), y0 (B, y_bs), w (packed), wref (Cw, gw, kt, kh, kw),
+# scale, shift (C,)
+def _x_rows(i, p, R, Cc):
+    buf = i["x"].cpu()
+    return buf[:, :R * p["ldx"]].view(buf.shape[0], R, p["ldx"])[..., p.get("x_off", 0):p.get("x_off", 0) + Cc]
+
+
+def expect_dwconv(i, p, drop=None, wrong_head=False, prefix_from=0):
+    """(Expect for y, pre-activation reference (B, To*Ho*Wo, C)).  wrong_head: the channels of every head but the first take
+    the shared filter one 8-channel chunk over (a lane that reduces its chunk modulo the wrong width); prefix_from = 1: the
+    prefix rows are copied from one row further down."""
+    B, T, H, W, Cc, npre, gw = p["B"], p["T"], p["H"], p["W"], p["C"], p["n_prefix"], max(p["gw"], 1)
+    rows = _x_rows(i, p, npre + T * H * W, Cc).double()
+    w = i["wref"].double()
+    if p["w_mod"] > 0:
+        idx = torch.arange(Cc) % p["w_mod"]
+        if wrong_head:
+            idx = torch.where(torch.arange(Cc) >= p["w_mod"], (idx + 8) % p["w_mod"], idx)
+        w = w[idx]
+    pre = ref_stencil(rows[:, npre:].reshape(B, T, H, W, Cc), w, p["s"], p["p"], gw, drop=drop)
+    pre = pre * i["scale"].double() + i["shift"].double()
+    pre = pre.reshape(B, -1, Cc)
+    want = torch.cat([rows[:, prefix_from:prefix_from + npre], ref_act(pre, p["act"])], 1)
+    exact = torch.zeros(B, want.shape[1], dtype=torch.bool)
+    exact[:, :npre] = True                                     # cls rows are copies
+    return Expect(want, i["y0"], p["ldy"], tol=TOL[i["y0"].dtype], exact=exact), pre
+
+
+def check_psum(psum, pre, p, nblk, tol, what="pv_dwconv3d"):
+    """psum (B * nblk + 1, round_up(C, 8)) as the launch left it (NaN before): every entry of the B * nblk blocks finite, the
+    padding channels exactly zero, the one block behind them untouched, and the mean over T,H,W within tol of the reference's."""
+    psum, Cc, B = psum.detach().cpu(), p["C"], p["B"]
+    assert psum.shape == (B * nblk + 1, round_up8(Cc)), what
+    body = psum[:B * nblk].view(B, nblk, -1)
+    assert torch.isfinite(body).all(), "%s: %d psum entries were not written" % (what, (~torch.isfinite(body)).sum().item())
+    assert (body[..., Cc:] == 0).all(), "%s: padding channels of psum are not zero" % what
+    assert torch.isnan(psum[-1]).all(), "%s: the psum block behind the last one was written" % what
+    err = _abs_rel(body[..., :Cc].double().sum(1) / pre.shape[1], pre.mean(1))
+    assert err <= tol, "%s: mean from psum off by %.3e of the reference abs-max > %.1e" % (what, err, tol)
+    return err
+
+
+def check_dwconv(got, i, p, psum=None, nblk=0):
+    """-> (error of y, error of the psum mean or None)"""
+    e, pre = expect_pwdw(i, p) if p.get("pw_cin", 0) else expect_dwconv(i, p)
+    what = "pv_dwconv3d(pw)" if p.get("pw_cin", 0) else "pv_dwconv3d"
+    err = e.check(got, what)
+    if psum is None:
+        return err, None
+    return err, check_psum(psum, pre, p, nblk, PSUM_TOL_FUSED if p.get("pw_cin", 0) else PSUM_TOL, what)
+
+
+def make_dwconv(dtype, B, T, H, W, Cc, k, s, pad, act, gw=0, w_mod=0, n_prefix=0, ldx=None, ldy=None, gap=16, qkv=False, seed=901):
+    """qkv: x is the middle third of a fused (q | k | v) token buffer, ldx = 3 * C."""
+    p = dict(B=B, T=T, H=H, W=W, C=Cc, k=tuple(k), s=tuple(s), p=tuple(pad), act=act, gw=gw, w_mod=w_mod, n_prefix=n_prefix)
+    cp = round_up8(Cc)
+    To, Ho, Wo = conv_out_dims(p)
+    Rx, Ry = n_prefix + T * H * W, n_prefix + To * Ho * Wo
+    p["ldx"], p["ldy"] = (3 * Cc if qkv else cp) if ldx is None else ldx, cp if ldy is None else ldy
+    p["x_bs"], p["y_bs"], p["x_off"] = Rx * p["ldx"] + gap, Ry * p["ldy"] + 2 * gap, Cc if qkv else 0
+    if qkv:
+        assert Cc % 8 == 0
+        x = torch.full((B, p["x_bs"]), CANARY, dtype=dtype)
+        x[:, :Rx * p["ldx"]] = randn((B, Rx * p["ldx"]), seed).to(dtype)
+    else:
+        x = rows_buf(randn((B, Rx, Cc), seed), p["ldx"], dtype, bs=p["x_bs"])
+    Cw, g = w_mod or Cc, max(gw, 1)
+    wref = randn((Cw, g) + tuple(k), seed + 1, (g * k[0] * k[1] * k[2]) ** -0.5 * 1.7)
+    i = dict(x=x, y0=canary_buf(B, p["y_bs"], dtype), w=pack_dw_weights(wref, round_up8(Cw)), wref=wref,
+             scale=randn((Cc,), seed + 2, 0.2, 1.0), shift=randn((Cc,), seed + 3, 0.5, 0.25))
+    return i, p
+
+
+# ---- pv_dwconv3d with the fused pointwise producer: p as above + pw_cin, pw_act; i as above + x of pw_cin channels,
+# pw_w (round_up(C, 32), round_up(pw_cin, 32)) bf16 zero padded, wa (C, pw_cin) bf16, pw_scale, pw_shift (C,)
+def expect_pwdw(i, p, halo_shift=False, drop=None):
+    """conv_a + affine + activation in float64, rounded to bf16, then the depthwise conv in float64; the expanded tensor is
+    ZERO outside the image.  halo_shift: it is act(pw_shift) there instead (a defect: the image of a zero input)."""
+    B, T, H, W, Cc, cin = p["B"], p["T"], p["H"], p["W"], p["C"], p["pw_cin"]
+    x = _x_rows(i, p, T * H * W, cin).double()
+    h = ref_act((x @ i["wa"].double().t()) * i["pw_scale"].double() + i["pw_shift"].double(), p["pw_act"])
+    h = h.to(torch.bfloat16).double().reshape(B, T, H, W, Cc)
+    halo = ref_act(i["pw_shift"].double(), p["pw_act"]).to(torch.bfloat16).double() if halo_shift else None
+    pre = ref_stencil(h, i["wref"].double(), p["s"], p["p"], 1, halo=halo, drop=drop)
+    pre = (pre * i["scale"].double() + i["shift"].double()).reshape(B, -1, Cc)
+    return Expect(ref_act(pre, p["act"]), i["y0"], p["ldy"], tol=TOL[torch.bfloat16]), pre
+
+
+def make_pwdw(B, T, H, W, cin, Cc, stride, act, pw_act, wide_ldx=False, gap=16, seed=921):
+    p = dict(B=B, T=T, H=H, W=W, C=Cc, k=(3, 3, 3), s=(1, stride, stride), p=(1, 1, 1), act=act, gw=0, w_mod=0, n_prefix=0,
+             pw_cin=cin, pw_act=pw_act, x_off=0)
+    cp, To, Ho, Wo = round_up8(Cc), *conv_out_dims(p)
+    p["ldx"], p["ldy"] = round_up8(cin) + (16 if wide_ldx else 0), cp + 8
+    p["x_bs"], p["y_bs"] = T * H * W * p["ldx"] + gap, To * Ho * Wo * p["ldy"] + 2 * gap
+    wa = randn((Cc, cin), seed + 4, cin ** -0.5).to(torch.bfloat16)
+    pw_w = torch.zeros(round_up32(Cc), round_up32(cin), dtype=torch.bfloat16)
+    pw_w[:Cc, :cin] = wa
+    wref = randn((Cc, 1, 3, 3, 3), seed + 1, 0.3)
+    i = dict(x=rows_buf(randn((B, T * H * W, cin), seed), p["ldx"], torch.bfloat16, bs=p["x_bs"]),
+             y0=canary_buf(B, p["y_bs"], torch.bfloat16), w=pack_dw_weights(wref, cp), wref=wref,
+             scale=randn((Cc,), seed + 2, 0.2, 1.0), shift=randn((Cc,), seed + 3, 0.5, 0.25),
+             pw_w=pw_w, wa=wa, pw_scale=randn((Cc,), seed + 5, 0.2, 1.0), pw_shift=randn((Cc,), seed + 6, 0.5, 0.3))
+    return i, p
+
+
+# ---- pv_token_pool: p = n, B, T, H, W, heads, hd, k, strides [n], n_prefix, eps, ldx [n], ldy [n], x_bs [n], y_bs [n];
+# i = x [n] (B, x_bs), y0 [n] (B, y_bs), w [n] ([taps][hd] packed), wref [n] (hd, 1, kt, kh, kw), gamma [n], beta [n] ((hd,) | None)
+def token_pool_out_dims(p, z):
+    return tuple((n + 2 * (k // 2) - k) // s + 1 for n, k, s in zip((p["T"], p["H"], p["W"]), p["k"], p["strides"][z]))
+
+
+def expect_token_pool(i, p, z, stat_width=None, drop=None, prefix_from=0):
+    """Tensor z of the launch.  stat_width: the LayerNorm statistics are taken over that many channels (the head's, then
+    zeros) instead of head_dim -- a defect for the checks' own test."""
+    B, T, H, W, heads, hd, npre = p["B"], p["T"], p["H"], p["W"], p["heads"], p["hd"], p["n_prefix"]
+    Cw = heads * hd
+    rows = rows_of(i["x"][z].cpu(), npre + T * H * W, p["ldx"][z], Cw).double()
+    To, Ho, Wo = token_pool_out_dims(p, z)
+    grid = rows[:, npre:].reshape(B, T, H, W, Cw)
+    w = i["wref"][z].double()[torch.arange(Cw) % hd]
+    pooled = ref_stencil(grid, w, p["strides"][z], tuple(kk // 2 for kk in p["k"]), 1, drop=drop)[:, :To, :Ho, :Wo]
+    v = torch.cat([rows[:, prefix_from:prefix_from + npre], pooled.reshape(B, -1, Cw)], 1).reshape(B, -1, heads, hd)
+    g, bt = i["gamma"][z], i["beta"][z]
+    if g is not None or bt is not None:
+        n = stat_width or hd
+        mean = v.sum(-1, keepdim=True) / n
+        var = (((v - mean) ** 2).sum(-1, keepdim=True) + (n - hd) * mean ** 2) / n
+        v = (v - mean) / torch.sqrt(var + p["eps"])
+        if g is not None:
+            v = v * g.double()
+        if bt is not None:
+            v = v + bt.double()
+    exact = None
+    if g is None and bt is None and npre:                      # nothing is computed on a cls row that is not normalised
+        exact = torch.zeros(B, v.shape[1], dtype=torch.bool)
+        exact[:, :npre] = True
+    return Expect(v.reshape(B, -1, Cw), i["y0"][z], p["ldy"][z], tol=TOL[i["y0"][z].dtype], exact=exact, written=Cw)
+
+
+def check_token_pool(gots, i, p):
+    return max(expect_token_pool(i, p, z).check(gots[z], "pv_token_pool[%d]" % z) for z in range(p["n"]))
+
+
+def make_token_pool(dtype, B, heads, hd, thw, k, strides, n_prefix, gamma=True, beta=True, wide=False, gap=0, seed=941):
+    T, H, W = thw
+    n, Cw = len(strides), heads * hd
+    p = dict(n=n, B=B, T=T, H=H, W=W, heads=heads, hd=hd, k=tuple(k), strides=[tuple(s) for s in strides], n_prefix=n_prefix,
+             eps=1e-6, ldx=[], ldy=[], x_bs=[], y_bs=[])
+    i = dict(x=[], y0=[], w=[], wref=[], gamma=[], beta=[])
+    for z in range(n):
+        To, Ho, Wo = token_pool_out_dims(p, z)
+        Rx, Ry = n_prefix + T * H * W, n_prefix + To * Ho * Wo
+        ldx, ldy = Cw + (8 if wide else 0), Cw + (16 if wide else 0)
+        p["ldx"].append(ldx), p["ldy"].append(ldy), p["x_bs"].append(Rx * ldx + gap), p["y_bs"].append(Ry * ldy + 2 * gap)
+        wref = randn((hd, 1) + tuple(k), seed + 10 * z + 1, (k[0] * k[1] * k[2]) ** -0.5 * 1.7)
+        i["x"].append(rows_buf(randn((B, Rx, Cw), seed + 10 * z, 1.0, 0.3), ldx, dtype, bs=p["x_bs"][z], written=Cw))
+        i["y0"].append(canary_buf(B, p["y_bs"][z], dtype))
+        i["w"].append(pack_dw_weights(wref, hd).reshape(-1, hd)), i["wref"].append(wref)
+        i["gamma"].append(randn((hd,), seed + 10 * z + 2, 0.2, 1.0) if gamma else None)
+        i["beta"].append(randn((hd,), seed + 10 * z + 3, 0.3) if beta else None)
+    return i, p
