@@ -491,8 +491,8 @@ int pv_yuv_views(const pv_yuv_views_desc* d, pv_stream_t stream);
  * |v_offset - u_offset| != 2); an odd src, frame_stride, u_offset, v_offset, y_pitch or c_pitch.  PV_ERR_UNSUPPORTED: as
  * pv_yuv_views; a staged strip beyond the kernels' LDS limit (two source rows of the widest window with their chroma, 64 KiB:
  * a window some 8000 columns wide).  Validation precedes every HIP call.
- * Out of scope: 4:2:2 and 4:4:4, filtered or sited chroma, transfer functions and tone mapping (PQ / HLG to SDR is the
- * caller's decision), big-endian samples, 16-bit RGB.
+ * Out of scope: 4:2:2 and 4:4:4, filtered or sited chroma, big-endian samples, 16-bit RGB.  Transfer functions are not touched
+ * here: the matrix is applied to the codes as they are (PQ / HLG to SDR per tap is pv_hdr_views, below).
  */
 int pv_yuv16_views(const pv_yuv_views_desc* d, pv_stream_t stream);
 
@@ -628,6 +628,51 @@ typedef struct pv_frame_views_desc {
   int32_t reserved;
 } pv_frame_views_desc;
 int pv_frame_views(const pv_frame_views_desc* d, pv_stream_t stream);
+
+/* ---- HDR sources: PQ / HLG taps converted to BT.709 SDR inside the launch ------------------------------------------------
+ * Most 10-bit streams are HDR: a phone's HLG (BT.2100, usually stored rotated), HDR10 / AV1 PQ (SMPTE ST 2084).  Their
+ * samples give BT.2020 R'G'B' under a PQ or HLG curve, and a network trained on BT.709 SDR reads mid-greys tens of codes off
+ * and the wrong primaries.  pv_hdr_views is pv_batch_views / pv_frame_views on 16-bit YUV 4:2:0 sources with one more step
+ * PER TAP, in registers: no colour pass over the video and no RGB copy stands between the decoder and the ingest.
+ * Launch:       `frames`, a whole pv_frame_views_desc.  frames.frame_ptrs == NULL (and frame_ptrs_dev NULL, n_frame_ptrs 0):
+ *               the records are whole videos, exactly pv_batch_views' meaning of frames.batch; otherwise pv_frame_views'
+ *               meaning.  src_layout PV_SRC_YUV420 with src_dtype PV_U16 only.  pv_view_source.orient is honoured and a
+ *               launch may mix orientations, as there.
+ * Arithmetic:   the rule of pv_yuv_views stands: convert each tap, then blend.  A tap of the virtual RGB frame is
+ *               rgb[c] = clamp(M (Y,U,V,1), 0, 255) as in pv_yuv16_views, M the caller's matrix (BT.2020, the stream's depth and
+ *               bit alignment).  With e_c = rgb[c] / 255 every tap is then mapped in fp32, tone[16] being fp32 values the
+ *               caller composes (transforms.tone_params) and uploads:
+ *                 1. to linear light in units of SDR reference white.
+ *                    PV_TRANSFER_PQ:  p = e^(1/m2), l_c = (max(p - c1, 0) / (c2 - c3 p))^(1/m1) * tone[0], with m1 = 2610/16384,
+ *                    m2 = 2523/4096 * 128, c1 = 3424/4096, c2 = 2413/4096 * 32, c3 = 2392/4096 * 32; tone[0] = 10000 / white_nits.
+ *                    PV_TRANSFER_HLG: s_c = e^2 / 3 for e <= 1/2, else (exp((e - c) / a) + b) / 12, a = 0.17883277, b = 1 - 4a,
+ *                    c = 0.5 - a ln(4a); Ys = 0.2627 s_R + 0.6780 s_G + 0.0593 s_B; l_c = s_c * Ys^tone[1] * tone[0], with
+ *                    tone[1] = gamma - 1 and tone[0] = peak_nits / white_nits.  No black-level lift; Ys = 0 gives 0.
+ *                 2. tone curve on max-RGB, hue-preserving ("mobius"): m = max(l_R, l_G, l_B),
+ *                    k = m > j ? s (m + a') / ((m + b') m) : 1, l_c *= k, with j, s, a', b' = tone[2..5].  j = 3e38 disables
+ *                    the curve (step 3 then clips).
+ *                 3. gamut: l = clamp(G l, 0, 1), G = tone[6..14] row-major (BT.2020 to BT.709, or the identity).
+ *                 4. back to a BT.709-coded signal with BT.2020's continuous constants: v = 4.5 l for l < 0.018053968510807,
+ *                    else 1.09929682680944 l^0.45 - 0.09929682680944.  The tap becomes 255 v.
+ *               tone[15] is 0.  x^y is exp2(y log2 x) on the hardware's transcendental units (1 ulp each), divisions are
+ *               multiplications by the hardware reciprocal; a zero base gives 0, never NaN: all-zero and all-0xFFFF surfaces
+ *               give finite output.  From there on: pv_resample_crop's blend, affine map and single rounding, unchanged.
+ *               Item i holds the same bits whatever else shares its launch, for a frame list as for the stacked video, and
+ *               for an oriented record as for a copy oriented beforehand.
+ * PV_ERR_INVALID: a null descriptor or tone; transfer outside 1..2; reserved != 0; a pointer table only half given
+ * (frame_ptrs without frame_ptrs_dev or the reverse), or n_frame_ptrs != 0 without a table; whatever the wrapped entry point
+ * rejects.  PV_ERR_UNSUPPORTED: any src_layout / src_dtype pair but PV_SRC_YUV420 / PV_U16 (8-bit HDR does not exist in
+ * practice); as the wrapped entry point otherwise.  Validation precedes every HIP call.
+ * Out of scope: dynamic metadata (HDR10+, Dolby Vision), BT.2390 / scene-adaptive curves, a transfer per record.
+ */
+enum { PV_TRANSFER_PQ = 1, PV_TRANSFER_HLG = 2 };
+typedef struct pv_hdr_views_desc {
+  pv_frame_views_desc frames;         /* frame_ptrs == NULL: whole videos (pv_batch_views); else pv_frame_views  */
+  const float* tone;                  /* [16] fp32 on the device, see "arithmetic"                              */
+  int32_t transfer;                   /* PV_TRANSFER_PQ / PV_TRANSFER_HLG                                       */
+  int32_t reserved;                   /* 0                                                                      */
+} pv_hdr_views_desc;                  /* sizeof(pv_frame_views_desc) + 16 */
+int pv_hdr_views(const pv_hdr_views_desc* d, pv_stream_t stream);
 
 /* ---- key-frame detection: the boxes of a forward mapped into its views, on the device ---------------------------------
  * A detection forward built by pv_batch_views holds one clip per key frame, and every key frame has person boxes given in the

@@ -107,6 +107,9 @@ BatchViewsDesc = _struct("BatchViewsDesc", [
             "dst_layout", "dst_dtype", "c_p", "ld"))
 FrameViewsDesc = _struct("FrameViewsDesc", [
     ("batch", BatchViewsDesc), ("frame_ptrs", _p), ("frame_ptrs_dev", _p)] + _ints("n_frame_ptrs", "reserved"))
+# pv_hdr_views: a whole FrameViewsDesc (frame_ptrs None: the records are whole videos, pv_batch_views' meaning) and the tap map
+TRANSFER_PQ, TRANSFER_HLG = 1, 2
+HdrViewsDesc = _struct("HdrViewsDesc", [("frames", FrameViewsDesc), ("tone", _p)] + _ints("transfer", "reserved"))
 BoxViewsDesc = _struct("BoxViewsDesc", [
     ("boxes", _p), ("box_item", _p), ("sources_dev", _p), ("items_dev", _p), ("dst", _p), ("dst_box", _p)]
     + _ints("n_boxes", "n_seq", "n_sources", "n_views", "box0", "n_launch", "item0", "n_items", "Ho", "Wo", "capacity",
@@ -193,6 +196,7 @@ _SYMBOLS = [
     ("pv_yuv16_views", C.c_int, [C.POINTER(YuvViewsDesc), _p]),
     ("pv_batch_views", C.c_int, [C.POINTER(BatchViewsDesc), _p]),
     ("pv_frame_views", C.c_int, [C.POINTER(FrameViewsDesc), _p]),
+    ("pv_hdr_views", C.c_int, [C.POINTER(HdrViewsDesc), _p]),
     ("pv_box_views", C.c_int, [C.POINTER(BoxViewsDesc), _p]),
     ("pv_layernorm", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_affine_rows", C.c_int, [C.POINTER(RowsDesc), _p]),

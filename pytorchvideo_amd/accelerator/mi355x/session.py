@@ -427,6 +427,11 @@ class Session:
         into the BatchViewsDesc it embeds."""
         self._views_into(f.batch, f.batch.C, ref, planar, "pv_frame_views", outer=f)
 
+    def hdr_views(self, h, ref, planar=None):
+        """`frame_views` for an HdrViewsDesc (PQ / HLG taps mapped to SDR inside the launch: pv_hdr_views; 16-bit YUV 4:2:0
+        sources, whole videos or frame lists); the destination goes into the BatchViewsDesc it embeds."""
+        self._views_into(h.frames.batch, 3, ref, planar, "pv_hdr_views", outer=h)
+
     def box_views(self, d, ptr):
         """Fill a detection head's box buffer `ptr` (`alloc_boxes`) by pv_box_views: `d` is a BoxViewsDesc whose boxes, item
         window, records and capacity the caller (transforms.DevicePacker.fill_boxes) has set; the destination is filled in

@@ -109,8 +109,7 @@ int bv_run(const pv_batch_views_desc& desc, pv_stream_t stream) {
   RsItemLaunch g;
   RsTileLaunch tg;
   size_t lds, lds_t;
-  const uintptr_t misaligned = desc.src_dtype == PV_F32 ? 3 : (desc.src_dtype == PV_U16 ? 1 : 0);   // address bits `src` may not have
-  auto check_src = [=](const pv_view_source& v) { return reinterpret_cast<uintptr_t>(v.src) & misaligned ? PV_ERR_INVALID : PV_OK; };
+  const auto check_src = rs_check_video_src(desc.src_dtype);
   if (int e = rs_item_launch(desc, check_src, g, lds, tg, lds_t)) return e;
   // the strips of a run of upright items: the whole launch when no record is oriented
   auto upright = [&](const pv_batch_views_desc& d) -> int {

@@ -1,4 +1,5 @@
-// What pv_frames.hip and pv_frames16.hip share: the item of a workgroup of pv_frame_views and the launch of its 16-bit kernels.
+// What pv_frames.hip and pv_frames16.hip share: the item of a workgroup of pv_frame_views and the launch of its 16-bit kernels;
+// and what pv_frames.hip and pv_hdr.hip share: the host checks of the pointer table.
 #pragma once
 #include "pv_rs.h"
 
@@ -28,6 +29,34 @@ __device__ __forceinline__ FvItem fv_item(const pv_batch_views_desc& d, int zi, 
   typedef const uint64_t __attribute__((address_space(4))) * table_ptr;
   r.frame = (uintptr_t) reinterpret_cast<table_ptr>(reinterpret_cast<uintptr_t>(r.S->src))[ts];
   return r;
+}
+
+// The pointer table of a pv_frame_views_desc: both copies, a device copy at a multiple of 8, a positive length.
+inline int fv_check_table(const pv_frame_views_desc& f) {
+  if (!f.frame_ptrs || !f.frame_ptrs_dev || f.n_frame_ptrs <= 0) return PV_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(f.frame_ptrs_dev) % 8) return PV_ERR_INVALID;
+  return PV_OK;
+}
+
+// check_src (rs_item_launch) of a launch whose records are slices of that table: `src` is a slice [k, k + N) whose entries are
+// frames (non-null; fp32: 4-byte aligned; 16-bit samples: even).  What the check needs is captured by value: it runs once
+// per record, over every frame of it.
+inline auto fv_check_src(const pv_frame_views_desc& f) {
+  const uintptr_t base = reinterpret_cast<uintptr_t>(f.frame_ptrs_dev);
+  const uint64_t* table = f.frame_ptrs;
+  const uint64_t n_table = (uint64_t)f.n_frame_ptrs;
+  const bool f32 = f.batch.src_dtype == PV_F32, u16 = f.batch.src_dtype == PV_U16;   // outside their layouts both are refused before
+  return [=](const pv_view_source& v) {
+    const uintptr_t at = reinterpret_cast<uintptr_t>(v.src);
+    if (at < base || (at - base) % 8) return PV_ERR_INVALID;
+    const uint64_t k = (at - base) / 8;
+    if (k + (uint64_t)v.N > n_table) return PV_ERR_INVALID;
+    for (int i = 0; i < v.N; ++i) {
+      const uint64_t p = table[k + i];
+      if (!p || (f32 && p % 4) || (u16 && !rs_yuv16_even((uintptr_t)p))) return PV_ERR_INVALID;
+    }
+    return PV_OK;
+  };
 }
 
 }  // namespace

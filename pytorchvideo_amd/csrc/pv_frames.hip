@@ -64,27 +64,10 @@ __global__ __launch_bounds__(kRsThreads) void frame_yuv_kernel(const pv_batch_vi
 }
 
 // The pointer table, then rs_item_launch (pv_rs.h) for everything pv_batch_views checks and sizes too.  This entry point's own
-// part of a record is its `src`: a slice [k, k + N) of the table whose entries are frames (non-null; fp32: 4-byte aligned;
-// 16-bit samples: even).  What the check needs is captured by value: it runs once per record, over every frame of it.
+// part of a record is its `src`, a slice of the table (fv_check_table, fv_check_src: pv_frames.h).
 int fv_run(const pv_frame_views_desc& f, pv_stream_t stream) {
-  const pv_batch_views_desc& d = f.batch;
-  if (!f.frame_ptrs || !f.frame_ptrs_dev || f.n_frame_ptrs <= 0) return PV_ERR_INVALID;
-  const uintptr_t base = reinterpret_cast<uintptr_t>(f.frame_ptrs_dev);
-  if (base % 8) return PV_ERR_INVALID;
-  const uint64_t* table = f.frame_ptrs;
-  const uint64_t n_table = (uint64_t)f.n_frame_ptrs;
-  const bool f32 = d.src_dtype == PV_F32, u16 = d.src_dtype == PV_U16;   // outside their layouts both are refused before
-  auto check_src = [=](const pv_view_source& v) {
-    const uintptr_t at = reinterpret_cast<uintptr_t>(v.src);
-    if (at < base || (at - base) % 8) return PV_ERR_INVALID;
-    const uint64_t k = (at - base) / 8;
-    if (k + (uint64_t)v.N > n_table) return PV_ERR_INVALID;
-    for (int i = 0; i < v.N; ++i) {
-      const uint64_t p = table[k + i];
-      if (!p || (f32 && p % 4) || (u16 && !rs_yuv16_even((uintptr_t)p))) return PV_ERR_INVALID;
-    }
-    return PV_OK;
-  };
+  if (int e = fv_check_table(f)) return e;
+  const auto check_src = fv_check_src(f);
   RsItemLaunch g;
   RsTileLaunch tg;
   size_t lds, lds_t;

@@ -5,6 +5,8 @@
 //   pv_frames.hip     pv_frame_views                      the same with every frame addressed through a pointer table
 //   pv_frames16.hip   (launched from pv_frames.hip)       the 16-bit YUV kernels of pv_frame_views
 //   pv_orient.hip     (launched from pv_batch.hip and pv_frames.hip)   the tile kernels of oriented records (orient != 0)
+//   pv_hdr.hip        pv_hdr_views (a seventh entry point)             pv_batch_views / pv_frame_views on 16-bit YUV with the PQ / HLG
+//                                                                       tap map: its own strip and tile kernel wrappers
 // What they compute with is here, once: the pinned source coordinate, the destination forms with their stores, the taps and
 // blends, the two staged-strip bodies (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather) that the nine kernel templates
 // wrap (resample_crop_kernel; yuv_views_kernel, yuv16_views_kernel; batch_views_kernel, batch_yuv_kernel,
@@ -155,11 +157,16 @@ template <typename SMP> __device__ __forceinline__ float yuv_sample(const unsign
   else return (float)*reinterpret_cast<const unsigned short*>(lds + off);
 }
 
+// The tap map: what a YUV body does to a converted, clamped tap before the blend.  RsTapNone, the default, is nothing: the
+// tap enters the blend as it is (pv_yuv_views' rule).  Any other type is a callable over the pair of taps yuv_tap2 makes,
+// void operator()(f32x2 (&rgb)[3]) const, workgroup-uniform state in registers (pv_hdr.hip: the PQ / HLG to SDR map).
+struct RsTapNone { static constexpr bool kNone = true; };
+
 // Two taps of the virtual RGB frame -- the same column of the two source rows -- as packed fp32 pairs (v_pk_fma_f32 does
-// both for the price of one): per channel three fused multiply-adds in the header's order, then the clamp.
-template <typename SMP = unsigned char>
+// both for the price of one): per channel three fused multiply-adds in the header's order, then the clamp, then the tap map.
+template <typename SMP = unsigned char, typename MAP = RsTapNone>
 __device__ __forceinline__ void yuv_tap2(const float (&m)[12], const unsigned char* lds, int oy0, int ou0, int ov0, int oy1, int ou1,
-                                         int ov1, f32x2 (&rgb)[3]) {
+                                         int ov1, f32x2 (&rgb)[3], const MAP& map = MAP()) {
   const f32x2 Y = {yuv_sample<SMP>(lds, oy0), yuv_sample<SMP>(lds, oy1)}, U = {yuv_sample<SMP>(lds, ou0), yuv_sample<SMP>(lds, ou1)},
               V = {yuv_sample<SMP>(lds, ov0), yuv_sample<SMP>(lds, ov1)};
 #pragma unroll
@@ -168,6 +175,7 @@ __device__ __forceinline__ void yuv_tap2(const float (&m)[12], const unsigned ch
                         __builtin_elementwise_fma(yuv_splat(m[c * 4]), Y, yuv_splat(m[c * 4 + 3]))));
     rgb[c] = f32x2{fminf(fmaxf(v[0], 0.f), 255.f), fminf(fmaxf(v[1], 0.f), 255.f)};
   }
+  if constexpr (!MAP::kNone) map(rgb);
 }
 
 // The pinned blend and the affine map with the contraction spelled out, so that every instantiation gives the same bits:
@@ -375,10 +383,11 @@ __host__ __device__ __forceinline__ void rs_chroma_planes(bool inter, int64_t u_
 // SMP: the sample, unsigned char or unsigned short (16-bit little-endian codes: P010 / yuv420p10le and their 12- and 16-bit
 // kin).  Spans, source addresses and LDS offsets count SB = sizeof(SMP) bytes per luma column and CSTEP * SB per chroma
 // column; pitches and plane offsets are bytes in either case.  Two-byte samples need even source addresses (checked on the
-// host: rs_check_yuv16_even), which makes every 16-bit LDS read naturally aligned.
-template <int CSTEP, int FORM, typename D, typename SMP = unsigned char>
+// host: rs_check_yuv16_even), which makes every 16-bit LDS read naturally aligned.  MAP: the tap map (RsTapNone: none).
+template <int CSTEP, int FORM, typename D, typename SMP = unsigned char, typename MAP = RsTapNone>
 __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitch_y, int pitch_c, int c_base, const RsYuvSrc& s,
-                                             const RsDst& d, const float* yuv2rgb, int zi, int t, bool check_span) {
+                                             const RsDst& d, const float* yuv2rgb, int zi, int t, bool check_span,
+                                             const MAP& map = MAP()) {
   constexpr int G = RsGroup<FORM, D>::G;
   constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
   constexpr int SB = (int)sizeof(SMP);             // bytes from one luma column to the next
@@ -481,8 +490,8 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
       const int o0 = (i0x - xs0) * SB, o1 = (i1x - xs0) * SB;
       const int c0 = ((i0x >> 1) - cxs0) * CB, c1 = ((i1x >> 1) - cxs0) * CB;
       f32x2 p0[3], p1[3];                          // {row i0y, row i1y} of column i0x / i1x, per channel
-      yuv_tap2<SMP>(m, lds, yo0 + o0, uo0 + c0, vo0 + c0, yo1 + o0, uo1 + c0, vo1 + c0, p0);
-      yuv_tap2<SMP>(m, lds, yo0 + o1, uo0 + c1, vo0 + c1, yo1 + o1, uo1 + c1, vo1 + c1, p1);
+      yuv_tap2<SMP, MAP>(m, lds, yo0 + o0, uo0 + c0, vo0 + c0, yo1 + o0, uo1 + c0, vo1 + c0, p0, map);
+      yuv_tap2<SMP, MAP>(m, lds, yo0 + o1, uo0 + c1, vo0 + c1, yo1 + o1, uo1 + c1, vo1 + c1, p1, map);
 #pragma unroll
       for (int c = 0; c < 3; ++c) out[c][j] = yuv_blend(ly0, ly1, lx0, lx1, p0[c], p1[c], sc[c], sh[c]);
       out[3][j] = 0.f;
@@ -651,10 +660,10 @@ __device__ __forceinline__ void rs_tile_rgb(unsigned char* lds, const RsTileLaun
   }
 }
 
-// CSTEP / FORM / D / SMP: as rs_strip_yuv.
-template <int CSTEP, int FORM, typename D, typename SMP>
+// CSTEP / FORM / D / SMP / MAP: as rs_strip_yuv.
+template <int CSTEP, int FORM, typename D, typename SMP, typename MAP = RsTapNone>
 __device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaunch& g, const RsYuvSrc& s, int orient, const RsDst& d,
-                                            const float* yuv2rgb, int zi, int t) {
+                                            const float* yuv2rgb, int zi, int t, const MAP& map = MAP()) {
   constexpr int G = RsGroup<FORM, D>::G;
   constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
   constexpr int SB = (int)sizeof(SMP);             // bytes from one luma column to the next
@@ -758,8 +767,8 @@ __device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaun
       tap(i0y, i1x, y01, u01, v01);
       tap(i1y, i1x, y11, u11, v11);
       f32x2 p0[3], p1[3];                          // {row i0y, row i1y} of column i0x / i1x, per channel
-      yuv_tap2<SMP>(m, lds, y00, u00, v00, y10, u10, v10, p0);
-      yuv_tap2<SMP>(m, lds, y01, u01, v01, y11, u11, v11, p1);
+      yuv_tap2<SMP, MAP>(m, lds, y00, u00, v00, y10, u10, v10, p0, map);
+      yuv_tap2<SMP, MAP>(m, lds, y01, u01, v01, y11, u11, v11, p1, map);
 #pragma unroll
       for (int c = 0; c < 3; ++c) out[c][j] = yuv_blend(ly0, ly1, lx0, lx1, p0[c], p1[c], sc[c], sh[c]);
       out[3][j] = 0.f;
@@ -892,6 +901,13 @@ inline int rs_check_yuv16_even(uintptr_t base, int y_pitch, int c_pitch, int64_t
 
 // ---- an item-sourced launch (pv_batch_views, pv_frame_views): validated and sized here, once -----------------------------
 inline bool rs_same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof(float)) == 0; }
+
+// check_src of a launch whose records are whole videos (pv_batch_views; pv_hdr_views without a pointer table): `src` is one
+// allocation of the source dtype, 4-byte aligned for fp32, even for 16-bit samples.
+inline auto rs_check_video_src(int src_dtype) {
+  const uintptr_t misaligned = src_dtype == PV_F32 ? 3 : (src_dtype == PV_U16 ? 1 : 0);   // address bits `src` may not have
+  return [=](const pv_view_source& v) { return reinterpret_cast<uintptr_t>(v.src) & misaligned ? PV_ERR_INVALID : PV_OK; };
+}
 
 // One record of such a launch: positive sizes, windows inside the scaled frame, sy / sx the library's own division, for YUV
 // the planes inside a frame, at even bytes for two-byte samples, and what its `src` points to (check_src: see below).

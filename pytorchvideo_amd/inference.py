@@ -57,17 +57,21 @@ class VideoPredictor:
     (`packer.video_batch` / `fill_batch`, `pv_frame_views`), the same items at the same batch positions.
     `orientation` (`transforms.orientation_code`): the video is STORED turned and / or mirrored, as a decoder hands out a
     portrait phone clip; a non-zero code walks it as a one-video batch too and reads it in place.
+    `hdr` ("pq", "hlg" or (transfer, `transforms.tone_params(...)`), for the 10- to 16-bit YUV layouts only): the video is
+    BT.2020 PQ / HLG and every tap is mapped to BT.709 SDR inside the ingest launch (`pv_hdr_views`, as `DevicePacker`); such
+    a predictor walks every video as a one-video batch.
     After a call `video_ensembler.counts` (and `clip_ensembler.counts`) hold the rows folded."""
 
     def __init__(self, deployed, clip_sampler, mean, std, div255, short_side, crop_size, spatial_idx=(0, 1, 2),
-                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), coded_height=None, height=None):
+                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), coded_height=None, height=None,
+                 hdr=None):
         if getattr(deployed, "_pv_load_boxes", None) is not None:
             raise ValueError("VideoPredictor scores videos; a detection model's boxes belong to key frames"
                              " (in any source layout, %s included)" % src_layout)
         if method not in ("sum", "max"):
             raise NotImplementedError("ensemble method %r (the reference knows 'sum' and 'max')" % method)
         self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout,
-                                   yuv, coded_height, height)
+                                   yuv, coded_height, height, hdr=hdr)
         self.sampler, self.method, self.src_layout = clip_sampler, method, src_layout
         self.video_ensembler = self.clip_ensembler = None
 
@@ -75,7 +79,7 @@ class VideoPredictor:
     def __call__(self, video, fps, return_clip_scores=False, orientation=0):
         p = self.packer
         device = p.sess.device
-        if isinstance(video, FrameList) or orientation:
+        if isinstance(video, FrameList) or orientation or p.hdr is not None:   # HDR taps: pv_hdr_views, an item-sourced launch
             return self._call_frames(video, fps, return_clip_scores, orientation)
         if video.dim() != (3 if p.is_yuv else 4):
             raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(video.shape)))
@@ -141,17 +145,19 @@ class VideoBatchPredictor:
     walked in chunks of the deploy batch, so a forward holds views of several videos and only the LAST forward of a call can
     be short; the frame tables of all videos are built, range-checked and uploaded once per call.
     `return_clip_scores=True` adds a list of V tensors [n_clips_j, num_classes].  `orientation` is one code
-    (`transforms.orientation_code`) or one per video: videos stored turned and / or mirrored are read in place.  After a call
+    (`transforms.orientation_code`) or one per video: videos stored turned and / or mirrored are read in place.  `hdr` as for
+    `VideoPredictor`: one transfer and one tone table for the videos of the predictor.  After a call
     `video_ensembler.counts` holds the views folded per video (and `clip_ensembler.counts` per clip, all videos' clips one after another)."""
 
     def __init__(self, deployed, clip_sampler, mean, std, div255, short_side, crop_size, spatial_idx=(0, 1, 2),
-                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False)):
+                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), hdr=None):
         if getattr(deployed, "_pv_load_boxes", None) is not None:
             raise ValueError("VideoBatchPredictor scores videos; a detection model's boxes belong to key frames"
                              " (in any source layout, %s included)" % src_layout)
         if method not in ("sum", "max"):
             raise NotImplementedError("ensemble method %r (the reference knows 'sum' and 'max')" % method)
-        self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv)
+        self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv,
+                                   hdr=hdr)
         self.sampler, self.method, self.src_layout = clip_sampler, method, src_layout
         self.video_ensembler = self.clip_ensembler = None
         self.forwards = 0                                        # forwards of the last call
@@ -237,6 +243,7 @@ class KeyframeDetector:
     LIST of videos, with `timestamps` and `boxes` given per video and `fps` one number or one per video.  `orientation` is one
     code (`transforms.orientation_code`) or one per video: the video is stored turned and / or mirrored and the boxes are
     pixels of the STORED frame (a detector that ran on the decoder's surfaces); `pv_box_views` takes them into the view.
+    `hdr` as for `VideoPredictor` (PQ / HLG sources in a 10- to 16-bit YUV layout, mapped to SDR per tap).
 
     Frame tables, the box list and its key-frame index are uploaded once per call; per forward there are only the ingest,
     one `pv_box_views` launch and the replay.  The key frames are walked by `keyframe_chunks`.  Everything is validated
@@ -244,7 +251,7 @@ class KeyframeDetector:
     over all videos of the call, in order) of each."""
 
     def __init__(self, deployed, clip_duration, mean, std, div255, short_side, crop_size=None, spatial_idx=1,
-                 frame_ratios=None, src_layout="NTHWC", yuv=("bt709", False), coded_height=None, height=None):
+                 frame_ratios=None, src_layout="NTHWC", yuv=("bt709", False), coded_height=None, height=None, hdr=None):
         if getattr(deployed, "_pv_load_boxes", None) is None or getattr(deployed, "_pv_box_capacity", None) is None:
             raise ValueError("KeyframeDetector scores the boxes of key frames with a detection model converted as a whole "
                              "by convert_to_deployable_form(det, (x, bboxes)); a classification model scores videos: "
@@ -254,7 +261,7 @@ class KeyframeDetector:
         if not isinstance(spatial_idx, int):
             raise ValueError("a detection model takes one view: its boxes belong to one crop")
         self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout,
-                                   yuv, coded_height, height, keyframes=True)
+                                   yuv, coded_height, height, keyframes=True, hdr=hdr)
         self.clip_duration, self.src_layout = clip_duration, src_layout
         self.forwards, self.chunks = 0, []
 
@@ -388,17 +395,19 @@ class StreamPredictor:
     it have been read on the host, or after a synchronise on the launch stream -- not when `push` returns.
 
     `orientation` (`transforms.orientation_code`): the frames are stored turned and / or mirrored and are read in place.
+    `hdr` as for `VideoPredictor`: the surfaces are PQ / HLG and every tap is mapped to SDR inside the ingest launch.
     `deployed` is a classification form; one object scores one stream; `reset()` starts a new one.  Windows are scored
     independently: nothing is smoothed or voted over windows."""
 
     def __init__(self, deployed, clip_duration, stride, fps, mean, std, div255, short_side, crop_size, spatial_idx=(1,),
-                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), orientation=0):
+                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), orientation=0, hdr=None):
         if getattr(deployed, "_pv_load_boxes", None) is not None:
             raise ValueError("StreamPredictor scores the windows of a stream with a classification form; a detection model's "
                              "boxes belong to key frames: KeyframeDetector")
         if method not in ("sum", "max"):
             raise NotImplementedError("ensemble method %r (the reference knows 'sum' and 'max')" % method)
-        self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv)
+        self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv,
+                                   hdr=hdr)
         self.method, self.src_layout, self.orientation = method, src_layout, orientation   # a stream has one orientation
         self.state = StreamState(clip_duration, stride, fps)
         self._frames = []

@@ -20,6 +20,11 @@ Decoder-native frames -- YUV 4:2:0 as NV12 / NV21 (what a GPU decoder writes) or
 a source layout of that same pass (`pv_yuv_views`): `yuv_matrix` composes the conversion, `yuv420_to_rgb` is the host mirror
 of the tap rule, and `device_scale_crop` / `DevicePacker` / `inference.VideoPredictor` take `src_layout="NV12"` and friends.
 
+HDR streams -- most 10-bit footage: a phone's HLG, HDR10 / AV1 PQ -- give BT.2020 R'G'B' under a PQ or HLG curve, which a
+network trained on BT.709 SDR misreads.  `hdr="pq"` / `"hlg"` / `(transfer, tone_params(...))` on `device_scale_crop`,
+`DevicePacker` and the predictors maps every tap to SDR inside the same launch (`pv_hdr_views`); `hdr_to_sdr` is the host
+mirror, composed with `yuv420_to_rgb`.
+
 Many videos per forward: `DevicePacker.video_batch` + `fill_batch` give every item of the deploy batch a source of its own
 (`pv_batch_views`), so that the views of videos of any lengths and frame sizes share a forward (`inference.VideoBatchPredictor`).
 
@@ -421,6 +426,108 @@ def yuv420_to_rgb(frames: torch.Tensor, layout: str, matrix, coded_height=None, 
     return torch.clamp(rgb, 0.0, 255.0).float()
 
 
+# --------------------------------------------------------------------------- HDR sources: PQ / HLG taps to BT.709 SDR
+HDR_TRANSFERS = ("pq", "hlg")
+HDR_GAMUTS = {"bt2020_to_bt709": ((1.6605, -0.5876, -0.0728), (-0.1246, 1.1329, -0.0083), (-0.0182, -0.1006, 1.1187)),   # BT.2087
+              None: ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))}
+_PQ_M1, _PQ_M2 = 2610.0 / 16384.0, 2523.0 / 4096.0 * 128.0
+_PQ_C1, _PQ_C2, _PQ_C3 = 3424.0 / 4096.0, 2413.0 / 4096.0 * 32.0, 2392.0 / 4096.0 * 32.0
+_HLG_A = 0.17883277
+_HLG_B = 1.0 - 4.0 * _HLG_A
+_HLG_C = 0.5 - _HLG_A * math.log(4.0 * _HLG_A)
+_OETF_BETA, _OETF_ALPHA = 0.018053968510807, 1.09929682680944          # BT.2020's continuous constants
+_TONE_OFF = 3e38                                                        # a knee no light reaches: the curve is never taken
+
+
+def tone_params(transfer: str, peak_nits: float = 1000.0, white_nits: float = 203.0, knee: float = 0.3, tone_map: str = "mobius",
+                gamut="bt2020_to_bt709") -> torch.Tensor:
+    """The fp32 [16] `tone` table of `pv_hdr_views` (include/pv_mi355x.h, "HDR sources"), composed in float64:
+    [0] the scale to SDR reference white (PQ: 10000 / white_nits; HLG: peak_nits / white_nits), [1] HLG's system gamma - 1
+    (gamma = 1.2 + 0.42 log10(peak_nits / 1000); 0 for PQ), [2..5] the knee j and s, a', b' of the hue-preserving "mobius"
+    curve on max-RGB -- the identity up to j, C1 there, and P = peak_nits / white_nits goes to 1 -- or, `tone_map="clip"`,
+    a knee that is never reached, [6..14] the gamut matrix row-major (`gamut=None`: the identity), [15] 0."""
+    if transfer not in HDR_TRANSFERS:
+        raise ValueError("transfer is one of %s, got %r" % (HDR_TRANSFERS, transfer))
+    if tone_map not in ("mobius", "clip"):
+        raise ValueError("tone_map is 'mobius' or 'clip', got %r" % (tone_map,))
+    if gamut not in HDR_GAMUTS:
+        raise ValueError("gamut is 'bt2020_to_bt709' or None, got %r" % (gamut,))
+    peak, white, j = float(peak_nits), float(white_nits), float(knee)
+    if not (white > 0.0 and peak > white):
+        raise ValueError("peak_nits lies above white_nits, and both are positive: got %r and %r" % (peak_nits, white_nits))
+    if not 0.0 < j < 1.0:
+        raise ValueError("knee lies inside (0, 1), got %r" % (knee,))
+    p = peak / white
+    if transfer == "pq":
+        head = [10000.0 / white, 0.0]
+    else:
+        head = [p, 1.2 + 0.42 * math.log10(peak / 1000.0) - 1.0]
+    if tone_map == "clip":
+        curve = [_TONE_OFF, 1.0, 0.0, 0.0]
+    else:
+        a = -j * j * (p - 1.0) / (j * j - 2.0 * j + p)
+        b = (j * j - 2.0 * j * p + p) / (p - 1.0)
+        curve = [j, (b * b + 2.0 * b * j + j * j) / (b - a), a, b]
+    return torch.tensor(head + curve + [g for row in HDR_GAMUTS[gamut] for g in row] + [0.0], dtype=torch.float64).float()
+
+
+def _transfer_code(transfer):
+    if isinstance(transfer, str) and transfer in HDR_TRANSFERS:
+        return HDR_TRANSFERS.index(transfer) + 1               # PV_TRANSFER_PQ = 1, PV_TRANSFER_HLG = 2
+    if transfer in (1, 2) and not isinstance(transfer, bool):
+        return int(transfer)
+    raise ValueError("transfer is one of %s, got %r" % (HDR_TRANSFERS, transfer))
+
+
+def hdr_to_sdr(rgb255: torch.Tensor, transfer, tone) -> torch.Tensor:
+    """The tap map of `pv_hdr_views` on the host, in float64: `rgb255` [..., 3, H, W] holds BT.2020 R'G'B' under the PQ or HLG
+    curve in 0..255 -- what `yuv420_to_rgb` gives for an HDR stream's matrix --, `tone` is `tone_params`' table (its fp32
+    values are what the device computes with).  Returns the BT.709-coded SDR frame in 0..255, float64, same shape: every
+    pixel on its own, to linear light, the tone curve on max-RGB, the gamut matrix with its clamp, BT.2020's OETF."""
+    code = _transfer_code(transfer)
+    t = torch.as_tensor(tone).detach().to("cpu", torch.float64).reshape(-1)
+    if t.numel() != 16:
+        raise ValueError("tone holds 16 values (tone_params), got %d" % t.numel())
+    x = torch.as_tensor(rgb255).detach().to("cpu", torch.float64)
+    if x.dim() < 3 or x.shape[-3] != 3:
+        raise ValueError("expected [..., 3, H, W], got %s" % (tuple(x.shape),))
+    e = x / 255.0
+    if code == 1:
+        p = e ** (1.0 / _PQ_M2)
+        lin = (torch.clamp(p - _PQ_C1, min=0.0) / (_PQ_C2 - _PQ_C3 * p)) ** (1.0 / _PQ_M1) * t[0]
+    else:
+        s = torch.where(e <= 0.5, e * e / 3.0, (torch.exp((e - _HLG_C) / _HLG_A) + _HLG_B) / 12.0)
+        ys = 0.2627 * s[..., 0:1, :, :] + 0.6780 * s[..., 1:2, :, :] + 0.0593 * s[..., 2:3, :, :]
+        gain = torch.where(ys > 0.0, torch.clamp(ys, min=1e-300) ** t[1] * t[0], torch.zeros_like(ys))
+        lin = s * gain
+    m = lin.amax(dim=-3, keepdim=True)
+    safe = torch.where(m > t[2], m, torch.ones_like(m))
+    lin = lin * torch.where(m > t[2], t[3] * (safe + t[4]) / ((safe + t[5]) * safe), torch.ones_like(m))
+    lin = torch.clamp(torch.einsum("ck,...khw->...chw", t[6:15].reshape(3, 3), lin), 0.0, 1.0)
+    v = torch.where(lin < _OETF_BETA, 4.5 * lin, _OETF_ALPHA * lin ** 0.45 - (_OETF_ALPHA - 1.0))
+    return 255.0 * v
+
+
+def _hdr_of(hdr, src_layout):
+    """`hdr` as every entry point takes it -- None, "pq" / "hlg" (`tone_params` with its defaults) or (transfer, tone tensor)
+    -- as (PV_TRANSFER code, fp32 [16] host tensor), or None.  ValueError for anything else, and for a source layout that is
+    not one of `YUV16_LAYOUTS`: 8-bit and RGB HDR sources do not exist in practice, and no path may drop the map."""
+    if hdr is None:
+        return None
+    if isinstance(hdr, str):
+        hdr = (hdr, tone_params(hdr))
+    if not (isinstance(hdr, (tuple, list)) and len(hdr) == 2 and isinstance(hdr[1], torch.Tensor)):
+        raise ValueError("hdr is None, 'pq', 'hlg' or (transfer, tone_params(...)), got %r" % (hdr,))
+    code = _transfer_code(hdr[0])
+    tone = hdr[1].detach().to("cpu", torch.float32).reshape(-1).contiguous()
+    if tone.numel() != 16:
+        raise ValueError("tone holds 16 values (tone_params), got %d" % tone.numel())
+    if src_layout not in YUV16_LAYOUTS:
+        raise ValueError("hdr= maps the taps of a 10- to 16-bit YUV 4:2:0 source (src_layout one of %s), not of %r"
+                         % (YUV16_LAYOUTS, src_layout))
+    return code, tone
+
+
 # --------------------------------------------------------------------------- fused device path
 def _affine(mean, std, div255, channels, device):
     """(ch_scale, ch_shift) of Div255 + Normalize as fp32 device tensors, or (None, None)."""
@@ -584,9 +691,10 @@ def _clip_rows(n_clips, clip_frames, num_frames):
     return (torch.arange(n_clips)[:, None] * clip_frames + idx[None, :]).to(torch.int32).contiguous()
 
 
-def _scale_crop_launch(d, entry, what, b, c, affine, dtype, device):
+def _scale_crop_launch(d, entry, what, b, c, affine, dtype, device, outer=None):
     """The tail of `device_scale_crop` for either kind of source: the planar [b * n_views, c, T, Ho, Wo] destination of
-    `dtype`, the affine map (`affine`: mean, std, div255) and the launch of `entry` on `device`'s current stream."""
+    `dtype`, the affine map (`affine`: mean, std, div255) and the launch of `entry` on `device`'s current stream (on `outer`,
+    the descriptor that embeds `d`, when given)."""
     import ctypes as C
     from . import _lib as L
     scale, shift = _affine(*affine, c, device)
@@ -595,17 +703,24 @@ def _scale_crop_launch(d, entry, what, b, c, affine, dtype, device):
     d.dst, d.dst_layout = out.data_ptr(), L.DST_NCTHW
     d.dst_dtype = L.PV_BF16 if dtype == torch.bfloat16 else L.PV_F32
     with torch.cuda.device(device):
-        L.check(getattr(L.lib(), entry)(C.byref(d), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), what)
+        L.check(getattr(L.lib(), entry)(C.byref(d if outer is None else outer),
+                                        C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), what)
     return out
 
 
-def _device_scale_crop_yuv(frames, short_side, crop_size, views, affine, num_frames, dtype, src_layout, yuv, coded_height, height):
+def _device_scale_crop_yuv(frames, short_side, crop_size, views, affine, num_frames, dtype, src_layout, yuv, coded_height, height,
+                           hdr=None):
     device = frames.device if frames.is_cuda else torch.device("cuda", torch.cuda.current_device())
     frames = frames.to(device, non_blocking=True)
     geom = yuv_geometry(frames, src_layout, coded_height, height)
     b, t_src = (1, frames.shape[0]) if frames.dim() == 3 else tuple(frames.shape[:2])
     table = _clip_rows(b, t_src, num_frames if num_frames is not None else t_src).to(device)
     matrix = _yuv_matrix_of(yuv, src_layout).float().reshape(12).to(device)
+    if hdr is not None:                                    # the clips as ONE source of pv_hdr_views, row b of the table per clip
+        geo = _view_geometry(geom["Hs"], geom["Ws"], short_side, crop_size, views)
+        src = HdrVideoSource(frames, geom, geo, b, len(views), device)
+        h = src.desc(table, matrix, src_layout, (crop_size, crop_size), (hdr[0], hdr[1].to(device)), 0, b * len(views))
+        return _scale_crop_launch(h.frames.batch, "pv_hdr_views", "hdr_views", b, 3, affine, dtype, device, outer=h)
     d = _yuv_desc(frames, geom, table, matrix, short_side, crop_size, views)
     entry = "pv_yuv16_views" if src_layout in YUV16_LAYOUTS else "pv_yuv_views"
     return _scale_crop_launch(d, entry, "yuv_views", b, 3, affine, dtype, device)
@@ -820,10 +935,59 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
                       ptrs, ptrs_dev, first)
 
 
+class HdrVideoSource:
+    """ONE upright video (or the frame sequence of B materialised clips) as the single record of `pv_hdr_views` launches: the
+    `pv_view_source` record and the video-major item sequence of its `n_clips` x `n_views` views, on the host and -- the very
+    same bytes -- on the device, built and uploaded once; `desc` is the descriptor of a window of that sequence.  The paths
+    that launch the one-source `pv_yuv16_views` for `hdr=None` run through this: that entry point has no tap map."""
+
+    def __init__(self, frames, geom, geo, n_clips, n_views, device):
+        from . import _lib as L
+        hn, wn, offsets = geo
+        self.frames, self.n_clips, self.n_views = frames, n_clips, n_views
+        self.sources = (L.ViewSource * 1)()
+        rec = self.sources[0]
+        for k in _YUV_PLANE_FIELDS:
+            setattr(rec, k, geom[k])
+        _set_views(rec, hn, wn, offsets)
+        rec.src, rec.N, rec.Hs, rec.Ws = frames.data_ptr(), geom["N"], geom["Hs"], geom["Ws"]
+        rec.sy, rec.sx = geom["Hs"] / hn, geom["Ws"] / wn          # as build_video_batch divides
+        items_t = batch_items([n_clips], n_views)[0]
+        self.items = (L.ViewItem * items_t.shape[0]).from_buffer_copy(items_t.numpy().tobytes())
+        self.sources_dev = torch.frombuffer(self.sources, dtype=torch.uint8).to(device)
+        self.items_dev = torch.frombuffer(self.items, dtype=torch.uint8).to(device)
+        self.key = self.key_of(frames, geom, geo, n_clips, n_views)
+
+    @staticmethod
+    def key_of(frames, geom, geo, n_clips, n_views):
+        """What the record and the item sequence depend on: two videos with one key share them."""
+        return (frames.data_ptr(), tuple(sorted(geom.items())), geo[0], geo[1], tuple(geo[2]), n_clips, n_views)
+
+    def desc(self, table, matrix, src_layout, window, hdr, item0, n_items):
+        """The HdrViewsDesc of items [item0, item0 + n_items) (destination and affine map are the caller's); `table` int32
+        [n_clips, T], `matrix` fp32 [12] and the tone table `hdr[1]` are on the device and stay alive until the launch has
+        run (the descriptor's `keep` holds them)."""
+        import ctypes as C
+        from . import _lib as L
+        h = L.HdrViewsDesc()
+        d = h.frames.batch
+        d.sources, d.sources_dev = C.addressof(self.sources), self.sources_dev.data_ptr()
+        first = min(item0, len(self.items) - 1) * C.sizeof(L.ViewItem)      # n_items == 0: any valid address, never read
+        d.items, d.items_dev = C.addressof(self.items) + first, self.items_dev.data_ptr() + first
+        d.t_index, d.n_rows, d.t_stride = table.data_ptr(), table.shape[0], table.stride(0)
+        d.n_sources, d.n_items, d.C, d.T = 1, n_items, 3, table.shape[1]
+        d.src_layout, d.src_dtype = _src_codes(src_layout, None)
+        d.c_step, d.yuv2rgb = (2 if src_layout in _YUV_INTERLEAVED else 1), matrix.data_ptr()
+        d.Ho, d.Wo, d.n_views = window[0], window[1], self.n_views
+        h.transfer, h.tone = hdr[0], hdr[1].data_ptr()
+        h.keep = (self, table, matrix, hdr[1])
+        return h
+
+
 @torch.no_grad()
 def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std=None, div255=False, num_frames=None,
                       dtype=torch.bfloat16, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None,
-                      orientation=0):
+                      orientation=0, hdr=None):
     """uniform_crop(short_side_scale(Normalize(Div255(uniform_temporal_subsample(clip, num_frames))))) for every view of
     `spatial_idx` in one launch of `pv_resample_crop`: a planar [B * n_views, C, T, crop, crop] tensor of `dtype` (bf16 or
     fp32) on the GPU, item b * n_views + v being view v of clip b.  `clip` is [B,C,T,H,W] ("NCTHW"; uint8 or float) or the
@@ -833,7 +997,9 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
     [T, Hc*3/2, W]: one clip) with the strides it has (`yuv_geometry`: `coded_height`, `height`), converted tap by tap inside
     the same launch (`pv_yuv_views`) by `yuv`: (standard, full_range) for `yuv_matrix`, or a 3 x 4 matrix.  With a layout of
     `YUV16_LAYOUTS` ("P010", "I010", ...) the clip is uint16 or int16 and read by `pv_yuv16_views`; a (standard, full_range)
-    pair is composed with the layout's depth and bit alignment: `src_layout="P010", yuv=("bt2020", False)`.
+    pair is composed with the layout's depth and bit alignment: `src_layout="P010", yuv=("bt2020", False)`.  `hdr` -- "pq",
+    "hlg" or (transfer, `tone_params(...)`), for such a layout only -- maps every tap from BT.2020 PQ / HLG to BT.709 SDR
+    before the blend, in the same launch (`pv_hdr_views`; `hdr_to_sdr` of `yuv420_to_rgb` is the host mirror).
 
     Materialised clips go through the one-source entry points, whose descriptors have no orientation: a non-zero
     `orientation` is refused; `DevicePacker.video_batch` reads turned and mirrored videos in place."""
@@ -843,9 +1009,10 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
     if dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("dtype is torch.bfloat16 or torch.float32")
     views = _views(spatial_idx)
+    hdr = _hdr_of(hdr, src_layout)                             # ValueError for an 8-bit or RGB source
     if src_layout in _YUV_ANY:
         return _device_scale_crop_yuv(clip, short_side, crop_size, views, (mean, std, div255), num_frames, dtype, src_layout,
-                                      yuv, coded_height, height)
+                                      yuv, coded_height, height, hdr)
     _source_geometry(clip, src_layout)
     device = clip.device if clip.is_cuda else torch.device("cuda", torch.cuda.current_device())
     clip = _device_source(clip, device)
@@ -881,6 +1048,8 @@ class DevicePacker:
     `YUV16_LAYOUTS` ("P010" / "P012" / "P016" / "I010" / "I012" / "I016": uint16 or int16 tensors, what a decoder hands out
     for 10- to 16-bit streams) go through every one of these paths the same way (`pv_yuv16_views`, `PV_U16`); a
     (standard, full_range) pair is composed with the layout's depth and bit alignment, and no narrowing pass exists.
+    `hdr` -- "pq", "hlg" or (transfer, `tone_params(...)`), for a layout of `YUV16_LAYOUTS` only (a ValueError otherwise) --
+    maps every tap from BT.2020 PQ / HLG to BT.709 SDR before the blend: every path of such a packer launches `pv_hdr_views`.
 
     `fill_video(video, tables, i0, n)` + `launch()` run the resampling packer on ONE decoded video instead of clips: items
     [i0, i0 + n) of its clips x views sequence, the clips being rows of a frame table (`data.clip_frame_table`, uploaded by
@@ -900,7 +1069,8 @@ class DevicePacker:
     The clip-at-a-time `packer(clip, bboxes)` keeps mapping the boxes on the host and keeps refusing YUV clips."""
 
     def __init__(self, deployed, mean=None, std=None, div255=False, frame_ratios=None, short_side=None, crop_size=None,
-                 spatial_idx=1, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None, keyframes=False):
+                 spatial_idx=1, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None, keyframes=False,
+                 hdr=None):
         self.subs = None
         if (short_side is None) != (crop_size is None) and not (keyframes and crop_size is None):
             raise ValueError("short_side and crop_size are given together (short_side alone -- no crop -- is a mode of the "
@@ -912,6 +1082,8 @@ class DevicePacker:
         self.short_side, self.crop_size, self.src_layout = short_side, crop_size, src_layout
         self.is_yuv, self.coded_height, self.height = src_layout in _YUV_ANY, coded_height, height
         self.is_yuv16 = src_layout in YUV16_LAYOUTS            # 16-bit samples: pv_yuv16_views / PV_U16
+        self.hdr = _hdr_of(hdr, src_layout)                    # (PV_TRANSFER code, tone table) or None; on the device below
+        self._hdr_src = None
         if self.is_yuv and not self.keyframes and (getattr(deployed, "_pv_load_boxes", None) is not None):
             raise ValueError("a detection model does not take %s frames: its boxes are mapped through the scaling and the crop "
                              "of an RGB clip on the host, and that path is not built for YUV sources (the key-frame path, "
@@ -924,7 +1096,7 @@ class DevicePacker:
             # sub-plan's input buffers, then ONE launch of the joint graph
             self.model = deployed
             self.subs = [DevicePacker(p, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv,
-                                      coded_height, height, keyframes) for p in deployed.parts]
+                                      coded_height, height, keyframes, hdr) for p in deployed.parts]
             self.window = self.subs[0].window
             self.sess, self.refs = self.subs[0].sess, self.subs[0].refs
             self.frame_ratios = self.subs[0].frame_ratios
@@ -960,6 +1132,8 @@ class DevicePacker:
         self._planar = {}
         self._clip_tables = {}
         self.yuv_matrix = _yuv_matrix_of(yuv, src_layout).float().reshape(12).to(self.sess.device) if self.is_yuv else None
+        if self.hdr is not None:
+            self.hdr = (self.hdr[0], self.hdr[1].to(self.sess.device))
 
     def _t_index(self, t_src, ref):
         key = (t_src, ref.T)
@@ -1162,6 +1336,15 @@ class DevicePacker:
         from . import _lib as L
         self._src = (video, tables)                        # alive until the launch has run
         c, nf, hs, ws, geom, geo = source
+        if self.hdr is not None:
+            # pv_yuv16_views has no tap map: the video is the one record of pv_hdr_views launches, uploaded once per video
+            if self._hdr_src is None or self._hdr_src.key != HdrVideoSource.key_of(video, geom, geo, tables[0].shape[0], len(self.views)):
+                self._hdr_src = HdrVideoSource(video, geom, geo, tables[0].shape[0], len(self.views), self.sess.device)
+            for i, (ref, tab) in enumerate(zip(self.refs, tables)):
+                h = self._hdr_src.desc(tab, self.yuv_matrix, self.src_layout, self.window, self.hdr, item0, n_items)
+                _set_affine(h.frames.batch, self.scale, self.shift)
+                self.sess.hdr_views(h, ref, planar=self._planar_for(i, ref))
+            return
         for i, (ref, tab) in enumerate(zip(self.refs, tables)):
             if self.is_yuv:
                 d = _yuv_desc(video, geom, tab, self.yuv_matrix, self.short_side, self.crop_size, self.views, geo)
@@ -1236,7 +1419,8 @@ class DevicePacker:
         from . import _lib as L
         self._src = batch                                  # alive until the launch has run
         for i, (ref, tab) in enumerate(zip(self.refs, batch.tables)):
-            f = L.FrameViewsDesc() if batch.frame_ptrs is not None else None
+            h = L.HdrViewsDesc() if self.hdr is not None else None           # pv_hdr_views: either source form, tap map behind
+            f = h.frames if h is not None else (L.FrameViewsDesc() if batch.frame_ptrs is not None else None)
             d = L.BatchViewsDesc() if f is None else f.batch
             d.sources, d.sources_dev = C.addressof(batch.sources), batch.sources_dev.data_ptr()
             first = min(item0, batch.total - 1) * C.sizeof(L.ViewItem)      # n_items == 0: any valid address, never read
@@ -1251,9 +1435,14 @@ class DevicePacker:
             if f is None:
                 self.sess.batch_views(d, ref, planar=self._planar_for(i, ref))
                 continue
-            f.frame_ptrs, f.frame_ptrs_dev = batch.frame_ptrs.data_ptr(), batch.frame_ptrs_dev.data_ptr()
-            f.n_frame_ptrs = batch.frame_ptrs.numel()
-            self.sess.frame_views(f, ref, planar=self._planar_for(i, ref))
+            if batch.frame_ptrs is not None:
+                f.frame_ptrs, f.frame_ptrs_dev = batch.frame_ptrs.data_ptr(), batch.frame_ptrs_dev.data_ptr()
+                f.n_frame_ptrs = batch.frame_ptrs.numel()
+            if h is None:
+                self.sess.frame_views(f, ref, planar=self._planar_for(i, ref))
+                continue
+            h.transfer, h.tone = self.hdr[0], self.hdr[1].data_ptr()
+            self.sess.hdr_views(h, ref, planar=self._planar_for(i, ref))
 
     # ------------------------------------------------------------------------- key-frame detection (pv_box_views)
     @property
