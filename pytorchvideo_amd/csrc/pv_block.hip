@@ -157,12 +157,37 @@ __global__ __launch_bounds__(512, 2) void bottleneck_block_kernel(const pv_bottl
 
   // ---- conv_a's filter and the folded BatchNorms -> LDS (once per workgroup; L2-resident after the first workgroups) ----
   {
+    // every request first (clamped index where a thread has no element; the trip counts are compile-time), ONE wait, then the
+    // LDS writes: written as copy loops this was a memory round trip per iteration, 6 for the 43 KB of the res4 filter plus
+    // one per table, before the first plane was asked for
     const u32x4* wa = static_cast<const u32x4*>(d.wa);
     u32x4* la = reinterpret_cast<u32x4*>(s_wa);
-    for (int i = tid; i < G::WA_BYTES / 16; i += 512) la[i] = wa[i];
-    for (int i = tid; i < CP; i += 512) { s_sa[i] = d.sa[i]; s_ha[i] = d.ha[i]; }
-    if constexpr (MODE == 0)
-      for (int i = tid; i < COUTP; i += 512) { s_sc[i] = i < d.cout ? d.sc[i] : 0.f; s_hc[i] = i < d.cout ? d.hc[i] : 0.f; }
+    constexpr int NWA = G::WA_BYTES / 16, WA_TRIPS = (NWA + 511) / 512;
+    static_assert(CP <= 512 && COUTP <= 512, "one BatchNorm table entry per thread");
+    u32x4 wa_v[WA_TRIPS];
+#pragma unroll
+    for (int k = 0; k < WA_TRIPS; ++k) {
+      const int i = tid + k * 512;
+      wa_v[k] = wa[i < NWA ? i : 0];
+    }
+    const int ia = tid < CP ? tid : 0;
+    const float sa_v = d.sa[ia], ha_v = d.ha[ia];
+    float sc_v = 0.f, hc_v = 0.f;
+    if constexpr (MODE == 0) {
+      const int ic = tid < d.cout ? tid : 0;
+      sc_v = d.sc[ic];
+      hc_v = d.hc[ic];
+    }
+    pv_wait_loads();
+#pragma unroll
+    for (int k = 0; k < WA_TRIPS; ++k) {
+      const int i = tid + k * 512;
+      if (i < NWA) la[i] = wa_v[k];
+    }
+    if (tid < CP) { s_sa[tid] = sa_v; s_ha[tid] = ha_v; }
+    if constexpr (MODE == 0) {
+      if (tid < COUTP) { s_sc[tid] = tid < d.cout ? sc_v : 0.f; s_hc[tid] = tid < d.cout ? hc_v : 0.f; }
+    }
   }
   __syncthreads();
 
@@ -401,10 +426,16 @@ __global__ __launch_bounds__(512, 2) void bottleneck_block_kernel(const pv_bottl
           } else {
             // ---- output plane p-1: BN -> bf16 -> global memory, fp32 sums for the squeeze ----
             const unsigned tb = (unsigned)(p - 1) * yplane_b;
+            // (the NWS store offsets and column predicates are loop-invariant; hoisted out of the T loop they took the registers
+            // of the taps, which were spilled and reloaded three times per plane at res4: 15 registers, 64 bytes of scratch.
+            // Opaque per iteration, they are recomputed here: 2 instructions per output beside its 81 FMAs.)
+            unsigned mo = st_ok ? m_off : 0x80000000u;   // (out of range stays out of range: mo + n * yvox_b + tb < 2^32)
+            int wlim = W - sow0;
+            asm volatile("" : "+v"(mo), "+s"(wlim));
 #pragma unroll
             for (int n = 0; n < G::NWS; ++n) {
-              const bool ok = st_ok && sow0 + n < W;
-              const unsigned off = (ok ? m_off + (unsigned)n * yvox_b : 0x80000000u) + tb;
+              const bool ok = st_ok && n < wlim;
+              const unsigned off = (n < wlim ? mo + (unsigned)n * yvox_b : 0x80000000u) + tb;
               if constexpr (PAIR) {
                 const float v0 = acc[0][n].x * sb2.x + hb2.x, v1 = acc[0][n].y * sb2.y + hb2.y;
                 if (ok) { ps.x += v0; ps.y += v1; }
@@ -427,12 +458,20 @@ __global__ __launch_bounds__(512, 2) void bottleneck_block_kernel(const pv_bottl
       if constexpr (ABL != 4) __syncthreads();
       if constexpr (ABL == 8) __syncthreads();
     }
-    if (MODE == 1 && d.psum != nullptr && p_ok && pch < pv_round_up(d.C, 8)) {
-      const int c_p = pv_round_up(d.C, 8);
-      const long blk = ((long)(tile_h * kTH + srow) * tiles_w + tile_w) * SEGS + seg;
-      float* dst = d.psum + ((long)b * ((long)tiles_h * kTH * tiles_w * SEGS) + blk) * c_p + pch;
-      if constexpr (PAIR) *reinterpret_cast<float2*>(dst) = soh < H ? ps : float2{0.f, 0.f};
-      else *dst = soh < H ? ps : 0.f;
+    if constexpr (MODE == 1) {
+      // the lane's channel, recomputed from the thread index behind the T loop: kept live across it for this one use, it and the
+      // address built on it were the last three registers the res4 form spilled
+      int tid2 = tid;
+      asm volatile("" : "+v"(tid2));
+      const int item2 = wpart * 64 + (tid2 & 63);
+      const int pch2 = item2 < G::NI ? IC * item2 : 0;
+      if (d.psum != nullptr && item2 < G::NI && pch2 < pv_round_up(d.C, 8)) {
+        const int c_p = pv_round_up(d.C, 8);
+        const long blk = ((long)(tile_h * kTH + srow) * tiles_w + tile_w) * SEGS + seg;
+        float* dst = d.psum + ((long)b * ((long)tiles_h * kTH * tiles_w * SEGS) + blk) * c_p + pch2;
+        if constexpr (PAIR) *reinterpret_cast<float2*>(dst) = soh < H ? ps : float2{0.f, 0.f};
+        else *dst = soh < H ? ps : 0.f;
+      }
     }
   }
 }

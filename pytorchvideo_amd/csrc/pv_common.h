@@ -141,6 +141,55 @@ template <bool FAST, int N> __device__ __forceinline__ void pv_apply_act_n(float
 __host__ __device__ __forceinline__ int pv_round_up(int v, int m) { return (v + m - 1) / m * m; }
 __host__ __device__ __forceinline__ long pv_ceil_div(long a, long b) { return (a + b - 1) / b; }
 
+// ---- kernel start-up: request everything, wait once ----
+// `s_waitcnt vmcnt(0)` alone (expcnt / lgkmcnt untouched), fenced so that neither the requests above it nor the LDS writes below
+// it move across.  The compiler's own waits come one per consumer (vmcnt(13), vmcnt(12), ... for a batch of 14 loads), and a
+// staging loop written as load / store per iteration pays one memory round trip per iteration.
+__device__ __forceinline__ void pv_wait_loads() {
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(0x0f70);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+typedef unsigned int pv_u32x4 __attribute__((ext_vector_type(4)));
+
+// Filter slab [rows][k] of bf16 in global memory -> LDS rows of `wld` elements, LDS row r = slab row perm(r): pairs of 16-row
+// MFMA tiles interleaved in groups of 4, so that a lane's accumulators are 8 consecutive output channels (pv_pwconv.hip,
+// pv_lateral.hip).  A thread moves up to NB 16-byte chunks: request() issues all of them, commit() writes them after the
+// caller's pv_wait_loads().  Rows >= rows_valid and chunks at k >= pitch are zero-filled by the buffer range check
+// (offset kOob >= num_records), without a branch around the load.  A slab of more than THREADS * NB chunks takes several
+// batches (chunk ids from batch0 * THREADS on): NB is what the kernel's register budget allows in flight beside its own loads.
+template <int THREADS, int NB> struct PvSlabStage {
+  pv_u32x4 v[NB];
+  int dst[NB];   // element offset in LDS, -1: no chunk
+  // W: first row of the slab; pitch: its row stride in elements (multiple of 8); rows_valid: rows that exist in global memory
+  __device__ __forceinline__ void request(const bf16_t* W, int lds_rows, int cpr, int wld, int pitch, int rows_valid, int tid, int batch0 = 0) {
+    constexpr unsigned kOob = 0x80000000u;
+    __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<bf16_t*>(W), 0, (int)((unsigned)(rows_valid > 0 ? rows_valid : 0) * (unsigned)pitch * 2u), 0x00020000);
+    const int total = lds_rows * cpr;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      v[i] = pv_u32x4{0u, 0u, 0u, 0u};
+      dst[i] = -1;
+      if ((batch0 + i) * THREADS < total) {   // workgroup-uniform: a short slab skips the index arithmetic of the chunks it does not have
+        const int id = (batch0 + i) * THREADS + tid;
+        const int r = id / cpr, kc = id - r * cpr;
+        const int tn = r >> 4, ii = r & 15;
+        const int c = (tn >> 1) * 32 + (ii >> 2) * 8 + (tn & 1) * 4 + (ii & 3);
+        const bool ok = id < total && c < rows_valid && kc * 8 < pitch;
+        v[i] = __builtin_amdgcn_raw_buffer_load_b128(rw, (int)(ok ? ((unsigned)c * (unsigned)pitch + (unsigned)kc * 8u) * 2u : kOob), 0, 0);
+        dst[i] = id < total ? r * wld + kc * 8 : -1;
+      }
+    }
+  }
+  __device__ __forceinline__ void commit(bf16_t* w_s) const {
+#pragma unroll
+    for (int i = 0; i < NB; ++i)
+      if (dst[i] >= 0) *reinterpret_cast<pv_u32x4*>(w_s + dst[i]) = v[i];
+  }
+};
+
 __device__ __forceinline__ float pv_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

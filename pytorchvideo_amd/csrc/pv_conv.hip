@@ -99,9 +99,22 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_de
       const long m_last = (m0 + BM < M ? m0 + BM : M) - 1;
       gate_lds = d.cin <= kGateMaxC && (d.cin & 7) == 0 && (int)(m_last / S_out) - gate_b0 <= 1;      // (workgroup-uniform)
       if (gate_lds) {
-        for (int i = tid; i < 2 * d.cin; i += kThreads) {
-          const int bb = gate_b0 + (i >= d.cin ? 1 : 0);
-          s_gate[i] = bb < d.B ? d.a_gate[(long)bb * d.cin + (i >= d.cin ? i - d.cin : i)] : 0.f;
+        // the rows of clips gate_b0 and gate_b0 + 1 are back to back: value i of the pair is base[i].  All of a thread's values
+        // are requested (clamped index), then written: as a copy loop this was a memory round trip per iteration, 4 at cin = 432
+        const float* __restrict__ base = d.a_gate + (long)gate_b0 * d.cin;
+        const int n_ok = gate_b0 + 1 < d.B ? 2 * d.cin : d.cin;   // the last clip has no next one
+        constexpr int GT = 2 * kGateMaxC / kThreads;
+        float gv[GT];
+#pragma unroll
+        for (int k = 0; k < GT; ++k) {
+          const int i = tid + k * kThreads;
+          gv[k] = base[i < n_ok ? i : 0];
+        }
+        pv_wait_loads();
+#pragma unroll
+        for (int k = 0; k < GT; ++k) {
+          const int i = tid + k * kThreads;
+          if (i < 2 * d.cin) s_gate[i] = i < n_ok ? gv[k] : 0.f;
         }
         __syncthreads();
       }

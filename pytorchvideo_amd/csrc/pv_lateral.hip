@@ -30,6 +30,9 @@
 namespace {
 
 constexpr int kLatThreads = 512;   // 8 waves share one filter slab
+// 16-byte chunks of the filter slab a thread stages, at the largest K a slab of NT row tiles is launched with: NT = 8 up to
+// K = 448 (the 120 KB of LDS), NT = 4 and 2 up to K = 640: NT * 16 rows x K / 8 chunks over 512 threads
+template <int NT> constexpr int kSlabChunks = NT == 8 ? 14 : (NT == 4 ? 10 : 5);
 
 struct TapConv {       // the convolution the kernel evaluates (a lateral connection is kh = kw = sh = sw = 1)
   const void* x; const void* w; void* y;
@@ -96,24 +99,65 @@ __global__ __launch_bounds__(kLatThreads, (PW2 && NT == 2) ? 4 : 1) void tap_str
   const int chunk = xcont ? xcd * ((nchunks + 7) >> 3) + slot / nsplit : (slot / nsplit) * 8 + xcd;
   const int n0 = (slot % nsplit) * (NT * 16);
 
-  // ---- stage the filter slab (LDS row r = channel n0 + perm(r)), BN scale / shift, the tap table ----
+  // ---- stage the filter slab (LDS row r = channel n0 + perm(r)), BN scale / shift, the tap table: every request first, one
+  // wait, then the LDS writes (the two-conv form on 64 registers, NT = 2, takes its slabs in batches of its own) ----
   {
     const bf16_t* __restrict__ Wt = static_cast<const bf16_t*>(d.w);
     const int K = taps * cin_p;
     const int cpr = Kp / 8;
-    for (int id = tid; id < NT * 16 * cpr; id += kLatThreads) {
-      const int r = id / cpr, kc = id - r * cpr;
-      const int tn = r >> 4, ii = r & 15;
-      const int c = n0 + (tn >> 1) * 32 + (ii >> 2) * 8 + (tn & 1) * 4 + (ii & 3);
-      bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (c < d.cout && kc * 8 < K) v = *reinterpret_cast<const bf16x8*>(Wt + (long)c * K + kc * 8);
-      *reinterpret_cast<bf16x8*>(w_s + r * WLD + kc * 8) = v;
+    constexpr int NB1 = kSlabChunks<NT>;                 // chunks per thread of the first slab (launch_lateral checks the bound)
+    constexpr int NB2 = PW2 ? (NT == 2 ? 4 : 16) : 1;    // second slab: cout2 <= 1024 rows x NT * 2 chunks, NT = 2 in two batches
+    constexpr bool kOneWait = !(PW2 && NT == 2);
+    const int c = n0 + tid;
+    const bool c_ok = tid < NT * 16 && c < d.cout;
+    const int cc = c_ok ? c : 0;                         // clamped, selected below
+    const float sc_v = d.scale ? d.scale[cc] : 1.f;
+    const float sh_v = d.shift ? d.shift[cc] : 0.f;
+    PvSlabStage<kLatThreads, NB1> st;
+    st.request(Wt + (long)n0 * K, NT * 16, cpr, WLD, K, d.cout - n0, tid);
+    if constexpr (PW2) {
+      const bf16_t* __restrict__ W2 = static_cast<const bf16_t*>(d.w2);
+      const int K2 = cout_p8;              // W2 is [cout2][round_up(cout, 8)]
+      constexpr int cpr2 = NT * 16 / 8;
+      float sc2_v[2], sh2_v[2];            // pairs2 * 32 <= 1024 entries: two per thread
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int i = tid + j * kLatThreads;
+        const int ic = i < d.cout2 ? i : 0;
+        sc2_v[j] = d.scale2 ? d.scale2[ic] : 1.f;
+        sh2_v[j] = d.shift2 ? d.shift2[ic] : 0.f;
+      }
+      if constexpr (kOneWait) {
+        PvSlabStage<kLatThreads, NB2> st2;
+        st2.request(W2, pairs2 * 32, cpr2, W2LD, K2, d.cout2, tid);
+        pv_wait_loads();
+        st.commit(w_s);
+        st2.commit(w2_s);
+      } else {
+        pv_wait_loads();
+        st.commit(w_s);
+        for (int b0 = 0; b0 * kLatThreads < pairs2 * 32 * cpr2; b0 += NB2) {
+          PvSlabStage<kLatThreads, NB2> st2;
+          st2.request(W2, pairs2 * 32, cpr2, W2LD, K2, d.cout2, tid, b0);
+          pv_wait_loads();
+          st2.commit(w2_s);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int i = tid + j * kLatThreads;
+        if (i < pairs2 * 32) {
+          sc2_s[i] = i < d.cout2 ? sc2_v[j] : 0.f;
+          sh2_s[i] = i < d.cout2 ? sh2_v[j] : 0.f;
+        }
+      }
+    } else {
+      pv_wait_loads();
+      st.commit(w_s);
     }
-    for (int i = tid; i < NT * 16; i += kLatThreads) {
-      const int c = n0 + i;
-      const bool ok = c < d.cout;
-      sc_s[i] = ok ? (d.scale ? d.scale[c] : 1.f) : 0.f;
-      sh_s[i] = ok ? (d.shift ? d.shift[c] : 0.f) : 0.f;
+    if (tid < NT * 16) {
+      sc_s[tid] = c_ok ? sc_v : 0.f;
+      sh_s[tid] = c_ok ? sh_v : 0.f;
     }
     for (int i = tid; i < ksteps * 4; i += kLatThreads) {
       const int k = (i >> 2) * 32 + (i & 3) * 8;
@@ -124,24 +168,6 @@ __global__ __launch_bounds__(kLatThreads, (PW2 && NT == 2) ? 4 : 1) void tap_str
                                    (int)((((unsigned)dt * (unsigned)d.Hi + (unsigned)dh) * (unsigned)d.Wi + (unsigned)dw) *
                                              (unsigned)d.ldx * 2u + (unsigned)c * 2u)}
                             : int2{-1, 0};
-    }
-    if constexpr (PW2) {
-      const bf16_t* __restrict__ W2 = static_cast<const bf16_t*>(d.w2);
-      const int K2 = cout_p8;              // W2 is [cout2][round_up(cout, 8)]
-      constexpr int cpr2 = NT * 16 / 8;
-      for (int id = tid; id < pairs2 * 32 * cpr2; id += kLatThreads) {
-        const int r = id / cpr2, kc = id - r * cpr2;
-        const int tn = r >> 4, ii = r & 15;
-        const int c = (tn >> 1) * 32 + (ii >> 2) * 8 + (tn & 1) * 4 + (ii & 3);
-        bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (c < d.cout2 && kc * 8 < K2) v = *reinterpret_cast<const bf16x8*>(W2 + (long)c * K2 + kc * 8);
-        *reinterpret_cast<bf16x8*>(w2_s + r * W2LD + kc * 8) = v;
-      }
-      for (int i = tid; i < pairs2 * 32; i += kLatThreads) {
-        const bool ok = i < d.cout2;
-        sc2_s[i] = ok ? (d.scale2 ? d.scale2[i] : 1.f) : 0.f;
-        sh2_s[i] = ok ? (d.shift2 ? d.shift2[i] : 0.f) : 0.f;
-      }
     }
   }
   __syncthreads();
@@ -331,6 +357,7 @@ int launch_lateral(const TapConv& d, int ksteps, size_t lds, int xcont, hipStrea
   const long ngroups = pv_ceil_div(M, (kLatThreads / 64) * TM * 16);
   const int nsplit = (int)pv_ceil_div(pv_round_up(d.cout, 8), NT * 16);
   if (PW2 && nsplit != 1) return PV_ERR_UNSUPPORTED;
+  if ((long)NT * 16 * ksteps * 4 > (long)kLatThreads * kSlabChunks<NT>) return PV_ERR_UNSUPPORTED;   // the start-up stages the slab in one batch
   auto kern = tap_stream_kernel<NT, TM, PW2>;
   if (lds > 64 * 1024)
     PV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

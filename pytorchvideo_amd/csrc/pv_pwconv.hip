@@ -34,7 +34,7 @@ struct PwRows {  // per-lane geometry of one wave tile group: clip index and vox
 // X2V: compiled with the second K operand (projection shortcut folded into conv_c); a separate variant so that
 // the common kernels do not carry its registers
 template <int NT, int TM, bool XFORM, int KS, bool F32, bool X2V>
-__global__ __launch_bounds__(kThreads, (KS >= 14 || X2V) ? 2 : ((NT >= 4 || KS >= 4) ? 3 : 4)) void pw_stream_kernel(const pv_conv3d_desc d, int ksteps_rt, int ngroups,
+__global__ __launch_bounds__(kThreads, (KS >= 14 || X2V) ? 2 : (((NT >= 4 || KS >= 4) && !(NT == 4 && KS == 1 && !XFORM && !F32)) ? 3 : 4)) void pw_stream_kernel(const pv_conv3d_desc d, int ksteps_rt, int ngroups,
                                                                 int nchunks, int nsplit) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int ksteps = KS > 0 ? KS : ksteps_rt;
@@ -59,29 +59,7 @@ __global__ __launch_bounds__(kThreads, (KS >= 14 || X2V) ? 2 : ((NT >= 4 || KS >
   const int n0 = (slot % nsplit) * (NT * 16);
   const long S_out = (long)d.To * d.Ho * d.Wo;
   const long M = (long)d.B * S_out;
-
-  // ---- stage weights (row r of LDS = output channel n0 + perm(r)), scale, shift ----
-  {
-    const bf16_t* __restrict__ Wt = static_cast<const bf16_t*>(d.w);
-    const int cpr = Kp / 8;  // chunks per row
-    const int w_pitch = X2V ? Kp : d.cin;   // two operands: rows are packed at the padded K
-    for (int id = tid; id < NT * 16 * cpr; id += kThreads) {
-      const int r = id / cpr, kc = id - r * cpr;
-      const int tn = r >> 4, ii = r & 15;
-      const int c = n0 + (tn >> 1) * 32 + (ii >> 2) * 8 + (tn & 1) * 4 + (ii & 3);
-      bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (c < d.cout && kc * 8 < w_pitch) v = *reinterpret_cast<const bf16x8*>(Wt + (long)c * w_pitch + kc * 8);
-      *reinterpret_cast<bf16x8*>(w_s + r * WLD + kc * 8) = v;
-    }
-    for (int i = tid; i < NT * 16; i += kThreads) {
-      const int c = n0 + i;
-      const bool ok = c < d.cout;
-      sc_s[i] = ok ? (d.scale ? d.scale[c] : 1.f) : 0.f;
-      sh_s[i] = ok ? (d.shift ? d.shift[c] : 0.f) : 0.f;
-      if constexpr (X2V) sc2_s[i] = ok ? (d.x2_scale ? d.x2_scale[c] : 1.f) : 0.f;
-    }
-  }
-  __syncthreads();
+  const bool m32 = M < 0x7fffffffL;   // (workgroup-uniform) voxel indices fit 32 bits: rows_of divides in 32 bits
 
   const bf16_t* __restrict__ X = static_cast<const bf16_t*>(d.x);
   const bf16_t* __restrict__ X2 = X2V ? static_cast<const bf16_t*>(d.x2) : nullptr;
@@ -101,9 +79,15 @@ __global__ __launch_bounds__(kThreads, (KS >= 14 || X2V) ? 2 : ((NT >= 4 || KS >
       const long m = m_base + t * 16 + n16;
       const bool ok = g < ngroups && m < M;
       const long mm = ok ? m : 0;
-      const long b = mm / S_out;
-      r.b[t] = (int)b;
-      r.sp[t] = ok ? (int)(mm - b * S_out) : -1;
+      if (m32) {   // same quotient and remainder as the 64-bit software division below, ~150 instructions shorter per group
+        const unsigned b = (unsigned)mm / (unsigned)S_out;
+        r.b[t] = (int)b;
+        r.sp[t] = ok ? (int)((unsigned)mm - b * (unsigned)S_out) : -1;
+      } else {
+        const long b = mm / S_out;
+        r.b[t] = (int)b;
+        r.sp[t] = ok ? (int)(mm - b * S_out) : -1;
+      }
       if constexpr (X2V) {
         const int sp = ok ? r.sp[t] : 0;
         const int to = sp / (d.Ho * d.Wo), r2 = sp - to * d.Ho * d.Wo;
@@ -115,12 +99,17 @@ __global__ __launch_bounds__(kThreads, (KS >= 14 || X2V) ? 2 : ((NT >= 4 || KS >
   auto load_x = [&](bf16x8 (&dst)[KSR][TM], const PwRows& r, int ks0) {
 #pragma unroll
     for (int kk = 0; kk < KSR; ++kk) {
-      if (X2V && ks0 + kk >= ks1) {   // second operand (wave-uniform): channel k2 of the strided x2 voxel
+      if constexpr (X2V) {
+        // second operand (wave-uniform choice): channel k2 of the strided x2 voxel.  ONE load site for both operands: with a
+        // load in each arm of the branch the compiler copied the loaded registers at the join, and waited for them there
+        const bool second = ks0 + kk >= ks1;
         const int k2 = (ks0 + kk - ks1) * 32 + q * 8;
+        const int k1 = (ks0 + kk) * 32 + q * 8;
 #pragma unroll
         for (int t = 0; t < TM; ++t) {
-          if (r.sp[t] >= 0 && k2 < d.x2_cin)
-            dst[kk][t] = *reinterpret_cast<const bf16x8*>(X2 + (long)r.b[t] * d.x2_bs + (long)r.sp2[t] * d.x2_ld + k2);
+          const bf16_t* p = second ? X2 + (long)r.b[t] * d.x2_bs + (long)r.sp2[t] * d.x2_ld + k2
+                                   : X + (long)r.b[t] * d.x_bs + (long)r.sp[t] * d.ldx + k1;
+          if (r.sp[t] >= 0 && (second ? k2 < d.x2_cin : k1 < d.cin)) dst[kk][t] = *reinterpret_cast<const bf16x8*>(p);
           else dst[kk][t] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
         }
         continue;
@@ -233,24 +222,98 @@ __global__ __launch_bounds__(kThreads, (KS >= 14 || X2V) ? 2 : ((NT >= 4 || KS >
       }
     }
   };
-  auto refresh_gate = [&](int g) {
-    if (!has_gate || g >= ngroups) return;
-    const long b_first = (((long)g * 4 + wave) * (TM * 16)) / S_out;  // wave-uniform
+  // Squeeze-excitation gate rows of the (at most two) clips of group g's wave tile: gate_request issues this lane's 2 cin / 64
+  // values as one batch (clamped index, selected at the commit: no branch between the loads), gate_commit writes them to the
+  // wave's LDS region.  The first group's request goes out with the start-up batch; a later group's at the end of the group
+  // before it, ahead of that group's residual request, so that its wait drains nothing younger than the gate itself (and
+  // holds no register across the transform and the MFMAs).
+  constexpr int GB = XFORM ? (KS > 0 ? KS : (NT == 8 ? 8 : 14)) : 1;   // cin <= 32 KS; generic form: ksteps <= 8 at NT = 8, <= 14 below
+  // (gv lives in the caller's scope, start-up or loop end, and is defined on every path: a value carried around the group loop
+  // would cost its registers for the whole kernel)
+  auto gate_request = [&](int g, float (&gv)[GB]) -> long {   // returns the clip whose rows gv holds (-1: nothing requested)
+#pragma unroll
+    for (int j = 0; j < GB; ++j) gv[j] = 0.f;
+    if (!has_gate || g >= ngroups) return -1;
+    long gate_bn = -1;
+    const long m_first = ((long)g * 4 + wave) * (TM * 16);
+    const long b_first = m32 ? (long)((unsigned)m_first / (unsigned)S_out) : m_first / S_out;  // wave-uniform
     if (b_first < d.B && b_first != gate_b0) {
-      for (int i = lane; i < 2 * d.cin; i += 64) {
-        const long bb = b_first + (i >= d.cin ? 1 : 0);
-        my_gate[i] = bb < d.B ? d.a_gate[bb * d.cin + (i >= d.cin ? i - d.cin : i)] : 0.f;
+      // the rows of clips b_first and b_first + 1 are back to back: value i of the pair is base[i]
+      const float* __restrict__ base = d.a_gate + b_first * d.cin;   // wave-uniform
+      const int n_ok = b_first + 1 < d.B ? 2 * d.cin : d.cin;        // the last clip has no next one
+      int ln = lane;
+      asm volatile("" : "+v"(ln));   // (keeps the 14 clamped offsets from being hoisted out of the group loop into registers)
+#pragma unroll
+      for (int j = 0; j < GB; ++j) {
+        const int i = ln + 64 * j;
+        gv[j] = base[i < n_ok ? i : 0];
       }
-      gate_b0 = b_first;
+      gate_bn = b_first;
     }
+    return gate_bn;
+  };
+  auto gate_commit = [&](long gate_bn, const float (&gv)[GB]) {
+    if (gate_bn < 0) return;   // wave-uniform
+    const int n_ok = gate_bn + 1 < d.B ? 2 * d.cin : d.cin;
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+#pragma unroll
+    for (int j = 0; j < GB; ++j) {
+      const int i = ln + 64 * j;
+      if (i < 2 * d.cin) my_gate[i] = i < n_ok ? gv[j] : 0.f;
+    }
+    gate_b0 = gate_bn;
   };
 
   PwRows cur, nxt;
   bf16x8 xf[KSR][TM];
   f32x4 rcur[NP][TM][F32 ? 2 : 1];
   int g = chunk < nchunks ? chunk : ngroups;   // padded blocks (grid is a multiple of 8 chunks) do nothing
+  // ---- start-up: everything the first group needs from global memory and the workgroup's filter slab are requested
+  // together, then one wait per slab batch, the LDS writes and the barrier.  (rows_of marks the rows of a padded workgroup and
+  // the rows past M invalid, and load_x / gate_request issue nothing for them: the hoist adds no access.) ----
   rows_of(g, cur);
+  float gv0[GB];
+  const long gb0 = gate_request(g, gv0);
   load_x(xf, cur, 0);
+  // (The residual is NOT part of this batch: the epilogue is its only consumer, so the request at the top of the group loop is
+  // already a transform and all MFMAs ahead of its use; requested here it cost the registers of a resident workgroup --
+  // <2, 2, true, 3> spilled at its 128, the two-operand <8, 1, true, 3> went from 165 to 174, over the 168 of three per CU --
+  // and the grid is sized by what is resident.)
+  {
+    // weights (row r of LDS = output channel n0 + perm(r)), scale, shift
+    const bf16_t* __restrict__ Wt = static_cast<const bf16_t*>(d.w);
+    const int cpr = Kp / 8;                 // chunks per row
+    const int w_pitch = X2V ? Kp : d.cin;   // two operands: rows are packed at the padded K
+    // chunks per thread: NT * 16 rows x 4 KS chunks over 256 threads (generic form: ksteps <= 8 at NT = 8, <= 14 below)
+    constexpr int NBT = KS > 0 ? (NT * KS + 3) / 4 : (NT == 8 ? 16 : (NT * 14 + 3) / 4);
+    // in flight beside the first group's operands: at most 8 chunks where the kernel lives on 128 / 168 registers (a batch of
+    // 14 spilled <8, 1, true, 7>), two batches of 14 in the 256-register KS = 14 form
+    constexpr int NBATCH = NBT <= 8 ? 1 : 2;
+    constexpr int NB = (NBT + NBATCH - 1) / NBATCH;
+    const int c = n0 + tid;
+    const bool c_ok = tid < NT * 16 && c < d.cout;
+    const int cc = c_ok ? c : 0;               // clamped, selected below
+    const float sc_v = d.scale ? d.scale[cc] : 1.f;
+    const float sh_v = d.shift ? d.shift[cc] : 0.f;
+    float sc2_v = 1.f;
+    if constexpr (X2V) sc2_v = d.x2_scale ? d.x2_scale[cc] : 1.f;
+#pragma unroll
+    for (int h = 0; h < NBATCH; ++h) {
+      PvSlabStage<kThreads, NB> st;
+      st.request(Wt + (long)n0 * w_pitch, NT * 16, cpr, WLD, w_pitch, d.cout - n0, tid, h * NB);
+      pv_wait_loads();
+      st.commit(w_s);
+    }
+    if (tid < NT * 16) {
+      sc_s[tid] = c_ok ? sc_v : 0.f;
+      sh_s[tid] = c_ok ? sh_v : 0.f;
+      if constexpr (X2V) sc2_s[tid] = c_ok ? sc2_v : 0.f;
+    }
+    gate_commit(gb0, gv0);
+  }
+  __syncthreads();
+
   for (; g < ngroups; g += nchunks) {
     load_res(rcur, cur);  // consumed by the epilogue: in flight during the transform and the MFMAs
     f32x4 acc[NT][TM];
@@ -264,7 +327,6 @@ __global__ __launch_bounds__(kThreads, (KS >= 14 || X2V) ? 2 : ((NT >= 4 || KS >
 #pragma unroll
         for (int t = 0; t < TM; ++t) acc2[a][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    refresh_gate(g);
     rows_of(g + nchunks, nxt);
     asm volatile("" : "+v"(w_opaque));
     if constexpr (KS > 0) {
@@ -340,6 +402,11 @@ __global__ __launch_bounds__(kThreads, (KS >= 14 || X2V) ? 2 : ((NT >= 4 || KS >
       }
     }
     cur = nxt;
+    {
+      float gv[GB];
+      const long gbn = gate_request(g + nchunks, gv);
+      gate_commit(gbn, gv);
+    }
   }
 }
 
