@@ -674,6 +674,54 @@ typedef struct pv_hdr_views_desc {
 } pv_hdr_views_desc;                  /* sizeof(pv_frame_views_desc) + 16 */
 int pv_hdr_views(const pv_hdr_views_desc* d, pv_stream_t stream);
 
+/* ---- a rectangle per frame: actor tubes resized in place ---------------------------------------------------------------------
+ * A detector and a tracker find people, and a classifier is run on each of them: a rectangle of the frame, of any size and
+ * aspect and usually moving from frame to frame, is cut out and resized to the network's input (the deterministic core of the
+ * reference's random_resized_crop: crop, then interpolate(size=(Ho, Wo), mode="bilinear")).  pv_batch_views cannot say that:
+ * its scale is Hd / Hn with an integer Hn, and it has one geometry per video.  pv_region_views is pv_batch_views /
+ * pv_frame_views with the geometry taken from a 32-byte record PER DESTINATION FRAME of every table row; the video is read where
+ * it lies, once, and no crop, no RGB copy of a YUV source and no resized tube is materialised.
+ * Launch:       `frames`, a whole pv_frame_views_desc.  frames.frame_ptrs == NULL (and frame_ptrs_dev NULL, n_frame_ptrs 0):
+ *               the records are whole videos, pv_batch_views' meaning of frames.batch; otherwise pv_frame_views' meaning.
+ *               n_views == 1 and every item's view == 0.  Item i is (source, row, view) as there.
+ * Regions:      regions[n_rows][t_stride], indexed exactly like t_index, on the host (`regions`: validated, and the launch is
+ *               sized from it) and the same bytes on the device (`regions_dev`, a multiple of 4: what the kernel reads), under
+ *               the rule of sources / sources_dev.  For destination frame t of an item the frame is t_index[row][t], clamped as
+ *               in pv_batch_views, and the rectangle is regions[row][t]: rows [top, top + h) x columns [left, left + w) of it.
+ *               sy = (float)h / (float)Ho and sx = (float)w / (float)Wo, divided by the caller in fp32.
+ * Arithmetic:   the output frame is the Ho x Wo bilinear resize of that rectangle ALONE: per axis pv_resample_crop's pinned
+ *               coordinate with s = sy, d = 0 .. Ho-1 and n_in = h, so that no tap leaves the rectangle -- crop, then
+ *               interpolate, not a window of the scaled full frame.  The source row of a tap is top + i0 / top + i1, columns
+ *               likewise.  Blend order, the YUV tap rule (every tap converted and clamped; the chroma of the ABSOLUTE pixel),
+ *               the affine map and the single rounding are unchanged.  Of a record, Hn, Wn, y_off, x_off, sy and sx are NOT
+ *               read.  ITEM i, FRAME t HOLDS, BIT FOR BIT, WHAT pv_batch_views WRITES FOR A DENSE ONE-FRAME COPY OF THAT
+ *               RECTANGLE GIVEN AS A SOURCE OF ITS OWN, with Hn = Ho, Wn = Wo and offsets 0 -- whatever else shares the launch,
+ *               and for a frame list as for the stacked video.
+ * Source forms: the upright forms of pv_batch_views / pv_frame_views: PV_SRC_NTHWC PV_U8, PV_SRC_NCTHW PV_U8 / PV_F32,
+ *               PV_SRC_YUV420 PV_U8 / PV_U16 with either c_step.  For PV_SRC_YUV420 top, left, h and w are all even: a dense
+ *               4:2:0 copy of the rectangle then exists, which is what the guarantee above is stated against.
+ * The kernel clamps top / left / h / w into the item's source frame before it forms an address: a device copy that differs from
+ * the validated one cannot read outside the video.
+ * PV_ERR_INVALID: a null descriptor, regions or regions_dev, a regions_dev that is no multiple of 4; a pointer table only half
+ * given, or n_frame_ptrs != 0 without a table; n_views != 1 or an item with view != 0; for every item of the launch and every
+ * t < T a rectangle with h < 1 or w < 1, one that leaves [0, Hs) x [0, Ws) of the item's source, sy / sx whose bits are not the
+ * library's own division, a non-zero reserved, or -- PV_SRC_YUV420 -- an odd member; whatever the wrapped entry point rejects
+ * (but nothing about the record fields named above).  PV_ERR_UNSUPPORTED: a record named by an item with orient != 0; a
+ * staged strip beyond the kernels' LDS limit; as the wrapped entry point otherwise.  Validation precedes every HIP call.
+ * Out of scope: oriented records (orient != 0) and the PQ / HLG tap map of pv_hdr_views.
+ */
+typedef struct pv_view_region {      /* 32 bytes: one rectangle of the frame, for ONE destination frame of ONE table row */
+  int32_t top, left, h, w;           /* rows [top, top+h) x columns [left, left+w) of the source frame                  */
+  float   sy, sx;                    /* (float)h / (float)Ho, (float)w / (float)Wo, divided by the caller in fp32        */
+  int32_t reserved[2];               /* 0                                                                                */
+} pv_view_region;
+typedef struct pv_region_views_desc {
+  pv_frame_views_desc frames;         /* frame_ptrs == NULL: whole videos (pv_batch_views' meaning); else pv_frame_views' */
+  const pv_view_region* regions;      /* [n_rows][t_stride] on the HOST, indexed exactly like t_index                     */
+  const pv_view_region* regions_dev;  /* the same bytes on the device                                                     */
+} pv_region_views_desc;               /* sizeof(pv_frame_views_desc) + 16 */
+int pv_region_views(const pv_region_views_desc* d, pv_stream_t stream);
+
 /* ---- key-frame detection: the boxes of a forward mapped into its views, on the device ---------------------------------
  * A detection forward built by pv_batch_views holds one clip per key frame, and every key frame has person boxes given in the
  * pixels of ITS source frame.  pv_box_views fills the RoI head's persistent [capacity][5] fp32 box buffer (what pv_roi_align

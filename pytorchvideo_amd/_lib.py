@@ -110,6 +110,9 @@ FrameViewsDesc = _struct("FrameViewsDesc", [
 # pv_hdr_views: a whole FrameViewsDesc (frame_ptrs None: the records are whole videos, pv_batch_views' meaning) and the tap map
 TRANSFER_PQ, TRANSFER_HLG = 1, 2
 HdrViewsDesc = _struct("HdrViewsDesc", [("frames", FrameViewsDesc), ("tone", _p)] + _ints("transfer", "reserved"))
+# pv_region_views: a whole FrameViewsDesc as in HdrViewsDesc, and a rectangle of the frame per (table row, destination frame)
+ViewRegion = _struct("ViewRegion", _ints("top", "left", "h", "w") + [("sy", _f32), ("sx", _f32), ("reserved", _i32 * 2)])
+RegionViewsDesc = _struct("RegionViewsDesc", [("frames", FrameViewsDesc), ("regions", _p), ("regions_dev", _p)])
 BoxViewsDesc = _struct("BoxViewsDesc", [
     ("boxes", _p), ("box_item", _p), ("sources_dev", _p), ("items_dev", _p), ("dst", _p), ("dst_box", _p)]
     + _ints("n_boxes", "n_seq", "n_sources", "n_views", "box0", "n_launch", "item0", "n_items", "Ho", "Wo", "capacity",
@@ -197,6 +200,7 @@ _SYMBOLS = [
     ("pv_batch_views", C.c_int, [C.POINTER(BatchViewsDesc), _p]),
     ("pv_frame_views", C.c_int, [C.POINTER(FrameViewsDesc), _p]),
     ("pv_hdr_views", C.c_int, [C.POINTER(HdrViewsDesc), _p]),
+    ("pv_region_views", C.c_int, [C.POINTER(RegionViewsDesc), _p]),
     ("pv_box_views", C.c_int, [C.POINTER(BoxViewsDesc), _p]),
     ("pv_layernorm", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_affine_rows", C.c_int, [C.POINTER(RowsDesc), _p]),

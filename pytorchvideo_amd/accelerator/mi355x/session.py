@@ -432,6 +432,11 @@ class Session:
         sources, whole videos or frame lists); the destination goes into the BatchViewsDesc it embeds."""
         self._views_into(h.frames.batch, 3, ref, planar, "pv_hdr_views", outer=h)
 
+    def region_views(self, r, ref, planar=None):
+        """`frame_views` for a RegionViewsDesc (a rectangle of the frame per destination frame, resized to the input:
+        pv_region_views; whole videos or frame lists); the destination goes into the BatchViewsDesc it embeds."""
+        self._views_into(r.frames.batch, r.frames.batch.C, ref, planar, "pv_region_views", outer=r)
+
     def box_views(self, d, ptr):
         """Fill a detection head's box buffer `ptr` (`alloc_boxes`) by pv_box_views: `d` is a BoxViewsDesc whose boxes, item
         window, records and capacity the caller (transforms.DevicePacker.fill_boxes) has set; the destination is filled in

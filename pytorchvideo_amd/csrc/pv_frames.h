@@ -1,5 +1,5 @@
 // What pv_frames.hip and pv_frames16.hip share: the item of a workgroup of pv_frame_views and the launch of its 16-bit kernels;
-// and what pv_frames.hip and pv_hdr.hip share: the host checks of the pointer table.
+// and what pv_frames.hip, pv_hdr.hip and pv_region.hip share: the host checks of the pointer table.
 #pragma once
 #include "pv_rs.h"
 

@@ -7,6 +7,8 @@
 //   pv_orient.hip     (launched from pv_batch.hip and pv_frames.hip)   the tile kernels of oriented records (orient != 0)
 //   pv_hdr.hip        pv_hdr_views (a seventh entry point)             pv_batch_views / pv_frame_views on 16-bit YUV with the PQ / HLG
 //                                                                       tap map: its own strip and tile kernel wrappers
+//   pv_region.hip     pv_region_views (an eighth)                      a rectangle of the frame per destination frame, resized to
+//                                                                       the window: its own strip kernel wrappers
 // What they compute with is here, once: the pinned source coordinate, the destination forms with their stores, the taps and
 // blends, the two staged-strip bodies (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather) that the nine kernel templates
 // wrap (resample_crop_kernel; yuv_views_kernel, yuv16_views_kernel; batch_views_kernel, batch_yuv_kernel,
@@ -233,6 +235,7 @@ __device__ __forceinline__ int rs_view_off(int view, int off0, int off1, int off
 
 // An RGB / planar source: clip `clip_frame0 / (planes * N)` of [.., C, N, Hs, Ws] or [.., N, Hs, Ws, 3].
 struct RsRgbSrc {
+  static constexpr bool kWindow = false;
   uintptr_t src;
   int Hs, Ws, N;        // N: frames per source plane, which is the plane stride in frames
   float sy, sx;         // (float)Hs / (float)Hn, (float)Ws / (float)Wn: divided once, on the host
@@ -241,9 +244,18 @@ struct RsRgbSrc {
   long clip_frame0;     // frames from `src` to frame 0 of the clip
 };
 
+// The same with a RECTANGLE of every frame as the source (pv_region.hip): Hs x Ws, what the coordinates are clamped with, are
+// the rectangle's, and the stored frame keeps an extent of its own, which the row and frame strides follow.
+struct RsRgbWin : RsRgbSrc {
+  static constexpr bool kWindow = true;
+  int Hf, Wf;           // the stored frame
+  int top, left;        // the rectangle's origin in it: rows [top, top + Hs) x columns [left, left + Ws)
+};
+
 // S: source element (unsigned char | float); INTER: frame-interleaved [.., Hs, Ws, 3] source; FORM / D: destination.
-template <typename S, bool INTER, int FORM, typename D>
-__device__ __forceinline__ void rs_strip_rgb(unsigned char* lds, int R, int pitch, const RsRgbSrc& s, const RsDst& d, int zi, int t,
+// SRC: RsRgbSrc, or RsRgbWin for a rectangle of the stored frame (deduced; the default keeps today's expressions).
+template <typename S, bool INTER, int FORM, typename D, typename SRC = RsRgbSrc>
+__device__ __forceinline__ void rs_strip_rgb(unsigned char* lds, int R, int pitch, const SRC& s, const RsDst& d, int zi, int t,
                                              bool check_span) {
   constexpr int G = RsGroup<FORM, D>::G;
   constexpr int XB = INTER ? 3 : (int)sizeof(S);   // bytes from one source column to the next
@@ -264,9 +276,16 @@ __device__ __forceinline__ void rs_strip_rgb(unsigned char* lds, int R, int pitc
   if (check_span && span_bytes + 15 > pitch) return;
 
   // byte address of column xs0 of source row y of plane `pl` of the selected frame
-  const long row_bytes = (long)s.Ws * XB;
-  const long frame_bytes = (long)s.Hs * row_bytes;
-  const long first = (s.clip_frame0 + s.ts) * frame_bytes + (long)xs0 * XB;
+  long row_bytes, frame_bytes, first;
+  if constexpr (SRC::kWindow) {                    // strides of the stored frame, the rectangle's origin in the first address
+    row_bytes = (long)s.Wf * XB;
+    frame_bytes = (long)s.Hf * row_bytes;
+    first = (s.clip_frame0 + s.ts) * frame_bytes + (long)s.top * row_bytes + (long)(s.left + xs0) * XB;
+  } else {
+    row_bytes = (long)s.Ws * XB;
+    frame_bytes = (long)s.Hs * row_bytes;
+    first = (s.clip_frame0 + s.ts) * frame_bytes + (long)xs0 * XB;
+  }
   const long plane_bytes = INTER ? 0 : (long)s.N * frame_bytes;
   auto row_addr = [&](int y, int pl) -> uintptr_t { return s.src + first + (long)pl * plane_bytes + (long)y * row_bytes; };
 
@@ -909,21 +928,30 @@ inline auto rs_check_video_src(int src_dtype) {
   return [=](const pv_view_source& v) { return reinterpret_cast<uintptr_t>(v.src) & misaligned ? PV_ERR_INVALID : PV_OK; };
 }
 
-// One record of such a launch: positive sizes, windows inside the scaled frame, sy / sx the library's own division, for YUV
-// the planes inside a frame, at even bytes for two-byte samples, and what its `src` points to (check_src: see below).
+// The part of a record's check that does not depend on the views (all that pv_region_views checks of a record: its geometry is
+// per frame): the stored frames -- positive sizes, the orientation code, for YUV the planes -- and what `src` points to.
 template <typename CheckSrc>
-inline int rs_check_record(const pv_batch_views_desc& d, const pv_view_source& v, bool yuv, const CheckSrc& check_src) {
-  if (!v.src || v.N <= 0 || v.Hs <= 0 || v.Ws <= 0 || v.Hn <= 0 || v.Wn <= 0) return PV_ERR_INVALID;
+inline int rs_check_record_frames(const pv_batch_views_desc& d, const pv_view_source& v, bool yuv, const CheckSrc& check_src) {
+  if (!v.src || v.N <= 0 || v.Hs <= 0 || v.Ws <= 0) return PV_ERR_INVALID;
   if (v.orient < 0 || v.orient > 7) return PV_ERR_INVALID;
-  if (int e = rs_check_views(d.n_views, v.y_off, v.x_off, d.Ho, d.Wo, v.Hn, v.Wn)) return e;
-  const int Hd = (v.orient & 1) ? v.Ws : v.Hs, Wd = (v.orient & 1) ? v.Hs : v.Ws;   // the displayed frame: Hn, Wn and the windows are its
-  if (!rs_same_bits(v.sy, (float)Hd / (float)v.Hn) || !rs_same_bits(v.sx, (float)Wd / (float)v.Wn)) return PV_ERR_INVALID;
   if (yuv) {
     const int sb = d.src_dtype == PV_U16 ? 2 : 1;
     if (int e = rs_check_yuv_planes(v.Hs, v.Ws, d.c_step, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset, sb)) return e;
     if (sb == 2 && rs_check_yuv16_even(0, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset)) return PV_ERR_INVALID;
   }
   return check_src(v);
+}
+
+// One record of such a launch: positive sizes, windows inside the scaled frame, sy / sx the library's own division, for YUV
+// the planes inside a frame, at even bytes for two-byte samples, and what its `src` points to (check_src: see below).
+template <typename CheckSrc>
+inline int rs_check_record(const pv_batch_views_desc& d, const pv_view_source& v, bool yuv, const CheckSrc& check_src) {
+  if (v.Hn <= 0 || v.Wn <= 0) return PV_ERR_INVALID;
+  if (int e = rs_check_record_frames(d, v, yuv, check_src)) return e;
+  if (int e = rs_check_views(d.n_views, v.y_off, v.x_off, d.Ho, d.Wo, v.Hn, v.Wn)) return e;
+  const int Hd = (v.orient & 1) ? v.Ws : v.Hs, Wd = (v.orient & 1) ? v.Hs : v.Ws;   // the displayed frame: Hn, Wn and the windows are its
+  if (!rs_same_bits(v.sy, (float)Hd / (float)v.Hn) || !rs_same_bits(v.sx, (float)Wd / (float)v.Wn)) return PV_ERR_INVALID;
+  return PV_OK;
 }
 
 // The descriptor, the items and the record behind each of them, then R, the LDS pitch(es) and the LDS bytes of the launch.
@@ -991,11 +1019,8 @@ inline int rs_tile_size(const pv_batch_views_desc& d, const pv_view_source* cons
   return PV_ERR_UNSUPPORTED;
 }
 
-// Items of upright records (orient == 0) run the staged strip, items of oriented records the staged tile: g / lds size the
-// first kind exactly as before (g.R == 0: the launch has none), tg / lds_t the second (tg.TR == 0: none).
-template <typename CheckSrc>
-inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_src, RsItemLaunch& g, size_t& lds, RsTileLaunch& tg,
-                          size_t& lds_t) {
+// The launch fields of an item-sourced descriptor: pointers, counts, the source form and the destination.
+inline int rs_check_item_desc(const pv_batch_views_desc& d) {
   if (!d.sources || !d.sources_dev || !d.items || !d.items_dev || !d.t_index || !d.dst) return PV_ERR_INVALID;
   if (d.n_sources <= 0 || d.n_items <= 0 || d.n_rows <= 0 || d.T <= 0 || d.C <= 0 || d.Ho <= 0 || d.Wo <= 0) return PV_ERR_INVALID;
   if (d.t_stride < d.T || d.n_items > 65535 || d.T > 65535) return PV_ERR_INVALID;   // grid.y / grid.z
@@ -1007,7 +1032,31 @@ inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_sr
   if (yuv && (!d.yuv2rgb || d.C != 3 || (d.c_step != 1 && d.c_step != 2))) return PV_ERR_INVALID;
   // the dtype / layout matrix
   if (yuv ? (d.src_dtype != PV_U8 && d.src_dtype != PV_U16) : (d.src_dtype != PV_U8 && d.src_dtype != PV_F32)) return PV_ERR_UNSUPPORTED;
-  if (int e = rs_check_dst(d.dst, d.dst_layout, d.dst_dtype, d.c_p, d.ld, d.bs, d.T, d.Ho, d.Wo)) return e;
+  return rs_check_dst(d.dst, d.dst_layout, d.dst_dtype, d.c_p, d.ld, d.bs, d.T, d.Ho, d.Wo);
+}
+
+// R, the LDS pitch(es) and the LDS bytes of a strip launch whose widest column span is `span` (chroma: `span_c`).
+inline int rs_strip_size(const pv_batch_views_desc& d, int span, int span_c, RsItemLaunch& g, size_t& lds) {
+  const bool yuv = d.src_layout == PV_SRC_YUV420, inter = d.src_layout == PV_SRC_NTHWC;
+  long per_row;                                    // LDS bytes of the two source rows of one output row
+  if (yuv) {
+    per_row = rs_yuv_pitches(span, span_c, d.c_step, d.src_dtype == PV_U16 ? 2 : 1, g.pitch, g.pitch_c);
+  } else {
+    g.pitch = pv_round_up(span * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
+    per_row = 2L * (inter ? 1 : d.C) * g.pitch;
+  }
+  if (int e = rs_strip_rows(per_row, d.Ho, g.R, lds)) return e;
+  g.c_base = 2 * g.R * g.pitch;
+  return PV_OK;
+}
+
+// Items of upright records (orient == 0) run the staged strip, items of oriented records the staged tile: g / lds size the
+// first kind exactly as before (g.R == 0: the launch has none), tg / lds_t the second (tg.TR == 0: none).
+template <typename CheckSrc>
+inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_src, RsItemLaunch& g, size_t& lds, RsTileLaunch& tg,
+                          size_t& lds_t) {
+  if (int e = rs_check_item_desc(d)) return e;
+  const bool yuv = d.src_layout == PV_SRC_YUV420;
   int span = 0, span_c = 0, n_upright = 0;
   std::vector<const pv_view_source*> oriented;     // the oriented records the items name, a video-major run once
   for (int i = 0; i < d.n_items; ++i) {
@@ -1030,16 +1079,7 @@ inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_sr
   if (!oriented.empty())
     if (int e = rs_tile_size(d, oriented.data(), oriented.size(), tg, lds_t)) return e;
   if (n_upright == 0) return PV_OK;
-  long per_row;                                    // LDS bytes of the two source rows of one output row
-  if (yuv) {
-    per_row = rs_yuv_pitches(span, span_c, d.c_step, d.src_dtype == PV_U16 ? 2 : 1, g.pitch, g.pitch_c);
-  } else {
-    g.pitch = pv_round_up(span * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
-    per_row = 2L * (inter ? 1 : d.C) * g.pitch;
-  }
-  if (int e = rs_strip_rows(per_row, d.Ho, g.R, lds)) return e;
-  g.c_base = 2 * g.R * g.pitch;
-  return PV_OK;
+  return rs_strip_size(d, span, span_c, g, lds);
 }
 
 // The launches of a validated item sequence: every maximal run of items of one kind -- upright records, oriented records --

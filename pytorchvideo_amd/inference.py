@@ -28,7 +28,7 @@ import torch
 
 from .data.clip_sampling import clip_frame_table, keyframe_frame_table, stream_windows
 from .ensemble import VideoEnsembler
-from .transforms import DevicePacker, FrameList, batch_chunks, temporal_indices
+from .transforms import (DevicePacker, FrameList, batch_chunks, box_regions, temporal_indices, track_boxes_at, yuv_geometry)
 
 
 def _resident(video, device, is_yuv):
@@ -332,6 +332,116 @@ class KeyframeDetector:
             p.fill_boxes(batch, boxes_dev, box_item, box0, n, item0, n_items)
             out[box0:box0 + n] = p.launch()[:n]                  # rows behind the n-th are padding
             item0, box0 = item0 + n_items, box0 + n
+            self.forwards += 1
+        p.release_batch()                                        # the videos are the caller's again
+        return out
+
+
+class TubePredictor:
+    """`TubePredictor(deployed, clip_duration, mean, std, div255, crop_size)(video, fps, timestamps, boxes)` =
+    [n_tubes, num_classes] fp32: the deploy form's output rows, one per ACTOR TUBE, in tube order (videos, then time stamps,
+    then the boxes of a time stamp).  The commonest deployment of a classification model: a detector and a tracker find
+    people, and the classifier is run on each person -- the person's rectangle of every frame of the clip, resized to the
+    network's input.  Nothing is cropped, converted or resized in front of the ingest: the rectangles go to the device as a
+    table, and the ingest reads each from the video where it lies (`pv_region_views`).
+
+    `deployed` is a classification model converted as a whole by `convert_to_deployable_form`; `crop_size`, an int or
+    (Ho, Wo), is its input size; `frame_ratios` as for `DevicePacker`.  Arguments are shaped as for `KeyframeDetector`:
+    around each of `timestamps` (seconds) a clip of `clip_duration` seconds is cut (`data.keyframe_frame_table`), and
+    `boxes[k]` is an [r_k, 4] tensor (x1, y1, x2, y2 in the pixels of the source frame, finite), r_k >= 0: r_k tubes, each
+    static over the clip.  With `tracks` (then `boxes` is None) `tracks[k]` is a list of tubes, each a pair
+    (frame_numbers [m], boxes [m, 4]) that is evaluated at the clip's frames (`transforms.track_boxes_at`): the rectangle
+    moves with the actor.  A box becomes a rectangle by `transforms.box_regions(box, H, W, context, square, even)`, `even`
+    for the YUV layouts.  `video` is one video, a list of videos (`timestamps`, `boxes` / `tracks` then per video, `fps`
+    one number or one per video), or `transforms.FrameList`s; `src_layout`, `yuv`, `coded_height`, `height` as for
+    `VideoPredictor`.
+
+    Every tube is one item of the deploy batch; the tubes of all key frames and videos of a call fill the forwards
+    (`batch_chunks`), so only the last one may be short.  Frame tables, rectangles and records are validated and uploaded
+    once per call.  After a call `forwards` holds the number of forwards.  Stored-rotated videos and HDR sources are not
+    taken here."""
+
+    def __init__(self, deployed, clip_duration, mean, std, div255, crop_size, context=1.0, square=True, frame_ratios=None,
+                 src_layout="NTHWC", yuv=("bt709", False), coded_height=None, height=None):
+        if getattr(deployed, "_pv_load_boxes", None) is not None:
+            raise ValueError("TubePredictor runs a classification model on every actor's own pixels; a detection model pools "
+                             "its boxes from the whole frame's features: KeyframeDetector")
+        self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, None, crop_size, 1, src_layout, yuv, coded_height,
+                                   height, regions=True)
+        self.clip_duration, self.src_layout = clip_duration, src_layout
+        self.context, self.square = float(context), bool(square)
+        self.forwards = 0
+
+    @torch.no_grad()
+    def __call__(self, video, fps, timestamps, boxes, tracks=None, height=None, coded_height=None):
+        p = self.packer
+        device = torch.device(p.sess.device)
+        if (boxes is None) == (tracks is None):
+            raise ValueError("give boxes (static over the clip) or tracks (a box per track point), one of them")
+        tubes = boxes if tracks is None else tracks
+        if isinstance(video, (list, tuple)):
+            videos, stamps, tube_lists = list(video), list(timestamps), list(tubes)
+            rates = list(fps) if isinstance(fps, (list, tuple)) else [fps] * len(videos)
+        else:
+            videos, stamps, tube_lists, rates = [video], [timestamps], [tubes], [fps]
+        if not videos or not (len(stamps) == len(tube_lists) == len(rates) == len(videos)):
+            raise ValueError("timestamps, boxes / tracks and fps are given per video: %d, %d and %d for %d videos"
+                             % (len(stamps), len(tube_lists), len(rates), len(videos)))
+
+        def per_video(x):
+            return list(x) if isinstance(x, (list, tuple)) else [x] * len(videos)
+
+        heights, coded = per_video(p.height if height is None else height), per_video(p.coded_height if coded_height is None else coded_height)
+        if not (len(heights) == len(coded) == len(videos)):
+            raise ValueError("height and coded_height are one value or one per video")
+        dims = 3 if p.is_yuv else 4
+        kept, tables, regions = [], [], []
+        for j, (vid, rate, ts, tl) in enumerate(zip(videos, rates, stamps, tube_lists)):
+            as_frames = isinstance(vid, FrameList)               # its frames are checked by video_batch, and never moved
+            if not as_frames and vid.dim() != dims:
+                raise RuntimeError("video %d: expected a %d-d %s video, got %s" % (j, dims, self.src_layout, tuple(vid.shape)))
+            ts, tl = list(ts), list(tl)
+            if len(ts) != len(tl) or not ts:
+                raise ValueError("video %d: %d box / track entries for %d time stamps" % (j, len(tl), len(ts)))
+            if as_frames:
+                (_, hs, ws, _), num_frames = vid.geometry(self.src_layout, coded[j], heights[j]), len(vid)
+            elif p.is_yuv:
+                geom = yuv_geometry(vid, self.src_layout, coded[j], heights[j])
+                hs, ws, num_frames = geom["Hs"], geom["Ws"], geom["N"]
+            elif self.src_layout == "NCTHW":
+                num_frames, hs, ws = vid.shape[1:]
+            else:
+                num_frames, hs, ws = vid.shape[:3]
+            table, _ = keyframe_frame_table(ts, self.clip_duration, num_frames, rate, p.clip_frames)
+            table = torch.as_tensor(table)
+            rows, rects = [], []
+            for k, entry in enumerate(tl):
+                if tracks is None:
+                    if not isinstance(entry, torch.Tensor) or entry.dim() != 2 or entry.shape[1] != 4:
+                        raise ValueError("video %d, time stamp %d: boxes are an [r, 4] tensor (x1, y1, x2, y2)" % (j, k))
+                    own = [r.expand(table.shape[1], 4) for r in box_regions(entry, hs, ws, self.context, self.square, even=p.is_yuv)]
+                else:
+                    own = [box_regions(track_boxes_at(fn, tb, table[k]), hs, ws, self.context, self.square, even=p.is_yuv)
+                           for fn, tb in entry]
+                rows.extend([k] * len(own))
+                rects.extend(own)
+            if not rows:
+                continue                                         # no time stamp of this video has a tube
+            if not as_frames:
+                vid = _resident(vid, device, p.is_yuv)
+            kept.append((vid, heights[j], coded[j]))
+            tables.append(table[rows])
+            regions.append(torch.stack(rects))
+        self.forwards = 0
+        classes = p.model._pv_result().shape[1]
+        out = torch.zeros((sum(r.shape[0] for r in regions), classes), dtype=torch.float32, device=device)
+        if not kept:
+            return out
+        batch = p.video_batch([k[0] for k in kept], tables, [k[1] for k in kept], [k[2] for k in kept],
+                              regions=regions)                   # every check, and the one upload
+        for i0, n in batch_chunks(batch.total, p.batch):
+            p.fill_batch(batch, i0, n)
+            out[i0:i0 + n] = p.launch()[:n]                      # rows of the zero-filled tail are padding
             self.forwards += 1
         p.release_batch()                                        # the videos are the caller's again
         return out

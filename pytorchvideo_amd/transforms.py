@@ -261,6 +261,113 @@ def boxes_to_view(boxes: torch.Tensor, height: int, width: int, short_side: int,
     return clip_boxes_to_image(crop_boxes(out, x, y), crop_size, crop_size)
 
 
+def _size_pair(size, what="size"):
+    """(Ho, Wo) of an int or a pair, both positive."""
+    ho, wo = (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size), int(size))
+    if ho < 1 or wo < 1 or (isinstance(size, (tuple, list)) and len(size) != 2):
+        raise ValueError("%s is a positive int or a pair (Ho, Wo); got %r" % (what, size))
+    return ho, wo
+
+
+def _check_regions(regions, height, width, even=False, what="regions"):
+    """`regions` as a host int64 tensor [..., 4] of (top, left, h, w), every rectangle at least 1 x 1 and inside the
+    height x width frame -- and, `even`, of even members (YUV 4:2:0: a chroma sample is never split).  ValueError otherwise."""
+    regions = torch.as_tensor(regions)
+    if regions.dim() < 1 or regions.shape[-1] != 4 or regions.numel() == 0 or regions.is_floating_point() or regions.dtype == torch.bool:
+        raise ValueError("%s are integer (top, left, h, w) rectangles [..., 4]; got %s %s" % (what, regions.dtype, tuple(regions.shape)))
+    regions = regions.detach().to("cpu", torch.int64)
+    top, left, h, w = regions.unbind(-1)
+    if bool((h < 1).any()) or bool((w < 1).any()):
+        raise ValueError("%s: a rectangle is at least 1 x 1" % what)
+    if bool((top < 0).any()) or bool((left < 0).any()) or bool((top + h > height).any()) or bool((left + w > width).any()):
+        raise ValueError("%s: a rectangle leaves the %d x %d frame" % (what, height, width))
+    if even and bool((regions % 2 != 0).any()):
+        raise ValueError("%s: the rectangles of a YUV 4:2:0 source have even top, left, h and w (box_regions(..., even=True))" % what)
+    return regions
+
+
+def resized_crop(frames: torch.Tensor, regions, size) -> torch.Tensor:
+    """The deterministic core of the reference's `random_resized_crop` (transforms/functional.py): rows
+    [top, top + h) x columns [left, left + w) of every frame, resized to `size` by
+    `interpolate(mode="bilinear", align_corners=False)`, frame by frame.  `frames` is (C, T, H, W); `regions` an integer
+    (top, left, h, w) -- one rectangle for the clip -- or [T, 4], one per frame (what `shift=True` builds); `size` an int or
+    (Ho, Wo).  Returns (C, T, Ho, Wo) fp32.  Every tap stays inside the rectangle: this is crop, then resize, not a window of
+    the resized frame.  The host mirror of `device_resized_crop` / `pv_region_views`."""
+    if frames.dim() != 4:
+        raise ValueError("frames are (C, T, H, W); got %s" % (tuple(frames.shape),))
+    c, t, height, width = frames.shape
+    ho, wo = _size_pair(size)
+    regions = _check_regions(regions, height, width)
+    if regions.dim() == 1:
+        regions = regions.expand(t, 4)
+    if tuple(regions.shape) != (t, 4):
+        raise ValueError("regions are one rectangle [4] or one per frame [%d, 4]; got %s" % (t, tuple(regions.shape)))
+    x = frames.float()
+    out = torch.empty((c, t, ho, wo), dtype=torch.float32, device=frames.device)
+    for k, (top, left, h, w) in enumerate(regions.tolist()):
+        out[:, k:k + 1] = torch.nn.functional.interpolate(x[:, k:k + 1, top:top + h, left:left + w], size=(ho, wo),
+                                                          mode="bilinear", align_corners=False)
+    return out
+
+
+def box_regions(boxes, height: int, width: int, context: float = 1.0, square: bool = False, even: bool = False) -> torch.Tensor:
+    """Float (x1, y1, x2, y2) boxes [..., 4] in the pixels of a height x width frame -> int64 (top, left, h, w) rectangles
+    [..., 4] for `resized_crop` / `device_resized_crop` / `DevicePacker.video_batch(regions=)`.  The rule, in float64:
+      1. the box is enlarged about its centre by `context` (a negative extent counts as 0);
+      2. `square`: the shorter side is set to the longer one, about the same centre;
+      3. the corners are clipped to [0, width] x [0, height];
+      4. left = floor(x1), right = ceil(x2), top = floor(y1), bottom = ceil(y2): every pixel the box touches;
+      5. at least one pixel: left <= width - 1, right >= left + 1 (a degenerate box, or one wholly outside the frame, becomes
+         the pixel nearest to it); rows likewise;
+      6. `even` (YUV 4:2:0 sources; `height` and `width` must be even): left and top go DOWN to even, right and bottom UP to
+         even -- outward, still inside the frame --, so the rectangle is at least 2 x 2.
+    Boxes must be finite."""
+    b = torch.as_tensor(boxes).detach().to("cpu", torch.float64)
+    if b.dim() < 1 or b.shape[-1] != 4:
+        raise ValueError("boxes are (x1, y1, x2, y2) [..., 4]; got %s" % (tuple(b.shape),))
+    if not bool(torch.isfinite(b).all()):
+        raise ValueError("boxes must be finite")
+    height, width = int(height), int(width)
+    if height < 1 or width < 1 or not context > 0:
+        raise ValueError("height and width are positive ints and context a positive factor")
+    if even and (height % 2 or width % 2):
+        raise ValueError("even=True is for YUV 4:2:0 frames, whose height and width are even; got %d x %d" % (height, width))
+    cx, cy = (b[..., 0] + b[..., 2]) / 2, (b[..., 1] + b[..., 3]) / 2
+    bw = torch.clamp(b[..., 2] - b[..., 0], min=0.0) * float(context)
+    bh = torch.clamp(b[..., 3] - b[..., 1], min=0.0) * float(context)
+    if square:
+        bw = bh = torch.maximum(bw, bh)
+    x1, x2 = torch.clamp(cx - bw / 2, 0.0, float(width)), torch.clamp(cx + bw / 2, 0.0, float(width))
+    y1, y2 = torch.clamp(cy - bh / 2, 0.0, float(height)), torch.clamp(cy + bh / 2, 0.0, float(height))
+    left = torch.clamp(torch.floor(x1).to(torch.int64), max=width - 1)
+    top = torch.clamp(torch.floor(y1).to(torch.int64), max=height - 1)
+    right = torch.maximum(torch.ceil(x2).to(torch.int64), left + 1)
+    bottom = torch.maximum(torch.ceil(y2).to(torch.int64), top + 1)
+    if even:
+        left, top = left - left % 2, top - top % 2
+        right, bottom = right + right % 2, bottom + bottom % 2
+    return torch.stack([top, left, bottom - top, right - left], dim=-1)
+
+
+def track_boxes_at(track_frames, track_boxes, frames) -> torch.Tensor:
+    """A box track -- `track_boxes` [m, 4] at the strictly increasing frame numbers `track_frames` [m] -- evaluated at the
+    frame numbers `frames` [n]: linear interpolation between the two neighbouring track points, the first / last box held
+    outside the track.  Returns float64 [n, 4]."""
+    tf = torch.as_tensor(track_frames).detach().to("cpu", torch.float64).reshape(-1)
+    tb = torch.as_tensor(track_boxes).detach().to("cpu", torch.float64)
+    at = torch.as_tensor(frames).detach().to("cpu", torch.float64).reshape(-1)
+    if tf.numel() == 0 or tuple(tb.shape) != (tf.numel(), 4):
+        raise ValueError("a track is frame numbers [m] and boxes [m, 4], m >= 1; got %s and %s" % (tuple(tf.shape), tuple(tb.shape)))
+    if tf.numel() > 1 and not bool((tf[1:] > tf[:-1]).all()):
+        raise ValueError("the frame numbers of a track increase strictly")
+    hi = torch.clamp(torch.searchsorted(tf, at, right=True), max=tf.numel() - 1)
+    lo = torch.clamp(hi - 1, min=0)
+    span = tf[hi] - tf[lo]
+    w = torch.where(span > 0, (at - tf[lo]) / torch.where(span > 0, span, torch.ones_like(span)), torch.zeros_like(span))
+    w = torch.clamp(w, 0.0, 1.0).unsqueeze(-1)
+    return tb[lo] + w * (tb[hi] - tb[lo])
+
+
 class ShortSideScale(torch.nn.Module):
     """transforms/transforms.py:100-121."""
 
@@ -838,11 +945,16 @@ class VideoBatch:
     concatenated table behind every item; `clips[j]` / `row0[j]` = the clips of video j and its first row.  For videos
     given as `FrameList`s `frame_ptrs` (host int64, video-major: the frame addresses of video j from `frame_first[j]` on)
     and `frame_ptrs_dev`, the same bytes on the device, are the pointer table of `pv_frame_views`, and the `src` of record j
-    is the device address of its slice; for tensors they are None."""
+    is the device address of its slice; for tensors they are None.  `regions` / `regions_dev`: the per-pathway rectangle
+    tables of `pv_region_views` for a batch built with `regions=`, else None."""
 
     def __init__(self, videos, sources, items, items_t, tables, video_of, clip_of, clips, row0, n_views, src_dtype, upload,
-                 frame_ptrs=None, frame_ptrs_dev=None, frame_first=None):
+                 frame_ptrs=None, frame_ptrs_dev=None, frame_first=None, regions=None):
         self.frame_ptrs, self.frame_ptrs_dev, self.frame_first = frame_ptrs, frame_ptrs_dev, frame_first
+        # per pathway the `pv_view_region` records of every (table row, destination frame) -- host int32 [n_rows, T_p, 8] and the
+        # same bytes on the device --, or None: the views are the records' own
+        self.regions = regions
+        self.regions_dev = None if regions is None else [upload(r) for r in regions]
         self.videos, self.sources, self.items = list(videos), sources, items
         self.n_views, self.src_dtype, self.clips, self.row0 = n_views, src_dtype, list(clips), list(row0)
         self.total, self.n_rows = len(items), sum(clips)
@@ -854,17 +966,40 @@ class VideoBatch:
         self.item_rows = items_t                   # host int32 [total, 4]: (source, row, view, 0)
 
 
+def region_records(regions, window):
+    """The `pv_view_region` records of validated rectangles [..., 4] (`_check_regions`) for a launch whose window is
+    `window` = (Ho, Wo): a contiguous host int32 tensor [..., 8] holding, per rectangle, top, left, h, w, the BITS of
+    sy = (float)h / (float)Ho and sx = (float)w / (float)Wo -- divided in fp32, as the library divides -- and two zeros."""
+    ho, wo = window
+    rec = torch.zeros(tuple(regions.shape[:-1]) + (8,), dtype=torch.int32)
+    rec[..., :4] = regions.to(torch.int32)
+    rec[..., 4] = (regions[..., 2].to(torch.float32) / torch.tensor(float(ho), dtype=torch.float32)).view(torch.int32)
+    rec[..., 5] = (regions[..., 3].to(torch.float32) / torch.tensor(float(wo), dtype=torch.float32)).view(torch.int32)
+    return rec.contiguous()
+
+
 def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, pathway_frames, channels, device, upload,
-                      height=None, coded_height=None, orientation=None):
+                      height=None, coded_height=None, orientation=None, regions=None):
     """The host half of `DevicePacker.video_batch` (see there): validate every video, build the records, the item sequence
     and the concatenated tables, and hand them to `upload` (host tensor -> device tensor) once.  `crop_size` is the side of
     the square crop, or a pair (Ho, Wo): NO crop -- the window is the whole scaled frame, and every video must scale to
     exactly Ho x Wo.  The videos are all tensors or all `FrameList`s; for `FrameList`s ONE int64 table of frame addresses,
     video-major, is uploaded in front of the records, and record j points at its slice of the device copy.
     `orientation`: one code (`orientation_code`) or one per video, None = 0 -- the videos are the STORED frames, as a decoder
-    hands them out; the record keeps the stored sizes and carries the code, and the views are cut from the displayed frame."""
+    hands them out; the record keeps the stored sizes and carries the code, and the views are cut from the displayed frame.
+    `regions`: one integer tensor [n_clips_j, clip_frames, 4] of (top, left, h, w) per video, aligned with `tables[j]` -- every
+    destination frame is the resize of ITS rectangle of ITS source frame to `crop_size` = (Ho, Wo) (`pv_region_views`); there
+    is then no short-side scale (`short_side` is not read), one view, and no orientation.  Pathway p gets the columns of the
+    rectangle table that `pathway_tables` gives it of the frame table."""
     from . import _lib as L
     videos = list(videos)
+    if regions is not None:
+        regions = list(regions)
+        if len(regions) != len(videos):
+            raise ValueError("%d region tables for %d videos" % (len(regions), len(videos)))
+        if len(views) != 1:
+            raise ValueError("regions are resized whole: one view, not %d" % len(views))
+        window = _size_pair(crop_size, "crop_size")
     if not videos or len(tables) != len(videos):
         raise ValueError("%d frame tables for %d videos" % (len(tables), len(videos)))
     as_frames = isinstance(videos[0], FrameList)
@@ -883,6 +1018,9 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
 
     heights, coded = per_video(height, "height"), per_video(coded_height, "coded_height")
     orients = [_orient(0 if o is None else o) for o in per_video(orientation, "orientation")]
+    if regions is not None and any(orients):
+        raise ValueError("regions are rectangles of the STORED frame and pv_region_views reads upright records only: "
+                         "orientation is not supported together with regions")
     sources = (L.ViewSource * len(videos))()
     nums_frames, dtype = [], videos[0].dtype
     for j, video in enumerate(videos):
@@ -901,7 +1039,11 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
         for k in _YUV_PLANE_FIELDS if is_yuv else ():
             setattr(rec, k, geom[k])
         hd, wd = displayed_size(hs, ws, orients[j])               # the views are cut from the displayed frame
-        hn, wn, offsets = _view_geometry(hd, wd, short_side, crop_size, views, what + ": ")
+        if regions is not None:                                   # the geometry is per frame; the record's own is not read
+            hn, wn, offsets = window[0], window[1], [(0, 0)]
+            regions[j] = _check_regions(regions[j], hs, ws, is_yuv, what + ": regions")
+        else:
+            hn, wn, offsets = _view_geometry(hd, wd, short_side, crop_size, views, what + ": ")
         _set_views(rec, hn, wn, offsets)
         rec.src, rec.N, rec.Hs, rec.Ws = (None if as_frames else video.data_ptr()), nf, hs, ws
         if orients[j]:                                            # default records keep the zero they were built with
@@ -918,11 +1060,20 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
             raise ValueError("video %d: a frame table is [n_clips, %s], got %s" % (j, clip_frames, tuple(t.shape)))
     cat = batch_tables(tables, pathway_frames, nums_frames)       # range-checks every table against ITS video
     clips = [int(torch.as_tensor(t).shape[0]) for t in tables]
+    region_tables = None
+    if regions is not None:
+        for j, r in enumerate(regions):
+            if tuple(r.shape) != (clips[j], clip_frames, 4):
+                raise ValueError("video %d: a region table is [n_clips, clip_frames, 4] = [%d, %d, 4] like its frame table, got %s"
+                                 % (j, clips[j], clip_frames, tuple(r.shape)))
+        whole = torch.cat(regions)                                # [n_rows, clip_frames, 4]: the rows of all videos
+        region_tables = [region_records(whole[:, temporal_indices(clip_frames, tp)], window) for tp in pathway_frames]
     items_t, video_of, clip_of, row0 = batch_items(clips, len(views))
     items = (L.ViewItem * items_t.shape[0]).from_buffer_copy(items_t.numpy().tobytes())
     src_dtype = _src_codes(src_layout, dtype)[1]
     if not as_frames:
-        return VideoBatch(videos, sources, items, items_t, cat, video_of, clip_of, clips, row0, len(views), src_dtype, upload)
+        return VideoBatch(videos, sources, items, items_t, cat, video_of, clip_of, clips, row0, len(views), src_dtype, upload,
+                          regions=region_tables)
     # the pointer table of the call: the frame addresses of video j from first[j] on; the records point into the DEVICE copy
     ptrs = torch.tensor([f.data_ptr() for video in videos for f in video.frames], dtype=torch.int64)
     first = [0]
@@ -932,7 +1083,7 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
     for rec, k in zip(sources, first):
         rec.src = ptrs_dev.data_ptr() + 8 * k
     return VideoBatch(videos, sources, items, items_t, cat, video_of, clip_of, clips, row0, len(views), src_dtype, upload,
-                      ptrs, ptrs_dev, first)
+                      ptrs, ptrs_dev, first, regions=region_tables)
 
 
 class HdrVideoSource:
@@ -982,6 +1133,63 @@ class HdrVideoSource:
         h.transfer, h.tone = hdr[0], hdr[1].data_ptr()
         h.keep = (self, table, matrix, hdr[1])
         return h
+
+
+def _batch_launch_fields(d, batch, table, item0, n_items, channels, src_layout, matrix, window):
+    """The fields of a BatchViewsDesc that say WHAT a launch over items [item0, item0 + n_items) of `batch` (a `VideoBatch`)
+    reads and how large it writes: records, item window, the device frame table `table` [n_rows, T], the source form and the
+    window (Ho, Wo).  Destination and affine map are the caller's."""
+    import ctypes as C
+    from . import _lib as L
+    d.sources, d.sources_dev = C.addressof(batch.sources), batch.sources_dev.data_ptr()
+    first = min(item0, batch.total - 1) * C.sizeof(L.ViewItem)      # n_items == 0: any valid address, never read
+    d.items, d.items_dev = C.addressof(batch.items) + first, batch.items_dev.data_ptr() + first
+    d.t_index, d.n_rows, d.t_stride = table.data_ptr(), table.shape[0], table.stride(0)
+    d.n_sources, d.n_items, d.C, d.T = len(batch.sources), n_items, channels, table.shape[1]
+    d.src_layout, d.src_dtype = _src_codes(src_layout, None)[0], batch.src_dtype
+    if src_layout in _YUV_ANY:
+        d.c_step, d.yuv2rgb = (2 if src_layout in _YUV_INTERLEAVED else 1), matrix.data_ptr()
+    d.Ho, d.Wo, d.n_views = window[0], window[1], batch.n_views
+
+
+@torch.no_grad()
+def device_resized_crop(clip, regions, size, mean=None, std=None, div255=False, dtype=torch.bfloat16, src_layout="NCTHW",
+                        yuv=("bt709", False), coded_height=None, height=None):
+    """Normalize(Div255(resized_crop(clip[b], regions[b], size))) for every clip b in ONE launch of `pv_region_views`: a planar
+    [B, C, T, Ho, Wo] tensor of `dtype` (bf16 or fp32) on the GPU.  `clip` is [B,C,T,H,W] ("NCTHW"; uint8 or float), the
+    decoder's [B,T,H,W,3] uint8 ("NTHWC"), or -- the YUV 4:2:0 layouts of `device_scale_crop`, 8- and 16-bit -- [B, T, Hc*3/2, W]
+    (or [T, Hc*3/2, W]: one clip) with the strides it has, converted tap by tap (`yuv`, `coded_height`, `height` as there).
+    `regions` is an integer [B, T, 4] tensor of (top, left, h, w): a rectangle per frame (`box_regions`; even members for
+    YUV); `size` an int or (Ho, Wo).  The clips are read where they lie: no crop, no RGB copy and no resized intermediate is
+    made.  The transform alone, as `device_scale_crop` is; `resized_crop` is the host mirror."""
+    from . import _lib as L
+    if src_layout not in ("NCTHW", "NTHWC") + _YUV_ANY:
+        raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("dtype is torch.bfloat16 or torch.float32")
+    window = _size_pair(size)
+    is_yuv = src_layout in _YUV_ANY
+    if is_yuv and clip.dim() == 3:
+        clip, regions = clip.unsqueeze(0), torch.as_tensor(regions).unsqueeze(0)
+    if clip.dim() != (4 if is_yuv else 5):
+        raise RuntimeError("expected %s clips [B, ...], got %s" % (src_layout, tuple(clip.shape),))
+    device = clip.device if clip.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    clip = clip.to(device, non_blocking=True) if is_yuv else _device_source(clip, device)
+    b, t = clip.shape[0], clip.shape[2] if src_layout == "NCTHW" else clip.shape[1]
+    regions = torch.as_tensor(regions)
+    if regions.dim() != 3 or tuple(regions.shape) != (b, t, 4):
+        raise ValueError("regions are [B, T, 4] = [%d, %d, 4], a rectangle per frame of every clip; got %s" % (b, t, tuple(regions.shape)))
+    channels = 3 if is_yuv else clip.shape[1 if src_layout == "NCTHW" else 4]
+    frames = torch.arange(t, dtype=torch.int32)[None]
+    # every clip a source of its own, its T frames one table row: the item-sourced launch of DevicePacker.fill_batch
+    batch = build_video_batch(list(clip.unbind(0)), [frames] * b, src_layout, None, window, (1,), [t], channels, device,
+                              lambda x: x.to(device), height, coded_height, None, [regions[j:j + 1] for j in range(b)])
+    g = L.RegionViewsDesc()
+    matrix = _yuv_matrix_of(yuv, src_layout).float().reshape(12).to(device) if is_yuv else None
+    _batch_launch_fields(g.frames.batch, batch, batch.tables[0], 0, b, channels, src_layout, matrix, window)
+    g.regions, g.regions_dev = batch.regions[0].data_ptr(), batch.regions_dev[0].data_ptr()
+    return _scale_crop_launch(g.frames.batch, "pv_region_views", "region_views", b, channels, (mean, std, div255), dtype, device,
+                              outer=g)
 
 
 @torch.no_grad()
@@ -1066,13 +1274,36 @@ class DevicePacker:
     (one view; every item is the clip around one key frame), any source layout is legal -- the boxes no longer pass through
     the host -- and `fill_boxes(batch, boxes_dev, box_item_dev, box0, n, item0, n_items)` fills the form's box buffer for the
     forward `fill_batch(batch, item0, n_items)` filled (`pv_box_views`); `inference.KeyframeDetector` is the loop around it.
-    The clip-at-a-time `packer(clip, bboxes)` keeps mapping the boxes on the host and keeps refusing YUV clips."""
+    The clip-at-a-time `packer(clip, bboxes)` keeps mapping the boxes on the host and keeps refusing YUV clips.
+
+    `regions=True` with `crop_size` (an int or (Ho, Wo): the deploy form's H x W) and WITHOUT `short_side` makes the packer the
+    ingest of actor tubes: `video_batch(videos, tables, regions=[...])` takes a rectangle (top, left, h, w) per frame of
+    every table row, and `fill_batch` resizes each rectangle of the video, read where it lies, to `crop_size`
+    (`pv_region_views`) -- no short-side scale, no crop window, one view; classification forms, any source layout, whole
+    videos or `FrameList`s; no `orientation` and no `hdr`.  This mode runs through `video_batch` / `fill_batch` only;
+    `inference.TubePredictor` is the loop around it."""
 
     def __init__(self, deployed, mean=None, std=None, div255=False, frame_ratios=None, short_side=None, crop_size=None,
                  spatial_idx=1, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None, keyframes=False,
-                 hdr=None):
+                 hdr=None, regions=False):
         self.subs = None
-        if (short_side is None) != (crop_size is None) and not (keyframes and crop_size is None):
+        self.region_mode = bool(regions)
+        if self.region_mode:
+            # the ingest of actor tubes: no short-side scale and no crop window -- every frame's rectangle is resized to crop_size
+            if short_side is not None:
+                raise ValueError("a regions packer resizes every rectangle to crop_size: short_side=%r contradicts it (the "
+                                 "whole frame is not scaled); give crop_size alone" % (short_side,))
+            if crop_size is None or keyframes:
+                raise ValueError("a regions packer takes crop_size, an int or (Ho, Wo): the size every rectangle is resized to"
+                                 " (keyframes=True is the detection models' path)")
+            if hdr is not None:
+                raise ValueError("hdr is not supported together with regions: pv_region_views has no PQ / HLG tap map")
+            if _views(spatial_idx) != (1,):
+                raise ValueError("a regions packer has one view (a rectangle is resized whole): spatial_idx=%r" % (spatial_idx,))
+            if getattr(deployed, "_pv_load_boxes", None) is not None:
+                raise ValueError("a detection model pools its boxes from the whole frame's features: inference.KeyframeDetector")
+            crop_size = _size_pair(crop_size, "crop_size")
+        elif (short_side is None) != (crop_size is None) and not (keyframes and crop_size is None):
             raise ValueError("short_side and crop_size are given together (short_side alone -- no crop -- is a mode of the "
                              "key-frame path: keyframes=True)")
         # keyframes=True and short_side alone: no crop (the detection tutorial's protocol) -- the window is the whole scaled frame
@@ -1089,14 +1320,14 @@ class DevicePacker:
                              "of an RGB clip on the host, and that path is not built for YUV sources (the key-frame path, "
                              "keyframes=True / inference.KeyframeDetector, maps them on the device for any layout)" % src_layout)
         self.views = _views(spatial_idx) if crop_size is not None else (1,)
-        if short_side is None and src_layout != "NCTHW":
+        if short_side is None and src_layout != "NCTHW" and not self.region_mode:
             raise ValueError("a frame-interleaved or YUV clip is read by the resampling path only: give short_side and crop_size")
         if hasattr(deployed, "parts") and hasattr(deployed, "_pv_launch"):
             # split-batch deploy form (convert_to_deployable_form(..., streams=k)): one packer per sub-batch fills that
             # sub-plan's input buffers, then ONE launch of the joint graph
             self.model = deployed
             self.subs = [DevicePacker(p, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv,
-                                      coded_height, height, keyframes, hdr) for p in deployed.parts]
+                                      coded_height, height, keyframes, hdr, regions) for p in deployed.parts]
             self.window = self.subs[0].window
             self.sess, self.refs = self.subs[0].sess, self.subs[0].refs
             self.frame_ratios = self.subs[0].frame_ratios
@@ -1117,8 +1348,8 @@ class DevicePacker:
         self.frame_ratios = tuple(int(r) for r in frame_ratios)
         if crop_size is not None:
             for ref in self.refs:
-                if (ref.H, ref.W) != (crop_size, crop_size):
-                    raise ValueError("crop_size %d is not the %d x %d input the deploy form was converted for"
+                if (ref.H, ref.W) != (crop_size if self.region_mode else (crop_size, crop_size)):
+                    raise ValueError("crop_size %s is not the %d x %d input the deploy form was converted for"
                                      % (crop_size, ref.H, ref.W))
             if len(self.views) > 1 and getattr(deployed, "_pv_load_boxes", None) is not None:
                 raise ValueError("a detection model takes one view: its boxes belong to one crop")
@@ -1126,7 +1357,7 @@ class DevicePacker:
             raise ValueError("the input pathways of one deploy form have one frame size")
         # (Ho, Wo) of the window every resampling launch writes: the crop, or -- no crop -- the deploy form's own H x W, which
         # every source must then scale to (checked per video, with both sizes named)
-        self.window = (self.refs[0].H, self.refs[0].W) if crop_size is None else (crop_size, crop_size)
+        self.window = (self.refs[0].H, self.refs[0].W) if crop_size is None or self.region_mode else (crop_size, crop_size)
         self.scale, self.shift = _affine(mean, std, div255, self.refs[0].C, self.sess.device)
         self._index = {}
         self._planar = {}
@@ -1169,6 +1400,9 @@ class DevicePacker:
     @torch.no_grad()
     def __call__(self, clip, bboxes=None, orientation=0):
         _refuse_orientation(orientation, "a clip-at-a-time call")
+        if self.region_mode:
+            raise RuntimeError("a regions packer runs through video_batch(..., regions=) / fill_batch; clips with a rectangle "
+                               "per frame alone: device_resized_crop")
         load_boxes = getattr(self.model, "_pv_load_boxes", None)
         if (bboxes is None) != (load_boxes is None):
             raise RuntimeError("bboxes are given to a detection model and only to a detection model")
@@ -1358,7 +1592,7 @@ class DevicePacker:
             fill(d, ref, planar=self._planar_for(i, ref))
 
     # ------------------------------------------------------------------------- many videos per forward (pv_batch_views)
-    def video_batch(self, videos, tables, height=None, coded_height=None, orientation=None):
+    def video_batch(self, videos, tables, height=None, coded_height=None, orientation=None, regions=None):
         """Prepare a list of decoded videos -- any lengths, any frame sizes, all in the packer's source layout and on the
         device -- for `fill_batch`: `tables[j]` is the [n_clips_j, clip_frames] frame table of video j
         (`data.clip_frame_table`).  Every video is validated as `fill_video` validates one (device, dtype, contiguity of the
@@ -1370,8 +1604,19 @@ class DevicePacker:
         it lies (`pv_frame_views`); a mix of tensors and FrameLists is a ValueError.  `orientation`: one code
         (`orientation_code`) or one per video for videos STORED turned and / or mirrored -- a portrait phone clip is landscape
         frames plus "rotate 90": the ingest reads them in place and cuts the views from the displayed frame, and
-        `fill_boxes` takes boxes given in stored pixels along.  Returns a `VideoBatch`, which keeps the videos alive."""
-        if self.short_side is None:
+        `fill_boxes` takes boxes given in stored pixels along.  Returns a `VideoBatch`, which keeps the videos alive.
+        `regions` (a packer constructed with `regions=True` and `crop_size` alone, and only such a packer): one integer
+        tensor [n_clips_j, clip_frames, 4] of (top, left, h, w) per video, aligned with `tables[j]` -- destination frame t of
+        row r is the rectangle `regions[j][r, t]` of frame `tables[j][r, t]`, resized to `crop_size` (`pv_region_views`; `box_regions` makes
+        rectangles of boxes).  Validated here (inside the frame, at least 1 x 1, even members for YUV layouts) and uploaded
+        once, with the records.  ValueError together with `orientation`; such a packer has no `hdr` and one view."""
+        if self.region_mode != (regions is not None):
+            if regions is not None:
+                raise ValueError("regions are resized to crop_size with no short-side scale: this packer scales every frame by "
+                                 "short_side=%r, which contradicts them -- construct it with regions=True and crop_size alone"
+                                 % (self.short_side,))
+            raise ValueError("a regions packer takes video_batch(videos, tables, regions=[...])")
+        if self.short_side is None and not self.region_mode:
             raise RuntimeError("video_batch resamples: construct the packer with short_side and crop_size")
         if getattr(self.model, "_pv_load_boxes", None) is not None and not self.keyframes:
             raise RuntimeError("a detection model takes boxes of key frames, not videos: construct the packer with "
@@ -1386,7 +1631,7 @@ class DevicePacker:
                                  self.window if self.no_crop else self.crop_size, self.views,
                                  [ref.T for ref in refs], refs[0].C, device, lambda t: t.to(device),
                                  self.height if height is None else height,
-                                 self.coded_height if coded_height is None else coded_height, orientation)
+                                 self.coded_height if coded_height is None else coded_height, orientation, regions)
 
     @torch.no_grad()
     def fill_batch(self, batch, i0, n):
@@ -1394,7 +1639,7 @@ class DevicePacker:
         the deploy batch: one pv_batch_views launch per pathway (and per sub-plan of a split-batch form -- a sub-plan's window
         is a pointer offset into the item sequence).  A short chunk zeroes the rest of the buffers, as `fill_video` does.
         Nothing is launched here but the ingest: run `launch()` next."""
-        if not isinstance(batch, VideoBatch) or batch.n_views != len(self.views):
+        if not isinstance(batch, VideoBatch) or batch.n_views != len(self.views) or (batch.regions is not None) != self.region_mode:
             raise RuntimeError("fill_batch takes what video_batch of this packer returned")
         if not (0 <= i0 and 0 < n <= self.batch and i0 + n <= batch.total):
             raise RuntimeError("items [%d, %d) are not a chunk of at most %d of the batch's %d items" % (i0, i0 + n, self.batch, batch.total))
@@ -1414,23 +1659,16 @@ class DevicePacker:
 
     def _fill_batch(self, batch, item0, n_items):
         """One pv_batch_views launch per pathway into this plan's buffers -- pv_frame_views, the same descriptor with the
-        call's pointer table beside it, for a batch of FrameLists; see Session.video_views for the tail."""
-        import ctypes as C
+        call's pointer table beside it, for a batch of FrameLists; pv_region_views, with the pathway's rectangle table beside
+        both, for a batch built with `regions=`; see Session.video_views for the tail."""
         from . import _lib as L
         self._src = batch                                  # alive until the launch has run
         for i, (ref, tab) in enumerate(zip(self.refs, batch.tables)):
+            g = L.RegionViewsDesc() if batch.regions is not None else None   # pv_region_views: either source form, rectangles behind
             h = L.HdrViewsDesc() if self.hdr is not None else None           # pv_hdr_views: either source form, tap map behind
-            f = h.frames if h is not None else (L.FrameViewsDesc() if batch.frame_ptrs is not None else None)
+            f = g.frames if g is not None else h.frames if h is not None else (L.FrameViewsDesc() if batch.frame_ptrs is not None else None)
             d = L.BatchViewsDesc() if f is None else f.batch
-            d.sources, d.sources_dev = C.addressof(batch.sources), batch.sources_dev.data_ptr()
-            first = min(item0, batch.total - 1) * C.sizeof(L.ViewItem)      # n_items == 0: any valid address, never read
-            d.items, d.items_dev = C.addressof(batch.items) + first, batch.items_dev.data_ptr() + first
-            d.t_index, d.n_rows, d.t_stride = tab.data_ptr(), tab.shape[0], tab.stride(0)
-            d.n_sources, d.n_items, d.C, d.T = len(batch.sources), n_items, ref.C, ref.T
-            d.src_layout, d.src_dtype = _src_codes(self.src_layout, None)[0], batch.src_dtype
-            if self.is_yuv:
-                d.c_step, d.yuv2rgb = (2 if self.src_layout in _YUV_INTERLEAVED else 1), self.yuv_matrix.data_ptr()
-            d.Ho, d.Wo, d.n_views = self.window[0], self.window[1], len(self.views)
+            _batch_launch_fields(d, batch, tab, item0, n_items, ref.C, self.src_layout, self.yuv_matrix, self.window)
             _set_affine(d, self.scale, self.shift)
             if f is None:
                 self.sess.batch_views(d, ref, planar=self._planar_for(i, ref))
@@ -1438,6 +1676,10 @@ class DevicePacker:
             if batch.frame_ptrs is not None:
                 f.frame_ptrs, f.frame_ptrs_dev = batch.frame_ptrs.data_ptr(), batch.frame_ptrs_dev.data_ptr()
                 f.n_frame_ptrs = batch.frame_ptrs.numel()
+            if g is not None:
+                g.regions, g.regions_dev = batch.regions[i].data_ptr(), batch.regions_dev[i].data_ptr()
+                self.sess.region_views(g, ref, planar=self._planar_for(i, ref))
+                continue
             if h is None:
                 self.sess.frame_views(f, ref, planar=self._planar_for(i, ref))
                 continue
