@@ -33,13 +33,26 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kBK = 32;
 constexpr int kMaxTaps = 512;
+constexpr int kGateMaxC = 512;   // widest layer whose squeeze-excitation gate rows the kernel stages in LDS
 
 template <typename T> struct LdsLd { static constexpr int v = kBK + 8; };
 template <> struct LdsLd<float> { static constexpr int v = kBK + 4; };
 
-template <typename T, int BM, int BN, int WM_, int WN_, bool PW>
+// FX: how the pointwise bf16 kernel fetches and transforms its operands (round 22).  kFxOff is the kernel as it was: loads behind
+// per-chunk tests, the operand transform decided at run time; the general and the fp32 instantiations are always kFxOff.
+// The other three fetch through buffer resources: every K step issues the same XCH + WCH loads with no branch around any of
+// them (rows past M, channels past cout and the K tail get an out-of-range offset and read zero), so the compiler can COUNT
+// the requests in flight and leaves the younger tile outstanding while the older one goes to LDS.
+//   kFxPlain      no gate, no operand activation
+//   kFxGateSwish  swish(x * gate), the gate rows of every tile staged in LDS (the host checks that no tile spans 3 clips)
+//   kFxAny        whatever the descriptor asks for, decided at run time as in kFxOff
+enum { kFxOff = 0, kFxPlain = 1, kFxGateSwish = 2, kFxAny = 3 };
+
+template <typename T, int BM, int BN, int WM_, int WN_, bool PW, int FX = kFxOff>
 __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_desc d) {
   constexpr int LD = LdsLd<T>::v;
+  constexpr bool BUF = FX != kFxOff;
+  static_assert(!BUF || (PW && sizeof(T) == 2), "buffer-addressed operands: pointwise bf16 only");
   constexpr int TM = BM / WM_ / 16;  // voxel tiles per wave
   constexpr int TN = BN / WN_ / 16;  // channel tiles per wave
   static_assert(WM_ * WN_ == 4, "4 waves");
@@ -53,7 +66,6 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_de
   __shared__ int s_tap[PW ? 1 : kMaxTaps];
   // the squeeze-excitation gates of the (at most two) clips a tile's rows belong to: read once per workgroup instead of once per
   // staged chunk -- the per-chunk global loads sat on the critical path of every K step (X3D res5's gated conv_c: 39 -> ... us)
-  constexpr int kGateMaxC = 512;
   __shared__ __attribute__((aligned(16))) float s_gate[PW ? 2 * kGateMaxC : 4];
 
   const int tid = threadIdx.x;
@@ -93,7 +105,23 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_de
 
   bool gate_lds = false;
   int gate_b0 = 0;
-  if constexpr (PW) {
+  // kFxGateSwish: row pitch of the two staged gate rows, a multiple of the K step; the entries behind cin hold 1.0f (they meet
+  // the zeros of the K tail), so that the K loop multiplies without asking where the row ends
+  const int gate_pitch = pv_round_up(d.cin, kBK);
+  constexpr int GT = 2 * kGateMaxC / kThreads;
+  float gv[GT];
+  if constexpr (FX == kFxGateSwish) {
+    // requested here, written to LDS behind the request for the first K tile (one wait for both, in front of the K loop)
+    gate_b0 = (int)(m0 / S_out);
+    const float* __restrict__ base = d.a_gate + (long)gate_b0 * d.cin;
+    const bool has_next = gate_b0 + 1 < d.B;   // the last clip has no next one
+#pragma unroll
+    for (int k = 0; k < GT; ++k) {
+      const int i = tid + k * kThreads;
+      const int r = i >= gate_pitch ? 1 : 0, c = i - r * gate_pitch;
+      gv[k] = base[c < d.cin && (r == 0 || has_next) ? r * d.cin + c : 0];      // (clamped index: every value is requested)
+    }
+  } else if constexpr (PW && FX != kFxPlain) {
     if (d.a_gate != nullptr) {
       gate_b0 = (int)(m0 / S_out);
       const long m_last = (m0 + BM < M ? m0 + BM : M) - 1;
@@ -167,6 +195,25 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_de
     w_ok[i] = (id < BN * KC) && (c < d.cout);
     w_off[i] = (long)c * K;
   }
+  // BUF: the same geometry as 32-bit byte offsets into two buffer resources (the host sends operands of 2 GiB or more down
+  // kFxOff).  kOob is past every record count, and stays there when the K step's offset is added: a row past M or a channel
+  // past cout reads zero without a test in the loop.
+  constexpr unsigned kOob = 0x80000000u;
+  __amdgpu_buffer_rsrc_t rx, rw;
+  unsigned x_bo[XCH], w_bo[WCH];
+  int g_lo[XCH];   // kFxGateSwish: where the row's gate values start in s_gate
+  if constexpr (BUF) {
+    const long x_elems = (long)(d.B - 1) * d.x_bs + (long)(S_out - 1) * d.ldx + d.cin;
+    rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)(x_elems * 2), 0x00020000);
+    rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(Wt), 0, (int)((long)d.cout * K * 2), 0x00020000);
+#pragma unroll
+    for (int i = 0; i < XCH; ++i) {
+      x_bo[i] = x_ok[i] ? (unsigned)(x_off[i] * 2) + (unsigned)kc * 16u : kOob;
+      g_lo[i] = (x_ok[i] ? x_b[i] - gate_b0 : 0) * gate_pitch + kc * 8;      // (rows past M carry zeros and clip 0)
+    }
+#pragma unroll
+    for (int i = 0; i < WCH; ++i) w_bo[i] = w_ok[i] ? (unsigned)(w_off[i] * 2) + (unsigned)kc * 16u : kOob;
+  }
 
   // Two K tiles in flight in registers, in two FIXED sets used alternately (round 6; no copies between them: a copy waits for the
   // load).  A step's global loads used to be hidden only behind ONE step of MFMAs (~0.1 us of a ~2 us latency), so small-M layers
@@ -175,6 +222,19 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_de
 
   auto load_global = [&](Chunk8<T> (&xr)[XCH], Chunk8<T> (&wr)[WCH], int ks) {
     const int k0 = ks * kBK + kc * 8;
+    if constexpr (BUF) {
+      // XCH + WCH requests, always: a chunk of the K tail (k0 >= K, also every chunk of a step past the last one) is sent out
+      // of range like a missing row and comes back as zero from the range check, without touching memory
+      const unsigned kb = (unsigned)ks * (kBK * 2);
+      const bool kok = k0 < K;
+#pragma unroll
+      for (int i = 0; i < XCH; ++i)
+        xr[i].v = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(kok ? x_bo[i] + kb : kOob), 0, 0));
+#pragma unroll
+      for (int i = 0; i < WCH; ++i)
+        wr[i].v = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)(kok ? w_bo[i] + kb : kOob), 0, 0));
+      return;
+    }
     if constexpr (PW) {
       const bool kok = k0 < K;
 #pragma unroll
@@ -211,7 +271,21 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_de
 #pragma unroll
     for (int i = 0; i < XCH; ++i) {
       const int r = tid / KC + i * (kThreads / KC);
-      if (d.a_gate != nullptr || d.a_act != PV_ACT_NONE) {
+      if constexpr (FX == kFxGateSwish) {
+        // straight-line: unpack, eight multiplies, eight sigmoids, pack.  Gate, Swish, round to bf16, as in the generic branch
+        float f[8];
+        xr[i].to_f32(f);
+        const float* g = s_gate + g_lo[i] + ks * kBK;
+        const float4 g0 = *reinterpret_cast<const float4*>(g);
+        const float4 g1 = *reinterpret_cast<const float4*>(g + 4);
+        f[0] *= g0.x; f[1] *= g0.y; f[2] *= g0.z; f[3] *= g0.w;
+        f[4] *= g1.x; f[5] *= g1.y; f[6] *= g1.z; f[7] *= g1.w;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] *= pv_sigmoid(f[j]);
+        xr[i].from_f32(f);
+      } else if constexpr (FX == kFxPlain) {
+        // the chunk goes to LDS as it came
+      } else if (d.a_gate != nullptr || d.a_act != PV_ACT_NONE) {
         // pointwise only (checked on the host): k0 is the input channel
         float f[8];
         xr[i].to_f32(f);
@@ -237,7 +311,9 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_de
 #pragma unroll
     for (int i = 0; i < WCH; ++i) {
       const int id = tid + i * kThreads;
-      if (id < BN * KC) wr[i].store(ws + w_row[i] * LD + kc * 8);
+      // (BUF: where the tile is whole chunks per thread the test is dropped at compile time -- the compiler does not know that
+      // tid < kThreads and put the store, and the wait for its chunk, behind an exec mask)
+      if ((BUF && BN * KC % kThreads == 0) || id < BN * KC) wr[i].store(ws + w_row[i] * LD + kc * 8);
     }
   };
 
@@ -248,7 +324,8 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_de
     for (int b = 0; b < TM; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // which channel-tile pairs of this wave hold real channels (wave-uniform)
-  const int wave_c0 = n0 + wn * (TN * 16);
+  // (BUF: from a scalar register, so that the tests around the MFMA groups are scalar branches, not exec masks)
+  const int wave_c0 = n0 + (BUF ? __builtin_amdgcn_readfirstlane(wn) : wn) * (TN * 16);
 
   const int nk = (K + kBK - 1) / kBK;
   auto compute = [&](int buf) {
@@ -289,23 +366,66 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_de
       }
     }
   };
-  load_global(xrA, wrA, 0);
-  store_lds(xrA, wrA, 0, 0);
-  if (nk > 1) load_global(xrA, wrA, 1);
-  if (nk > 2) load_global(xrB, wrB, 2);
-  __syncthreads();
-  for (int ks = 0; ks < nk; ks += 2) {
-    // even step: tile ks + 1 waits in set A, tile ks + 2 is on its way into set B
+  if constexpr (BUF) {
+    // The same steps in the same order, but every load_global is issued whether its tile exists or not (a tile past the last
+    // one is XCH + WCH range-checked requests that return zero and are never stored).  With a request count that no branch
+    // changes, the wait in front of each store_lds is vmcnt(XCH + WCH) or higher: it retires the older set and leaves the
+    // XCH + WCH requests of the younger tile -- the set the NEXT step stores -- outstanding across the barrier.  (Behind
+    // `if (ks + 3 < nk)` the compiler had to assume either count and waited for vmcnt(0): one memory round trip per K step.)
+    load_global(xrA, wrA, 0);
+    if constexpr (FX == kFxGateSwish) {
+      const bool has_next = gate_b0 + 1 < d.B;
+      pv_wait_loads();
+#pragma unroll
+      for (int k = 0; k < GT; ++k) {
+        const int i = tid + k * kThreads;
+        const int r = i >= gate_pitch ? 1 : 0, c = i - r * gate_pitch;
+        if (i < 2 * gate_pitch) s_gate[i] = c >= d.cin ? 1.0f : (r == 0 || has_next) ? gv[k] : 0.f;
+      }
+      __syncthreads();
+    }
+    store_lds(xrA, wrA, 0, 0);
+    load_global(xrA, wrA, 1);
+    load_global(xrB, wrB, 2);
+    __syncthreads();
+    // whole pairs of steps in the loop, the last one or two steps behind it: one exit and one back edge.  (With a `break` in
+    // the middle the loop had a second way back to its head on which set B was the OLDER one, and the wait for set A fell to 0.)
+    int ks = 0;
+    for (; ks + 2 < nk; ks += 2) {
+      compute(0);
+      store_lds(xrA, wrA, 1, ks + 1);     // waits for set A; set B (tile ks + 2) stays in flight
+      load_global(xrA, wrA, ks + 3);
+      __syncthreads();
+      compute(1);
+      store_lds(xrB, wrB, 0, ks + 2);     // waits for set B; set A (tile ks + 3) stays in flight
+      load_global(xrB, wrB, ks + 4);
+      __syncthreads();
+    }
     compute(0);
-    if (ks + 1 < nk) store_lds(xrA, wrA, 1, ks + 1);
-    if (ks + 3 < nk) load_global(xrA, wrA, ks + 3);
+    if (ks + 1 < nk) {
+      store_lds(xrA, wrA, 1, ks + 1);
+      __syncthreads();
+      compute(1);
+    }
+  } else {
+    load_global(xrA, wrA, 0);
+    store_lds(xrA, wrA, 0, 0);
+    if (nk > 1) load_global(xrA, wrA, 1);
+    if (nk > 2) load_global(xrB, wrB, 2);
     __syncthreads();
-    if (ks + 1 >= nk) break;
-    // odd step: tile ks + 2 waits in set B, tile ks + 3 is on its way into set A
-    compute(1);
-    if (ks + 2 < nk) store_lds(xrB, wrB, 0, ks + 2);
-    if (ks + 4 < nk) load_global(xrB, wrB, ks + 4);
-    __syncthreads();
+    for (int ks = 0; ks < nk; ks += 2) {
+      // even step: tile ks + 1 waits in set A, tile ks + 2 is on its way into set B
+      compute(0);
+      if (ks + 1 < nk) store_lds(xrA, wrA, 1, ks + 1);
+      if (ks + 3 < nk) load_global(xrA, wrA, ks + 3);
+      __syncthreads();
+      if (ks + 1 >= nk) break;
+      // odd step: tile ks + 2 waits in set B, tile ks + 3 is on its way into set A
+      compute(1);
+      if (ks + 2 < nk) store_lds(xrB, wrB, 0, ks + 2);
+      if (ks + 4 < nk) load_global(xrB, wrB, ks + 4);
+      __syncthreads();
+    }
   }
 
   // ---- epilogue: lane owns channels c0..c0+7 of voxel m for every (pair p, tile t) ----
@@ -365,6 +485,24 @@ __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const pv_conv3d_de
   }
 }
 
+// Which operand path a pointwise bf16 layer takes on tiles of `bm` voxels (the FX parameter of the kernel).
+int pw_operand_path(const pv_conv3d_desc& d, int bm) {
+  // pv_tune "igemm_pw_buf" = 0 (experiments, parity tests): the kernel with per-chunk tests, as before round 22
+  if (!pv_tune("igemm_pw_buf", 1)) return kFxOff;
+  const long S_out = (long)d.To * d.Ho * d.Wo, M = (long)d.B * S_out;
+  // 32-bit byte offsets below 2^31 from the operand's first element; a larger clip or filter keeps 64-bit addresses (kFxOff)
+  if (d.x_bs < 0 || d.ldx < d.cin) return kFxOff;
+  const long x_bytes = ((long)(d.B - 1) * d.x_bs + (S_out - 1) * d.ldx + d.cin) * 2, w_bytes = (long)d.cout * d.cin * 2;
+  if (x_bytes > 0x7fffffffL || w_bytes > 0x7fffffffL) return kFxOff;
+  if (!d.a_gate && d.a_act == PV_ACT_NONE) return kFxPlain;
+  if (!d.a_gate || d.a_act != PV_ACT_SWISH || d.cin > kGateMaxC) return kFxAny;
+  // the kernel stages the gate rows of TWO clips per tile: every tile must lie within two (always so from bm - 1 voxels per clip on)
+  if (S_out < bm - 1)
+    for (long m0 = 0; m0 < M; m0 += bm)
+      if (((m0 + bm < M ? m0 + bm : M) - 1) / S_out - m0 / S_out > 1) return kFxAny;
+  return kFxGateSwish;
+}
+
 template <typename T, int BM, int BN, int WM_, int WN_>
 int launch_cfg(const pv_conv3d_desc& d, bool pw, hipStream_t s) {
   const long M = (long)d.B * d.To * d.Ho * d.Wo;
@@ -372,6 +510,14 @@ int launch_cfg(const pv_conv3d_desc& d, bool pw, hipStream_t s) {
   const long tiles = pv_ceil_div(M, BM) * pv_ceil_div(cout_p8, BN);
   if (tiles <= 0 || tiles > 0x7fffffffL) return PV_ERR_INVALID;
   dim3 grid((unsigned)tiles), block(kThreads);
+  if constexpr (sizeof(T) == 2) {
+    switch (pw ? pw_operand_path(d, BM) : kFxOff) {
+      case kFxPlain: PV_LAUNCH((conv_igemm_kernel<T, BM, BN, WM_, WN_, true, kFxPlain>), grid, block, 0, s, d); PV_LAUNCH_CHECK(); return PV_OK;
+      case kFxGateSwish: PV_LAUNCH((conv_igemm_kernel<T, BM, BN, WM_, WN_, true, kFxGateSwish>), grid, block, 0, s, d); PV_LAUNCH_CHECK(); return PV_OK;
+      case kFxAny: PV_LAUNCH((conv_igemm_kernel<T, BM, BN, WM_, WN_, true, kFxAny>), grid, block, 0, s, d); PV_LAUNCH_CHECK(); return PV_OK;
+      default: break;
+    }
+  }
   if (pw) PV_LAUNCH((conv_igemm_kernel<T, BM, BN, WM_, WN_, true>), grid, block, 0, s, d);
   else PV_LAUNCH((conv_igemm_kernel<T, BM, BN, WM_, WN_, false>), grid, block, 0, s, d);
   PV_LAUNCH_CHECK();
@@ -381,7 +527,8 @@ int launch_cfg(const pv_conv3d_desc& d, bool pw, hipStream_t s) {
 template <typename T> int launch_conv(const pv_conv3d_desc& d, bool pw, hipStream_t s) {
   const int cout_p8 = pv_round_up(d.cout, 8);
   if (cout_p8 <= 32) return launch_cfg<T, 256, 32, 4, 1>(d, pw, s);
-  if (cout_p8 <= 64) return launch_cfg<T, 128, 64, 4, 1>(d, pw, s);
+  // pv_tune "igemm_bn64" (experiments): 64-channel tiles for wide layers too -- 3 workgroups per 192 channels instead of 2 (profiles/r22)
+  if (cout_p8 <= 64 || pv_tune("igemm_bn64", 0)) return launch_cfg<T, 128, 64, 4, 1>(d, pw, s);
   return launch_cfg<T, 128, 128, 2, 2>(d, pw, s);
 }
 
