@@ -722,6 +722,58 @@ typedef struct pv_region_views_desc {
 } pv_region_views_desc;               /* sizeof(pv_frame_views_desc) + 16 */
 int pv_region_views(const pv_region_views_desc* d, pv_stream_t stream);
 
+/* ---- box-filtered downscale: interpolation="area" inside the launch ---------------------------------------------------------
+ * pv_resample_crop's four taps per output pixel are right for sources that were shrunk beforehand.  A decoder surface of 1080p
+ * scaled to a short side of 256 has some 18 source pixels under every output pixel (2160p: 70), and four taps of them are point
+ * sampling: aliasing, moire, noise at full amplitude.  The reference's downscale mode for that is interpolation="area"
+ * (short_side_scale / ShortSideScale / short_side_scale_with_boxes pass it to F.interpolate; transforms/functional.py:92-131,
+ * 195-231): adaptive average pooling, a box filter.  pv_area_views is pv_batch_views / pv_frame_views with that filter in place
+ * of the blend; the video is read where it lies, and no float RGB copy, interpolate pass or crop is materialised.
+ * Launch:       `frames`, a whole pv_frame_views_desc.  frames.frame_ptrs == NULL (and frame_ptrs_dev NULL, n_frame_ptrs 0):
+ *               the records are whole videos, pv_batch_views' meaning of frames.batch; otherwise pv_frame_views' meaning.
+ *               Records, items, the frame table, views, destination forms, the affine map and the item window are the wrapped
+ *               entry point's; the same pv_view_source records serve both filters: sy / sx are validated as there (their bits
+ *               against the library's own division) and NOT used by the arithmetic.  filter = PV_FILTER_AREA.
+ * Arithmetic:   per axis, for destination index d of the virtually scaled frame (d = window offset + index inside the window,
+ *               n_in = Hs or Ws, n_out = Hn or Wn), in integers with floor division:
+ *                   start = (d * n_in) / n_out;   end = ((d + 1) * n_in + n_out - 1) / n_out          (end > start always)
+ *               The value is the mean of the taps in rows [start_y, end_y) x columns [start_x, end_x): exactly the windows of
+ *               torch.nn.functional.interpolate(size=(Hn, Wn), mode="area").  Windows of neighbouring outputs overlap by one
+ *               row or column when the ratio is no integer; upscaling gives windows of one or two pixels.  The order is pinned,
+ *               so that every instantiation gives the same bits: per channel
+ *                   1. for each source column of the window, the fp32 sum of its taps over the window's rows, ascending;
+ *                   2. the fp32 sum of those column sums over the window's columns, ascending;
+ *                   3. ONE IEEE division by (float)((end_y - start_y) * (end_x - start_x));
+ *                   4. out = fmaf(v, ch_scale[c], ch_shift[c]), rounded once to dst_dtype.
+ *               For uint8 RGB / planar sources the sums are exact integers.  PV_SRC_YUV420 (8- and 16-bit): pv_yuv_views' rule
+ *               stands -- every tap is converted and clamped first, rgb[c] = clamp(M (Y,U,V,1), 0, 255) with the chroma of
+ *               pixel (y, x) the sample at (y >> 1, x >> 1), THEN averaged; the clamp makes averaging Y, U and V separately a
+ *               different function.
+ *               Item i holds the same bits whatever else shares its launch (strip height, column tile and LDS pitch are sized
+ *               from the launch's widest record and enter no value), and the same bits for a frame list as for the stacked
+ *               video.  Where Hn == Hs and Wn == Ws every window is one pixel and item i holds, bit for bit, what pv_batch_views
+ *               writes (whose weights are then 1 and 0).
+ * Index limit:  Hs * Hn <= 2^24 and Ws * Wn <= 2^24 for every record an item names.  Beyond it torch's own index arithmetic is
+ *               done in float and is no longer the integer one above, so no reference would exist.
+ * Source forms: the upright forms of pv_batch_views / pv_frame_views: PV_SRC_NTHWC PV_U8, PV_SRC_NCTHW PV_U8 / PV_F32,
+ *               PV_SRC_YUV420 PV_U8 / PV_U16 with either c_step, pitched surfaces, coded heights, any byte base as there.
+ * PV_ERR_INVALID: a null descriptor; filter outside {PV_FILTER_AREA}; a non-zero reserved; a pointer table only half given, or
+ * n_frame_ptrs != 0 without a table; whatever the wrapped entry point rejects.  PV_ERR_UNSUPPORTED: a record named by an item
+ * with orient != 0; the index limit; the dtype / layout matrix of the wrapped entry point; a window so large that the source
+ * rectangle under ONE output row x 8 output columns, in the source dtype, exceeds the kernels' LDS limit of 64 KiB (some 2000
+ * taps per channel plane: a ratio beyond 50 for uint8 sources and 25 for fp32 ones; the frame WIDTH is no limit, a workgroup
+ * owns a tile of columns).  Validation precedes every HIP call.
+ * Out of scope: oriented records (orient != 0), the PQ / HLG tap map of pv_hdr_views, pv_region_views' rectangles (tubes are
+ * resized by about 1-2x), the one-source entry points, bicubic and nearest.
+ */
+enum { PV_FILTER_AREA = 1 };
+typedef struct pv_area_views_desc {
+  pv_frame_views_desc frames;         /* frame_ptrs == NULL: whole videos (pv_batch_views' meaning); else pv_frame_views' */
+  int32_t filter;                     /* PV_FILTER_AREA                                                                   */
+  int32_t reserved[3];                /* 0                                                                                */
+} pv_area_views_desc;                 /* sizeof(pv_frame_views_desc) + 16 */
+int pv_area_views(const pv_area_views_desc* d, pv_stream_t stream);
+
 /* ---- key-frame detection: the boxes of a forward mapped into its views, on the device ---------------------------------
  * A detection forward built by pv_batch_views holds one clip per key frame, and every key frame has person boxes given in the
  * pixels of ITS source frame.  pv_box_views fills the RoI head's persistent [capacity][5] fp32 box buffer (what pv_roi_align

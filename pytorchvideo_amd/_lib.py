@@ -113,6 +113,10 @@ HdrViewsDesc = _struct("HdrViewsDesc", [("frames", FrameViewsDesc), ("tone", _p)
 # pv_region_views: a whole FrameViewsDesc as in HdrViewsDesc, and a rectangle of the frame per (table row, destination frame)
 ViewRegion = _struct("ViewRegion", _ints("top", "left", "h", "w") + [("sy", _f32), ("sx", _f32), ("reserved", _i32 * 2)])
 RegionViewsDesc = _struct("RegionViewsDesc", [("frames", FrameViewsDesc), ("regions", _p), ("regions_dev", _p)])
+# pv_area_views: a whole FrameViewsDesc as in HdrViewsDesc, and the filter that replaces the four-tap blend (the box filter of
+# F.interpolate(mode="area"))
+PV_FILTER_AREA = 1
+AreaViewsDesc = _struct("AreaViewsDesc", [("frames", FrameViewsDesc), ("filter", _i32), ("reserved", _i32 * 3)])
 BoxViewsDesc = _struct("BoxViewsDesc", [
     ("boxes", _p), ("box_item", _p), ("sources_dev", _p), ("items_dev", _p), ("dst", _p), ("dst_box", _p)]
     + _ints("n_boxes", "n_seq", "n_sources", "n_views", "box0", "n_launch", "item0", "n_items", "Ho", "Wo", "capacity",
@@ -201,6 +205,7 @@ _SYMBOLS = [
     ("pv_frame_views", C.c_int, [C.POINTER(FrameViewsDesc), _p]),
     ("pv_hdr_views", C.c_int, [C.POINTER(HdrViewsDesc), _p]),
     ("pv_region_views", C.c_int, [C.POINTER(RegionViewsDesc), _p]),
+    ("pv_area_views", C.c_int, [C.POINTER(AreaViewsDesc), _p]),
     ("pv_box_views", C.c_int, [C.POINTER(BoxViewsDesc), _p]),
     ("pv_layernorm", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_affine_rows", C.c_int, [C.POINTER(RowsDesc), _p]),

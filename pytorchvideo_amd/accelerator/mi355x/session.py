@@ -437,6 +437,11 @@ class Session:
         pv_region_views; whole videos or frame lists); the destination goes into the BatchViewsDesc it embeds."""
         self._views_into(r.frames.batch, r.frames.batch.C, ref, planar, "pv_region_views", outer=r)
 
+    def area_views(self, a, ref, planar=None):
+        """`frame_views` for an AreaViewsDesc (the box filter of interpolation="area" in place of the four-tap blend:
+        pv_area_views; whole videos or frame lists); the destination goes into the BatchViewsDesc it embeds."""
+        self._views_into(a.frames.batch, a.frames.batch.C, ref, planar, "pv_area_views", outer=a)
+
     def box_views(self, d, ptr):
         """Fill a detection head's box buffer `ptr` (`alloc_boxes`) by pv_box_views: `d` is a BoxViewsDesc whose boxes, item
         window, records and capacity the caller (transforms.DevicePacker.fill_boxes) has set; the destination is filled in

@@ -1,0 +1,477 @@
+// pv_area_views: pv_batch_views / pv_frame_views with a BOX FILTER in place of the four-tap blend (include/pv_mi355x.h, "box-
+// filtered downscale"): every output pixel is the mean of all the source pixels under its window, the windows being those of
+// F.interpolate(mode="area").  A 1080p decoder surface scaled to a short side of 256 then reaches the network averaged, not
+// point-sampled, and no float RGB copy of the video, no interpolate pass and no crop stand between the decoder and the ingest.
+//
+// A box filter reads every source row under a strip, not two per output row, so the staged strips of pv_rs.h cannot carry it.
+// The body here is a staged TILE (the shape of rs_tile_rgb / rs_tile_yuv, without the orientation map): one workgroup owns R
+// output rows x X output columns (blockIdx.x = strip * tiles_x + column tile) of one frame t of one item zi.
+//   1. stage: the windows of the tile's outputs cover ONE rectangle of the source, rows [start_y(first), end_y(last)) x columns
+//      likewise.  Its rows are copied to LDS in the source dtype exactly as the tiles of pv_rs.h copy theirs: the aligned 16-byte
+//      granules that cover each row's span, a batch of four loads per thread, the LDS image of a row keeping the span's
+//      `addr & 15`.  YUV stages the chroma rectangle [ys0 >> 1, (ys1 - 1) >> 1] x [xs0 >> 1, (xs1 - 1) >> 1] behind the luma one.
+//      Tiling in x keeps the staged bytes independent of the frame width (a no-crop view of a 2160p frame is 3840 columns).
+//   2. barrier; sum: a thread owns ONE output pixel, so all 256 threads work whatever the destination form.  It walks its
+//      window's columns in ascending order and, per column, the window's rows in ascending order (the pinned order: the column
+//      sum first, then the sum of the column sums), divides once, applies the affine map and leaves the fp32 result in a second
+//      LDS image [c][R][X].  A column sum is needed by the one or two outputs of its row whose windows hold the column, so it
+//      is formed where it is used and never shared.  YUV converts and clamps every tap with yuv_tap2 -- two rows of one
+//      column per call, the packed-fp32 pair -- before it is added.
+//   3. barrier; store: a thread takes G x-adjacent results of one row from that image and hands them to rs_store_group, so the
+//      three destination forms, their 16-byte stores and their edge handling are the strips' own.  X is a multiple of 8, so a
+//      group starts where a strip's group starts.
+// The host sizes R, X, the staged rows and the LDS pitch(es) from the widest footprint over the records x views the launch's
+// items name (ar_size), with the very calls the kernel makes; none of them enters a value.  A workgroup whose footprint
+// exceeds them -- a device copy that is not the validated one -- stages nothing and writes nothing.
+// One item loader serves whole videos and frame lists (`frames` is workgroup-uniform, as in pv_hdr.hip / pv_region.hip).
+// 3 RGB / planar forms and 2 chroma arrangements x 2 sample widths, x 5 destination forms: 35 kernels.
+#include "pv_frames.h"
+
+namespace {
+
+// What stays per launch: filled by ar_size.
+struct ArLaunch {
+  int32_t R, X;             // output rows x columns per workgroup; X a multiple of 8
+  int32_t tiles_x;          // column tiles per window row
+  int32_t rows, pitch;      // staged source rows, LDS bytes per staged (row, plane) -- YUV: luma
+  int32_t rows_c, pitch_c, c_base;   // YUV: staged chroma rows, LDS bytes per chroma (row, plane), LDS offset of the chroma image
+  int32_t out_base;         // LDS offset of the fp32 results [c][R][X]; a multiple of 16
+};
+
+constexpr int kArTiles[][2] = {{8, 64}, {8, 32}, {4, 32}, {4, 16}, {2, 16}, {2, 8}, {1, 8}};   // R x X, largest first
+
+// The tile of this workgroup and the source rectangle under it.
+struct ArTile {
+  int row0, col0, nrows, ncols;
+  int ys0, ys1, xs0, xs1;   // source rows [ys0, ys1) x columns [xs0, xs1)
+};
+__device__ __forceinline__ ArTile ar_tile(const ArLaunch& g, int Ho, int Wo, int yoff, int xoff, int Hs, int Ws, int Hn, int Wn) {
+  ArTile a;
+  const int strip = blockIdx.x / g.tiles_x, tile_x = blockIdx.x - strip * g.tiles_x;
+  a.row0 = strip * g.R, a.col0 = tile_x * g.X;
+  a.nrows = min(g.R, Ho - a.row0), a.ncols = min(g.X, Wo - a.col0);
+  int unused;
+  rs_area_win(yoff + a.row0, Hs, Hn, a.ys0, unused);
+  rs_area_win(yoff + a.row0 + a.nrows - 1, Hs, Hn, unused, a.ys1);
+  rs_area_win(xoff + a.col0, Ws, Wn, a.xs0, unused);
+  rs_area_win(xoff + a.col0 + a.ncols - 1, Ws, Wn, unused, a.xs1);
+  return a;
+}
+
+// Step 3: the results of the tile, G x-adjacent pixels of one row per thread, to the destination.
+template <int FORM, typename D>
+__device__ __forceinline__ void ar_store(const float* res, const ArLaunch& g, const ArTile& a, const RsDst& d, int C, int zi, int t) {
+  constexpr int G = RsGroup<FORM, D>::G;
+  const int gpr = (a.ncols + G - 1) / G;           // groups per tile row
+  const int items = a.nrows * gpr;
+  for (int it = threadIdx.x; it < items; it += kRsThreads) {
+    const int r = it / gpr, gx = it - r * gpr;
+    float out[4][G];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int j = 0; j < G; ++j) out[c][j] = c < C ? res[(c * g.R + r) * g.X + gx * G + j] : 0.f;   // past ncols: not stored
+    const int x0 = a.col0 + gx * G;
+    rs_store_group<FORM, D, G>(d.dst, out, C, d.T, d.Ho, d.Wo, d.c_p, d.ld, d.bs, zi, t, a.row0 + r, x0, min(G, d.Wo - x0));
+  }
+}
+
+// S / INTER / FORM / D: as rs_strip_rgb.  Hn x Wn: the scaled frame the windows are counted in.
+template <typename S, bool INTER, int FORM, typename D>
+__device__ __forceinline__ void ar_tile_rgb(unsigned char* lds, const ArLaunch& g, const RsRgbSrc& s, int Hn, int Wn, const RsDst& d,
+                                            int zi, int t) {
+  constexpr int XB = INTER ? 3 : (int)sizeof(S);   // bytes from one source column to the next
+  const int tid = threadIdx.x;
+  const ArTile a = ar_tile(g, d.Ho, d.Wo, s.yoff, s.xoff, s.Hs, s.Ws, Hn, Wn);
+  if (a.nrows <= 0 || a.ncols <= 0) return;
+  const int planes = INTER ? 1 : d.C;
+  const int pitch = g.pitch;
+  const int nslots = a.ys1 - a.ys0;
+  const int span_bytes = (a.xs1 - a.xs0) * XB;
+  if (nslots > g.rows || span_bytes + 15 > pitch) return;
+
+  // byte address of column xs0 of source row y of plane `pl` of the selected frame
+  const long row_bytes = (long)s.Ws * XB;
+  const long frame_bytes = (long)s.Hs * row_bytes;
+  const long first = (s.clip_frame0 + s.ts) * frame_bytes + (long)a.xs0 * XB;
+  const long plane_bytes = INTER ? 0 : (long)s.N * frame_bytes;
+  auto row_addr = [&](int y, int pl) -> uintptr_t { return s.src + first + (long)pl * plane_bytes + (long)y * row_bytes; };
+
+  // ---- stage -------------------------------------------------------------------------------------------------
+  const int cpr = pitch >> 4;                      // 16-byte chunks per staged row
+  const int total = nslots * planes * cpr;
+  for (int base = tid; base < total; base += kRsThreads * 4) {
+    u32x4 val[4];
+    int off[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = base + u * kRsThreads;
+      off[u] = -1;
+      if (idx < total) {
+        const int sp = idx / cpr, ch = idx - sp * cpr;
+        const int slot = sp / planes, pl = sp - slot * planes;
+        const uintptr_t ad = row_addr(a.ys0 + slot, pl);
+        if (ch * 16 < (int)(ad & 15) + span_bytes) {
+          val[u] = *reinterpret_cast<const u32x4*>((ad & ~(uintptr_t)15) + (uintptr_t)ch * 16);
+          off[u] = sp * pitch + ch * 16;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (off[u] >= 0) *reinterpret_cast<u32x4*>(lds + off[u]) = val[u];
+  }
+  __syncthreads();
+
+  // ---- sum ---------------------------------------------------------------------------------------------------
+  float sc[4], sh[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    sc[c] = (d.ch_scale && c < d.C) ? d.ch_scale[c] : 1.f;
+    sh[c] = (d.ch_scale && d.ch_shift && c < d.C) ? d.ch_shift[c] : 0.f;
+  }
+  // the low address bits of a staged row: 32-bit arithmetic keeps `addr & 15`
+  const unsigned rb32 = (unsigned)row_bytes, pb32 = (unsigned)plane_bytes, a32 = (unsigned)(s.src + first);
+  float* res = reinterpret_cast<float*>(lds + g.out_base);
+  const int npix = a.nrows * a.ncols;
+  for (int p = tid; p < npix; p += kRsThreads) {
+    const int r = p / a.ncols, x = p - r * a.ncols;
+    int wy0, wy1, wx0, wx1;
+    rs_area_win(s.yoff + a.row0 + r, s.Hs, Hn, wy0, wy1);
+    rs_area_win(s.xoff + a.col0 + x, s.Ws, Wn, wx0, wx1);
+    float tot[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int cx = wx0; cx < wx1; ++cx) {
+      float cs[4] = {0.f, 0.f, 0.f, 0.f};          // the column sums, rows ascending
+      const int ox = (cx - a.xs0) * XB;
+      for (int cy = wy0; cy < wy1; ++cy) {
+        const int slot = cy - a.ys0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if (c < d.C) {
+            const int pl = INTER ? 0 : c;
+            const int lo = (int)((a32 + (unsigned)pl * pb32 + (unsigned)cy * rb32) & 15u);
+            cs[c] += rs_tap<S>(lds, (slot * planes + pl) * pitch + lo + ox + (INTER ? c : 0));
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) tot[c] += cs[c];  // columns ascending
+    }
+    const float cnt = (float)((wy1 - wy0) * (wx1 - wx0));
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < d.C) res[(c * g.R + r) * g.X + x] = fmaf(tot[c] / cnt, sc[c], sh[c]);
+  }
+  __syncthreads();
+
+  ar_store<FORM, D>(res, g, a, d, d.C, zi, t);
+}
+
+// CSTEP / FORM / D / SMP: as rs_strip_yuv.
+template <int CSTEP, int FORM, typename D, typename SMP>
+__device__ __forceinline__ void ar_tile_yuv(unsigned char* lds, const ArLaunch& g, const RsYuvSrc& s, int Hn, int Wn, const RsDst& d,
+                                            const float* yuv2rgb, int zi, int t) {
+  constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
+  constexpr int SB = (int)sizeof(SMP);             // bytes from one luma column to the next
+  constexpr int CB = CSTEP * SB;                   // bytes from one chroma column to the next
+  const int tid = threadIdx.x;
+  const ArTile a = ar_tile(g, d.Ho, d.Wo, s.yoff, s.xoff, s.Hs, s.Ws, Hn, Wn);
+  if (a.nrows <= 0 || a.ncols <= 0) return;
+  const int pitch_y = g.pitch, pitch_c = g.pitch_c, c_base = g.c_base;
+  const int cr0 = a.ys0 >> 1, cc0 = a.xs0 >> 1;
+  const int nslots = a.ys1 - a.ys0, ncslots = ((a.ys1 - 1) >> 1) - cr0 + 1;
+  const int span_y = (a.xs1 - a.xs0) * SB;
+  const int span_c = (((a.xs1 - 1) >> 1) - cc0 + 1) * CB;
+  if (nslots > g.rows || ncslots > g.rows_c || span_y + 15 > pitch_y || span_c + 15 > pitch_c) return;
+
+  const uintptr_t frame = s.src + s.frame_off;
+  auto y_addr = [&](int y) -> uintptr_t { return frame + (long)y * s.y_pitch + a.xs0 * SB; };
+  auto c_addr = [&](int cy, int pl) -> uintptr_t {
+    return frame + (pl == 0 ? s.c_off_a : s.c_off_b) + (long)cy * s.c_pitch + (long)cc0 * CB;
+  };
+
+  // ---- stage -------------------------------------------------------------------------------------------------
+  const int cpr_y = pitch_y >> 4, cpr_c = pitch_c >> 4;   // 16-byte chunks per staged row
+  const int total_y = nslots * cpr_y;
+  const int total = total_y + ncslots * CP * cpr_c;
+  for (int base = tid; base < total; base += kRsThreads * 4) {
+    u32x4 val[4];
+    int off[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = base + u * kRsThreads;
+      off[u] = -1;
+      if (idx < total) {
+        const bool luma = idx < total_y;
+        const int j = luma ? idx : idx - total_y;
+        const int cpr = luma ? cpr_y : cpr_c;
+        const int sp = j / cpr, ch = j - sp * cpr;             // luma: sp = slot; chroma: sp = slot * CP + plane
+        const int slot = luma ? sp : sp / CP, pl = luma ? 0 : sp - slot * CP;
+        const uintptr_t ad = luma ? y_addr(a.ys0 + slot) : c_addr(cr0 + slot, pl);
+        if (ch * 16 < (int)(ad & 15) + (luma ? span_y : span_c)) {
+          val[u] = *reinterpret_cast<const u32x4*>((ad & ~(uintptr_t)15) + (uintptr_t)ch * 16);
+          off[u] = (luma ? sp * pitch_y : c_base + sp * pitch_c) + ch * 16;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (off[u] >= 0) *reinterpret_cast<u32x4*>(lds + off[u]) = val[u];
+  }
+  __syncthreads();
+
+  // ---- sum ---------------------------------------------------------------------------------------------------
+  float m[12], sc[3], sh[3];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) m[i] = yuv2rgb[i];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    sc[c] = d.ch_scale ? d.ch_scale[c] : 1.f;
+    sh[c] = (d.ch_scale && d.ch_shift) ? d.ch_shift[c] : 0.f;
+  }
+  // the low address bits of a staged row: 32-bit arithmetic keeps `addr & 15`
+  const unsigned ya32 = (unsigned)(frame + a.xs0 * SB), yp32 = (unsigned)s.y_pitch, cp32 = (unsigned)s.c_pitch;
+  const unsigned ua32 = (unsigned)(frame + s.c_off_a + (long)cc0 * CB), va32 = (unsigned)(frame + s.c_off_b + (long)cc0 * CB);
+  // LDS byte offsets of the Y, U and V samples of source pixel (y, column offsets oyx / ocx)
+  auto tap = [&](int y, int oyx, int ocx, int& oy, int& ou, int& ov) {
+    oy = (y - a.ys0) * pitch_y + (int)((ya32 + (unsigned)y * yp32) & 15u) + oyx;
+    const int cr = y >> 1, crow = c_base + (cr - cr0) * CP * pitch_c;
+    ou = crow + (int)((ua32 + (unsigned)cr * cp32) & 15u) + s.u_byte + ocx;
+    ov = crow + (CP - 1) * pitch_c + (int)((va32 + (unsigned)cr * cp32) & 15u) + s.v_byte + ocx;
+  };
+  float* res = reinterpret_cast<float*>(lds + g.out_base);
+  const int npix = a.nrows * a.ncols;
+  for (int p = tid; p < npix; p += kRsThreads) {
+    const int r = p / a.ncols, x = p - r * a.ncols;
+    int wy0, wy1, wx0, wx1;
+    rs_area_win(s.yoff + a.row0 + r, s.Hs, Hn, wy0, wy1);
+    rs_area_win(s.xoff + a.col0 + x, s.Ws, Wn, wx0, wx1);
+    float tot[3] = {0.f, 0.f, 0.f};
+    for (int cx = wx0; cx < wx1; ++cx) {
+      float cs[3] = {0.f, 0.f, 0.f};               // the column sums of the converted, clamped taps, rows ascending
+      const int oyx = (cx - a.xs0) * SB, ocx = ((cx >> 1) - cc0) * CB;
+      for (int cy = wy0; cy < wy1; cy += 2) {      // two rows per call: yuv_tap2's packed pair
+        const bool two = cy + 1 < wy1;
+        int y0, u0, v0, y1, u1, v1;
+        tap(cy, oyx, ocx, y0, u0, v0);
+        tap(two ? cy + 1 : cy, oyx, ocx, y1, u1, v1);
+        f32x2 rgb[3];
+        yuv_tap2<SMP>(m, lds, y0, u0, v0, y1, u1, v1, rgb);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          cs[c] += rgb[c][0];
+          if (two) cs[c] += rgb[c][1];
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) tot[c] += cs[c];  // columns ascending
+    }
+    const float cnt = (float)((wy1 - wy0) * (wx1 - wx0));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) res[(c * g.R + r) * g.X + x] = fmaf(tot[c] / cnt, sc[c], sh[c]);
+  }
+  __syncthreads();
+
+  ar_store<FORM, D>(res, g, a, d, 3, zi, t);
+}
+
+// The item of this workgroup, clamped into range before anything is addressed through it (pv_hdr.hip's loader): its record
+// and view, and the selected frame as the video with a frame index (whole videos) or as the frame itself (frame lists).
+struct ArItem {
+  const pv_view_source* __restrict__ S;
+  int view, ts;         // frame lists: ts = 0
+  uintptr_t src;        // the video, or -- frame lists -- the selected frame
+};
+__device__ __forceinline__ ArItem ar_item(const pv_batch_views_desc& d, int frames, int zi, int t) {
+  const pv_view_item* __restrict__ it = d.items_dev + zi;
+  ArItem r;
+  r.S = d.sources_dev + min(max(it->source, 0), d.n_sources - 1);
+  r.view = min(max(it->view, 0), d.n_views - 1);
+  const int row = min(max(it->row, 0), d.n_rows - 1);
+  const int ts = min(max(d.t_index[(long)row * d.t_stride + t], 0), r.S->N - 1);
+  if (frames) {   // read as constant memory: one scalar load (pv_frames.h)
+    typedef const uint64_t __attribute__((address_space(4))) * table_ptr;
+    r.src = (uintptr_t) reinterpret_cast<table_ptr>(reinterpret_cast<uintptr_t>(r.S->src))[ts];
+    r.ts = 0;
+  } else {
+    r.src = reinterpret_cast<uintptr_t>(r.S->src);
+    r.ts = ts;
+  }
+  return r;
+}
+
+// S / INTER / FORM / D: as rs_strip_rgb.
+template <typename S, bool INTER, int FORM, typename D>
+__global__ __launch_bounds__(kRsThreads) void area_views_kernel(const pv_batch_views_desc d, const ArLaunch g, const int frames) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ar_lds[];
+  const int t = blockIdx.y;
+  const int zi = blockIdx.z;                       // destination item of this launch
+  const ArItem item = ar_item(d, frames, zi, t);
+  const pv_view_source* __restrict__ V = item.S;
+  RsRgbSrc s;
+  s.src = item.src;
+  s.Hs = V->Hs, s.Ws = V->Ws, s.N = frames ? 1 : V->N;   // a frame of a list is dense [C, Hs, Ws]: the plane stride of ONE frame
+  s.sy = V->sy, s.sx = V->sx;                      // not used: the windows are integers
+  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
+  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
+  s.ts = item.ts;
+  s.clip_frame0 = 0;
+  ar_tile_rgb<S, INTER, FORM, D>(ar_lds, g, s, V->Hn, V->Wn, rs_dst(d, d.C), zi, t);
+}
+
+// CSTEP / SMP / FORM / D: as rs_strip_yuv.
+template <int CSTEP, typename SMP, int FORM, typename D>
+__global__ __launch_bounds__(kRsThreads) void area_yuv_kernel(const pv_batch_views_desc d, const ArLaunch g, const int frames) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ay_lds[];
+  const int t = blockIdx.y;
+  const int zi = blockIdx.z;                       // destination item of this launch
+  const ArItem item = ar_item(d, frames, zi, t);
+  const pv_view_source* __restrict__ V = item.S;
+  RsYuvSrc s;
+  s.src = item.src;
+  s.frame_off = (long)item.ts * V->frame_stride;
+  s.Hs = V->Hs, s.Ws = V->Ws;
+  s.sy = V->sy, s.sx = V->sx;                      // not used: the windows are integers
+  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
+  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
+  s.y_pitch = V->y_pitch, s.c_pitch = V->c_pitch;
+  rs_chroma_planes(CSTEP == 2, V->u_offset, V->v_offset, s);
+  ar_tile_yuv<CSTEP, FORM, D, SMP>(ay_lds, g, s, V->Hn, V->Wn, rs_dst(d, 3), d.yuv2rgb, zi, t);
+}
+
+// RS_DISPATCH over the tile grid with the further kernel argument; expects d, g, lds, stream and fr in scope.
+#define AR_DISPATCH(KERNEL, ...)                                                                                         \
+  do {                                                                                                                   \
+    const dim3 grid((unsigned)(pv_ceil_div(d.Ho, g.R) * g.tiles_x), (unsigned)d.T, (unsigned)d.n_items), block(kRsThreads); \
+    hipStream_t s = static_cast<hipStream_t>(stream);                                                                    \
+    if (d.dst_layout == PV_DST_NCTHW) {                                                                                  \
+      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, bf16_t>), grid, block, lds, s, d, g, fr);    \
+      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, float>), grid, block, lds, s, d, g, fr);                            \
+    } else if (d.c_p == 4) {                                                                                             \
+      PV_LAUNCH((KERNEL<__VA_ARGS__, RS_C4, bf16_t>), grid, block, lds, s, d, g, fr);                                    \
+    } else {                                                                                                             \
+      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, bf16_t>), grid, block, lds, s, d, g, fr);        \
+      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, float>), grid, block, lds, s, d, g, fr);                                \
+    }                                                                                                                    \
+  } while (0)
+
+// Folds the widest footprint of an R x X tile of record v over its views into n: source rows, source columns, chroma rows,
+// chroma columns.  Rows and columns are independent, so the bands of strips and of column tiles are walked separately, with
+// the very calls the kernel makes (ar_tile).
+inline void ar_footprint(const pv_view_source& v, int n_views, int Ho, int Wo, int R, int X, int (&n)[4]) {
+  auto fold = [&](int lo, int end, int at) {       // source interval [lo, end) of rows (at = 0) / of columns (at = 1)
+    const int a = end - lo, c = ((end - 1) >> 1) - (lo >> 1) + 1;
+    n[at] = a > n[at] ? a : n[at];
+    n[at + 2] = c > n[at + 2] ? c : n[at + 2];
+  };
+  for (int view = 0; view < n_views; ++view) {
+    int lo, end, unused;
+    for (int row0 = 0; row0 < Ho; row0 += R) {
+      rs_area_win(v.y_off[view] + row0, v.Hs, v.Hn, lo, unused);
+      rs_area_win(v.y_off[view] + row0 + (R < Ho - row0 ? R : Ho - row0) - 1, v.Hs, v.Hn, unused, end);
+      fold(lo, end, 0);
+    }
+    for (int col0 = 0; col0 < Wo; col0 += X) {
+      rs_area_win(v.x_off[view] + col0, v.Ws, v.Wn, lo, unused);
+      rs_area_win(v.x_off[view] + col0 + (X < Wo - col0 ? X : Wo - col0) - 1, v.Ws, v.Wn, unused, end);
+      fold(lo, end, 1);
+    }
+  }
+}
+
+// R x X, the staged rows and the LDS pitch(es) of a launch over `records` (the records the launch's items name): the largest
+// tile of kArTiles whose widest footprint, with the results behind it, fits the staging budget of the strips, else the
+// smallest one if it fits the LDS limit.  That last refusal needs a window of some 2000 taps per channel plane (a ratio
+// beyond 50 for uint8 sources, beyond 25 for fp32 ones: a 2160p frame scaled to a short side of 80).
+inline int ar_size(const pv_batch_views_desc& d, const std::vector<const pv_view_source*>& records, ArLaunch& g, size_t& lds) {
+  const bool yuv = d.src_layout == PV_SRC_YUV420, inter = d.src_layout == PV_SRC_NTHWC;
+  const int sb = d.src_dtype == PV_U16 ? 2 : 1;
+  constexpr size_t n_tiles = sizeof(kArTiles) / sizeof(kArTiles[0]);
+  for (size_t k = 0; k < n_tiles; ++k) {
+    const int R = kArTiles[k][0], X = kArTiles[k][1];
+    int n[4] = {0, 0, 0, 0};
+    for (const pv_view_source* v : records) ar_footprint(*v, d.n_views, d.Ho, d.Wo, R, X, n);
+    g = {};
+    g.R = R, g.X = X, g.tiles_x = (int32_t)pv_ceil_div(d.Wo, X);
+    g.rows = n[0], g.rows_c = n[2];
+    long bytes;
+    if (yuv) {
+      rs_yuv_pitches(n[1], n[3], d.c_step, sb, g.pitch, g.pitch_c);
+      g.c_base = g.rows * g.pitch;
+      bytes = (long)g.c_base + (long)g.rows_c * (d.c_step == 2 ? 1 : 2) * g.pitch_c;
+    } else {
+      g.pitch = pv_round_up(n[1] * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
+      bytes = (long)g.rows * (inter ? 1 : d.C) * g.pitch;
+    }
+    if (bytes > kRsLdsMax) {                       // before it is narrowed to 32 bits
+      if (k + 1 == n_tiles) return PV_ERR_UNSUPPORTED;
+      continue;
+    }
+    g.out_base = (int32_t)bytes;                   // pitches are multiples of 16
+    bytes += (long)d.C * R * X * (long)sizeof(float);
+    lds = (size_t)bytes;
+    if (bytes <= kRsLdsBudget) return PV_OK;
+    if (k + 1 == n_tiles) return bytes <= kRsLdsMax ? PV_OK : PV_ERR_UNSUPPORTED;
+  }
+  return PV_ERR_UNSUPPORTED;
+}
+
+// The descriptor as the wrapped entry point checks it (rs_check_item_desc), then every item: its range and its record
+// (rs_check_record with the entry point's check of `src`) -- all of PV_ERR_INVALID first --, then what this entry point does
+// not carry: oriented records and products beyond the index limit.  The launch is sized from the records the items name.
+template <typename CheckSrc>
+int ar_run(const pv_batch_views_desc& d, bool frames, const CheckSrc& check_src, pv_stream_t stream) {
+  if (int e = rs_check_item_desc(d)) return e;
+  const bool yuv = d.src_layout == PV_SRC_YUV420;
+  std::vector<const pv_view_source*> records;      // the records the items name, a video-major run once
+  for (int i = 0; i < d.n_items; ++i) {
+    const pv_view_item& it = d.items[i];
+    if (it.source < 0 || it.source >= d.n_sources || it.row < 0 || it.row >= d.n_rows || it.view < 0 || it.view >= d.n_views)
+      return PV_ERR_INVALID;
+    const pv_view_source& v = d.sources[it.source];
+    if (i > 0 && it.source == d.items[i - 1].source) continue;   // a video-major sequence names the record just checked
+    if (int e = rs_check_record(d, v, yuv, check_src)) return e;
+    records.push_back(&v);
+  }
+  constexpr long kIndexLimit = 1L << 24;
+  for (const pv_view_source* v : records) {
+    if (v->orient != 0) return PV_ERR_UNSUPPORTED;
+    if ((long)v->Hs * v->Hn > kIndexLimit || (long)v->Ws * v->Wn > kIndexLimit) return PV_ERR_UNSUPPORTED;
+  }
+  ArLaunch g = {};
+  size_t lds = 0;
+  if (int e = ar_size(d, records, g, lds)) return e;
+  const int fr = frames ? 1 : 0;
+  if (yuv && d.src_dtype == PV_U16) {
+    if (d.c_step == 2) AR_DISPATCH(area_yuv_kernel, 2, unsigned short);
+    else AR_DISPATCH(area_yuv_kernel, 1, unsigned short);
+  } else if (yuv) {
+    if (d.c_step == 2) AR_DISPATCH(area_yuv_kernel, 2, unsigned char);
+    else AR_DISPATCH(area_yuv_kernel, 1, unsigned char);
+  } else if (d.src_layout == PV_SRC_NTHWC) {
+    AR_DISPATCH(area_views_kernel, unsigned char, true);
+  } else if (d.src_dtype == PV_U8) {
+    AR_DISPATCH(area_views_kernel, unsigned char, false);
+  } else {
+    AR_DISPATCH(area_views_kernel, float, false);
+  }
+  PV_LAUNCH_CHECK();
+  return PV_OK;
+}
+
+}  // namespace
+
+extern "C" int pv_area_views(const pv_area_views_desc* ap, pv_stream_t stream) {
+  if (!ap) return PV_ERR_INVALID;
+  const pv_frame_views_desc& f = ap->frames;
+  if (ap->filter != PV_FILTER_AREA) return PV_ERR_INVALID;
+  if (ap->reserved[0] != 0 || ap->reserved[1] != 0 || ap->reserved[2] != 0) return PV_ERR_INVALID;
+  if ((f.frame_ptrs == nullptr) != (f.frame_ptrs_dev == nullptr)) return PV_ERR_INVALID;   // a table only half given
+  const bool frames = f.frame_ptrs != nullptr;
+  if (!frames && f.n_frame_ptrs != 0) return PV_ERR_INVALID;
+  if (frames) {
+    if (int e = fv_check_table(f)) return e;
+    return ar_run(f.batch, true, fv_check_src(f), stream);
+  }
+  return ar_run(f.batch, false, rs_check_video_src(f.batch.src_dtype), stream);
+}

@@ -9,6 +9,9 @@
 //                                                                       tap map: its own strip and tile kernel wrappers
 //   pv_region.hip     pv_region_views (an eighth)                      a rectangle of the frame per destination frame, resized to
 //                                                                       the window: its own strip kernel wrappers
+//   pv_area.hip       pv_area_views (a ninth)                          pv_batch_views / pv_frame_views with a box filter (the windows of
+//                                                                       interpolate(mode="area")) in place of the blend: a staged-tile body
+//                                                                       of its own (a window's rows are not two), the shared pieces from here
 // What they compute with is here, once: the pinned source coordinate, the destination forms with their stores, the taps and
 // blends, the two staged-strip bodies (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather) that the nine kernel templates
 // wrap (resample_crop_kernel; yuv_views_kernel, yuv16_views_kernel; batch_views_kernel, batch_yuv_kernel,
@@ -72,6 +75,18 @@ __host__ __device__ __forceinline__ void rs_coord(float s, int d, int n_in, int&
   i0 = i0 < n_in - 1 ? i0 : n_in - 1;   // r < n_in - 0.5 for every d inside the scaled frame; this keeps reads in bounds regardless
   i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
   l1 = r - (float)i0;
+}
+
+// The box filter's window of destination index d (pv_area_views: the pinned integer formula, the windows of
+// F.interpolate(mode="area")): source indices [start, end).  d < n_out and n_in * n_out <= 2^24 on a validated launch, so the
+// products fit 32 bits and 0 <= start < end <= n_in; the clamps keep a device copy that is not the validated one in bounds.
+__host__ __device__ __forceinline__ void rs_area_win(int d, int n_in, int n_out, int& start, int& end) {
+  n_out = n_out > 0 ? n_out : 1;
+  start = (d * n_in) / n_out;
+  end = ((d + 1) * n_in + n_out - 1) / n_out;
+  start = start < 0 ? 0 : (start < n_in - 1 ? start : n_in - 1);
+  end = end > n_in ? n_in : end;
+  end = end > start ? end : start + 1;
 }
 
 template <typename D> struct RsVec;   // one 16-byte store of G = 16 / sizeof(D) elements

@@ -28,7 +28,8 @@ import torch
 
 from .data.clip_sampling import clip_frame_table, keyframe_frame_table, stream_windows
 from .ensemble import VideoEnsembler
-from .transforms import (DevicePacker, FrameList, batch_chunks, box_regions, temporal_indices, track_boxes_at, yuv_geometry)
+from .transforms import (DevicePacker, FrameList, _interpolation, batch_chunks, box_regions, temporal_indices, track_boxes_at,
+                         yuv_geometry)
 
 
 def _resident(video, device, is_yuv):
@@ -60,18 +61,22 @@ class VideoPredictor:
     `hdr` ("pq", "hlg" or (transfer, `transforms.tone_params(...)`), for the 10- to 16-bit YUV layouts only): the video is
     BT.2020 PQ / HLG and every tap is mapped to BT.709 SDR inside the ingest launch (`pv_hdr_views`, as `DevicePacker`); such
     a predictor walks every video as a one-video batch.
+    `interpolation="area"`: the short-side scale is the box filter of `transforms.short_side_scale(x, size, "area")` -- every
+    source pixel under an output pixel averaged, what a 720p or larger source needs -- inside the ingest launch
+    (`pv_area_views`, as `DevicePacker`); such a predictor walks every video as a one-video batch too.  A ValueError together
+    with `hdr` or a non-zero `orientation`.
     After a call `video_ensembler.counts` (and `clip_ensembler.counts`) hold the rows folded."""
 
     def __init__(self, deployed, clip_sampler, mean, std, div255, short_side, crop_size, spatial_idx=(0, 1, 2),
                  frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), coded_height=None, height=None,
-                 hdr=None):
+                 hdr=None, interpolation="bilinear"):
         if getattr(deployed, "_pv_load_boxes", None) is not None:
             raise ValueError("VideoPredictor scores videos; a detection model's boxes belong to key frames"
                              " (in any source layout, %s included)" % src_layout)
         if method not in ("sum", "max"):
             raise NotImplementedError("ensemble method %r (the reference knows 'sum' and 'max')" % method)
         self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout,
-                                   yuv, coded_height, height, hdr=hdr)
+                                   yuv, coded_height, height, hdr=hdr, interpolation=interpolation)
         self.sampler, self.method, self.src_layout = clip_sampler, method, src_layout
         self.video_ensembler = self.clip_ensembler = None
 
@@ -79,7 +84,8 @@ class VideoPredictor:
     def __call__(self, video, fps, return_clip_scores=False, orientation=0):
         p = self.packer
         device = p.sess.device
-        if isinstance(video, FrameList) or orientation or p.hdr is not None:   # HDR taps: pv_hdr_views, an item-sourced launch
+        # HDR taps and the box filter: pv_hdr_views / pv_area_views, item-sourced launches
+        if isinstance(video, FrameList) or orientation or p.hdr is not None or p.area:
             return self._call_frames(video, fps, return_clip_scores, orientation)
         if video.dim() != (3 if p.is_yuv else 4):
             raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(video.shape)))
@@ -146,18 +152,20 @@ class VideoBatchPredictor:
     be short; the frame tables of all videos are built, range-checked and uploaded once per call.
     `return_clip_scores=True` adds a list of V tensors [n_clips_j, num_classes].  `orientation` is one code
     (`transforms.orientation_code`) or one per video: videos stored turned and / or mirrored are read in place.  `hdr` as for
-    `VideoPredictor`: one transfer and one tone table for the videos of the predictor.  After a call
+    `VideoPredictor`: one transfer and one tone table for the videos of the predictor.  `interpolation="area"` as for
+    `VideoPredictor`: the box-filtered short-side scale (`pv_area_views`).  After a call
     `video_ensembler.counts` holds the views folded per video (and `clip_ensembler.counts` per clip, all videos' clips one after another)."""
 
     def __init__(self, deployed, clip_sampler, mean, std, div255, short_side, crop_size, spatial_idx=(0, 1, 2),
-                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), hdr=None):
+                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), hdr=None,
+                 interpolation="bilinear"):
         if getattr(deployed, "_pv_load_boxes", None) is not None:
             raise ValueError("VideoBatchPredictor scores videos; a detection model's boxes belong to key frames"
                              " (in any source layout, %s included)" % src_layout)
         if method not in ("sum", "max"):
             raise NotImplementedError("ensemble method %r (the reference knows 'sum' and 'max')" % method)
         self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv,
-                                   hdr=hdr)
+                                   hdr=hdr, interpolation=interpolation)
         self.sampler, self.method, self.src_layout = clip_sampler, method, src_layout
         self.video_ensembler = self.clip_ensembler = None
         self.forwards = 0                                        # forwards of the last call
@@ -244,6 +252,8 @@ class KeyframeDetector:
     code (`transforms.orientation_code`) or one per video: the video is stored turned and / or mirrored and the boxes are
     pixels of the STORED frame (a detector that ran on the decoder's surfaces); `pv_box_views` takes them into the view.
     `hdr` as for `VideoPredictor` (PQ / HLG sources in a 10- to 16-bit YUV layout, mapped to SDR per tap).
+    `interpolation="area"` as for `VideoPredictor`: the box-filtered short-side scale (`pv_area_views`); the boxes depend on
+    the geometry only and are mapped exactly as before.
 
     Frame tables, the box list and its key-frame index are uploaded once per call; per forward there are only the ingest,
     one `pv_box_views` launch and the replay.  The key frames are walked by `keyframe_chunks`.  Everything is validated
@@ -251,7 +261,8 @@ class KeyframeDetector:
     over all videos of the call, in order) of each."""
 
     def __init__(self, deployed, clip_duration, mean, std, div255, short_side, crop_size=None, spatial_idx=1,
-                 frame_ratios=None, src_layout="NTHWC", yuv=("bt709", False), coded_height=None, height=None, hdr=None):
+                 frame_ratios=None, src_layout="NTHWC", yuv=("bt709", False), coded_height=None, height=None, hdr=None,
+                 interpolation="bilinear"):
         if getattr(deployed, "_pv_load_boxes", None) is None or getattr(deployed, "_pv_box_capacity", None) is None:
             raise ValueError("KeyframeDetector scores the boxes of key frames with a detection model converted as a whole "
                              "by convert_to_deployable_form(det, (x, bboxes)); a classification model scores videos: "
@@ -261,7 +272,7 @@ class KeyframeDetector:
         if not isinstance(spatial_idx, int):
             raise ValueError("a detection model takes one view: its boxes belong to one crop")
         self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout,
-                                   yuv, coded_height, height, keyframes=True, hdr=hdr)
+                                   yuv, coded_height, height, keyframes=True, hdr=hdr, interpolation=interpolation)
         self.clip_duration, self.src_layout = clip_duration, src_layout
         self.forwards, self.chunks = 0, []
 
@@ -506,18 +517,21 @@ class StreamPredictor:
 
     `orientation` (`transforms.orientation_code`): the frames are stored turned and / or mirrored and are read in place.
     `hdr` as for `VideoPredictor`: the surfaces are PQ / HLG and every tap is mapped to SDR inside the ingest launch.
+    `interpolation="area"` as for `VideoPredictor`: the box-filtered short-side scale (`pv_area_views`).
     `deployed` is a classification form; one object scores one stream; `reset()` starts a new one.  Windows are scored
     independently: nothing is smoothed or voted over windows."""
 
     def __init__(self, deployed, clip_duration, stride, fps, mean, std, div255, short_side, crop_size, spatial_idx=(1,),
-                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), orientation=0, hdr=None):
+                 frame_ratios=None, src_layout="NTHWC", method="sum", yuv=("bt709", False), orientation=0, hdr=None,
+                 interpolation="bilinear"):
         if getattr(deployed, "_pv_load_boxes", None) is not None:
             raise ValueError("StreamPredictor scores the windows of a stream with a classification form; a detection model's "
                              "boxes belong to key frames: KeyframeDetector")
         if method not in ("sum", "max"):
             raise NotImplementedError("ensemble method %r (the reference knows 'sum' and 'max')" % method)
         self.packer = DevicePacker(deployed, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv,
-                                   hdr=hdr)
+                                   hdr=hdr, interpolation=interpolation)
+        _interpolation(interpolation, orientation, None, "StreamPredictor")   # a turned stream has no box filter: before any push
         self.method, self.src_layout, self.orientation = method, src_layout, orientation   # a stream has one orientation
         self.state = StreamState(clip_duration, stride, fps)
         self._frames = []

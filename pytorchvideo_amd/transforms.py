@@ -122,7 +122,10 @@ def short_side_scale(x: torch.Tensor, size: int, interpolation: str = "bilinear"
     if backend != "pytorch":
         raise NotImplementedError("%s backend not supported." % backend)
     _, _, h, w = x.shape
-    return torch.nn.functional.interpolate(x, size=scaled_size(h, w, size), mode=interpolation, align_corners=False)
+    # torch takes align_corners with the interpolating modes only; "area" and "nearest" have no corners to align (the
+    # reference passes False for every mode, which torch refuses for these two)
+    corners = False if interpolation in ("linear", "bilinear", "bicubic", "trilinear") else None
+    return torch.nn.functional.interpolate(x, size=scaled_size(h, w, size), mode=interpolation, align_corners=corners)
 
 
 def uniform_crop(images: torch.Tensor, size: int, spatial_idx: int) -> torch.Tensor:
@@ -900,6 +903,28 @@ def _refuse_orientation(orientation, what):
                            "fill_batch (inference.VideoPredictor and its kin take orientation= too)" % what)
 
 
+INTERPOLATIONS = ("bilinear", "area")
+
+
+def _interpolation(interpolation, orientation=None, hdr=None, what="the device ingest"):
+    """`interpolation` as every device entry point takes it: "bilinear" (the four-tap blend of `pv_resample_crop`) or "area"
+    (the box filter of `pv_area_views`: F.interpolate(mode="area"), the downscale mode for 720p and larger sources).  Returns
+    whether it is "area"; ValueError for any other string, and for "area" together with what `pv_area_views` does not carry:
+    a non-zero `orientation` (one code or one per video) and `hdr`."""
+    if interpolation not in INTERPOLATIONS:
+        raise ValueError("%s: interpolation is 'bilinear' or 'area', got %r" % (what, interpolation))
+    if interpolation != "area":
+        return False
+    codes = orientation if isinstance(orientation, (list, tuple)) else [orientation]
+    if any(_orient(0 if o is None else o) for o in codes):
+        raise ValueError("%s: interpolation='area' reads upright records only (pv_area_views): orientation is not supported "
+                         "together with it" % what)
+    if hdr is not None:
+        raise ValueError("%s: interpolation='area' has no PQ / HLG tap map (pv_area_views): hdr is not supported together "
+                         "with it" % what)
+    return True
+
+
 def _refuse_frames(video, what):
     if isinstance(video, FrameList):
         raise RuntimeError("%s takes one tensor; a FrameList goes through video_batch / fill_batch" % what)
@@ -1195,7 +1220,7 @@ def device_resized_crop(clip, regions, size, mean=None, std=None, div255=False, 
 @torch.no_grad()
 def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std=None, div255=False, num_frames=None,
                       dtype=torch.bfloat16, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None,
-                      orientation=0, hdr=None):
+                      orientation=0, hdr=None, interpolation="bilinear"):
     """uniform_crop(short_side_scale(Normalize(Div255(uniform_temporal_subsample(clip, num_frames))))) for every view of
     `spatial_idx` in one launch of `pv_resample_crop`: a planar [B * n_views, C, T, crop, crop] tensor of `dtype` (bf16 or
     fp32) on the GPU, item b * n_views + v being view v of clip b.  `clip` is [B,C,T,H,W] ("NCTHW"; uint8 or float) or the
@@ -1210,7 +1235,12 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
     before the blend, in the same launch (`pv_hdr_views`; `hdr_to_sdr` of `yuv420_to_rgb` is the host mirror).
 
     Materialised clips go through the one-source entry points, whose descriptors have no orientation: a non-zero
-    `orientation` is refused; `DevicePacker.video_batch` reads turned and mirrored videos in place."""
+    `orientation` is refused; `DevicePacker.video_batch` reads turned and mirrored videos in place.
+
+    `interpolation="area"` scales with the box filter of `short_side_scale(x, size, "area")` instead of four taps -- what a
+    720p or larger source needs: every clip is a source of its own in ONE launch of `pv_area_views`, any source layout, up to
+    three views; a ValueError together with a non-zero `orientation` or `hdr`, and for any other string."""
+    area = _interpolation(interpolation, orientation, hdr, "device_scale_crop")
     _refuse_orientation(orientation, "device_scale_crop")
     if src_layout not in ("NCTHW", "NTHWC") + _YUV_ANY:
         raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
@@ -1218,6 +1248,9 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
         raise ValueError("dtype is torch.bfloat16 or torch.float32")
     views = _views(spatial_idx)
     hdr = _hdr_of(hdr, src_layout)                             # ValueError for an 8-bit or RGB source
+    if area:
+        return _device_scale_crop_area(clip, short_side, crop_size, views, (mean, std, div255), num_frames, dtype, src_layout,
+                                       yuv, coded_height, height)
     if src_layout in _YUV_ANY:
         return _device_scale_crop_yuv(clip, short_side, crop_size, views, (mean, std, div255), num_frames, dtype, src_layout,
                                       yuv, coded_height, height, hdr)
@@ -1229,6 +1262,30 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
         index = temporal_indices(d.src_T, num_frames).to(torch.int32).to(device)
         d.T, d.t_index = num_frames, index.data_ptr()
     return _scale_crop_launch(d, "pv_resample_crop", "resample_crop", d.B, d.C, (mean, std, div255), dtype, device)
+
+
+def _device_scale_crop_area(clip, short_side, crop_size, views, affine, num_frames, dtype, src_layout, yuv, coded_height, height):
+    """`device_scale_crop(interpolation="area")`: every clip a source of its own, its frames one table row -- the item-sourced
+    launch of `DevicePacker.fill_batch`, as `device_resized_crop` builds it -- and one launch of `pv_area_views`."""
+    from . import _lib as L
+    is_yuv = src_layout in _YUV_ANY
+    if is_yuv and clip.dim() == 3:
+        clip = clip.unsqueeze(0)
+    if clip.dim() != (4 if is_yuv else 5):
+        raise RuntimeError("expected %s clips [B, ...], got %s" % (src_layout, tuple(clip.shape),))
+    device = clip.device if clip.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    clip = clip.to(device, non_blocking=True) if is_yuv else _device_source(clip, device)
+    b, t_src = clip.shape[0], clip.shape[2] if src_layout == "NCTHW" else clip.shape[1]
+    channels = 3 if is_yuv else clip.shape[1 if src_layout == "NCTHW" else 4]
+    t = t_src if num_frames is None else num_frames
+    frames = temporal_indices(t_src, t).to(torch.int32)[None]
+    batch = build_video_batch(list(clip.unbind(0)), [frames] * b, src_layout, short_side, crop_size, views, [t], channels, device,
+                              lambda x: x.to(device), height, coded_height)
+    a = L.AreaViewsDesc()
+    a.filter = L.PV_FILTER_AREA
+    matrix = _yuv_matrix_of(yuv, src_layout).float().reshape(12).to(device) if is_yuv else None
+    _batch_launch_fields(a.frames.batch, batch, batch.tables[0], 0, batch.total, channels, src_layout, matrix, (crop_size, crop_size))
+    return _scale_crop_launch(a.frames.batch, "pv_area_views", "area_views", b, channels, affine, dtype, device, outer=a)
 
 
 class DevicePacker:
@@ -1281,13 +1338,26 @@ class DevicePacker:
     every table row, and `fill_batch` resizes each rectangle of the video, read where it lies, to `crop_size`
     (`pv_region_views`) -- no short-side scale, no crop window, one view; classification forms, any source layout, whole
     videos or `FrameList`s; no `orientation` and no `hdr`.  This mode runs through `video_batch` / `fill_batch` only;
-    `inference.TubePredictor` is the loop around it."""
+    `inference.TubePredictor` is the loop around it.
+
+    `interpolation="area"` scales with a box filter -- `short_side_scale(x, size, "area")`, every source pixel under an output
+    pixel averaged, what a 720p or larger source needs -- instead of four taps: `video_batch` / `fill_batch` then launch
+    `pv_area_views`, for whole videos and `FrameList`s, every source layout, `keyframes=True` and its no-crop mode included
+    (boxes depend on the geometry only: `fill_boxes` is the same).  A ValueError with `regions=True`, with `hdr`, for a
+    non-zero `orientation` in `video_batch` and for the clip-at-a-time `packer(clip)` call (use `video_batch` or
+    `device_scale_crop`)."""
 
     def __init__(self, deployed, mean=None, std=None, div255=False, frame_ratios=None, short_side=None, crop_size=None,
                  spatial_idx=1, src_layout="NCTHW", yuv=("bt709", False), coded_height=None, height=None, keyframes=False,
-                 hdr=None, regions=False):
+                 hdr=None, regions=False, interpolation="bilinear"):
         self.subs = None
         self.region_mode = bool(regions)
+        self.area = _interpolation(interpolation, None, hdr, "DevicePacker")
+        if self.area and self.region_mode:
+            raise ValueError("interpolation='area' is not supported together with regions: pv_region_views resizes a tube by "
+                             "about 1-2x with four taps")
+        if self.area and short_side is None:
+            raise ValueError("interpolation='area' is the filter of the short-side scale: give short_side")
         if self.region_mode:
             # the ingest of actor tubes: no short-side scale and no crop window -- every frame's rectangle is resized to crop_size
             if short_side is not None:
@@ -1327,7 +1397,7 @@ class DevicePacker:
             # sub-plan's input buffers, then ONE launch of the joint graph
             self.model = deployed
             self.subs = [DevicePacker(p, mean, std, div255, frame_ratios, short_side, crop_size, spatial_idx, src_layout, yuv,
-                                      coded_height, height, keyframes, hdr, regions) for p in deployed.parts]
+                                      coded_height, height, keyframes, hdr, regions, interpolation) for p in deployed.parts]
             self.window = self.subs[0].window
             self.sess, self.refs = self.subs[0].sess, self.subs[0].refs
             self.frame_ratios = self.subs[0].frame_ratios
@@ -1399,6 +1469,9 @@ class DevicePacker:
 
     @torch.no_grad()
     def __call__(self, clip, bboxes=None, orientation=0):
+        if self.area:
+            raise ValueError("interpolation='area' runs through video_batch / fill_batch (every item a source of its own: "
+                             "pv_area_views); for clips alone use device_scale_crop(..., interpolation='area')")
         _refuse_orientation(orientation, "a clip-at-a-time call")
         if self.region_mode:
             raise RuntimeError("a regions packer runs through video_batch(..., regions=) / fill_batch; clips with a rectangle "
@@ -1529,6 +1602,9 @@ class DevicePacker:
         YUV layout, uint8 [N, Hc*3/2, W] on the device with the strides it has (`yuv_geometry`) -- and must stay alive until
         the forward has run.  Nothing is launched here but the ingest: run `launch()` next."""
         _refuse_frames(video, "fill_video")
+        if self.area:
+            raise ValueError("interpolation='area' runs through video_batch / fill_batch (pv_area_views), a video alone as a "
+                             "batch of one")
         if self.short_side is None or self.no_crop:
             raise RuntimeError("fill_video resamples: construct the packer with short_side and crop_size")
         if getattr(self.model, "_pv_load_boxes", None) is not None:
@@ -1610,6 +1686,8 @@ class DevicePacker:
         row r is the rectangle `regions[j][r, t]` of frame `tables[j][r, t]`, resized to `crop_size` (`pv_region_views`; `box_regions` makes
         rectangles of boxes).  Validated here (inside the frame, at least 1 x 1, even members for YUV layouts) and uploaded
         once, with the records.  ValueError together with `orientation`; such a packer has no `hdr` and one view."""
+        if self.area:
+            _interpolation("area", orientation, None, "video_batch")
         if self.region_mode != (regions is not None):
             if regions is not None:
                 raise ValueError("regions are resized to crop_size with no short-side scale: this packer scales every frame by "
@@ -1660,13 +1738,16 @@ class DevicePacker:
     def _fill_batch(self, batch, item0, n_items):
         """One pv_batch_views launch per pathway into this plan's buffers -- pv_frame_views, the same descriptor with the
         call's pointer table beside it, for a batch of FrameLists; pv_region_views, with the pathway's rectangle table beside
-        both, for a batch built with `regions=`; see Session.video_views for the tail."""
+        both, for a batch built with `regions=`; pv_area_views, the filter beside either source form, for a packer with
+        `interpolation="area"`; see Session.video_views for the tail."""
         from . import _lib as L
         self._src = batch                                  # alive until the launch has run
         for i, (ref, tab) in enumerate(zip(self.refs, batch.tables)):
             g = L.RegionViewsDesc() if batch.regions is not None else None   # pv_region_views: either source form, rectangles behind
             h = L.HdrViewsDesc() if self.hdr is not None else None           # pv_hdr_views: either source form, tap map behind
-            f = g.frames if g is not None else h.frames if h is not None else (L.FrameViewsDesc() if batch.frame_ptrs is not None else None)
+            a = L.AreaViewsDesc() if self.area else None                     # pv_area_views: either source form, the filter behind
+            f = (a.frames if a is not None else g.frames if g is not None else h.frames if h is not None
+                 else (L.FrameViewsDesc() if batch.frame_ptrs is not None else None))
             d = L.BatchViewsDesc() if f is None else f.batch
             _batch_launch_fields(d, batch, tab, item0, n_items, ref.C, self.src_layout, self.yuv_matrix, self.window)
             _set_affine(d, self.scale, self.shift)
@@ -1676,6 +1757,10 @@ class DevicePacker:
             if batch.frame_ptrs is not None:
                 f.frame_ptrs, f.frame_ptrs_dev = batch.frame_ptrs.data_ptr(), batch.frame_ptrs_dev.data_ptr()
                 f.n_frame_ptrs = batch.frame_ptrs.numel()
+            if a is not None:
+                a.filter = L.PV_FILTER_AREA
+                self.sess.area_views(a, ref, planar=self._planar_for(i, ref))
+                continue
             if g is not None:
                 g.regions, g.regions_dev = batch.regions[i].data_ptr(), batch.regions_dev[i].data_ptr()
                 self.sess.region_views(g, ref, planar=self._planar_for(i, ref))
