@@ -23,7 +23,8 @@
 // The host sizes R, X, the staged rows and the LDS pitch(es) from the widest footprint over the records x views the launch's
 // items name (ar_size), with the very calls the kernel makes; none of them enters a value.  A workgroup whose footprint
 // exceeds them -- a device copy that is not the validated one -- stages nothing and writes nothing.
-// One item loader serves whole videos and frame lists (`frames` is workgroup-uniform, as in pv_hdr.hip / pv_region.hip).
+// In front of the body stand the item loader and the geometry builders of pv_rs.h, serving whole videos and frame lists
+// (`frames` is workgroup-uniform, as in pv_orient.hip); the body does not read sy / sx: its windows are integers.
 // 3 RGB / planar forms and 2 chroma arrangements x 2 sample widths, x 5 destination forms: 35 kernels.
 #include "pv_frames.h"
 
@@ -275,48 +276,14 @@ __device__ __forceinline__ void ar_tile_yuv(unsigned char* lds, const ArLaunch& 
   ar_store<FORM, D>(res, g, a, d, 3, zi, t);
 }
 
-// The item of this workgroup, clamped into range before anything is addressed through it (pv_hdr.hip's loader): its record
-// and view, and the selected frame as the video with a frame index (whole videos) or as the frame itself (frame lists).
-struct ArItem {
-  const pv_view_source* __restrict__ S;
-  int view, ts;         // frame lists: ts = 0
-  uintptr_t src;        // the video, or -- frame lists -- the selected frame
-};
-__device__ __forceinline__ ArItem ar_item(const pv_batch_views_desc& d, int frames, int zi, int t) {
-  const pv_view_item* __restrict__ it = d.items_dev + zi;
-  ArItem r;
-  r.S = d.sources_dev + min(max(it->source, 0), d.n_sources - 1);
-  r.view = min(max(it->view, 0), d.n_views - 1);
-  const int row = min(max(it->row, 0), d.n_rows - 1);
-  const int ts = min(max(d.t_index[(long)row * d.t_stride + t], 0), r.S->N - 1);
-  if (frames) {   // read as constant memory: one scalar load (pv_frames.h)
-    typedef const uint64_t __attribute__((address_space(4))) * table_ptr;
-    r.src = (uintptr_t) reinterpret_cast<table_ptr>(reinterpret_cast<uintptr_t>(r.S->src))[ts];
-    r.ts = 0;
-  } else {
-    r.src = reinterpret_cast<uintptr_t>(r.S->src);
-    r.ts = ts;
-  }
-  return r;
-}
-
 // S / INTER / FORM / D: as rs_strip_rgb.
 template <typename S, bool INTER, int FORM, typename D>
 __global__ __launch_bounds__(kRsThreads) void area_views_kernel(const pv_batch_views_desc d, const ArLaunch g, const int frames) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ar_lds[];
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
-  const ArItem item = ar_item(d, frames, zi, t);
-  const pv_view_source* __restrict__ V = item.S;
-  RsRgbSrc s;
-  s.src = item.src;
-  s.Hs = V->Hs, s.Ws = V->Ws, s.N = frames ? 1 : V->N;   // a frame of a list is dense [C, Hs, Ws]: the plane stride of ONE frame
-  s.sy = V->sy, s.sx = V->sx;                      // not used: the windows are integers
-  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
-  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
-  s.ts = item.ts;
-  s.clip_frame0 = 0;
-  ar_tile_rgb<S, INTER, FORM, D>(ar_lds, g, s, V->Hn, V->Wn, rs_dst(d, d.C), zi, t);
+  const RsItem item = rs_item<RS_EITHER>(d, zi, t, frames);
+  ar_tile_rgb<S, INTER, FORM, D>(ar_lds, g, rs_item_rgb(item), item.S->Hn, item.S->Wn, rs_dst(d, d.C), zi, t);
 }
 
 // CSTEP / SMP / FORM / D: as rs_strip_yuv.
@@ -325,35 +292,13 @@ __global__ __launch_bounds__(kRsThreads) void area_yuv_kernel(const pv_batch_vie
   extern __shared__ __attribute__((aligned(16))) unsigned char ay_lds[];
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
-  const ArItem item = ar_item(d, frames, zi, t);
-  const pv_view_source* __restrict__ V = item.S;
-  RsYuvSrc s;
-  s.src = item.src;
-  s.frame_off = (long)item.ts * V->frame_stride;
-  s.Hs = V->Hs, s.Ws = V->Ws;
-  s.sy = V->sy, s.sx = V->sx;                      // not used: the windows are integers
-  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
-  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
-  s.y_pitch = V->y_pitch, s.c_pitch = V->c_pitch;
-  rs_chroma_planes(CSTEP == 2, V->u_offset, V->v_offset, s);
-  ar_tile_yuv<CSTEP, FORM, D, SMP>(ay_lds, g, s, V->Hn, V->Wn, rs_dst(d, 3), d.yuv2rgb, zi, t);
+  const RsItem item = rs_item<RS_EITHER>(d, zi, t, frames);
+  ar_tile_yuv<CSTEP, FORM, D, SMP>(ay_lds, g, rs_item_yuv<CSTEP>(item), item.S->Hn, item.S->Wn, rs_dst(d, 3), d.yuv2rgb, zi, t);
 }
 
-// RS_DISPATCH over the tile grid with the further kernel argument; expects d, g, lds, stream and fr in scope.
-#define AR_DISPATCH(KERNEL, ...)                                                                                         \
-  do {                                                                                                                   \
-    const dim3 grid((unsigned)(pv_ceil_div(d.Ho, g.R) * g.tiles_x), (unsigned)d.T, (unsigned)d.n_items), block(kRsThreads); \
-    hipStream_t s = static_cast<hipStream_t>(stream);                                                                    \
-    if (d.dst_layout == PV_DST_NCTHW) {                                                                                  \
-      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, bf16_t>), grid, block, lds, s, d, g, fr);    \
-      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, float>), grid, block, lds, s, d, g, fr);                            \
-    } else if (d.c_p == 4) {                                                                                             \
-      PV_LAUNCH((KERNEL<__VA_ARGS__, RS_C4, bf16_t>), grid, block, lds, s, d, g, fr);                                    \
-    } else {                                                                                                             \
-      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, bf16_t>), grid, block, lds, s, d, g, fr);        \
-      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, float>), grid, block, lds, s, d, g, fr);                                \
-    }                                                                                                                    \
-  } while (0)
+#define AR_TILES(KERNEL, ...) RS_DISPATCH(pv_ceil_div(d.Ho, g.R) * g.tiles_x, lds, (d, g, fr), KERNEL, __VA_ARGS__)
+#define AR_RGB(S, INTER) AR_TILES(area_views_kernel, S, INTER)
+#define AR_YUV(CSTEP, SMP) AR_TILES(area_yuv_kernel, CSTEP, SMP)
 
 // Folds the widest footprint of an R x X tile of record v over its views into n: source rows, source columns, chroma rows,
 // chroma columns.  Rows and columns are independent, so the bands of strips and of column tiles are walked separately, with
@@ -384,8 +329,6 @@ inline void ar_footprint(const pv_view_source& v, int n_views, int Ho, int Wo, i
 // smallest one if it fits the LDS limit.  That last refusal needs a window of some 2000 taps per channel plane (a ratio
 // beyond 50 for uint8 sources, beyond 25 for fp32 ones: a 2160p frame scaled to a short side of 80).
 inline int ar_size(const pv_batch_views_desc& d, const std::vector<const pv_view_source*>& records, ArLaunch& g, size_t& lds) {
-  const bool yuv = d.src_layout == PV_SRC_YUV420, inter = d.src_layout == PV_SRC_NTHWC;
-  const int sb = d.src_dtype == PV_U16 ? 2 : 1;
   constexpr size_t n_tiles = sizeof(kArTiles) / sizeof(kArTiles[0]);
   for (size_t k = 0; k < n_tiles; ++k) {
     const int R = kArTiles[k][0], X = kArTiles[k][1];
@@ -393,16 +336,7 @@ inline int ar_size(const pv_batch_views_desc& d, const std::vector<const pv_view
     for (const pv_view_source* v : records) ar_footprint(*v, d.n_views, d.Ho, d.Wo, R, X, n);
     g = {};
     g.R = R, g.X = X, g.tiles_x = (int32_t)pv_ceil_div(d.Wo, X);
-    g.rows = n[0], g.rows_c = n[2];
-    long bytes;
-    if (yuv) {
-      rs_yuv_pitches(n[1], n[3], d.c_step, sb, g.pitch, g.pitch_c);
-      g.c_base = g.rows * g.pitch;
-      bytes = (long)g.c_base + (long)g.rows_c * (d.c_step == 2 ? 1 : 2) * g.pitch_c;
-    } else {
-      g.pitch = pv_round_up(n[1] * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
-      bytes = (long)g.rows * (inter ? 1 : d.C) * g.pitch;
-    }
+    long bytes = rs_tile_layout(d, n, g);           // the staged source rectangle, as a tile of pv_rs.h lays it out
     if (bytes > kRsLdsMax) {                       // before it is narrowed to 32 bits
       if (k + 1 == n_tiles) return PV_ERR_UNSUPPORTED;
       continue;
@@ -416,23 +350,21 @@ inline int ar_size(const pv_batch_views_desc& d, const std::vector<const pv_view
   return PV_ERR_UNSUPPORTED;
 }
 
-// The descriptor as the wrapped entry point checks it (rs_check_item_desc), then every item: its range and its record
-// (rs_check_record with the entry point's check of `src`) -- all of PV_ERR_INVALID first --, then what this entry point does
-// not carry: oriented records and products beyond the index limit.  The launch is sized from the records the items name.
+// The descriptor as the wrapped entry point checks it (rs_check_item_desc), then every item (rs_walk_items): its range and
+// its record (rs_check_record with the entry point's check of `src`) -- all of PV_ERR_INVALID first --, then what this entry
+// point does not carry: oriented records and products beyond the index limit.  The launch is sized from the records the items
+// name.
 template <typename CheckSrc>
 int ar_run(const pv_batch_views_desc& d, bool frames, const CheckSrc& check_src, pv_stream_t stream) {
   if (int e = rs_check_item_desc(d)) return e;
   const bool yuv = d.src_layout == PV_SRC_YUV420;
   std::vector<const pv_view_source*> records;      // the records the items name, a video-major run once
-  for (int i = 0; i < d.n_items; ++i) {
-    const pv_view_item& it = d.items[i];
-    if (it.source < 0 || it.source >= d.n_sources || it.row < 0 || it.row >= d.n_rows || it.view < 0 || it.view >= d.n_views)
-      return PV_ERR_INVALID;
-    const pv_view_source& v = d.sources[it.source];
-    if (i > 0 && it.source == d.items[i - 1].source) continue;   // a video-major sequence names the record just checked
-    if (int e = rs_check_record(d, v, yuv, check_src)) return e;
-    records.push_back(&v);
-  }
+  const auto check = [&](const pv_view_source& v) { return rs_check_record(d, v, yuv, check_src); };
+  const auto each = [&](const pv_view_item&, const pv_view_source& v, bool again) {
+    if (!again) records.push_back(&v);
+    return PV_OK;
+  };
+  if (int e = rs_walk_items(d, check, each)) return e;
   constexpr long kIndexLimit = 1L << 24;
   for (const pv_view_source* v : records) {
     if (v->orient != 0) return PV_ERR_UNSUPPORTED;
@@ -442,19 +374,7 @@ int ar_run(const pv_batch_views_desc& d, bool frames, const CheckSrc& check_src,
   size_t lds = 0;
   if (int e = ar_size(d, records, g, lds)) return e;
   const int fr = frames ? 1 : 0;
-  if (yuv && d.src_dtype == PV_U16) {
-    if (d.c_step == 2) AR_DISPATCH(area_yuv_kernel, 2, unsigned short);
-    else AR_DISPATCH(area_yuv_kernel, 1, unsigned short);
-  } else if (yuv) {
-    if (d.c_step == 2) AR_DISPATCH(area_yuv_kernel, 2, unsigned char);
-    else AR_DISPATCH(area_yuv_kernel, 1, unsigned char);
-  } else if (d.src_layout == PV_SRC_NTHWC) {
-    AR_DISPATCH(area_views_kernel, unsigned char, true);
-  } else if (d.src_dtype == PV_U8) {
-    AR_DISPATCH(area_views_kernel, unsigned char, false);
-  } else {
-    AR_DISPATCH(area_views_kernel, float, false);
-  }
+  RS_SOURCE_FORMS(AR_RGB, AR_YUV);
   PV_LAUNCH_CHECK();
   return PV_OK;
 }
@@ -463,15 +383,8 @@ int ar_run(const pv_batch_views_desc& d, bool frames, const CheckSrc& check_src,
 
 extern "C" int pv_area_views(const pv_area_views_desc* ap, pv_stream_t stream) {
   if (!ap) return PV_ERR_INVALID;
-  const pv_frame_views_desc& f = ap->frames;
   if (ap->filter != PV_FILTER_AREA) return PV_ERR_INVALID;
   if (ap->reserved[0] != 0 || ap->reserved[1] != 0 || ap->reserved[2] != 0) return PV_ERR_INVALID;
-  if ((f.frame_ptrs == nullptr) != (f.frame_ptrs_dev == nullptr)) return PV_ERR_INVALID;   // a table only half given
-  const bool frames = f.frame_ptrs != nullptr;
-  if (!frames && f.n_frame_ptrs != 0) return PV_ERR_INVALID;
-  if (frames) {
-    if (int e = fv_check_table(f)) return e;
-    return ar_run(f.batch, true, fv_check_src(f), stream);
-  }
-  return ar_run(f.batch, false, rs_check_video_src(f.batch.src_dtype), stream);
+  const pv_batch_views_desc& d = ap->frames.batch;
+  return fv_with_table(ap->frames, [&](bool frames, const auto& check_src) { return ar_run(d, frames, check_src, stream); });
 }

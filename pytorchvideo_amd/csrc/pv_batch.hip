@@ -4,11 +4,10 @@
 //
 // The kernels are the staged strips of pv_rs.h (rs_strip_rgb, rs_strip_yuv), the bodies of pv_video_views / pv_yuv_views,
 // with the geometry those take by value -- Hs, Ws, the window origins, sy / sx, the source address and, for YUV, the plane
-// offsets -- read from the item's 96-byte record (pv_view_source) instead: blockIdx.z loads its 16-byte item, clamps source /
-// row / view into range and loads the record.  Everything in the record is uniform over the workgroup, so these are scalar
-// loads; the record is read field by field through a pointer (a by-value copy indexed at run time would be scratch) and
-// the view is selected, not indexed.  One body serves both, so an item holds the bits pv_video_views / pv_yuv_views writes
-// for its video alone.
+// offsets -- read from the item's 96-byte record (pv_view_source) instead: rs_item loads and clamps the item of blockIdx.z,
+// rs_item_rgb / rs_item_yuv fill the geometry from its record (pv_rs.h; pv_frame_views and the entry points built on the
+// two use the same pair).  One body serves both, so an item holds the bits pv_video_views / pv_yuv_views writes for its video
+// alone.
 //
 // What stays per LAUNCH is what sizes the workgroup (RsItemLaunch): R output rows per strip and the LDS pitch(es) of a staged
 // row.  The host sizes the pitch from the widest column span over every (source an item refers to) x view and R from the LDS
@@ -18,27 +17,12 @@
 // host copy -- makes the body return before it stages anything.
 //
 // This file holds the three kernel wrappers (batch_views_kernel, batch_yuv_kernel, batch_yuv16_kernel: 35 kernels) and the
-// dispatch over them.  The host checks and the sizing are rs_item_launch (pv_rs.h), shared with pv_frame_views; what is
-// checked here is only that a record's `src` is one allocation of the source dtype.
+// dispatch over them.  The 8-bit and the 16-bit YUV wrapper differ in the sample type alone and keep a name each: the
+// code-object tests count the kernels of each name.  The host checks and the sizing are rs_item_launch (pv_rs.h), shared with
+// pv_frame_views; what is checked here is only that a record's `src` is one allocation of the source dtype.
 #include "pv_rs.h"
 
 namespace {
-
-// The item of this workgroup, clamped into range before anything is addressed through it, and the frame its table row
-// selects, clamped the same way: a malformed table can never read outside the item's source.
-struct BvItem {
-  const pv_view_source* __restrict__ S;
-  int view, ts;
-};
-__device__ __forceinline__ BvItem bv_item(const pv_batch_views_desc& d, int zi, int t) {
-  const pv_view_item* __restrict__ it = d.items_dev + zi;
-  BvItem r;
-  r.S = d.sources_dev + min(max(it->source, 0), d.n_sources - 1);
-  r.view = min(max(it->view, 0), d.n_views - 1);
-  const int row = min(max(it->row, 0), d.n_rows - 1);
-  r.ts = min(max(d.t_index[(long)row * d.t_stride + t], 0), r.S->N - 1);
-  return r;
-}
 
 // S / INTER / FORM / D: as rs_strip_rgb.
 template <typename S, bool INTER, int FORM, typename D>
@@ -46,61 +30,37 @@ __global__ __launch_bounds__(kRsThreads) void batch_views_kernel(const pv_batch_
   extern __shared__ __attribute__((aligned(16))) unsigned char bv_lds[];
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
-  const BvItem item = bv_item(d, zi, t);
-  const pv_view_source* __restrict__ V = item.S;
-  RsRgbSrc s;
-  s.src = reinterpret_cast<uintptr_t>(V->src);
-  s.Hs = V->Hs, s.Ws = V->Ws, s.N = V->N;
-  s.sy = V->sy, s.sx = V->sx;
-  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
-  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
-  s.ts = item.ts;
-  s.clip_frame0 = 0;
+  const RsRgbSrc s = rs_item_rgb(rs_item<RS_VIDEOS>(d, zi, t));
   rs_strip_rgb<S, INTER, FORM, D>(bv_lds, g.R, g.pitch, s, rs_dst(d, d.C), zi, t, true);
 }
 
-// CSTEP / FORM / D: as rs_strip_yuv.  Which byte of an interleaved pair is U / V, and where the staged chroma plane(s) start
-// inside a frame, follow from the record's offsets.
+// CSTEP / FORM / D: as rs_strip_yuv.
 template <int CSTEP, int FORM, typename D>
 __global__ __launch_bounds__(kRsThreads) void batch_yuv_kernel(const pv_batch_views_desc d, const RsItemLaunch g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char by_lds[];
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
-  const BvItem item = bv_item(d, zi, t);
-  const pv_view_source* __restrict__ V = item.S;
-  RsYuvSrc s;
-  s.src = reinterpret_cast<uintptr_t>(V->src);
-  s.frame_off = (long)item.ts * V->frame_stride;
-  s.Hs = V->Hs, s.Ws = V->Ws;
-  s.sy = V->sy, s.sx = V->sx;
-  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
-  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
-  s.y_pitch = V->y_pitch, s.c_pitch = V->c_pitch;
-  rs_chroma_planes(CSTEP == 2, V->u_offset, V->v_offset, s);
+  const RsYuvSrc s = rs_item_yuv<CSTEP>(rs_item<RS_VIDEOS>(d, zi, t));
   rs_strip_yuv<CSTEP, FORM, D>(by_lds, g.R, g.pitch, g.pitch_c, g.c_base, s, rs_dst(d, 3), d.yuv2rgb, zi, t, true);
 }
 
-// The same on two-byte samples (PV_U16 / pv_yuv16_views).  A kernel of its own, spelled out rather than sharing a wrapper
-// with the one above: routed through a common inline function the 8-bit kernels come out with other instructions than
-// they had (commuted scalar adds), and their code is pinned.
+// The same on two-byte samples (PV_U16 / pv_yuv16_views).
 template <int CSTEP, int FORM, typename D>
 __global__ __launch_bounds__(kRsThreads) void batch_yuv16_kernel(const pv_batch_views_desc d, const RsItemLaunch g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char by_lds[];
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
-  const BvItem item = bv_item(d, zi, t);
-  const pv_view_source* __restrict__ V = item.S;
-  RsYuvSrc s;
-  s.src = reinterpret_cast<uintptr_t>(V->src);
-  s.frame_off = (long)item.ts * V->frame_stride;
-  s.Hs = V->Hs, s.Ws = V->Ws;
-  s.sy = V->sy, s.sx = V->sx;
-  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
-  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
-  s.y_pitch = V->y_pitch, s.c_pitch = V->c_pitch;
-  rs_chroma_planes(CSTEP == 2, V->u_offset, V->v_offset, s);
+  const RsYuvSrc s = rs_item_yuv<CSTEP>(rs_item<RS_VIDEOS>(d, zi, t));
   rs_strip_yuv<CSTEP, FORM, D, unsigned short>(by_lds, g.R, g.pitch, g.pitch_c, g.c_base, s, rs_dst(d, 3), d.yuv2rgb, zi, t, true);
 }
+
+#define BV_STRIPS(KERNEL, ...) RS_DISPATCH(pv_ceil_div(d.Ho, g.R), lds, (d, g), KERNEL, __VA_ARGS__)
+#define BV_RGB(S, INTER) BV_STRIPS(batch_views_kernel, S, INTER)
+#define BV_YUV(CSTEP, SMP)                                             \
+  do {                                                                 \
+    if (sizeof(SMP) == 2) BV_STRIPS(batch_yuv16_kernel, CSTEP);        \
+    else BV_STRIPS(batch_yuv_kernel, CSTEP);                           \
+  } while (0)
 
 // Validation and sizing are rs_item_launch's (pv_rs.h); this entry point's own part is the record's `src`, one allocation:
 // 4-byte aligned for fp32, even for 16-bit samples (either dtype outside its layouts is refused before a record is read).
@@ -113,20 +73,7 @@ int bv_run(const pv_batch_views_desc& desc, pv_stream_t stream) {
   if (int e = rs_item_launch(desc, check_src, g, lds, tg, lds_t)) return e;
   // the strips of a run of upright items: the whole launch when no record is oriented
   auto upright = [&](const pv_batch_views_desc& d) -> int {
-    const bool yuv = d.src_layout == PV_SRC_YUV420;
-    if (yuv && d.src_dtype == PV_U16) {
-      if (d.c_step == 2) RS_DISPATCH(batch_yuv16_kernel, 2);
-      else RS_DISPATCH(batch_yuv16_kernel, 1);
-    } else if (yuv) {
-      if (d.c_step == 2) RS_DISPATCH(batch_yuv_kernel, 2);
-      else RS_DISPATCH(batch_yuv_kernel, 1);
-    } else if (d.src_layout == PV_SRC_NTHWC) {
-      RS_DISPATCH(batch_views_kernel, unsigned char, true);
-    } else if (d.src_dtype == PV_U8) {
-      RS_DISPATCH(batch_views_kernel, unsigned char, false);
-    } else {
-      RS_DISPATCH(batch_views_kernel, float, false);
-    }
+    RS_SOURCE_FORMS(BV_RGB, BV_YUV);
     PV_LAUNCH_CHECK();
     return PV_OK;
   };

@@ -4,7 +4,7 @@
 // The box list of a whole call (every key frame of every video) is uploaded once; a forward holds a window of the call's
 // item sequence and a window of its boxes, so one launch per forward replaces the host mapping and the host-to-device copy
 // of every forward.  One thread per destination row: a row inside the launch loads its box, finds its item (clamped source
-// and view, as bv_item of pv_batch_views.hip clamps them) and reads the geometry from that item's record; a row behind the
+// and view, as rs_item of pv_rs.h clamps them) and reads the geometry from that item's record; a row behind the
 // launch -- and a box whose item lies outside the window -- becomes {-1, 0, 0, 0, 0}, which pv_roi_align answers with zeros.
 // The arithmetic is clip_boxes_to_image, short_side_scale_with_boxes, crop_boxes, clip_boxes_to_image of the reference in
 // fp32, every operation rounded on its own: the rule rs_coord (pv_rs.h) uses for coordinates.  Boxes are finite.  Boxes stay

@@ -1,5 +1,6 @@
-// What pv_frames.hip and pv_frames16.hip share: the item of a workgroup of pv_frame_views and the launch of its 16-bit kernels;
-// and what pv_frames.hip, pv_hdr.hip and pv_region.hip share: the host checks of the pointer table.
+// The pointer table of pv_frame_views on the host, for pv_frames.hip and for the entry points that take it optionally
+// (pv_hdr.hip, pv_region.hip, pv_area.hip): its checks, the check of a record's slice of it, and the prologue that tells a
+// launch over frame lists from one over whole videos.  (On the device the table is read by rs_item, pv_rs.h.)
 #pragma once
 #include "pv_rs.h"
 
@@ -8,28 +9,6 @@
 int pv_frame_yuv16_launch(const pv_batch_views_desc& d, const RsItemLaunch& g, size_t lds, pv_stream_t stream);
 
 namespace {
-
-// The item of this workgroup, clamped into range before anything is addressed through it, and the base address of the
-// frame its table row selects: the entry is clamped into [0, N-1] of the item's source before the slice is indexed, so a
-// malformed table can never read outside the item's slice.
-struct FvItem {
-  const pv_view_source* __restrict__ S;
-  int view;
-  uintptr_t frame;
-};
-__device__ __forceinline__ FvItem fv_item(const pv_batch_views_desc& d, int zi, int t) {
-  const pv_view_item* __restrict__ it = d.items_dev + zi;
-  FvItem r;
-  r.S = d.sources_dev + min(max(it->source, 0), d.n_sources - 1);
-  r.view = min(max(it->view, 0), d.n_views - 1);
-  const int row = min(max(it->row, 0), d.n_rows - 1);
-  const int ts = min(max(d.t_index[(long)row * d.t_stride + t], 0), r.S->N - 1);
-  // `src` is a generic pointer loaded from memory: read through it the entry would be a per-lane flat load.  The table is
-  // global memory that nothing writes while the kernel runs, so it is read as constant memory: one scalar load.
-  typedef const uint64_t __attribute__((address_space(4))) * table_ptr;
-  r.frame = (uintptr_t) reinterpret_cast<table_ptr>(reinterpret_cast<uintptr_t>(r.S->src))[ts];
-  return r;
-}
 
 // The pointer table of a pv_frame_views_desc: both copies, a device copy at a multiple of 8, a positive length.
 inline int fv_check_table(const pv_frame_views_desc& f) {
@@ -57,6 +36,20 @@ inline auto fv_check_src(const pv_frame_views_desc& f) {
     }
     return PV_OK;
   };
+}
+
+// An entry point whose table is optional: with one its records are slices of it (frame lists), without one whole videos.
+// A table only half given and a length without a table are PV_ERR_INVALID; then `supported` -- what the entry point carries
+// of the source forms, judged before the table is read -- else PV_ERR_UNSUPPORTED; then run(frames, check_src) with the
+// check of a record's `src` that goes with the kind, behind the table's own checks.
+template <typename Run> inline int fv_with_table(const pv_frame_views_desc& f, const Run& run, bool supported = true) {
+  if ((f.frame_ptrs == nullptr) != (f.frame_ptrs_dev == nullptr)) return PV_ERR_INVALID;
+  const bool frames = f.frame_ptrs != nullptr;
+  if (!frames && f.n_frame_ptrs != 0) return PV_ERR_INVALID;
+  if (!supported) return PV_ERR_UNSUPPORTED;
+  if (!frames) return run(false, rs_check_video_src(f.batch.src_dtype));
+  if (int e = fv_check_table(f)) return e;
+  return run(true, fv_check_src(f));
 }
 
 }  // namespace

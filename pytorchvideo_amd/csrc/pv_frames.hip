@@ -2,24 +2,25 @@
 // -- one allocation per frame, uniform geometry and pitch, any order, reused -- and a live stream never is one tensor; here
 // a source is a slice of a device table of frame base addresses instead of one allocation with a constant frame stride.
 //
-// The kernels are the staged strips of pv_rs.h (rs_strip_rgb, rs_strip_yuv), wrapped as pv_batch.hip wraps them: blockIdx.z
-// loads its 16-byte item, clamps source / row / view into range, loads the item's record and clamps the table entry into
-// [0, N-1] of that source.  Where batch_views_kernel multiplies the entry by the frame size, these load the frame's base
-// address from the record's slice (record.src + 8 * entry) -- one more workgroup-uniform, scalar load -- and hand the
-// body a geometry with the frame at offset 0: a one-frame source (N = 1, ts = 0) for the RGB / planar forms, frame_off = 0
-// for YUV.  Every other value the body sees is the one batch_views_kernel gives it, so an item holds the bits
-// pv_batch_views writes for the same frames in one allocation.  The body fetches only the aligned 16-byte granules that
-// cover a byte of the span, and such a granule lies in the page of that byte: a frame that ends at the end of its
-// allocation is safe.
+// The kernels are the staged strips of pv_rs.h (rs_strip_rgb, rs_strip_yuv) behind the item loader and the geometry builders
+// of pv_rs.h, as in pv_batch.hip, with the loader told at compile time that sources are frame lists (rs_item<RS_FRAMES>).
+// Where batch_views_kernel multiplies the table entry by the frame size, these load the frame's base address from the
+// record's slice (record.src + 8 * entry) -- one more workgroup-uniform, scalar load -- and hand the body a geometry with the
+// frame at offset 0: a one-frame source (N = 1, ts = 0) for the RGB / planar forms, frame_off = 0 for YUV.  Every other
+// value the body sees is the one batch_views_kernel gives it, so an item holds the bits pv_batch_views writes for the same
+// frames in one allocation.  The body fetches only the aligned 16-byte granules that cover a byte of the span, and such a
+// granule lies in the page of that byte: a frame that ends at the end of its allocation is safe.
 //
 // What stays per launch -- R, the LDS pitch(es): RsItemLaunch -- is sized as pv_batch_views sizes it, from the host copies of
 // the records the items name.  The descriptor embeds a whole pv_batch_views_desc, and one routine validates and sizes both
 // (rs_item_launch, pv_rs.h); fv_run checks the pointer table in front of it and hands it the check of a record's `src`,
 // read as a table slice.
 //
-// This file holds two kernel wrappers (frame_views_kernel, frame_yuv_kernel) and the dispatch over them.  PV_U16 sources
-// (16-bit YUV samples) are validated and sized here and launched from pv_frames16.hip, which holds their kernels: this
-// translation unit keeps exactly its 25.  pv_frames.h has what the two share on the device: the item loader.
+// This file holds two kernel wrappers (frame_views_kernel, frame_yuv_kernel: 25 kernels) and the dispatch over them.  PV_U16
+// sources (16-bit YUV samples) are validated and sized here and launched from pv_frames16.hip, which holds their wrapper,
+// frame_yuv16_kernel: the two differ in the sample type alone.  The second translation unit stays because the code-object
+// tests compile the two apart and count the kernels of each; build time argues neither way (10 s and 5 s of a parallel build
+// whose slowest units take 27 s).
 #include "pv_frames.h"
 
 namespace {
@@ -30,16 +31,7 @@ __global__ __launch_bounds__(kRsThreads) void frame_views_kernel(const pv_batch_
   extern __shared__ __attribute__((aligned(16))) unsigned char fv_lds[];
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
-  const FvItem item = fv_item(d, zi, t);
-  const pv_view_source* __restrict__ V = item.S;
-  RsRgbSrc s;
-  s.src = item.frame;
-  s.Hs = V->Hs, s.Ws = V->Ws, s.N = 1;
-  s.sy = V->sy, s.sx = V->sx;
-  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
-  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
-  s.ts = 0;
-  s.clip_frame0 = 0;
+  const RsRgbSrc s = rs_item_rgb(rs_item<RS_FRAMES>(d, zi, t));
   rs_strip_rgb<S, INTER, FORM, D>(fv_lds, g.R, g.pitch, s, rs_dst(d, d.C), zi, t, true);
 }
 
@@ -49,19 +41,16 @@ __global__ __launch_bounds__(kRsThreads) void frame_yuv_kernel(const pv_batch_vi
   extern __shared__ __attribute__((aligned(16))) unsigned char fy_lds[];
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
-  const FvItem item = fv_item(d, zi, t);
-  const pv_view_source* __restrict__ V = item.S;
-  RsYuvSrc s;
-  s.src = item.frame;
-  s.frame_off = 0;
-  s.Hs = V->Hs, s.Ws = V->Ws;
-  s.sy = V->sy, s.sx = V->sx;
-  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
-  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
-  s.y_pitch = V->y_pitch, s.c_pitch = V->c_pitch;
-  rs_chroma_planes(CSTEP == 2, V->u_offset, V->v_offset, s);
+  const RsYuvSrc s = rs_item_yuv<CSTEP>(rs_item<RS_FRAMES>(d, zi, t));
   rs_strip_yuv<CSTEP, FORM, D>(fy_lds, g.R, g.pitch, g.pitch_c, g.c_base, s, rs_dst(d, 3), d.yuv2rgb, zi, t, true);
 }
+
+#define FV_RGB(S, INTER) RS_DISPATCH(pv_ceil_div(d.Ho, g.R), lds, (d, g), frame_views_kernel, S, INTER)
+#define FV_YUV(CSTEP, SMP)                                                                          \
+  do {                                                                                              \
+    if (sizeof(SMP) == 2) return pv_frame_yuv16_launch(d, g, lds, stream);   /* pv_frames16.hip */  \
+    RS_DISPATCH(pv_ceil_div(d.Ho, g.R), lds, (d, g), frame_yuv_kernel, CSTEP);                      \
+  } while (0)
 
 // The pointer table, then rs_item_launch (pv_rs.h) for everything pv_batch_views checks and sizes too.  This entry point's own
 // part of a record is its `src`, a slice of the table (fv_check_table, fv_check_src: pv_frames.h).
@@ -74,19 +63,7 @@ int fv_run(const pv_frame_views_desc& f, pv_stream_t stream) {
   if (int e = rs_item_launch(f.batch, check_src, g, lds, tg, lds_t)) return e;
   // the strips of a run of upright items: the whole launch when no record is oriented
   auto upright = [&](const pv_batch_views_desc& d) -> int {
-    const bool yuv = d.src_layout == PV_SRC_YUV420;
-    if (yuv && d.src_dtype == PV_U16) {
-      return pv_frame_yuv16_launch(d, g, lds, stream);   // pv_frames16.hip
-    } else if (yuv) {
-      if (d.c_step == 2) RS_DISPATCH(frame_yuv_kernel, 2);
-      else RS_DISPATCH(frame_yuv_kernel, 1);
-    } else if (d.src_layout == PV_SRC_NTHWC) {
-      RS_DISPATCH(frame_views_kernel, unsigned char, true);
-    } else if (d.src_dtype == PV_U8) {
-      RS_DISPATCH(frame_views_kernel, unsigned char, false);
-    } else {
-      RS_DISPATCH(frame_views_kernel, float, false);
-    }
+    RS_SOURCE_FORMS(FV_RGB, FV_YUV);
     PV_LAUNCH_CHECK();
     return PV_OK;
   };

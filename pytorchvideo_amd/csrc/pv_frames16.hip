@@ -11,25 +11,15 @@ __global__ __launch_bounds__(kRsThreads) void frame_yuv16_kernel(const pv_batch_
   extern __shared__ __attribute__((aligned(16))) unsigned char fy_lds[];
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
-  const FvItem item = fv_item(d, zi, t);
-  const pv_view_source* __restrict__ V = item.S;
-  RsYuvSrc s;
-  s.src = item.frame;
-  s.frame_off = 0;
-  s.Hs = V->Hs, s.Ws = V->Ws;
-  s.sy = V->sy, s.sx = V->sx;
-  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
-  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
-  s.y_pitch = V->y_pitch, s.c_pitch = V->c_pitch;
-  rs_chroma_planes(CSTEP == 2, V->u_offset, V->v_offset, s);
+  const RsYuvSrc s = rs_item_yuv<CSTEP>(rs_item<RS_FRAMES>(d, zi, t));
   rs_strip_yuv<CSTEP, FORM, D, unsigned short>(fy_lds, g.R, g.pitch, g.pitch_c, g.c_base, s, rs_dst(d, 3), d.yuv2rgb, zi, t, true);
 }
 
 }  // namespace
 
 int pv_frame_yuv16_launch(const pv_batch_views_desc& d, const RsItemLaunch& g, size_t lds, pv_stream_t stream) {
-  if (d.c_step == 2) RS_DISPATCH(frame_yuv16_kernel, 2);
-  else RS_DISPATCH(frame_yuv16_kernel, 1);
+  if (d.c_step == 2) RS_DISPATCH(pv_ceil_div(d.Ho, g.R), lds, (d, g), frame_yuv16_kernel, 2);
+  else RS_DISPATCH(pv_ceil_div(d.Ho, g.R), lds, (d, g), frame_yuv16_kernel, 1);
   PV_LAUNCH_CHECK();
   return PV_OK;
 }

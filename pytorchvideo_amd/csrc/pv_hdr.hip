@@ -6,10 +6,9 @@
 //
 // The kernels are the staged strip and the staged tile of pv_rs.h (rs_strip_yuv, rs_tile_yuv) with the tap map HdrMap as their
 // trailing template argument: staging, coordinates, the clamp, the pinned blend, the affine map and the stores are the bodies'
-// own, so everything but the map is what pv_yuv16_views computes.  The wrappers are spelled out here rather than shared with
-// pv_batch.hip / pv_frames16.hip / pv_orient.hip, whose kernels are pinned instruction for instruction.  One item loader
-// serves both source forms: `frames` is workgroup-uniform, so the frame is `src` plus the table entry times the frame stride
-// (whole videos) or the entry of the record's slice of the pointer table (frame lists), as in pv_orient.hip.  The transfer is
+// own, so everything but the map is what pv_yuv16_views computes.  One item loader serves both source forms: `frames` is
+// workgroup-uniform, so the frame is `src` plus the table entry times the frame stride (whole videos) or the entry of the
+// record's slice of the pointer table (frame lists), as in pv_orient.hip.  The transfer is
 // a template argument -- each kernel carries one curve, which keeps the G = 8 planar forms (32 mapped taps per thread,
 // unrolled) inside the instruction cache's reach: 2 transfers x 2 chroma arrangements x 5 destination forms x (strip, tile)
 // = 40 kernels.
@@ -88,8 +87,11 @@ template <int TRANSFER> struct HdrMap {
   }
 };
 
-// The item of this workgroup, clamped into range before anything is addressed through it (pv_orient.hip's loader): its
-// record, view and orientation, and the selected frame as (base, byte offset).
+// The item of this workgroup, clamped into range before anything is addressed through it, as rs_item (pv_rs.h) does: its
+// record, view and orientation, and the selected frame as (base, byte offset).  This file's own: the byte offset is formed
+// inside the branch that tells the two kinds of source apart, and behind rs_item / rs_item_yuv, which multiply after it, all
+// 40 kernels come out with that scalar multiply moved and other scalar registers (the same VGPR counts; profiles/r24/
+// isa_vs_parent.md), which is not taken without the bit comparison and the timing on the device.
 struct HdrItem {
   const pv_view_source* __restrict__ S;
   int view, orient;
@@ -104,7 +106,7 @@ __device__ __forceinline__ HdrItem hdr_item(const pv_batch_views_desc& d, int fr
   const int row = min(max(it->row, 0), d.n_rows - 1);
   const int ts = min(max(d.t_index[(long)row * d.t_stride + t], 0), r.S->N - 1);
   r.orient = r.S->orient & 7;
-  if (frames) {   // read as constant memory: one scalar load (pv_frames.h)
+  if (frames) {   // read as constant memory: one scalar load (rs_item, pv_rs.h)
     typedef const uint64_t __attribute__((address_space(4))) * table_ptr;
     r.src = (uintptr_t) reinterpret_cast<table_ptr>(reinterpret_cast<uintptr_t>(r.S->src))[ts];
     r.frame_off = 0;
@@ -156,29 +158,15 @@ __global__ __launch_bounds__(kRsThreads) void hdr_tile_kernel(const pv_batch_vie
   rs_tile_yuv<CSTEP, FORM, D, unsigned short, HdrMap<TRANSFER>>(ht_lds, g, s, item.orient, rs_dst(d, 3), d.yuv2rgb, zi, t, map);
 }
 
-// RS_DISPATCH with the two further kernel arguments; expects d, g, grid, lds, stream, fr and tone in scope.
-#define HDR_FORMS(KERNEL, CSTEP, TRANSFER)                                                                               \
-  do {                                                                                                                   \
-    const dim3 block(kRsThreads);                                                                                        \
-    hipStream_t s = static_cast<hipStream_t>(stream);                                                                    \
-    if (d.dst_layout == PV_DST_NCTHW) {                                                                                  \
-      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<CSTEP, TRANSFER, RS_PLANAR, bf16_t>), grid, block, lds, s, d, g, fr, tone); \
-      else PV_LAUNCH((KERNEL<CSTEP, TRANSFER, RS_PLANAR, float>), grid, block, lds, s, d, g, fr, tone);                  \
-    } else if (d.c_p == 4) {                                                                                             \
-      PV_LAUNCH((KERNEL<CSTEP, TRANSFER, RS_C4, bf16_t>), grid, block, lds, s, d, g, fr, tone);                          \
-    } else {                                                                                                             \
-      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<CSTEP, TRANSFER, RS_CL, bf16_t>), grid, block, lds, s, d, g, fr, tone); \
-      else PV_LAUNCH((KERNEL<CSTEP, TRANSFER, RS_CL, float>), grid, block, lds, s, d, g, fr, tone);                      \
-    }                                                                                                                    \
-  } while (0)
-#define HDR_DISPATCH(KERNEL)                                                                                             \
+// The transfer and the chroma arrangement in front of RS_DISPATCH; expects d, g, lds, stream, fr, tone and transfer in scope.
+#define HDR_DISPATCH(GRID_X, KERNEL)                                                                                     \
   do {                                                                                                                   \
     if (transfer == PV_TRANSFER_PQ) {                                                                                    \
-      if (d.c_step == 2) HDR_FORMS(KERNEL, 2, PV_TRANSFER_PQ);                                                           \
-      else HDR_FORMS(KERNEL, 1, PV_TRANSFER_PQ);                                                                         \
+      if (d.c_step == 2) RS_DISPATCH(GRID_X, lds, (d, g, fr, tone), KERNEL, 2, PV_TRANSFER_PQ);                          \
+      else RS_DISPATCH(GRID_X, lds, (d, g, fr, tone), KERNEL, 1, PV_TRANSFER_PQ);                                        \
     } else {                                                                                                             \
-      if (d.c_step == 2) HDR_FORMS(KERNEL, 2, PV_TRANSFER_HLG);                                                          \
-      else HDR_FORMS(KERNEL, 1, PV_TRANSFER_HLG);                                                                        \
+      if (d.c_step == 2) RS_DISPATCH(GRID_X, lds, (d, g, fr, tone), KERNEL, 2, PV_TRANSFER_HLG);                         \
+      else RS_DISPATCH(GRID_X, lds, (d, g, fr, tone), KERNEL, 1, PV_TRANSFER_HLG);                                       \
     }                                                                                                                    \
   } while (0)
 
@@ -195,8 +183,7 @@ int hdr_run(const pv_hdr_views_desc& h, bool frames, const CheckSrc& check_src, 
   auto upright = [&](const pv_batch_views_desc& d) -> int {
     const RsItemLaunch& g = sg;
     const size_t lds = lds_s;
-    const dim3 grid((unsigned)pv_ceil_div(d.Ho, g.R), (unsigned)d.T, (unsigned)d.n_items);
-    HDR_DISPATCH(hdr_strip_kernel);
+    HDR_DISPATCH(pv_ceil_div(d.Ho, g.R), hdr_strip_kernel);
     PV_LAUNCH_CHECK();
     return PV_OK;
   };
@@ -204,8 +191,7 @@ int hdr_run(const pv_hdr_views_desc& h, bool frames, const CheckSrc& check_src, 
     const RsTileLaunch& g = tg;
     const size_t lds = lds_t;
     if (g.TR <= 0 || g.TC <= 0 || g.tiles_x <= 0) return PV_ERR_INVALID;   // not sized: no oriented item was announced
-    const dim3 grid((unsigned)(pv_ceil_div(d.Ho, g.TR) * g.tiles_x), (unsigned)d.T, (unsigned)d.n_items);
-    HDR_DISPATCH(hdr_tile_kernel);
+    HDR_DISPATCH(pv_ceil_div(d.Ho, g.TR) * g.tiles_x, hdr_tile_kernel);
     PV_LAUNCH_CHECK();
     return PV_OK;
   };
@@ -219,13 +205,7 @@ extern "C" int pv_hdr_views(const pv_hdr_views_desc* hp, pv_stream_t stream) {
   const pv_frame_views_desc& f = hp->frames;
   if (!hp->tone || hp->reserved != 0) return PV_ERR_INVALID;
   if (hp->transfer != PV_TRANSFER_PQ && hp->transfer != PV_TRANSFER_HLG) return PV_ERR_INVALID;
-  if ((f.frame_ptrs == nullptr) != (f.frame_ptrs_dev == nullptr)) return PV_ERR_INVALID;   // a table only half given
-  const bool frames = f.frame_ptrs != nullptr;
-  if (!frames && f.n_frame_ptrs != 0) return PV_ERR_INVALID;
-  if (f.batch.src_layout != PV_SRC_YUV420 || f.batch.src_dtype != PV_U16) return PV_ERR_UNSUPPORTED;
-  if (frames) {
-    if (int e = fv_check_table(f)) return e;
-    return hdr_run(*hp, true, fv_check_src(f), stream);
-  }
-  return hdr_run(*hp, false, rs_check_video_src(f.batch.src_dtype), stream);
+  // a 16-bit YUV 4:2:0 source is all this entry point carries
+  return fv_with_table(f, [&](bool frames, const auto& check_src) { return hdr_run(*hp, frames, check_src, stream); },
+                       f.batch.src_layout == PV_SRC_YUV420 && f.batch.src_dtype == PV_U16);
 }

@@ -1,12 +1,16 @@
 // The kernels of oriented records (pv_view_source.orient != 0: a video stored turned and / or mirrored, include/pv_mi355x.h)
-// of pv_batch_views and pv_frame_views: the staged tiles of pv_rs.h (rs_tile_rgb, rs_tile_yuv), wrapped as pv_batch.hip and
-// pv_frames.hip wrap the strips.  blockIdx.z loads its 16-byte item, clamps source / row / view into range, loads the
-// item's record and clamps the table entry into [0, N-1] of that source; the frame is then `src` plus the entry times the
-// frame size (pv_batch_views) or, `frames` set, the entry of the record's slice of the pointer table (pv_frame_views) -- a
-// workgroup-uniform choice, so one set of 35 kernels serves both entry points.  blockIdx.x is the tile, row-major over the
-// window.  The two entry points validate and size (rs_item_launch, rs_tile_size) and call pv_orient_launch for every run of
-// oriented items; upright items never come here, and a record whose orient is 0 on the device only would still be written
-// correctly (the map of code 0 is the identity).
+// of pv_batch_views and pv_frame_views: the staged tiles of pv_rs.h (rs_tile_rgb, rs_tile_yuv).  blockIdx.z loads its item and
+// the item's record as rs_item (pv_rs.h) does; the frame is then `src` plus the entry times the frame size (pv_batch_views) or,
+// `frames` set, the entry of the record's slice of the pointer table (pv_frame_views) -- a workgroup-uniform choice, so one set
+// of 35 kernels serves both entry points.  blockIdx.x is the tile, row-major over the window.  The two entry points validate
+// and size (rs_item_launch, rs_tile_size) and call pv_orient_launch for every run of oriented items; upright items never come
+// here, and a record whose orient is 0 on the device only would still be written correctly (the map of code 0 is the identity).
+//
+// The loader and the two fills below are this file's own, not rs_item / rs_item_rgb / rs_item_yuv: they make the choice
+// between the two kinds of source with selects after one conditional load, where rs_item branches once.  Behind the shared
+// loader all 35 kernels come out with other code -- a shorter prologue, but another register allocation throughout, up to 4
+// VGPRs fewer in six of the YUV kernels and up to 4 more in four (profiles/r24/isa_vs_parent.md) -- and a change of that
+// size is not taken without measuring it on the device.
 #include "pv_rs.h"
 
 namespace {
@@ -25,7 +29,7 @@ __device__ __forceinline__ OvItem ov_item(const pv_batch_views_desc& d, int fram
   r.ts = min(max(d.t_index[(long)row * d.t_stride + t], 0), r.S->N - 1);
   r.orient = r.S->orient & 7;
   r.frame = 0;
-  if (frames) {   // read as constant memory: one scalar load (pv_frames.h)
+  if (frames) {   // read as constant memory: one scalar load (rs_item, pv_rs.h)
     typedef const uint64_t __attribute__((address_space(4))) * table_ptr;
     r.frame = (uintptr_t) reinterpret_cast<table_ptr>(reinterpret_cast<uintptr_t>(r.S->src))[r.ts];
   }
@@ -71,41 +75,16 @@ __global__ __launch_bounds__(kRsThreads) void orient_yuv_kernel(const pv_batch_v
   rs_tile_yuv<CSTEP, FORM, D, SMP>(oy_lds, g, s, item.orient, rs_dst(d, 3), d.yuv2rgb, zi, t);
 }
 
-// RS_DISPATCH over a grid of tiles x d.T frames x d.n_items destination items, with the `frames` flag behind the sizing.
-#define OV_DISPATCH(KERNEL, ...)                                                                                         \
-  do {                                                                                                                   \
-    const dim3 grid((unsigned)(pv_ceil_div(d.Ho, g.TR) * g.tiles_x), (unsigned)d.T, (unsigned)d.n_items), block(kRsThreads); \
-    hipStream_t s = static_cast<hipStream_t>(stream);                                                                    \
-    if (d.dst_layout == PV_DST_NCTHW) {                                                                                  \
-      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, bf16_t>), grid, block, lds, s, d, g, fr);    \
-      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, float>), grid, block, lds, s, d, g, fr);                            \
-    } else if (d.c_p == 4) {                                                                                             \
-      PV_LAUNCH((KERNEL<__VA_ARGS__, RS_C4, bf16_t>), grid, block, lds, s, d, g, fr);                                    \
-    } else {                                                                                                             \
-      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, bf16_t>), grid, block, lds, s, d, g, fr);        \
-      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, float>), grid, block, lds, s, d, g, fr);                                \
-    }                                                                                                                    \
-  } while (0)
+#define OV_TILES(KERNEL, ...) RS_DISPATCH(pv_ceil_div(d.Ho, g.TR) * g.tiles_x, lds, (d, g, fr), KERNEL, __VA_ARGS__)
+#define OV_RGB(S, INTER) OV_TILES(orient_views_kernel, S, INTER)
+#define OV_YUV(CSTEP, SMP) OV_TILES(orient_yuv_kernel, CSTEP, SMP)
 
 }  // namespace
 
 int pv_orient_launch(const pv_batch_views_desc& d, bool frames, const RsTileLaunch& g, size_t lds, pv_stream_t stream) {
   const int fr = frames ? 1 : 0;
   if (g.TR <= 0 || g.TC <= 0 || g.tiles_x <= 0) return PV_ERR_INVALID;   // not sized: no oriented item was announced
-  const bool yuv = d.src_layout == PV_SRC_YUV420;
-  if (yuv && d.src_dtype == PV_U16) {
-    if (d.c_step == 2) OV_DISPATCH(orient_yuv_kernel, 2, unsigned short);
-    else OV_DISPATCH(orient_yuv_kernel, 1, unsigned short);
-  } else if (yuv) {
-    if (d.c_step == 2) OV_DISPATCH(orient_yuv_kernel, 2, unsigned char);
-    else OV_DISPATCH(orient_yuv_kernel, 1, unsigned char);
-  } else if (d.src_layout == PV_SRC_NTHWC) {
-    OV_DISPATCH(orient_views_kernel, unsigned char, true);
-  } else if (d.src_dtype == PV_U8) {
-    OV_DISPATCH(orient_views_kernel, unsigned char, false);
-  } else {
-    OV_DISPATCH(orient_views_kernel, float, false);
-  }
+  RS_SOURCE_FORMS(OV_RGB, OV_YUV);
   PV_LAUNCH_CHECK();
   return PV_OK;
 }

@@ -14,7 +14,8 @@
 //                  leaves every other kernel of the ingest with the instructions it had.
 // Hence an item's frame holds the bits pv_batch_views writes for a dense copy of the rectangle with Hn = Ho, Wn = Wo.
 //
-// One item loader serves whole videos and frame lists (`frames` is workgroup-uniform, as in pv_hdr.hip).  The launch is sized
+// The item loader of pv_rs.h serves whole videos and frame lists (`frames` is workgroup-uniform, as in pv_area.hip), and the
+// geometry is the builders' with what the rectangle changes written over it.  The launch is sized
 // as rs_item_launch sizes one: the pitch from the widest rectangle over the launch's items x T frames, read from the host copy
 // of the regions, R from the LDS budget; a workgroup whose span exceeds the pitch -- a device copy that is not the validated
 // one -- stages nothing and writes nothing.  Each strip decides dense / sparse staging for itself; a tube is usually
@@ -24,32 +25,18 @@
 
 namespace {
 
-// The item of this workgroup, clamped into range before anything is addressed through it (pv_hdr.hip's loader), and the
-// rectangle of (row, t) clamped into the stored frame: top / left inside it, h / w at least 1 and ending inside it.
-struct RgItem {
-  const pv_view_source* __restrict__ S;
-  uintptr_t src;        // the video, or -- frame lists -- the selected frame
-  int ts;               // the selected frame of the video; frame lists: 0
+// The shared item with what is this entry point's own on top: the rectangle of the item's (row, t), clamped into the stored
+// frame before any address is formed -- top / left inside it, h / w at least 1 and ending inside it -- and its sy / sx.
+// (One function, the loader's call inside it: with the rectangle read by a function of its own behind the loader, its loads
+// are ordered otherwise and every kernel of this file changes -- profiles/r24/isa_vs_parent.md.)
+struct RgItem : RsItem {
   int top, left, h, w;
   float sy, sx;
 };
 __device__ __forceinline__ RgItem rg_item(const pv_batch_views_desc& d, const pv_view_region* __restrict__ regions, int frames, int zi,
                                           int t) {
-  const pv_view_item* __restrict__ it = d.items_dev + zi;
-  RgItem r;
-  r.S = d.sources_dev + min(max(it->source, 0), d.n_sources - 1);
-  const int row = min(max(it->row, 0), d.n_rows - 1);
-  const long at = (long)row * d.t_stride + t;
-  const int ts = min(max(d.t_index[at], 0), r.S->N - 1);
-  if (frames) {   // read as constant memory: one scalar load (pv_frames.h)
-    typedef const uint64_t __attribute__((address_space(4))) * table_ptr;
-    r.src = (uintptr_t) reinterpret_cast<table_ptr>(reinterpret_cast<uintptr_t>(r.S->src))[ts];
-    r.ts = 0;
-  } else {
-    r.src = reinterpret_cast<uintptr_t>(r.S->src);
-    r.ts = ts;
-  }
-  const pv_view_region* __restrict__ G = regions + at;
+  RgItem r{rs_item<RS_EITHER>(d, zi, t, frames)};
+  const pv_view_region* __restrict__ G = regions + r.at;
   const int Hs = r.S->Hs, Ws = r.S->Ws;
   r.top = min(max(G->top, 0), Hs - 1), r.left = min(max(G->left, 0), Ws - 1);
   r.h = min(max(G->h, 1), Hs - r.top), r.w = min(max(G->w, 1), Ws - r.left);
@@ -66,14 +53,12 @@ __global__ __launch_bounds__(kRsThreads) void region_views_kernel(const pv_batch
   const int zi = blockIdx.z;                       // destination item of this launch
   const RgItem item = rg_item(d, regions, frames, zi, t);
   RsRgbWin s;
-  s.src = item.src;
-  s.Hs = item.h, s.Ws = item.w, s.N = frames ? 1 : item.S->N;   // a frame of a list is dense [C, Hs, Ws]: the plane stride of ONE frame
+  static_cast<RsRgbSrc&>(s) = rs_item_rgb(item);
+  s.Hf = s.Hs, s.Wf = s.Ws;                        // the stored frame keeps the strides; the body's source is the rectangle
+  s.top = item.top, s.left = item.left;
+  s.Hs = item.h, s.Ws = item.w;
   s.sy = item.sy, s.sx = item.sx;
   s.yoff = 0, s.xoff = 0;
-  s.ts = item.ts;
-  s.clip_frame0 = 0;
-  s.Hf = item.S->Hs, s.Wf = item.S->Ws;
-  s.top = item.top, s.left = item.left;
   rs_strip_rgb<S, INTER, FORM, D>(rg_lds, g.R, g.pitch, s, rs_dst(d, d.C), zi, t, true);
 }
 
@@ -86,38 +71,22 @@ __global__ __launch_bounds__(kRsThreads) void region_yuv_kernel(const pv_batch_v
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
   const RgItem item = rg_item(d, regions, frames, zi, t);
-  const pv_view_source* __restrict__ V = item.S;
-  RsYuvSrc s;
-  s.src = item.src;
+  RsYuvSrc s = rs_item_yuv<CSTEP>(item);
   s.Hs = item.h, s.Ws = item.w;
   s.sy = item.sy, s.sx = item.sx;
   s.yoff = 0, s.xoff = 0;
-  s.y_pitch = V->y_pitch, s.c_pitch = V->c_pitch;
-  rs_chroma_planes(CSTEP == 2, V->u_offset, V->v_offset, s);
   // the rectangle's origin, folded in: luma into the frame offset, and the chroma planes -- addressed from the same frame
   // offset -- by what their origin differs from it
   const long luma0 = (long)item.top * s.y_pitch + (long)item.left * SB;
   const long chroma0 = (long)(item.top >> 1) * s.c_pitch + (long)(item.left >> 1) * CB;
-  s.frame_off = (long)item.ts * V->frame_stride + luma0;
+  s.frame_off += luma0;
   s.c_off_a += chroma0 - luma0, s.c_off_b += chroma0 - luma0;
   rs_strip_yuv<CSTEP, FORM, D, SMP>(ry_lds, g.R, g.pitch, g.pitch_c, g.c_base, s, rs_dst(d, 3), d.yuv2rgb, zi, t, true);
 }
 
-// RS_DISPATCH with the two further kernel arguments; expects d, g, lds, stream, fr and regions in scope.
-#define RG_DISPATCH(KERNEL, ...)                                                                                         \
-  do {                                                                                                                   \
-    const dim3 grid((unsigned)pv_ceil_div(d.Ho, g.R), (unsigned)d.T, (unsigned)d.n_items), block(kRsThreads);            \
-    hipStream_t s = static_cast<hipStream_t>(stream);                                                                    \
-    if (d.dst_layout == PV_DST_NCTHW) {                                                                                  \
-      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, bf16_t>), grid, block, lds, s, d, g, fr, regions); \
-      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, float>), grid, block, lds, s, d, g, fr, regions);                   \
-    } else if (d.c_p == 4) {                                                                                             \
-      PV_LAUNCH((KERNEL<__VA_ARGS__, RS_C4, bf16_t>), grid, block, lds, s, d, g, fr, regions);                           \
-    } else {                                                                                                             \
-      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, bf16_t>), grid, block, lds, s, d, g, fr, regions); \
-      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, float>), grid, block, lds, s, d, g, fr, regions);                       \
-    }                                                                                                                    \
-  } while (0)
+#define RG_STRIPS(KERNEL, ...) RS_DISPATCH(pv_ceil_div(d.Ho, g.R), lds, (d, g, fr, regions), KERNEL, __VA_ARGS__)
+#define RG_RGB(S, INTER) RG_STRIPS(region_views_kernel, S, INTER)
+#define RG_YUV(CSTEP, SMP) RG_STRIPS(region_yuv_kernel, CSTEP, SMP)
 
 // One rectangle against the frame of the item's source and the launch's window.
 inline int rg_check_region(const pv_view_region& r, const pv_view_source& v, int Ho, int Wo, bool yuv) {
@@ -129,52 +98,38 @@ inline int rg_check_region(const pv_view_region& r, const pv_view_source& v, int
   return PV_OK;
 }
 
-// The descriptor as the wrapped entry point checks it (rs_check_item_desc), one view, then every item: its range, the stored
-// frames of its record (rs_check_record_frames with the entry point's check of `src`; the record's view geometry is not read)
-// and the rectangles of its row against that record.  The widest column span over every (item, t) -- computed with the very
-// calls the kernel makes -- sizes the staged rows; R and the LDS bytes follow as in rs_item_launch (rs_strip_size).
+// The descriptor as the wrapped entry point checks it (rs_check_item_desc), one view, then every item (rs_walk_items): its
+// range, the stored frames of its record (rs_check_record_frames with the entry point's check of `src`; the record's view
+// geometry is not read) and the rectangles of its row against that record.  The widest column span over every (item, t) --
+// computed with the very calls the kernel makes -- sizes the staged rows; R and the LDS bytes follow as in rs_item_launch
+// (rs_strip_size).
 template <typename CheckSrc>
 int rg_run(const pv_region_views_desc& r, bool frames, const CheckSrc& check_src, pv_stream_t stream) {
   const pv_batch_views_desc& d = r.frames.batch;
   if (int e = rs_check_item_desc(d)) return e;
-  if (d.n_views != 1) return PV_ERR_INVALID;
+  if (d.n_views != 1) return PV_ERR_INVALID;       // so the walk accepts view 0 only
   const bool yuv = d.src_layout == PV_SRC_YUV420;
   int span = 0, span_c = 0;
   bool oriented = false;
   const int32_t origin = 0;
-  for (int i = 0; i < d.n_items; ++i) {
-    const pv_view_item& it = d.items[i];
-    if (it.source < 0 || it.source >= d.n_sources || it.row < 0 || it.row >= d.n_rows || it.view != 0) return PV_ERR_INVALID;
-    const pv_view_source& v = d.sources[it.source];
-    const bool again = i > 0 && it.source == d.items[i - 1].source;   // a video-major sequence names the record just checked
-    if (!again)
-      if (int e = rs_check_record_frames(d, v, yuv, check_src)) return e;
+  const auto check = [&](const pv_view_source& v) { return rs_check_record_frames(d, v, yuv, check_src); };
+  const auto each = [&](const pv_view_item& it, const pv_view_source& v, bool) -> int {
     oriented |= v.orient != 0;
     const pv_view_region* row = r.regions + (long)it.row * d.t_stride;
     for (int t = 0; t < d.T; ++t) {
       if (int e = rg_check_region(row[t], v, d.Ho, d.Wo, yuv)) return e;
       rs_widest_span(row[t].sx, &origin, 1, d.Wo, row[t].w, span, span_c);
     }
-  }
+    return PV_OK;
+  };
+  if (int e = rs_walk_items(d, check, each)) return e;
   if (oriented) return PV_ERR_UNSUPPORTED;
   RsItemLaunch g = {};
   size_t lds = 0;
   if (int e = rs_strip_size(d, span, span_c, g, lds)) return e;
   const int fr = frames ? 1 : 0;
   const pv_view_region* regions = r.regions_dev;
-  if (yuv && d.src_dtype == PV_U16) {
-    if (d.c_step == 2) RG_DISPATCH(region_yuv_kernel, 2, unsigned short);
-    else RG_DISPATCH(region_yuv_kernel, 1, unsigned short);
-  } else if (yuv) {
-    if (d.c_step == 2) RG_DISPATCH(region_yuv_kernel, 2, unsigned char);
-    else RG_DISPATCH(region_yuv_kernel, 1, unsigned char);
-  } else if (d.src_layout == PV_SRC_NTHWC) {
-    RG_DISPATCH(region_views_kernel, unsigned char, true);
-  } else if (d.src_dtype == PV_U8) {
-    RG_DISPATCH(region_views_kernel, unsigned char, false);
-  } else {
-    RG_DISPATCH(region_views_kernel, float, false);
-  }
+  RS_SOURCE_FORMS(RG_RGB, RG_YUV);
   PV_LAUNCH_CHECK();
   return PV_OK;
 }
@@ -183,14 +138,6 @@ int rg_run(const pv_region_views_desc& r, bool frames, const CheckSrc& check_src
 
 extern "C" int pv_region_views(const pv_region_views_desc* rp, pv_stream_t stream) {
   if (!rp) return PV_ERR_INVALID;
-  const pv_frame_views_desc& f = rp->frames;
   if (!rp->regions || !rp->regions_dev || reinterpret_cast<uintptr_t>(rp->regions_dev) % 4) return PV_ERR_INVALID;
-  if ((f.frame_ptrs == nullptr) != (f.frame_ptrs_dev == nullptr)) return PV_ERR_INVALID;   // a table only half given
-  const bool frames = f.frame_ptrs != nullptr;
-  if (!frames && f.n_frame_ptrs != 0) return PV_ERR_INVALID;
-  if (frames) {
-    if (int e = fv_check_table(f)) return e;
-    return rg_run(*rp, true, fv_check_src(f), stream);
-  }
-  return rg_run(*rp, false, rs_check_video_src(f.batch.src_dtype), stream);
+  return fv_with_table(rp->frames, [&](bool frames, const auto& check_src) { return rg_run(*rp, frames, check_src, stream); });
 }

@@ -69,12 +69,13 @@ int rs_run(pv_resample_desc d, bool one_video, int tab_stride, pv_stream_t strea
   const bool inter = d.src_layout == PV_SRC_NTHWC;
   int span = 0, span_c = 0;
   rs_widest_span(g.sx, d.x_off, d.n_views, d.Wo, d.Ws, span, span_c);
-  g.pitch = pv_round_up(span * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
+  g.pitch = rs_rgb_pitch(span, d.src_layout, d.src_dtype);
   size_t lds;
   if (int e = rs_strip_rows(2L * (inter ? 1 : d.C) * g.pitch, d.Ho, g.R, lds)) return e;   // two source rows per output row
-  if (inter) RS_DISPATCH(resample_crop_kernel, unsigned char, true);
-  else if (d.src_dtype == PV_U8) RS_DISPATCH(resample_crop_kernel, unsigned char, false);
-  else RS_DISPATCH(resample_crop_kernel, float, false);
+#define RC_STRIPS(S, INTER) RS_DISPATCH(pv_ceil_div(d.Ho, g.R), lds, (d, g), resample_crop_kernel, S, INTER)
+  if (inter) RC_STRIPS(unsigned char, true);
+  else if (d.src_dtype == PV_U8) RC_STRIPS(unsigned char, false);
+  else RC_STRIPS(float, false);
   PV_LAUNCH_CHECK();
   return PV_OK;
 }

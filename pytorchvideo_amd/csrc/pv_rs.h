@@ -1,28 +1,30 @@
-// The resampling ingest: six entry points in five translation units.
+// The resampling ingest: ten entry points in nine translation units.
 //   pv_resample.hip   pv_resample_crop, pv_video_views    RGB / planar sources, one source per launch
 //   pv_yuv.hip        pv_yuv_views, pv_yuv16_views        YUV 4:2:0 sources of 8- / 16-bit samples, one source per launch
 //   pv_batch.hip      pv_batch_views                      either, one source per destination item
 //   pv_frames.hip     pv_frame_views                      the same with every frame addressed through a pointer table
 //   pv_frames16.hip   (launched from pv_frames.hip)       the 16-bit YUV kernels of pv_frame_views
 //   pv_orient.hip     (launched from pv_batch.hip and pv_frames.hip)   the tile kernels of oriented records (orient != 0)
-//   pv_hdr.hip        pv_hdr_views (a seventh entry point)             pv_batch_views / pv_frame_views on 16-bit YUV with the PQ / HLG
-//                                                                       tap map: its own strip and tile kernel wrappers
-//   pv_region.hip     pv_region_views (an eighth)                      a rectangle of the frame per destination frame, resized to
-//                                                                       the window: its own strip kernel wrappers
-//   pv_area.hip       pv_area_views (a ninth)                          pv_batch_views / pv_frame_views with a box filter (the windows of
-//                                                                       interpolate(mode="area")) in place of the blend: a staged-tile body
-//                                                                       of its own (a window's rows are not two), the shared pieces from here
+//   pv_hdr.hip        pv_hdr_views      pv_batch_views / pv_frame_views on 16-bit YUV with the PQ / HLG tap map
+//   pv_region.hip     pv_region_views   a rectangle of the frame per destination frame, resized to the window
+//   pv_area.hip       pv_area_views     a box filter (the windows of interpolate(mode="area")) in place of the blend: a staged-tile
+//                                       body of its own (a window's rows are not two)
 // What they compute with is here, once: the pinned source coordinate, the destination forms with their stores, the taps and
-// blends, the two staged-strip bodies (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather) that the nine kernel templates
-// wrap (resample_crop_kernel; yuv_views_kernel, yuv16_views_kernel; batch_views_kernel, batch_yuv_kernel,
-// batch_yuv16_kernel; frame_views_kernel, frame_yuv_kernel; frame_yuv16_kernel), the launch arithmetic (widest span, rows
-// per strip, destination-form dispatch), the host-side checks of views, item range, destination and YUV planes, and the
-// whole validation and sizing of an item-sourced launch (rs_item_launch).  rs_strip_yuv takes the sample type: bytes, or the
-// 16-bit codes of P010 / yuv420p10le (PV_U16 sources).  The files keep what differs: where a workgroup's geometry comes
-// from (the kernel wrappers), the validation of the one-source descriptors (rs_run, yuv_run) and, for the item-sourced two,
-// what a record's `src` must be.
-// Records with orient != 0 -- a video stored turned and / or mirrored -- have two bodies of their own, the staged tiles
-// (rs_tile_rgb, rs_tile_yuv), sized by rs_tile_size; rs_item_runs hands every run of items of one kind to its kernels.
+// blends, the two staged-strip bodies (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather) and the two staged-tile bodies of
+// oriented records (rs_tile_rgb, rs_tile_yuv), the launch arithmetic (widest span, rows per strip, the LDS layout of a staged
+// tile), the host-side checks of views, item range, destination and YUV planes, and the validation and sizing of an
+// item-sourced launch (rs_item_launch).
+// Around the bodies, every item-sourced kernel and entry point is made of the same pieces, each of them here once as well:
+//   device  rs_item            the item of a workgroup: record, view, orientation and the selected frame, everything clamped
+//           rs_item_rgb / rs_item_yuv   the geometry a body takes (RsRgbSrc / RsYuvSrc), filled from an item
+//   host    RS_DISPATCH        the destination-form dispatch, grid and kernel arguments as parameters
+//           RS_SOURCE_FORMS    the source-form dispatch in front of it
+//           rs_walk_items      the walk over a launch's items: range, the record behind each, checked once per run
+//           (fv_with_table, pv_frames.h: the optional pointer table in front of an entry point)
+// The files keep what differs: the kernel wrappers (a __global__ function per body and source kind, two or three lines), what
+// a rectangle or a tap map changes of the geometry, the validation of the one-source descriptors (rs_run, yuv_run), whose
+// kernels fill the geometry from a by-value descriptor instead of a record, and the sizing that is an entry point's own.
+// (Two device loaders are still apart, OvItem of pv_orient.hip and HdrItem of pv_hdr.hip: see rs_item.)
 // Everything but RsItemLaunch, RsTileLaunch and pv_orient_launch is inline in an anonymous namespace: each translation unit
 // keeps its own kernels.
 #pragma once
@@ -813,6 +815,78 @@ __device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaun
   }
 }
 
+// ---- the item of a workgroup -------------------------------------------------------------------------------------------
+// Every item-sourced kernel starts the same way: blockIdx.z loads its 16-byte item, clamps source / row / view into range
+// before anything is addressed through them, loads the item's record and clamps the entry of its table row into [0, N-1] of
+// that source, so a malformed item or table can never read outside the item's source.  Everything is uniform over the
+// workgroup, so these are scalar loads; the record is read field by field through a pointer (a by-value copy indexed at run
+// time would be scratch).  The selected frame is (src, ts): the video and the entry (whole videos), or the frame itself and 0
+// (frame lists: `src` of a record is a slice of a device table of frame addresses, and the entry picks one).
+// There `src` is a generic pointer loaded from memory: read through it the table entry would be a per-lane flat load.  The
+// table is global memory that nothing writes while the kernel runs, so it is read as constant memory: one scalar load.
+// KIND says which of the two a launch has: known at compile time (pv_batch.hip, pv_frames*.hip, whose kernels then hold no
+// trace of the other kind) or asked of the workgroup-uniform kernel argument `frames`, so that one set of kernels serves both
+// (pv_region.hip, pv_area.hip).  pv_orient.hip and pv_hdr.hip still carry a loader of their own that takes the same steps:
+// behind this one their kernels come out with other code, and each file says what moves.
+enum { RS_VIDEOS = 0, RS_FRAMES = 1, RS_EITHER = 2 };
+struct RsItem {
+  const pv_view_source* __restrict__ S;
+  int view, orient;
+  long at;              // where (row, t) lies in the frame table -- and in whatever else a launch keeps per (row, t)
+  uintptr_t src;        // the video, or -- frame lists -- the selected frame
+  int ts;               // the selected frame of the video, clamped; frame lists: 0
+  bool list;            // `src` is a frame of a list
+};
+template <int KIND> __device__ __forceinline__ RsItem rs_item(const pv_batch_views_desc& d, int zi, int t, int frames = 0) {
+  const pv_view_item* __restrict__ it = d.items_dev + zi;
+  RsItem r;
+  r.S = d.sources_dev + min(max(it->source, 0), d.n_sources - 1);
+  r.view = min(max(it->view, 0), d.n_views - 1);
+  r.orient = r.S->orient & 7;
+  const int row = min(max(it->row, 0), d.n_rows - 1);
+  r.at = (long)row * d.t_stride + t;
+  const int ts = min(max(d.t_index[r.at], 0), r.S->N - 1);
+  r.list = KIND == RS_FRAMES || (KIND == RS_EITHER && frames);
+  if (r.list) {
+    typedef const uint64_t __attribute__((address_space(4))) * table_ptr;
+    r.src = (uintptr_t) reinterpret_cast<table_ptr>(reinterpret_cast<uintptr_t>(r.S->src))[ts];
+    r.ts = 0;
+  } else {
+    r.src = reinterpret_cast<uintptr_t>(r.S->src);
+    r.ts = ts;
+  }
+  return r;
+}
+
+// The geometry a body takes, from an item's record: the stored frame, the scale, the item's window (selected, not indexed)
+// and the selected frame.  Which byte of an interleaved pair is U / V, and where the staged chroma plane(s) start inside a
+// frame, follow from the record's offsets.
+__device__ __forceinline__ RsRgbSrc rs_item_rgb(const RsItem& item) {
+  const pv_view_source* __restrict__ V = item.S;
+  RsRgbSrc s;
+  s.src = item.src;
+  s.Hs = V->Hs, s.Ws = V->Ws, s.N = item.list ? 1 : V->N;   // a frame of a list is dense [C, Hs, Ws]: the plane stride of ONE frame
+  s.sy = V->sy, s.sx = V->sx;
+  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
+  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
+  s.ts = item.ts;
+  s.clip_frame0 = 0;
+  return s;
+}
+template <int CSTEP> __device__ __forceinline__ RsYuvSrc rs_item_yuv(const RsItem& item) {
+  const pv_view_source* __restrict__ V = item.S;
+  RsYuvSrc s;
+  s.src = item.src;
+  s.frame_off = (long)item.ts * V->frame_stride;
+  s.Hs = V->Hs, s.Ws = V->Ws;
+  s.sy = V->sy, s.sx = V->sx;
+  s.yoff = rs_view_off(item.view, V->y_off[0], V->y_off[1], V->y_off[2]);
+  s.xoff = rs_view_off(item.view, V->x_off[0], V->x_off[1], V->x_off[2]);
+  s.y_pitch = V->y_pitch, s.c_pitch = V->c_pitch;
+  rs_chroma_planes(CSTEP == 2, V->u_offset, V->v_offset, s);
+  return s;
+}
+
 // ---- the launch arithmetic shared by the entry points ---------------------------------------------------------------
 // Folds the widest source column span of a record's views into `span`, and the chroma span behind it into `span_c`, both in
 // columns: times the bytes of a column (rs_yuv_pitches for YUV) they size the staged rows.
@@ -848,20 +922,61 @@ inline int rs_strip_rows(long per_row, int Ho, int32_t& R_out, size_t& lds) {
   return PV_OK;
 }
 
-// The destination-form dispatch: KERNEL<leading template arguments..., FORM, D>(d, g) over a grid of strips x d.T frames x
-// d.n_items destination items; expects d, g (g.R set), lds and stream in scope.
-#define RS_DISPATCH(KERNEL, ...)                                                                                         \
+// The LDS pitch of a staged RGB / planar (row, plane) for the widest span (columns) of a launch.
+inline int32_t rs_rgb_pitch(int span, int src_layout, int src_dtype) {
+  return pv_round_up(span * (src_layout == PV_SRC_NTHWC ? 3 : (src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
+}
+
+// The LDS layout of a staged tile (RsTileLaunch, or a launch struct with the same fields: pv_area.hip) whose widest footprint
+// is n = {rows, columns, chroma rows, chroma columns}: every staged row of every plane at its pitch, for YUV the chroma image
+// behind the luma one.  Returns the bytes, not yet narrowed to 32 bits.
+template <typename Launch> inline long rs_tile_layout(const pv_batch_views_desc& d, const int (&n)[4], Launch& g) {
+  g.rows = n[0], g.rows_c = n[2];
+  if (d.src_layout == PV_SRC_YUV420) {
+    rs_yuv_pitches(n[1], n[3], d.c_step, d.src_dtype == PV_U16 ? 2 : 1, g.pitch, g.pitch_c);
+    g.c_base = g.rows * g.pitch;
+    return (long)g.c_base + (long)g.rows_c * (d.c_step == 2 ? 1 : 2) * g.pitch_c;
+  }
+  g.pitch = rs_rgb_pitch(n[1], d.src_layout, d.src_dtype);
+  return (long)g.rows * (d.src_layout == PV_SRC_NTHWC ? 1 : d.C) * g.pitch;
+}
+
+// The destination-form dispatch: KERNEL<leading template arguments..., FORM, D>ARGS over a grid of GRID_X workgroups (strips,
+// or tiles) x d.T frames x d.n_items destination items with LDS bytes of staging.  ARGS is the kernel's argument list in
+// parentheses; expects d (the descriptor the destination is read from) and stream in scope.
+#define RS_ARGS(...) __VA_ARGS__
+#define RS_DISPATCH(GRID_X, LDS, ARGS, KERNEL, ...)                                                                      \
   do {                                                                                                                   \
-    const dim3 grid((unsigned)pv_ceil_div(d.Ho, g.R), (unsigned)d.T, (unsigned)d.n_items), block(kRsThreads);            \
+    const dim3 grid((unsigned)(GRID_X), (unsigned)d.T, (unsigned)d.n_items), block(kRsThreads);                          \
     hipStream_t s = static_cast<hipStream_t>(stream);                                                                    \
     if (d.dst_layout == PV_DST_NCTHW) {                                                                                  \
-      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, bf16_t>), grid, block, lds, s, d, g);        \
-      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, float>), grid, block, lds, s, d, g);                                \
+      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, bf16_t>), grid, block, LDS, s, RS_ARGS ARGS); \
+      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_PLANAR, float>), grid, block, LDS, s, RS_ARGS ARGS);                        \
     } else if (d.c_p == 4) {                                                                                             \
-      PV_LAUNCH((KERNEL<__VA_ARGS__, RS_C4, bf16_t>), grid, block, lds, s, d, g);                                        \
+      PV_LAUNCH((KERNEL<__VA_ARGS__, RS_C4, bf16_t>), grid, block, LDS, s, RS_ARGS ARGS);                                \
     } else {                                                                                                             \
-      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, bf16_t>), grid, block, lds, s, d, g);            \
-      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, float>), grid, block, lds, s, d, g);                                    \
+      if (d.dst_dtype == PV_BF16) PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, bf16_t>), grid, block, LDS, s, RS_ARGS ARGS);    \
+      else PV_LAUNCH((KERNEL<__VA_ARGS__, RS_CL, float>), grid, block, LDS, s, RS_ARGS ARGS);                            \
+    }                                                                                                                    \
+  } while (0)
+
+// The source-form dispatch of an item-sourced launch in front of it: YUV(CSTEP, SMP) for YUV 4:2:0 -- two-byte or one-byte
+// samples, one interleaved chroma plane or two -- else RGB(S, INTER) for [T, H, W, 3] bytes and for planar bytes / fp32.
+// RGB and YUV are the unit's own macros, as a rule one RS_DISPATCH each; expects d in scope.
+#define RS_SOURCE_FORMS(RGB, YUV)                                                                                        \
+  do {                                                                                                                   \
+    if (d.src_layout == PV_SRC_YUV420 && d.src_dtype == PV_U16) {                                                        \
+      if (d.c_step == 2) YUV(2, unsigned short);                                                                         \
+      else YUV(1, unsigned short);                                                                                       \
+    } else if (d.src_layout == PV_SRC_YUV420) {                                                                          \
+      if (d.c_step == 2) YUV(2, unsigned char);                                                                          \
+      else YUV(1, unsigned char);                                                                                        \
+    } else if (d.src_layout == PV_SRC_NTHWC) {                                                                           \
+      RGB(unsigned char, true);                                                                                          \
+    } else if (d.src_dtype == PV_U8) {                                                                                   \
+      RGB(unsigned char, false);                                                                                         \
+    } else {                                                                                                             \
+      RGB(float, false);                                                                                                 \
     }                                                                                                                    \
   } while (0)
 
@@ -969,12 +1084,6 @@ inline int rs_check_record(const pv_batch_views_desc& d, const pv_view_source& v
   return PV_OK;
 }
 
-// The descriptor, the items and the record behind each of them, then R, the LDS pitch(es) and the LDS bytes of the launch.
-// check_src(record) is the entry point's own part: whether the record's `src` is a source of d.src_dtype (PV_ERR_INVALID if
-// not).  A launch is a window of a longer sequence and reads only the records its items name (the kernel clamps `source`
-// into range and the items are the validated ones), so its cost does not grow with the number of videos of the whole
-// sequence; a video-major sequence names the record just checked, which is not checked again, and any other record named
-// again is, which is cheaper than remembering.  The widest column span(s) of any such record x view size the staged rows.
 // The widest stored footprint of a TR x TC tile of oriented record v over its views: stored rows x columns, and the chroma
 // rows x columns behind them.  The map takes displayed rows to one stored axis and displayed columns to the other, so the
 // bands of tile rows and of tile columns are walked separately, with the very calls the kernel makes.
@@ -1009,24 +1118,13 @@ inline void rs_tile_footprint(const pv_view_source& v, int n_views, int Ho, int 
 inline int rs_tile_size(const pv_batch_views_desc& d, const pv_view_source* const* records, size_t n_records, RsTileLaunch& g,
                         size_t& lds) {
   static const int tiles[][2] = {{32, 32}, {16, 32}, {16, 16}, {8, 16}, {8, 8}, {4, 8}, {2, 8}, {1, 8}};
-  const bool yuv = d.src_layout == PV_SRC_YUV420, inter = d.src_layout == PV_SRC_NTHWC;
-  const int sb = d.src_dtype == PV_U16 ? 2 : 1;
   for (size_t k = 0; k < sizeof(tiles) / sizeof(tiles[0]); ++k) {
     const int TR = tiles[k][0], TC = tiles[k][1];
     int n[4] = {0, 0, 0, 0};
     for (size_t i = 0; i < n_records; ++i) rs_tile_footprint(*records[i], d.n_views, d.Ho, d.Wo, TR, TC, n);
     g = {};
     g.TR = TR, g.TC = TC, g.tiles_x = (int32_t)pv_ceil_div(d.Wo, TC);
-    g.rows = n[0], g.rows_c = n[2];
-    long bytes;
-    if (yuv) {
-      rs_yuv_pitches(n[1], n[3], d.c_step, sb, g.pitch, g.pitch_c);
-      g.c_base = g.rows * g.pitch;
-      bytes = (long)g.c_base + (long)g.rows_c * (d.c_step == 2 ? 1 : 2) * g.pitch_c;
-    } else {
-      g.pitch = pv_round_up(n[1] * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
-      bytes = (long)g.rows * (inter ? 1 : d.C) * g.pitch;
-    }
+    const long bytes = rs_tile_layout(d, n, g);
     lds = (size_t)bytes;
     if (bytes <= kRsLdsBudget) return PV_OK;
     if (k + 1 == sizeof(tiles) / sizeof(tiles[0])) return bytes <= kRsLdsMax ? PV_OK : PV_ERR_UNSUPPORTED;
@@ -1052,21 +1150,44 @@ inline int rs_check_item_desc(const pv_batch_views_desc& d) {
 
 // R, the LDS pitch(es) and the LDS bytes of a strip launch whose widest column span is `span` (chroma: `span_c`).
 inline int rs_strip_size(const pv_batch_views_desc& d, int span, int span_c, RsItemLaunch& g, size_t& lds) {
-  const bool yuv = d.src_layout == PV_SRC_YUV420, inter = d.src_layout == PV_SRC_NTHWC;
   long per_row;                                    // LDS bytes of the two source rows of one output row
-  if (yuv) {
+  if (d.src_layout == PV_SRC_YUV420) {
     per_row = rs_yuv_pitches(span, span_c, d.c_step, d.src_dtype == PV_U16 ? 2 : 1, g.pitch, g.pitch_c);
   } else {
-    g.pitch = pv_round_up(span * (inter ? 3 : (d.src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
-    per_row = 2L * (inter ? 1 : d.C) * g.pitch;
+    g.pitch = rs_rgb_pitch(span, d.src_layout, d.src_dtype);
+    per_row = 2L * (d.src_layout == PV_SRC_NTHWC ? 1 : d.C) * g.pitch;
   }
   if (int e = rs_strip_rows(per_row, d.Ho, g.R, lds)) return e;
   g.c_base = 2 * g.R * g.pitch;
   return PV_OK;
 }
 
-// Items of upright records (orient == 0) run the staged strip, items of oriented records the staged tile: g / lds size the
-// first kind exactly as before (g.R == 0: the launch has none), tg / lds_t the second (tg.TR == 0: none).
+// The walk over the items of a launch, in order: the range of source / row / view, then check(record) -- rs_check_record or
+// rs_check_record_frames with the entry point's check_src -- then each(item, record, again), which sizes the launch from the
+// record and may refuse the item (what a launch keeps per row: pv_region.hip).  The first refusal ends the walk and is
+// returned.  A launch is a window of a longer sequence and reads only the records its items name (the kernel clamps `source`
+// into range and the items are the validated ones), so its cost does not grow with the number of videos of the whole
+// sequence; a video-major sequence names the record just checked (`again`), which is not checked again, and any other record
+// named again is, which is cheaper than remembering.
+template <typename Check, typename Each>
+inline int rs_walk_items(const pv_batch_views_desc& d, const Check& check, const Each& each) {
+  for (int i = 0; i < d.n_items; ++i) {
+    const pv_view_item& it = d.items[i];
+    if (it.source < 0 || it.source >= d.n_sources || it.row < 0 || it.row >= d.n_rows || it.view < 0 || it.view >= d.n_views)
+      return PV_ERR_INVALID;
+    const pv_view_source& v = d.sources[it.source];
+    const bool again = i > 0 && it.source == d.items[i - 1].source;
+    if (!again)
+      if (int e = check(v)) return e;
+    if (int e = each(it, v, again)) return e;
+  }
+  return PV_OK;
+}
+
+// The descriptor, the items and the record behind each of them, then the sizes of the launch.  check_src(record) is the
+// entry point's own part: whether the record's `src` is a source of d.src_dtype (PV_ERR_INVALID if not).  Items of upright
+// records (orient == 0) run the staged strip, sized by the widest column span(s) of any such record x view: g / lds
+// (g.R == 0: the launch has none).  Items of oriented records run the staged tile: tg / lds_t (tg.TR == 0: none).
 template <typename CheckSrc>
 inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_src, RsItemLaunch& g, size_t& lds, RsTileLaunch& tg,
                           size_t& lds_t) {
@@ -1074,21 +1195,17 @@ inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_sr
   const bool yuv = d.src_layout == PV_SRC_YUV420;
   int span = 0, span_c = 0, n_upright = 0;
   std::vector<const pv_view_source*> oriented;     // the oriented records the items name, a video-major run once
-  for (int i = 0; i < d.n_items; ++i) {
-    const pv_view_item& it = d.items[i];
-    if (it.source < 0 || it.source >= d.n_sources || it.row < 0 || it.row >= d.n_rows || it.view < 0 || it.view >= d.n_views)
-      return PV_ERR_INVALID;
-    const pv_view_source& v = d.sources[it.source];
-    const bool again = i > 0 && it.source == d.items[i - 1].source;   // a video-major sequence names the record just checked
-    if (!again)
-      if (int e = rs_check_record(d, v, yuv, check_src)) return e;
+  const auto check = [&](const pv_view_source& v) { return rs_check_record(d, v, yuv, check_src); };
+  const auto each = [&](const pv_view_item&, const pv_view_source& v, bool again) {
     if (v.orient != 0) {
       if (!again) oriented.push_back(&v);
-      continue;
+    } else {
+      ++n_upright;
+      rs_widest_span(v.sx, v.x_off, d.n_views, d.Wo, v.Ws, span, span_c);
     }
-    ++n_upright;
-    rs_widest_span(v.sx, v.x_off, d.n_views, d.Wo, v.Ws, span, span_c);
-  }
+    return PV_OK;
+  };
+  if (int e = rs_walk_items(d, check, each)) return e;
   g = {}, tg = {};
   lds = lds_t = 0;
   if (!oriented.empty())

@@ -89,12 +89,13 @@ int yuv_run(pv_yuv_views_desc d, pv_stream_t stream, int sb) {
   size_t lds;
   if (int e = rs_strip_rows(rs_yuv_pitches(span_y, span_c, d.c_step, sb, g.pitch_y, g.pitch_c), d.Ho, g.R, lds)) return e;
   g.c_base = 2 * g.R * g.pitch_y;
+#define YV_STRIPS(KERNEL, CSTEP) RS_DISPATCH(pv_ceil_div(d.Ho, g.R), lds, (d, g), KERNEL, CSTEP)
   if (sb == 2) {
-    if (d.c_step == 2) RS_DISPATCH(yuv16_views_kernel, 2);
-    else RS_DISPATCH(yuv16_views_kernel, 1);
+    if (d.c_step == 2) YV_STRIPS(yuv16_views_kernel, 2);
+    else YV_STRIPS(yuv16_views_kernel, 1);
   } else {
-    if (d.c_step == 2) RS_DISPATCH(yuv_views_kernel, 2);
-    else RS_DISPATCH(yuv_views_kernel, 1);
+    if (d.c_step == 2) YV_STRIPS(yuv_views_kernel, 2);
+    else YV_STRIPS(yuv_views_kernel, 1);
   }
   PV_LAUNCH_CHECK();
   return PV_OK;
