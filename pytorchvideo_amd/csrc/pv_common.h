@@ -22,7 +22,8 @@ int pv_tune(const char* key, int dflt);                // pv_plan.hip
   } while (0)
 #define PV_LAUNCH_CHECK() PV_HIP_CHECK(hipGetLastError())
 // Every kernel launch goes through PV_LAUNCH: it notes the kernel's symbol (a pointer store) so that pv_plan_profile can
-// report which kernel an op was routed to -- bench.py's `roofline` is per kernel SYMBOL, not per op label.
+// report which kernel an op was routed to -- bench.py's `roofline` is per kernel SYMBOL, not per op label.  (One exception:
+// pv_gemm_launch_persistent in pv_gemm_tile.h launches through a function pointer and notes the kernel's name itself.)
 void pv_note_kernel(const char* name);                 // pv_plan.hip
 #define PV_LAUNCH(kernel, ...)              \
   do {                                      \

@@ -23,9 +23,7 @@
 //   * tiles are numbered so that consecutive workgroups (same XCD -> same L2) share the
 //     activation rows and walk the weight panels.
 #include <stdlib.h>
-#include "pv_common.h"
-
-__device__ __attribute__((aligned(16))) unsigned int pv_zero_page[4] = {0u, 0u, 0u, 0u};
+#include "pv_gemm_tile.h"
 
 namespace {
 
@@ -36,12 +34,6 @@ constexpr int kMaxTaps = 512;
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
-
-// LDS row rho of the weight tile holds output channel chi(rho): within each 32-row MFMA tile,
-// accumulator register r of lane-half hi is MFMA row (r&3) + 8*(r>>2) + 4*hi -> channel 16*hi + r
-__device__ __forceinline__ int chi(int rho) {
-  return (rho & ~31) + 16 * ((rho >> 2) & 1) + 4 * ((rho >> 3) & 3) + (rho & 3);
-}
 
 struct GemmGeom {   // per-thread staging geometry of one output tile
   long w_off[4];    // element offset of the weight row carried by item j, or -1
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_glds_kernel(const pv_conv3d_
   const int cout_p8 = pv_round_up(d.cout, 8);
   const bf16_t* __restrict__ X = static_cast<const bf16_t*>(d.x);
   const bf16_t* __restrict__ Wt = static_cast<const bf16_t*>(d.w);
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(pv_zero_page);
+  const bf16_t* zero = reinterpret_cast<const bf16_t*>(pv_gemm_zero_page);
 
   if constexpr (!PW) {
     for (int t = tid; t < taps; t += kThreads) {
@@ -133,7 +125,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_glds_kernel(const pv_conv3d_
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int row = (j * kThreads + tid) / CPR;
-      const int n = gg.n0 + chi(row);
+      const int n = gg.n0 + pv_chi(row);
       gg.w_off[j] = n < d.cout ? (long)n * K : -1;
       const long m = gg.m0 + row;
       if (j < NJX && m < M) {
@@ -165,10 +157,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_glds_kernel(const pv_conv3d_
   // Source selection is done with bit masks, not `?:` -- the compiler would turn a select between two
   // pointers into two exec-masked LDS-DMA instructions.
   const unsigned long zaddr = (unsigned long)zero;
-  auto pick = [&](bool ok, const bf16_t* p) -> const bf16_t* {
-    const unsigned long m = 0ul - (unsigned long)ok;
-    return reinterpret_cast<const bf16_t*>(((unsigned long)p & m) | (zaddr & ~m));
-  };
+  auto pick = [&](bool ok, const bf16_t* p) { return pv_pick(ok, (unsigned long)p, zaddr); };
   auto stage = [&](int buf, const GemmGeom& gg, int ks) {
     bf16_t* wb = smem + buf * 2 * TILE_ELEMS;
     bf16_t* xb = wb + TILE_ELEMS;
@@ -246,7 +235,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_glds_kernel(const pv_conv3d_
 #pragma unroll
   for (int t = 0; t < VT; ++t) b_row[t] = wm * 32 * VT + t * 32 + l31;
   // s_waitcnt simm16 on gfx9: vmcnt = bits [3:0] | [15:14]; expcnt [6:4] and lgkmcnt [11:8] left at "no wait"
-  constexpr auto vm = [](int n) { return (n & 15) | ((n >> 4) << 14) | (7 << 4) | (15 << 8); };
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   constexpr unsigned kOOB = 0x80000000u;
   __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
@@ -277,11 +265,11 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_glds_kernel(const pv_conv3d_
       if (first_wait_stores) {
         // the LDS-DMA of this step was issued BEFORE the previous tile's stores (in-order return):
         // leave exactly those stores in flight
-        if (d.y_f32) __builtin_amdgcn_s_waitcnt(vm(8 * VT));
-        else __builtin_amdgcn_s_waitcnt(vm(4 * VT));
+        if (d.y_f32) __builtin_amdgcn_s_waitcnt(pv_vm(8 * VT));
+        else __builtin_amdgcn_s_waitcnt(pv_vm(4 * VT));
         first_wait_stores = false;
       } else {
-        __builtin_amdgcn_s_waitcnt(vm(0));
+        __builtin_amdgcn_s_waitcnt(pv_vm(0));
       }
       __builtin_amdgcn_s_barrier();
       if constexpr (ABL != 1) {
@@ -487,7 +475,7 @@ int pv_gemm_glds_try(const pv_conv3d_desc& d, bool pw, hipStream_t s) {
   const long tiles_m = pv_ceil_div(M, 64 * vt);
   const long total = tiles_m * tiles_n;
   if (total <= 0 || total > 0x7fffffffL || M > 0x7fffffffL) return PV_ERR_UNSUPPORTED;
-  if ((long)d.B * d.y_bs * (d.y_f32 ? 4 : 2) > 0x7fffffffL) return PV_ERR_UNSUPPORTED;   // 31-bit buffer offsets
+  if (!pv_gemm_store_range_ok(d)) return PV_ERR_UNSUPPORTED;   // 31-bit buffer offsets
   const float inv_cin = 1.0f / (float)d.cin;
   // temporal-tap rotation (see geom_of): pure (3,1,1) convs, stride / dilation 1, whole tiles inside one frame
   int tap_rot = (!pw && d.kt == 3 && d.kh == 1 && d.kw == 1 && d.st == 1 && d.pt == 1 && d.dil_t <= 1 && d.To >= 3 &&

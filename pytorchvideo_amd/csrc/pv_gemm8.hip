@@ -26,9 +26,7 @@
 // tiles (large batches); the layers of the BASELINE workloads are too small for 256-voxel tiles and stay on the
 // 128 x 128 kernel.
 #include <stdlib.h>
-#include "pv_common.h"
-
-__device__ __attribute__((aligned(16))) unsigned int pv_zero_page8[4] = {0u, 0u, 0u, 0u};
+#include "pv_gemm_tile.h"
 
 namespace {
 
@@ -39,9 +37,6 @@ constexpr int kMaxTaps8 = 512;
 typedef const __attribute__((address_space(1))) void* gptr8_t;
 typedef __attribute__((address_space(3))) void* lptr8_t;
 
-__device__ __forceinline__ int chi8(int rho) {   // LDS row -> channel inside a 32-row MFMA tile group
-  return (rho & ~31) + 16 * ((rho >> 2) & 1) + 4 * ((rho >> 3) & 3) + (rho & 3);
-}
 
 template <int NJW, int NJX>
 struct Geom8 {        // per-thread staging geometry of one output tile (element offsets fit 31 bits: host check)
@@ -80,7 +75,7 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm8_kernel(const pv_conv3d_des
   const int cout_p8 = pv_round_up(d.cout, 8);
   const bf16_t* __restrict__ X = static_cast<const bf16_t*>(d.x);
   const bf16_t* __restrict__ Wt = static_cast<const bf16_t*>(d.w);
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(pv_zero_page8);
+  const bf16_t* zero = reinterpret_cast<const bf16_t*>(pv_gemm_zero_page);
 
   if constexpr (!PW) {
     for (int t = tid; t < taps; t += kThreads8) {
@@ -103,13 +98,7 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm8_kernel(const pv_conv3d_des
 #pragma unroll
   for (int j = 0; j < NJX; ++j) { const int g = j * kThreads8 + tid; kch_x[j] = (g & (CPR - 1)) ^ swz(g >> LCPR); }
 
-  auto tile_origin = [&](int it, long& m0, int& n0) {   // XCD-aware tile order (bijective for any tile count)
-    const int xcd = it & 7, slot = it >> 3;
-    const int qn = total_tiles >> 3, rn = total_tiles & 7;
-    const int tile = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
-    m0 = (long)(tile / tiles_n) * BMV8;
-    n0 = (tile % tiles_n) * BN;
-  };
+  const PvTileOrder<BMV8, BN> tile_origin{total_tiles, tiles_n};
   auto geom_of = [&](int it, Geom8<NJW, NJX>& gg) {
     long m0;
     int n0;
@@ -117,7 +106,7 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm8_kernel(const pv_conv3d_des
 #pragma unroll
     for (int j = 0; j < NJW; ++j) {
       const int row = (j * kThreads8 + tid) >> LCPR;
-      const int n = n0 + chi8(row);
+      const int n = n0 + pv_chi(row);
       gg.w_off[j] = n < d.cout ? n * K : -1;
     }
 #pragma unroll
@@ -147,10 +136,7 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm8_kernel(const pv_conv3d_des
 
   // source selection with bit masks, not `?:` (a select between two pointers becomes two exec-masked DMAs)
   const unsigned long zaddr = (unsigned long)zero;
-  auto pick = [&](bool ok, const bf16_t* p) -> const bf16_t* {
-    const unsigned long m = 0ul - (unsigned long)ok;
-    return reinterpret_cast<const bf16_t*>(((unsigned long)p & m) | (zaddr & ~m));
-  };
+  auto pick = [&](bool ok, const bf16_t* p) { return pv_pick(ok, (unsigned long)p, zaddr); };
   auto stage = [&](int slot, const Geom8<NJW, NJX>& gg, int ks, bool live) {
     bf16_t* wb = smem + slot * STAGE_ELEMS;
     bf16_t* xb = wb + BN * BK8;
@@ -187,7 +173,6 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm8_kernel(const pv_conv3d_des
 #pragma unroll
   for (int t = 0; t < 2; ++t) b_row[t] = wm * 64 + t * 32 + l31;
   // s_waitcnt simm16 on gfx9: vmcnt = bits [3:0] | [15:14]; expcnt [6:4] and lgkmcnt [11:8] left at "no wait"
-  constexpr auto vm = [](int n) { return (n & 15) | ((n >> 4) << 14) | (7 << 4) | (15 << 8); };
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   constexpr unsigned kOOB = 0x80000000u;
   __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
@@ -224,7 +209,7 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm8_kernel(const pv_conv3d_des
   const bool half_b = wave >= 4;   // wave-uniform (scalar)
   int gslot = 0;         // ring slot of the stage being multiplied
   int pend = 0;          // stages for which the previous tile's stores may still sit in the queue (wave-uniform)
-  __builtin_amdgcn_s_waitcnt(vm((NS8 - 2) * LPS));   // this wave's share of stage 0
+  __builtin_amdgcn_s_waitcnt(pv_vm((NS8 - 2) * LPS));   // this wave's share of stage 0
   if (half_b) __builtin_amdgcn_s_barrier();  // the offset
   for (int it = blockIdx.x; it < total_tiles; it += gridDim.x) {
     long m0;
@@ -258,11 +243,11 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm8_kernel(const pv_conv3d_des
       // this wave's share of stage gc+1 has landed when at most the two youngest stages (and, after an epilogue,
       // that tile's stores, issued between them) are outstanding; the fragment reads are complete as well
       if (pend > 0) {
-        if (d.y_f32) __builtin_amdgcn_s_waitcnt(vm((NS8 - 2) * LPS + E_F32) & ~(15 << 8));
-        else __builtin_amdgcn_s_waitcnt(vm((NS8 - 2) * LPS + E_BF16) & ~(15 << 8));
+        if (d.y_f32) __builtin_amdgcn_s_waitcnt(pv_vml((NS8 - 2) * LPS + E_F32));
+        else __builtin_amdgcn_s_waitcnt(pv_vml((NS8 - 2) * LPS + E_BF16));
         --pend;
       } else {
-        __builtin_amdgcn_s_waitcnt(vm((NS8 - 2) * LPS) & ~(15 << 8));   // ... and lgkmcnt(0)
+        __builtin_amdgcn_s_waitcnt(pv_vml((NS8 - 2) * LPS));   // ... and lgkmcnt(0)
       }
       __builtin_amdgcn_s_barrier();   // B2
       // ---- C ----
@@ -280,19 +265,12 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm8_kernel(const pv_conv3d_des
 
     // ---- epilogue: lane owns channels cb..cb+15 of voxel m for every (channel tile a, voxel tile v) ----
     if (pend > 0) {   // K shorter than the ring: the previous tile's stores are still counted -- drain once
-      __builtin_amdgcn_s_waitcnt(vm(0));
+      __builtin_amdgcn_s_waitcnt(pv_vm(0));
       pend = 0;
     }
     long e_b[2], e_sp[2];
     bool e_ok[2];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-      const long m = m0 + wm * 64 + v * 32 + l31;
-      e_ok[v] = m < M;
-      const long mm = e_ok[v] ? m : 0;
-      e_b[v] = (long)((unsigned)mm / (unsigned)S_out);
-      e_sp[v] = mm - e_b[v] * S_out;
-    }
+    PvEpiRows<2, 64, int>{m0, wm, l31, e_ok, M, e_b, S_out, e_sp}();
 #pragma unroll
     for (int a = 0; a < CT; ++a) {
       const int cb = n0 + wn * 32 * CT + a * 32 + 16 * hi;
@@ -407,21 +385,15 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm8_kernel(const pv_conv3d_des
     pend = NS8 - 2;
   }
   if (!half_b) __builtin_amdgcn_s_barrier();   // matches the second half's offset barrier
-  __builtin_amdgcn_s_waitcnt(vm(0));   // the stream's trailing (zero-page) DMAs land before the LDS is released
+  __builtin_amdgcn_s_waitcnt(pv_vm(0));   // the stream's trailing (zero-page) DMAs land before the LDS is released
 }
 
 template <bool PW, int CT, int BK, int NS>
 int launch8(const pv_conv3d_desc& d, int tiles_n, long total, hipStream_t s) {
   constexpr int BN = 64 * CT;
   const size_t lds = (size_t)NS * (BN + BMV8) * BK * 2 + (PW ? 16 : (size_t)kMaxTaps8 * 4);
-  auto kern = gemm8_kernel<PW, CT, BK, NS>;
-  PV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const long resident = 256;   // one workgroup per CU
-  dim3 grid((unsigned)(total < resident ? total : resident)), block(kThreads8);
-  PV_LAUNCH(kern, grid, block, lds, s, d, tiles_n, (int)total, 1.0f / (float)d.cin);
-  pv_note_kernel("gemm8_kernel");   // (launched through a function pointer: PV_LAUNCH saw only the variable)
-  PV_LAUNCH_CHECK();
-  return PV_OK;
+  return pv_gemm_launch_persistent(gemm8_kernel<PW, CT, BK, NS>, "gemm8_kernel", kThreads8, lds, total, s,
+                                   d, tiles_n, (int)total, 1.0f / (float)d.cin);
 }
 
 }  // namespace
@@ -430,7 +402,7 @@ int launch8(const pv_conv3d_desc& d, int tiles_n, long total, hipStream_t s) {
 int pv_gemm8_try(const pv_conv3d_desc& d, bool pw, hipStream_t s) {
   const int mode = pv_tune("gemm8", 1);   // 0 off, 1 heuristic, 2 BN=128, 4 BN=256
   if (mode == 0) return PV_ERR_UNSUPPORTED;
-  if (d.dtype != PV_BF16 || d.a_gate != nullptr || d.a_act != PV_ACT_NONE || d.x2 != nullptr) return PV_ERR_UNSUPPORTED;
+  if (!pv_gemm_plain_operands(d)) return PV_ERR_UNSUPPORTED;
   const int taps = d.kt * d.kh * d.kw;
   if (taps > kMaxTaps8 || d.kt > 255 || d.kh > 255 || d.kw > 255) return PV_ERR_UNSUPPORTED;
   const long M = (long)d.B * d.To * d.Ho * d.Wo;
@@ -438,7 +410,7 @@ int pv_gemm8_try(const pv_conv3d_desc& d, bool pw, hipStream_t s) {
   const int cout_p8 = pv_round_up(d.cout, 8);
   // 31-bit element offsets in the staging geometry, 31-bit byte offsets in the store descriptor
   if (M > 0x7fffffffL || (long)d.B * d.x_bs > 0x7fffffffL || (long)d.cout * K > 0x7fffffffL) return PV_ERR_UNSUPPORTED;
-  if ((long)d.B * d.y_bs * (d.y_f32 ? 4 : 2) > 0x7fffffffL) return PV_ERR_UNSUPPORTED;
+  if (!pv_gemm_store_range_ok(d)) return PV_ERR_UNSUPPORTED;
   if (K < 3 * 64) return PV_ERR_UNSUPPORTED;   // at least three stages per tile
   const long tiles_m = pv_ceil_div(M, BMV8);
   int ct = 0;

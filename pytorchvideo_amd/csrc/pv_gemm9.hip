@@ -37,9 +37,7 @@
 // LDS swizzle as in the older kernels (chunk ^= (row >> 1) & 7 on the DMA's SOURCE address and on the read: conflict-free
 // `ds_read_b128`, both sides or neither).
 #include <stdlib.h>
-#include "pv_common.h"
-
-__device__ __attribute__((aligned(16))) unsigned int pv_zero_page9[4] = {0u, 0u, 0u, 0u};
+#include "pv_gemm_tile.h"
 
 namespace {
 
@@ -57,13 +55,8 @@ constexpr int kGeo9 = kTab9 + 2 * 2048;          // implicit-GEMM staging geomet
 constexpr int kLds9Bytes = kGeo9 + kThreads9 * 32;
 constexpr int kRegionB9 = 4 * UNIT9 * 2;   // byte offset of the voxel units (folded into the read base: immediates stay < 64 K)
 
-typedef const __attribute__((address_space(1))) void* gptr9_t;
-typedef __attribute__((address_space(3))) void* lptr9_t;
-
-// LDS row -> channel inside a 32-row MFMA tile (accumulator register r of lane-half hi is channel 16*hi + r)
-__device__ __forceinline__ int chi9(int rho) {
-  return (rho & ~31) + 16 * ((rho >> 2) & 1) + 4 * ((rho >> 3) & 3) + (rho & 3);
-}
+typedef pv_gptr_t gptr9_t;
+typedef pv_lptr_t lptr9_t;
 
 struct Geom9 {         // per-thread staging rows of one output tile (DMA j of a unit covers unit rows 64 j + 8 wave + lane / 8)
   unsigned a_row;      // BYTE offset in w of the weight row of (a = 0, j = 0); (a, j) is 64 a + 128 j rows further, clamped at use
@@ -92,16 +85,10 @@ __global__ __launch_bounds__(kThreads9) void gemm_quad_kernel(const pv_conv3d_de
   const int dil_t = d.dil_t > 1 ? d.dil_t : 1, dil_h = d.dil_h > 1 ? d.dil_h : 1, dil_w = d.dil_w > 1 ? d.dil_w : 1;
   const bf16_t* __restrict__ X = static_cast<const bf16_t*>(d.x);
   const char* __restrict__ Wb = static_cast<const char*>(d.w);
-  const unsigned long zaddr = (unsigned long)reinterpret_cast<const bf16_t*>(pv_zero_page9);
+  const unsigned long zaddr = (unsigned long)reinterpret_cast<const bf16_t*>(pv_gemm_zero_page);
 
   // ---- staging rows of this thread (the same for every unit): DMA j covers unit rows 64 j + 8 wave + lane / 8 ----
-  auto tile_origin = [&](int it, long& m0, int& n0) __attribute__((always_inline)) {   // XCD-aware tile order (bijective for any tile count)
-    const int xcd = it & 7, slot = it >> 3;
-    const int qn = total_tiles >> 3, rn = total_tiles & 7;
-    const int tile = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
-    m0 = (long)(tile / tiles_n) * BT9;
-    n0 = (tile % tiles_n) * BT9;
-  };
+  const PvTileOrder<BT9, BT9> tile_origin{total_tiles, tiles_n};
   // K chunk (8 elements) that lands on LDS position lane % 8 of this thread's staging rows: the swizzle key (row >> 1) & 7 is
   // the same for both DMAs of a unit (rows 64 apart) -- one register for all eight staging rows
   const int chunk8 = ((lane & 7) ^ (((8 * wave + (lane >> 3)) >> 1) & 7)) * 8;
@@ -112,66 +99,37 @@ __global__ __launch_bounds__(kThreads9) void gemm_quad_kernel(const pv_conv3d_de
   int* geo = reinterpret_cast<int*>(smem9_raw + kGeo9) + tid * 8;   // (!PW) this thread's staging geometry
   int iss_c0 = 0, iss_dt = 0, iss_dh = 0, iss_dw = 0;   // channel offset inside the tap, tap coordinates (wave-uniform)
   unsigned iss_wk = 0;                                  // byte offset of the stream's K tile inside a weight row
-  auto geom_of = [&](int it, Geom9& g) __attribute__((always_inline)) {
+  Geom9 g;
+  const PvTapStart<PW> tile_start{iss_c0, iss_dh, iss_dw, tap_rot, S_out, d, iss_dt, iss_wk};
+  auto geom_of = [&](int it) __attribute__((always_inline)) {
     long m0;
     int n0;
     tile_origin(it, m0, n0);
-    iss_c0 = iss_dh = iss_dw = 0;
-    // temporal-tap rotation (tap_rot: temporal stride 1, whole tiles inside one frame -- host check): the tile of output frame t
-    // starts its reduction at tap (pt - t) mod kt and wraps, so that in step i EVERY concurrent tile reads an input frame with
-    // index = i (mod kt): the kt consumers of a frame fetch it at the same moment instead of kt times through a 4 MB L2
-    // (SlowFast res4 conv_a: 32 tiles per XCD touch 7.3 MB of frames per tap; PMC fetch 2.95 x the input without this)
-    int rot = 0;
-    if constexpr (!PW) {
-      if (tap_rot) {
-        const unsigned sp = (unsigned)m0 % (unsigned)S_out;
-        rot = (d.pt - (int)(sp / (unsigned)(d.Ho * d.Wo))) % d.kt;
-        rot = rot < 0 ? rot + d.kt : rot;
-      }
-    }
-    iss_dt = rot;
-    iss_wk = (unsigned)(rot * d.kh * d.kw * d.cin) * 2u;
+    tile_start(m0);
     const int rho0 = 8 * wave + (lane >> 3);   // unit row of DMA 0 (< 64)
-    g.a_row = (unsigned)(n0 + 32 * (rho0 >> 5) + chi9(rho0 & 31)) * a_pitch;
+    g.a_row = (unsigned)(n0 + 32 * (rho0 >> 5) + pv_chi(rho0 & 31)) * a_pitch;
     if constexpr (PW) {
       g.b_row = (unsigned)((int)m0 + 64 * (rho0 >> 5) + (rho0 & 31)) * b_pitch;
     } else {
+      const PvWindow window_of{d, M, S_out, dil_t, dil_h, dil_w, chunk8};
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
-          long m = m0 + 128 * j + 64 * (rho0 >> 5) + 32 * v + (rho0 & 31);
-          m = m < M ? m : M - 1;                              // M tail: a clamped row, never stored
-          const unsigned b = (unsigned)m / (unsigned)S_out;
-          const unsigned sp = (unsigned)m - b * (unsigned)S_out;
-          const unsigned to = sp / (unsigned)(d.Ho * d.Wo);
-          const unsigned r2 = sp - to * (unsigned)(d.Ho * d.Wo);
-          const unsigned ho = r2 / (unsigned)d.Wo;
-          const int t0 = (int)to * d.st - d.pt, h0 = (int)ho * d.sh - d.ph, w0 = (int)(r2 - ho * (unsigned)d.Wo) * d.sw - d.pw;
-          geo[v * 4 + j] = (int)((long)b * d.x_bs + ((long)(t0 * d.Hi + h0) * d.Wi + w0) * d.ldx) + chunk8;
-          unsigned msk = 0u;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            if (q < d.kt && (unsigned)(t0 + q * dil_t) < (unsigned)d.Ti) msk |= 1u << q;
-            if (q < d.kh && (unsigned)(h0 + q * dil_h) < (unsigned)d.Hi) msk |= 1u << (8 + q);
-            if (q < d.kw && (unsigned)(w0 + q * dil_w) < (unsigned)d.Wi) msk |= 1u << (16 + q);
-          }
+          const long m = m0 + 128 * j + 64 * (rho0 >> 5) + 32 * v + (rho0 & 31);
+          unsigned msk;
+          window_of(m, geo[v * 4 + j], msk);
           geo[v * 4 + 2 + j] = (int)msk;
         }
     }
   };
 
   // ---- issue side: the DMA stream, K tile by K tile across output tiles (all of this state is wave-uniform) ----
-  Geom9 g;
   int iss_it = blockIdx.x, iss_ku = 0, iss_jt = 0;   // work item, K tile inside it, this workgroup's tile count
   bool iss_live = iss_it < total_tiles;
-  geom_of(iss_live ? iss_it : 0, g);
+  geom_of(iss_live ? iss_it : 0);
 
-  // source selection with bit masks, not `?:` (a select between two pointers becomes two exec-masked DMAs)
-  auto pick = [&](bool ok, unsigned long p) __attribute__((always_inline)) -> const bf16_t* {
-    const unsigned long m = 0ul - (unsigned long)ok;
-    return reinterpret_cast<const bf16_t*>((p & m) | (zaddr & ~m));
-  };
+  auto pick = [&](bool ok, unsigned long p) __attribute__((always_inline)) { return pv_pick(ok, p, zaddr); };
   // jsel: 0 / 1 = that DMA of the unit only, -1 = both
   auto issue_a = [&](int a, int unit, int jsel) __attribute__((always_inline)) {   // channel half a of the stream's K tile -> LDS unit `unit`
     const unsigned kc = iss_wk + (unsigned)(chunk8 * 2);
@@ -184,7 +142,7 @@ __global__ __launch_bounds__(kThreads9) void gemm_quad_kernel(const pv_conv3d_de
                                        (lptr9_t)(smem + unit + (j * 8 + wave) * 512), 16, 0, 0);
     }
   };
-  typedef int i32x4 __attribute__((ext_vector_type(4)));
+  typedef pv_i32x4 i32x4;
   auto issue_b = [&](int v, int unit, int jsel, const i32x4& gq) __attribute__((always_inline)) {   // voxel half v (gq: its geometry)
     if constexpr (PW) {
       const unsigned kc = (unsigned)(iss_ku * 128 + chunk8 * 2);
@@ -209,58 +167,24 @@ __global__ __launch_bounds__(kThreads9) void gemm_quad_kernel(const pv_conv3d_de
       }
     }
   };
-  auto load_geo = [&](int v) __attribute__((always_inline)) -> i32x4 {
-    if constexpr (PW) {
-      return i32x4{0, 0, 0, 0};
-    } else {
-      // (the address is rebuilt from the thread index behind an empty asm: as a loop-invariant register it was the one value the
-      // compiler spilled, and its reload -- a scratch load + vmcnt(0) in the loop header -- drained the DMA pipeline every K-tile pair)
-      unsigned t = threadIdx.x;
-      asm volatile("" : "+v"(t));
-      return *reinterpret_cast<const i32x4*>(smem9_raw + kGeo9 + t * 32u + (unsigned)v * 16u);
-    }
-  };
-  // folded BatchNorm / bias tables of the stream's tile -> LDS, one 4-byte DMA per thread: wave w < 4 carries scale[64 w ..
-  // 64 w + 63] of the tile's 256 channels, w >= 4 the shift (channels past cout read a clamped entry: zeroed in the epilogue).
-  // The global round trips of 2 x 64 table loads per thread were a third of the per-tile fixed cost (epilogue reads: ds_read).
-  // Extra DMAs inside the counted windows only make the waits stricter (an older unit completes earlier), never weaker.
-  auto issue_tables = [&]() __attribute__((always_inline)) {
-    const float* tab = wave < 4 ? d.scale : d.shift;
-    if (tab != nullptr && iss_live) {
-      long m0;
-      int n0;
-      tile_origin(iss_it, m0, n0);
-      int n = n0 + 64 * (wave & 3) + lane;
-      n = n < d.cout ? n : d.cout - 1;
-      __builtin_amdgcn_global_load_lds((gptr9_t)(tab + n), (lptr9_t)(smem9_raw + kTab9 + (iss_jt & 1) * 2048 + wave * 256), 4, 0, 0);
-    }
-  };
-  auto advance = [&]() __attribute__((always_inline)) {   // next K tile of the stream
-    ++iss_ku;
-    iss_wk += 128u;
-    if constexpr (!PW) {
-      iss_c0 += 64;
-      if (iss_c0 == d.cin) {
-        iss_c0 = 0;
-        if (++iss_dw == d.kw) {
-          iss_dw = 0;
-          if (++iss_dh == d.kh) {
-            iss_dh = 0;
-            if (++iss_dt == d.kt) { iss_dt = 0; iss_wk = 0u; }   // (a rotated reduction wraps to tap 0 = weight column 0)
-          }
-        }
-      }
-    }
-    if (iss_ku == nk) {
-      iss_ku = 0;
-      iss_wk = 0u;
-      iss_it += gridDim.x;
-      ++iss_jt;
-      iss_live = iss_it < total_tiles;
-      if (iss_live) geom_of(iss_it, g);
-      issue_tables();
-    }
-  };
+  auto load_geo = [&](int v) __attribute__((always_inline)) { return pv_load_geo<PW, 32u>(smem9_raw + kGeo9, (unsigned)v * 16u); };
+  const PvIssueTables<PvTileOrder<BT9, BT9>> tables{wave, d, iss_live, tile_origin, iss_it, lane, iss_jt};
+  auto issue_tables = [&]() __attribute__((always_inline)) { tables(smem9_raw + kTab9); };
+  const PvTapAdvance<PW, decltype(geom_of), decltype(issue_tables)> advance{   // next K tile of the stream
+      iss_ku,         // K tile inside the work item
+      iss_wk,         // byte offset inside a weight row
+      iss_c0,         // channel offset inside the tap
+      d,
+      iss_dw,         // tap coordinates
+      iss_dh,
+      iss_dt,
+      nk,
+      iss_it,         // work item
+      iss_jt,         // tile count
+      iss_live,
+      total_tiles,
+      geom_of,
+      issue_tables};
 
   // ---- read side: this lane's fragment position inside a unit, as a BYTE offset from the LDS base ----
   // A rows: wn*64 + ta*32 + (lane & 31) (ta = 1: + 32 rows = + 4096 bytes, same swizzle); B rows: wm*32 + (lane & 31).
@@ -277,12 +201,9 @@ __global__ __launch_bounds__(kThreads9) void gemm_quad_kernel(const pv_conv3d_de
   typedef const __attribute__((address_space(3))) bf16x8* lfrag9_t;
 #define PV9_RD(BASE, S, BYTES) (*(lfrag9_t)(unsigned long)(((BASE) ^ ((S) * 32u)) + (unsigned)(BYTES)))
 
-  // s_waitcnt simm16 on gfx9: vmcnt = bits [3:0] | [15:14]; expcnt [6:4] "no wait"; lgkmcnt [11:8] = 0
-  constexpr auto vml = [](int n) { return (n & 15) | ((n >> 4) << 14) | (7 << 4); };
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   constexpr unsigned kOOB = 0x80000000u;
-  __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-      d.y, 0, (int)((unsigned)d.B * (unsigned)d.y_bs * (YF32 ? 4u : 2u)), 0x00020000);   // stores per thread per tile: 32 (fp32) / 16
+  __amdgpu_buffer_rsrc_t ry = pv_epi_rsrc(d, YF32);   // stores per thread per tile: 32 (fp32) / 16
 
   // ---- prologue: the first tile's tables, AE BE BO AO of K tile 0, AE BE of K tile 1 ----
   issue_tables();
@@ -293,7 +214,7 @@ __global__ __launch_bounds__(kThreads9) void gemm_quad_kernel(const pv_conv3d_de
   advance();
   issue_a(0, unit_a(1, 0), -1);
   issue_b(0, unit_b(1, 0), -1, load_geo(0));
-  __builtin_amdgcn_s_waitcnt(vml(8));   // AE, BE of K tile 0: this thread's share
+  __builtin_amdgcn_s_waitcnt(pv_vml(8));   // AE, BE of K tile 0: this thread's share
   __builtin_amdgcn_s_barrier();
   const bool half_b = wave >= 4;        // wave-uniform
   if (half_b) __builtin_amdgcn_s_barrier();   // the offset between the two halves
@@ -309,8 +230,8 @@ __global__ __launch_bounds__(kThreads9) void gemm_quad_kernel(const pv_conv3d_de
   // then comes BEFORE this phase's DMAs and leaves three units (6 DMAs) in flight instead of four.
 #define PV9_WAIT_B1(FIRST)                                                                          \
   do {                                                                                              \
-    if ((FIRST) && stores_behind) __builtin_amdgcn_s_waitcnt(vml((DM ? 6 : 8) + (YF32 ? 32 : 16)));  \
-    else __builtin_amdgcn_s_waitcnt(vml(DM ? 6 : 8));                                               \
+    if ((FIRST) && stores_behind) __builtin_amdgcn_s_waitcnt(pv_vml((DM ? 6 : 8) + (YF32 ? 32 : 16)));  \
+    else __builtin_amdgcn_s_waitcnt(pv_vml(DM ? 6 : 8));                                               \
     __builtin_amdgcn_s_barrier();                                                                   \
     __builtin_amdgcn_sched_barrier(0);                                                              \
   } while (0)
@@ -417,113 +338,30 @@ __global__ __launch_bounds__(kThreads9) void gemm_quad_kernel(const pv_conv3d_de
     tile_origin(it, m0, n0);
     long e_b[2], e_sp[2];
     bool e_ok[2];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-      const long m = m0 + wm * 64 + v * 32 + l31;
-      e_ok[v] = m < M;
-      const long mm = e_ok[v] ? m : 0;
-      e_b[v] = (long)((unsigned)mm / (unsigned)S_out);
-      e_sp[v] = mm - e_b[v] * S_out;
-    }
+    PvEpiRows<2, 64, int>{m0, wm, l31, e_ok, M, e_b, S_out, e_sp}();
     const float* tabs = reinterpret_cast<const float*>(smem9_raw + kTab9 + (jt & 1) * 2048);
-    typedef f32x4 res_t[2][2][2];   // [v][h8][half]: 8 channels as 2 x f32x4 (fp32) or 1 x 16 bytes (bf16)
-    auto load_res = [&](int a, res_t& res) __attribute__((always_inline)) {
-      if (d.residual == nullptr) return;
-      const int cb = n0 + wn * 128 + a * 32 + 16 * hi;
-#pragma unroll
-      for (int v = 0; v < 2; ++v)
-#pragma unroll
-        for (int h8 = 0; h8 < 2; ++h8) {
-          const bool ok = e_ok[v] && cb + h8 * 8 < cout_p8;
-          const long ro = ok ? e_b[v] * d.r_bs + e_sp[v] * d.ldr + cb + h8 * 8 : 0;
-          if (d.r_f32) {
-            const float* rp = static_cast<const float*>(d.residual) + ro;
-            res[v][h8][0] = *reinterpret_cast<const f32x4*>(rp);
-            res[v][h8][1] = *reinterpret_cast<const f32x4*>(rp + 4);
-          } else {
-            res[v][h8][0] = *reinterpret_cast<const f32x4*>(static_cast<const bf16_t*>(d.residual) + ro);
-          }
-        }
-    };
-    auto finish = [&](int a, const res_t& res) __attribute__((always_inline)) {
-      const int cl = wn * 128 + a * 32 + 16 * hi;   // channel inside the tile
-      const int cb = n0 + cl;
-      if (d.scale != nullptr) {
-        f32x4 sc[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sc[q] = *reinterpret_cast<const f32x4*>(tabs + cl + 4 * q);
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] *= sc[r >> 2][r & 3];
-      }
-      if (d.shift != nullptr) {
-        f32x4 sh[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sh[q] = *reinterpret_cast<const f32x4*>(tabs + 256 + cl + 4 * q);
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] += sh[r >> 2][r & 3];
-      }
-      if (d.residual != nullptr) {
-        if (d.r_f32) {
-#pragma unroll
-          for (int v = 0; v < 2; ++v)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][v][r] += res[v][r >> 3][(r >> 2) & 1][r & 3];
-        } else {
-#pragma unroll
-          for (int v = 0; v < 2; ++v)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][v][r] += (float)__builtin_bit_cast(bf16x8, res[v][r >> 3][0])[r & 7];
-        }
-      }
-      if (d.act == PV_ACT_RELU) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] = fmaxf(acc[a][v][r], 0.f);
-      } else if (d.act == PV_ACT_GELU) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] = pv_gelu_fast(acc[a][v][r]);
-      } else if (d.act == PV_ACT_SWISH) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] *= pv_sigmoid(acc[a][v][r]);
-      } else if (d.act == PV_ACT_SIGMOID) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] = pv_sigmoid(acc[a][v][r]);
-      }
-      if (cb + 16 > d.cout) {   // ragged last channel tile: the padding up to the 8-multiple is written as zeros
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] = cb + r < d.cout ? acc[a][v][r] : 0.f;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
+    const PvEpiLoadRes<2, 128> load_res{d, n0, wn, hi, e_ok, cout_p8, e_b, e_sp};
+    const PvEpiFinish<4, 2, 128> finish{d, acc, tabs, n0, wn, hi};
     // (requesting the residual rows of tile a + 1 before tile a is finished -- a second 32-register set -- measured nothing and
     // pushed the epilogue into scratch: one set)
     // (literal channel-tile indices: inside a loop the lambdas' `a` is a run-time index when the accumulators are first split
     // into registers, and half of them then live in scratch for the whole kernel)
     {
-      res_t r0;
+      pv_epi_res_t<2> r0;
       load_res(0, r0);
       finish(0, r0);
+      __builtin_amdgcn_sched_barrier(0);
       load_res(1, r0);
       finish(1, r0);
+      __builtin_amdgcn_sched_barrier(0);
       load_res(2, r0);
       finish(2, r0);
+      __builtin_amdgcn_sched_barrier(0);
       load_res(3, r0);
       finish(3, r0);
+      __builtin_amdgcn_sched_barrier(0);
     }
-    // ... then nothing but stores (E_BF16 / E_F32 of them, whatever is masked)
+    // ... then nothing but stores (32 / 16 of them, whatever is masked)
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const int cb = n0 + wn * 128 + a * 32 + 16 * hi;
@@ -565,46 +403,25 @@ __global__ __launch_bounds__(kThreads9) void gemm_quad_kernel(const pv_conv3d_de
 #undef PV9_WAIT_B1
 #undef PV9_RD
   if (!half_b) __builtin_amdgcn_s_barrier();   // matches the second half's offset barrier
-  __builtin_amdgcn_s_waitcnt(vml(0));          // the stream's trailing (zero-page) DMAs land before the LDS is released
+  __builtin_amdgcn_s_waitcnt(pv_vml(0));          // the stream's trailing (zero-page) DMAs land before the LDS is released
 }
 
 template <bool PW, bool YF32, int VAR>
 int launch9(const pv_conv3d_desc& d, int tiles_n, long total, hipStream_t s) {
-  const size_t lds = (size_t)kLds9Bytes;   // 128 KB of units + 4 KB of epilogue tables
-  auto kern = gemm_quad_kernel<PW, YF32, VAR>;
-  PV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const long resident = 256;   // one workgroup per CU
-  dim3 grid((unsigned)(total < resident ? total : resident)), block(kThreads9);
   // tap rotation: only where a whole tile lies inside one output frame and frames map to taps one to one
   const int tap_rot = !PW && d.kt > 1 && d.st == 1 && d.dil_t <= 1 && (d.Ho * d.Wo) % BT9 == 0 && pv_tune("gemm9_tap_rot", 1);
-  PV_LAUNCH(kern, grid, block, lds, s, d, tiles_n, (int)total, tap_rot);
-  pv_note_kernel("gemm_quad_kernel");   // (launched through a function pointer: PV_LAUNCH saw only the variable)
-  PV_LAUNCH_CHECK();
-  return PV_OK;
+  // 128 KB of units + 4 KB of epilogue tables + the staging geometry
+  return pv_gemm_launch_persistent(gemm_quad_kernel<PW, YF32, VAR>, "gemm_quad_kernel", kThreads9, (size_t)kLds9Bytes, total, s,
+                                   d, tiles_n, (int)total, tap_rot);
 }
 
 }  // namespace
 
 // Can this kernel run the geometry at all?  (pointers are not looked at)
 static bool gemm9_geometry_ok(const pv_conv3d_desc& d, long& M, long& K, long& tiles_m, int& tiles_n) {
-  if (d.dtype != PV_BF16 || d.a_gate != nullptr || d.a_act != PV_ACT_NONE || d.x2 != nullptr) return false;
-  if (d.kt > 8 || d.kh > 8 || d.kw > 8) return false;                                // 8-bit window masks per axis
-  // dilated convs (detection backbones' res5) stay on the 128 x 128 kernel, whose dilation path has kernel tests
-  // (test_dilated_dense_conv); the window masks here fold dil_* in, but no test forces a dilated descriptor onto these tiles
-  if (d.dil_t > 1 || d.dil_h > 1 || d.dil_w > 1) return false;
-  const int taps = d.kt * d.kh * d.kw;
-  if (d.cin % 64 != 0 || ((long)taps * d.cin) % 128 != 0) return false;             // a K step of 64 inside one tap; K tiles in pairs
-  M = (long)d.B * d.To * d.Ho * d.Wo;
-  K = (long)taps * d.cin;
-  const int cout_p8 = pv_round_up(d.cout, 8);
-  if (K < 256) return false;                                                         // a first and a last pair of K tiles
-  // 31-bit element offsets into x, 32-bit byte offsets into w, 31-bit byte offsets in the store descriptor
-  if (M > 0x7fffffffL || (long)d.B * d.x_bs > 0x7fffffffL || ((long)d.cout + 256) * K * 2 > 0xffffffffL ||
-      (M + 256) * d.ldx * 2 > 0xffffffffL)
-    return false;
-  if ((long)d.B * d.y_bs * (d.y_f32 ? 4 : 2) > 0x7fffffffL) return false;
+  if (!pv_gemm_stream_geometry_ok(d, 128, 256, M, K)) return false;   // K tiles in pairs, a first and a last pair
   tiles_m = pv_ceil_div(M, BT9);
-  tiles_n = (int)pv_ceil_div(cout_p8, BT9);
+  tiles_n = (int)pv_ceil_div(pv_round_up(d.cout, 8), BT9);
   return tiles_m * tiles_n > 0 && tiles_m * tiles_n < 0x3fffffffL;
 }
 
@@ -653,13 +470,8 @@ int pv_gemm9_try(const pv_conv3d_desc& d, bool pw, hipStream_t s) {
   // kernel on SlowFast's res4 / res5 shapes -- the implicit-GEMM form of it kept an accumulator block in scratch).
   int var = pv_tune("gemm9_var", -1);
   if (var < 0) var = K >= 384 ? 2 : 0;
-#define PV9_GO(PWv, YFv)                                                  \
-  if (var == 2) return launch9<PWv, YFv, 2>(d, tiles_n, total, s);        \
-  return launch9<PWv, YFv, 0>(d, tiles_n, total, s);
-  if (d.y_f32) {
-    if (rows) { PV9_GO(true, true) } else { PV9_GO(false, true) }
-  } else {
-    if (rows) { PV9_GO(true, false) } else { PV9_GO(false, false) }
-  }
+#define PV9_GO(PWv, YFv) \
+  return var == 2 ? launch9<PWv, YFv, 2>(d, tiles_n, total, s) : launch9<PWv, YFv, 0>(d, tiles_n, total, s)
+  PV_GEMM_PW_YF32(rows, d.y_f32, PV9_GO);
 #undef PV9_GO
 }

@@ -19,9 +19,7 @@
 //     behind MFMA 2, 4 and 6, every unit requested four phases before its first read.  K tiles come in triples (K % 192 == 0:
 //     every LDS address is a per-lane base + an immediate); the waits are the counted `vmcnt(6)` / `vmcnt(5)`.
 #include <stdlib.h>
-#include "pv_common.h"
-
-__device__ __attribute__((aligned(16))) unsigned int pv_zero_pageh[4] = {0u, 0u, 0u, 0u};
+#include "pv_gemm_tile.h"
 
 namespace {
 
@@ -33,12 +31,9 @@ constexpr int kTabH = 3 * kBufBytesH;       // epilogue tables: [tile parity][sc
 constexpr int kGeoH = kTabH + 2 * 2048;     // implicit-GEMM staging geometry: 16 bytes per thread [off j0, off j1, mask j0, mask j1]
 constexpr int kLdsHBytes = kGeoH + kThreadsH * 16;   // 156 KB
 
-typedef const __attribute__((address_space(1))) void* gptrh_t;
-typedef __attribute__((address_space(3))) void* lptrh_t;
-typedef int i32x4h __attribute__((ext_vector_type(4)));
-
-// LDS row -> channel inside a 32-row MFMA tile (accumulator register r of lane-half hi is channel 16*hi + r)
-__device__ __forceinline__ int chih(int rho) { return 16 * ((rho >> 2) & 1) + 4 * ((rho >> 3) & 3) + (rho & 3); }
+typedef pv_gptr_t gptrh_t;
+typedef pv_lptr_t lptrh_t;
+typedef pv_i32x4 i32x4h;
 
 template <bool PW, bool YF32, bool TR>
 __global__ __launch_bounds__(kThreadsH) void gemm_quad_half_kernel(const pv_conv3d_desc d, int tiles_n, int total_tiles, int tap_rot) {
@@ -57,26 +52,23 @@ __global__ __launch_bounds__(kThreadsH) void gemm_quad_half_kernel(const pv_conv
   const int dil_t = d.dil_t > 1 ? d.dil_t : 1, dil_h = d.dil_h > 1 ? d.dil_h : 1, dil_w = d.dil_w > 1 ? d.dil_w : 1;
   const bf16_t* __restrict__ X = static_cast<const bf16_t*>(d.x);
   const char* __restrict__ Wb = static_cast<const char*>(d.w);
-  const unsigned long zaddr = (unsigned long)reinterpret_cast<const bf16_t*>(pv_zero_pageh);
+  const unsigned long zaddr = (unsigned long)reinterpret_cast<const bf16_t*>(pv_gemm_zero_page);
 
   // TR: the transposed tile, 256 voxels x 128 channels -- the SPLIT operand (two 128-row units, one per phase) is the voxels,
   // the WHOLE one (a single unit, read in phase 0 and kept) the weights; everything else is the same loop
   constexpr int BM = TR ? 2 * BMH : BMH, BN = TR ? BNH / 2 : BNH;
-  auto tile_origin = [&](int it, long& m0, int& n0) __attribute__((always_inline)) {   // XCD-aware tile order (bijective for any tile count)
-    const int xcd = it & 7, slot = it >> 3;
-    const int qn = total_tiles >> 3, rn = total_tiles & 7;
-    const int tile = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
-    m0 = (long)(tile / tiles_n) * BM;
-    n0 = (tile % tiles_n) * BN;
-  };
+  const PvTileOrder<BM, BN> tile_origin{total_tiles, tiles_n};
   // DMA j of a unit covers unit rows 64 j + rho0, rho0 = 8 wave + lane / 8; K chunk (8 elements) that lands on LDS position
   // lane % 8 of those rows (the swizzle key (row >> 1) & 7 is the same for rows 64 apart)
   const int rho0 = 8 * wave + (lane >> 3);
   const int chunk8 = ((lane & 7) ^ ((rho0 >> 1) & 7)) * 8;
   const unsigned a_pitch = (unsigned)K * 2u, a_last = (unsigned)(d.cout - 1) * a_pitch;
   const unsigned b_pitch = (unsigned)d.ldx * 2u, b_last = (unsigned)(M - 1) * b_pitch;
-  int iss_c0 = 0, iss_dt = 0, iss_dh = 0, iss_dw = 0;   // channel offset inside the tap, tap coordinates (wave-uniform)
+  // ---- issue side: the DMA stream, K tile by K tile across output tiles (all of this state is wave-uniform) ----
+  int iss_c0 = 0, iss_dt = 0, iss_dh = 0, iss_dw = 0;   // channel offset inside the tap, tap coordinates
   unsigned iss_wk = 0;                                  // byte offset of the stream's K tile inside a weight row
+  int iss_it = blockIdx.x, iss_ku = 0, iss_jt = 0;      // work item, K tile inside it, this workgroup's tile count
+  bool iss_live = iss_it < total_tiles;
   unsigned g_a_row = 0, g_b_row = 0;   // byte offsets of this thread's staging rows (half 0, j = 0) of the stream's output tile
   unsigned gm0 = 0, gm1 = 0, gm2 = 0, gm3 = 0;   // (TR, implicit GEMM) window masks of the four voxel rows [v][j]
   // Row maps (g4 = wave & 3, g2 = wave >> 2; DMA j of a unit covers its rows 64 j + rho0):
@@ -99,34 +91,20 @@ __global__ __launch_bounds__(kThreadsH) void gemm_quad_half_kernel(const pv_conv
     }
     iss_dt = rot;
     iss_wk = (unsigned)(rot * d.kh * d.kw * d.cin) * 2u;
-    if constexpr (!TR) g_a_row = (unsigned)(n0 + 64 * (rho0 >> 5) + chih(rho0 & 31)) * a_pitch;   // (h, j): 32 h + 128 j rows further, clamped at use
-    else g_a_row = (unsigned)(n0 + 32 * (rho0 >> 5) + chih(rho0 & 31)) * a_pitch;                 // j: 64 rows further
+    if constexpr (!TR) g_a_row = (unsigned)(n0 + 64 * (rho0 >> 5) + pv_chi(rho0 & 31)) * a_pitch;   // (h, j): 32 h + 128 j rows further, clamped at use
+    else g_a_row = (unsigned)(n0 + 32 * (rho0 >> 5) + pv_chi(rho0 & 31)) * a_pitch;                 // j: 64 rows further
     if constexpr (PW) {
       if constexpr (!TR) g_b_row = (unsigned)((int)m0 + rho0) * b_pitch;                          // j: 64 rows further, clamped at use
       else g_b_row = (unsigned)((int)m0 + 64 * (rho0 >> 5) + (rho0 & 31)) * b_pitch;              // (h, j): 32 h + 128 j rows further
     } else {
       int* geo = reinterpret_cast<int*>(smemh_raw + kGeoH) + tid * 4;
       unsigned msk4[4];
+      const PvWindow window_of{d, M, S_out, dil_t, dil_h, dil_w, chunk8};
 #pragma unroll
       for (int q4 = 0; q4 < (TR ? 4 : 2); ++q4) {
         const int j = q4 & 1, h = q4 >> 1;
         long m = TR ? m0 + 128 * j + 64 * (rho0 >> 5) + 32 * h + (rho0 & 31) : m0 + 64 * j + rho0;
-        m = m < M ? m : M - 1;                              // M tail: a clamped row, never stored
-        const unsigned b = (unsigned)m / (unsigned)S_out;
-        const unsigned sp = (unsigned)m - b * (unsigned)S_out;
-        const unsigned to = sp / (unsigned)(d.Ho * d.Wo);
-        const unsigned r2 = sp - to * (unsigned)(d.Ho * d.Wo);
-        const unsigned ho = r2 / (unsigned)d.Wo;
-        const int t0 = (int)to * d.st - d.pt, h0 = (int)ho * d.sh - d.ph, w0 = (int)(r2 - ho * (unsigned)d.Wo) * d.sw - d.pw;
-        geo[q4] = (int)((long)b * d.x_bs + ((long)(t0 * d.Hi + h0) * d.Wi + w0) * d.ldx) + chunk8;
-        unsigned msk = 0u;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          if (q < d.kt && (unsigned)(t0 + q * dil_t) < (unsigned)d.Ti) msk |= 1u << q;
-          if (q < d.kh && (unsigned)(h0 + q * dil_h) < (unsigned)d.Hi) msk |= 1u << (8 + q);
-          if (q < d.kw && (unsigned)(w0 + q * dil_w) < (unsigned)d.Wi) msk |= 1u << (16 + q);
-        }
-        msk4[q4] = msk;
+        window_of(m, geo[q4], msk4[q4]);
       }
       if constexpr (TR) {       // 16 bytes of LDS per thread hold the four offsets; the masks stay in registers
         gm0 = msk4[0]; gm1 = msk4[1]; gm2 = msk4[2]; gm3 = msk4[3];
@@ -136,16 +114,9 @@ __global__ __launch_bounds__(kThreadsH) void gemm_quad_half_kernel(const pv_conv
     }
   };
 
-  // ---- issue side: the DMA stream, K tile by K tile across output tiles (all of this state is wave-uniform) ----
-  int iss_it = blockIdx.x, iss_ku = 0, iss_jt = 0;   // work item, K tile inside it, this workgroup's tile count
-  bool iss_live = iss_it < total_tiles;
   geom_of(iss_live ? iss_it : 0);
 
-  // source selection with bit masks, not `?:` (a select between two pointers becomes two exec-masked DMAs)
-  auto pick = [&](bool ok, unsigned long p) __attribute__((always_inline)) -> const bf16_t* {
-    const unsigned long m = 0ul - (unsigned long)ok;
-    return reinterpret_cast<const bf16_t*>((p & m) | (zaddr & ~m));
-  };
+  auto pick = [&](bool ok, unsigned long p) __attribute__((always_inline)) { return pv_pick(ok, p, zaddr); };
   auto dma_w = [&](int rows, int unit, int j) __attribute__((always_inline)) {   // one weight row per lane: g_a_row + rows
     unsigned off = g_a_row + (unsigned)rows * a_pitch;
     off = (off < a_last ? off : a_last) + iss_wk + (unsigned)(chunk8 * 2);   // N tail: a clamped row, zeroed in the epilogue
@@ -176,54 +147,24 @@ __global__ __launch_bounds__(kThreadsH) void gemm_quad_half_kernel(const pv_conv
     if constexpr (!TR) dma_x(64 * j, gq[j], (unsigned)gq[2 + j], 3 * buf + 2, j);
     else dma_w(64 * j, 3 * buf + 2, j);
   };
-  auto load_geo = [&]() __attribute__((always_inline)) -> i32x4h {
-    if constexpr (PW) {
-      return i32x4h{0, 0, 0, 0};
-    } else {
-      unsigned t = threadIdx.x;   // (rebuilt behind an empty asm: see pv_gemm9.hip)
-      asm volatile("" : "+v"(t));
-      return *reinterpret_cast<const i32x4h*>(smemh_raw + kGeoH + t * 16u);
-    }
-  };
-  // folded BatchNorm / bias tables of the stream's tile -> LDS, one 4-byte DMA per thread (wave w < 4: scale[64 w .. 64 w + 63]
-  // of the tile's 256 channels, w >= 4: shift).  Extra DMAs inside the counted windows only make the waits stricter.
-  auto issue_tables = [&]() __attribute__((always_inline)) {
-    const float* tab = wave < 4 ? d.scale : d.shift;
-    if (tab != nullptr && iss_live) {
-      long m0;
-      int n0;
-      tile_origin(iss_it, m0, n0);
-      int n = n0 + 64 * (wave & 3) + lane;
-      n = n < d.cout ? n : d.cout - 1;
-      __builtin_amdgcn_global_load_lds((gptrh_t)(tab + n), (lptrh_t)(smemh_raw + kTabH + (iss_jt & 1) * 2048 + wave * 256), 4, 0, 0);
-    }
-  };
-  auto advance = [&]() __attribute__((always_inline)) {   // next K tile of the stream
-    ++iss_ku;
-    iss_wk += 128u;
-    if constexpr (!PW) {
-      iss_c0 += 64;
-      if (iss_c0 == d.cin) {
-        iss_c0 = 0;
-        if (++iss_dw == d.kw) {
-          iss_dw = 0;
-          if (++iss_dh == d.kh) {
-            iss_dh = 0;
-            if (++iss_dt == d.kt) { iss_dt = 0; iss_wk = 0u; }   // (a rotated reduction wraps to tap 0 = weight column 0)
-          }
-        }
-      }
-    }
-    if (iss_ku == nk) {
-      iss_ku = 0;
-      iss_wk = 0u;
-      iss_it += gridDim.x;
-      ++iss_jt;
-      iss_live = iss_it < total_tiles;
-      if (iss_live) geom_of(iss_it);
-      issue_tables();
-    }
-  };
+  auto load_geo = [&]() __attribute__((always_inline)) { return pv_load_geo<PW, 16u>(smemh_raw + kGeoH, 0u); };
+  const PvIssueTables<PvTileOrder<BM, BN>> tables{wave, d, iss_live, tile_origin, iss_it, lane, iss_jt};
+  auto issue_tables = [&]() __attribute__((always_inline)) { tables(smemh_raw + kTabH); };
+  const PvTapAdvance<PW, decltype(geom_of), decltype(issue_tables)> advance{   // next K tile of the stream
+      iss_ku,         // K tile inside the work item
+      iss_wk,         // byte offset inside a weight row
+      iss_c0,         // channel offset inside the tap
+      d,
+      iss_dw,         // tap coordinates
+      iss_dh,
+      iss_dt,
+      nk,
+      iss_it,         // work item
+      iss_jt,         // tile count
+      iss_live,
+      total_tiles,
+      geom_of,
+      issue_tables};
 
   // ---- read side: this lane's fragment position inside a unit, as a BYTE offset from the LDS base ----
   // split unit h: row 32 g4 + (lane & 31); whole unit: row 64 g2 + 32 h + (lane & 31) (h = 1: + 4096 bytes, same swizzle key).
@@ -241,13 +182,8 @@ __global__ __launch_bounds__(kThreadsH) void gemm_quad_half_kernel(const pv_conv
   typedef const __attribute__((address_space(3))) bf16x8* lfragh_t;
 #define PVH_RD(BASE, S, BYTES) (*(lfragh_t)(unsigned long)(((BASE) ^ ((S) * 32u)) + (unsigned)(BYTES)))
 
-  // s_waitcnt simm16 on gfx9: vmcnt = bits [3:0] | [15:14]; expcnt [6:4] "no wait"; lgkmcnt [11:8] = 0
-  constexpr auto vml = [](int n) { return (n & 15) | ((n >> 4) << 14) | (7 << 4); };
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  constexpr unsigned kOOB = 0x80000000u;
   constexpr int kStores = YF32 ? 16 : 8;   // stores per thread and output tile (whatever is masked)
-  __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-      d.y, 0, (int)((unsigned)d.B * (unsigned)d.y_bs * (YF32 ? 4u : 2u)), 0x00020000);
+  __amdgpu_buffer_rsrc_t ry = pv_epi_rsrc(d, YF32);
 
   // ---- prologue: the first tile's tables, K tiles 0 and 1 in stream order (A0, B, A1) ----
   issue_tables();
@@ -257,7 +193,7 @@ __global__ __launch_bounds__(kThreadsH) void gemm_quad_half_kernel(const pv_conv
     advance();
     issue_s(0, 1, 0, gq); issue_s(0, 1, 1, gq); issue_w(1, 0, gq); issue_w(1, 1, gq); issue_s(1, 1, 0, gq); issue_s(1, 1, 1, gq);
   }
-  __builtin_amdgcn_s_waitcnt(vml(8));   // A0, B of K tile 0: this thread's share
+  __builtin_amdgcn_s_waitcnt(pv_vml(8));   // A0, B of K tile 0: this thread's share
   __builtin_amdgcn_s_barrier();
   const bool half_b = wave >= 4;        // wave-uniform
   if (half_b) __builtin_amdgcn_s_barrier();   // the offset between the two halves
@@ -270,8 +206,8 @@ __global__ __launch_bounds__(kThreadsH) void gemm_quad_half_kernel(const pv_conv
   // one phase:  [reads] wait(N) | B1 | 8 MFMAs with the phase's three DMAs behind MFMA 2, 4 and 6 | B2
 #define PVH_WAIT_B1(FIRST, N)                                                                       \
   do {                                                                                              \
-    if ((FIRST) && stores_behind) __builtin_amdgcn_s_waitcnt(vml((N) + kStores));                   \
-    else __builtin_amdgcn_s_waitcnt(vml(N));                                                        \
+    if ((FIRST) && stores_behind) __builtin_amdgcn_s_waitcnt(pv_vml((N) + kStores));                \
+    else __builtin_amdgcn_s_waitcnt(pv_vml(N));                                                     \
     __builtin_amdgcn_s_barrier();                                                                   \
     __builtin_amdgcn_sched_barrier(0);                                                              \
   } while (0)
@@ -369,124 +305,20 @@ __global__ __launch_bounds__(kThreadsH) void gemm_quad_half_kernel(const pv_conv
       e_sp[v] = mm - e_b[v] * S_out;
     }
     const float* tabs = reinterpret_cast<const float*>(smemh_raw + kTabH + (jt & 1) * 2048);
-    typedef f32x4 res_t[2][2][2];   // [v][h8][half]: 8 channels as 2 x f32x4 (fp32) or 1 x 16 bytes (bf16)
-    auto load_res = [&](int a, res_t& res) __attribute__((always_inline)) {
-      if (d.residual == nullptr) return;
-      const int cb = n0 + wn * 64 + a * 32 + 16 * hi;
-#pragma unroll
-      for (int v = 0; v < 2; ++v)
-#pragma unroll
-        for (int h8 = 0; h8 < 2; ++h8) {
-          const bool ok = e_ok[v] && cb + h8 * 8 < cout_p8;
-          const long ro = ok ? e_b[v] * d.r_bs + e_sp[v] * d.ldr + cb + h8 * 8 : 0;
-          if (d.r_f32) {
-            const float* rp = static_cast<const float*>(d.residual) + ro;
-            res[v][h8][0] = *reinterpret_cast<const f32x4*>(rp);
-            res[v][h8][1] = *reinterpret_cast<const f32x4*>(rp + 4);
-          } else {
-            res[v][h8][0] = *reinterpret_cast<const f32x4*>(static_cast<const bf16_t*>(d.residual) + ro);
-          }
-        }
-    };
-    auto finish = [&](int a, const res_t& res) __attribute__((always_inline)) {
-      const int cl = wn * 64 + a * 32 + 16 * hi;   // channel inside the tile
-      const int cb = n0 + cl;
-      if (d.scale != nullptr) {
-        f32x4 sc[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sc[q] = *reinterpret_cast<const f32x4*>(tabs + cl + 4 * q);
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] *= sc[r >> 2][r & 3];
-      }
-      if (d.shift != nullptr) {
-        f32x4 sh[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sh[q] = *reinterpret_cast<const f32x4*>(tabs + 256 + cl + 4 * q);
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] += sh[r >> 2][r & 3];
-      }
-      if (d.residual != nullptr) {
-        if (d.r_f32) {
-#pragma unroll
-          for (int v = 0; v < 2; ++v)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][v][r] += res[v][r >> 3][(r >> 2) & 1][r & 3];
-        } else {
-#pragma unroll
-          for (int v = 0; v < 2; ++v)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][v][r] += (float)__builtin_bit_cast(bf16x8, res[v][r >> 3][0])[r & 7];
-        }
-      }
-      if (d.act == PV_ACT_RELU) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] = fmaxf(acc[a][v][r], 0.f);
-      } else if (d.act == PV_ACT_GELU) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] = pv_gelu_fast(acc[a][v][r]);
-      } else if (d.act == PV_ACT_SWISH) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] *= pv_sigmoid(acc[a][v][r]);
-      } else if (d.act == PV_ACT_SIGMOID) {
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] = pv_sigmoid(acc[a][v][r]);
-      }
-      if (cb + 16 > d.cout) {   // ragged last channel tile: the padding up to the 8-multiple is written as zeros
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][v][r] = cb + r < d.cout ? acc[a][v][r] : 0.f;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
+    const PvEpiLoadRes<2, 64> load_res{d, n0, wn, hi, e_ok, cout_p8, e_b, e_sp};
+    const PvEpiFinish<2, 2, 64> finish{d, acc, tabs, n0, wn, hi};
     {   // (literal channel-half indices: see pv_gemm9.hip)
-      res_t r0;
+      pv_epi_res_t<2> r0;
       load_res(0, r0);
       finish(0, r0);
+      __builtin_amdgcn_sched_barrier(0);
       load_res(1, r0);
       finish(1, r0);
+      __builtin_amdgcn_sched_barrier(0);
     }
     // ... then nothing but stores (kStores of them, whatever is masked)
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const int cb = n0 + wn * 64 + a * 32 + 16 * hi;
-#pragma unroll
-      for (int v = 0; v < 2; ++v) {
-        const unsigned yo = (unsigned)(e_b[v] * d.y_bs + e_sp[v] * d.ldy + cb);
-#pragma unroll
-        for (int h8 = 0; h8 < 2; ++h8) {
-          const bool ok = e_ok[v] && cb + h8 * 8 < cout_p8;
-          const int r0 = h8 * 8;
-          if constexpr (YF32) {
-            const unsigned off = ok ? (yo + r0) * 4u : kOOB;
-            __builtin_amdgcn_raw_buffer_store_b128(
-                u32x4{__float_as_uint(acc[a][v][r0 + 0]), __float_as_uint(acc[a][v][r0 + 1]),
-                      __float_as_uint(acc[a][v][r0 + 2]), __float_as_uint(acc[a][v][r0 + 3])}, ry, (int)off, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(
-                u32x4{__float_as_uint(acc[a][v][r0 + 4]), __float_as_uint(acc[a][v][r0 + 5]),
-                      __float_as_uint(acc[a][v][r0 + 6]), __float_as_uint(acc[a][v][r0 + 7])}, ry,
-                (int)(ok ? off + 16u : kOOB), 0, 0);
-          } else {
-            bf16x8 ob;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) ob[r] = (bf16_t)acc[a][v][r0 + r];
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ob), ry, (int)(ok ? (yo + r0) * 2u : kOOB), 0, 0);
-          }
-        }
-      }
-    }
+    const PvEpiStore<2, 2, 64, YF32> store{n0, wn, hi, e_b, d, e_sp, e_ok, cout_p8, acc, ry};
+    store();
     stores_behind = true;
     if (half_b) __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -500,21 +332,14 @@ __global__ __launch_bounds__(kThreadsH) void gemm_quad_half_kernel(const pv_conv
 #undef PVH_WAIT_B1
 #undef PVH_RD
   if (!half_b) __builtin_amdgcn_s_barrier();   // matches the second half's offset barrier
-  __builtin_amdgcn_s_waitcnt(vml(0));          // the stream's trailing (zero-page) DMAs land before the LDS is released
+  __builtin_amdgcn_s_waitcnt(pv_vml(0));       // the stream's trailing (zero-page) DMAs land before the LDS is released
 }
 
 template <bool PW, bool YF32, bool TR>
 int launch9h(const pv_conv3d_desc& d, int tiles_n, long total, hipStream_t s) {
-  const size_t lds = (size_t)kLdsHBytes;
-  auto kern = gemm_quad_half_kernel<PW, YF32, TR>;
-  PV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const long resident = 256;   // one workgroup per CU
-  dim3 grid((unsigned)(total < resident ? total : resident)), block(kThreadsH);
   const int tap_rot = !PW && d.kt > 1 && d.st == 1 && d.dil_t <= 1 && (d.Ho * d.Wo) % (TR ? 2 * BMH : BMH) == 0 && pv_tune("gemm9_tap_rot", 1);
-  PV_LAUNCH(kern, grid, block, lds, s, d, tiles_n, (int)total, tap_rot);
-  pv_note_kernel("gemm_quad_half_kernel");
-  PV_LAUNCH_CHECK();
-  return PV_OK;
+  return pv_gemm_launch_persistent(gemm_quad_half_kernel<PW, YF32, TR>, "gemm_quad_half_kernel", kThreadsH, (size_t)kLdsHBytes, total, s,
+                                   d, tiles_n, (int)total, tap_rot);
 }
 
 }  // namespace
@@ -524,18 +349,9 @@ int launch9h(const pv_conv3d_desc& d, int tiles_n, long total, hipStream_t s) {
 int pv_gemm9h_try(const pv_conv3d_desc& d, bool pw, hipStream_t s) {
   const int mode = pv_tune("gemm9h", 1);   // 0 off, 1 heuristic, 2 wherever the kernel can run
   if (mode == 0) return PV_ERR_UNSUPPORTED;
-  if (d.dtype != PV_BF16 || d.a_gate != nullptr || d.a_act != PV_ACT_NONE || d.x2 != nullptr) return PV_ERR_UNSUPPORTED;
-  if (d.kt > 8 || d.kh > 8 || d.kw > 8) return PV_ERR_UNSUPPORTED;                  // 8-bit window masks per axis
-  if (d.dil_t > 1 || d.dil_h > 1 || d.dil_w > 1) return PV_ERR_UNSUPPORTED;         // dilated: the 128 x 128 kernel (see pv_gemm9.hip)
-  const long K = (long)d.kt * d.kh * d.kw * d.cin;
-  if (d.cin % 64 != 0 || K % 192 != 0 || K < 384) return PV_ERR_UNSUPPORTED;        // a K step inside one tap; K tiles in triples
-  const long M = (long)d.B * d.To * d.Ho * d.Wo;
+  long M, K;
+  if (!pv_gemm_stream_geometry_ok(d, 192, 384, M, K)) return PV_ERR_UNSUPPORTED;   // K tiles in triples, at least two of them
   const int cout_p8 = pv_round_up(d.cout, 8);
-  // 31-bit element offsets into x, 32-bit byte offsets into w, 31-bit byte offsets in the store descriptor
-  if (M > 0x7fffffffL || (long)d.B * d.x_bs > 0x7fffffffL || ((long)d.cout + 256) * K * 2 > 0xffffffffL ||
-      (M + 256) * d.ldx * 2 > 0xffffffffL)
-    return PV_ERR_UNSUPPORTED;
-  if ((long)d.B * d.y_bs * (d.y_f32 ? 4 : 2) > 0x7fffffffL) return PV_ERR_UNSUPPORTED;
   // tile shape: 128 voxels x 256 channels where 256-channel tiles fit the layer, else the transposed 256 x 128 tile (SlowFast
   // res3's 1x3x3 convs: 128 channels) -- pv_tune "gemm9h_tr": -1 by the padding each shape costs, 0 / 1 forced
   const double waste256 = (double)(pv_ceil_div(cout_p8, BNH) * BNH - cout_p8) / (double)cout_p8;
@@ -556,12 +372,8 @@ int pv_gemm9h_try(const pv_conv3d_desc& d, bool pw, hipStream_t s) {
     if (total < (tr ? pv_tune("gemm9h_tr_min_tiles", 100) : pv_tune("gemm9h_min_tiles", 32))) return PV_ERR_UNSUPPORTED;
   }
   const bool rows = pw && d.x_bs == (long)d.To * d.Ho * d.Wo * d.ldx;
-#define PVH_GO(PWv, YFv)                                                \
-  return tr ? launch9h<PWv, YFv, true>(d, tiles_n, total, s) : launch9h<PWv, YFv, false>(d, tiles_n, total, s);
-  if (d.y_f32) {
-    if (rows) { PVH_GO(true, true) } else { PVH_GO(false, true) }
-  } else {
-    if (rows) { PVH_GO(true, false) } else { PVH_GO(false, false) }
-  }
+#define PVH_GO(PWv, YFv) \
+  return tr ? launch9h<PWv, YFv, true>(d, tiles_n, total, s) : launch9h<PWv, YFv, false>(d, tiles_n, total, s)
+  PV_GEMM_PW_YF32(rows, d.y_f32, PVH_GO);
 #undef PVH_GO
 }

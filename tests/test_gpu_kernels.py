@@ -947,8 +947,11 @@ def test_lateral_fusion_writes_the_slow_buffers_channel_slice(dtype, B, Ti, H, W
 
 
 # ------------------------------------------------------------------ large-tile GEMM (256-voxel tiles, 4-stage LDS ring)
-def _gemm8_case(ct, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, knob="gemm8"):
-    """pv_conv3d forced onto a large-tile kernel (pv_tune gemm8 = 2 | 4, or gemm9 = 2) vs torch on the same bf16-rounded data."""
+def _dense_gemm_case(ct, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, knob="gemm8", with_shift=True):
+    """pv_conv3d forced onto one of the four dense GEMM kernels vs torch on the same bf16-rounded data: knob "gemm8" (ct = 2 | 4: the
+    ring kernel's tile), "gemm9" / "gemm9h" (the eight-phase kernels) or "gemm" (the 128 x 128 kernel: conv_route = 2, the others
+    off).  with_shift = False: no shift table.  The knobs are put back to the library's defaults (conv_route 0, gemm8 / gemm9 / gemm9h 1),
+    as every test here does: the binding has no getter."""
     dtype = torch.bfloat16
     pad = tuple(kk // 2 for kk in k)
     g = torch.Generator().manual_seed(7 * cin + cout)
@@ -964,25 +967,30 @@ def _gemm8_case(ct, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, k
         want = F.conv3d(x.float().permute(0, 4, 1, 2, 3), w.float(), stride=stride, padding=pad)
     if affine:
         want = want * scale.view(1, -1, 1, 1, 1)
-    want = want + shift.view(1, -1, 1, 1, 1)
+    if with_shift:
+        want = want + shift.view(1, -1, 1, 1, 1)
     To, Ho, Wo = want.shape[2:]
     cp = (cout + 7) // 8 * 8
     r = None
     if res:
         r = torch.randn(B, To, Ho, Wo, cp, generator=g).to(torch.float32 if y_f32 else dtype).cuda()
         want = want + r[..., :cout].float().permute(0, 4, 1, 2, 3)
-    want = {L.ACT_NONE: lambda t: t, L.ACT_RELU: F.relu, L.ACT_GELU: F.gelu}[act](want)
+    want = {L.ACT_NONE: lambda t: t, L.ACT_RELU: F.relu, L.ACT_GELU: F.gelu, L.ACT_SWISH: F.silu, L.ACT_SIGMOID: torch.sigmoid}[act](want)
     y = torch.full((B, To, Ho, Wo, cp), 5.0, dtype=torch.float32 if y_f32 else dtype, device="cuda")
     wp = w.permute(0, 2, 3, 4, 1).reshape(cout, -1).contiguous()
     d = L.Conv3dDesc()
-    d.x, d.w, d.y, d.shift = x.data_ptr(), wp.data_ptr(), y.data_ptr(), shift.data_ptr()
+    d.x, d.w, d.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
+    d.shift = shift.data_ptr() if with_shift else None
     d.scale = scale.data_ptr() if affine else None
     d.residual = r.data_ptr() if res else None
     d.x_bs, d.y_bs, d.r_bs, d.ldx, d.ldy, d.ldr = T * H * W * cin, To * Ho * Wo * cp, To * Ho * Wo * cp, cin, cp, cp
     d.B, d.Ti, d.Hi, d.Wi, d.cin, d.To, d.Ho, d.Wo, d.cout = B, T, H, W, cin, To, Ho, Wo, cout
     d.kt, d.kh, d.kw, d.st, d.sh, d.sw, d.pt, d.ph, d.pw = (*k, *stride, *pad)
     d.act, d.a_act, d.dtype, d.y_f32, d.r_f32 = act, L.ACT_NONE, L.PV_BF16, int(y_f32), int(y_f32 and res)
-    L.tune(**{knob: ct})
+    if knob == "gemm":
+        L.tune(conv_route=2, gemm8=0, gemm9=0)
+    else:
+        L.tune(**{knob: ct})
     if knob == "gemm8":                  # pv_conv3d asks the eight-phase kernels first: keep them away from the ring kernel's cases
         L.tune(gemm9=0)
     try:
@@ -991,9 +999,14 @@ def _gemm8_case(ct, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, k
         got1 = y.clone()
         call("pv_conv3d", d)                       # a second launch gives the same bits
     finally:
-        L.tune(**{knob: 1})
+        if knob == "gemm":
+            L.tune(conv_route=0, gemm8=1)
+        else:
+            L.tune(**{knob: 1})
         L.tune(gemm9=1)
-    if knob in ("gemm9", "gemm9h"):
+    if knob == "gemm":
+        assert routed == "gemm_glds_kernel", routed
+    elif knob in ("gemm9", "gemm9h"):
         assert routed == {"gemm9": "gemm_quad_kernel", "gemm9h": "gemm_quad_half_kernel"}[knob], routed
     elif cin * k[0] * k[1] * k[2] >= 192 and (k == (1, 1, 1) or cin >= 64):
         # the ring kernel takes every forced case pv_conv3d offers it (pointwise, or >= 64 input channels) with at least three
@@ -1017,7 +1030,7 @@ def _gemm8_case(ct, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, k
     (1, 32, 6, 6, 128, 256, (7, 1, 1), (4, 1, 1), L.ACT_RELU, False, False, True),      # lateral-shaped (7,1,1) / stride 4
 ])
 def test_large_tile_gemm_kernel(ct, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine):
-    _gemm8_case(ct, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine)
+    _dense_gemm_case(ct, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine)
 
 
 # ------------------------------------------------------------------ temporal-tap rotation / uniform-tap staging of the 128 x 128 GEMM
@@ -1082,7 +1095,7 @@ def test_temporal_conv_tap_rotation_and_uniform_tap_staging(B, T, H, W, cin, cou
     (2, 4, 16, 16, 256, 512, (1, 1, 1), (1, 2, 2), L.ACT_NONE, False, False, True),     # projection shortcut: strided 1x1x1
 ])
 def test_quad_phase_gemm_kernel(B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine):
-    _gemm8_case(2, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, knob="gemm9")
+    _dense_gemm_case(2, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, knob="gemm9")
 
 
 # ------------------------------------------------------------------ the same loop on 128 x 256 tiles, three LDS buffers (pv_gemm9h.hip)
@@ -1104,7 +1117,7 @@ def test_quad_phase_gemm_kernel(B, T, H, W, cin, cout, k, stride, act, res, y_f3
     (2, 4, 16, 16, 384, 512, (1, 1, 1), (1, 2, 2), L.ACT_NONE, False, False, True),     # projection shortcut: strided 1x1x1
 ])
 def test_quad_phase_gemm_kernel_on_half_height_tiles(B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine):
-    _gemm8_case(2, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, knob="gemm9h")
+    _dense_gemm_case(2, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, knob="gemm9h")
 
 
 @pytest.mark.parametrize("B,T,H,W,cin,cout,k,stride,act,res,y_f32,affine", [
@@ -1124,11 +1137,22 @@ def test_quad_phase_gemm_kernel_on_transposed_half_tiles(B, T, H, W, cin, cout, 
     """pv_gemm9h.hip with the 256 (voxels) x 128 (channels) tile: the voxel rows are the split operand."""
     L.tune(gemm9h_tr=1)
     try:
-        _gemm8_case(2, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, knob="gemm9h")
+        _dense_gemm_case(2, B, T, H, W, cin, cout, k, stride, act, res, y_f32, affine, knob="gemm9h")
     finally:
         L.tune(gemm9h_tr=-1)
 
 
+
+
+# the epilogue branches no other kernel-level case reaches, on each of the four dense GEMM kernels: pointwise, M = 100 (less than one
+# tile, an M tail), K = 384 (the smallest all four accept), 70 channels (a ragged last channel tile, two padding channels)
+@pytest.mark.parametrize("knob", ["gemm", "gemm8", "gemm9", "gemm9h"])
+@pytest.mark.parametrize("act,res_f32,affine,with_shift", [
+    (L.ACT_SWISH, False, True, False),      # swish, scale without shift, bf16 residual
+    (L.ACT_SIGMOID, True, False, True),     # sigmoid, shift without scale, fp32 residual and output
+])
+def test_dense_gemm_epilogue_swish_sigmoid_scale_only_shift_only(knob, act, res_f32, affine, with_shift):
+    _dense_gemm_case(2, 1, 1, 1, 100, 384, 70, (1, 1, 1), (1, 1, 1), act, True, res_f32, affine, knob=knob, with_shift=with_shift)
 
 
 # temporal-tap rotation of the eight-phase kernels (whole tiles inside one output frame, temporal stride 1): the tile of output
@@ -1150,9 +1174,9 @@ def test_quad_phase_gemm_kernel_on_transposed_half_tiles(B, T, H, W, cin, cout, 
 def test_eight_phase_kernels_temporal_tap_rotation(knob, tr, B, T, H, W, cin, cout, k, stride):
     L.tune(gemm9h_tr=tr)
     try:
-        _gemm8_case(2, B, T, H, W, cin, cout, k, stride, L.ACT_RELU, False, False, True, knob=knob)
+        _dense_gemm_case(2, B, T, H, W, cin, cout, k, stride, L.ACT_RELU, False, False, True, knob=knob)
         L.tune(gemm9_tap_rot=0)            # ... and the same stream code without the rotation
-        _gemm8_case(2, B, T, H, W, cin, cout, k, stride, L.ACT_RELU, False, False, True, knob=knob)
+        _dense_gemm_case(2, B, T, H, W, cin, cout, k, stride, L.ACT_RELU, False, False, True, knob=knob)
     finally:
         L.tune(gemm9h_tr=-1, gemm9_tap_rot=1)
 
