@@ -561,11 +561,13 @@ int pv_yuv16_views(const pv_yuv_views_desc* d, pv_stream_t stream);
  *               tile footprint beyond the LDS limit.
  */
 enum { PV_SRC_YUV420 = 2 };   /* pv_batch_views_desc.src_layout only, beside pv_resample_src_layout */
+/* Packed pixels (see "packed pixels" below); pv_batch_views_desc.src_layout only.  The value 3 is no layout. */
+enum { PV_SRC_BGR = 4, PV_SRC_RGBA = 5, PV_SRC_BGRA = 6, PV_SRC_ARGB = 7, PV_SRC_ABGR = 8 };
 typedef struct pv_view_source {      /* one decoded video; 96 bytes, 8-byte aligned */
   const void* src;                   /* device address of the video / of frame 0                              */
-  int64_t frame_stride;              /* YUV sources: bytes between frames (RGB / planar sources: dense)       */
+  int64_t frame_stride;              /* YUV and packed sources: bytes between frames (RGB / planar: dense)    */
   int64_t u_offset, v_offset;        /* YUV sources, as in pv_yuv_views_desc                                   */
-  int32_t y_pitch, c_pitch;          /* YUV sources                                                            */
+  int32_t y_pitch, c_pitch;          /* YUV sources; packed pixels: y_pitch = the row pitch, c_pitch = 0      */
   int32_t N, Hs, Ws;                 /* frames, frame size                                                     */
   int32_t Hn, Wn;                    /* size after scaling                                                     */
   int32_t y_off[3], x_off[3];        /* per view: window origin inside Hn x Wn                                 */
@@ -586,7 +588,7 @@ typedef struct pv_batch_views_desc {
   int64_t bs;                         /* PV_DST_NDHWC only: batch stride in elements                           */
   int32_t n_sources, n_items, n_rows, t_stride;
   int32_t C, T;                       /* channels (<= 4; 3 for YUV), DESTINATION frames per item               */
-  int32_t src_dtype, src_layout;      /* pv_dtype; PV_SRC_NCTHW / PV_SRC_NTHWC / PV_SRC_YUV420                 */
+  int32_t src_dtype, src_layout;      /* pv_dtype; PV_SRC_NCTHW / PV_SRC_NTHWC / PV_SRC_YUV420 / PV_SRC_BGR .. */
   int32_t c_step;                     /* PV_SRC_YUV420: 2 interleaved chroma, 1 planar                         */
   int32_t Ho, Wo, n_views;            /* crop window; views per clip, 1..3                                     */
   int32_t dst_layout, dst_dtype;
@@ -773,6 +775,44 @@ typedef struct pv_area_views_desc {
   int32_t reserved[3];                /* 0                                                                                */
 } pv_area_views_desc;                 /* sizeof(pv_frame_views_desc) + 16 */
 int pv_area_views(const pv_area_views_desc* d, pv_stream_t stream);
+
+/* ---- packed pixels: BGR24 and 32-bit RGBA / BGRA / ARGB / ABGR surfaces read where they lie ---------------------------------
+ * An OpenCV pipeline holds BGR24; screen capture, colour converters, compositor / DRM / GL surfaces and `-pix_fmt bgra|rgb0`
+ * hand out 32-bit pixels, usually PITCHED.  PV_SRC_NTHWC is dense R,G,B only, so such frames needed a channel-select pass plus
+ * copy over the whole video before the launch.  Five more values of pv_batch_views_desc.src_layout (declared beside
+ * PV_SRC_YUV420; the value 3 is no layout and stays PV_ERR_INVALID) name them:
+ *                   PV_SRC_BGR   3 bytes a pixel: B G R           PV_SRC_RGBA  4 bytes: R G B x       PV_SRC_BGRA  4 bytes: B G R x
+ *                   PV_SRC_ARGB  4 bytes: x R G B                 PV_SRC_ABGR  4 bytes: x B G R
+ *               The layout alone gives the pixel size PB (3 or 4) and the bytes of R, G and B inside a pixel; x (alpha, or
+ *               the unused byte of RGBX / BGRX / XRGB / XBGR) never enters a value.
+ * Honoured by:  pv_batch_views, pv_frame_views, pv_region_views and pv_area_views -- whole videos and frame lists, orient 0..7
+ *               where the entry point takes it, up to three views, all five destination forms.  NOT by pv_hdr_views (16-bit
+ *               YUV only) and not by the one-source entry points (pv_resample_crop, pv_video_views, pv_yuv_views,
+ *               pv_yuv16_views): their refusals are what they were.
+ * Record:       src_dtype PV_U8 and C == 3 (the launch); per pv_view_source
+ *                   pixel(y, x) = frame + y * y_pitch + x * PB                        0 <= y < Hs, 0 <= x < Ws
+ *               y_pitch: the ROW PITCH IN BYTES, >= Ws * PB.  frame_stride: the bytes between frames (whole videos) or the
+ *               extent of one frame (frame lists), >= (Hs - 1) * y_pitch + Ws * PB.  u_offset, v_offset and c_pitch are 0.
+ *               PB == 4: src -- or every frame address of a list --, y_pitch and frame_stride are multiples of 4: a pixel is
+ *               one aligned dword.  PB == 3: any byte base, any pitch.  A column slice of a wider surface is a record whose
+ *               src points at the slice's first pixel and whose y_pitch is the surface's.
+ *               Only the aligned 16-byte granules that cover a byte of a staged span are fetched, as for every other source,
+ *               so a surface that ends at the end of its allocation is read safely; the bytes between Ws * PB and the pitch
+ *               are never read from the staged rows.
+ * Arithmetic:   nothing new happens to a value: the taps, the pinned coordinate, the blend order, the windows and the
+ *               summation order of pv_area_views, the rectangles of pv_region_views, the affine map and the single rounding are
+ *               those of the PV_SRC_NTHWC path.  AN ITEM OF A PACKED LAUNCH HOLDS, BIT FOR BIT, WHAT THE SAME ENTRY POINT WRITES
+ *               WITH PV_SRC_NTHWC FOR THE DENSE [N,Hs,Ws,3] R,G,B COPY OF THE SAME FRAMES -- whatever else shares the launch,
+ *               and for a frame list as for the stacked video.
+ * Kernels:      pixel size is compiled in (two source forms), the three byte offsets are a workgroup-uniform kernel argument;
+ *               a 4-byte pixel is one dword LDS read per tap with the channels taken out of the register, a 3-byte pixel
+ *               three byte reads (pytorchvideo_amd/csrc/pv_packed.hip).
+ * PV_ERR_INVALID: y_pitch < Ws * PB; frame_stride < (Hs - 1) * y_pitch + Ws * PB; a non-zero u_offset, v_offset or c_pitch;
+ * src_dtype != PV_U8 or C != 3; PB == 4 with a src, frame address, y_pitch or frame_stride that is no multiple of 4; and
+ * whatever the entry point rejects of any launch.  PV_ERR_UNSUPPORTED: unchanged in meaning (the LDS limits of a staged strip
+ * or tile -- a column counts PB bytes --, the index limit of pv_area_views, src_dtype PV_U16 outside YUV).  Validation precedes
+ * every HIP call, and an invalid field wins over an unsupported size.
+ */
 
 /* ---- key-frame detection: the boxes of a forward mapped into its views, on the device ---------------------------------
  * A detection forward built by pv_batch_views holds one clip per key frame, and every key frame has person boxes given in the

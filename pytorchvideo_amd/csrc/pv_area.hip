@@ -26,147 +26,12 @@
 // In front of the body stand the item loader and the geometry builders of pv_rs.h, serving whole videos and frame lists
 // (`frames` is workgroup-uniform, as in pv_orient.hip); the body does not read sy / sx: its windows are integers.
 // 3 RGB / planar forms and 2 chroma arrangements x 2 sample widths, x 5 destination forms: 35 kernels.
-#include "pv_frames.h"
+#include "pv_area.h"
 
 namespace {
 
-// What stays per launch: filled by ar_size.
-struct ArLaunch {
-  int32_t R, X;             // output rows x columns per workgroup; X a multiple of 8
-  int32_t tiles_x;          // column tiles per window row
-  int32_t rows, pitch;      // staged source rows, LDS bytes per staged (row, plane) -- YUV: luma
-  int32_t rows_c, pitch_c, c_base;   // YUV: staged chroma rows, LDS bytes per chroma (row, plane), LDS offset of the chroma image
-  int32_t out_base;         // LDS offset of the fp32 results [c][R][X]; a multiple of 16
-};
-
+// ArLaunch, the tile of a workgroup, the store and ar_tile_rgb are in pv_area.h: pv_packed.hip instantiates them too.
 constexpr int kArTiles[][2] = {{8, 64}, {8, 32}, {4, 32}, {4, 16}, {2, 16}, {2, 8}, {1, 8}};   // R x X, largest first
-
-// The tile of this workgroup and the source rectangle under it.
-struct ArTile {
-  int row0, col0, nrows, ncols;
-  int ys0, ys1, xs0, xs1;   // source rows [ys0, ys1) x columns [xs0, xs1)
-};
-__device__ __forceinline__ ArTile ar_tile(const ArLaunch& g, int Ho, int Wo, int yoff, int xoff, int Hs, int Ws, int Hn, int Wn) {
-  ArTile a;
-  const int strip = blockIdx.x / g.tiles_x, tile_x = blockIdx.x - strip * g.tiles_x;
-  a.row0 = strip * g.R, a.col0 = tile_x * g.X;
-  a.nrows = min(g.R, Ho - a.row0), a.ncols = min(g.X, Wo - a.col0);
-  int unused;
-  rs_area_win(yoff + a.row0, Hs, Hn, a.ys0, unused);
-  rs_area_win(yoff + a.row0 + a.nrows - 1, Hs, Hn, unused, a.ys1);
-  rs_area_win(xoff + a.col0, Ws, Wn, a.xs0, unused);
-  rs_area_win(xoff + a.col0 + a.ncols - 1, Ws, Wn, unused, a.xs1);
-  return a;
-}
-
-// Step 3: the results of the tile, G x-adjacent pixels of one row per thread, to the destination.
-template <int FORM, typename D>
-__device__ __forceinline__ void ar_store(const float* res, const ArLaunch& g, const ArTile& a, const RsDst& d, int C, int zi, int t) {
-  constexpr int G = RsGroup<FORM, D>::G;
-  const int gpr = (a.ncols + G - 1) / G;           // groups per tile row
-  const int items = a.nrows * gpr;
-  for (int it = threadIdx.x; it < items; it += kRsThreads) {
-    const int r = it / gpr, gx = it - r * gpr;
-    float out[4][G];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int j = 0; j < G; ++j) out[c][j] = c < C ? res[(c * g.R + r) * g.X + gx * G + j] : 0.f;   // past ncols: not stored
-    const int x0 = a.col0 + gx * G;
-    rs_store_group<FORM, D, G>(d.dst, out, C, d.T, d.Ho, d.Wo, d.c_p, d.ld, d.bs, zi, t, a.row0 + r, x0, min(G, d.Wo - x0));
-  }
-}
-
-// S / INTER / FORM / D: as rs_strip_rgb.  Hn x Wn: the scaled frame the windows are counted in.
-template <typename S, bool INTER, int FORM, typename D>
-__device__ __forceinline__ void ar_tile_rgb(unsigned char* lds, const ArLaunch& g, const RsRgbSrc& s, int Hn, int Wn, const RsDst& d,
-                                            int zi, int t) {
-  constexpr int XB = INTER ? 3 : (int)sizeof(S);   // bytes from one source column to the next
-  const int tid = threadIdx.x;
-  const ArTile a = ar_tile(g, d.Ho, d.Wo, s.yoff, s.xoff, s.Hs, s.Ws, Hn, Wn);
-  if (a.nrows <= 0 || a.ncols <= 0) return;
-  const int planes = INTER ? 1 : d.C;
-  const int pitch = g.pitch;
-  const int nslots = a.ys1 - a.ys0;
-  const int span_bytes = (a.xs1 - a.xs0) * XB;
-  if (nslots > g.rows || span_bytes + 15 > pitch) return;
-
-  // byte address of column xs0 of source row y of plane `pl` of the selected frame
-  const long row_bytes = (long)s.Ws * XB;
-  const long frame_bytes = (long)s.Hs * row_bytes;
-  const long first = (s.clip_frame0 + s.ts) * frame_bytes + (long)a.xs0 * XB;
-  const long plane_bytes = INTER ? 0 : (long)s.N * frame_bytes;
-  auto row_addr = [&](int y, int pl) -> uintptr_t { return s.src + first + (long)pl * plane_bytes + (long)y * row_bytes; };
-
-  // ---- stage -------------------------------------------------------------------------------------------------
-  const int cpr = pitch >> 4;                      // 16-byte chunks per staged row
-  const int total = nslots * planes * cpr;
-  for (int base = tid; base < total; base += kRsThreads * 4) {
-    u32x4 val[4];
-    int off[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int idx = base + u * kRsThreads;
-      off[u] = -1;
-      if (idx < total) {
-        const int sp = idx / cpr, ch = idx - sp * cpr;
-        const int slot = sp / planes, pl = sp - slot * planes;
-        const uintptr_t ad = row_addr(a.ys0 + slot, pl);
-        if (ch * 16 < (int)(ad & 15) + span_bytes) {
-          val[u] = *reinterpret_cast<const u32x4*>((ad & ~(uintptr_t)15) + (uintptr_t)ch * 16);
-          off[u] = sp * pitch + ch * 16;
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (off[u] >= 0) *reinterpret_cast<u32x4*>(lds + off[u]) = val[u];
-  }
-  __syncthreads();
-
-  // ---- sum ---------------------------------------------------------------------------------------------------
-  float sc[4], sh[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    sc[c] = (d.ch_scale && c < d.C) ? d.ch_scale[c] : 1.f;
-    sh[c] = (d.ch_scale && d.ch_shift && c < d.C) ? d.ch_shift[c] : 0.f;
-  }
-  // the low address bits of a staged row: 32-bit arithmetic keeps `addr & 15`
-  const unsigned rb32 = (unsigned)row_bytes, pb32 = (unsigned)plane_bytes, a32 = (unsigned)(s.src + first);
-  float* res = reinterpret_cast<float*>(lds + g.out_base);
-  const int npix = a.nrows * a.ncols;
-  for (int p = tid; p < npix; p += kRsThreads) {
-    const int r = p / a.ncols, x = p - r * a.ncols;
-    int wy0, wy1, wx0, wx1;
-    rs_area_win(s.yoff + a.row0 + r, s.Hs, Hn, wy0, wy1);
-    rs_area_win(s.xoff + a.col0 + x, s.Ws, Wn, wx0, wx1);
-    float tot[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int cx = wx0; cx < wx1; ++cx) {
-      float cs[4] = {0.f, 0.f, 0.f, 0.f};          // the column sums, rows ascending
-      const int ox = (cx - a.xs0) * XB;
-      for (int cy = wy0; cy < wy1; ++cy) {
-        const int slot = cy - a.ys0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          if (c < d.C) {
-            const int pl = INTER ? 0 : c;
-            const int lo = (int)((a32 + (unsigned)pl * pb32 + (unsigned)cy * rb32) & 15u);
-            cs[c] += rs_tap<S>(lds, (slot * planes + pl) * pitch + lo + ox + (INTER ? c : 0));
-          }
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) tot[c] += cs[c];  // columns ascending
-    }
-    const float cnt = (float)((wy1 - wy0) * (wx1 - wx0));
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      if (c < d.C) res[(c * g.R + r) * g.X + x] = fmaf(tot[c] / cnt, sc[c], sh[c]);
-  }
-  __syncthreads();
-
-  ar_store<FORM, D>(res, g, a, d, d.C, zi, t);
-}
 
 // CSTEP / FORM / D / SMP: as rs_strip_yuv.
 template <int CSTEP, int FORM, typename D, typename SMP>
@@ -373,6 +238,7 @@ int ar_run(const pv_batch_views_desc& d, bool frames, const CheckSrc& check_src,
   ArLaunch g = {};
   size_t lds = 0;
   if (int e = ar_size(d, records, g, lds)) return e;
+  if (rs_packed_px(d.src_layout)) return pv_packed_area(d, frames, g, lds, stream);   // pv_packed.hip
   const int fr = frames ? 1 : 0;
   RS_SOURCE_FORMS(AR_RGB, AR_YUV);
   PV_LAUNCH_CHECK();

@@ -69,10 +69,11 @@ int bv_run(const pv_batch_views_desc& desc, pv_stream_t stream) {
   RsItemLaunch g;
   RsTileLaunch tg;
   size_t lds, lds_t;
-  const auto check_src = rs_check_video_src(desc.src_dtype);
+  const auto check_src = rs_check_video_src(desc.src_dtype, desc.src_layout);
   if (int e = rs_item_launch(desc, check_src, g, lds, tg, lds_t)) return e;
   // the strips of a run of upright items: the whole launch when no record is oriented
   auto upright = [&](const pv_batch_views_desc& d) -> int {
+    if (rs_packed_px(d.src_layout)) return pv_packed_strips(d, false, g, lds, stream);   // pv_packed.hip
     RS_SOURCE_FORMS(BV_RGB, BV_YUV);
     PV_LAUNCH_CHECK();
     return PV_OK;

@@ -24,7 +24,8 @@ inline auto fv_check_src(const pv_frame_views_desc& f) {
   const uintptr_t base = reinterpret_cast<uintptr_t>(f.frame_ptrs_dev);
   const uint64_t* table = f.frame_ptrs;
   const uint64_t n_table = (uint64_t)f.n_frame_ptrs;
-  const bool f32 = f.batch.src_dtype == PV_F32, u16 = f.batch.src_dtype == PV_U16;   // outside their layouts both are refused before
+  // outside their layouts both dtypes are refused before; a 4-byte packed pixel is one aligned dword, as an fp32 element is
+  const bool f32 = f.batch.src_dtype == PV_F32 || rs_packed_px(f.batch.src_layout) == 4, u16 = f.batch.src_dtype == PV_U16;
   return [=](const pv_view_source& v) {
     const uintptr_t at = reinterpret_cast<uintptr_t>(v.src);
     if (at < base || (at - base) % 8) return PV_ERR_INVALID;
@@ -47,7 +48,7 @@ template <typename Run> inline int fv_with_table(const pv_frame_views_desc& f, c
   const bool frames = f.frame_ptrs != nullptr;
   if (!frames && f.n_frame_ptrs != 0) return PV_ERR_INVALID;
   if (!supported) return PV_ERR_UNSUPPORTED;
-  if (!frames) return run(false, rs_check_video_src(f.batch.src_dtype));
+  if (!frames) return run(false, rs_check_video_src(f.batch.src_dtype, f.batch.src_layout));
   if (int e = fv_check_table(f)) return e;
   return run(true, fv_check_src(f));
 }

@@ -84,6 +84,7 @@ __global__ __launch_bounds__(kRsThreads) void orient_yuv_kernel(const pv_batch_v
 int pv_orient_launch(const pv_batch_views_desc& d, bool frames, const RsTileLaunch& g, size_t lds, pv_stream_t stream) {
   const int fr = frames ? 1 : 0;
   if (g.TR <= 0 || g.TC <= 0 || g.tiles_x <= 0) return PV_ERR_INVALID;   // not sized: no oriented item was announced
+  if (rs_packed_px(d.src_layout)) return pv_packed_tiles(d, frames, g, lds, stream);   // pv_packed.hip
   RS_SOURCE_FORMS(OV_RGB, OV_YUV);
   PV_LAUNCH_CHECK();
   return PV_OK;

@@ -25,25 +25,7 @@
 
 namespace {
 
-// The shared item with what is this entry point's own on top: the rectangle of the item's (row, t), clamped into the stored
-// frame before any address is formed -- top / left inside it, h / w at least 1 and ending inside it -- and its sy / sx.
-// (One function, the loader's call inside it: with the rectangle read by a function of its own behind the loader, its loads
-// are ordered otherwise and every kernel of this file changes -- profiles/r24/isa_vs_parent.md.)
-struct RgItem : RsItem {
-  int top, left, h, w;
-  float sy, sx;
-};
-__device__ __forceinline__ RgItem rg_item(const pv_batch_views_desc& d, const pv_view_region* __restrict__ regions, int frames, int zi,
-                                          int t) {
-  RgItem r{rs_item<RS_EITHER>(d, zi, t, frames)};
-  const pv_view_region* __restrict__ G = regions + r.at;
-  const int Hs = r.S->Hs, Ws = r.S->Ws;
-  r.top = min(max(G->top, 0), Hs - 1), r.left = min(max(G->left, 0), Ws - 1);
-  r.h = min(max(G->h, 1), Hs - r.top), r.w = min(max(G->w, 1), Ws - r.left);
-  r.sy = G->sy, r.sx = G->sx;
-  return r;
-}
-
+// The item with its rectangle is rg_item (pv_rs.h: the packed kernels of pv_packed.hip load it too).
 // S / INTER / FORM / D: as rs_strip_rgb.
 template <typename S, bool INTER, int FORM, typename D>
 __global__ __launch_bounds__(kRsThreads) void region_views_kernel(const pv_batch_views_desc d, const RsItemLaunch g, const int frames,
@@ -51,14 +33,7 @@ __global__ __launch_bounds__(kRsThreads) void region_views_kernel(const pv_batch
   extern __shared__ __attribute__((aligned(16))) unsigned char rg_lds[];
   const int t = blockIdx.y;
   const int zi = blockIdx.z;                       // destination item of this launch
-  const RgItem item = rg_item(d, regions, frames, zi, t);
-  RsRgbWin s;
-  static_cast<RsRgbSrc&>(s) = rs_item_rgb(item);
-  s.Hf = s.Hs, s.Wf = s.Ws;                        // the stored frame keeps the strides; the body's source is the rectangle
-  s.top = item.top, s.left = item.left;
-  s.Hs = item.h, s.Ws = item.w;
-  s.sy = item.sy, s.sx = item.sx;
-  s.yoff = 0, s.xoff = 0;
+  const RsRgbWin s = rg_item_rgb(rg_item(d, regions, frames, zi, t));
   rs_strip_rgb<S, INTER, FORM, D>(rg_lds, g.R, g.pitch, s, rs_dst(d, d.C), zi, t, true);
 }
 
@@ -127,6 +102,7 @@ int rg_run(const pv_region_views_desc& r, bool frames, const CheckSrc& check_src
   RsItemLaunch g = {};
   size_t lds = 0;
   if (int e = rs_strip_size(d, span, span_c, g, lds)) return e;
+  if (rs_packed_px(d.src_layout)) return pv_packed_regions(d, frames, g, lds, r.regions_dev, stream);   // pv_packed.hip
   const int fr = frames ? 1 : 0;
   const pv_view_region* regions = r.regions_dev;
   RS_SOURCE_FORMS(RG_RGB, RG_YUV);

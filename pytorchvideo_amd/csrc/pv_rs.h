@@ -1,4 +1,4 @@
-// The resampling ingest: ten entry points in nine translation units.
+// The resampling ingest: ten entry points in ten translation units.
 //   pv_resample.hip   pv_resample_crop, pv_video_views    RGB / planar sources, one source per launch
 //   pv_yuv.hip        pv_yuv_views, pv_yuv16_views        YUV 4:2:0 sources of 8- / 16-bit samples, one source per launch
 //   pv_batch.hip      pv_batch_views                      either, one source per destination item
@@ -8,7 +8,9 @@
 //   pv_hdr.hip        pv_hdr_views      pv_batch_views / pv_frame_views on 16-bit YUV with the PQ / HLG tap map
 //   pv_region.hip     pv_region_views   a rectangle of the frame per destination frame, resized to the window
 //   pv_area.hip       pv_area_views     a box filter (the windows of interpolate(mode="area")) in place of the blend: a staged-tile
-//                                       body of its own (a window's rows are not two)
+//                                       body of its own (a window's rows are not two; its RGB body is in pv_area.h)
+//   pv_packed.hip     (launched from pv_batch.hip, pv_frames.hip, pv_orient.hip, pv_region.hip and pv_area.hip)   the kernels of
+//                                       packed-pixel launches (PV_SRC_BGR .. PV_SRC_ABGR): the RGB bodies with RsPacked<PB>
 // What they compute with is here, once: the pinned source coordinate, the destination forms with their stores, the taps and
 // blends, the two staged-strip bodies (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather) and the two staged-tile bodies of
 // oriented records (rs_tile_rgb, rs_tile_yuv), the launch arithmetic (widest span, rows per strip, the LDS layout of a staged
@@ -53,6 +55,14 @@ struct RsTileLaunch {
 // The tile kernels (pv_orient.hip) over the items of `d`, all of oriented records, on a launch rs_item_launch has validated
 // and sized; frames: `src` of a record is a slice of the pointer table of pv_frame_views.
 int pv_orient_launch(const pv_batch_views_desc& d, bool frames, const RsTileLaunch& g, size_t lds, pv_stream_t stream);
+
+// The kernels of packed-pixel launches (pv_packed.hip: src_layout PV_SRC_BGR .. PV_SRC_ABGR), each on a launch its entry point
+// has validated and sized: the strips of pv_batch_views / pv_frame_views, the tiles of their oriented records (called by
+// pv_orient_launch) and the strips of pv_region_views (`regions`: its device copy); frames as above.
+int pv_packed_strips(const pv_batch_views_desc& d, bool frames, const RsItemLaunch& g, size_t lds, pv_stream_t stream);
+int pv_packed_tiles(const pv_batch_views_desc& d, bool frames, const RsTileLaunch& g, size_t lds, pv_stream_t stream);
+int pv_packed_regions(const pv_batch_views_desc& d, bool frames, const RsItemLaunch& g, size_t lds, const pv_view_region* regions,
+                      pv_stream_t stream);
 
 namespace {
 
@@ -269,13 +279,68 @@ struct RsRgbWin : RsRgbSrc {
   int top, left;        // the rectangle's origin in it: rows [top, top + Hs) x columns [left, left + Ws)
 };
 
+// A PACKED source (PV_SRC_BGR .. PV_SRC_ABGR, include/pv_mi355x.h "packed pixels"): a frame-interleaved uint8 source whose
+// pixel has PB = 3 or 4 bytes, R, G and B at bytes o[0..2] of it -- workgroup-uniform, so they stay in scalar registers and one
+// kernel serves every channel order of its pixel size --, rows at the record's pitch and frames at its stride (a dense source
+// derives both from Ws and Hs).  The bodies take it behind a last template parameter whose default, RsDense, leaves every other
+// kernel of the ingest with the instructions it had.  PB == 4: a pixel is one aligned dword of the source (the entry points
+// refuse anything else) and of its LDS image, which keeps a row's `addr & 15`: a tap is ONE dword LDS read (rs_px4) and the
+// channels are bytes of the register (rs_px4_ch); the fourth byte never enters a value.  PB == 3 reads bytes, as [.., 3] does.
+struct RsDense { static constexpr bool kPacked = false; static constexpr int PB = 0; };
+template <int PB_> struct RsPacked {
+  static constexpr bool kPacked = true;
+  static constexpr int PB = PB_;
+  int o[3];                   // byte of R, G, B inside a pixel
+  long row_bytes, frame_bytes;
+};
+struct RsPackedArg { int32_t r, g, b; };   // the kernel argument behind o[]
+// R, G, B byte offsets and the pixel size of a packed src_layout (0: not a packed layout).
+inline int rs_packed_px(int src_layout, RsPackedArg* o = nullptr) {
+  static const int8_t at[5][4] = {{2, 1, 0, 3}, {0, 1, 2, 4}, {2, 1, 0, 4}, {1, 2, 3, 4}, {3, 2, 1, 4}};   // BGR RGBA BGRA ARGB ABGR
+  if (src_layout < PV_SRC_BGR || src_layout > PV_SRC_ABGR) return 0;
+  const int8_t* a = at[src_layout - PV_SRC_BGR];
+  if (o) *o = RsPackedArg{a[0], a[1], a[2]};
+  return a[3];
+}
+template <int PB> __device__ __forceinline__ RsPacked<PB> rs_item_packed(const pv_view_source* __restrict__ V, const RsPackedArg& o) {
+  return RsPacked<PB>{{o.r, o.g, o.b}, (long)V->y_pitch, (long)V->frame_stride};
+}
+// The byte of channel c behind the LDS offset of a pixel: c for [.., 3], the record's order for 3-byte pixels, none for dwords.
+template <typename PK> __device__ __forceinline__ int rs_ch_byte(const PK& pk, int c) {
+  if constexpr (!PK::kPacked) return c;
+  else if constexpr (PK::PB == 4) return 0;
+  else return pk.o[c < 3 ? c : 0];
+}
+__device__ __forceinline__ unsigned rs_px4(const unsigned char* lds, int off) { return *reinterpret_cast<const unsigned*>(lds + off); }
+__device__ __forceinline__ float rs_px4_ch(unsigned w, int byte) { return (float)((w >> (8 * byte)) & 0xffu); }
+// The four taps of channel c of a packed pixel quad: bytes of the four dwords (PB == 4) or four byte reads at the channel's offset.
+template <typename PK>
+__device__ __forceinline__ void rs_packed_taps(const PK& pk, const unsigned char* lds, const int (&at)[4], const unsigned (&w)[4], int c,
+                                               float (&p)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if constexpr (PK::PB == 4) p[k] = rs_px4_ch(w[k], pk.o[c]);
+    else p[k] = (float)lds[at[k] + pk.o[c]];
+  }
+}
+// The blend and the affine map of the RGB bodies,
+//   v = ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11),  out = v * sc + sh,
+// with the contraction spelled out as the compiler forms it in every dense instantiation (profiles/r26/isa_vs_parent.md): left
+// to the compiler, the packed instantiations fuse the other product of each sum and differ in the last bit of an fp32 output.
+__device__ __forceinline__ float rs_blend_rgb(float ly0, float ly1, float lx0, float lx1, const float (&p)[4], float sc, float sh) {
+#pragma clang fp contract(off)
+  const float h0 = fmaf(lx0, p[0], lx1 * p[1]), h1 = fmaf(lx0, p[2], lx1 * p[3]);   // p: (row 0, row 1) x (column i0x, i1x)
+  return fmaf(fmaf(ly0, h0, ly1 * h1), sc, sh);
+}
+
 // S: source element (unsigned char | float); INTER: frame-interleaved [.., Hs, Ws, 3] source; FORM / D: destination.
 // SRC: RsRgbSrc, or RsRgbWin for a rectangle of the stored frame (deduced; the default keeps today's expressions).
-template <typename S, bool INTER, int FORM, typename D, typename SRC = RsRgbSrc>
+// PK: RsDense, or RsPacked<PB> for packed pixels (INTER, bytes, three channels; deduced from the last argument).
+template <typename S, bool INTER, int FORM, typename D, typename SRC = RsRgbSrc, typename PK = RsDense>
 __device__ __forceinline__ void rs_strip_rgb(unsigned char* lds, int R, int pitch, const SRC& s, const RsDst& d, int zi, int t,
-                                             bool check_span) {
+                                             bool check_span, const PK& pk = PK()) {
   constexpr int G = RsGroup<FORM, D>::G;
-  constexpr int XB = INTER ? 3 : (int)sizeof(S);   // bytes from one source column to the next
+  constexpr int XB = PK::kPacked ? PK::PB : (INTER ? 3 : (int)sizeof(S));   // bytes from one source column to the next
   const int tid = threadIdx.x;
   const int row0 = blockIdx.x * R;
   const int nrows = min(R, d.Ho - row0);
@@ -294,7 +359,12 @@ __device__ __forceinline__ void rs_strip_rgb(unsigned char* lds, int R, int pitc
 
   // byte address of column xs0 of source row y of plane `pl` of the selected frame
   long row_bytes, frame_bytes, first;
-  if constexpr (SRC::kWindow) {                    // strides of the stored frame, the rectangle's origin in the first address
+  if constexpr (PK::kPacked) {                     // the record's pitch and stride; a rectangle's origin in the first address
+    row_bytes = pk.row_bytes;
+    frame_bytes = pk.frame_bytes;
+    first = (s.clip_frame0 + s.ts) * frame_bytes + (long)xs0 * XB;
+    if constexpr (SRC::kWindow) first += (long)s.top * row_bytes + (long)s.left * XB;
+  } else if constexpr (SRC::kWindow) {             // strides of the stored frame, the rectangle's origin in the first address
     row_bytes = (long)s.Wf * XB;
     frame_bytes = (long)s.Hf * row_bytes;
     first = (s.clip_frame0 + s.ts) * frame_bytes + (long)s.top * row_bytes + (long)(s.left + xs0) * XB;
@@ -356,6 +426,8 @@ __device__ __forceinline__ void rs_strip_rgb(unsigned char* lds, int R, int pitc
     const float ly0 = 1.f - ly1;
     const int s0 = dense ? i0y - ybase : 2 * r, s1 = dense ? i1y - ybase : 2 * r + 1;
     int ro0[4], ro1[4];                            // LDS byte offset of column xs0, channel c, in the two source rows
+    int pb0 = 0, pb1 = 0;                          // packed pixels: of the pixel itself
+    if constexpr (PK::kPacked) pb0 = s0 * pitch + (int)(row_addr(i0y, 0) & 15), pb1 = s1 * pitch + (int)(row_addr(i1y, 0) & 15);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       if (INTER) {
@@ -376,17 +448,35 @@ __device__ __forceinline__ void rs_strip_rgb(unsigned char* lds, int R, int pitc
       rs_coord(s.sx, s.xoff + x, s.Ws, i0x, i1x, lx1);
       const float lx0 = 1.f - lx1;
       const int o0 = (i0x - xs0) * XB, o1 = (i1x - xs0) * XB;
+      if constexpr (PK::kPacked) {                 // PB == 4: four dword reads, the channels out of the registers
+        const int at[4] = {pb0 + o0, pb0 + o1, pb1 + o0, pb1 + o1};
+        unsigned w[4] = {0, 0, 0, 0};
+        if constexpr (PK::PB == 4) {
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        if (c < d.C) {
-          const float p00 = rs_tap<S>(lds, ro0[c] + o0), p01 = rs_tap<S>(lds, ro0[c] + o1);
-          const float p10 = rs_tap<S>(lds, ro1[c] + o0), p11 = rs_tap<S>(lds, ro1[c] + o1);
-          const float v = ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11);
-          out[c][j] = v * sc[c] + sh[c];
-        } else {
-          out[c][j] = 0.f;
+          for (int k = 0; k < 4; ++k) w[k] = rs_px4(lds, at[k]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          float p[4];
+          rs_packed_taps(pk, lds, at, w, c, p);
+          out[c][j] = rs_blend_rgb(ly0, ly1, lx0, lx1, p, sc[c], sh[c]);
+        }
+        out[3][j] = 0.f;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if (c < d.C) {
+            const float p00 = rs_tap<S>(lds, ro0[c] + o0), p01 = rs_tap<S>(lds, ro0[c] + o1);
+            const float p10 = rs_tap<S>(lds, ro1[c] + o0), p11 = rs_tap<S>(lds, ro1[c] + o1);
+            const float v = ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11);
+            out[c][j] = v * sc[c] + sh[c];
+          } else {
+            out[c][j] = 0.f;
+          }
         }
       }
+      // packed pixels: finish this pixel before the next one starts (as in rs_strip_yuv: 134 -> 70 VGPRs for G = 8)
+      if constexpr (PK::kPacked) asm volatile("" : "+v"(out[0][j]), "+v"(out[1][j]), "+v"(out[2][j]));
     }
     const int x0 = gx * G;
     const int nvalid = min(G, d.Wo - x0);
@@ -588,12 +678,12 @@ __host__ __device__ __forceinline__ void rs_tile_range(float s, int first, int n
   rs_coord(s, first + n - 1, n_in, unused, d1, lunused);
 }
 
-// S / INTER / FORM / D: as rs_strip_rgb.
-template <typename S, bool INTER, int FORM, typename D>
+// S / INTER / FORM / D / PK: as rs_strip_rgb.
+template <typename S, bool INTER, int FORM, typename D, typename PK = RsDense>
 __device__ __forceinline__ void rs_tile_rgb(unsigned char* lds, const RsTileLaunch& g, const RsRgbSrc& s, int orient, const RsDst& d,
-                                            int zi, int t) {
+                                            int zi, int t, const PK& pk = PK()) {
   constexpr int G = RsGroup<FORM, D>::G;
-  constexpr int XB = INTER ? 3 : (int)sizeof(S);   // bytes from one source column to the next
+  constexpr int XB = PK::kPacked ? PK::PB : (INTER ? 3 : (int)sizeof(S));   // bytes from one source column to the next
   const int tid = threadIdx.x;
   const int tile_y = blockIdx.x / g.tiles_x, tile_x = blockIdx.x - tile_y * g.tiles_x;
   const int row0 = tile_y * g.TR, col0 = tile_x * g.TC;
@@ -612,9 +702,10 @@ __device__ __forceinline__ void rs_tile_rgb(unsigned char* lds, const RsTileLaun
   const int span_bytes = (sc1 - sc0 + 1) * XB;
   if (nslots > g.rows || span_bytes + 15 > pitch) return;
 
-  // byte address of column sc0 of stored row r of plane `pl` of the selected frame
-  const long row_bytes = (long)s.Ws * XB;
-  const long frame_bytes = (long)s.Hs * row_bytes;
+  // byte address of column sc0 of stored row r of plane `pl` of the selected frame (packed: the record's pitch and stride)
+  long row_bytes = (long)s.Ws * XB;
+  long frame_bytes = (long)s.Hs * row_bytes;
+  if constexpr (PK::kPacked) row_bytes = pk.row_bytes, frame_bytes = pk.frame_bytes;
   const long first = (s.clip_frame0 + s.ts) * frame_bytes + (long)sc0 * XB;
   const long plane_bytes = INTER ? 0 : (long)s.N * frame_bytes;
   auto row_addr = [&](int r, int pl) -> uintptr_t { return s.src + first + (long)pl * plane_bytes + (long)r * row_bytes; };
@@ -678,18 +769,36 @@ __device__ __forceinline__ void rs_tile_rgb(unsigned char* lds, const RsTileLaun
       float lx1;
       rs_coord(s.sx, s.xoff + x, Wd, i0x, i1x, lx1);
       const float lx0 = 1.f - lx1;
+      if constexpr (PK::kPacked) {                 // PB == 4: four dword reads, the channels out of the registers
+        const int at[4] = {tap(i0y, i0x, 0), tap(i0y, i1x, 0), tap(i1y, i0x, 0), tap(i1y, i1x, 0)};
+        unsigned w[4] = {0, 0, 0, 0};
+        if constexpr (PK::PB == 4) {
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        if (c < d.C) {
-          const int pl = INTER ? 0 : c, cb = INTER ? c : 0;
-          const float p00 = rs_tap<S>(lds, tap(i0y, i0x, pl) + cb), p01 = rs_tap<S>(lds, tap(i0y, i1x, pl) + cb);
-          const float p10 = rs_tap<S>(lds, tap(i1y, i0x, pl) + cb), p11 = rs_tap<S>(lds, tap(i1y, i1x, pl) + cb);
-          const float v = ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11);
-          out[c][j] = v * sc[c] + sh[c];
-        } else {
-          out[c][j] = 0.f;
+          for (int k = 0; k < 4; ++k) w[k] = rs_px4(lds, at[k]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          float p[4];
+          rs_packed_taps(pk, lds, at, w, c, p);
+          out[c][j] = rs_blend_rgb(ly0, ly1, lx0, lx1, p, sc[c], sh[c]);
+        }
+        out[3][j] = 0.f;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if (c < d.C) {
+            const int pl = INTER ? 0 : c, cb = INTER ? c : 0;
+            const float p00 = rs_tap<S>(lds, tap(i0y, i0x, pl) + cb), p01 = rs_tap<S>(lds, tap(i0y, i1x, pl) + cb);
+            const float p10 = rs_tap<S>(lds, tap(i1y, i0x, pl) + cb), p11 = rs_tap<S>(lds, tap(i1y, i1x, pl) + cb);
+            const float v = ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11);
+            out[c][j] = v * sc[c] + sh[c];
+          } else {
+            out[c][j] = 0.f;
+          }
         }
       }
+      // packed pixels: finish this pixel before the next one starts (as in rs_strip_yuv)
+      if constexpr (PK::kPacked) asm volatile("" : "+v"(out[0][j]), "+v"(out[1][j]), "+v"(out[2][j]));
     }
     const int nvalid = min(G, d.Wo - x0);
     rs_store_group<FORM, D, G>(d.dst, out, d.C, d.T, d.Ho, d.Wo, d.c_p, d.ld, d.bs, zi, t, y, x0, nvalid);
@@ -887,6 +996,37 @@ template <int CSTEP> __device__ __forceinline__ RsYuvSrc rs_item_yuv(const RsIte
   return s;
 }
 
+// The shared item with what is pv_region_views' own on top (pv_region.hip, and its packed kernels in pv_packed.hip): the
+// rectangle of the item's (row, t), clamped into the stored frame before any address is formed -- top / left inside it, h / w
+// at least 1 and ending inside it -- and its sy / sx.
+// (One function, the loader's call inside it: with the rectangle read by a function of its own behind the loader, its loads
+// are ordered otherwise and every kernel of pv_region.hip changes -- profiles/r24/isa_vs_parent.md.)
+struct RgItem : RsItem {
+  int top, left, h, w;
+  float sy, sx;
+};
+__device__ __forceinline__ RgItem rg_item(const pv_batch_views_desc& d, const pv_view_region* __restrict__ regions, int frames, int zi,
+                                          int t) {
+  RgItem r{rs_item<RS_EITHER>(d, zi, t, frames)};
+  const pv_view_region* __restrict__ G = regions + r.at;
+  const int Hs = r.S->Hs, Ws = r.S->Ws;
+  r.top = min(max(G->top, 0), Hs - 1), r.left = min(max(G->left, 0), Ws - 1);
+  r.h = min(max(G->h, 1), Hs - r.top), r.w = min(max(G->w, 1), Ws - r.left);
+  r.sy = G->sy, r.sx = G->sx;
+  return r;
+}
+// The geometry of rs_strip_rgb over that rectangle: the stored frame keeps the strides, the body's source is the rectangle.
+__device__ __forceinline__ RsRgbWin rg_item_rgb(const RgItem& item) {
+  RsRgbWin s;
+  static_cast<RsRgbSrc&>(s) = rs_item_rgb(item);
+  s.Hf = s.Hs, s.Wf = s.Ws;
+  s.top = item.top, s.left = item.left;
+  s.Hs = item.h, s.Ws = item.w;
+  s.sy = item.sy, s.sx = item.sx;
+  s.yoff = 0, s.xoff = 0;
+  return s;
+}
+
 // ---- the launch arithmetic shared by the entry points ---------------------------------------------------------------
 // Folds the widest source column span of a record's views into `span`, and the chroma span behind it into `span_c`, both in
 // columns: times the bytes of a column (rs_yuv_pitches for YUV) they size the staged rows.
@@ -924,8 +1064,11 @@ inline int rs_strip_rows(long per_row, int Ho, int32_t& R_out, size_t& lds) {
 
 // The LDS pitch of a staged RGB / planar (row, plane) for the widest span (columns) of a launch.
 inline int32_t rs_rgb_pitch(int span, int src_layout, int src_dtype) {
-  return pv_round_up(span * (src_layout == PV_SRC_NTHWC ? 3 : (src_dtype == PV_F32 ? 4 : 1)) + 15, 16);
+  const int pb = rs_packed_px(src_layout);         // packed pixels: PB bytes per column
+  return pv_round_up(span * (pb ? pb : (src_layout == PV_SRC_NTHWC ? 3 : (src_dtype == PV_F32 ? 4 : 1))) + 15, 16);
 }
+// Frame-interleaved sources stage ONE plane per row: [.., 3] and the packed layouts.
+inline bool rs_interleaved(int src_layout) { return src_layout == PV_SRC_NTHWC || rs_packed_px(src_layout) != 0; }
 
 // The LDS layout of a staged tile (RsTileLaunch, or a launch struct with the same fields: pv_area.hip) whose widest footprint
 // is n = {rows, columns, chroma rows, chroma columns}: every staged row of every plane at its pitch, for YUV the chroma image
@@ -938,7 +1081,7 @@ template <typename Launch> inline long rs_tile_layout(const pv_batch_views_desc&
     return (long)g.c_base + (long)g.rows_c * (d.c_step == 2 ? 1 : 2) * g.pitch_c;
   }
   g.pitch = rs_rgb_pitch(n[1], d.src_layout, d.src_dtype);
-  return (long)g.rows * (d.src_layout == PV_SRC_NTHWC ? 1 : d.C) * g.pitch;
+  return (long)g.rows * (rs_interleaved(d.src_layout) ? 1 : d.C) * g.pitch;
 }
 
 // The destination-form dispatch: KERNEL<leading template arguments..., FORM, D>ARGS over a grid of GRID_X workgroups (strips,
@@ -1053,8 +1196,9 @@ inline bool rs_same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof(f
 
 // check_src of a launch whose records are whole videos (pv_batch_views; pv_hdr_views without a pointer table): `src` is one
 // allocation of the source dtype, 4-byte aligned for fp32, even for 16-bit samples.
-inline auto rs_check_video_src(int src_dtype) {
-  const uintptr_t misaligned = src_dtype == PV_F32 ? 3 : (src_dtype == PV_U16 ? 1 : 0);   // address bits `src` may not have
+inline auto rs_check_video_src(int src_dtype, int src_layout = PV_SRC_NCTHW) {
+  // address bits `src` may not have (4-byte pixels: a pixel is one aligned dword)
+  const uintptr_t misaligned = src_dtype == PV_F32 || rs_packed_px(src_layout) == 4 ? 3 : (src_dtype == PV_U16 ? 1 : 0);
   return [=](const pv_view_source& v) { return reinterpret_cast<uintptr_t>(v.src) & misaligned ? PV_ERR_INVALID : PV_OK; };
 }
 
@@ -1068,6 +1212,11 @@ inline int rs_check_record_frames(const pv_batch_views_desc& d, const pv_view_so
     const int sb = d.src_dtype == PV_U16 ? 2 : 1;
     if (int e = rs_check_yuv_planes(v.Hs, v.Ws, d.c_step, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset, sb)) return e;
     if (sb == 2 && rs_check_yuv16_even(0, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset)) return PV_ERR_INVALID;
+  }
+  if (const int pb = rs_packed_px(d.src_layout)) {   // packed pixels: a pitch that holds a row, a stride that holds a frame, dwords aligned
+    if (v.y_pitch < (int64_t)v.Ws * pb || v.frame_stride < (int64_t)(v.Hs - 1) * v.y_pitch + (int64_t)v.Ws * pb) return PV_ERR_INVALID;
+    if (v.u_offset != 0 || v.v_offset != 0 || v.c_pitch != 0) return PV_ERR_INVALID;
+    if (pb == 4 && ((v.y_pitch | v.frame_stride) & 3)) return PV_ERR_INVALID;
   }
   return check_src(v);
 }
@@ -1138,7 +1287,7 @@ inline int rs_check_item_desc(const pv_batch_views_desc& d) {
   if (d.n_sources <= 0 || d.n_items <= 0 || d.n_rows <= 0 || d.T <= 0 || d.C <= 0 || d.Ho <= 0 || d.Wo <= 0) return PV_ERR_INVALID;
   if (d.t_stride < d.T || d.n_items > 65535 || d.T > 65535) return PV_ERR_INVALID;   // grid.y / grid.z
   if (d.C > 4 || d.n_views < 1 || d.n_views > 3) return PV_ERR_INVALID;
-  const bool yuv = d.src_layout == PV_SRC_YUV420, inter = d.src_layout == PV_SRC_NTHWC;
+  const bool yuv = d.src_layout == PV_SRC_YUV420, inter = rs_interleaved(d.src_layout);   // [.., 3] or packed pixels
   if (!yuv && !inter && d.src_layout != PV_SRC_NCTHW) return PV_ERR_INVALID;
   if (!yuv && d.src_dtype == PV_U16) return PV_ERR_UNSUPPORTED;   // 16-bit samples are a YUV 4:2:0 source only
   if (inter && (d.src_dtype != PV_U8 || d.C != 3)) return PV_ERR_INVALID;
@@ -1155,7 +1304,7 @@ inline int rs_strip_size(const pv_batch_views_desc& d, int span, int span_c, RsI
     per_row = rs_yuv_pitches(span, span_c, d.c_step, d.src_dtype == PV_U16 ? 2 : 1, g.pitch, g.pitch_c);
   } else {
     g.pitch = rs_rgb_pitch(span, d.src_layout, d.src_dtype);
-    per_row = 2L * (d.src_layout == PV_SRC_NTHWC ? 1 : d.C) * g.pitch;
+    per_row = 2L * (rs_interleaved(d.src_layout) ? 1 : d.C) * g.pitch;
   }
   if (int e = rs_strip_rows(per_row, d.Ho, g.R, lds)) return e;
   g.c_base = 2 * g.R * g.pitch;

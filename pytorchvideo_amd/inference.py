@@ -32,10 +32,11 @@ from .transforms import (DevicePacker, FrameList, _interpolation, batch_chunks, 
                          yuv_geometry)
 
 
-def _resident(video, device, is_yuv):
-    """The video on the device in a dtype the ingest reads: YUV frames are read in place, with the strides they have."""
+def _resident(video, device, in_place):
+    """The video on the device in a dtype the ingest reads: YUV frames and packed pixels (`DevicePacker.in_place`) are read in
+    place, with the strides they have."""
     video = video.to(device, non_blocking=True)
-    if is_yuv:
+    if in_place:
         return video
     if video.dtype not in (torch.uint8, torch.float32):
         video = video.float()
@@ -84,8 +85,8 @@ class VideoPredictor:
     def __call__(self, video, fps, return_clip_scores=False, orientation=0):
         p = self.packer
         device = p.sess.device
-        # HDR taps and the box filter: pv_hdr_views / pv_area_views, item-sourced launches
-        if isinstance(video, FrameList) or orientation or p.hdr is not None or p.area:
+        # HDR taps, the box filter and packed pixels: pv_hdr_views / pv_area_views / pv_batch_views, item-sourced launches
+        if isinstance(video, FrameList) or orientation or p.hdr is not None or p.area or p.is_packed:
             return self._call_frames(video, fps, return_clip_scores, orientation)
         if video.dim() != (3 if p.is_yuv else 4):
             raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(video.shape)))
@@ -125,7 +126,7 @@ class VideoPredictor:
             if frames.dim() != (3 if p.is_yuv else 4):
                 raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(frames.shape)))
             num_frames = frames.shape[1] if self.src_layout == "NCTHW" else frames.shape[0]
-            frames = _resident(frames, device, p.is_yuv)
+            frames = _resident(frames, device, p.in_place)
         table, _ = clip_frame_table(self.sampler, num_frames, fps, p.clip_frames)
         batch = p.video_batch([frames], [table], orientation=orientation)    # every check, and the one upload
         zeros = torch.zeros(p.batch, dtype=torch.int32, device=device)
@@ -316,7 +317,7 @@ class KeyframeDetector:
                 continue                                         # no key frame of this video has a box
             if not as_frames:
                 vid = vid.to(device, non_blocking=True)
-            if not as_frames and not p.is_yuv:
+            if not as_frames and not p.in_place:
                 if vid.dtype not in (torch.uint8, torch.float32):
                     vid = vid.float()
                 vid = vid.contiguous()
@@ -439,7 +440,7 @@ class TubePredictor:
             if not rows:
                 continue                                         # no time stamp of this video has a tube
             if not as_frames:
-                vid = _resident(vid, device, p.is_yuv)
+                vid = _resident(vid, device, p.in_place)
             kept.append((vid, heights[j], coded[j]))
             tables.append(table[rows])
             regions.append(torch.stack(rects))

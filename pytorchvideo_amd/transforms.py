@@ -394,6 +394,71 @@ class UniformCropVideo(torch.nn.Module):
         return x
 
 
+# --------------------------------------------------------------------------- packed pixels (BGR24, 32-bit RGBA and kin)
+# What an OpenCV pipeline holds ("BGR") and what screen capture, colour converters and compositor surfaces hand out (four
+# bytes per pixel, the fourth unused, usually pitched): read where they lie by pv_batch_views / pv_frame_views /
+# pv_region_views / pv_area_views (include/pv_mi355x.h, "packed pixels").  layout -> the bytes of R, G, B inside a pixel.
+_PACKED_RGB = {"BGR": (2, 1, 0), "RGBA": (0, 1, 2), "BGRA": (2, 1, 0), "ARGB": (1, 2, 3), "ABGR": (3, 2, 1)}
+PACKED_LAYOUTS = tuple(_PACKED_RGB)
+_PACKED_ALIASES = {"RGBX": "RGBA", "BGRX": "BGRA", "XRGB": "ARGB", "XBGR": "ABGR"}     # the fourth byte is unused either way
+_PACKED_ANY = PACKED_LAYOUTS + tuple(_PACKED_ALIASES)
+
+
+def _packed_name(layout):
+    """The layout of `PACKED_LAYOUTS` behind a packed `src_layout` string (an "X" spelling is its "A" one), else None."""
+    layout = _PACKED_ALIASES.get(layout, layout) if isinstance(layout, str) else None
+    return layout if layout in _PACKED_RGB else None
+
+
+def _packed_bytes(layout):
+    """Bytes per pixel of a packed layout: 3 for "BGR", 4 for the others."""
+    return 3 if _packed_name(layout) == "BGR" else 4
+
+
+def packed_to_rgb(x: torch.Tensor, layout: str) -> torch.Tensor:
+    """The host mirror of the packed layouts: [..., PB] pixels in `layout` -> [..., 3] in R, G, B order, by a pure index (no
+    arithmetic; the fourth byte of a 32-bit pixel is dropped).  The ingest holds, bit for bit, what it writes for
+    `packed_to_rgb(video, layout).contiguous()` read as "NTHWC"."""
+    name = _packed_name(layout)
+    if name is None:
+        raise ValueError("a packed layout is one of %s, got %r" % (PACKED_LAYOUTS, layout))
+    if x.shape[-1] != _packed_bytes(name):
+        raise ValueError("%s pixels have %d bytes, the last dimension has %d" % (name, _packed_bytes(name), x.shape[-1]))
+    return x[..., list(_PACKED_RGB[name])]
+
+
+def packed_geometry(frames: torch.Tensor, layout: str) -> dict:
+    """Where the pixels of packed frames lie: `frames` is uint8 [N, H, W, PB] (or [H, W, PB]: one frame) with
+    stride(-1) == 1, stride(-2) == PB and a row stride >= W * PB -- a pitched surface, or a column slice of a wider one, is
+    read where it lies; the frame stride may be anything that keeps the frames apart.  Returns N, Hs, Ws and the record's
+    fields in BYTES: y_pitch (the row stride), frame_stride (between frames; one frame: its extent) and zero u_offset /
+    v_offset / c_pitch.  ValueError, naming the stride, for anything else: no copy is ever made."""
+    name = _packed_name(layout)
+    if name is None:
+        raise ValueError("a packed layout is one of %s, got %r" % (PACKED_LAYOUTS, layout))
+    pb = _packed_bytes(name)
+    if frames.dim() == 3:
+        frames = frames[None]
+    if frames.dim() != 4 or frames.shape[-1] != pb or frames.dtype != torch.uint8:
+        raise ValueError("%s frames are uint8 [N, H, W, %d], got %s %s" % (name, pb, frames.dtype, tuple(frames.shape)))
+    n, h, w, _ = frames.shape
+    if frames.stride(3) != 1:
+        raise ValueError("%s frames: stride(-1) is %d, not 1: the bytes of a pixel are adjacent" % (name, frames.stride(3)))
+    if frames.stride(2) != pb:
+        raise ValueError("%s frames: stride(-2) is %d, not %d: the pixels of a row are adjacent" % (name, frames.stride(2), pb))
+    pitch = frames.stride(1) if h > 1 else max(frames.stride(1), w * pb)
+    if pitch < w * pb:
+        raise ValueError("%s frames: the row stride, stride(-3), is %d, less than the %d bytes of a row" % (name, pitch, w * pb))
+    extent = (h - 1) * pitch + w * pb
+    frame_stride = frames.stride(0) if n > 1 else extent
+    if frame_stride < extent:
+        raise ValueError("%s frames: the frame stride, stride(0), is %d, less than the %d bytes of a frame" % (name, frame_stride, extent))
+    if pb == 4 and (pitch % 4 or frame_stride % 4 or frames.data_ptr() % 4):
+        raise ValueError("%s frames: a 4-byte pixel is one aligned dword -- the address, the row stride %d and the frame stride %d "
+                         "are multiples of 4" % (name, pitch, frame_stride))
+    return dict(N=n, Hs=h, Ws=w, y_pitch=pitch, frame_stride=frame_stride, u_offset=0, v_offset=0, c_pitch=0)
+
+
 # --------------------------------------------------------------------------- YUV 4:2:0 sources
 YUV_LAYOUTS = ("NV12", "NV21", "I420", "YV12")
 # 16-bit little-endian samples.  P0xx: the NV12 arrangement with the value in the HIGH bits (what a hardware decoder writes for
@@ -402,6 +467,9 @@ YUV16_LAYOUTS = ("P010", "P012", "P016", "I010", "I012", "I016")
 _YUV_ANY = YUV_LAYOUTS + YUV16_LAYOUTS
 _YUV_INTERLEAVED = ("NV12", "NV21", "P010", "P012", "P016")
 _YUV_PLANE_FIELDS = ("frame_stride", "u_offset", "v_offset", "y_pitch", "c_pitch")   # of `yuv_geometry`, a descriptor, a record
+_SRC_LAYOUTS = ("NCTHW", "NTHWC") + _YUV_ANY + _PACKED_ANY      # every `src_layout` the device ingest takes
+_LAYOUT_ERROR = ("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,)
+                 + " or %s" % (PACKED_LAYOUTS,))
 _YUV16_DEPTH = {"P010": (10, True), "P012": (12, True), "P016": (16, True), "I010": (10, False), "I012": (12, False),
                 "I016": (16, False)}                       # layout -> (bit depth, MSB-aligned)
 _YUV_KR_KB = {"bt709": (0.2126, 0.0722), "bt601": (0.299, 0.114)}
@@ -703,6 +771,8 @@ def _src_codes(src_layout, dtype):
     from . import _lib as L
     if src_layout in _YUV_ANY:
         return L.SRC_YUV420, L.PV_U16 if src_layout in YUV16_LAYOUTS else L.PV_U8
+    if src_layout in _PACKED_ANY:
+        return getattr(L, "SRC_" + _packed_name(src_layout)), L.PV_U8
     return L.SRC_NCTHW if src_layout == "NCTHW" else L.SRC_NTHWC, L.PV_U8 if dtype == torch.uint8 else L.PV_F32
 
 
@@ -749,11 +819,17 @@ def _on_device(video, device, what):
 
 def _video_source(video, src_layout, device, coded_height=None, height=None, what="the video"):
     """What a legal video tensor is for `src_layout`, for `fill_video` and `video_batch` alike: on `device`, and either
-    contiguous uint8 / fp32 [C,N,H,W], contiguous uint8 [N,H,W,3], or YUV frames with the strides `yuv_geometry` accepts.
-    Returns (C, N, Hs, Ws, geom), `geom` being `yuv_geometry` of the frames, or None.  RuntimeError, naming `what`, if not."""
+    contiguous uint8 / fp32 [C,N,H,W], contiguous uint8 [N,H,W,3], YUV frames with the strides `yuv_geometry` accepts, or
+    packed pixels [N,H,W,PB] with the strides `packed_geometry` accepts (a ValueError naming the stride otherwise).
+    Returns (C, N, Hs, Ws, geom), `geom` being `yuv_geometry` / `packed_geometry` of the frames, or None.  RuntimeError, naming `what`, if not."""
     _on_device(video, device, what)
     if src_layout in _YUV_ANY:
         geom = yuv_geometry(video, src_layout, coded_height, height)
+        return 3, geom["N"], geom["Hs"], geom["Ws"], geom
+    if src_layout in _PACKED_ANY:                                # read where it lies: strides checked, never copied
+        if video.dim() != 4:
+            raise RuntimeError("expected one 4-d %s video, got %s" % (src_layout, tuple(video.shape),))
+        geom = packed_geometry(video, src_layout)
         return 3, geom["N"], geom["Hs"], geom["Ws"], geom
     c, nf, hs, ws = _video_geometry(video, src_layout)
     if not video.is_contiguous() or video.dtype not in (torch.uint8, torch.float32):
@@ -846,7 +922,8 @@ class FrameList:
     contiguous uint8 [H, W, 3]; "NCTHW" a contiguous uint8 or fp32 [C, H, W]; the YUV layouts a uint8 (`YUV16_LAYOUTS`:
     uint16 or int16) 2-d [Hc*3/2, W] with stride(1) == 1 and any row pitch P >= W (`yuv_geometry` of a one-frame view: the surface is the Hc*3/2 * P bytes from
     its first sample -- the half-pitch chroma rows of I420 / YV12 lie partly behind column W).  `src_layout`, when given,
-    checks that form at construction; `video_batch` checks it in any case.  A frame may be a view at any offset inside a
+    checks that form at construction; `video_batch` checks it in any case.  The packed layouts (`PACKED_LAYOUTS`): a uint8
+    [H, W, PB] with stride(-1) == 1, stride(-2) == PB and any row stride >= W * PB (`packed_geometry`).  A frame may be a view at any offset inside a
     larger buffer and appear more than once, and the frames may have been allocated in any order.  The list keeps its
     tensors alive; `len()` is the frame count; `stack(src_layout)` is the contiguous video the frames make up."""
 
@@ -880,8 +957,13 @@ class FrameList:
                 raise RuntimeError("a %s frame is uint8 [Hc*3/2, W], got %s %s" % (src_layout, f.dtype, tuple(f.shape)))
             geom = yuv_geometry(f[None], src_layout, coded_height, height)
             return 3, geom["Hs"], geom["Ws"], geom
+        if src_layout in _PACKED_ANY:
+            if f.dim() != 3:
+                raise RuntimeError("a %s frame is uint8 [H, W, %d], got %s %s" % (src_layout, _packed_bytes(src_layout), f.dtype, tuple(f.shape)))
+            geom = packed_geometry(f, src_layout)
+            return 3, geom["Hs"], geom["Ws"], geom
         if src_layout not in ("NCTHW", "NTHWC"):
-            raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
+            raise ValueError(_LAYOUT_ERROR)
         if f.dim() != 3 or not f.is_contiguous() or f.dtype not in (torch.uint8, torch.float32):
             raise RuntimeError("a frame of a FrameList is a contiguous uint8 or fp32 [H,W,3] / [C,H,W] tensor, got %s %s with "
                                "strides %s" % (f.dtype, tuple(f.shape), f.stride()))
@@ -1061,7 +1143,7 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
             raise RuntimeError("the videos of one batch have one dtype: video %d is %s, video 0 %s" % (j, video.dtype, dtype))
         if c != channels:
             raise RuntimeError("video %d has %d channels, the deploy form takes %d" % (j, c, channels))
-        for k in _YUV_PLANE_FIELDS if is_yuv else ():
+        for k in _YUV_PLANE_FIELDS if geom is not None else ():   # YUV planes; packed pixels: the row pitch and the frame stride
             setattr(rec, k, geom[k])
         hd, wd = displayed_size(hs, ws, orients[j])               # the views are cut from the displayed frame
         if regions is not None:                                   # the geometry is per frame; the record's own is not read
@@ -1188,8 +1270,8 @@ def device_resized_crop(clip, regions, size, mean=None, std=None, div255=False, 
     YUV); `size` an int or (Ho, Wo).  The clips are read where they lie: no crop, no RGB copy and no resized intermediate is
     made.  The transform alone, as `device_scale_crop` is; `resized_crop` is the host mirror."""
     from . import _lib as L
-    if src_layout not in ("NCTHW", "NTHWC") + _YUV_ANY:
-        raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
+    if src_layout not in _SRC_LAYOUTS:
+        raise ValueError(_LAYOUT_ERROR)
     if dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("dtype is torch.bfloat16 or torch.float32")
     window = _size_pair(size)
@@ -1198,13 +1280,16 @@ def device_resized_crop(clip, regions, size, mean=None, std=None, div255=False, 
         clip, regions = clip.unsqueeze(0), torch.as_tensor(regions).unsqueeze(0)
     if clip.dim() != (4 if is_yuv else 5):
         raise RuntimeError("expected %s clips [B, ...], got %s" % (src_layout, tuple(clip.shape),))
+    if src_layout in _PACKED_ANY:                                # the stride rules, before any device is touched
+        packed_geometry(clip[0], src_layout)
     device = clip.device if clip.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    clip = clip.to(device, non_blocking=True) if is_yuv else _device_source(clip, device)
+    in_place = is_yuv or src_layout in _PACKED_ANY               # read with the strides they have: never copied
+    clip = clip.to(device, non_blocking=True) if in_place else _device_source(clip, device)
     b, t = clip.shape[0], clip.shape[2] if src_layout == "NCTHW" else clip.shape[1]
     regions = torch.as_tensor(regions)
     if regions.dim() != 3 or tuple(regions.shape) != (b, t, 4):
         raise ValueError("regions are [B, T, 4] = [%d, %d, 4], a rectangle per frame of every clip; got %s" % (b, t, tuple(regions.shape)))
-    channels = 3 if is_yuv else clip.shape[1 if src_layout == "NCTHW" else 4]
+    channels = 3 if in_place else clip.shape[1 if src_layout == "NCTHW" else 4]
     frames = torch.arange(t, dtype=torch.int32)[None]
     # every clip a source of its own, its T frames one table row: the item-sourced launch of DevicePacker.fill_batch
     batch = build_video_batch(list(clip.unbind(0)), [frames] * b, src_layout, None, window, (1,), [t], channels, device,
@@ -1237,20 +1322,25 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
     Materialised clips go through the one-source entry points, whose descriptors have no orientation: a non-zero
     `orientation` is refused; `DevicePacker.video_batch` reads turned and mirrored videos in place.
 
+    With a layout of `PACKED_LAYOUTS` ("BGR", "RGBA", "BGRA", "ARGB", "ABGR"; "RGBX" and kin are aliases) the clip is uint8
+    [B, T, H, W, PB] packed pixels with the strides it has (`packed_geometry`: a pitched surface is read in place, a
+    ValueError names a stride that is not legal, nothing is ever made contiguous); every clip is a source of its own in one
+    launch of `pv_batch_views`, and the result is bit for bit that of "NTHWC" on `packed_to_rgb(clip, layout).contiguous()`.
+
     `interpolation="area"` scales with the box filter of `short_side_scale(x, size, "area")` instead of four taps -- what a
     720p or larger source needs: every clip is a source of its own in ONE launch of `pv_area_views`, any source layout, up to
     three views; a ValueError together with a non-zero `orientation` or `hdr`, and for any other string."""
     area = _interpolation(interpolation, orientation, hdr, "device_scale_crop")
     _refuse_orientation(orientation, "device_scale_crop")
-    if src_layout not in ("NCTHW", "NTHWC") + _YUV_ANY:
-        raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
+    if src_layout not in _SRC_LAYOUTS:
+        raise ValueError(_LAYOUT_ERROR)
     if dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("dtype is torch.bfloat16 or torch.float32")
     views = _views(spatial_idx)
     hdr = _hdr_of(hdr, src_layout)                             # ValueError for an 8-bit or RGB source
-    if area:
-        return _device_scale_crop_area(clip, short_side, crop_size, views, (mean, std, div255), num_frames, dtype, src_layout,
-                                       yuv, coded_height, height)
+    if area or src_layout in _PACKED_ANY:                      # item-sourced launches: pv_area_views, or pv_batch_views for packed pixels
+        return _device_scale_crop_items(clip, short_side, crop_size, views, (mean, std, div255), num_frames, dtype, src_layout,
+                                        yuv, coded_height, height, area)
     if src_layout in _YUV_ANY:
         return _device_scale_crop_yuv(clip, short_side, crop_size, views, (mean, std, div255), num_frames, dtype, src_layout,
                                       yuv, coded_height, height, hdr)
@@ -1264,26 +1354,35 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
     return _scale_crop_launch(d, "pv_resample_crop", "resample_crop", d.B, d.C, (mean, std, div255), dtype, device)
 
 
-def _device_scale_crop_area(clip, short_side, crop_size, views, affine, num_frames, dtype, src_layout, yuv, coded_height, height):
-    """`device_scale_crop(interpolation="area")`: every clip a source of its own, its frames one table row -- the item-sourced
-    launch of `DevicePacker.fill_batch`, as `device_resized_crop` builds it -- and one launch of `pv_area_views`."""
+def _device_scale_crop_items(clip, short_side, crop_size, views, affine, num_frames, dtype, src_layout, yuv, coded_height, height,
+                             area):
+    """`device_scale_crop(interpolation="area")`, and `device_scale_crop` of packed pixels: every clip a source of its own, its
+    frames one table row -- the item-sourced launch of `DevicePacker.fill_batch`, as `device_resized_crop` builds it -- and one
+    launch of `pv_area_views` (`area`) or `pv_batch_views` (the one-source entry points do not read packed pixels)."""
     from . import _lib as L
     is_yuv = src_layout in _YUV_ANY
+    in_place = is_yuv or src_layout in _PACKED_ANY               # read with the strides they have: never copied
     if is_yuv and clip.dim() == 3:
         clip = clip.unsqueeze(0)
     if clip.dim() != (4 if is_yuv else 5):
         raise RuntimeError("expected %s clips [B, ...], got %s" % (src_layout, tuple(clip.shape),))
+    if src_layout in _PACKED_ANY:                                # the stride rules, before any device is touched
+        packed_geometry(clip[0], src_layout)
     device = clip.device if clip.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    clip = clip.to(device, non_blocking=True) if is_yuv else _device_source(clip, device)
+    clip = clip.to(device, non_blocking=True) if in_place else _device_source(clip, device)
     b, t_src = clip.shape[0], clip.shape[2] if src_layout == "NCTHW" else clip.shape[1]
-    channels = 3 if is_yuv else clip.shape[1 if src_layout == "NCTHW" else 4]
+    channels = 3 if in_place else clip.shape[1 if src_layout == "NCTHW" else 4]
     t = t_src if num_frames is None else num_frames
     frames = temporal_indices(t_src, t).to(torch.int32)[None]
     batch = build_video_batch(list(clip.unbind(0)), [frames] * b, src_layout, short_side, crop_size, views, [t], channels, device,
                               lambda x: x.to(device), height, coded_height)
+    matrix = _yuv_matrix_of(yuv, src_layout).float().reshape(12).to(device) if is_yuv else None
+    if not area:
+        d = L.BatchViewsDesc()
+        _batch_launch_fields(d, batch, batch.tables[0], 0, batch.total, channels, src_layout, matrix, (crop_size, crop_size))
+        return _scale_crop_launch(d, "pv_batch_views", "batch_views", b, channels, affine, dtype, device)
     a = L.AreaViewsDesc()
     a.filter = L.PV_FILTER_AREA
-    matrix = _yuv_matrix_of(yuv, src_layout).float().reshape(12).to(device) if is_yuv else None
     _batch_launch_fields(a.frames.batch, batch, batch.tables[0], 0, batch.total, channels, src_layout, matrix, (crop_size, crop_size))
     return _scale_crop_launch(a.frames.batch, "pv_area_views", "area_views", b, channels, affine, dtype, device, outer=a)
 
@@ -1315,6 +1414,16 @@ class DevicePacker:
     (standard, full_range) pair is composed with the layout's depth and bit alignment, and no narrowing pass exists.
     `hdr` -- "pq", "hlg" or (transfer, `tone_params(...)`), for a layout of `YUV16_LAYOUTS` only (a ValueError otherwise) --
     maps every tap from BT.2020 PQ / HLG to BT.709 SDR before the blend: every path of such a packer launches `pv_hdr_views`.
+
+    `src_layout` of `PACKED_LAYOUTS` ("BGR", "RGBA", "BGRA", "ARGB", "ABGR"; "RGBX" / "BGRX" / "XRGB" / "XBGR" are aliases):
+    uint8 packed pixels, [B, T, H, W, PB] clips, [N, H, W, PB] videos or `FrameList`s of [H, W, PB] frames, with
+    stride(-1) == 1, stride(-2) == PB and a row stride >= W * PB (`packed_geometry`; a ValueError names the stride otherwise,
+    and nothing is ever made contiguous): OpenCV's BGR24 and pitched 32-bit capture / compositor surfaces are read where they
+    lie, the tensor's row and frame strides being the record's y_pitch / frame_stride.  Every path of such a packer is
+    item-sourced (`pv_batch_views`, `pv_frame_views`, `pv_region_views`, `pv_area_views`: the clip-at-a-time call and
+    `fill_video` run a batch with every clip, or the one video, a source of its own), `keyframes=True`, `regions=True`,
+    `interpolation="area"` and `orientation=` included; `hdr` is refused, as for every layout without 16-bit samples.  An item
+    holds the bits of the "NTHWC" path on `packed_to_rgb(video, layout).contiguous()`.
 
     `fill_video(video, tables, i0, n)` + `launch()` run the resampling packer on ONE decoded video instead of clips: items
     [i0, i0 + n) of its clips x views sequence, the clips being rows of a frame table (`data.clip_frame_table`, uploaded by
@@ -1378,20 +1487,23 @@ class DevicePacker:
                              "key-frame path: keyframes=True)")
         # keyframes=True and short_side alone: no crop (the detection tutorial's protocol) -- the window is the whole scaled frame
         self.no_crop, self.keyframes = short_side is not None and crop_size is None, bool(keyframes)
-        if src_layout not in ("NCTHW", "NTHWC") + _YUV_ANY:
-            raise ValueError("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,))
+        if src_layout not in _SRC_LAYOUTS:
+            raise ValueError(_LAYOUT_ERROR)
         self.short_side, self.crop_size, self.src_layout = short_side, crop_size, src_layout
         self.is_yuv, self.coded_height, self.height = src_layout in _YUV_ANY, coded_height, height
         self.is_yuv16 = src_layout in YUV16_LAYOUTS            # 16-bit samples: pv_yuv16_views / PV_U16
+        self.is_packed = src_layout in _PACKED_ANY             # packed pixels: item-sourced launches only
+        self.in_place = self.is_yuv or self.is_packed          # read with the strides they have: never made contiguous
+        self._packed_video = None
         self.hdr = _hdr_of(hdr, src_layout)                    # (PV_TRANSFER code, tone table) or None; on the device below
         self._hdr_src = None
-        if self.is_yuv and not self.keyframes and (getattr(deployed, "_pv_load_boxes", None) is not None):
+        if self.in_place and not self.keyframes and (getattr(deployed, "_pv_load_boxes", None) is not None):
             raise ValueError("a detection model does not take %s frames: its boxes are mapped through the scaling and the crop "
                              "of an RGB clip on the host, and that path is not built for YUV sources (the key-frame path, "
                              "keyframes=True / inference.KeyframeDetector, maps them on the device for any layout)" % src_layout)
         self.views = _views(spatial_idx) if crop_size is not None else (1,)
         if short_side is None and src_layout != "NCTHW" and not self.region_mode:
-            raise ValueError("a frame-interleaved or YUV clip is read by the resampling path only: give short_side and crop_size")
+            raise ValueError("a frame-interleaved, packed or YUV clip is read by the resampling path only: give short_side and crop_size")
         if hasattr(deployed, "parts") and hasattr(deployed, "_pv_launch"):
             # split-batch deploy form (convert_to_deployable_form(..., streams=k)): one packer per sub-batch fills that
             # sub-plan's input buffers, then ONE launch of the joint graph
@@ -1479,7 +1591,7 @@ class DevicePacker:
         load_boxes = getattr(self.model, "_pv_load_boxes", None)
         if (bboxes is None) != (load_boxes is None):
             raise RuntimeError("bboxes are given to a detection model and only to a detection model")
-        if self.is_yuv and load_boxes is not None:
+        if self.in_place and load_boxes is not None:
             raise ValueError("a detection model does not take %s frames a clip at a time: its boxes are mapped on the host "
                              "there; use video_batch / fill_batch / fill_boxes (inference.KeyframeDetector)" % self.src_layout)
         _refuse_frames(clip, "a clip-at-a-time call")
@@ -1488,6 +1600,8 @@ class DevicePacker:
                                "fill_boxes; a clip at a time takes short_side and crop_size")
         if self.is_yuv:
             return self._call_yuv(clip)
+        if self.is_packed:
+            return self._call_packed(clip)
         if clip.dim() != 5:
             raise RuntimeError("expected a [B,C,T,H,W] clip, got %s" % (tuple(clip.shape),))
         resample = self.short_side is not None
@@ -1538,6 +1652,34 @@ class DevicePacker:
             self._clip_tables[(b, t)] = [_clip_rows(b, t, ref.T).to(self.sess.device) for ref in refs]
         self.fill_video(clips.to(self.sess.device, non_blocking=True), self._clip_tables[(b, t)], 0, self.batch)
         return self.launch()
+
+    def _call_packed(self, clips):
+        """B materialised clips of packed pixels [B, T', H, W, PB], read with the strides they have: every clip a source of its
+        own, its frames one table row (`video_batch` + `fill_batch`: pv_batch_views), then the forward."""
+        if clips.dim() != 5:
+            raise RuntimeError("expected %s clips [B, T, H, W, %d], got %s" % (self.src_layout, _packed_bytes(self.src_layout), tuple(clips.shape),))
+        b, t = clips.shape[:2]
+        if b * len(self.views) != self.batch:
+            raise RuntimeError("deploy form was converted for a batch of %d = clips x views, got %d clips x %d views"
+                               % (self.batch, b, len(self.views)))
+        if t != self.clip_frames:
+            raise RuntimeError("the deploy form takes clips of %d frames, the clips have %d" % (self.clip_frames, t))
+        rows = torch.arange(t, dtype=torch.int32)[None]
+        batch = self.video_batch(list(clips.to(self.sess.device, non_blocking=True).unbind(0)), [rows] * b)
+        self.fill_batch(batch, 0, batch.total)
+        return self.launch()
+
+    def _fill_packed_video(self, video, tables, i0, n):
+        """`fill_video` of packed pixels: the one-source entry points do not read them, so the video is a batch of one
+        (pv_batch_views) whose records and items are uploaded once per (video, tables) and whose frame tables are the
+        caller's, already on the device."""
+        key = (video.data_ptr(), tuple(video.shape), video.stride(), tuple(t.data_ptr() for t in tables))
+        if self._packed_video is None or self._packed_video[0] != key:
+            rows = torch.zeros((tables[0].shape[0], self.clip_frames), dtype=torch.int32)   # frame 0: the tables are the caller's
+            batch = self.video_batch([video], [rows])
+            batch.tables = list(tables)
+            self._packed_video = (key, batch)
+        self.fill_batch(self._packed_video[1], i0, n)
 
     def _fill(self, clip):
         t_src = clip.shape[2]
@@ -1623,6 +1765,8 @@ class DevicePacker:
         if not (0 <= i0 and 0 < n <= self.batch and i0 + n <= total):
             raise RuntimeError("items [%d, %d) are not a chunk of at most %d of the video's %d clips x views"
                                % (i0, i0 + n, self.batch, total))
+        if self.is_packed:
+            return self._fill_packed_video(video, tables, i0, n)
         if self.subs is None:
             return self._fill_video(video, source, tables, i0, n)
         lo = 0
