@@ -563,6 +563,8 @@ int pv_yuv16_views(const pv_yuv_views_desc* d, pv_stream_t stream);
 enum { PV_SRC_YUV420 = 2 };   /* pv_batch_views_desc.src_layout only, beside pv_resample_src_layout */
 /* Packed pixels (see "packed pixels" below); pv_batch_views_desc.src_layout only.  The value 3 is no layout. */
 enum { PV_SRC_BGR = 4, PV_SRC_RGBA = 5, PV_SRC_BGRA = 6, PV_SRC_ARGB = 7, PV_SRC_ABGR = 8 };
+/* YUV 4:2:2 and 4:4:4 (see "YUV 4:2:2 and 4:4:4" below); pv_batch_views_desc.src_layout only.  The value 9 is no layout. */
+enum { PV_SRC_YUV422 = 10, PV_SRC_YUV444 = 11 };
 typedef struct pv_view_source {      /* one decoded video; 96 bytes, 8-byte aligned */
   const void* src;                   /* device address of the video / of frame 0                              */
   int64_t frame_stride;              /* YUV and packed sources: bytes between frames (RGB / planar: dense)    */
@@ -584,12 +586,12 @@ typedef struct pv_batch_views_desc {
   void* dst;
   const float* ch_scale;              /* [C] or NULL                                                           */
   const float* ch_shift;              /* [C] or NULL                                                           */
-  const float* yuv2rgb;               /* PV_SRC_YUV420: [3][4] fp32 on the device                              */
+  const float* yuv2rgb;               /* PV_SRC_YUV420 / 422 / 444: [3][4] fp32 on the device                  */
   int64_t bs;                         /* PV_DST_NDHWC only: batch stride in elements                           */
   int32_t n_sources, n_items, n_rows, t_stride;
   int32_t C, T;                       /* channels (<= 4; 3 for YUV), DESTINATION frames per item               */
   int32_t src_dtype, src_layout;      /* pv_dtype; PV_SRC_NCTHW / PV_SRC_NTHWC / PV_SRC_YUV420 / PV_SRC_BGR .. */
-  int32_t c_step;                     /* PV_SRC_YUV420: 2 interleaved chroma, 1 planar                         */
+  int32_t c_step;                     /* PV_SRC_YUV420 / 422 / 444: 2 interleaved chroma, 1 planar             */
   int32_t Ho, Wo, n_views;            /* crop window; views per clip, 1..3                                     */
   int32_t dst_layout, dst_dtype;
   int32_t c_p, ld;                    /* PV_DST_NDHWC only                                                     */
@@ -812,6 +814,51 @@ int pv_area_views(const pv_area_views_desc* d, pv_stream_t stream);
  * whatever the entry point rejects of any launch.  PV_ERR_UNSUPPORTED: unchanged in meaning (the LDS limits of a staged strip
  * or tile -- a column counts PB bytes --, the index limit of pv_area_views, src_dtype PV_U16 outside YUV).  Validation precedes
  * every HIP call, and an invalid field wins over an unsupported size.
+ */
+
+/* ---- YUV 4:2:2 and 4:4:4: planar and semi-planar frames of 8- to 16-bit samples read where they lie -----------------------
+ * A CPU decoder hands out more than 4:2:0: yuvj422p from MJPEG (most USB and IP cameras), yuv422p10le from ProRes / DNxHR and
+ * contribution feeds, NV16 / P210 from capture SDKs, yuv444p / yuv444p10le from screen recordings, High 4:4:4 streams and
+ * lossless archives.  PV_SRC_YUV420 hard-wires the chroma of pixel (y, x) to (y >> 1, x >> 1), so such a video needed a chroma
+ * decimation into a 4:2:0 copy, or an RGB copy, before the launch.  Two more values of pv_batch_views_desc.src_layout (declared
+ * beside PV_SRC_YUV420; the value 9 is no layout and stays PV_ERR_INVALID) name them:
+ *                   PV_SRC_YUV422   (csy, csx) = (0, 1): chroma halved in x only        PV_SRC_YUV444   (0, 0): full-size chroma
+ *               (PV_SRC_YUV420 is (1, 1)).  The subsampling belongs to the LAUNCH, as c_step and the sample width do.
+ * Honoured by:  pv_batch_views, pv_frame_views, pv_region_views and pv_area_views -- whole videos and frame lists, orient 0..7
+ *               where the entry point takes it, up to three views, all five destination forms.  NOT by pv_hdr_views, which
+ *               answers PV_ERR_UNSUPPORTED as for everything but 16-bit 4:2:0, and not by the one-source entry points
+ *               (pv_resample_crop, pv_video_views, pv_yuv_views, pv_yuv16_views), which have no field for them.
+ * Record:       the fields of a PV_SRC_YUV420 record with the same meaning, in bytes; sb = 1 (PV_U8) or 2 (PV_U16):
+ *                   Y(y, x) = frame[y * y_pitch + x * sb]                                  0 <= y < Hs, 0 <= x < Ws
+ *                   U(j, i) = frame[u_offset + j * c_pitch + i * c_step * sb]              0 <= j < ceil(Hs / 2^csy),
+ *                   V(j, i) = frame[v_offset + j * c_pitch + i * c_step * sb]              0 <= i < ceil(Ws / 2^csx)
+ *                   tap (y, x) uses U(y >> csy, x >> csx) and V(y >> csy, x >> csx)
+ *               c_step 1 (two planes: yuv422p, yuv444p and their 10- to 16-bit kin) and c_step 2 (one interleaved plane,
+ *               |v_offset - u_offset| == sb: NV16 / NV61 / P210, and with PV_SRC_YUV444 NV24 / NV42) are valid with both.
+ *               PV_SRC_YUV422 needs an even Ws and takes any Hs; PV_SRC_YUV444 takes any Hs and Ws, odd included.  PV_U16: the
+ *               evenness rules of pv_yuv16_views (src or every frame address, pitches, offsets and frame_stride even).  Pitched
+ *               surfaces and coded heights are what y_pitch, c_pitch and the offsets say; depth and bit alignment live in
+ *               yuv2rgb, as for P010 / yuv420p10le.
+ * pv_region_views: only the members the subsampling halves are even: left and w for PV_SRC_YUV422, none for PV_SRC_YUV444.
+ * Arithmetic:   pv_yuv_views' pinned rule, unchanged: each tap is converted with the three fused multiply-adds and clamped, then
+ *               the pinned blend or the pinned window sums of pv_area_views, the affine map, one rounding.  Chroma is REPLICATED
+ *               over the luma pixels it covers; sited or filtered chroma stays out of scope.  Hence the guarantee of every new
+ *               launch: AN ITEM HOLDS, BIT FOR BIT, WHAT THE SAME ENTRY POINT WRITES WITH PV_SRC_YUV444 FOR THE FRAMES WHOSE
+ *               CHROMA PLANES HOLD EVERY SAMPLE REPLICATED OVER THE PIXELS IT COVERS -- and a PV_SRC_YUV420 launch holds what
+ *               both new layouts write for its replicated copies.
+ * Orientation:  for a subsampled layout a quarter turn of the STORED frame is no layout of its own (4:2:2 turned is chroma halved
+ *               in y), so the contract of an oriented record is stated through the full-resolution copy: the chroma of displayed
+ *               pixel (y, x) is the chroma sample of the stored pixel it maps to, and AN ITEM OF AN ORIENTED RECORD HOLDS, BIT
+ *               FOR BIT, WHAT THE SAME LAUNCH WRITES WITH PV_SRC_YUV444 AND orient = 0 FOR THE REPLICATED COPY ORIENTED
+ *               BEFOREHAND.  (PV_SRC_YUV444 itself keeps the 4:2:0 wording: Y, U and V planes oriented separately.)
+ * Kernels:      chroma arrangement and sample width are compiled in, the two shifts are a workgroup-uniform kernel argument:
+ *               one kernel serves both layouts (pytorchvideo_amd/csrc/pv_yuv4.hip).  A staged strip or tile holds the luma
+ *               span and the chroma span behind it; with full-size chroma that is up to three times the luma bytes.
+ * PV_ERR_INVALID, before every HIP call: a pitch that cannot hold a row; a plane outside [0, frame_stride); an odd Ws with
+ * PV_SRC_YUV422; c_step outside {1, 2}, or 2 with |v_offset - u_offset| != sb; C != 3; a null yuv2rgb; PV_U16 with an odd
+ * address, pitch, offset or stride; an odd rectangle member the subsampling halves; and whatever the entry point rejects of any
+ * launch.  PV_ERR_UNSUPPORTED: a staged strip or tile beyond the LDS limit, the index limit of pv_area_views, oriented records
+ * in pv_region_views / pv_area_views, pv_hdr_views.  An invalid field wins over an unsupported size.
  */
 
 /* ---- key-frame detection: the boxes of a forward mapped into its views, on the device ---------------------------------

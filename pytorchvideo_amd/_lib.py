@@ -94,6 +94,8 @@ YuvViewsDesc = _struct("YuvViewsDesc", [
 SRC_YUV420 = 2   # BatchViewsDesc.src_layout only
 # packed pixels (the header's "packed pixels"): BatchViewsDesc.src_layout only; the value 3 is no layout
 SRC_BGR, SRC_RGBA, SRC_BGRA, SRC_ARGB, SRC_ABGR = 4, 5, 6, 7, 8
+# YUV 4:2:2 and 4:4:4 (the header's "YUV 4:2:2 and 4:4:4"): BatchViewsDesc.src_layout only; the value 9 is no layout
+SRC_YUV422, SRC_YUV444 = 10, 11
 ViewSource = _struct("ViewSource", [
     ("src", _p), ("frame_stride", _i64), ("u_offset", _i64), ("v_offset", _i64)]
     + _ints("y_pitch", "c_pitch", "N", "Hs", "Ws", "Hn", "Wn") + [("y_off", _i32 * 3), ("x_off", _i32 * 3), ("sy", _f32), ("sx", _f32)]

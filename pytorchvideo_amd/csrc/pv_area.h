@@ -1,7 +1,8 @@
-// The staged-tile body of pv_area_views over RGB / planar sources (pv_area.hip describes the three steps), with what it is
-// made of: the launch record, the tile of a workgroup and the store of its results.  It is here, not in pv_area.hip, because
-// two translation units instantiate it: pv_area.hip for the dense forms and pv_packed.hip for packed pixels (RsPacked,
-// pv_rs.h).  ar_tile_yuv, the sizing and the entry point stay in pv_area.hip.
+// The staged-tile bodies of pv_area_views (pv_area.hip describes the three steps), with what they are made of: the launch
+// record, the tile of a workgroup and the store of its results.  They are here, not in pv_area.hip, because other translation
+// units instantiate them: ar_tile_rgb serves pv_area.hip (the dense forms) and pv_packed.hip (packed pixels: RsPacked,
+// pv_rs.h), ar_tile_yuv serves pv_area.hip (4:2:0) and pv_yuv4.hip (4:2:2 / 4:4:4: RsSub, pv_rs.h).  The sizing and the entry
+// point stay in pv_area.hip.
 #pragma once
 #include "pv_frames.h"
 
@@ -17,6 +18,8 @@ struct ArLaunch {
 
 // The packed-pixel kernels of pv_area_views (pv_packed.hip) on a launch ar_run (pv_area.hip) has validated and sized.
 int pv_packed_area(const pv_batch_views_desc& d, bool frames, const ArLaunch& g, size_t lds, pv_stream_t stream);
+// Likewise the YUV 4:2:2 / 4:4:4 kernels of pv_area_views (pv_yuv4.hip).
+int pv_yuv4_area(const pv_batch_views_desc& d, bool frames, const ArLaunch& g, size_t lds, pv_stream_t stream);
 
 namespace {
 
@@ -153,6 +156,114 @@ __device__ __forceinline__ void ar_tile_rgb(unsigned char* lds, const ArLaunch& 
   __syncthreads();
 
   ar_store<FORM, D>(res, g, a, d, d.C, zi, t);
+}
+
+// CSTEP / FORM / D / SMP / SUB: as rs_strip_yuv.
+template <int CSTEP, int FORM, typename D, typename SMP, typename SUB = RsSub420>
+__device__ __forceinline__ void ar_tile_yuv(unsigned char* lds, const ArLaunch& g, const RsYuvSrc& s, int Hn, int Wn, const RsDst& d,
+                                            const float* yuv2rgb, int zi, int t, const SUB& sub = SUB()) {
+  constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
+  constexpr int SB = (int)sizeof(SMP);             // bytes from one luma column to the next
+  constexpr int CB = CSTEP * SB;                   // bytes from one chroma column to the next
+  const int tid = threadIdx.x;
+  const ArTile a = ar_tile(g, d.Ho, d.Wo, s.yoff, s.xoff, s.Hs, s.Ws, Hn, Wn);
+  if (a.nrows <= 0 || a.ncols <= 0) return;
+  const int pitch_y = g.pitch, pitch_c = g.pitch_c, c_base = g.c_base;
+  const int cr0 = a.ys0 >> sub.csy, cc0 = a.xs0 >> sub.csx;
+  const int nslots = a.ys1 - a.ys0, ncslots = ((a.ys1 - 1) >> sub.csy) - cr0 + 1;
+  const int span_y = (a.xs1 - a.xs0) * SB;
+  const int span_c = (((a.xs1 - 1) >> sub.csx) - cc0 + 1) * CB;
+  if (nslots > g.rows || ncslots > g.rows_c || span_y + 15 > pitch_y || span_c + 15 > pitch_c) return;
+
+  const uintptr_t frame = s.src + s.frame_off;
+  auto y_addr = [&](int y) -> uintptr_t { return frame + (long)y * s.y_pitch + a.xs0 * SB; };
+  auto c_addr = [&](int cy, int pl) -> uintptr_t {
+    return frame + (pl == 0 ? s.c_off_a : s.c_off_b) + (long)cy * s.c_pitch + (long)cc0 * CB;
+  };
+
+  // ---- stage -------------------------------------------------------------------------------------------------
+  const int cpr_y = pitch_y >> 4, cpr_c = pitch_c >> 4;   // 16-byte chunks per staged row
+  const int total_y = nslots * cpr_y;
+  const int total = total_y + ncslots * CP * cpr_c;
+  for (int base = tid; base < total; base += kRsThreads * 4) {
+    u32x4 val[4];
+    int off[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = base + u * kRsThreads;
+      off[u] = -1;
+      if (idx < total) {
+        const bool luma = idx < total_y;
+        const int j = luma ? idx : idx - total_y;
+        const int cpr = luma ? cpr_y : cpr_c;
+        const int sp = j / cpr, ch = j - sp * cpr;             // luma: sp = slot; chroma: sp = slot * CP + plane
+        const int slot = luma ? sp : sp / CP, pl = luma ? 0 : sp - slot * CP;
+        const uintptr_t ad = luma ? y_addr(a.ys0 + slot) : c_addr(cr0 + slot, pl);
+        if (ch * 16 < (int)(ad & 15) + (luma ? span_y : span_c)) {
+          val[u] = *reinterpret_cast<const u32x4*>((ad & ~(uintptr_t)15) + (uintptr_t)ch * 16);
+          off[u] = (luma ? sp * pitch_y : c_base + sp * pitch_c) + ch * 16;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (off[u] >= 0) *reinterpret_cast<u32x4*>(lds + off[u]) = val[u];
+  }
+  __syncthreads();
+
+  // ---- sum ---------------------------------------------------------------------------------------------------
+  float m[12], sc[3], sh[3];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) m[i] = yuv2rgb[i];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    sc[c] = d.ch_scale ? d.ch_scale[c] : 1.f;
+    sh[c] = (d.ch_scale && d.ch_shift) ? d.ch_shift[c] : 0.f;
+  }
+  // the low address bits of a staged row: 32-bit arithmetic keeps `addr & 15`
+  const unsigned ya32 = (unsigned)(frame + a.xs0 * SB), yp32 = (unsigned)s.y_pitch, cp32 = (unsigned)s.c_pitch;
+  const unsigned ua32 = (unsigned)(frame + s.c_off_a + (long)cc0 * CB), va32 = (unsigned)(frame + s.c_off_b + (long)cc0 * CB);
+  // LDS byte offsets of the Y, U and V samples of source pixel (y, column offsets oyx / ocx)
+  auto tap = [&](int y, int oyx, int ocx, int& oy, int& ou, int& ov) {
+    oy = (y - a.ys0) * pitch_y + (int)((ya32 + (unsigned)y * yp32) & 15u) + oyx;
+    const int cr = y >> sub.csy, crow = c_base + (cr - cr0) * CP * pitch_c;
+    ou = crow + (int)((ua32 + (unsigned)cr * cp32) & 15u) + s.u_byte + ocx;
+    ov = crow + (CP - 1) * pitch_c + (int)((va32 + (unsigned)cr * cp32) & 15u) + s.v_byte + ocx;
+  };
+  float* res = reinterpret_cast<float*>(lds + g.out_base);
+  const int npix = a.nrows * a.ncols;
+  for (int p = tid; p < npix; p += kRsThreads) {
+    const int r = p / a.ncols, x = p - r * a.ncols;
+    int wy0, wy1, wx0, wx1;
+    rs_area_win(s.yoff + a.row0 + r, s.Hs, Hn, wy0, wy1);
+    rs_area_win(s.xoff + a.col0 + x, s.Ws, Wn, wx0, wx1);
+    float tot[3] = {0.f, 0.f, 0.f};
+    for (int cx = wx0; cx < wx1; ++cx) {
+      float cs[3] = {0.f, 0.f, 0.f};               // the column sums of the converted, clamped taps, rows ascending
+      const int oyx = (cx - a.xs0) * SB, ocx = ((cx >> sub.csx) - cc0) * CB;
+      for (int cy = wy0; cy < wy1; cy += 2) {      // two rows per call: yuv_tap2's packed pair
+        const bool two = cy + 1 < wy1;
+        int y0, u0, v0, y1, u1, v1;
+        tap(cy, oyx, ocx, y0, u0, v0);
+        tap(two ? cy + 1 : cy, oyx, ocx, y1, u1, v1);
+        f32x2 rgb[3];
+        yuv_tap2<SMP>(m, lds, y0, u0, v0, y1, u1, v1, rgb);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          cs[c] += rgb[c][0];
+          if (two) cs[c] += rgb[c][1];
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) tot[c] += cs[c];  // columns ascending
+    }
+    const float cnt = (float)((wy1 - wy0) * (wx1 - wx0));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) res[(c * g.R + r) * g.X + x] = fmaf(tot[c] / cnt, sc[c], sh[c]);
+  }
+  __syncthreads();
+
+  ar_store<FORM, D>(res, g, a, d, 3, zi, t);
 }
 
 }  // namespace

@@ -9,7 +9,8 @@
 //   1. stage: the windows of the tile's outputs cover ONE rectangle of the source, rows [start_y(first), end_y(last)) x columns
 //      likewise.  Its rows are copied to LDS in the source dtype exactly as the tiles of pv_rs.h copy theirs: the aligned 16-byte
 //      granules that cover each row's span, a batch of four loads per thread, the LDS image of a row keeping the span's
-//      `addr & 15`.  YUV stages the chroma rectangle [ys0 >> 1, (ys1 - 1) >> 1] x [xs0 >> 1, (xs1 - 1) >> 1] behind the luma one.
+//      `addr & 15`.  YUV stages the chroma rectangle [ys0 >> 1, (ys1 - 1) >> 1] x [xs0 >> 1, (xs1 - 1) >> 1] behind the luma one
+//      (4:2:0; the shifts are the layout's, RsSub of pv_rs.h).
 //      Tiling in x keeps the staged bytes independent of the frame width (a no-crop view of a 2160p frame is 3840 columns).
 //   2. barrier; sum: a thread owns ONE output pixel, so all 256 threads work whatever the destination form.  It walks its
 //      window's columns in ascending order and, per column, the window's rows in ascending order (the pinned order: the column
@@ -30,116 +31,9 @@
 
 namespace {
 
-// ArLaunch, the tile of a workgroup, the store and ar_tile_rgb are in pv_area.h: pv_packed.hip instantiates them too.
+// ArLaunch, the tile of a workgroup, the store, ar_tile_rgb and ar_tile_yuv are in pv_area.h: pv_packed.hip and pv_yuv4.hip
+// instantiate them too.
 constexpr int kArTiles[][2] = {{8, 64}, {8, 32}, {4, 32}, {4, 16}, {2, 16}, {2, 8}, {1, 8}};   // R x X, largest first
-
-// CSTEP / FORM / D / SMP: as rs_strip_yuv.
-template <int CSTEP, int FORM, typename D, typename SMP>
-__device__ __forceinline__ void ar_tile_yuv(unsigned char* lds, const ArLaunch& g, const RsYuvSrc& s, int Hn, int Wn, const RsDst& d,
-                                            const float* yuv2rgb, int zi, int t) {
-  constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
-  constexpr int SB = (int)sizeof(SMP);             // bytes from one luma column to the next
-  constexpr int CB = CSTEP * SB;                   // bytes from one chroma column to the next
-  const int tid = threadIdx.x;
-  const ArTile a = ar_tile(g, d.Ho, d.Wo, s.yoff, s.xoff, s.Hs, s.Ws, Hn, Wn);
-  if (a.nrows <= 0 || a.ncols <= 0) return;
-  const int pitch_y = g.pitch, pitch_c = g.pitch_c, c_base = g.c_base;
-  const int cr0 = a.ys0 >> 1, cc0 = a.xs0 >> 1;
-  const int nslots = a.ys1 - a.ys0, ncslots = ((a.ys1 - 1) >> 1) - cr0 + 1;
-  const int span_y = (a.xs1 - a.xs0) * SB;
-  const int span_c = (((a.xs1 - 1) >> 1) - cc0 + 1) * CB;
-  if (nslots > g.rows || ncslots > g.rows_c || span_y + 15 > pitch_y || span_c + 15 > pitch_c) return;
-
-  const uintptr_t frame = s.src + s.frame_off;
-  auto y_addr = [&](int y) -> uintptr_t { return frame + (long)y * s.y_pitch + a.xs0 * SB; };
-  auto c_addr = [&](int cy, int pl) -> uintptr_t {
-    return frame + (pl == 0 ? s.c_off_a : s.c_off_b) + (long)cy * s.c_pitch + (long)cc0 * CB;
-  };
-
-  // ---- stage -------------------------------------------------------------------------------------------------
-  const int cpr_y = pitch_y >> 4, cpr_c = pitch_c >> 4;   // 16-byte chunks per staged row
-  const int total_y = nslots * cpr_y;
-  const int total = total_y + ncslots * CP * cpr_c;
-  for (int base = tid; base < total; base += kRsThreads * 4) {
-    u32x4 val[4];
-    int off[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int idx = base + u * kRsThreads;
-      off[u] = -1;
-      if (idx < total) {
-        const bool luma = idx < total_y;
-        const int j = luma ? idx : idx - total_y;
-        const int cpr = luma ? cpr_y : cpr_c;
-        const int sp = j / cpr, ch = j - sp * cpr;             // luma: sp = slot; chroma: sp = slot * CP + plane
-        const int slot = luma ? sp : sp / CP, pl = luma ? 0 : sp - slot * CP;
-        const uintptr_t ad = luma ? y_addr(a.ys0 + slot) : c_addr(cr0 + slot, pl);
-        if (ch * 16 < (int)(ad & 15) + (luma ? span_y : span_c)) {
-          val[u] = *reinterpret_cast<const u32x4*>((ad & ~(uintptr_t)15) + (uintptr_t)ch * 16);
-          off[u] = (luma ? sp * pitch_y : c_base + sp * pitch_c) + ch * 16;
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (off[u] >= 0) *reinterpret_cast<u32x4*>(lds + off[u]) = val[u];
-  }
-  __syncthreads();
-
-  // ---- sum ---------------------------------------------------------------------------------------------------
-  float m[12], sc[3], sh[3];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) m[i] = yuv2rgb[i];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    sc[c] = d.ch_scale ? d.ch_scale[c] : 1.f;
-    sh[c] = (d.ch_scale && d.ch_shift) ? d.ch_shift[c] : 0.f;
-  }
-  // the low address bits of a staged row: 32-bit arithmetic keeps `addr & 15`
-  const unsigned ya32 = (unsigned)(frame + a.xs0 * SB), yp32 = (unsigned)s.y_pitch, cp32 = (unsigned)s.c_pitch;
-  const unsigned ua32 = (unsigned)(frame + s.c_off_a + (long)cc0 * CB), va32 = (unsigned)(frame + s.c_off_b + (long)cc0 * CB);
-  // LDS byte offsets of the Y, U and V samples of source pixel (y, column offsets oyx / ocx)
-  auto tap = [&](int y, int oyx, int ocx, int& oy, int& ou, int& ov) {
-    oy = (y - a.ys0) * pitch_y + (int)((ya32 + (unsigned)y * yp32) & 15u) + oyx;
-    const int cr = y >> 1, crow = c_base + (cr - cr0) * CP * pitch_c;
-    ou = crow + (int)((ua32 + (unsigned)cr * cp32) & 15u) + s.u_byte + ocx;
-    ov = crow + (CP - 1) * pitch_c + (int)((va32 + (unsigned)cr * cp32) & 15u) + s.v_byte + ocx;
-  };
-  float* res = reinterpret_cast<float*>(lds + g.out_base);
-  const int npix = a.nrows * a.ncols;
-  for (int p = tid; p < npix; p += kRsThreads) {
-    const int r = p / a.ncols, x = p - r * a.ncols;
-    int wy0, wy1, wx0, wx1;
-    rs_area_win(s.yoff + a.row0 + r, s.Hs, Hn, wy0, wy1);
-    rs_area_win(s.xoff + a.col0 + x, s.Ws, Wn, wx0, wx1);
-    float tot[3] = {0.f, 0.f, 0.f};
-    for (int cx = wx0; cx < wx1; ++cx) {
-      float cs[3] = {0.f, 0.f, 0.f};               // the column sums of the converted, clamped taps, rows ascending
-      const int oyx = (cx - a.xs0) * SB, ocx = ((cx >> 1) - cc0) * CB;
-      for (int cy = wy0; cy < wy1; cy += 2) {      // two rows per call: yuv_tap2's packed pair
-        const bool two = cy + 1 < wy1;
-        int y0, u0, v0, y1, u1, v1;
-        tap(cy, oyx, ocx, y0, u0, v0);
-        tap(two ? cy + 1 : cy, oyx, ocx, y1, u1, v1);
-        f32x2 rgb[3];
-        yuv_tap2<SMP>(m, lds, y0, u0, v0, y1, u1, v1, rgb);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          cs[c] += rgb[c][0];
-          if (two) cs[c] += rgb[c][1];
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) tot[c] += cs[c];  // columns ascending
-    }
-    const float cnt = (float)((wy1 - wy0) * (wx1 - wx0));
-#pragma unroll
-    for (int c = 0; c < 3; ++c) res[(c * g.R + r) * g.X + x] = fmaf(tot[c] / cnt, sc[c], sh[c]);
-  }
-  __syncthreads();
-
-  ar_store<FORM, D>(res, g, a, d, 3, zi, t);
-}
 
 // S / INTER / FORM / D: as rs_strip_rgb.
 template <typename S, bool INTER, int FORM, typename D>
@@ -168,9 +62,10 @@ __global__ __launch_bounds__(kRsThreads) void area_yuv_kernel(const pv_batch_vie
 // Folds the widest footprint of an R x X tile of record v over its views into n: source rows, source columns, chroma rows,
 // chroma columns.  Rows and columns are independent, so the bands of strips and of column tiles are walked separately, with
 // the very calls the kernel makes (ar_tile).
-inline void ar_footprint(const pv_view_source& v, int n_views, int Ho, int Wo, int R, int X, int (&n)[4]) {
+inline void ar_footprint(const pv_view_source& v, int n_views, int Ho, int Wo, int R, int X, int (&n)[4], RsSub sub) {
   auto fold = [&](int lo, int end, int at) {       // source interval [lo, end) of rows (at = 0) / of columns (at = 1)
-    const int a = end - lo, c = ((end - 1) >> 1) - (lo >> 1) + 1;
+    const int cs = at == 0 ? sub.csy : sub.csx;    // the chroma shift of the axis
+    const int a = end - lo, c = ((end - 1) >> cs) - (lo >> cs) + 1;
     n[at] = a > n[at] ? a : n[at];
     n[at + 2] = c > n[at + 2] ? c : n[at + 2];
   };
@@ -195,10 +90,12 @@ inline void ar_footprint(const pv_view_source& v, int n_views, int Ho, int Wo, i
 // beyond 50 for uint8 sources, beyond 25 for fp32 ones: a 2160p frame scaled to a short side of 80).
 inline int ar_size(const pv_batch_views_desc& d, const std::vector<const pv_view_source*>& records, ArLaunch& g, size_t& lds) {
   constexpr size_t n_tiles = sizeof(kArTiles) / sizeof(kArTiles[0]);
+  RsSub sub = {1, 1};
+  rs_yuv_sub(d.src_layout, &sub);
   for (size_t k = 0; k < n_tiles; ++k) {
     const int R = kArTiles[k][0], X = kArTiles[k][1];
     int n[4] = {0, 0, 0, 0};
-    for (const pv_view_source* v : records) ar_footprint(*v, d.n_views, d.Ho, d.Wo, R, X, n);
+    for (const pv_view_source* v : records) ar_footprint(*v, d.n_views, d.Ho, d.Wo, R, X, n, sub);
     g = {};
     g.R = R, g.X = X, g.tiles_x = (int32_t)pv_ceil_div(d.Wo, X);
     long bytes = rs_tile_layout(d, n, g);           // the staged source rectangle, as a tile of pv_rs.h lays it out
@@ -222,7 +119,7 @@ inline int ar_size(const pv_batch_views_desc& d, const std::vector<const pv_view
 template <typename CheckSrc>
 int ar_run(const pv_batch_views_desc& d, bool frames, const CheckSrc& check_src, pv_stream_t stream) {
   if (int e = rs_check_item_desc(d)) return e;
-  const bool yuv = d.src_layout == PV_SRC_YUV420;
+  const bool yuv = rs_yuv_sub(d.src_layout);
   std::vector<const pv_view_source*> records;      // the records the items name, a video-major run once
   const auto check = [&](const pv_view_source& v) { return rs_check_record(d, v, yuv, check_src); };
   const auto each = [&](const pv_view_item&, const pv_view_source& v, bool again) {
@@ -239,6 +136,7 @@ int ar_run(const pv_batch_views_desc& d, bool frames, const CheckSrc& check_src,
   size_t lds = 0;
   if (int e = ar_size(d, records, g, lds)) return e;
   if (rs_packed_px(d.src_layout)) return pv_packed_area(d, frames, g, lds, stream);   // pv_packed.hip
+  if (rs_yuv4(d.src_layout)) return pv_yuv4_area(d, frames, g, lds, stream);           // pv_yuv4.hip
   const int fr = frames ? 1 : 0;
   RS_SOURCE_FORMS(AR_RGB, AR_YUV);
   PV_LAUNCH_CHECK();

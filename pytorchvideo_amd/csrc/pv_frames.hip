@@ -64,6 +64,7 @@ int fv_run(const pv_frame_views_desc& f, pv_stream_t stream) {
   // the strips of a run of upright items: the whole launch when no record is oriented
   auto upright = [&](const pv_batch_views_desc& d) -> int {
     if (rs_packed_px(d.src_layout)) return pv_packed_strips(d, true, g, lds, stream);   // pv_packed.hip
+    if (rs_yuv4(d.src_layout)) return pv_yuv4_strips(d, true, g, lds, stream);           // pv_yuv4.hip
     RS_SOURCE_FORMS(FV_RGB, FV_YUV);
     PV_LAUNCH_CHECK();
     return PV_OK;

@@ -64,12 +64,13 @@ __global__ __launch_bounds__(kRsThreads) void region_yuv_kernel(const pv_batch_v
 #define RG_YUV(CSTEP, SMP) RG_STRIPS(region_yuv_kernel, CSTEP, SMP)
 
 // One rectangle against the frame of the item's source and the launch's window.
-inline int rg_check_region(const pv_view_region& r, const pv_view_source& v, int Ho, int Wo, bool yuv) {
+// even: the members a YUV layout's subsampling halves (bit 0: top and h, bit 1: left and w) must be even.
+inline int rg_check_region(const pv_view_region& r, const pv_view_source& v, int Ho, int Wo, int even) {
   if (r.h < 1 || r.w < 1 || r.top < 0 || r.left < 0) return PV_ERR_INVALID;
   if ((long)r.top + r.h > v.Hs || (long)r.left + r.w > v.Ws) return PV_ERR_INVALID;
   if (!rs_same_bits(r.sy, (float)r.h / (float)Ho) || !rs_same_bits(r.sx, (float)r.w / (float)Wo)) return PV_ERR_INVALID;
   if (r.reserved[0] != 0 || r.reserved[1] != 0) return PV_ERR_INVALID;
-  if (yuv && ((r.top | r.left | r.h | r.w) & 1)) return PV_ERR_INVALID;
+  if ((((even & 1) ? (r.top | r.h) : 0) | ((even & 2) ? (r.left | r.w) : 0)) & 1) return PV_ERR_INVALID;
   return PV_OK;
 }
 
@@ -83,7 +84,9 @@ int rg_run(const pv_region_views_desc& r, bool frames, const CheckSrc& check_src
   const pv_batch_views_desc& d = r.frames.batch;
   if (int e = rs_check_item_desc(d)) return e;
   if (d.n_views != 1) return PV_ERR_INVALID;       // so the walk accepts view 0 only
-  const bool yuv = d.src_layout == PV_SRC_YUV420;
+  RsSub sub = {1, 1};
+  const bool yuv = rs_yuv_sub(d.src_layout, &sub);
+  const int even = yuv ? sub.csy | (sub.csx << 1) : 0;
   int span = 0, span_c = 0;
   bool oriented = false;
   const int32_t origin = 0;
@@ -92,8 +95,8 @@ int rg_run(const pv_region_views_desc& r, bool frames, const CheckSrc& check_src
     oriented |= v.orient != 0;
     const pv_view_region* row = r.regions + (long)it.row * d.t_stride;
     for (int t = 0; t < d.T; ++t) {
-      if (int e = rg_check_region(row[t], v, d.Ho, d.Wo, yuv)) return e;
-      rs_widest_span(row[t].sx, &origin, 1, d.Wo, row[t].w, span, span_c);
+      if (int e = rg_check_region(row[t], v, d.Ho, d.Wo, even)) return e;
+      rs_widest_span(row[t].sx, &origin, 1, d.Wo, row[t].w, span, span_c, sub.csx);
     }
     return PV_OK;
   };
@@ -103,6 +106,7 @@ int rg_run(const pv_region_views_desc& r, bool frames, const CheckSrc& check_src
   size_t lds = 0;
   if (int e = rs_strip_size(d, span, span_c, g, lds)) return e;
   if (rs_packed_px(d.src_layout)) return pv_packed_regions(d, frames, g, lds, r.regions_dev, stream);   // pv_packed.hip
+  if (rs_yuv4(d.src_layout)) return pv_yuv4_regions(d, frames, g, lds, r.regions_dev, stream);           // pv_yuv4.hip
   const int fr = frames ? 1 : 0;
   const pv_view_region* regions = r.regions_dev;
   RS_SOURCE_FORMS(RG_RGB, RG_YUV);

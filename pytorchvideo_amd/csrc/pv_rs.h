@@ -11,6 +11,8 @@
 //                                       body of its own (a window's rows are not two; its RGB body is in pv_area.h)
 //   pv_packed.hip     (launched from pv_batch.hip, pv_frames.hip, pv_orient.hip, pv_region.hip and pv_area.hip)   the kernels of
 //                                       packed-pixel launches (PV_SRC_BGR .. PV_SRC_ABGR): the RGB bodies with RsPacked<PB>
+//   pv_yuv4.hip       (launched from the same five)       the kernels of YUV 4:2:2 / 4:4:4 launches (PV_SRC_YUV422, PV_SRC_YUV444):
+//                                       the YUV bodies with the chroma shifts as a kernel argument (RsSub)
 // What they compute with is here, once: the pinned source coordinate, the destination forms with their stores, the taps and
 // blends, the two staged-strip bodies (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather) and the two staged-tile bodies of
 // oriented records (rs_tile_rgb, rs_tile_yuv), the launch arithmetic (widest span, rows per strip, the LDS layout of a staged
@@ -31,6 +33,7 @@
 // keeps its own kernels.
 #pragma once
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "pv_common.h"
@@ -63,6 +66,13 @@ int pv_packed_strips(const pv_batch_views_desc& d, bool frames, const RsItemLaun
 int pv_packed_tiles(const pv_batch_views_desc& d, bool frames, const RsTileLaunch& g, size_t lds, pv_stream_t stream);
 int pv_packed_regions(const pv_batch_views_desc& d, bool frames, const RsItemLaunch& g, size_t lds, const pv_view_region* regions,
                       pv_stream_t stream);
+
+// The kernels of YUV 4:2:2 / 4:4:4 launches (pv_yuv4.hip: src_layout PV_SRC_YUV422, PV_SRC_YUV444), each on a launch its entry
+// point has validated and sized, as the packed ones above.
+int pv_yuv4_strips(const pv_batch_views_desc& d, bool frames, const RsItemLaunch& g, size_t lds, pv_stream_t stream);
+int pv_yuv4_tiles(const pv_batch_views_desc& d, bool frames, const RsTileLaunch& g, size_t lds, pv_stream_t stream);
+int pv_yuv4_regions(const pv_batch_views_desc& d, bool frames, const RsItemLaunch& g, size_t lds, const pv_view_region* regions,
+                    pv_stream_t stream);
 
 namespace {
 
@@ -223,7 +233,8 @@ __device__ __forceinline__ float yuv_blend(float ly0, float ly1, float lx0, floa
 //      rows are at most 2R, as in upscaling, that contiguous run of rows once), columns [i0x(first), i1x(last)] -- is
 //      copied to LDS in the SOURCE dtype with aligned 16-byte global loads, a batch of four per thread, and 16-byte LDS
 //      writes.  YUV stages the luma span and the chroma span behind it: chroma rows (y >> 1) of the same rows, columns
-//      [xs0 >> 1, xs1 >> 1]; in the contiguous case every chroma row once, so half as many as luma rows.  A row of a span
+//      [xs0 >> 1, xs1 >> 1]; in the contiguous case every chroma row once, so half as many as luma rows (4:2:0; the shifts are
+//      the layout's -- RsSub -- and full-height chroma stages as many chroma rows as luma rows, at most 2R).  A row of a span
 //      may start at any byte address (Ws = 340 gives 4-byte-aligned rows, an odd Ws, a pitched surface, an odd base or the
 //      +1 of the second interleaved sample none at all): the loads fetch the aligned 16-byte granules that cover the span,
 //      and the LDS image of each row keeps the span's offset inside its first granule (`addr & 15`), so unaligned rows cost
@@ -484,7 +495,25 @@ __device__ __forceinline__ void rs_strip_rgb(unsigned char* lds, int R, int pitc
   }
 }
 
-// A YUV 4:2:0 source: the planes of the selected frame.
+// The chroma subsampling of a YUV launch: the chroma sample of luma pixel (y, x) is (y >> csy, x >> csx).  The YUV bodies take
+// it behind a last template parameter whose default, RsSub420, is the constant pair (1, 1) and leaves every 4:2:0 kernel with
+// the instructions it had.  RsSub is the pair as a by-value kernel argument (PV_SRC_YUV422: (0, 1), PV_SRC_YUV444: (0, 0);
+// include/pv_mi355x.h, "YUV 4:2:2 and 4:4:4") -- uniform over the launch and held in scalar registers, so one kernel of
+// pv_yuv4.hip serves both layouts, as RsPackedArg serves every channel order.
+// (Static constants, not functions: `y >> sub.csy` is then the literal `y >> 1` from the front end on, and the 4:2:0 kernels
+// come out instruction for instruction as they were; behind a constexpr member function they did not -- profiles/r27.)
+struct RsSub420 { static constexpr int csy = 1, csx = 1; };
+struct RsSub { int32_t csy, csx; };
+// The shifts of a YUV src_layout; false: not a YUV layout.
+inline bool rs_yuv_sub(int src_layout, RsSub* c = nullptr) {
+  const bool yuv = src_layout == PV_SRC_YUV420 || src_layout == PV_SRC_YUV422 || src_layout == PV_SRC_YUV444;
+  if (yuv && c) *c = RsSub{src_layout == PV_SRC_YUV420 ? 1 : 0, src_layout == PV_SRC_YUV444 ? 0 : 1};
+  return yuv;
+}
+// The layouts whose kernels are in pv_yuv4.hip.
+inline bool rs_yuv4(int src_layout) { return src_layout == PV_SRC_YUV422 || src_layout == PV_SRC_YUV444; }
+
+// A YUV source: the planes of the selected frame.
 struct RsYuvSrc {
   uintptr_t src;
   long frame_off;           // bytes from `src` to the selected frame, its index clamped before the product
@@ -510,10 +539,11 @@ __host__ __device__ __forceinline__ void rs_chroma_planes(bool inter, int64_t u_
 // kin).  Spans, source addresses and LDS offsets count SB = sizeof(SMP) bytes per luma column and CSTEP * SB per chroma
 // column; pitches and plane offsets are bytes in either case.  Two-byte samples need even source addresses (checked on the
 // host: rs_check_yuv16_even), which makes every 16-bit LDS read naturally aligned.  MAP: the tap map (RsTapNone: none).
-template <int CSTEP, int FORM, typename D, typename SMP = unsigned char, typename MAP = RsTapNone>
+// SUB: the chroma subsampling (RsSub420, or RsSub for the 4:2:2 / 4:4:4 kernels of pv_yuv4.hip; deduced from the last argument).
+template <int CSTEP, int FORM, typename D, typename SMP = unsigned char, typename MAP = RsTapNone, typename SUB = RsSub420>
 __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitch_y, int pitch_c, int c_base, const RsYuvSrc& s,
                                              const RsDst& d, const float* yuv2rgb, int zi, int t, bool check_span,
-                                             const MAP& map = MAP()) {
+                                             const MAP& map = MAP(), const SUB& sub = SUB()) {
   constexpr int G = RsGroup<FORM, D>::G;
   constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
   constexpr int SB = (int)sizeof(SMP);             // bytes from one luma column to the next
@@ -530,10 +560,10 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
   rs_coord(s.sy, s.yoff + row0 + nrows - 1, s.Hs, unused, ylast, lunused);
   const bool dense = ylast - ybase + 1 <= 2 * R;   // the strip's source rows fit the 2R slots as one contiguous run
   const int nslots = dense ? ylast - ybase + 1 : 2 * nrows;
-  const int cxs0 = xs0 >> 1, cybase = ybase >> 1;
-  const int ncslots = dense ? (ylast >> 1) - cybase + 1 : 2 * nrows;   // dense: <= R + 1 <= 2R
+  const int cxs0 = xs0 >> sub.csx, cybase = ybase >> sub.csy;
+  const int ncslots = dense ? (ylast >> sub.csy) - cybase + 1 : 2 * nrows;   // dense: <= R + 1 (4:2:0), <= 2R (full-height chroma)
   const int span_y = (xs1 - xs0 + 1) * SB;
-  const int span_c = ((xs1 >> 1) - cxs0 + 1) * CB;
+  const int span_c = ((xs1 >> sub.csx) - cxs0 + 1) * CB;
   if (check_span && (span_y + 15 > pitch_y || span_c + 15 > pitch_c)) return;
 
   const uintptr_t frame = s.src + s.frame_off;
@@ -564,7 +594,7 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
           int i0, i1;
           rs_coord(s.sy, s.yoff + row0 + (slot >> 1), s.Hs, i0, i1, lunused);
           y = (slot & 1) ? i1 : i0;
-          cy = y >> 1;
+          cy = y >> sub.csy;
         }
         const uintptr_t a = luma ? y_addr(y) : c_addr(cy, pl);
         if (ch * 16 < (int)(a & 15) + (luma ? span_y : span_c)) {
@@ -598,13 +628,13 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
     rs_coord(s.sy, s.yoff + y, s.Hs, i0y, i1y, ly1);
     const float ly0 = 1.f - ly1;
     const int s0 = dense ? i0y - ybase : 2 * r, s1 = dense ? i1y - ybase : 2 * r + 1;
-    const int cs0 = dense ? (i0y >> 1) - cybase : 2 * r, cs1 = dense ? (i1y >> 1) - cybase : 2 * r + 1;
+    const int cs0 = dense ? (i0y >> sub.csy) - cybase : 2 * r, cs1 = dense ? (i1y >> sub.csy) - cybase : 2 * r + 1;
     // LDS byte offset of column xs0 (luma) / cxs0 (U, V) in the two source rows
     const int yo0 = s0 * pitch_y + (int)(y_addr(i0y) & 15), yo1 = s1 * pitch_y + (int)(y_addr(i1y) & 15);
-    const int uo0 = c_base + cs0 * CP * pitch_c + (int)(c_addr(i0y >> 1, 0) & 15) + s.u_byte;
-    const int uo1 = c_base + cs1 * CP * pitch_c + (int)(c_addr(i1y >> 1, 0) & 15) + s.u_byte;
-    const int vo0 = c_base + (cs0 * CP + CP - 1) * pitch_c + (int)(c_addr(i0y >> 1, CP - 1) & 15) + s.v_byte;
-    const int vo1 = c_base + (cs1 * CP + CP - 1) * pitch_c + (int)(c_addr(i1y >> 1, CP - 1) & 15) + s.v_byte;
+    const int uo0 = c_base + cs0 * CP * pitch_c + (int)(c_addr(i0y >> sub.csy, 0) & 15) + s.u_byte;
+    const int uo1 = c_base + cs1 * CP * pitch_c + (int)(c_addr(i1y >> sub.csy, 0) & 15) + s.u_byte;
+    const int vo0 = c_base + (cs0 * CP + CP - 1) * pitch_c + (int)(c_addr(i0y >> sub.csy, CP - 1) & 15) + s.v_byte;
+    const int vo1 = c_base + (cs1 * CP + CP - 1) * pitch_c + (int)(c_addr(i1y >> sub.csy, CP - 1) & 15) + s.v_byte;
     float out[4][G];
 #pragma unroll
     for (int j = 0; j < G; ++j) {
@@ -614,7 +644,7 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
       rs_coord(s.sx, s.xoff + x, s.Ws, i0x, i1x, lx1);
       const float lx0 = 1.f - lx1;
       const int o0 = (i0x - xs0) * SB, o1 = (i1x - xs0) * SB;
-      const int c0 = ((i0x >> 1) - cxs0) * CB, c1 = ((i1x >> 1) - cxs0) * CB;
+      const int c0 = ((i0x >> sub.csx) - cxs0) * CB, c1 = ((i1x >> sub.csx) - cxs0) * CB;
       f32x2 p0[3], p1[3];                          // {row i0y, row i1y} of column i0x / i1x, per channel
       yuv_tap2<SMP, MAP>(m, lds, yo0 + o0, uo0 + c0, vo0 + c0, yo1 + o0, uo1 + c0, vo1 + c0, p0, map);
       yuv_tap2<SMP, MAP>(m, lds, yo0 + o1, uo0 + c1, vo0 + c1, yo1 + o1, uo1 + c1, vo1 + c1, p1, map);
@@ -805,10 +835,10 @@ __device__ __forceinline__ void rs_tile_rgb(unsigned char* lds, const RsTileLaun
   }
 }
 
-// CSTEP / FORM / D / SMP / MAP: as rs_strip_yuv.
-template <int CSTEP, int FORM, typename D, typename SMP, typename MAP = RsTapNone>
+// CSTEP / FORM / D / SMP / MAP / SUB: as rs_strip_yuv.  The shifts apply to STORED rows and columns.
+template <int CSTEP, int FORM, typename D, typename SMP, typename MAP = RsTapNone, typename SUB = RsSub420>
 __device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaunch& g, const RsYuvSrc& s, int orient, const RsDst& d,
-                                            const float* yuv2rgb, int zi, int t, const MAP& map = MAP()) {
+                                            const float* yuv2rgb, int zi, int t, const MAP& map = MAP(), const SUB& sub = SUB()) {
   constexpr int G = RsGroup<FORM, D>::G;
   constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
   constexpr int SB = (int)sizeof(SMP);             // bytes from one luma column to the next
@@ -826,10 +856,10 @@ __device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaun
   rs_tile_range(s.sy, s.yoff + row0, nrows, Hd, dy0, dy1);
   rs_tile_range(s.sx, s.xoff + col0, ncols, Wd, dx0, dx1);
   rs_tile_rect(o, dy0, dy1, dx0, dx1, s.Hs, s.Ws, sr0, sr1, sc0, sc1);
-  const int cr0 = sr0 >> 1, cc0 = sc0 >> 1;
-  const int nslots = sr1 - sr0 + 1, ncslots = (sr1 >> 1) - cr0 + 1;
+  const int cr0 = sr0 >> sub.csy, cc0 = sc0 >> sub.csx;
+  const int nslots = sr1 - sr0 + 1, ncslots = (sr1 >> sub.csy) - cr0 + 1;
   const int span_y = (sc1 - sc0 + 1) * SB;
-  const int span_c = ((sc1 >> 1) - cc0 + 1) * CB;
+  const int span_c = ((sc1 >> sub.csx) - cc0 + 1) * CB;
   if (nslots > g.rows || ncslots > g.rows_c || span_y + 15 > pitch_y || span_c + 15 > pitch_c) return;
 
   const uintptr_t frame = s.src + s.frame_off;
@@ -884,7 +914,11 @@ __device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaun
   auto tap = [&](int iy, int ix, int& oy, int& ou, int& ov) {
     const int r = rs_clampi(o.r0 + o.ry * iy + o.rx * ix, sr0, sr1), c = rs_clampi(o.c0 + o.cy * iy + o.cx * ix, sc0, sc1);
     oy = (r - sr0) * pitch_y + (int)((ya32 + (unsigned)r * yp32) & 15u) + (c - sc0) * SB;
-    const int cr = r >> 1, co = ((c >> 1) - cc0) * CB, crow = c_base + (cr - cr0) * CP * pitch_c;
+    // (RsSub420 is named by its type here: the lambda then does not capture `sub`, which changed the 4:2:0 tile kernels)
+    int cr, cq;                                    // the chroma row and column of the stored pixel
+    if constexpr (std::is_empty<SUB>::value) cr = r >> SUB::csy, cq = c >> SUB::csx;
+    else cr = r >> sub.csy, cq = c >> sub.csx;
+    const int co = (cq - cc0) * CB, crow = c_base + (cr - cr0) * CP * pitch_c;
     ou = crow + (int)((ua32 + (unsigned)cr * cp32) & 15u) + s.u_byte + co;
     ov = crow + (CP - 1) * pitch_c + (int)((va32 + (unsigned)cr * cp32) & 15u) + s.v_byte + co;
   };
@@ -1030,14 +1064,15 @@ __device__ __forceinline__ RsRgbWin rg_item_rgb(const RgItem& item) {
 // ---- the launch arithmetic shared by the entry points ---------------------------------------------------------------
 // Folds the widest source column span of a record's views into `span`, and the chroma span behind it into `span_c`, both in
 // columns: times the bytes of a column (rs_yuv_pitches for YUV) they size the staged rows.
-inline void rs_widest_span(float sx, const int32_t* x_off, int n_views, int Wo, int Ws, int& span, int& span_c) {
+// csx: the chroma column shift of the launch (rs_yuv_sub; ignored by the RGB / planar forms, which do not read span_c).
+inline void rs_widest_span(float sx, const int32_t* x_off, int n_views, int Wo, int Ws, int& span, int& span_c, int csx = 1) {
   for (int v = 0; v < n_views; ++v) {
     int a, b, u;
     float l;
     rs_coord(sx, x_off[v], Ws, a, u, l);
     rs_coord(sx, x_off[v] + Wo - 1, Ws, u, b, l);
     span = b - a + 1 > span ? b - a + 1 : span;
-    const int c = (b >> 1) - (a >> 1) + 1;
+    const int c = (b >> csx) - (a >> csx) + 1;
     span_c = c > span_c ? c : span_c;
   }
 }
@@ -1075,7 +1110,7 @@ inline bool rs_interleaved(int src_layout) { return src_layout == PV_SRC_NTHWC |
 // behind the luma one.  Returns the bytes, not yet narrowed to 32 bits.
 template <typename Launch> inline long rs_tile_layout(const pv_batch_views_desc& d, const int (&n)[4], Launch& g) {
   g.rows = n[0], g.rows_c = n[2];
-  if (d.src_layout == PV_SRC_YUV420) {
+  if (rs_yuv_sub(d.src_layout)) {
     rs_yuv_pitches(n[1], n[3], d.c_step, d.src_dtype == PV_U16 ? 2 : 1, g.pitch, g.pitch_c);
     g.c_base = g.rows * g.pitch;
     return (long)g.c_base + (long)g.rows_c * (d.c_step == 2 ? 1 : 2) * g.pitch_c;
@@ -1167,18 +1202,19 @@ inline bool plane_inside(int64_t off, int64_t rows, int64_t pitch, int64_t cols,
   return off >= 0 && off + (rows - 1) * pitch + (cols - 1) * step + (sb - 1) < frame_stride;
 }
 
-// The planes of one YUV 4:2:0 frame of Hs x Ws (both positive) of sb-byte samples: even sizes, the chroma form (c_step counts
-// samples), pitches that hold a row, and luma and chroma planes inside [0, frame_stride).  Pitches, offsets and the frame
-// stride are bytes.
+// The planes of one YUV frame of Hs x Ws (both positive) of sb-byte samples: a size the subsampling halves is even (4:2:0: both;
+// 4:2:2: Ws; 4:4:4: neither), the chroma form (c_step counts samples), pitches that hold a row, and luma and chroma planes --
+// Hs >> csy rows of Ws >> csx samples -- inside [0, frame_stride).  Pitches, offsets and the frame stride are bytes.
 inline int rs_check_yuv_planes(int Hs, int Ws, int c_step, int y_pitch, int c_pitch, int64_t frame_stride, int64_t u_offset,
-                               int64_t v_offset, int sb = 1) {
-  if ((Hs | Ws) & 1) return PV_ERR_INVALID;
+                               int64_t v_offset, int sb = 1, RsSub c = RsSub{1, 1}) {
+  if (((c.csy ? Hs : 0) | (c.csx ? Ws : 0)) & 1) return PV_ERR_INVALID;
   if (c_step != 1 && c_step != 2) return PV_ERR_INVALID;
-  if (y_pitch < (int64_t)Ws * sb || c_pitch < (int64_t)(Ws / 2) * c_step * sb || frame_stride <= 0) return PV_ERR_INVALID;
+  const int Hc = Hs >> c.csy, Wc = Ws >> c.csx;
+  if (y_pitch < (int64_t)Ws * sb || c_pitch < (int64_t)Wc * c_step * sb || frame_stride <= 0) return PV_ERR_INVALID;
   if (c_step == 2 && v_offset - u_offset != sb && u_offset - v_offset != sb) return PV_ERR_INVALID;
   if (!plane_inside(0, Hs, y_pitch, Ws, sb, frame_stride, sb) ||
-      !plane_inside(u_offset, Hs / 2, c_pitch, Ws / 2, (int64_t)c_step * sb, frame_stride, sb) ||
-      !plane_inside(v_offset, Hs / 2, c_pitch, Ws / 2, (int64_t)c_step * sb, frame_stride, sb))
+      !plane_inside(u_offset, Hc, c_pitch, Wc, (int64_t)c_step * sb, frame_stride, sb) ||
+      !plane_inside(v_offset, Hc, c_pitch, Wc, (int64_t)c_step * sb, frame_stride, sb))
     return PV_ERR_INVALID;
   return PV_OK;
 }
@@ -1210,7 +1246,9 @@ inline int rs_check_record_frames(const pv_batch_views_desc& d, const pv_view_so
   if (v.orient < 0 || v.orient > 7) return PV_ERR_INVALID;
   if (yuv) {
     const int sb = d.src_dtype == PV_U16 ? 2 : 1;
-    if (int e = rs_check_yuv_planes(v.Hs, v.Ws, d.c_step, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset, sb)) return e;
+    RsSub c = {1, 1};
+    rs_yuv_sub(d.src_layout, &c);
+    if (int e = rs_check_yuv_planes(v.Hs, v.Ws, d.c_step, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset, sb, c)) return e;
     if (sb == 2 && rs_check_yuv16_even(0, v.y_pitch, v.c_pitch, v.frame_stride, v.u_offset, v.v_offset)) return PV_ERR_INVALID;
   }
   if (const int pb = rs_packed_px(d.src_layout)) {   // packed pixels: a pitch that holds a row, a stride that holds a frame, dwords aligned
@@ -1236,12 +1274,14 @@ inline int rs_check_record(const pv_batch_views_desc& d, const pv_view_source& v
 // The widest stored footprint of a TR x TC tile of oriented record v over its views: stored rows x columns, and the chroma
 // rows x columns behind them.  The map takes displayed rows to one stored axis and displayed columns to the other, so the
 // bands of tile rows and of tile columns are walked separately, with the very calls the kernel makes.
-inline void rs_tile_footprint(const pv_view_source& v, int n_views, int Ho, int Wo, int TR, int TC, int (&n)[4]) {
+inline void rs_tile_footprint(const pv_view_source& v, int n_views, int Ho, int Wo, int TR, int TC, int (&n)[4],
+                              RsSub sub = RsSub{1, 1}) {
   const bool turned = v.orient & 1;
   const int Hd = turned ? v.Ws : v.Hs, Wd = turned ? v.Hs : v.Ws;
   const RsOrient o = rs_orient_map(v.orient, v.Hs, v.Ws);
   auto fold = [&](int lo, int hi, bool rows) {     // a stored interval of rows / of columns
-    const int a = hi - lo + 1, c = (hi >> 1) - (lo >> 1) + 1;
+    const int cs = rows ? sub.csy : sub.csx;
+    const int a = hi - lo + 1, c = (hi >> cs) - (lo >> cs) + 1;
     int& na = n[rows ? 0 : 1];
     int& nc = n[rows ? 2 : 3];
     na = a > na ? a : na, nc = c > nc ? c : nc;
@@ -1270,7 +1310,9 @@ inline int rs_tile_size(const pv_batch_views_desc& d, const pv_view_source* cons
   for (size_t k = 0; k < sizeof(tiles) / sizeof(tiles[0]); ++k) {
     const int TR = tiles[k][0], TC = tiles[k][1];
     int n[4] = {0, 0, 0, 0};
-    for (size_t i = 0; i < n_records; ++i) rs_tile_footprint(*records[i], d.n_views, d.Ho, d.Wo, TR, TC, n);
+    RsSub sub = {1, 1};
+    rs_yuv_sub(d.src_layout, &sub);
+    for (size_t i = 0; i < n_records; ++i) rs_tile_footprint(*records[i], d.n_views, d.Ho, d.Wo, TR, TC, n, sub);
     g = {};
     g.TR = TR, g.TC = TC, g.tiles_x = (int32_t)pv_ceil_div(d.Wo, TC);
     const long bytes = rs_tile_layout(d, n, g);
@@ -1287,9 +1329,9 @@ inline int rs_check_item_desc(const pv_batch_views_desc& d) {
   if (d.n_sources <= 0 || d.n_items <= 0 || d.n_rows <= 0 || d.T <= 0 || d.C <= 0 || d.Ho <= 0 || d.Wo <= 0) return PV_ERR_INVALID;
   if (d.t_stride < d.T || d.n_items > 65535 || d.T > 65535) return PV_ERR_INVALID;   // grid.y / grid.z
   if (d.C > 4 || d.n_views < 1 || d.n_views > 3) return PV_ERR_INVALID;
-  const bool yuv = d.src_layout == PV_SRC_YUV420, inter = rs_interleaved(d.src_layout);   // [.., 3] or packed pixels
+  const bool yuv = rs_yuv_sub(d.src_layout), inter = rs_interleaved(d.src_layout);   // [.., 3] or packed pixels
   if (!yuv && !inter && d.src_layout != PV_SRC_NCTHW) return PV_ERR_INVALID;
-  if (!yuv && d.src_dtype == PV_U16) return PV_ERR_UNSUPPORTED;   // 16-bit samples are a YUV 4:2:0 source only
+  if (!yuv && d.src_dtype == PV_U16) return PV_ERR_UNSUPPORTED;   // 16-bit samples are a YUV source only
   if (inter && (d.src_dtype != PV_U8 || d.C != 3)) return PV_ERR_INVALID;
   if (yuv && (!d.yuv2rgb || d.C != 3 || (d.c_step != 1 && d.c_step != 2))) return PV_ERR_INVALID;
   // the dtype / layout matrix
@@ -1300,7 +1342,7 @@ inline int rs_check_item_desc(const pv_batch_views_desc& d) {
 // R, the LDS pitch(es) and the LDS bytes of a strip launch whose widest column span is `span` (chroma: `span_c`).
 inline int rs_strip_size(const pv_batch_views_desc& d, int span, int span_c, RsItemLaunch& g, size_t& lds) {
   long per_row;                                    // LDS bytes of the two source rows of one output row
-  if (d.src_layout == PV_SRC_YUV420) {
+  if (rs_yuv_sub(d.src_layout)) {
     per_row = rs_yuv_pitches(span, span_c, d.c_step, d.src_dtype == PV_U16 ? 2 : 1, g.pitch, g.pitch_c);
   } else {
     g.pitch = rs_rgb_pitch(span, d.src_layout, d.src_dtype);
@@ -1341,7 +1383,8 @@ template <typename CheckSrc>
 inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_src, RsItemLaunch& g, size_t& lds, RsTileLaunch& tg,
                           size_t& lds_t) {
   if (int e = rs_check_item_desc(d)) return e;
-  const bool yuv = d.src_layout == PV_SRC_YUV420;
+  RsSub sub = {1, 1};
+  const bool yuv = rs_yuv_sub(d.src_layout, &sub);
   int span = 0, span_c = 0, n_upright = 0;
   std::vector<const pv_view_source*> oriented;     // the oriented records the items name, a video-major run once
   const auto check = [&](const pv_view_source& v) { return rs_check_record(d, v, yuv, check_src); };
@@ -1350,7 +1393,7 @@ inline int rs_item_launch(const pv_batch_views_desc& d, const CheckSrc& check_sr
       if (!again) oriented.push_back(&v);
     } else {
       ++n_upright;
-      rs_widest_span(v.sx, v.x_off, d.n_views, d.Wo, v.Ws, span, span_c);
+      rs_widest_span(v.sx, v.x_off, d.n_views, d.Wo, v.Ws, span, span_c, sub.csx);
     }
     return PV_OK;
   };

@@ -86,7 +86,7 @@ class VideoPredictor:
         p = self.packer
         device = p.sess.device
         # HDR taps, the box filter and packed pixels: pv_hdr_views / pv_area_views / pv_batch_views, item-sourced launches
-        if isinstance(video, FrameList) or orientation or p.hdr is not None or p.area or p.is_packed:
+        if isinstance(video, FrameList) or orientation or p.hdr is not None or p.area or p.item_only:
             return self._call_frames(video, fps, return_clip_scores, orientation)
         if video.dim() != (3 if p.is_yuv else 4):
             raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(video.shape)))
@@ -431,9 +431,9 @@ class TubePredictor:
                 if tracks is None:
                     if not isinstance(entry, torch.Tensor) or entry.dim() != 2 or entry.shape[1] != 4:
                         raise ValueError("video %d, time stamp %d: boxes are an [r, 4] tensor (x1, y1, x2, y2)" % (j, k))
-                    own = [r.expand(table.shape[1], 4) for r in box_regions(entry, hs, ws, self.context, self.square, even=p.is_yuv)]
+                    own = [r.expand(table.shape[1], 4) for r in box_regions(entry, hs, ws, self.context, self.square, even=p.region_even)]
                 else:
-                    own = [box_regions(track_boxes_at(fn, tb, table[k]), hs, ws, self.context, self.square, even=p.is_yuv)
+                    own = [box_regions(track_boxes_at(fn, tb, table[k]), hs, ws, self.context, self.square, even=p.region_even)
                            for fn, tb in entry]
                 rows.extend([k] * len(own))
                 rects.extend(own)

@@ -274,7 +274,8 @@ def _size_pair(size, what="size"):
 
 def _check_regions(regions, height, width, even=False, what="regions"):
     """`regions` as a host int64 tensor [..., 4] of (top, left, h, w), every rectangle at least 1 x 1 and inside the
-    height x width frame -- and, `even`, of even members (YUV 4:2:0: a chroma sample is never split).  ValueError otherwise."""
+    height x width frame -- and, `even`, of even members (YUV 4:2:0: a chroma sample is never split; `even="width"`, YUV
+    4:2:2: left and w only).  ValueError otherwise."""
     regions = torch.as_tensor(regions)
     if regions.dim() < 1 or regions.shape[-1] != 4 or regions.numel() == 0 or regions.is_floating_point() or regions.dtype == torch.bool:
         raise ValueError("%s are integer (top, left, h, w) rectangles [..., 4]; got %s %s" % (what, regions.dtype, tuple(regions.shape)))
@@ -284,7 +285,10 @@ def _check_regions(regions, height, width, even=False, what="regions"):
         raise ValueError("%s: a rectangle is at least 1 x 1" % what)
     if bool((top < 0).any()) or bool((left < 0).any()) or bool((top + h > height).any()) or bool((left + w > width).any()):
         raise ValueError("%s: a rectangle leaves the %d x %d frame" % (what, height, width))
-    if even and bool((regions % 2 != 0).any()):
+    if even == "width":
+        if bool((regions[..., 1::2] % 2 != 0).any()):
+            raise ValueError("%s: the rectangles of a YUV 4:2:2 source have even left and w (box_regions(..., even='width'))" % what)
+    elif even and bool((regions % 2 != 0).any()):
         raise ValueError("%s: the rectangles of a YUV 4:2:0 source have even top, left, h and w (box_regions(..., even=True))" % what)
     return regions
 
@@ -323,7 +327,8 @@ def box_regions(boxes, height: int, width: int, context: float = 1.0, square: bo
       5. at least one pixel: left <= width - 1, right >= left + 1 (a degenerate box, or one wholly outside the frame, becomes
          the pixel nearest to it); rows likewise;
       6. `even` (YUV 4:2:0 sources; `height` and `width` must be even): left and top go DOWN to even, right and bottom UP to
-         even -- outward, still inside the frame --, so the rectangle is at least 2 x 2.
+         even -- outward, still inside the frame --, so the rectangle is at least 2 x 2.  `even="width"` (YUV 4:2:2 sources;
+         `width` must be even): left and right only.
     Boxes must be finite."""
     b = torch.as_tensor(boxes).detach().to("cpu", torch.float64)
     if b.dim() < 1 or b.shape[-1] != 4:
@@ -333,7 +338,10 @@ def box_regions(boxes, height: int, width: int, context: float = 1.0, square: bo
     height, width = int(height), int(width)
     if height < 1 or width < 1 or not context > 0:
         raise ValueError("height and width are positive ints and context a positive factor")
-    if even and (height % 2 or width % 2):
+    if even == "width":
+        if width % 2:
+            raise ValueError("even='width' is for YUV 4:2:2 frames, whose width is even; got %d x %d" % (height, width))
+    elif even and (height % 2 or width % 2):
         raise ValueError("even=True is for YUV 4:2:0 frames, whose height and width are even; got %d x %d" % (height, width))
     cx, cy = (b[..., 0] + b[..., 2]) / 2, (b[..., 1] + b[..., 3]) / 2
     bw = torch.clamp(b[..., 2] - b[..., 0], min=0.0) * float(context)
@@ -347,8 +355,9 @@ def box_regions(boxes, height: int, width: int, context: float = 1.0, square: bo
     right = torch.maximum(torch.ceil(x2).to(torch.int64), left + 1)
     bottom = torch.maximum(torch.ceil(y2).to(torch.int64), top + 1)
     if even:
-        left, top = left - left % 2, top - top % 2
-        right, bottom = right + right % 2, bottom + bottom % 2
+        left, right = left - left % 2, right + right % 2
+    if even and even != "width":
+        top, bottom = top - top % 2, bottom + bottom % 2
     return torch.stack([top, left, bottom - top, right - left], dim=-1)
 
 
@@ -464,14 +473,39 @@ YUV_LAYOUTS = ("NV12", "NV21", "I420", "YV12")
 # 16-bit little-endian samples.  P0xx: the NV12 arrangement with the value in the HIGH bits (what a hardware decoder writes for
 # 10- / 12- / 16-bit streams); I0xx: the I420 arrangement with the value in the LOW bits (yuv420p10le and friends).
 YUV16_LAYOUTS = ("P010", "P012", "P016", "I010", "I012", "I016")
-_YUV_ANY = YUV_LAYOUTS + YUV16_LAYOUTS
-_YUV_INTERLEAVED = ("NV12", "NV21", "P010", "P012", "P016")
+# YUV 4:2:2 and 4:4:4 (include/pv_mi355x.h, "YUV 4:2:2 and 4:4:4"), read by the item-sourced entry points only.  I422 / YV16:
+# yuv422p / yuvj422p (MJPEG cameras), U (V) first; NV16 / NV61: one interleaved chroma plane, U (V) first; P210 / P212 / P216:
+# NV16's arrangement with 16-bit samples, the value in the HIGH bits; I210 / I212 / I216: yuv422p10le and kin, the value in the
+# LOW bits.  I444 / YV24: yuv444p / yuvj444p; I410 / I412 / I416: yuv444p10le and kin.  (NV24 / NV42 have no string: the C ABI
+# reads them -- PV_SRC_YUV444 with c_step 2.)
+YUV422_LAYOUTS = ("I422", "YV16", "NV16", "NV61", "P210", "P212", "P216", "I210", "I212", "I216")
+YUV444_LAYOUTS = ("I444", "YV24", "I410", "I412", "I416")
+_YUV4_ANY = YUV422_LAYOUTS + YUV444_LAYOUTS
+_YUV_ANY = YUV_LAYOUTS + YUV16_LAYOUTS + _YUV4_ANY
+_YUV_INTERLEAVED = ("NV12", "NV21", "P010", "P012", "P016", "NV16", "NV61", "P210", "P212", "P216")
+_YUV_V_FIRST = ("NV21", "YV12", "YV16", "NV61", "YV24")
 _YUV_PLANE_FIELDS = ("frame_stride", "u_offset", "v_offset", "y_pitch", "c_pitch")   # of `yuv_geometry`, a descriptor, a record
 _SRC_LAYOUTS = ("NCTHW", "NTHWC") + _YUV_ANY + _PACKED_ANY      # every `src_layout` the device ingest takes
 _LAYOUT_ERROR = ("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,)
-                 + " or %s" % (PACKED_LAYOUTS,))
+                 + " or %s" % (YUV422_LAYOUTS,) + " or %s" % (YUV444_LAYOUTS,) + " or %s" % (PACKED_LAYOUTS,))
 _YUV16_DEPTH = {"P010": (10, True), "P012": (12, True), "P016": (16, True), "I010": (10, False), "I012": (12, False),
-                "I016": (16, False)}                       # layout -> (bit depth, MSB-aligned)
+                "I016": (16, False),                       # layout -> (bit depth, MSB-aligned)
+                "P210": (10, True), "P212": (12, True), "P216": (16, True), "I210": (10, False), "I212": (12, False),
+                "I216": (16, False), "I410": (10, False), "I412": (12, False), "I416": (16, False)}
+_YUV_WIDE = tuple(_YUV16_DEPTH)                            # every layout of 16-bit samples (PV_U16)
+
+
+def _yuv_sub(layout):
+    """(csy, csx) of a YUV layout: the chroma sample of luma pixel (y, x) is (y >> csy, x >> csx)."""
+    return (0, 1) if layout in YUV422_LAYOUTS else (0, 0) if layout in YUV444_LAYOUTS else (1, 1)
+
+
+def region_evenness(src_layout):
+    """The `even` of `box_regions` / of the rectangle check for a source layout: True (YUV 4:2:0: all four members even),
+    "width" (YUV 4:2:2: left and w) or False (everything else, YUV 4:4:4 included)."""
+    if src_layout not in _YUV_ANY or src_layout in YUV444_LAYOUTS:
+        return False
+    return "width" if src_layout in YUV422_LAYOUTS else True
 _YUV_KR_KB = {"bt709": (0.2126, 0.0722), "bt601": (0.299, 0.114)}
 _YUV_KR_KB_DEEP = {"bt2020": (0.2627, 0.0593)}             # Rec. 2020 defines 10- and 12-bit quantisation only: no 8-bit form
 
@@ -522,34 +556,48 @@ def _yuv_matrix_of(yuv, layout=None) -> torch.Tensor:
 
 
 def yuv_geometry(frames: torch.Tensor, layout: str, coded_height=None, height=None) -> dict:
-    """Where the samples of YUV 4:2:0 frames are, in bytes, read off the tensor's shape and strides (nothing is copied).
+    """Where the samples of YUV frames are, in bytes, read off the tensor's shape and strides (nothing is copied).
 
-    `frames` is uint8 [N, Hc*3/2, W] (a video) or [B, T', Hc*3/2, W] (clips; then N = B * T' and clip b starts at frame
-    b * T'), Hc being the coded height: Hc luma rows, then the chroma.  `height` is the display height Hs <= Hc (default Hc)
-    and `coded_height`, when given, is checked against the shape.  The only stride requirement is stride(-1) == 1: the
-    row pitch P = stride(-2) may exceed W and the frame stride the frame, so a pitched decoder surface is read in place.
-    NV12 / NV21: chroma row j is tensor row Hc + j, U and V (V and U) interleaved.  I420 / YV12: two planes of Hc/2 rows
-    with pitch P/2 behind the luma, U (V) first -- for P == W exactly the contiguous yuv420p frame.
+    4:2:0 (`YUV_LAYOUTS`, `YUV16_LAYOUTS`): `frames` is uint8 [N, Hc*3/2, W] (a video) or [B, T', Hc*3/2, W] (clips; then
+    N = B * T' and clip b starts at frame b * T'), Hc being the coded height: Hc luma rows, then the chroma.  `height` is the
+    display height Hs <= Hc (default Hc) and `coded_height`, when given, is checked against the shape.  The only stride
+    requirement is stride(-1) == 1: the row pitch P = stride(-2) may exceed W and the frame stride the frame, so a pitched
+    decoder surface is read in place.  NV12 / NV21: chroma row j is tensor row Hc + j, U and V (V and U) interleaved.
+    I420 / YV12: two planes of Hc/2 rows with pitch P/2 behind the luma, U (V) first -- for P == W exactly the contiguous
+    yuv420p frame.
 
-    The layouts of `YUV16_LAYOUTS` hold 16-bit samples: P010 / P012 / P016 are NV12's arrangement, I010 / I012 / I016 are
-    I420's (yuv420p10le).  `frames` is then torch.uint16 or torch.int16 (the same bits; decoder bindings differ) with the
-    same shape and stride rules IN ELEMENTS, and the returned frame_stride, pitches and offsets are BYTES, as the
-    descriptors take them (c_step stays 2 / 1: samples)."""
+    4:2:2 (`YUV422_LAYOUTS`): [N, Hc*2, W] with the same stride rules, W even, any Hc and Hs.  I422 / YV16 and their 16-bit
+    kin: two planes of Hc rows with pitch P/2 behind the luma, U (V) first -- for P == W exactly the contiguous yuv422p frame.
+    NV16 / NV61 / P21x: Hc rows of interleaved U and V (V and U) at pitch P.
+    4:4:4 (`YUV444_LAYOUTS`): [N, Hc*3, W], any W, Hc and Hs: three planes of Hc rows at pitch P, Y, U, V (YV24: Y, V, U).
+    For these two the result also carries the subsampling, csy and csx: the chroma of pixel (y, x) is (y >> csy, x >> csx).
+
+    The layouts of 16-bit samples -- `YUV16_LAYOUTS` (P010 / P012 / P016: NV12's arrangement; I010 / I012 / I016: I420's,
+    yuv420p10le), P210 / I210 / I410 and their 12- and 16-bit kin -- take torch.uint16 or torch.int16 (the same bits; decoder
+    bindings differ) with the same shape and stride rules IN ELEMENTS, and the returned frame_stride, pitches and offsets are
+    BYTES, as the descriptors take them (c_step stays 2 / 1: samples)."""
     if layout not in _YUV_ANY:
-        raise ValueError("a YUV layout is one of %s, got %r" % (YUV_LAYOUTS, layout) + " (16-bit samples: %s)" % (YUV16_LAYOUTS,))
-    wide = layout in YUV16_LAYOUTS
+        raise ValueError("a YUV layout is one of %s, got %r" % (YUV_LAYOUTS, layout) + " (16-bit samples: %s;" % (YUV16_LAYOUTS,)
+                         + " 4:2:2: %s; 4:4:4: %s)" % (YUV422_LAYOUTS, YUV444_LAYOUTS))
+    wide = layout in _YUV_WIDE
+    csy, csx = _yuv_sub(layout)
+    num, den = {(1, 1): (3, 2), (0, 1): (2, 1), (0, 0): (3, 1)}[(csy, csx)]     # tensor rows per coded luma row
+    form = "Hc*3/2" if csy else "Hc*%d" % num
     if frames.dim() not in (3, 4) or (frames.dtype not in (torch.uint16, torch.int16) if wide else frames.dtype != torch.uint8):
-        raise RuntimeError("%s frames are %s [N, Hc*3/2, W] or [B, T, Hc*3/2, W], got %s %s"
-                           % (layout, "uint16 or int16" if wide else "uint8", frames.dtype, tuple(frames.shape)))
+        raise RuntimeError("%s frames are %s [N, %s, W] or [B, T, %s, W], got %s %s"
+                           % (layout, "uint16 or int16" if wide else "uint8", form, form, frames.dtype, tuple(frames.shape)))
     rows, w = frames.shape[-2:]
-    hc = rows * 2 // 3
-    if rows == 0 or hc * 3 != rows * 2 or hc % 2 or w % 2 or w == 0:
-        raise RuntimeError("%d x %d is not Hc*3/2 rows of an even width W with an even coded height Hc" % (rows, w))
+    hc = rows * den // num
+    if csy:
+        if rows == 0 or hc * 3 != rows * 2 or hc % 2 or w % 2 or w == 0:
+            raise RuntimeError("%d x %d is not Hc*3/2 rows of an even width W with an even coded height Hc" % (rows, w))
+    elif rows == 0 or hc * num != rows or w == 0 or (csx and w % 2):
+        raise RuntimeError("%d x %d is not %s rows of %s width W" % (rows, w, form, "an even" if csx else "a"))
     if coded_height is not None and coded_height != hc:
-        raise RuntimeError("coded_height %d, but the frames have %d = %d * 3 / 2 rows" % (coded_height, rows, hc))
+        raise RuntimeError("coded_height %d, but the frames have %d = %d * %d / %d rows" % (coded_height, rows, hc, num, den))
     hs = hc if height is None else int(height)
-    if not 0 < hs <= hc or hs % 2:
-        raise RuntimeError("the display height %d is even and at most the coded height %d" % (hs, hc))
+    if not 0 < hs <= hc or (csy and hs % 2):
+        raise RuntimeError("the display height %d is %sat most the coded height %d" % (hs, "even and " if csy else "", hc))
     pitch = frames.stride(-2)
     if frames.stride(-1) != 1 or pitch < w:
         raise RuntimeError("%s frames have stride(-1) == 1 and a row pitch >= W; got strides %s" % (layout, frames.stride()))
@@ -560,18 +608,58 @@ def yuv_geometry(frames: torch.Tensor, layout: str, coded_height=None, height=No
     if frame_stride < (rows - 1) * pitch + w:
         raise RuntimeError("frames overlap: frame stride %d for %d rows of pitch %d" % (frame_stride, rows, pitch))
     first = hc * pitch
+    swap = layout in _YUV_V_FIRST
     if layout in _YUV_INTERLEAVED:
         c_step, c_pitch = 2, pitch
-        u, v = (first + 1, first) if layout == "NV21" else (first, first + 1)
+        u, v = (first + 1, first) if swap else (first, first + 1)
     else:
-        if pitch % 2:
+        if csx and pitch % 2:
             raise RuntimeError("%s chroma rows have half the luma pitch: the pitch %d must be even" % (layout, pitch))
-        c_step, c_pitch = 1, pitch // 2
-        second = first + (hc // 2) * c_pitch
-        u, v = (second, first) if layout == "YV12" else (first, second)
+        c_step, c_pitch = 1, pitch >> csx
+        second = first + (hc >> csy) * c_pitch
+        u, v = (second, first) if swap else (first, second)
     sb = 2 if wide else 1                                   # elements -> bytes
-    return dict(N=n, Hs=hs, Ws=w, Hc=hc, frame_stride=frame_stride * sb, y_pitch=pitch * sb, c_pitch=c_pitch * sb, c_step=c_step,
-                u_offset=u * sb, v_offset=v * sb)
+    g = dict(N=n, Hs=hs, Ws=w, Hc=hc, frame_stride=frame_stride * sb, y_pitch=pitch * sb, c_pitch=c_pitch * sb, c_step=c_step,
+             u_offset=u * sb, v_offset=v * sb)
+    if layout in _YUV4_ANY:
+        g.update(csy=csy, csx=csx)
+    return g
+
+
+def yuv_to_rgb(frames: torch.Tensor, layout: str, matrix, coded_height=None, height=None) -> torch.Tensor:
+    """The virtual RGB frame the YUV ingest takes its taps from (include/pv_mi355x.h), on the host, for EVERY YUV layout: fp32
+    [..., 3, Hs, Ws] with rgb(y, x) = clamp(M . (Y[y][x], U[y >> csy][x >> csx], V[y >> csy][x >> csx], 1), 0, 255), NOT
+    rounded to an integer -- chroma is replicated over the luma pixels it covers: 2 x 2 for 4:2:0, 1 x 2 for 4:2:2, none
+    for 4:4:4.  `frames`, `layout`, `coded_height` and `height` as in `yuv_geometry`; `matrix` is a 3 x 4 matrix
+    (`yuv_matrix`).  The conversion runs in fp64 and is rounded once to fp32.  16-bit codes are read UNSIGNED, whichever of
+    uint16 / int16 the tensor is."""
+    g = yuv_geometry(frames, layout, coded_height, height)
+    m = torch.as_tensor(matrix, dtype=torch.float64).cpu()
+    if tuple(m.shape) != (3, 4):
+        raise ValueError("matrix is 3 x 4, got %s" % (tuple(m.shape),))
+    frames = frames.cpu() if frames.is_cuda else frames
+    sb = 2 if layout in _YUV_WIDE else 1                    # the geometry is bytes, as_strided counts elements
+    if frames.dtype == torch.uint16:
+        frames = frames.view(torch.int16)                   # the same bits, in the type every CPU operator has
+    lead, lead_strides = tuple(frames.shape[:-2]), tuple(frames.stride()[:-2])
+    off = frames.storage_offset()
+    csy, csx = g.get("csy", 1), g.get("csx", 1)
+
+    def plane(rows, cols, pitch, step, start):
+        p = torch.as_strided(frames, lead + (rows, cols), lead_strides + (pitch // sb, step), off + start // sb).to(torch.float64)
+        return torch.where(p < 0, p + 65536.0, p) if sb == 2 else p
+
+    y = plane(g["Hs"], g["Ws"], g["y_pitch"], 1, 0)
+    hcr, wcr = (g["Hs"] + csy) >> csy, (g["Ws"] + csx) >> csx
+    u = plane(hcr, wcr, g["c_pitch"], g["c_step"], g["u_offset"])
+    v = plane(hcr, wcr, g["c_pitch"], g["c_step"], g["v_offset"])
+    if csy:
+        u, v = [c.repeat_interleave(2, -2) for c in (u, v)]
+    if csx:
+        u, v = [c.repeat_interleave(2, -1) for c in (u, v)]
+    yuv1 = torch.stack([y, u, v, torch.ones_like(y)], dim=-3)                       # [..., 4, Hs, Ws]
+    rgb = torch.einsum("ck,...khw->...chw", m, yuv1)
+    return torch.clamp(rgb, 0.0, 255.0).float()
 
 
 def yuv420_to_rgb(frames: torch.Tensor, layout: str, matrix, coded_height=None, height=None) -> torch.Tensor:
@@ -579,29 +667,11 @@ def yuv420_to_rgb(frames: torch.Tensor, layout: str, matrix, coded_height=None, 
     rgb(y, x) = clamp(M . (Y[y][x], U[y >> 1][x >> 1], V[y >> 1][x >> 1], 1), 0, 255), NOT rounded to an integer.  Chroma is
     replicated over its 2 x 2 luma block.  `frames`, `layout`, `coded_height` and `height` as in `yuv_geometry`; `matrix`
     is a 3 x 4 matrix (`yuv_matrix`).  The conversion runs in fp64 and is rounded once to fp32.  The 16-bit codes of a
-    `YUV16_LAYOUTS` layout are read UNSIGNED, whichever of uint16 / int16 the tensor is (`pv_yuv16_views`)."""
-    g = yuv_geometry(frames, layout, coded_height, height)
-    m = torch.as_tensor(matrix, dtype=torch.float64).cpu()
-    if tuple(m.shape) != (3, 4):
-        raise ValueError("matrix is 3 x 4, got %s" % (tuple(m.shape),))
-    frames = frames.cpu() if frames.is_cuda else frames
-    sb = 2 if layout in YUV16_LAYOUTS else 1                # the geometry is bytes, as_strided counts elements
-    if frames.dtype == torch.uint16:
-        frames = frames.view(torch.int16)                   # the same bits, in the type every CPU operator has
-    lead, lead_strides = tuple(frames.shape[:-2]), tuple(frames.stride()[:-2])
-    off = frames.storage_offset()
-
-    def plane(rows, cols, pitch, step, start):
-        p = torch.as_strided(frames, lead + (rows, cols), lead_strides + (pitch // sb, step), off + start // sb).to(torch.float64)
-        return torch.where(p < 0, p + 65536.0, p) if sb == 2 else p
-
-    y = plane(g["Hs"], g["Ws"], g["y_pitch"], 1, 0)
-    u = plane(g["Hs"] // 2, g["Ws"] // 2, g["c_pitch"], g["c_step"], g["u_offset"])
-    v = plane(g["Hs"] // 2, g["Ws"] // 2, g["c_pitch"], g["c_step"], g["v_offset"])
-    u, v = [c.repeat_interleave(2, -2).repeat_interleave(2, -1) for c in (u, v)]
-    yuv1 = torch.stack([y, u, v, torch.ones_like(y)], dim=-3)                       # [..., 4, Hs, Ws]
-    rgb = torch.einsum("ck,...khw->...chw", m, yuv1)
-    return torch.clamp(rgb, 0.0, 255.0).float()
+    `YUV16_LAYOUTS` layout are read UNSIGNED, whichever of uint16 / int16 the tensor is (`pv_yuv16_views`).  `yuv_to_rgb` with
+    a 4:2:0 layout: the name the 4:2:0 paths have always called."""
+    if layout not in YUV_LAYOUTS + YUV16_LAYOUTS:
+        raise ValueError("a YUV 4:2:0 layout is one of %s, got %r" % (YUV_LAYOUTS, layout) + " (16-bit samples: %s)" % (YUV16_LAYOUTS,))
+    return yuv_to_rgb(frames, layout, matrix, coded_height, height)
 
 
 # --------------------------------------------------------------------------- HDR sources: PQ / HLG taps to BT.709 SDR
@@ -701,8 +771,9 @@ def _hdr_of(hdr, src_layout):
     if tone.numel() != 16:
         raise ValueError("tone holds 16 values (tone_params), got %d" % tone.numel())
     if src_layout not in YUV16_LAYOUTS:
-        raise ValueError("hdr= maps the taps of a 10- to 16-bit YUV 4:2:0 source (src_layout one of %s), not of %r"
-                         % (YUV16_LAYOUTS, src_layout))
+        raise ValueError("hdr= maps the taps of a 10- to 16-bit YUV 4:2:0 source (src_layout one of %s), not of %r%s"
+                         % (YUV16_LAYOUTS, src_layout,
+                            ": pv_hdr_views does not read YUV 4:2:2 / 4:4:4" if src_layout in _YUV4_ANY else ""))
     return code, tone
 
 
@@ -770,7 +841,8 @@ def _src_codes(src_layout, dtype):
     """(src_layout, src_dtype) as the descriptors code them; `dtype` is the tensors' and decides for RGB / planar sources."""
     from . import _lib as L
     if src_layout in _YUV_ANY:
-        return L.SRC_YUV420, L.PV_U16 if src_layout in YUV16_LAYOUTS else L.PV_U8
+        code = L.SRC_YUV422 if src_layout in YUV422_LAYOUTS else L.SRC_YUV444 if src_layout in YUV444_LAYOUTS else L.SRC_YUV420
+        return code, L.PV_U16 if src_layout in _YUV_WIDE else L.PV_U8
     if src_layout in _PACKED_ANY:
         return getattr(L, "SRC_" + _packed_name(src_layout)), L.PV_U8
     return L.SRC_NCTHW if src_layout == "NCTHW" else L.SRC_NTHWC, L.PV_U8 if dtype == torch.uint8 else L.PV_F32
@@ -954,7 +1026,8 @@ class FrameList:
         f = self.frames[0]
         if src_layout in _YUV_ANY:
             if f.dim() != 2:
-                raise RuntimeError("a %s frame is uint8 [Hc*3/2, W], got %s %s" % (src_layout, f.dtype, tuple(f.shape)))
+                raise RuntimeError("a %s frame is 2-d: uint8 [Hc*3/2, W] (4:2:2: [Hc*2, W], 4:4:4: [Hc*3, W]; 16-bit layouts: uint16 "
+                                   "or int16), got %s %s" % (src_layout, f.dtype, tuple(f.shape)))
             geom = yuv_geometry(f[None], src_layout, coded_height, height)
             return 3, geom["Hs"], geom["Ws"], geom
         if src_layout in _PACKED_ANY:
@@ -1148,7 +1221,7 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
         hd, wd = displayed_size(hs, ws, orients[j])               # the views are cut from the displayed frame
         if regions is not None:                                   # the geometry is per frame; the record's own is not read
             hn, wn, offsets = window[0], window[1], [(0, 0)]
-            regions[j] = _check_regions(regions[j], hs, ws, is_yuv, what + ": regions")
+            regions[j] = _check_regions(regions[j], hs, ws, region_evenness(src_layout), what + ": regions")
         else:
             hn, wn, offsets = _view_geometry(hd, wd, short_side, crop_size, views, what + ": ")
         _set_views(rec, hn, wn, offsets)
@@ -1327,6 +1400,11 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
     ValueError names a stride that is not legal, nothing is ever made contiguous); every clip is a source of its own in one
     launch of `pv_batch_views`, and the result is bit for bit that of "NTHWC" on `packed_to_rgb(clip, layout).contiguous()`.
 
+    With a layout of `YUV422_LAYOUTS` ("I422", "NV16", "I210", ...) or `YUV444_LAYOUTS` ("I444", "I410", ...) the clip is YUV
+    4:2:2 [B, T, Hc*2, W] or 4:4:4 [B, T, Hc*3, W], uint8 or -- the 10- to 16-bit layouts -- uint16 / int16, with the strides it
+    has (`yuv_geometry`); every clip is a source of its own in one launch of `pv_batch_views` (the one-source entry points read
+    4:2:0 only), chroma is replicated over the pixels it covers and `yuv_to_rgb` is the host mirror.  `hdr` is a ValueError.
+
     `interpolation="area"` scales with the box filter of `short_side_scale(x, size, "area")` instead of four taps -- what a
     720p or larger source needs: every clip is a source of its own in ONE launch of `pv_area_views`, any source layout, up to
     three views; a ValueError together with a non-zero `orientation` or `hdr`, and for any other string."""
@@ -1338,7 +1416,8 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
         raise ValueError("dtype is torch.bfloat16 or torch.float32")
     views = _views(spatial_idx)
     hdr = _hdr_of(hdr, src_layout)                             # ValueError for an 8-bit or RGB source
-    if area or src_layout in _PACKED_ANY:                      # item-sourced launches: pv_area_views, or pv_batch_views for packed pixels
+    # item-sourced launches: pv_area_views, or pv_batch_views for packed pixels and YUV 4:2:2 / 4:4:4
+    if area or src_layout in _PACKED_ANY or src_layout in _YUV4_ANY:
         return _device_scale_crop_items(clip, short_side, crop_size, views, (mean, std, div255), num_frames, dtype, src_layout,
                                         yuv, coded_height, height, area)
     if src_layout in _YUV_ANY:
@@ -1491,10 +1570,13 @@ class DevicePacker:
             raise ValueError(_LAYOUT_ERROR)
         self.short_side, self.crop_size, self.src_layout = short_side, crop_size, src_layout
         self.is_yuv, self.coded_height, self.height = src_layout in _YUV_ANY, coded_height, height
-        self.is_yuv16 = src_layout in YUV16_LAYOUTS            # 16-bit samples: pv_yuv16_views / PV_U16
+        self.is_yuv16 = src_layout in _YUV_WIDE                # 16-bit samples: pv_yuv16_views / PV_U16
         self.is_packed = src_layout in _PACKED_ANY             # packed pixels: item-sourced launches only
+        self.is_yuv4 = src_layout in _YUV4_ANY                 # YUV 4:2:2 / 4:4:4: item-sourced launches only
+        self.item_only = self.is_packed or self.is_yuv4        # the one-source entry points do not read these
+        self.region_even = region_evenness(src_layout)         # what `box_regions(..., even=)` takes for this layout
         self.in_place = self.is_yuv or self.is_packed          # read with the strides they have: never made contiguous
-        self._packed_video = None
+        self._items_video = None
         self.hdr = _hdr_of(hdr, src_layout)                    # (PV_TRANSFER code, tone table) or None; on the device below
         self._hdr_src = None
         if self.in_place and not self.keyframes and (getattr(deployed, "_pv_load_boxes", None) is not None):
@@ -1598,10 +1680,10 @@ class DevicePacker:
         if self.no_crop:
             raise RuntimeError("the no-crop mode (short_side without crop_size) runs through video_batch / fill_batch / "
                                "fill_boxes; a clip at a time takes short_side and crop_size")
+        if self.item_only:
+            return self._call_items(clip)
         if self.is_yuv:
             return self._call_yuv(clip)
-        if self.is_packed:
-            return self._call_packed(clip)
         if clip.dim() != 5:
             raise RuntimeError("expected a [B,C,T,H,W] clip, got %s" % (tuple(clip.shape),))
         resample = self.short_side is not None
@@ -1653,10 +1735,13 @@ class DevicePacker:
         self.fill_video(clips.to(self.sess.device, non_blocking=True), self._clip_tables[(b, t)], 0, self.batch)
         return self.launch()
 
-    def _call_packed(self, clips):
-        """B materialised clips of packed pixels [B, T', H, W, PB], read with the strides they have: every clip a source of its
-        own, its frames one table row (`video_batch` + `fill_batch`: pv_batch_views), then the forward."""
-        if clips.dim() != 5:
+    def _call_items(self, clips):
+        """B materialised clips of packed pixels [B, T', H, W, PB] -- or of YUV 4:2:2 / 4:4:4 frames [B, T', rows, W] --, read
+        with the strides they have: every clip a source of its own, its frames one table row (`video_batch` + `fill_batch`:
+        pv_batch_views), then the forward."""
+        if self.is_yuv4 and clips.dim() != 4:
+            raise RuntimeError("expected %s clips [B, T, rows, W], got %s" % (self.src_layout, tuple(clips.shape),))
+        if self.is_packed and clips.dim() != 5:
             raise RuntimeError("expected %s clips [B, T, H, W, %d], got %s" % (self.src_layout, _packed_bytes(self.src_layout), tuple(clips.shape),))
         b, t = clips.shape[:2]
         if b * len(self.views) != self.batch:
@@ -1669,17 +1754,17 @@ class DevicePacker:
         self.fill_batch(batch, 0, batch.total)
         return self.launch()
 
-    def _fill_packed_video(self, video, tables, i0, n):
-        """`fill_video` of packed pixels: the one-source entry points do not read them, so the video is a batch of one
-        (pv_batch_views) whose records and items are uploaded once per (video, tables) and whose frame tables are the
-        caller's, already on the device."""
+    def _fill_items_video(self, video, tables, i0, n):
+        """`fill_video` of packed pixels and of YUV 4:2:2 / 4:4:4: the one-source entry points do not read them, so the video
+        is a batch of one (pv_batch_views) whose records and items are uploaded once per (video, tables) and whose frame
+        tables are the caller's, already on the device."""
         key = (video.data_ptr(), tuple(video.shape), video.stride(), tuple(t.data_ptr() for t in tables))
-        if self._packed_video is None or self._packed_video[0] != key:
+        if self._items_video is None or self._items_video[0] != key:
             rows = torch.zeros((tables[0].shape[0], self.clip_frames), dtype=torch.int32)   # frame 0: the tables are the caller's
             batch = self.video_batch([video], [rows])
             batch.tables = list(tables)
-            self._packed_video = (key, batch)
-        self.fill_batch(self._packed_video[1], i0, n)
+            self._items_video = (key, batch)
+        self.fill_batch(self._items_video[1], i0, n)
 
     def _fill(self, clip):
         t_src = clip.shape[2]
@@ -1765,8 +1850,8 @@ class DevicePacker:
         if not (0 <= i0 and 0 < n <= self.batch and i0 + n <= total):
             raise RuntimeError("items [%d, %d) are not a chunk of at most %d of the video's %d clips x views"
                                % (i0, i0 + n, self.batch, total))
-        if self.is_packed:
-            return self._fill_packed_video(video, tables, i0, n)
+        if self.item_only:
+            return self._fill_items_video(video, tables, i0, n)
         if self.subs is None:
             return self._fill_video(video, source, tables, i0, n)
         lo = 0
