@@ -969,7 +969,7 @@ typedef struct pv_attention_desc {
   int64_t q_bs, k_bs, v_bs, o_bs;
   int32_t ldq, ldk, ldv, ldo;
   int32_t B, heads, head_dim, Nq, Nk;
-  float scale;
+  float scale;          /* finite and > 0, else PV_ERR_INVALID (row maxima are taken before scaling) */
   int32_t residual_q;   /* 1: o += q (residual_pool, layers/attention.py:536-537) */
   int32_t dtype;
 } pv_attention_desc;

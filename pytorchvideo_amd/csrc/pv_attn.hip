@@ -25,16 +25,12 @@
 // fp32 (parity mode) uses v_mfma_f32_32x32x2_f32 with the same lane-private structure.
 #include <math.h>
 #include <type_traits>
-#include "pv_common.h"
-
-int pv_attn_w64_try(const pv_attention_desc& d, hipStream_t s);   // pv_attn64.hip; PV_ERR_UNSUPPORTED = not its case
+#include "pv_attn.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kQB = 128;  // query rows per workgroup
-
-__device__ __forceinline__ int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 template <typename T, int D> struct AttnCfg;
 template <int D> struct AttnCfg<bf16_t, D> {
@@ -54,6 +50,16 @@ template <int D> struct AttnCfg<float, D> {
   static constexpr int V_ELEMS = KT * VLD;
 };
 
+// V^T fragment i = sk * NDB + db (A operand of O^T): channel db * 32 + l31, keys {4hi.., 8 + 4hi..} of 16-key slot sk
+template <int D> __device__ __forceinline__ bf16x8 read_vt_frag(const bf16_t* vs_, int i, int l31, int hi) {
+  constexpr int NDB = D / 32;
+  const int sk = i / NDB, db = i - sk * NDB;
+  const bf16_t* vp = vs_ + (db * 32 + l31) * AttnCfg<bf16_t, D>::VLD + sk * 16 + hi * 4;
+  const bf16x4 lo = *reinterpret_cast<const bf16x4*>(vp);
+  const bf16x4 up = *reinterpret_cast<const bf16x4*>(vp + 8);
+  return bf16x8{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
+}
+
 template <typename T, int D>
 __global__ __launch_bounds__(kThreads, 2) void attn_kernel(const pv_attention_desc d, int nqb, int total) {
   using Cfg = AttnCfg<T, D>;
@@ -63,31 +69,19 @@ __global__ __launch_bounds__(kThreads, 2) void attn_kernel(const pv_attention_de
   constexpr int NDB = D / 32;     // 32-channel output blocks
   __shared__ __attribute__((aligned(16))) T smem[NBUF * (Cfg::K_ELEMS + Cfg::V_ELEMS)];
 
-  // XCD-aware order: consecutive work items (same batch/head -> same K/V) share an XCD's L2
-  int w;
-  {
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int qn = total >> 3, rn = total & 7;
-    w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
-  }
-  const int bh = w / nqb;
-  const int qb = w - bh * nqb;
-  const int b = bh / d.heads;
-  const int h = bh - b * d.heads;
-
+  const AttnItem<T, D> it = attn_item<T, D>(d, nqb, total);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int l31 = lane & 31;
   const int hi = lane >> 5;
 
-  const T* __restrict__ Q = static_cast<const T*>(d.q) + (long)b * d.q_bs + h * D;
-  const T* __restrict__ K = static_cast<const T*>(d.k) + (long)b * d.k_bs + h * D;
-  const T* __restrict__ V = static_cast<const T*>(d.v) + (long)b * d.v_bs + h * D;
-  T* __restrict__ O = static_cast<T*>(d.o) + (long)b * d.o_bs + h * D;
+  const T* __restrict__ Q = it.q(d);
+  const T* __restrict__ K = it.k(d);
+  const T* __restrict__ V = it.v(d);
+  T* __restrict__ O = it.o(d);
 
-  const int q_row = qb * kQB + wave * 32 + l31;
+  const int q_row = it.qblk * kQB + wave * 32 + l31;
   const bool q_ok = q_row < d.Nq;
   const int ntiles = (d.Nk + KT - 1) / KT;
   const float sc = d.scale * 1.44269504088896340736f;  // softmax in the exp2 domain
@@ -254,7 +248,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_kernel(const pv_attention_de
     for (int sub = 0; sub < NSUB; ++sub)
 #pragma unroll
       for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[sub][r]);
-    mx *= sc;   // sc > 0: max commutes with the scaling
+    mx *= sc;   // sc > 0 (pv_attention checks): max commutes with the scaling
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     if (__any(mx > m_run + kDefer)) {
       const float m_new = fmaxf(m_run, mx);
@@ -288,13 +282,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_kernel(const pv_attention_de
         for (int j = 0; j < 8; ++j) pb[i][j] = (bf16_t)s[i >> 1][(i & 1) * 8 + j];
       constexpr int NF = NSUB * 2 * NDB;   // fragment sequence: i = (sub*2 + k2) * NDB + db
       bf16x8 vf[3];
-      auto read_v = [&](int slot, int i) {
-        const int sk = i / NDB, db = i - sk * NDB;
-        const T* vp = vs_ + (db * 32 + l31) * VLD + sk * 16 + hi * 4;
-        const bf16x4 lo = *reinterpret_cast<const bf16x4*>(vp);
-        const bf16x4 up = *reinterpret_cast<const bf16x4*>(vp + 8);
-        vf[slot] = bf16x8{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
-      };
+      auto read_v = [&](int slot, int i) { vf[slot] = read_vt_frag<D>(vs_, i, l31, hi); };
       read_v(0, 0);
       read_v(1, 1);
 #pragma unroll
@@ -366,29 +354,19 @@ __global__ __launch_bounds__(kThreads, 2) void attn_pipe_kernel(const pv_attenti
   T* const vb0 = smem + 2 * Cfg::K_ELEMS;
   T* const vb1 = vb0 + Cfg::V_ELEMS;
 
-  int w;
-  {
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int qn = total >> 3, rn = total & 7;
-    w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
-  }
-  const int bh = w / nqb;
-  const int qb = w - bh * nqb;
-  const int b = bh / d.heads;
-  const int h = bh - b * d.heads;
+  const AttnItem<T, D> it = attn_item<T, D>(d, nqb, total);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int l31 = lane & 31;
   const int hi = lane >> 5;
 
-  const T* __restrict__ Q = static_cast<const T*>(d.q) + (long)b * d.q_bs + h * D;
-  const T* __restrict__ K = static_cast<const T*>(d.k) + (long)b * d.k_bs + h * D;
-  const T* __restrict__ V = static_cast<const T*>(d.v) + (long)b * d.v_bs + h * D;
-  T* __restrict__ O = static_cast<T*>(d.o) + (long)b * d.o_bs + h * D;
+  const T* __restrict__ Q = it.q(d);
+  const T* __restrict__ K = it.k(d);
+  const T* __restrict__ V = it.v(d);
+  T* __restrict__ O = it.o(d);
 
-  const int q_row = qb * kQB + wave * 32 + l31;
+  const int q_row = it.qblk * kQB + wave * 32 + l31;
   const bool q_ok = q_row < d.Nq;
   const int ntiles = (d.Nk + KT - 1) / KT;
   const float sc = d.scale * 1.44269504088896340736f;
@@ -406,8 +384,8 @@ __global__ __launch_bounds__(kThreads, 2) void attn_pipe_kernel(const pv_attenti
   constexpr int KCH = (KT * CPR + kThreads - 1) / kThreads;
   constexpr unsigned kOOB = 0x80000000u;
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(K), 0, (int)(((long)(d.Nk - 1) * d.ldk + D) * 2), 0x00020000);
-  __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(V), 0, (int)(((long)(d.Nk - 1) * d.ldv + D) * 2), 0x00020000);
+  __amdgpu_buffer_rsrc_t rk = attn_kv_rsrc<D>(K, d.Nk, d.ldk);
+  __amdgpu_buffer_rsrc_t rv = attn_kv_rsrc<D>(V, d.Nk, d.ldv);
   unsigned koff[KCH], voff;
 #pragma unroll
   for (int i = 0; i < KCH; ++i) {
@@ -498,10 +476,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_pipe_kernel(const pv_attenti
     // ---- deferred rescale (see attn_kernel); the row max came out of the previous step's PV phase ----
     constexpr float kDefer = 8.0f;
     {
-      float mx = mx_next * sc;
-      const unsigned mu = __builtin_bit_cast(unsigned, mx);
-      auto sw = __builtin_amdgcn_permlane32_swap(mu, mu, false, false);
-      mx = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
+      const float mx = attn_max_swap32(mx_next * sc);
       if (__any(mx > m_run + kDefer)) {
         const float m_new = fmaxf(m_run, mx);
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
@@ -559,13 +534,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_pipe_kernel(const pv_attenti
     bf16x8 pb[NSUB * 2];
     constexpr int NF = NSUB * 2 * NDB;
     bf16x8 vf[3];
-    auto read_v = [&](int slot, int i) {
-      const int sk = i / NDB, db = i - sk * NDB;
-      const T* vp = vc + (db * 32 + l31) * VLD + sk * 16 + hi * 4;
-      const bf16x4 lo = *reinterpret_cast<const bf16x4*>(vp);
-      const bf16x4 up = *reinterpret_cast<const bf16x4*>(vp + 8);
-      vf[slot] = bf16x8{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
-    };
+    auto read_v = [&](int slot, int i) { vf[slot] = read_vt_frag<D>(vc, i, l31, hi); };
     read_v(0, 0);
     read_v(1, 1);
     float mxa = -1e30f, mxb = -1e30f;
@@ -662,9 +631,9 @@ template <typename T, int D> int launch_attn(const pv_attention_desc& d, hipStre
   const int nqb = (d.Nq + kQB - 1) / kQB;
   const long total = (long)d.B * d.heads * nqb;
   if (total <= 0 || total > 0x7fffffffL) return PV_ERR_UNSUPPORTED;
-  if constexpr (sizeof(T) == 2 && D <= 96) {   // (D = 128 would spill: two score sets + 64 O accumulators)
+  if constexpr (sizeof(T) == 2 && D <= 64) {   // (96: attn_w64_kernel, which refuses only where this bound refuses too; 128 would spill)
     const long kv_bytes = ((long)(d.Nk + 192) * (d.ldk > d.ldv ? d.ldk : d.ldv) + D) * 2;   // 32-bit offsets, 2 tiles past the end
-    if (pv_tune("attn_pipe", 1) && kv_bytes < 0x7fffffffL) {
+    if (kv_bytes < 0x7fffffffL) {
       PV_LAUNCH((attn_pipe_kernel<D>), dim3((unsigned)total), dim3(kThreads), 0, s, d, nqb, (int)total);
       PV_LAUNCH_CHECK();
       return PV_OK;
@@ -695,10 +664,11 @@ extern "C" int pv_attention(const pv_attention_desc* dp, pv_stream_t stream) {
   const int align = d.dtype == PV_BF16 ? 8 : 4;  // 16-byte vector accesses
   if (d.ldq % align || d.ldk % align || d.ldv % align || d.ldo % align) return PV_ERR_INVALID;
   if (d.q_bs % align || d.k_bs % align || d.v_bs % align || d.o_bs % align) return PV_ERR_INVALID;
+  if (!(d.scale > 0.f) || isinf(d.scale)) return PV_ERR_INVALID;   // the kernels take row maxima before scaling
   const int width = d.heads * d.head_dim;
   if (d.ldq < width || d.ldk < width || d.ldv < width || d.ldo < width) return PV_ERR_INVALID;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  {   // bf16, head dim 96 (MViT): the one-wave-per-SIMD kernel of pv_attn64.hip
+  {   // bf16, head dim 96 (MViT): the kernel of pv_attn64.hip
     const int r = pv_attn_w64_try(d, s);
     if (r != PV_ERR_UNSUPPORTED) return r;
   }

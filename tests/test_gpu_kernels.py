@@ -124,54 +124,45 @@ def test_attention_online_softmax_rescale_branch(dtype):
     assert rel_err(got[0, 17], v[0, 333].float()) <= 2e-2  # the spiked row is (almost) a copy of v[333]
 
 
-@pytest.mark.parametrize("form", [0, 1, 2, 3, 4])
+@pytest.mark.parametrize("hd", [96, 64, 32])
 @pytest.mark.parametrize("B,heads,Nq,Nk,res", [
     (2, 2, 785, 785, True),       # MViT-B block 15, residual_pool
     (1, 1, 1000, 197, False),     # ragged key tail, several workgroups
     (2, 4, 129, 65, True),        # one row past a 32-row block / one key past a tile
     (1, 2, 300, 64, False),       # exactly one key tile: prologue + last step only
     (1, 1, 130, 128, True),       # two full tiles
-    (1, 3, 257, 192, False),      # three full tiles (odd count), one row past a 256-row item
+    (1, 3, 257, 192, False),      # three full tiles (odd count), one row past two 128-row items
     (1, 1, 40, 384, True),        # six full tiles: the pipelined steps on both parities
     (1, 8, 33, 3137, False),      # long key loop
     (2, 1, 3137, 785, True),      # MViT-B blocks 4-13 (one head of it)
 ])
-def test_attention_every_kernel_form_of_head_dim_96(form, B, heads, Nq, Nk, res):
-    """pv_attention routes bf16 / head_dim 96 (MViT) by size between the forms of attn_w64_kernel (pv_attn64.hip: 64 query
-    rows per wave on one wave per SIMD; 32 rows per wave on two waves per SIMD as one 8-wave or two 4-wave workgroups per
-    CU) -- the default routing would leave a form untested at a given size, so each is forced through the development knob
-    (0 = attn_pipe_kernel of pv_attn.hip, 3 = the default, 4 = forms 1 / 3 by size), against the fp32 reference (layers/attention.py:531-539)."""
-    hd, dtype = 96, torch.bfloat16
+def test_attention_every_kernel_form_of_head_dim_96(hd, B, heads, Nq, Nk, res):
+    """The two pipelined bf16 kernels at the tile counts their steps distinguish, against the fp32 reference
+    (layers/attention.py:531-539): pv_attention routes head_dim 96 (MViT) to attn_w64_kernel (pv_attn64.hip) and head_dim
+    64 / 32 to attn_pipe_kernel (pv_attn.hip); the route is asserted, no knob is involved."""
+    dtype = torch.bfloat16
     Cw = heads * hd
     q, k, v = _rand((B, Nq, Cw), 41, dtype), _rand((B, Nk, Cw), 42, dtype), _rand((B, Nk, Cw), 43, dtype)
     want = _attention_ref(q, k, v, heads, hd ** -0.5, res)
     routed = []
-    L.tune(attn_w64=form)
-    try:
-        got = _run_attention(q, k, v, heads, hd ** -0.5, res, pad=8, routed=routed)
-    finally:
-        L.tune(attn_w64=3)
+    got = _run_attention(q, k, v, heads, hd ** -0.5, res, pad=8, routed=routed)
     assert rel_err(got, want) <= TOL[dtype]
-    assert routed[0] == ("attn_pipe_kernel" if form == 0 else "attn_w64_kernel"), routed
+    assert routed[0] == ("attn_w64_kernel" if hd == 96 else "attn_pipe_kernel"), routed
 
 
-@pytest.mark.parametrize("form", [1, 2, 3])
-def test_attention_forms_take_the_rescale_branch_and_a_masked_first_tile(form):
-    """The rescale block of attn_w64_kernel (accumulator registers scaled through inline assembly in the one-wave form) and the
-    ragged single-tile path: a spiked key late in the sequence, one in the very first tile, and Nk < 64."""
-    B, heads, hd, Nq, Nk = 1, 1, 96, 64, 400
+@pytest.mark.parametrize("hd", [96, 64])
+def test_attention_forms_take_the_rescale_branch_and_a_masked_first_tile(hd):
+    """The rescale block of attn_w64_kernel (head_dim 96) and of attn_pipe_kernel (head_dim 64), and their ragged single-tile
+    path: a spiked key late in the sequence, one in the very first tile, and Nk < 64."""
+    B, heads, Nq, Nk = 1, 1, 64, 400
     dtype = torch.bfloat16
     q, k, v = _rand((B, Nq, hd), 11, dtype, 0.5), _rand((B, Nk, hd), 12, dtype, 0.5), _rand((B, Nk, hd), 13, dtype)
     k[0, 333] = (q[0, 17].float() * 8.0).to(dtype)
     k[0, 2] = (q[0, 40].float() * 8.0).to(dtype)
-    k[0, 130] = (q[0, 50].float() * 6.0).to(dtype)    # row 50 (second 32-row block of a 64-row wave) grows at another tile
+    k[0, 130] = (q[0, 50].float() * 6.0).to(dtype)    # row 50 (another wave's 32-row block) grows at another tile
     want = _attention_ref(q, k, v, heads, hd ** -0.5, False)
-    L.tune(attn_w64=form)
-    try:
-        got = _run_attention(q, k, v, heads, hd ** -0.5, False)
-        small = _run_attention(q[:, :, :], k[:, :37], v[:, :37], heads, hd ** -0.5, True)
-    finally:
-        L.tune(attn_w64=3)
+    got = _run_attention(q, k, v, heads, hd ** -0.5, False)
+    small = _run_attention(q[:, :, :], k[:, :37], v[:, :37], heads, hd ** -0.5, True)
     assert rel_err(got, want) <= TOL[dtype]
     assert rel_err(got[0, 17], v[0, 333].float()) <= 2e-2
     assert rel_err(small, _attention_ref(q, k[:, :37], v[:, :37], heads, hd ** -0.5, True)) <= TOL[dtype]
@@ -187,7 +178,23 @@ def test_attention_rejects_bad_descriptors():
     d.ldq = d.ldk = d.ldv = d.ldo = 40
     d.q_bs = d.k_bs = d.v_bs = d.o_bs = 320
     d.dtype = L.PV_F32
+    d.scale = 1.0
     assert lib.pv_attention(C.byref(d), None) == L.PV_ERR_UNSUPPORTED  # head_dim 40
+    # scale must be finite and > 0 (the kernels take row maxima before scaling), whichever kernel the descriptor routes to
+    qb, ob = torch.zeros(1, 8, 32, dtype=torch.bfloat16, device="cuda"), torch.zeros(1, 8, 32, dtype=torch.bfloat16, device="cuda")
+    d = L.AttentionDesc()
+    d.q = d.k = d.v = qb.data_ptr()
+    d.o = ob.data_ptr()
+    d.B, d.heads, d.head_dim, d.Nq, d.Nk = 1, 1, 32, 8, 8
+    d.ldq = d.ldk = d.ldv = d.ldo = 32
+    d.q_bs = d.k_bs = d.v_bs = d.o_bs = 256
+    d.dtype = L.PV_BF16
+    for bad in (0.0, -0.125, float("inf"), float("nan")):
+        d.scale = bad
+        assert lib.pv_attention(C.byref(d), None) == L.PV_ERR_INVALID, bad
+    d.scale = 0.125
+    assert lib.pv_attention(C.byref(d), None) == L.PV_OK
+    torch.cuda.synchronize()
 
 
 # ------------------------------------------------------------------ depthwise conv on tokens
