@@ -21,6 +21,7 @@ int pv_tune(const char* key, int dflt);                // pv_plan.hip
     if (_e != hipSuccess) return pv_set_hip_error(_e, #expr); \
   } while (0)
 #define PV_LAUNCH_CHECK() PV_HIP_CHECK(hipGetLastError())
+inline int pv_launch_status() { PV_LAUNCH_CHECK(); return PV_OK; }   // `return pv_launch_status();` ends an entry that launched
 // Every kernel launch goes through PV_LAUNCH: it notes the kernel's symbol (a pointer store) so that pv_plan_profile can
 // report which kernel an op was routed to -- bench.py's `roofline` is per kernel SYMBOL, not per op label.  (One exception:
 // pv_gemm_launch_persistent in pv_gemm_tile.h launches through a function pointer and notes the kernel's name itself.)
@@ -141,6 +142,21 @@ template <bool FAST, int N> __device__ __forceinline__ void pv_apply_act_n(float
 
 __host__ __device__ __forceinline__ int pv_round_up(int v, int m) { return (v + m - 1) / m * m; }
 __host__ __device__ __forceinline__ long pv_ceil_div(long a, long b) { return (a + b - 1) / b; }
+inline unsigned pv_blocks(long total, int threads) { return (unsigned)pv_ceil_div(total, threads); }
+
+// ---- host side: from a descriptor's dtype code to the element type ----
+// Calls f(PvType<T>()) with T = float | bf16_t (U8: | unsigned char, the sources of the layout kernels) and returns its
+// status; PV_ERR_UNSUPPORTED for every other code.  f is a generic lambda that launches its kernel<T> through PV_LAUNCH
+// (the noted name is cut at `<`, so `kernel<T>` reports `kernel`) and returns pv_launch_status().
+template <typename T> struct PvType { typedef T type; };
+template <bool U8 = false, typename F> inline int pv_for_dtype(int dtype, F&& f) {
+  if (dtype == PV_F32) return f(PvType<float>());
+  if (dtype == PV_BF16) return f(PvType<bf16_t>());
+  if constexpr (U8) {
+    if (dtype == PV_U8) return f(PvType<unsigned char>());
+  }
+  return PV_ERR_UNSUPPORTED;
+}
 
 // ---- kernel start-up: request everything, wait once ----
 // `s_waitcnt vmcnt(0)` alone (expcnt / lgkmcnt untouched), fenced so that neither the requests above it nor the LDS writes below

@@ -38,7 +38,7 @@ def _routed_kernel(op, d):
         lib.pv_plan_destroy(plan)
 
 
-# ------------------------------------------------------------------ pv_misc.hip family: float64 references and checks
+# ------------------------------------------------------------------ pv_rows / pv_pool / pv_layout / pv_segate.hip families: float64 references and checks
 # Everything below runs on the CPU (tests/test_misc_kernel_checks.py feeds the checks their own reference and defective
 # copies of it); tests/test_gpu_misc_kernels.py feeds them what the kernels left on the device.
 #

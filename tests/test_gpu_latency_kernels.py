@@ -1,4 +1,4 @@
-"""The two latency-bound launches of X3D's critical path, pv_misc.hip's se_gate_fast_kernel and pool_reduce_kernel, at the
+"""The two latency-bound launches of X3D's critical path, pv_segate.hip's se_gate_fast_kernel and pv_pool.hip's pool_reduce_kernel, at the
 sizes where the way their bytes arrive changes: the SE gate stages fc2's [C][cr] matrix through LDS (flat 16-byte loads, a
 dword head and tail where the matrix does not start or end on a 16-byte boundary, rows spread at pitch cr | 1) and runs 256,
 512 or 1024 threads by instantiation; the pool issues a thread's taps in straight-line batches of 8 loads (whole batches, then

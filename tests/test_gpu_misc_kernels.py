@@ -1,6 +1,6 @@
-"""Direct parity of the pv_misc.hip family on the MI355X: every C-ABI entry of the row, pooling, layout and head kernels
-against a float64 CPU reference of the same operation on the same (bf16-rounded) inputs, at the smallest shapes that reach
-each branch of the dispatchers, with the routed symbol asserted.
+"""Direct parity of the pv_rows.hip, pv_pool.hip, pv_layout.hip and pv_segate.hip families on the MI355X: every C-ABI entry of
+the row, pooling, layout, SE-gate and head kernels against a float64 CPU reference of the same operation on the same
+(bf16-rounded) inputs, at the smallest shapes that reach each branch of the dispatchers, with the routed symbol asserted.
 
 Every case also asserts that the padding channels [C, round_up(C, 8)) of written rows are zero where the kernel's contract
 says so, and that a canary (7.0) survives beyond the padding up to the row stride, in rows the launch does not own and in
@@ -13,7 +13,7 @@ pv_add_posenc in the kernel's own order); one bf16 rounding (2**-8 per element) 
 
 Case -> symbol -> template arguments (the symbol is asserted; the arguments follow from the dispatch condition quoted):
 
-pv_se_gate (C <= 448 && cr <= 32 && c_p <= 512: fast kernel, cj = ceil(C / 64))
+pv_se_gate [pv_segate.hip] (C <= 448 && cr <= 32 && c_p <= 512: fast kernel, cj = ceil(C / 64))
   (64, 8)                          se_gate_fast_kernel<1, 8>     cj <= 1 && cr <= 8
   (65, 8) (128, 8)                 se_gate_fast_kernel<2, 8>     cj <= 2 && cr <= 8
   (129, 8) (48, 16) (256, 16)      se_gate_fast_kernel<4, 16>    cj <= 4 && cr <= 16
@@ -21,7 +21,7 @@ pv_se_gate (C <= 448 && cr <= 32 && c_p <= 512: fast kernel, cj = ceil(C / 64))
   (257, 16) (448, 32)              se_gate_fast_kernel<7, 32>    else
   (448, 32) with c_p = 456         se_gate_fast_kernel<7, 32>    c_p above round_up(C, 8)
   (449, 32) (448, 33)              se_gate_kernel                C > 448 | cr > 32
-pv_pool3d (T = float | bf16_t for every kernel)
+pv_pool3d [pv_pool.hip] (T = float | bf16_t for every kernel)
   (16,7,7) / 432, (8,7,7) / 2048,
   (4,4,4) s2 p1 / 40, (4,4,4) / 4  pool_reduce_kernel<T>         taps >= 64
   (7,3,3), 63 taps                 pool_direct_kernel<T>         taps < 64, not 3x3x3 / 1x3x3
@@ -30,14 +30,14 @@ pv_pool3d (T = float | bf16_t for every kernel)
   prefix, 3x3x3 pool_window = 0,
   prefix, 2x2x2                    pool_direct_kernel<T>         + pool_prefix_kernel<T>
   prefix, 4x4x4                    pool_reduce_kernel<T>         + pool_prefix_kernel<T>
-pv_ingest_ncdhw
+pv_ingest_ncdhw [pv_layout.hip]
   generic, six (src, dst) pairs    ingest_kernel<S, T>           c_p = 16: not the 4-channel layout
   c4, frame 9 x 11                 ingest_c4_kernel<S>           S = float | bf16_t | unsigned char; H*W % 8 != 0
   c4, frame 8 x 12                 ingest_c4_vec8_kernel<S>      H*W % 8 == 0, 16-byte aligned planes
   c4, frame 8 x 12, source + 1     ingest_c4_kernel<S>           source pointer not 16-byte aligned
-pv_egress_ncdhw
+pv_egress_ncdhw [pv_layout.hip]
   four (src, dst) pairs            egress_kernel<T, S>
-pv_affine_rows
+pv_affine_rows [pv_rows.hip, as every entry below]
   C = 20, x_f32 -> bf16            affine_rows_kernel<float, bf16_t>
   C = 20, fp32 / bf16              affine_rows_kernel<float, float> / <bf16_t, bf16_t>
   8200 x 2048 bf16 in place        affine_rows_kernel<bf16_t, bf16_t>   8200 blocks asked, 8192 launched: second grid trip
@@ -54,8 +54,8 @@ pv_layernorm (CG = round_up(C, 8) / 8; same dtype T in and out unless x_f32)
   x_f32 C = 260                                layernorm_f32in_kernel<bf16_t, 64, 2>   2 CG <= 128
   x_f32 trip C = 520                           layernorm_f32in_kernel<bf16_t, 64, 4>   CG <= 128
   x_f32 C = 1032, 1536                         layernorm_kernel<float, bf16_t, 4>      CG > 128
-  No descriptor reaches layernorm_kernel<float, bf16_t, 1 | 2> or layernorm16_kernel<float, bf16_t, 16 | 32>: an x_f32 row
-  of CG <= 128 is taken by layernorm_f32in_kernel first, and g_period > 1 refuses x_f32.
+  layernorm_kernel<float, bf16_t, 1 | 2> and layernorm16_kernel<float, bf16_t, 16 | 32> do not exist: an x_f32 row of
+  CG <= 128 is taken by layernorm_f32in_kernel first, and g_period > 1 refuses x_f32.
 pv_softmax_rows   every case       softmax_rows_kernel<T>
 pv_mean_rows      every case       mean_rows_kernel<T>
 pv_add_posenc     every case       posenc_kernel<T>

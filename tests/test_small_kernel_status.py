@@ -1,0 +1,111 @@
+"""Statuses of the row, pooling, layout and SE-gate entries for descriptors they reject before any launch: one table of
+(entry, change to a valid descriptor, status).  PV_ERR_INVALID is a descriptor that contradicts itself, PV_ERR_UNSUPPORTED
+one that is consistent but has no kernel; callers tell them apart, so the table pins which of the two each case gets.
+No compute, runs without a GPU: the pointers are addresses of a host buffer that no entry dereferences."""
+import ctypes as C
+
+from pytorchvideo_amd import _lib as L
+
+INVALID, UNSUPPORTED = L.PV_ERR_INVALID, L.PV_ERR_UNSUPPORTED
+_BUF = C.create_string_buffer(256)
+P = (C.addressof(_BUF) + 63) // 64 * 64        # a 64-byte aligned non-null address
+NO_DTYPE = 7
+
+# entry -> (descriptor type, a descriptor the entry would launch)
+BASE = {
+    "pv_se_gate": (L.SeGateDesc, dict(psum=P, gate=P, w1=P, w2=P, B=2, C=20, c_p=24, cr=6, nblk=3, inv_count=0.5)),
+    # 3x3x3 window, stride (1, 2, 2), padding 1: 4 x 5 x 5 -> 4 x 3 x 3
+    "pv_pool3d": (L.Pool3dDesc, dict(x=P, y=P, x_bs=2400, y_bs=864, ldx=24, ldy=24, B=1, Ti=4, Hi=5, Wi=5, C=20, To=4, Ho=3,
+                                     Wo=3, kt=3, kh=3, kw=3, st=1, sh=2, sw=2, pt=1, ph=1, pw=1, mode=L.POOL_MAX,
+                                     dtype=L.PV_F32)),
+    "pv_ingest_ncdhw": (L.LayoutDesc, dict(src=P, dst=P, B=1, C=3, T=2, H=3, W=5, c_p=16, ld=24, bs=720, src_dtype=L.PV_F32,
+                                           dst_dtype=L.PV_BF16)),
+    # the 4-channel first-layer layout
+    "pv_ingest_ncdhw/c4": (L.LayoutDesc, dict(src=P, dst=P, B=1, C=3, T=2, H=3, W=5, c_p=4, ld=4, bs=120,
+                                              src_dtype=L.PV_U8, dst_dtype=L.PV_BF16)),
+    "pv_egress_ncdhw": (L.LayoutDesc, dict(src=P, dst=P, B=1, C=3, T=2, H=3, W=5, c_p=16, ld=24, bs=720,
+                                           src_dtype=L.PV_BF16, dst_dtype=L.PV_F32)),
+}
+_ROWS = dict(x=P, y=P, rows=10, C=20, ldx=24, ldy=24, eps=1e-6, dtype=L.PV_F32)
+for _e in ("pv_layernorm", "pv_affine_rows", "pv_softmax_rows"):
+    BASE[_e] = (L.RowsDesc, _ROWS)
+BASE["pv_mean_rows"] = (L.RowsDesc, dict(_ROWS, rows_per_batch=5))
+BASE["pv_add_posenc"] = (L.PosencDesc, dict(x=P, pos_spatial=P, B=1, T=2, HW=4, C=20, ld=24, dtype=L.PV_F32))
+BASE["pv_add_act"] = (L.AddDesc, dict(a=P, b=P, y=P, rows=5, C=20, lda=24, ldb=24, ldy=24, dtype=L.PV_F32))
+BASE["pv_ensemble_scores"] = (L.EnsembleDesc, dict(logits=P, video_index=P, accum=P, counts=P, N=3, C=10, ld=16, V=2, mode=0))
+
+
+def _each(entry, status, **values):
+    """One row per (field, value): every change alone."""
+    return [(entry, {k: v}, status) for k, vs in values.items() for v in (vs if isinstance(vs, tuple) else (vs,))]
+
+
+TABLE = (
+    [(e, None, INVALID) for e in BASE]                                    # no descriptor at all
+    # ---- pv_se_gate
+    + _each("pv_se_gate", INVALID, psum=None, gate=None, w1=None, w2=None, B=0, C=(0, -1), cr=0, nblk=0,
+            c_p=(16, 25))                                                 # c_p < C; c_p no multiple of 8
+    # ---- pv_pool3d
+    + _each("pv_pool3d", INVALID, x=None, y=None, B=0, C=0, To=(0, 5), Ho=(0, 4), Wo=(0, 2),   # zero / not what the window gives
+            ldx=20, ldy=20, x_bs=2404, y_bs=868, kt=0, kh=0, kw=0, st=0, sh=0, sw=0, mode=(2, -1))
+    + _each("pv_pool3d", UNSUPPORTED, dtype=(NO_DTYPE, L.PV_U8))
+    + [("pv_pool3d", dict(mode=2, dtype=NO_DTYPE), INVALID)]              # the mode is checked before the dtype
+    # ---- pv_ingest_ncdhw, generic layout
+    + _each("pv_ingest_ncdhw", INVALID, src=None, dst=None, B=0, C=0, T=0, H=0, W=0, c_p=(12, 0), ld=(20, 8), bs=724)
+    + [("pv_ingest_ncdhw", dict(t_index=P, src_T=0), INVALID),
+       ("pv_ingest_ncdhw", dict(t_index=P, src_T=0, src_dtype=NO_DTYPE), INVALID)]
+    + _each("pv_ingest_ncdhw", UNSUPPORTED, src_dtype=(NO_DTYPE, L.PV_U16), dst_dtype=(NO_DTYPE, L.PV_U8))
+    # ---- pv_ingest_ncdhw, 4-channel layout; a descriptor that is not quite one falls through to the generic check
+    + [("pv_ingest_ncdhw/c4", dict(t_index=P, src_T=0), INVALID),
+       ("pv_ingest_ncdhw/c4", dict(t_index=P, src_T=0, src_dtype=NO_DTYPE), INVALID),
+       ("pv_ingest_ncdhw/c4", dict(src_dtype=NO_DTYPE), UNSUPPORTED),
+       ("pv_ingest_ncdhw/c4", dict(src_dtype=NO_DTYPE, H=4, W=4, bs=128), UNSUPPORTED),   # the 8-voxel form's geometry
+       ("pv_ingest_ncdhw/c4", dict(bs=122), INVALID),                     # bs % 4 != 0
+       ("pv_ingest_ncdhw/c4", dict(dst_dtype=L.PV_F32), INVALID),
+       ("pv_ingest_ncdhw/c4", dict(C=5), INVALID),
+       ("pv_ingest_ncdhw/c4", dict(ld=8), INVALID),
+       ("pv_ingest_ncdhw/c4", dict(B=0), INVALID),
+       ("pv_ingest_ncdhw/c4", dict(src=None), INVALID)]
+    # ---- pv_egress_ncdhw
+    + _each("pv_egress_ncdhw", INVALID, src=None, dst=None, B=0, C=0, T=0, H=0, W=0, c_p=(12, 4, 0), ld=(20, 8), bs=724)
+    + _each("pv_egress_ncdhw", UNSUPPORTED, src_dtype=(NO_DTYPE, L.PV_U8), dst_dtype=(NO_DTYPE, L.PV_U8))
+    # ---- pv_layernorm
+    + _each("pv_layernorm", INVALID, x=None, y=None, rows=0, C=0, ldx=20, ldy=20, g_period=(17, -1))
+    + _each("pv_layernorm", UNSUPPORTED, g_period=(3, 5), dtype=NO_DTYPE)
+    + [("pv_layernorm", dict(g_period=8, x_f32=1, dtype=L.PV_BF16), UNSUPPORTED),
+       ("pv_layernorm", dict(g_period=8, C=264, ldx=264, ldy=264), UNSUPPORTED),          # 33 chunks: beyond the narrow-row kernel
+       ("pv_layernorm", dict(g_period=17, x_f32=1, dtype=L.PV_BF16), INVALID)]
+    + [("pv_layernorm", dict(C=2056, ldx=2056, ldy=2056, dtype=dt, x_f32=xf), UNSUPPORTED)  # 257 chunks
+       for dt, xf in ((L.PV_F32, 0), (L.PV_BF16, 0), (L.PV_BF16, 1), (NO_DTYPE, 0))]
+    # ---- pv_affine_rows
+    + _each("pv_affine_rows", INVALID, x=None, y=None, rows=0, C=0, ldx=20, ldy=20, g_period=1, n_prefix=(-1, 1),
+            rows_per_batch=-1)                                            # n_prefix = 1 without rows_per_batch
+    + _each("pv_affine_rows", UNSUPPORTED, dtype=(NO_DTYPE, L.PV_U8))
+    # ---- pv_softmax_rows
+    + _each("pv_softmax_rows", INVALID, x=None, y=None, rows=(0, -1), C=0)
+    + _each("pv_softmax_rows", UNSUPPORTED, dtype=NO_DTYPE)
+    # ---- pv_mean_rows
+    + _each("pv_mean_rows", INVALID, x=None, y=None, rows=0, C=0, rows_per_batch=(0, -1, 3, 20))   # 10 % 3, 10 % 20
+    + _each("pv_mean_rows", UNSUPPORTED, dtype=NO_DTYPE)
+    # ---- pv_add_posenc
+    + _each("pv_add_posenc", INVALID, x=None, pos_spatial=None, B=0, T=0, HW=0, C=0, ld=20, cls_only=1)   # no cls_token
+    + _each("pv_add_posenc", UNSUPPORTED, dtype=NO_DTYPE)
+    + [("pv_add_posenc", dict(cls_only=1, dtype=NO_DTYPE), INVALID)]
+    # ---- pv_add_act
+    + _each("pv_add_act", INVALID, a=None, b=None, y=None, rows=0, C=0, lda=20, ldb=20, ldy=20)
+    + _each("pv_add_act", UNSUPPORTED, dtype=NO_DTYPE)
+    # ---- pv_ensemble_scores
+    + _each("pv_ensemble_scores", INVALID, logits=None, video_index=None, accum=None, counts=None, N=0, C=0, V=0, ld=8,
+            mode=(2, -1))
+)
+
+
+def test_every_rejected_descriptor_gets_its_status(pv_lib):
+    wrong = []
+    for entry, change, status in TABLE:
+        cls, base = BASE[entry]
+        fn = getattr(pv_lib, entry.split("/")[0])
+        got = fn(None, None) if change is None else fn(C.byref(cls(**dict(base, **change))), None)
+        if got != status:
+            wrong.append("%s %s: status %d, expected %d" % (entry, change, got, status))
+    assert not wrong, "\n".join(wrong)
