@@ -565,6 +565,8 @@ enum { PV_SRC_YUV420 = 2 };   /* pv_batch_views_desc.src_layout only, beside pv_
 enum { PV_SRC_BGR = 4, PV_SRC_RGBA = 5, PV_SRC_BGRA = 6, PV_SRC_ARGB = 7, PV_SRC_ABGR = 8 };
 /* YUV 4:2:2 and 4:4:4 (see "YUV 4:2:2 and 4:4:4" below); pv_batch_views_desc.src_layout only.  The value 9 is no layout. */
 enum { PV_SRC_YUV422 = 10, PV_SRC_YUV444 = 11 };
+/* Packed YUV 4:2:2 (see "packed YUV 4:2:2" below); pv_batch_views_desc.src_layout only.  The value 12 is no layout. */
+enum { PV_SRC_YUYV422 = 13 };
 typedef struct pv_view_source {      /* one decoded video; 96 bytes, 8-byte aligned */
   const void* src;                   /* device address of the video / of frame 0                              */
   int64_t frame_stride;              /* YUV and packed sources: bytes between frames (RGB / planar: dense)    */
@@ -591,7 +593,7 @@ typedef struct pv_batch_views_desc {
   int32_t n_sources, n_items, n_rows, t_stride;
   int32_t C, T;                       /* channels (<= 4; 3 for YUV), DESTINATION frames per item               */
   int32_t src_dtype, src_layout;      /* pv_dtype; PV_SRC_NCTHW / PV_SRC_NTHWC / PV_SRC_YUV420 / PV_SRC_BGR .. */
-  int32_t c_step;                     /* PV_SRC_YUV420 / 422 / 444: 2 interleaved chroma, 1 planar             */
+  int32_t c_step;                     /* PV_SRC_YUV420 / 422 / 444: 2 interleaved chroma, 1 planar; YUYV422: 4 */
   int32_t Ho, Wo, n_views;            /* crop window; views per clip, 1..3                                     */
   int32_t dst_layout, dst_dtype;
   int32_t c_p, ld;                    /* PV_DST_NDHWC only                                                     */
@@ -859,6 +861,43 @@ int pv_area_views(const pv_area_views_desc* d, pv_stream_t stream);
  * address, pitch, offset or stride; an odd rectangle member the subsampling halves; and whatever the entry point rejects of any
  * launch.  PV_ERR_UNSUPPORTED: a staged strip or tile beyond the LDS limit, the index limit of pv_area_views, oriented records
  * in pv_region_views / pv_area_views, pv_hdr_views.  An invalid field wins over an unsupported size.
+ */
+
+/* ---- packed YUV 4:2:2: YUY2 / YVYU / UYVY / VYUY and Y210 / Y212 / Y216 frames read where they lie ----------------------------
+ * Live sources hand out 4:2:2 in ONE plane: UVC webcams and V4L2 (YUYV), SDI / HDMI capture cards (UYVY), DXVA / VAAPI / Media
+ * Foundation for 10- to 16-bit 4:2:2 (Y210 / Y212 / Y216).  Luma and chroma are interleaved in macropixels of four samples, so
+ * such a frame needed a de-interleave pass into planes before the launch.  One more value of pv_batch_views_desc.src_layout
+ * (declared beside PV_SRC_YUV422; the value 12 is no layout and stays PV_ERR_INVALID) names it:
+ *                   PV_SRC_YUYV422   one plane of Hs rows of Ws / 2 macropixels; (csy, csx) = (0, 1), as PV_SRC_YUV422
+ * Honoured by:  pv_batch_views, pv_frame_views, pv_region_views and pv_area_views -- whole videos and frame lists, orient 0..7
+ *               where the entry point takes it, up to three views, all five destination forms.  pv_box_views reads such
+ *               records unchanged.  NOT by pv_hdr_views, which answers PV_ERR_UNSUPPORTED, and not by the one-source entry
+ *               points, which have no field for it.
+ * Descriptor:   c_step = 4: the samples between x-adjacent samples of one chroma component, which is what c_step counts in
+ *               every YUV layout (1 and 2 are PV_ERR_INVALID here, 4 is PV_ERR_INVALID everywhere else).  C = 3; yuv2rgb is
+ *               required.  src_dtype PV_U8 (sb = 1) or PV_U16 (sb = 2: little-endian codes; Y210 / Y212 / Y216 keep the value
+ *               in the high bits, which lives in yuv2rgb as for every 16-bit layout).
+ * Record:       y_pitch: bytes per row, >= 2 * Ws * sb.  c_pitch: 0, as for packed pixels.  frame_stride >= (Hs - 1) * y_pitch +
+ *               2 * Ws * sb.  u_offset / v_offset: the byte of the first U / V sample FROM THE START OF A ROW, read per record, so
+ *               records of different sample orders share a launch as NV12 and NV21 records do.  Exactly these pairs are valid:
+ *                   (sb, 3 sb) YUY2 (Y0 U Y1 V)     (3 sb, sb) YVYU (Y0 V Y1 U)     (0, 2 sb) UYVY (U Y0 V Y1)     (2 sb, 0) VYUY
+ *               and luma lies at the other two sample positions:
+ *                   U(y, i) = frame[y * y_pitch + u_offset + i * 4 sb]        V likewise        0 <= y < Hs, 0 <= i < Ws / 2
+ *                   Y(y, x) = frame[y * y_pitch + y0 + x * 2 sb]              y0 = 0 where U and V are odd samples, else sb
+ *                   tap (y, x) uses U(y, x >> 1) and V(y, x >> 1)
+ *               Ws is even; any Hs.  PV_U8 frames may start at any byte; PV_U16: the evenness rules of pv_yuv16_views.
+ * pv_region_views: left and w are even, as for PV_SRC_YUV422.
+ * Arithmetic:   nothing new.  AN ITEM HOLDS, BIT FOR BIT, WHAT THE SAME ENTRY POINT WRITES WITH PV_SRC_YUV422, c_step 1, THE SAME
+ *               MATRIX AND THE SAME src_dtype FOR THE PLANAR COPY OF THE SAME FRAMES (Y, U and V planes de-interleaved, nothing
+ *               else touched): taps, the per-tap conversion and clamp, the pinned blend, the box filter's windows and summation
+ *               order, the affine map and the single rounding are those of that launch, orientation included.
+ * Kernels:      pytorchvideo_amd/csrc/pv_yuyv.hip.  A source row is staged ONCE -- the macropixels that cover the span -- and
+ *               serves as luma and chroma image both; the sample order is read from the record.
+ * PV_ERR_INVALID, before every HIP call: any other (u_offset, v_offset) pair; c_step other than 4; a non-zero c_pitch; an odd Ws;
+ * a y_pitch or frame_stride too small; PV_U16 with an odd address, pitch, offset or stride; a rectangle with an odd left or w; C != 3;
+ * a null yuv2rgb; and whatever the entry point rejects of any launch.  PV_ERR_UNSUPPORTED: a staged strip or tile beyond the LDS
+ * limit, the index limit of pv_area_views, oriented records in pv_region_views / pv_area_views, pv_hdr_views.  An invalid field
+ * wins over an unsupported size.
  */
 
 /* ---- key-frame detection: the boxes of a forward mapped into its views, on the device ---------------------------------

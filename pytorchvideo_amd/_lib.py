@@ -96,6 +96,8 @@ SRC_YUV420 = 2   # BatchViewsDesc.src_layout only
 SRC_BGR, SRC_RGBA, SRC_BGRA, SRC_ARGB, SRC_ABGR = 4, 5, 6, 7, 8
 # YUV 4:2:2 and 4:4:4 (the header's "YUV 4:2:2 and 4:4:4"): BatchViewsDesc.src_layout only; the value 9 is no layout
 SRC_YUV422, SRC_YUV444 = 10, 11
+# packed YUV 4:2:2 (the header's "packed YUV 4:2:2"): BatchViewsDesc.src_layout only, c_step 4; the value 12 is no layout
+SRC_YUYV422 = 13
 ViewSource = _struct("ViewSource", [
     ("src", _p), ("frame_stride", _i64), ("u_offset", _i64), ("v_offset", _i64)]
     + _ints("y_pitch", "c_pitch", "N", "Hs", "Ws", "Hn", "Wn") + [("y_off", _i32 * 3), ("x_off", _i32 * 3), ("sy", _f32), ("sx", _f32)]

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 INCLUDE = os.path.join(ROOT, "include")
 OUT_DIR = os.path.join(os.path.dirname(HERE), "_lib")
 LIB = os.path.join(OUT_DIR, "libpv_mi355x.so")
-SOURCES = ["pv_conv.hip", "pv_pwconv.hip", "pv_gemm.hip", "pv_gemm8.hip", "pv_gemm9.hip", "pv_gemm9h.hip", "pv_stem.hip", "pv_dwconv.hip", "pv_pwdw.hip", "pv_segate.hip", "pv_pool.hip", "pv_layout.hip", "pv_rows.hip", "pv_resample.hip", "pv_yuv.hip", "pv_batch.hip", "pv_frames.hip", "pv_frames16.hip", "pv_orient.hip", "pv_hdr.hip", "pv_region.hip", "pv_area.hip", "pv_packed.hip", "pv_yuv4.hip", "pv_boxes.hip", "pv_tokpool.hip", "pv_attn.hip", "pv_attn64.hip", "pv_roi.hip", "pv_lateral.hip", "pv_mlp.hip", "pv_block.hip", "pv_headgemm.hip", "pv_comm.hip", "pv_plan.hip"]
+SOURCES = ["pv_conv.hip", "pv_pwconv.hip", "pv_gemm.hip", "pv_gemm8.hip", "pv_gemm9.hip", "pv_gemm9h.hip", "pv_stem.hip", "pv_dwconv.hip", "pv_pwdw.hip", "pv_segate.hip", "pv_pool.hip", "pv_layout.hip", "pv_rows.hip", "pv_resample.hip", "pv_yuv.hip", "pv_batch.hip", "pv_frames.hip", "pv_frames16.hip", "pv_orient.hip", "pv_hdr.hip", "pv_region.hip", "pv_area.hip", "pv_packed.hip", "pv_yuv4.hip", "pv_yuyv.hip", "pv_boxes.hip", "pv_tokpool.hip", "pv_attn.hip", "pv_attn64.hip", "pv_roi.hip", "pv_lateral.hip", "pv_mlp.hip", "pv_block.hip", "pv_headgemm.hip", "pv_comm.hip", "pv_plan.hip"]
 HEADERS = [os.path.join(HERE, "pv_common.h"), os.path.join(HERE, "pv_attn.h"), os.path.join(HERE, "pv_gemm_tile.h"), os.path.join(HERE, "pv_rs.h"), os.path.join(HERE, "pv_frames.h"), os.path.join(HERE, "pv_area.h"), os.path.join(INCLUDE, "pv_mi355x.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", HERE,

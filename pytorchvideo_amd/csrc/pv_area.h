@@ -1,7 +1,7 @@
 // The staged-tile bodies of pv_area_views (pv_area.hip describes the three steps), with what they are made of: the launch
 // record, the tile of a workgroup and the store of its results.  They are here, not in pv_area.hip, because other translation
 // units instantiate them: ar_tile_rgb serves pv_area.hip (the dense forms) and pv_packed.hip (packed pixels: RsPacked,
-// pv_rs.h), ar_tile_yuv serves pv_area.hip (4:2:0) and pv_yuv4.hip (4:2:2 / 4:4:4: RsSub, pv_rs.h).  The sizing and the entry
+// pv_rs.h), ar_tile_yuv serves pv_area.hip (4:2:0), pv_yuv4.hip (4:2:2 / 4:4:4: RsSub, pv_rs.h) and pv_yuyv.hip (packed 4:2:2: RsMacro).  The sizing and the entry
 // point stay in pv_area.hip.
 #pragma once
 #include "pv_frames.h"
@@ -20,6 +20,8 @@ struct ArLaunch {
 int pv_packed_area(const pv_batch_views_desc& d, bool frames, const ArLaunch& g, size_t lds, pv_stream_t stream);
 // Likewise the YUV 4:2:2 / 4:4:4 kernels of pv_area_views (pv_yuv4.hip).
 int pv_yuv4_area(const pv_batch_views_desc& d, bool frames, const ArLaunch& g, size_t lds, pv_stream_t stream);
+// Likewise the packed YUV 4:2:2 kernels of pv_area_views (pv_yuyv.hip).
+int pv_yuyv_area(const pv_batch_views_desc& d, bool frames, const ArLaunch& g, size_t lds, pv_stream_t stream);
 
 namespace {
 
@@ -158,8 +160,8 @@ __device__ __forceinline__ void ar_tile_rgb(unsigned char* lds, const ArLaunch& 
   ar_store<FORM, D>(res, g, a, d, d.C, zi, t);
 }
 
-// CSTEP / FORM / D / SMP / SUB: as rs_strip_yuv.
-template <int CSTEP, int FORM, typename D, typename SMP, typename SUB = RsSub420>
+// CSTEP / FORM / D / SMP / SUB / ARR: as rs_strip_yuv; the staged rows of RsMacro span the macropixels [xs0 >> 1, (xs1 - 1) >> 1].
+template <int CSTEP, int FORM, typename D, typename SMP, typename SUB = RsSub420, typename ARR = RsPlanes>
 __device__ __forceinline__ void ar_tile_yuv(unsigned char* lds, const ArLaunch& g, const RsYuvSrc& s, int Hn, int Wn, const RsDst& d,
                                             const float* yuv2rgb, int zi, int t, const SUB& sub = SUB()) {
   constexpr int CP = CSTEP == 1 ? 2 : 1;           // staged chroma planes
@@ -170,13 +172,14 @@ __device__ __forceinline__ void ar_tile_yuv(unsigned char* lds, const ArLaunch& 
   if (a.nrows <= 0 || a.ncols <= 0) return;
   const int pitch_y = g.pitch, pitch_c = g.pitch_c, c_base = g.c_base;
   const int cr0 = a.ys0 >> sub.csy, cc0 = a.xs0 >> sub.csx;
-  const int nslots = a.ys1 - a.ys0, ncslots = ((a.ys1 - 1) >> sub.csy) - cr0 + 1;
-  const int span_y = (a.xs1 - a.xs0) * SB;
+  const int nslots = a.ys1 - a.ys0, ncslots = ARR::kMacro ? 0 : ((a.ys1 - 1) >> sub.csy) - cr0 + 1;
+  const int span_y = ARR::kMacro ? (((a.xs1 - 1) >> 1) - cc0 + 1) * CB : (a.xs1 - a.xs0) * SB;   // macropixels: one staged row, the span of both
   const int span_c = (((a.xs1 - 1) >> sub.csx) - cc0 + 1) * CB;
-  if (nslots > g.rows || ncslots > g.rows_c || span_y + 15 > pitch_y || span_c + 15 > pitch_c) return;
+  if (nslots > g.rows || ncslots > g.rows_c || span_y + 15 > pitch_y || (!ARR::kMacro && span_c + 15 > pitch_c)) return;
 
   const uintptr_t frame = s.src + s.frame_off;
-  auto y_addr = [&](int y) -> uintptr_t { return frame + (long)y * s.y_pitch + a.xs0 * SB; };
+  // the first staged byte of source row y: luma column xs0, or the macropixel that holds it
+  auto y_addr = [&](int y) -> uintptr_t { return frame + (long)y * s.y_pitch + (ARR::kMacro ? cc0 * CB : a.xs0 * SB); };
   auto c_addr = [&](int cy, int pl) -> uintptr_t {
     return frame + (pl == 0 ? s.c_off_a : s.c_off_b) + (long)cy * s.c_pitch + (long)cc0 * CB;
   };
@@ -193,7 +196,7 @@ __device__ __forceinline__ void ar_tile_yuv(unsigned char* lds, const ArLaunch& 
       const int idx = base + u * kRsThreads;
       off[u] = -1;
       if (idx < total) {
-        const bool luma = idx < total_y;
+        const bool luma = ARR::kMacro || idx < total_y;
         const int j = luma ? idx : idx - total_y;
         const int cpr = luma ? cpr_y : cpr_c;
         const int sp = j / cpr, ch = j - sp * cpr;             // luma: sp = slot; chroma: sp = slot * CP + plane
@@ -221,11 +224,15 @@ __device__ __forceinline__ void ar_tile_yuv(unsigned char* lds, const ArLaunch& 
     sh[c] = (d.ch_scale && d.ch_shift) ? d.ch_shift[c] : 0.f;
   }
   // the low address bits of a staged row: 32-bit arithmetic keeps `addr & 15`
-  const unsigned ya32 = (unsigned)(frame + a.xs0 * SB), yp32 = (unsigned)s.y_pitch, cp32 = (unsigned)s.c_pitch;
+  const unsigned ya32 = (unsigned)(frame + (ARR::kMacro ? cc0 * CB : a.xs0 * SB)), yp32 = (unsigned)s.y_pitch, cp32 = (unsigned)s.c_pitch;
   const unsigned ua32 = (unsigned)(frame + s.c_off_a + (long)cc0 * CB), va32 = (unsigned)(frame + s.c_off_b + (long)cc0 * CB);
   // LDS byte offsets of the Y, U and V samples of source pixel (y, column offsets oyx / ocx)
   auto tap = [&](int y, int oyx, int ocx, int& oy, int& ou, int& ov) {
     oy = (y - a.ys0) * pitch_y + (int)((ya32 + (unsigned)y * yp32) & 15u) + oyx;
+    if constexpr (ARR::kMacro) {                   // one staged row: U and V at their bytes of the macropixel (oyx holds luma's)
+      ou = oy - oyx + s.u_byte + ocx, ov = oy - oyx + s.v_byte + ocx;
+      return;
+    }
     const int cr = y >> sub.csy, crow = c_base + (cr - cr0) * CP * pitch_c;
     ou = crow + (int)((ua32 + (unsigned)cr * cp32) & 15u) + s.u_byte + ocx;
     ov = crow + (CP - 1) * pitch_c + (int)((va32 + (unsigned)cr * cp32) & 15u) + s.v_byte + ocx;
@@ -240,7 +247,8 @@ __device__ __forceinline__ void ar_tile_yuv(unsigned char* lds, const ArLaunch& 
     float tot[3] = {0.f, 0.f, 0.f};
     for (int cx = wx0; cx < wx1; ++cx) {
       float cs[3] = {0.f, 0.f, 0.f};               // the column sums of the converted, clamped taps, rows ascending
-      const int oyx = (cx - a.xs0) * SB, ocx = ((cx >> sub.csx) - cc0) * CB;
+      const int ocx = ((cx >> sub.csx) - cc0) * CB;
+      const int oyx = ARR::kMacro ? rs_macro_y_byte<SB>(s.u_byte) + (cx - 2 * cc0) * 2 * SB : (cx - a.xs0) * SB;
       for (int cy = wy0; cy < wy1; cy += 2) {      // two rows per call: yuv_tap2's packed pair
         const bool two = cy + 1 < wy1;
         int y0, u0, v0, y1, u1, v1;

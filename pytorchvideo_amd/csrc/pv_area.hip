@@ -137,6 +137,7 @@ int ar_run(const pv_batch_views_desc& d, bool frames, const CheckSrc& check_src,
   if (int e = ar_size(d, records, g, lds)) return e;
   if (rs_packed_px(d.src_layout)) return pv_packed_area(d, frames, g, lds, stream);   // pv_packed.hip
   if (rs_yuv4(d.src_layout)) return pv_yuv4_area(d, frames, g, lds, stream);           // pv_yuv4.hip
+  if (rs_yuyv(d.src_layout)) return pv_yuyv_area(d, frames, g, lds, stream);           // pv_yuyv.hip
   const int fr = frames ? 1 : 0;
   RS_SOURCE_FORMS(AR_RGB, AR_YUV);
   PV_LAUNCH_CHECK();

@@ -75,6 +75,7 @@ int bv_run(const pv_batch_views_desc& desc, pv_stream_t stream) {
   auto upright = [&](const pv_batch_views_desc& d) -> int {
     if (rs_packed_px(d.src_layout)) return pv_packed_strips(d, false, g, lds, stream);   // pv_packed.hip
     if (rs_yuv4(d.src_layout)) return pv_yuv4_strips(d, false, g, lds, stream);           // pv_yuv4.hip
+    if (rs_yuyv(d.src_layout)) return pv_yuyv_strips(d, false, g, lds, stream);           // pv_yuyv.hip
     RS_SOURCE_FORMS(BV_RGB, BV_YUV);
     PV_LAUNCH_CHECK();
     return PV_OK;

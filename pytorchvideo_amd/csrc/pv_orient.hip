@@ -86,6 +86,7 @@ int pv_orient_launch(const pv_batch_views_desc& d, bool frames, const RsTileLaun
   if (g.TR <= 0 || g.TC <= 0 || g.tiles_x <= 0) return PV_ERR_INVALID;   // not sized: no oriented item was announced
   if (rs_packed_px(d.src_layout)) return pv_packed_tiles(d, frames, g, lds, stream);   // pv_packed.hip
   if (rs_yuv4(d.src_layout)) return pv_yuv4_tiles(d, frames, g, lds, stream);           // pv_yuv4.hip
+  if (rs_yuyv(d.src_layout)) return pv_yuyv_tiles(d, frames, g, lds, stream);           // pv_yuyv.hip
   RS_SOURCE_FORMS(OV_RGB, OV_YUV);
   PV_LAUNCH_CHECK();
   return PV_OK;

@@ -107,6 +107,7 @@ int rg_run(const pv_region_views_desc& r, bool frames, const CheckSrc& check_src
   if (int e = rs_strip_size(d, span, span_c, g, lds)) return e;
   if (rs_packed_px(d.src_layout)) return pv_packed_regions(d, frames, g, lds, r.regions_dev, stream);   // pv_packed.hip
   if (rs_yuv4(d.src_layout)) return pv_yuv4_regions(d, frames, g, lds, r.regions_dev, stream);           // pv_yuv4.hip
+  if (rs_yuyv(d.src_layout)) return pv_yuyv_regions(d, frames, g, lds, r.regions_dev, stream);           // pv_yuyv.hip
   const int fr = frames ? 1 : 0;
   const pv_view_region* regions = r.regions_dev;
   RS_SOURCE_FORMS(RG_RGB, RG_YUV);

@@ -13,6 +13,8 @@
 //                                       packed-pixel launches (PV_SRC_BGR .. PV_SRC_ABGR): the RGB bodies with RsPacked<PB>
 //   pv_yuv4.hip       (launched from the same five)       the kernels of YUV 4:2:2 / 4:4:4 launches (PV_SRC_YUV422, PV_SRC_YUV444):
 //                                       the YUV bodies with the chroma shifts as a kernel argument (RsSub)
+//   pv_yuyv.hip       (launched from the same five)       the kernels of packed YUV 4:2:2 launches (PV_SRC_YUYV422): the YUV bodies
+//                                       with the macropixel arrangement (RsMacro)
 // What they compute with is here, once: the pinned source coordinate, the destination forms with their stores, the taps and
 // blends, the two staged-strip bodies (rs_strip_rgb, rs_strip_yuv: stage, barrier, gather) and the two staged-tile bodies of
 // oriented records (rs_tile_rgb, rs_tile_yuv), the launch arithmetic (widest span, rows per strip, the LDS layout of a staged
@@ -72,6 +74,12 @@ int pv_packed_regions(const pv_batch_views_desc& d, bool frames, const RsItemLau
 int pv_yuv4_strips(const pv_batch_views_desc& d, bool frames, const RsItemLaunch& g, size_t lds, pv_stream_t stream);
 int pv_yuv4_tiles(const pv_batch_views_desc& d, bool frames, const RsTileLaunch& g, size_t lds, pv_stream_t stream);
 int pv_yuv4_regions(const pv_batch_views_desc& d, bool frames, const RsItemLaunch& g, size_t lds, const pv_view_region* regions,
+                    pv_stream_t stream);
+
+// The kernels of packed YUV 4:2:2 launches (pv_yuyv.hip: src_layout PV_SRC_YUYV422), likewise.
+int pv_yuyv_strips(const pv_batch_views_desc& d, bool frames, const RsItemLaunch& g, size_t lds, pv_stream_t stream);
+int pv_yuyv_tiles(const pv_batch_views_desc& d, bool frames, const RsTileLaunch& g, size_t lds, pv_stream_t stream);
+int pv_yuyv_regions(const pv_batch_views_desc& d, bool frames, const RsItemLaunch& g, size_t lds, const pv_view_region* regions,
                     pv_stream_t stream);
 
 namespace {
@@ -506,12 +514,33 @@ struct RsSub420 { static constexpr int csy = 1, csx = 1; };
 struct RsSub { int32_t csy, csx; };
 // The shifts of a YUV src_layout; false: not a YUV layout.
 inline bool rs_yuv_sub(int src_layout, RsSub* c = nullptr) {
-  const bool yuv = src_layout == PV_SRC_YUV420 || src_layout == PV_SRC_YUV422 || src_layout == PV_SRC_YUV444;
+  const bool yuv = src_layout == PV_SRC_YUV420 || src_layout == PV_SRC_YUV422 || src_layout == PV_SRC_YUV444 ||
+                   src_layout == PV_SRC_YUYV422;   // packed 4:2:2 subsamples as PV_SRC_YUV422 does
   if (yuv && c) *c = RsSub{src_layout == PV_SRC_YUV420 ? 1 : 0, src_layout == PV_SRC_YUV444 ? 0 : 1};
   return yuv;
 }
 // The layouts whose kernels are in pv_yuv4.hip.
 inline bool rs_yuv4(int src_layout) { return src_layout == PV_SRC_YUV422 || src_layout == PV_SRC_YUV444; }
+
+// The sample arrangement of a YUV launch, the last template parameter of the YUV bodies.  RsPlanes, the default, is a luma
+// image and a chroma image behind it (every layout but one) and leaves each of those kernels with the instructions it had.
+// RsMacro is PACKED 4:2:2 (PV_SRC_YUYV422; include/pv_mi355x.h, "packed YUV 4:2:2"; the kernels are in pv_yuyv.hip): ONE plane
+// whose row is Ws / 2 macropixels of four samples -- two luma, one U, one V, in the record's order -- so a source row is staged
+// once and serves as both images.  What changes in a body, and nothing else:
+//   the staged span of a row is that of the macropixels [xs0 >> 1, xs1 >> 1], CB = 4 SB bytes each (CSTEP is 4), at pitch_y;
+//   no chroma row is staged: pitch_c and c_base are unused;
+//   luma column i is at y_byte + (i - x_first) * 2 SB of its staged row, x_first = xs0 & ~1 the column the span starts at,
+//   and its U / V sample at u_byte / v_byte + ((i >> 1) - (x_first >> 1)) * CB of THE SAME row.
+// u_byte / v_byte are the record's offsets inside a macropixel (RsYuvSrc; c_off_a = c_off_b = 0) and luma takes the other two
+// samples: y_byte is 0 where U and V are the odd samples (YUY2, YVYU) and SB where they are the even ones (UYVY, VYUY).  The
+// subsampling is the constant pair RsSub422.  (A static constant, as RsSub420's: see there.)
+struct RsPlanes { static constexpr bool kMacro = false; };
+struct RsMacro { static constexpr bool kMacro = true; };
+struct RsSub422 { static constexpr int csy = 0, csx = 1; };
+// The layout whose kernels are in pv_yuyv.hip.
+inline bool rs_yuyv(int src_layout) { return src_layout == PV_SRC_YUYV422; }
+// Byte of the first luma sample of a macropixel whose U sample is at u_byte.
+template <int SB> __host__ __device__ __forceinline__ int rs_macro_y_byte(int u_byte) { return (u_byte & SB) ? 0 : SB; }
 
 // A YUV source: the planes of the selected frame.
 struct RsYuvSrc {
@@ -540,7 +569,9 @@ __host__ __device__ __forceinline__ void rs_chroma_planes(bool inter, int64_t u_
 // column; pitches and plane offsets are bytes in either case.  Two-byte samples need even source addresses (checked on the
 // host: rs_check_yuv16_even), which makes every 16-bit LDS read naturally aligned.  MAP: the tap map (RsTapNone: none).
 // SUB: the chroma subsampling (RsSub420, or RsSub for the 4:2:2 / 4:4:4 kernels of pv_yuv4.hip; deduced from the last argument).
-template <int CSTEP, int FORM, typename D, typename SMP = unsigned char, typename MAP = RsTapNone, typename SUB = RsSub420>
+// ARR: the sample arrangement (RsPlanes, or RsMacro for the packed 4:2:2 kernels of pv_yuyv.hip, with CSTEP 4 and RsSub422).
+template <int CSTEP, int FORM, typename D, typename SMP = unsigned char, typename MAP = RsTapNone, typename SUB = RsSub420,
+          typename ARR = RsPlanes>
 __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitch_y, int pitch_c, int c_base, const RsYuvSrc& s,
                                              const RsDst& d, const float* yuv2rgb, int zi, int t, bool check_span,
                                              const MAP& map = MAP(), const SUB& sub = SUB()) {
@@ -561,13 +592,14 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
   const bool dense = ylast - ybase + 1 <= 2 * R;   // the strip's source rows fit the 2R slots as one contiguous run
   const int nslots = dense ? ylast - ybase + 1 : 2 * nrows;
   const int cxs0 = xs0 >> sub.csx, cybase = ybase >> sub.csy;
-  const int ncslots = dense ? (ylast >> sub.csy) - cybase + 1 : 2 * nrows;   // dense: <= R + 1 (4:2:0), <= 2R (full-height chroma)
-  const int span_y = (xs1 - xs0 + 1) * SB;
+  const int ncslots = ARR::kMacro ? 0 : (dense ? (ylast >> sub.csy) - cybase + 1 : 2 * nrows);   // dense: <= R + 1 (4:2:0), <= 2R (full-height chroma)
+  const int span_y = ARR::kMacro ? ((xs1 >> 1) - cxs0 + 1) * CB : (xs1 - xs0 + 1) * SB;   // macropixels: one staged row, the span of both
   const int span_c = ((xs1 >> sub.csx) - cxs0 + 1) * CB;
-  if (check_span && (span_y + 15 > pitch_y || span_c + 15 > pitch_c)) return;
+  if (check_span && (span_y + 15 > pitch_y || (!ARR::kMacro && span_c + 15 > pitch_c))) return;
 
   const uintptr_t frame = s.src + s.frame_off;
-  auto y_addr = [&](int y) -> uintptr_t { return frame + (long)y * s.y_pitch + xs0 * SB; };
+  // the first staged byte of source row y: luma column xs0, or the macropixel that holds it
+  auto y_addr = [&](int y) -> uintptr_t { return frame + (long)y * s.y_pitch + (ARR::kMacro ? cxs0 * CB : xs0 * SB); };
   auto c_addr = [&](int cy, int pl) -> uintptr_t {
     return frame + (pl == 0 ? s.c_off_a : s.c_off_b) + (long)cy * s.c_pitch + (long)cxs0 * CB;
   };
@@ -584,7 +616,7 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
       const int idx = base + u * kRsThreads;
       off[u] = -1;
       if (idx < total) {
-        const bool luma = idx < total_y;
+        const bool luma = ARR::kMacro || idx < total_y;
         const int j = luma ? idx : idx - total_y;
         const int cpr = luma ? cpr_y : cpr_c;
         const int sp = j / cpr, ch = j - sp * cpr;             // luma: sp = slot; chroma: sp = slot * CP + plane
@@ -630,11 +662,17 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
     const int s0 = dense ? i0y - ybase : 2 * r, s1 = dense ? i1y - ybase : 2 * r + 1;
     const int cs0 = dense ? (i0y >> sub.csy) - cybase : 2 * r, cs1 = dense ? (i1y >> sub.csy) - cybase : 2 * r + 1;
     // LDS byte offset of column xs0 (luma) / cxs0 (U, V) in the two source rows
-    const int yo0 = s0 * pitch_y + (int)(y_addr(i0y) & 15), yo1 = s1 * pitch_y + (int)(y_addr(i1y) & 15);
-    const int uo0 = c_base + cs0 * CP * pitch_c + (int)(c_addr(i0y >> sub.csy, 0) & 15) + s.u_byte;
-    const int uo1 = c_base + cs1 * CP * pitch_c + (int)(c_addr(i1y >> sub.csy, 0) & 15) + s.u_byte;
-    const int vo0 = c_base + (cs0 * CP + CP - 1) * pitch_c + (int)(c_addr(i0y >> sub.csy, CP - 1) & 15) + s.v_byte;
-    const int vo1 = c_base + (cs1 * CP + CP - 1) * pitch_c + (int)(c_addr(i1y >> sub.csy, CP - 1) & 15) + s.v_byte;
+    int yo0 = s0 * pitch_y + (int)(y_addr(i0y) & 15), yo1 = s1 * pitch_y + (int)(y_addr(i1y) & 15);
+    int uo0, uo1, vo0, vo1;
+    if constexpr (ARR::kMacro) {                   // the staged row is the chroma row: U, V and luma at their bytes of a macropixel
+      uo0 = yo0 + s.u_byte, uo1 = yo1 + s.u_byte, vo0 = yo0 + s.v_byte, vo1 = yo1 + s.v_byte;
+      yo0 += rs_macro_y_byte<SB>(s.u_byte), yo1 += rs_macro_y_byte<SB>(s.u_byte);
+    } else {
+      uo0 = c_base + cs0 * CP * pitch_c + (int)(c_addr(i0y >> sub.csy, 0) & 15) + s.u_byte;
+      uo1 = c_base + cs1 * CP * pitch_c + (int)(c_addr(i1y >> sub.csy, 0) & 15) + s.u_byte;
+      vo0 = c_base + (cs0 * CP + CP - 1) * pitch_c + (int)(c_addr(i0y >> sub.csy, CP - 1) & 15) + s.v_byte;
+      vo1 = c_base + (cs1 * CP + CP - 1) * pitch_c + (int)(c_addr(i1y >> sub.csy, CP - 1) & 15) + s.v_byte;
+    }
     float out[4][G];
 #pragma unroll
     for (int j = 0; j < G; ++j) {
@@ -643,7 +681,8 @@ __device__ __forceinline__ void rs_strip_yuv(unsigned char* lds, int R, int pitc
       float lx1;
       rs_coord(s.sx, s.xoff + x, s.Ws, i0x, i1x, lx1);
       const float lx0 = 1.f - lx1;
-      const int o0 = (i0x - xs0) * SB, o1 = (i1x - xs0) * SB;
+      const int o0 = ARR::kMacro ? (i0x - 2 * cxs0) * 2 * SB : (i0x - xs0) * SB;   // macropixels: luma columns are 2 SB apart
+      const int o1 = ARR::kMacro ? (i1x - 2 * cxs0) * 2 * SB : (i1x - xs0) * SB;
       const int c0 = ((i0x >> sub.csx) - cxs0) * CB, c1 = ((i1x >> sub.csx) - cxs0) * CB;
       f32x2 p0[3], p1[3];                          // {row i0y, row i1y} of column i0x / i1x, per channel
       yuv_tap2<SMP, MAP>(m, lds, yo0 + o0, uo0 + c0, vo0 + c0, yo1 + o0, uo1 + c0, vo1 + c0, p0, map);
@@ -836,7 +875,8 @@ __device__ __forceinline__ void rs_tile_rgb(unsigned char* lds, const RsTileLaun
 }
 
 // CSTEP / FORM / D / SMP / MAP / SUB: as rs_strip_yuv.  The shifts apply to STORED rows and columns.
-template <int CSTEP, int FORM, typename D, typename SMP, typename MAP = RsTapNone, typename SUB = RsSub420>
+// ARR: as rs_strip_yuv; the staged rectangle's rows then span the macropixels [sc0 >> 1, sc1 >> 1].
+template <int CSTEP, int FORM, typename D, typename SMP, typename MAP = RsTapNone, typename SUB = RsSub420, typename ARR = RsPlanes>
 __device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaunch& g, const RsYuvSrc& s, int orient, const RsDst& d,
                                             const float* yuv2rgb, int zi, int t, const MAP& map = MAP(), const SUB& sub = SUB()) {
   constexpr int G = RsGroup<FORM, D>::G;
@@ -857,13 +897,14 @@ __device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaun
   rs_tile_range(s.sx, s.xoff + col0, ncols, Wd, dx0, dx1);
   rs_tile_rect(o, dy0, dy1, dx0, dx1, s.Hs, s.Ws, sr0, sr1, sc0, sc1);
   const int cr0 = sr0 >> sub.csy, cc0 = sc0 >> sub.csx;
-  const int nslots = sr1 - sr0 + 1, ncslots = (sr1 >> sub.csy) - cr0 + 1;
-  const int span_y = (sc1 - sc0 + 1) * SB;
+  const int nslots = sr1 - sr0 + 1, ncslots = ARR::kMacro ? 0 : (sr1 >> sub.csy) - cr0 + 1;
+  const int span_y = ARR::kMacro ? ((sc1 >> 1) - cc0 + 1) * CB : (sc1 - sc0 + 1) * SB;   // macropixels: one staged row, the span of both
   const int span_c = ((sc1 >> sub.csx) - cc0 + 1) * CB;
-  if (nslots > g.rows || ncslots > g.rows_c || span_y + 15 > pitch_y || span_c + 15 > pitch_c) return;
+  if (nslots > g.rows || ncslots > g.rows_c || span_y + 15 > pitch_y || (!ARR::kMacro && span_c + 15 > pitch_c)) return;
 
   const uintptr_t frame = s.src + s.frame_off;
-  auto y_addr = [&](int r) -> uintptr_t { return frame + (long)r * s.y_pitch + sc0 * SB; };
+  // the first staged byte of stored row r: luma column sc0, or the macropixel that holds it
+  auto y_addr = [&](int r) -> uintptr_t { return frame + (long)r * s.y_pitch + (ARR::kMacro ? cc0 * CB : sc0 * SB); };
   auto c_addr = [&](int cr, int pl) -> uintptr_t {
     return frame + (pl == 0 ? s.c_off_a : s.c_off_b) + (long)cr * s.c_pitch + (long)cc0 * CB;
   };
@@ -880,7 +921,7 @@ __device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaun
       const int idx = base + u * kRsThreads;
       off[u] = -1;
       if (idx < total) {
-        const bool luma = idx < total_y;
+        const bool luma = ARR::kMacro || idx < total_y;
         const int j = luma ? idx : idx - total_y;
         const int cpr = luma ? cpr_y : cpr_c;
         const int sp = j / cpr, ch = j - sp * cpr;             // luma: sp = slot; chroma: sp = slot * CP + plane
@@ -908,11 +949,17 @@ __device__ __forceinline__ void rs_tile_yuv(unsigned char* lds, const RsTileLaun
     sh[c] = (d.ch_scale && d.ch_shift) ? d.ch_shift[c] : 0.f;
   }
   // the low address bits of a staged row: 32-bit arithmetic keeps `addr & 15`
-  const unsigned ya32 = (unsigned)(frame + sc0 * SB), yp32 = (unsigned)s.y_pitch, cp32 = (unsigned)s.c_pitch;
+  const unsigned ya32 = (unsigned)(frame + (ARR::kMacro ? cc0 * CB : sc0 * SB)), yp32 = (unsigned)s.y_pitch, cp32 = (unsigned)s.c_pitch;
   const unsigned ua32 = (unsigned)(frame + s.c_off_a + (long)cc0 * CB), va32 = (unsigned)(frame + s.c_off_b + (long)cc0 * CB);
   // LDS byte offsets of the Y, U and V samples of the tap at displayed (iy, ix)
   auto tap = [&](int iy, int ix, int& oy, int& ou, int& ov) {
     const int r = rs_clampi(o.r0 + o.ry * iy + o.rx * ix, sr0, sr1), c = rs_clampi(o.c0 + o.cy * iy + o.cx * ix, sc0, sc1);
+    if constexpr (ARR::kMacro) {                   // one staged row: U, V and luma at their bytes of a macropixel
+      const int row = (r - sr0) * pitch_y + (int)((ya32 + (unsigned)r * yp32) & 15u), co = ((c >> 1) - cc0) * CB;
+      oy = row + rs_macro_y_byte<SB>(s.u_byte) + (c - 2 * cc0) * 2 * SB;
+      ou = row + s.u_byte + co, ov = row + s.v_byte + co;
+      return;
+    }
     oy = (r - sr0) * pitch_y + (int)((ya32 + (unsigned)r * yp32) & 15u) + (c - sc0) * SB;
     // (RsSub420 is named by its type here: the lambda then does not capture `sub`, which changed the 4:2:0 tile kernels)
     int cr, cq;                                    // the chroma row and column of the stored pixel
@@ -1078,8 +1125,13 @@ inline void rs_widest_span(float sx, const int32_t* x_off, int n_views, int Wo, 
 }
 
 // The LDS pitches of a staged luma row and a staged chroma (row, plane) for the widest spans (columns) of a launch whose
-// samples have `sb` bytes, and the LDS bytes of the two source rows of one output row with their chroma.
+// samples have `sb` bytes, and the LDS bytes of the two source rows of one output row with their chroma.  c_step 4 is the
+// macropixel arrangement (RsMacro), whose widest macropixel span is span_c.
 inline long rs_yuv_pitches(int span, int span_c, int c_step, int sb, int32_t& pitch_y, int32_t& pitch_c) {
+  if (c_step == 4) {                               // packed 4:2:2: one staged row of span_c macropixels, no chroma image
+    pitch_y = pv_round_up(span_c * 4 * sb + 15, 16), pitch_c = 0;
+    return 2L * pitch_y;
+  }
   pitch_y = pv_round_up(span * sb + 15, 16);
   pitch_c = pv_round_up(span_c * c_step * sb + 15, 16);
   return 2L * (pitch_y + (long)(c_step == 2 ? 1 : 2) * pitch_c);
@@ -1113,7 +1165,7 @@ template <typename Launch> inline long rs_tile_layout(const pv_batch_views_desc&
   if (rs_yuv_sub(d.src_layout)) {
     rs_yuv_pitches(n[1], n[3], d.c_step, d.src_dtype == PV_U16 ? 2 : 1, g.pitch, g.pitch_c);
     g.c_base = g.rows * g.pitch;
-    return (long)g.c_base + (long)g.rows_c * (d.c_step == 2 ? 1 : 2) * g.pitch_c;
+    return (long)g.c_base + (long)g.rows_c * (d.c_step == 2 ? 1 : 2) * g.pitch_c;   // packed 4:2:2: pitch_c is 0
   }
   g.pitch = rs_rgb_pitch(n[1], d.src_layout, d.src_dtype);
   return (long)g.rows * (rs_interleaved(d.src_layout) ? 1 : d.C) * g.pitch;
@@ -1205,9 +1257,21 @@ inline bool plane_inside(int64_t off, int64_t rows, int64_t pitch, int64_t cols,
 // The planes of one YUV frame of Hs x Ws (both positive) of sb-byte samples: a size the subsampling halves is even (4:2:0: both;
 // 4:2:2: Ws; 4:4:4: neither), the chroma form (c_step counts samples), pitches that hold a row, and luma and chroma planes --
 // Hs >> csy rows of Ws >> csx samples -- inside [0, frame_stride).  Pitches, offsets and the frame stride are bytes.
+// c_step 4 is the ONE plane of packed 4:2:2 (the caller has matched it with the layout: rs_check_item_desc): rows of Ws / 2
+// macropixels of four samples at y_pitch, no chroma pitch, and u_offset / v_offset the bytes of U / V inside a macropixel --
+// two different samples of it that are both even or both odd, which leaves luma the other two.
 inline int rs_check_yuv_planes(int Hs, int Ws, int c_step, int y_pitch, int c_pitch, int64_t frame_stride, int64_t u_offset,
                                int64_t v_offset, int sb = 1, RsSub c = RsSub{1, 1}) {
   if (((c.csy ? Hs : 0) | (c.csx ? Ws : 0)) & 1) return PV_ERR_INVALID;
+  if (c_step == 4) {
+    if (c.csy != 0 || c.csx != 1 || c_pitch != 0) return PV_ERR_INVALID;
+    const int64_t row = 2 * (int64_t)Ws * sb;
+    if (y_pitch < row || frame_stride < (int64_t)(Hs - 1) * y_pitch + row) return PV_ERR_INVALID;
+    const int64_t du = u_offset - v_offset;
+    if (u_offset < 0 || v_offset < 0 || u_offset >= 4 * sb || v_offset >= 4 * sb || u_offset % sb || (du != 2 * sb && du != -2 * sb))
+      return PV_ERR_INVALID;
+    return PV_OK;
+  }
   if (c_step != 1 && c_step != 2) return PV_ERR_INVALID;
   const int Hc = Hs >> c.csy, Wc = Ws >> c.csx;
   if (y_pitch < (int64_t)Ws * sb || c_pitch < (int64_t)Wc * c_step * sb || frame_stride <= 0) return PV_ERR_INVALID;
@@ -1333,7 +1397,7 @@ inline int rs_check_item_desc(const pv_batch_views_desc& d) {
   if (!yuv && !inter && d.src_layout != PV_SRC_NCTHW) return PV_ERR_INVALID;
   if (!yuv && d.src_dtype == PV_U16) return PV_ERR_UNSUPPORTED;   // 16-bit samples are a YUV source only
   if (inter && (d.src_dtype != PV_U8 || d.C != 3)) return PV_ERR_INVALID;
-  if (yuv && (!d.yuv2rgb || d.C != 3 || (d.c_step != 1 && d.c_step != 2))) return PV_ERR_INVALID;
+  if (yuv && (!d.yuv2rgb || d.C != 3 || (rs_yuyv(d.src_layout) ? d.c_step != 4 : (d.c_step != 1 && d.c_step != 2)))) return PV_ERR_INVALID;
   // the dtype / layout matrix
   if (yuv ? (d.src_dtype != PV_U8 && d.src_dtype != PV_U16) : (d.src_dtype != PV_U8 && d.src_dtype != PV_F32)) return PV_ERR_UNSUPPORTED;
   return rs_check_dst(d.dst, d.dst_layout, d.dst_dtype, d.c_p, d.ld, d.bs, d.T, d.Ho, d.Wo);

@@ -88,8 +88,8 @@ class VideoPredictor:
         # HDR taps, the box filter and packed pixels: pv_hdr_views / pv_area_views / pv_batch_views, item-sourced launches
         if isinstance(video, FrameList) or orientation or p.hdr is not None or p.area or p.item_only:
             return self._call_frames(video, fps, return_clip_scores, orientation)
-        if video.dim() != (3 if p.is_yuv else 4):
-            raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(video.shape)))
+        if video.dim() != p.video_dims:
+            raise RuntimeError("expected one %d-d %s video, got %s" % (p.video_dims, self.src_layout, tuple(video.shape)))
         num_frames = video.shape[1] if self.src_layout == "NCTHW" else video.shape[0]
         table, _ = clip_frame_table(self.sampler, num_frames, fps, p.clip_frames)
         tables = p.video_tables(table, num_frames)               # the one upload
@@ -123,8 +123,8 @@ class VideoPredictor:
         if isinstance(frames, FrameList):
             num_frames = len(frames)
         else:
-            if frames.dim() != (3 if p.is_yuv else 4):
-                raise RuntimeError("expected one %d-d %s video, got %s" % (3 if p.is_yuv else 4, self.src_layout, tuple(frames.shape)))
+            if frames.dim() != p.video_dims:
+                raise RuntimeError("expected one %d-d %s video, got %s" % (p.video_dims, self.src_layout, tuple(frames.shape)))
             num_frames = frames.shape[1] if self.src_layout == "NCTHW" else frames.shape[0]
             frames = _resident(frames, device, p.in_place)
         table, _ = clip_frame_table(self.sampler, num_frames, fps, p.clip_frames)
@@ -181,7 +181,7 @@ class VideoBatchPredictor:
         rates = list(fps) if isinstance(fps, (list, tuple)) else [fps] * len(videos)
         if len(rates) != len(videos):
             raise ValueError("fps is one number or one per video: %d for %d videos" % (len(rates), len(videos)))
-        dims = 3 if p.is_yuv else 4
+        dims = p.video_dims
         tables = []
         for j, (video, rate) in enumerate(zip(videos, rates)):
             if isinstance(video, FrameList):                     # its frames are checked by video_batch
@@ -289,7 +289,7 @@ class KeyframeDetector:
         if not videos or not (len(stamps) == len(box_lists) == len(rates) == len(videos)):
             raise ValueError("timestamps, boxes and fps are given per video: %d, %d and %d for %d videos"
                              % (len(stamps), len(box_lists), len(rates), len(videos)))
-        dims = 3 if p.is_yuv else 4
+        dims = p.video_dims
 
         def per_video(x):
             return list(x) if isinstance(x, (list, tuple)) else [x] * len(videos)
@@ -406,7 +406,7 @@ class TubePredictor:
         heights, coded = per_video(p.height if height is None else height), per_video(p.coded_height if coded_height is None else coded_height)
         if not (len(heights) == len(coded) == len(videos)):
             raise ValueError("height and coded_height are one value or one per video")
-        dims = 3 if p.is_yuv else 4
+        dims = p.video_dims
         kept, tables, regions = [], [], []
         for j, (vid, rate, ts, tl) in enumerate(zip(videos, rates, stamps, tube_lists)):
             as_frames = isinstance(vid, FrameList)               # its frames are checked by video_batch, and never moved

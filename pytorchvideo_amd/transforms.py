@@ -480,32 +480,58 @@ YUV16_LAYOUTS = ("P010", "P012", "P016", "I010", "I012", "I016")
 # reads them -- PV_SRC_YUV444 with c_step 2.)
 YUV422_LAYOUTS = ("I422", "YV16", "NV16", "NV61", "P210", "P212", "P216", "I210", "I212", "I216")
 YUV444_LAYOUTS = ("I444", "YV24", "I410", "I412", "I416")
-_YUV4_ANY = YUV422_LAYOUTS + YUV444_LAYOUTS
+# Packed YUV 4:2:2 (include/pv_mi355x.h, "packed YUV 4:2:2"), read by the item-sourced entry points only: ONE plane of
+# macropixels of four samples, frames [N, H, W, 2] (`yuyv_geometry`).  YUY2 ("YUYV" is an alias): Y0 U Y1 V, what UVC webcams
+# and V4L2 hand out; YVYU: Y0 V Y1 U; UYVY: U Y0 V Y1, what SDI / HDMI capture cards hand out; Y210 / Y212 / Y216: YUY2's
+# order with 16-bit samples, the value in the HIGH bits.  (VYUY has no string: the C ABI reads it.)
+YUYV_LAYOUTS = ("YUY2", "YVYU", "UYVY", "Y210", "Y212", "Y216")
+_YUYV_ALIASES = {"YUYV": "YUY2"}
+_YUYV_ANY = YUYV_LAYOUTS + tuple(_YUYV_ALIASES)
+_YUYV_UV = {"YUY2": (1, 3), "YVYU": (3, 1), "UYVY": (0, 2), "Y210": (1, 3), "Y212": (1, 3), "Y216": (1, 3)}   # the samples of U, V
+_YUV4_ANY = YUV422_LAYOUTS + YUV444_LAYOUTS + _YUYV_ANY    # the YUV layouts of the item-sourced entry points only
 _YUV_ANY = YUV_LAYOUTS + YUV16_LAYOUTS + _YUV4_ANY
 _YUV_INTERLEAVED = ("NV12", "NV21", "P010", "P012", "P016", "NV16", "NV61", "P210", "P212", "P216")
 _YUV_V_FIRST = ("NV21", "YV12", "YV16", "NV61", "YV24")
 _YUV_PLANE_FIELDS = ("frame_stride", "u_offset", "v_offset", "y_pitch", "c_pitch")   # of `yuv_geometry`, a descriptor, a record
 _SRC_LAYOUTS = ("NCTHW", "NTHWC") + _YUV_ANY + _PACKED_ANY      # every `src_layout` the device ingest takes
 _LAYOUT_ERROR = ("src_layout is 'NCTHW', 'NTHWC' or one of %s" % (YUV_LAYOUTS,) + " or %s" % (YUV16_LAYOUTS,)
-                 + " or %s" % (YUV422_LAYOUTS,) + " or %s" % (YUV444_LAYOUTS,) + " or %s" % (PACKED_LAYOUTS,))
+                 + " or %s" % (YUV422_LAYOUTS,) + " or %s" % (YUV444_LAYOUTS,) + " or %s" % (PACKED_LAYOUTS,)
+                 + " or %s" % (YUYV_LAYOUTS,))
 _YUV16_DEPTH = {"P010": (10, True), "P012": (12, True), "P016": (16, True), "I010": (10, False), "I012": (12, False),
                 "I016": (16, False),                       # layout -> (bit depth, MSB-aligned)
                 "P210": (10, True), "P212": (12, True), "P216": (16, True), "I210": (10, False), "I212": (12, False),
-                "I216": (16, False), "I410": (10, False), "I412": (12, False), "I416": (16, False)}
+                "I216": (16, False), "I410": (10, False), "I412": (12, False), "I416": (16, False),
+                "Y210": (10, True), "Y212": (12, True), "Y216": (16, True)}
 _YUV_WIDE = tuple(_YUV16_DEPTH)                            # every layout of 16-bit samples (PV_U16)
+
+
+def _yuyv_name(layout):
+    """The layout of `YUYV_LAYOUTS` behind a packed 4:2:2 `src_layout` string ("YUYV" is "YUY2"), else None."""
+    layout = _YUYV_ALIASES.get(layout, layout) if isinstance(layout, str) else None
+    return layout if layout in YUYV_LAYOUTS else None
 
 
 def _yuv_sub(layout):
     """(csy, csx) of a YUV layout: the chroma sample of luma pixel (y, x) is (y >> csy, x >> csx)."""
-    return (0, 1) if layout in YUV422_LAYOUTS else (0, 0) if layout in YUV444_LAYOUTS else (1, 1)
+    return (0, 1) if layout in YUV422_LAYOUTS or layout in _YUYV_ANY else (0, 0) if layout in YUV444_LAYOUTS else (1, 1)
+
+
+def _yuv_c_step(layout):
+    """`c_step` of a YUV layout: the samples between x-adjacent samples of one chroma component."""
+    return 4 if layout in _YUYV_ANY else 2 if layout in _YUV_INTERLEAVED else 1
+
+
+def _yuv_dims(layout):
+    """The dimensions of ONE FRAME of a YUV layout: 2 ([rows, W]), or 3 for packed 4:2:2 ([H, W, 2])."""
+    return 3 if layout in _YUYV_ANY else 2
 
 
 def region_evenness(src_layout):
     """The `even` of `box_regions` / of the rectangle check for a source layout: True (YUV 4:2:0: all four members even),
-    "width" (YUV 4:2:2: left and w) or False (everything else, YUV 4:4:4 included)."""
+    "width" (YUV 4:2:2, planar or packed: left and w) or False (everything else, YUV 4:4:4 included)."""
     if src_layout not in _YUV_ANY or src_layout in YUV444_LAYOUTS:
         return False
-    return "width" if src_layout in YUV422_LAYOUTS else True
+    return "width" if src_layout in YUV422_LAYOUTS or src_layout in _YUYV_ANY else True
 _YUV_KR_KB = {"bt709": (0.2126, 0.0722), "bt601": (0.299, 0.114)}
 _YUV_KR_KB_DEEP = {"bt2020": (0.2627, 0.0593)}             # Rec. 2020 defines 10- and 12-bit quantisation only: no 8-bit form
 
@@ -555,6 +581,65 @@ def _yuv_matrix_of(yuv, layout=None) -> torch.Tensor:
     return m
 
 
+def yuyv_geometry(frames: torch.Tensor, layout: str) -> dict:
+    """Where the samples of packed YUV 4:2:2 frames lie (`YUYV_LAYOUTS`; "YUYV" is "YUY2"): `frames` is [N, H, W, 2] (or
+    [H, W, 2]: one frame; what `cv2.VideoCapture` hands out with CAP_PROP_CONVERT_RGB = 0) -- uint8, or uint16 / int16 for Y210 /
+    Y212 / Y216 -- with an even W, stride(-1) == 1, stride(-2) == 2 and a row stride >= 2 * W, counted in ELEMENTS: a pitched
+    surface, or a column slice of a wider one that starts at an even column, is read where it lies; the frame stride may be
+    anything that keeps the frames apart.  Returns N, Hs, Ws, the subsampling (csy, csx) = (0, 1), c_step 4 and the record's
+    fields in BYTES: y_pitch (the row stride), frame_stride (between frames; one frame: its extent), c_pitch 0 and u_offset /
+    v_offset, the byte of the first U / V sample from the start of a row.  ValueError, naming the stride, for anything else: no
+    copy is ever made."""
+    name = _yuyv_name(layout)
+    if name is None:
+        raise ValueError("a packed YUV 4:2:2 layout is one of %s, got %r" % (YUYV_LAYOUTS, layout))
+    wide = name in _YUV_WIDE
+    if frames.dim() == 3:
+        frames = frames[None]
+    if frames.dim() != 4 or frames.shape[-1] != 2 or (frames.dtype not in (torch.uint16, torch.int16) if wide else frames.dtype != torch.uint8):
+        raise ValueError("%s frames are %s [N, H, W, 2], got %s %s" % (name, "uint16 or int16" if wide else "uint8", frames.dtype, tuple(frames.shape)))
+    n, h, w, _ = frames.shape
+    if n == 0 or h == 0 or w == 0 or w % 2:
+        raise ValueError("%s frames: a row is W / 2 macropixels of two pixels, W is even and positive; got %d frames of %d x %d" % (name, n, h, w))
+    if frames.stride(3) != 1:
+        raise ValueError("%s frames: stride(-1) is %d, not 1: the two samples of a pixel are adjacent" % (name, frames.stride(3)))
+    if frames.stride(2) != 2:
+        raise ValueError("%s frames: stride(-2) is %d, not 2: the pixels of a row are adjacent" % (name, frames.stride(2)))
+    pitch = frames.stride(1) if h > 1 else max(frames.stride(1), 2 * w)
+    if pitch < 2 * w:
+        raise ValueError("%s frames: the row stride, stride(-3), is %d, less than the %d samples of a row" % (name, pitch, 2 * w))
+    extent = (h - 1) * pitch + 2 * w
+    frame_stride = frames.stride(0) if n > 1 else extent
+    if frame_stride < extent:
+        raise ValueError("%s frames: the frame stride, stride(0), is %d, less than the %d samples of a frame" % (name, frame_stride, extent))
+    sb = 2 if wide else 1                                   # elements -> bytes
+    u, v = _YUYV_UV[name]
+    return dict(N=n, Hs=h, Ws=w, Hc=h, frame_stride=frame_stride * sb, y_pitch=pitch * sb, c_pitch=0, c_step=4,
+                u_offset=u * sb, v_offset=v * sb, csy=0, csx=1)
+
+
+def yuyv_to_planar(frames: torch.Tensor, layout: str) -> torch.Tensor:
+    """The host mirror of the packed 4:2:2 layouts, by a pure index (no arithmetic): [N, H, W, 2] (or [H, W, 2]) frames in
+    `layout` -> the contiguous I422-arranged copy [N, 2H, W] (or [2H, W]) of the same dtype -- H rows of luma, then H rows of U
+    and H rows of V at half the pitch, which is "I422" for uint8 and "I216" for 16-bit samples (the codes are not touched, so
+    the matrix of the packed layout goes with it).  The ingest holds, bit for bit, what it writes for that copy."""
+    name = _yuyv_name(layout)
+    if name is None:
+        raise ValueError("a packed YUV 4:2:2 layout is one of %s, got %r" % (YUYV_LAYOUTS, layout))
+    g = yuyv_geometry(frames, name)
+    one = frames.dim() == 3
+    x = frames[None] if one else frames
+    if frames.dtype == torch.uint16:
+        x = x.view(torch.int16)                             # the same bits, in the type every operator has
+    h, w = g["Hs"], g["Ws"]
+    u, v = _YUYV_UV[name]
+    flat = x.reshape(x.shape[0], h, w // 2, 4)             # a row as macropixels of four samples
+    luma = flat[..., [1 - (u & 1), 3 - (u & 1)]].reshape(-1, h, w)
+    chroma = [flat[..., k].reshape(-1, h * (w // 2)) for k in (u, v)]                        # H rows of W / 2 samples each
+    planar = torch.cat([luma.reshape(-1, h * w)] + chroma, dim=1).reshape(-1, 2 * h, w).view(frames.dtype)
+    return planar[0] if one else planar
+
+
 def yuv_geometry(frames: torch.Tensor, layout: str, coded_height=None, height=None) -> dict:
     """Where the samples of YUV frames are, in bytes, read off the tensor's shape and strides (nothing is copied).
 
@@ -575,10 +660,27 @@ def yuv_geometry(frames: torch.Tensor, layout: str, coded_height=None, height=No
     The layouts of 16-bit samples -- `YUV16_LAYOUTS` (P010 / P012 / P016: NV12's arrangement; I010 / I012 / I016: I420's,
     yuv420p10le), P210 / I210 / I410 and their 12- and 16-bit kin -- take torch.uint16 or torch.int16 (the same bits; decoder
     bindings differ) with the same shape and stride rules IN ELEMENTS, and the returned frame_stride, pitches and offsets are
-    BYTES, as the descriptors take them (c_step stays 2 / 1: samples)."""
+    BYTES, as the descriptors take them (c_step stays 2 / 1: samples).
+
+    Packed 4:2:2 (`YUYV_LAYOUTS`): frames [N, H, W, 2], [B, T, H, W, 2] or [H, W, 2] -- `yuyv_geometry`, whose result this is
+    (c_step 4); there is no coded height beside the shape's, so `coded_height` and `height`, when given, are H."""
+    if layout in _YUYV_ANY:
+        lead = tuple(frames.shape[:2]) if frames.dim() == 5 else None
+        if lead is not None:                                # clips: one sequence of B * T frames, as below
+            if lead[0] > 1 and lead[1] > 1 and frames.stride(0) != lead[1] * frames.stride(1):
+                raise RuntimeError("clips [B, T, ...] are one sequence of B * T frames: stride(0) == T * stride(1); got %s" % (frames.stride(),))
+            seq = frames[0] if lead[0] == 1 else frames[:, 0] if lead[1] == 1 else frames.as_strided(
+                (lead[0] * lead[1],) + tuple(frames.shape[2:]), frames.stride()[1:])
+            g = yuyv_geometry(seq, layout)
+        else:
+            g = yuyv_geometry(frames, layout)
+        for what, given in (("coded_height", coded_height), ("height", height)):
+            if given is not None and int(given) != g["Hs"]:
+                raise RuntimeError("%s %d, but %s frames have the %d rows of their shape" % (what, given, layout, g["Hs"]))
+        return g
     if layout not in _YUV_ANY:
         raise ValueError("a YUV layout is one of %s, got %r" % (YUV_LAYOUTS, layout) + " (16-bit samples: %s;" % (YUV16_LAYOUTS,)
-                         + " 4:2:2: %s; 4:4:4: %s)" % (YUV422_LAYOUTS, YUV444_LAYOUTS))
+                         + " 4:2:2: %s; 4:4:4: %s; packed 4:2:2: %s)" % (YUV422_LAYOUTS, YUV444_LAYOUTS, YUYV_LAYOUTS))
     wide = layout in _YUV_WIDE
     csy, csx = _yuv_sub(layout)
     num, den = {(1, 1): (3, 2), (0, 1): (2, 1), (0, 0): (3, 1)}[(csy, csx)]     # tensor rows per coded luma row
@@ -632,7 +734,13 @@ def yuv_to_rgb(frames: torch.Tensor, layout: str, matrix, coded_height=None, hei
     rounded to an integer -- chroma is replicated over the luma pixels it covers: 2 x 2 for 4:2:0, 1 x 2 for 4:2:2, none
     for 4:4:4.  `frames`, `layout`, `coded_height` and `height` as in `yuv_geometry`; `matrix` is a 3 x 4 matrix
     (`yuv_matrix`).  The conversion runs in fp64 and is rounded once to fp32.  16-bit codes are read UNSIGNED, whichever of
-    uint16 / int16 the tensor is."""
+    uint16 / int16 the tensor is.  A layout of `YUYV_LAYOUTS` (frames [..., H, W, 2]) gives what its `yuyv_to_planar` copy gives."""
+    if layout in _YUYV_ANY:
+        frames = frames.cpu() if frames.is_cuda else frames
+        lead = tuple(frames.shape[:-3])
+        planar = yuyv_to_planar(frames.reshape((-1,) + tuple(frames.shape[-3:])), layout)
+        rgb = yuv_to_rgb(planar, "I216" if layout in _YUV_WIDE else "I422", matrix, coded_height, height)
+        return rgb.reshape(lead + tuple(rgb.shape[-3:]))
     g = yuv_geometry(frames, layout, coded_height, height)
     m = torch.as_tensor(matrix, dtype=torch.float64).cpu()
     if tuple(m.shape) != (3, 4):
@@ -773,7 +881,8 @@ def _hdr_of(hdr, src_layout):
     if src_layout not in YUV16_LAYOUTS:
         raise ValueError("hdr= maps the taps of a 10- to 16-bit YUV 4:2:0 source (src_layout one of %s), not of %r%s"
                          % (YUV16_LAYOUTS, src_layout,
-                            ": pv_hdr_views does not read YUV 4:2:2 / 4:4:4" if src_layout in _YUV4_ANY else ""))
+                            ": pv_hdr_views does not read packed YUV 4:2:2" if src_layout in _YUYV_ANY
+                            else ": pv_hdr_views does not read YUV 4:2:2 / 4:4:4" if src_layout in _YUV4_ANY else ""))
     return code, tone
 
 
@@ -841,7 +950,8 @@ def _src_codes(src_layout, dtype):
     """(src_layout, src_dtype) as the descriptors code them; `dtype` is the tensors' and decides for RGB / planar sources."""
     from . import _lib as L
     if src_layout in _YUV_ANY:
-        code = L.SRC_YUV422 if src_layout in YUV422_LAYOUTS else L.SRC_YUV444 if src_layout in YUV444_LAYOUTS else L.SRC_YUV420
+        code = (L.SRC_YUV422 if src_layout in YUV422_LAYOUTS else L.SRC_YUV444 if src_layout in YUV444_LAYOUTS
+                else L.SRC_YUYV422 if src_layout in _YUYV_ANY else L.SRC_YUV420)
         return code, L.PV_U16 if src_layout in _YUV_WIDE else L.PV_U8
     if src_layout in _PACKED_ANY:
         return getattr(L, "SRC_" + _packed_name(src_layout)), L.PV_U8
@@ -995,7 +1105,9 @@ class FrameList:
     uint16 or int16) 2-d [Hc*3/2, W] with stride(1) == 1 and any row pitch P >= W (`yuv_geometry` of a one-frame view: the surface is the Hc*3/2 * P bytes from
     its first sample -- the half-pitch chroma rows of I420 / YV12 lie partly behind column W).  `src_layout`, when given,
     checks that form at construction; `video_batch` checks it in any case.  The packed layouts (`PACKED_LAYOUTS`): a uint8
-    [H, W, PB] with stride(-1) == 1, stride(-2) == PB and any row stride >= W * PB (`packed_geometry`).  A frame may be a view at any offset inside a
+    [H, W, PB] with stride(-1) == 1, stride(-2) == PB and any row stride >= W * PB (`packed_geometry`).  The packed 4:2:2 layouts
+    (`YUYV_LAYOUTS`): a uint8 (Y21x: uint16 or int16) [H, W, 2] with stride(-1) == 1, stride(-2) == 2 and any row stride >= 2 * W
+    (`yuyv_geometry`) -- what `cv2.VideoCapture.read()` returns with CAP_PROP_CONVERT_RGB = 0.  A frame may be a view at any offset inside a
     larger buffer and appear more than once, and the frames may have been allocated in any order.  The list keeps its
     tensors alive; `len()` is the frame count; `stack(src_layout)` is the contiguous video the frames make up."""
 
@@ -1025,6 +1137,12 @@ class FrameList:
         layouts (frame_stride: the extent of one frame) and None otherwise.  RuntimeError for a frame of another form."""
         f = self.frames[0]
         if src_layout in _YUV_ANY:
+            if src_layout in _YUYV_ANY:
+                if f.dim() != 3:
+                    raise RuntimeError("a %s frame is [H, W, 2] (uint8; Y210 / Y212 / Y216: uint16 or int16), got %s %s"
+                                       % (src_layout, f.dtype, tuple(f.shape)))
+                geom = yuyv_geometry(f, src_layout)
+                return 3, geom["Hs"], geom["Ws"], geom
             if f.dim() != 2:
                 raise RuntimeError("a %s frame is 2-d: uint8 [Hc*3/2, W] (4:2:2: [Hc*2, W], 4:4:4: [Hc*3, W]; 16-bit layouts: uint16 "
                                    "or int16), got %s %s" % (src_layout, f.dtype, tuple(f.shape)))
@@ -1209,8 +1327,8 @@ def build_video_batch(videos, tables, src_layout, short_side, crop_size, views, 
             _on_device(video, device, what)
             (c, hs, ws, geom), nf = video.geometry(src_layout, coded[j], heights[j]), len(video)
         else:
-            if is_yuv and video.dim() != 3:
-                raise RuntimeError("video %d: expected one 3-d %s video, got %s" % (j, src_layout, tuple(video.shape)))
+            if is_yuv and video.dim() != 1 + _yuv_dims(src_layout):
+                raise RuntimeError("video %d: expected one %d-d %s video, got %s" % (j, 1 + _yuv_dims(src_layout), src_layout, tuple(video.shape)))
             c, nf, hs, ws, geom = _video_source(video, src_layout, device, coded[j], heights[j], what)
         if (as_frames or not is_yuv) and video.dtype != dtype:
             raise RuntimeError("the videos of one batch have one dtype: video %d is %s, video 0 %s" % (j, video.dtype, dtype))
@@ -1308,7 +1426,7 @@ class HdrVideoSource:
         d.t_index, d.n_rows, d.t_stride = table.data_ptr(), table.shape[0], table.stride(0)
         d.n_sources, d.n_items, d.C, d.T = 1, n_items, 3, table.shape[1]
         d.src_layout, d.src_dtype = _src_codes(src_layout, None)
-        d.c_step, d.yuv2rgb = (2 if src_layout in _YUV_INTERLEAVED else 1), matrix.data_ptr()
+        d.c_step, d.yuv2rgb = _yuv_c_step(src_layout), matrix.data_ptr()
         d.Ho, d.Wo, d.n_views = window[0], window[1], self.n_views
         h.transfer, h.tone = hdr[0], hdr[1].data_ptr()
         h.keep = (self, table, matrix, hdr[1])
@@ -1328,7 +1446,7 @@ def _batch_launch_fields(d, batch, table, item0, n_items, channels, src_layout, 
     d.n_sources, d.n_items, d.C, d.T = len(batch.sources), n_items, channels, table.shape[1]
     d.src_layout, d.src_dtype = _src_codes(src_layout, None)[0], batch.src_dtype
     if src_layout in _YUV_ANY:
-        d.c_step, d.yuv2rgb = (2 if src_layout in _YUV_INTERLEAVED else 1), matrix.data_ptr()
+        d.c_step, d.yuv2rgb = _yuv_c_step(src_layout), matrix.data_ptr()
     d.Ho, d.Wo, d.n_views = window[0], window[1], batch.n_views
 
 
@@ -1349,12 +1467,14 @@ def device_resized_crop(clip, regions, size, mean=None, std=None, div255=False, 
         raise ValueError("dtype is torch.bfloat16 or torch.float32")
     window = _size_pair(size)
     is_yuv = src_layout in _YUV_ANY
-    if is_yuv and clip.dim() == 3:
+    if is_yuv and clip.dim() == 1 + _yuv_dims(src_layout):
         clip, regions = clip.unsqueeze(0), torch.as_tensor(regions).unsqueeze(0)
-    if clip.dim() != (4 if is_yuv else 5):
+    if clip.dim() != (2 + _yuv_dims(src_layout) if is_yuv else 5):
         raise RuntimeError("expected %s clips [B, ...], got %s" % (src_layout, tuple(clip.shape),))
     if src_layout in _PACKED_ANY:                                # the stride rules, before any device is touched
         packed_geometry(clip[0], src_layout)
+    if src_layout in _YUYV_ANY:
+        yuyv_geometry(clip[0], src_layout)
     device = clip.device if clip.is_cuda else torch.device("cuda", torch.cuda.current_device())
     in_place = is_yuv or src_layout in _PACKED_ANY               # read with the strides they have: never copied
     clip = clip.to(device, non_blocking=True) if in_place else _device_source(clip, device)
@@ -1405,6 +1525,12 @@ def device_scale_crop(clip, short_side, crop_size, spatial_idx=1, mean=None, std
     has (`yuv_geometry`); every clip is a source of its own in one launch of `pv_batch_views` (the one-source entry points read
     4:2:0 only), chroma is replicated over the pixels it covers and `yuv_to_rgb` is the host mirror.  `hdr` is a ValueError.
 
+    With a layout of `YUYV_LAYOUTS` ("YUY2" -- alias "YUYV" --, "YVYU", "UYVY", "Y210" / "Y212" / "Y216") the clip is packed YUV
+    4:2:2 [B, T, H, W, 2] (or [T, H, W, 2]: one clip), uint8 or -- Y21x -- uint16 / int16, with the strides it has (`yuyv_geometry`:
+    a pitched surface or a column slice from an even column is read in place, a ValueError names a stride that is not legal);
+    every clip is a source of its own in one launch of `pv_batch_views`, and the result is bit for bit that of "I422" / "I216"
+    on `yuyv_to_planar(clip, layout)` with the same matrix.  `hdr` is a ValueError.
+
     `interpolation="area"` scales with the box filter of `short_side_scale(x, size, "area")` instead of four taps -- what a
     720p or larger source needs: every clip is a source of its own in ONE launch of `pv_area_views`, any source layout, up to
     three views; a ValueError together with a non-zero `orientation` or `hdr`, and for any other string."""
@@ -1441,12 +1567,14 @@ def _device_scale_crop_items(clip, short_side, crop_size, views, affine, num_fra
     from . import _lib as L
     is_yuv = src_layout in _YUV_ANY
     in_place = is_yuv or src_layout in _PACKED_ANY               # read with the strides they have: never copied
-    if is_yuv and clip.dim() == 3:
+    if is_yuv and clip.dim() == 1 + _yuv_dims(src_layout):
         clip = clip.unsqueeze(0)
-    if clip.dim() != (4 if is_yuv else 5):
+    if clip.dim() != (2 + _yuv_dims(src_layout) if is_yuv else 5):
         raise RuntimeError("expected %s clips [B, ...], got %s" % (src_layout, tuple(clip.shape),))
     if src_layout in _PACKED_ANY:                                # the stride rules, before any device is touched
         packed_geometry(clip[0], src_layout)
+    if src_layout in _YUYV_ANY:
+        yuyv_geometry(clip[0], src_layout)
     device = clip.device if clip.is_cuda else torch.device("cuda", torch.cuda.current_device())
     clip = clip.to(device, non_blocking=True) if in_place else _device_source(clip, device)
     b, t_src = clip.shape[0], clip.shape[2] if src_layout == "NCTHW" else clip.shape[1]
@@ -1572,7 +1700,8 @@ class DevicePacker:
         self.is_yuv, self.coded_height, self.height = src_layout in _YUV_ANY, coded_height, height
         self.is_yuv16 = src_layout in _YUV_WIDE                # 16-bit samples: pv_yuv16_views / PV_U16
         self.is_packed = src_layout in _PACKED_ANY             # packed pixels: item-sourced launches only
-        self.is_yuv4 = src_layout in _YUV4_ANY                 # YUV 4:2:2 / 4:4:4: item-sourced launches only
+        self.is_yuv4 = src_layout in _YUV4_ANY                 # YUV 4:2:2 (planar or packed) / 4:4:4: item-sourced launches only
+        self.video_dims = 1 + _yuv_dims(src_layout) if self.is_yuv else 4   # of one whole video in this layout
         self.item_only = self.is_packed or self.is_yuv4        # the one-source entry points do not read these
         self.region_even = region_evenness(src_layout)         # what `box_regions(..., even=)` takes for this layout
         self.in_place = self.is_yuv or self.is_packed          # read with the strides they have: never made contiguous
@@ -1739,8 +1868,8 @@ class DevicePacker:
         """B materialised clips of packed pixels [B, T', H, W, PB] -- or of YUV 4:2:2 / 4:4:4 frames [B, T', rows, W] --, read
         with the strides they have: every clip a source of its own, its frames one table row (`video_batch` + `fill_batch`:
         pv_batch_views), then the forward."""
-        if self.is_yuv4 and clips.dim() != 4:
-            raise RuntimeError("expected %s clips [B, T, rows, W], got %s" % (self.src_layout, tuple(clips.shape),))
+        if self.is_yuv4 and clips.dim() != 1 + self.video_dims:
+            raise RuntimeError("expected %s clips [B, T, %s], got %s" % (self.src_layout, "H, W, 2" if self.video_dims == 4 else "rows, W", tuple(clips.shape),))
         if self.is_packed and clips.dim() != 5:
             raise RuntimeError("expected %s clips [B, T, H, W, %d], got %s" % (self.src_layout, _packed_bytes(self.src_layout), tuple(clips.shape),))
         b, t = clips.shape[:2]
