@@ -733,3 +733,170 @@ def make_token_pool(dtype, B, heads, hd, thw, k, strides, n_prefix, gamma=True, 
         i["gamma"].append(randn((hd,), seed + 10 * z + 2, 0.2, 1.0) if gamma else None)
         i["beta"].append(randn((hd,), seed + 10 * z + 3, 0.3) if beta else None)
     return i, p
+
+
+# ------------------------------------------------------------------ streaming conv family (pv_pwconv.hip, pv_lateral.hip, pv_stem.hip)
+# pw_stream_kernel, tap_stream_kernel and stem_c4_kernel launch about one resident generation of workgroups and walk the voxel
+# groups in a grid-stride loop.  The float64 references and the two checks below serve tests/test_gpu_stream_kernels.py, whose
+# cases run several trips of that loop; tests/test_stream_kernel_checks.py feeds the checks their own reference and defective
+# copies of it on the CPU.
+#
+# An output is ONE allocation: STREAM_GUARD canaries, M rows of `ld` elements, STREAM_GUARD canaries.  A launch owns channels
+# [c_off, c_off + round_up(cout, 8)) of every row; the rest of a row (the slow pathway's slice of a lateral connection) comes
+# back as it went in.
+STREAM_GUARD = 4096
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def stream_chunks(resident, per_cu, nsplit):
+    """Candidate `nchunks` of a launcher that sizes its grid as ceil(resident * per_cu / nsplit), for every residency the
+    runtime may report."""
+    return [cdiv(resident * p, nsplit) for p in per_cu]
+
+
+def assert_trips(ngroups, candidates, full=2):
+    """The condition on the INPUTS of a multi-trip case: under every candidate grid the loop runs more than `full` whole trips'
+    worth of groups and the last trip is ragged (some workgroups run one trip more than their neighbours)."""
+    for n in candidates:
+        assert ngroups > full * n, "ngroups %d is no more than %d trips of %d chunks" % (ngroups, full, n)
+        assert ngroups % n != 0, "ngroups %d is a whole number of trips of %d chunks" % (ngroups, n)
+
+
+def stream_buf(M, ld, dtype, fill=None, guard=STREAM_GUARD):
+    """The allocation of an output: canaries everywhere, or rows of `fill` (M, ld) between the two guards."""
+    buf = torch.full((2 * guard + M * ld,), CANARY, dtype=dtype)
+    if fill is not None:
+        buf[guard:guard + M * ld] = fill.reshape(-1).to(dtype)
+    return buf
+
+
+class StreamExpect:
+    """What one launch of a streaming conv kernel must leave in its output allocation.
+
+    want     (M, cout) float64 reference
+    before   the allocation as it was handed to the launch (stream_buf)
+    S        voxels per clip; gvox: voxels (MFMA columns) per group of the grid-stride loop
+    nchunks  candidate grid sizes in chunks; a failure names g // n for each, the trip of the loop the voxel was computed on
+    unit     (M,) index of the MFMA column a voxel sits in, where that is not the voxel itself (two outputs per column)
+    """
+
+    def __init__(self, want, before, ld, S, gvox, nchunks, tol, c_off=0, unit=None, guard=STREAM_GUARD):
+        self.want, self.before, self.ld, self.S, self.gvox = want.cpu().double(), before.cpu().clone(), ld, S, gvox
+        self.nchunks, self.tol, self.c_off, self.unit, self.guard = list(nchunks), tol, c_off, unit, guard
+        self.M, self.C = want.shape
+        self.written = round_up8(self.C)
+        assert self.before.numel() == 2 * guard + self.M * ld and c_off + self.written <= ld
+
+    def rows(self, buf):
+        return buf[self.guard:self.guard + self.M * self.ld].view(self.M, self.ld)
+
+    def group_of(self, m):
+        return int(m if self.unit is None else self.unit[m]) // self.gvox
+
+    def where(self, m):
+        g = self.group_of(m)
+        return "voxel %d (clip %d, voxel %d of it), group g = %d, trip g // nchunks = %s" % (
+            m, m // self.S, m % self.S, g, ", ".join("%d of nchunks %d" % (g // n, n) for n in self.nchunks))
+
+    def ideal(self):
+        """The allocation a kernel that computes the reference exactly leaves."""
+        buf = self.before.clone()
+        r = self.rows(buf)
+        r[:, self.c_off:self.c_off + self.C] = self.want.to(buf.dtype)
+        r[:, self.c_off + self.C:self.c_off + self.written] = 0
+        return buf
+
+    def check(self, got, what=""):
+        """-> error relative to the reference abs-max.  The message of a failure carries the worst voxel's place in the loop."""
+        got = got.detach().cpu()
+        assert got.shape == self.before.shape and got.dtype == self.before.dtype, what
+        g, n = self.guard, self.M * self.ld
+        bad = (got[:g] != self.before[:g]).sum().item() + (got[g + n:] != self.before[g + n:]).sum().item()
+        assert bad == 0, "%s: %d canary elements around the output changed" % (what, bad)
+        r = self.rows(got)
+        diff = (r[:, self.c_off:self.c_off + self.C].double() - self.want).abs()
+        diff = torch.where(torch.isnan(diff), torch.full_like(diff, float("inf")), diff)
+        per_voxel = diff.max(1).values
+        m = int(per_voxel.argmax())
+        err = per_voxel[m].item() / max(self.want.abs().max().item(), 1e-6)
+        assert err <= self.tol, "%s: error %.3e of the reference abs-max > %.1e, worst at %s, channel %d" % (
+            what, err, self.tol, self.where(m), int(diff[m].argmax()))
+        pads = r[:, self.c_off + self.C:self.c_off + self.written]
+        if pads.numel() and (pads != 0).any():
+            m = int((pads != 0).any(1).nonzero()[0])
+            raise AssertionError("%s: %d padding channels are not zero, first at %s" % (what, (pads != 0).sum().item(), self.where(m)))
+        rest_got, rest_before = r.clone(), self.rows(self.before).clone()
+        rest_got[:, self.c_off:self.c_off + self.written] = 0
+        rest_before[:, self.c_off:self.c_off + self.written] = 0
+        bad = (rest_got != rest_before).sum().item()
+        assert bad == 0, "%s: %d elements of the rows that the launch does not own changed" % (what, bad)
+        return err
+
+    def check_trips(self, got, pieces, what=""):
+        """Trip invariance, bit for bit: `pieces` is an allocation like `got` that a series of one-trip sub-launches filled
+        (each through a pointer offset into it).  A voxel's value comes from the same instruction sequence in the same order on
+        any trip of the loop and in any MFMA column, so the two allocations are equal; nothing here is a tolerance."""
+        got, pieces = got.detach().cpu(), pieces.detach().cpu()
+        assert got.shape == pieces.shape == self.before.shape and got.dtype == pieces.dtype, what
+        if torch.equal(got, pieces):
+            return
+        g, n = self.guard, self.M * self.ld
+        assert torch.equal(got[:g], pieces[:g]) and torch.equal(got[g + n:], pieces[g + n:]), "%s: the canaries differ" % what
+        ne = self.rows(got) != self.rows(pieces)
+        voxels = ne.any(1).nonzero().flatten()
+        m = int(voxels[0])
+        c = int(ne[m].nonzero()[0])
+        raise AssertionError("%s: the large launch and the one-trip sub-launches differ in %d elements of %d voxels; first at %s, "
+                             "column %d of the row: %r against %r; last at %s" % (
+                                 what, ne.sum().item(), len(voxels), self.where(m), c, self.rows(got)[m, c].item(),
+                                 self.rows(pieces)[m, c].item(), self.where(int(voxels[-1]))))
+
+
+def ref_pointwise(x, w, scale, shift, act, gate=None, a_act=0, clip=None, res=None, x2=None, w2=None, scale2=None):
+    """pw_stream_kernel's operation in float64: act(((a(x * gate[clip])) @ w^T) * scale + shift + (x2 @ w2^T) * scale2 + res).
+    x (M, cin), w (cout, cin), gate (B, cin), clip (M,) the clip whose gate row a voxel takes, res (M, cout), x2 (M, cin2) the
+    second operand already gathered.  The gated / activated operand is rounded to bf16 where the kernel rounds it."""
+    xin = x.double()
+    if gate is not None:
+        xin = xin * gate.double()[clip]
+    if gate is not None or a_act:
+        xin = ref_act(xin, a_act).to(torch.bfloat16).double()
+    out = (xin @ w.double().t()) * scale.double() + shift.double()
+    if x2 is not None:
+        out = out + (x2.double() @ w2.double().t()) * scale2.double()
+    if res is not None:
+        out = out + res.double()
+    return ref_act(out, act)
+
+
+def ref_tap_conv(x, w, stride, pad, scale=None, shift=None, act=0):
+    """nn.Conv3d(cin, cout, k, stride, pad, bias=False) + affine + activation of a (B, T, H, W, cin) grid in float64, one filter
+    tap at a time; w (cout, cin, kt, kh, kw).  -> (B, To, Ho, Wo, cout)"""
+    B, T, H, W, cin = x.shape
+    cout, _, kt, kh, kw = w.shape
+    xp = torch.zeros(B, T + 2 * pad[0], H + 2 * pad[1], W + 2 * pad[2], cin, dtype=torch.float64)
+    xp[:, pad[0]:pad[0] + T, pad[1]:pad[1] + H, pad[2]:pad[2] + W] = x
+    To, Ho, Wo = ((n + 2 * p - k) // s + 1 for n, p, k, s in zip((T, H, W), pad, (kt, kh, kw), stride))
+    out = torch.zeros(B * To * Ho * Wo, cout, dtype=torch.float64)
+    wd = w.double()
+    for dt in range(kt):
+        for dh in range(kh):
+            for dw in range(kw):
+                tap = xp[:, dt:dt + (To - 1) * stride[0] + 1:stride[0], dh:dh + (Ho - 1) * stride[1] + 1:stride[1],
+                         dw:dw + (Wo - 1) * stride[2] + 1:stride[2]]
+                out.addmm_(tap.reshape(-1, cin), wd[:, :, dt, dh, dw].t())
+    if scale is not None:
+        out = out * scale.double()
+    if shift is not None:
+        out = out + shift.double()
+    return ref_act(out, act).view(B, To, Ho, Wo, cout)
+
+
+def ref_tap_pw2(x, w, stride, pad, scale, shift, act, w2, scale2, shift2, act2, res=None):
+    """tap_stream_kernel's two-conv form: the inner tensor is rounded to bf16 (it becomes an MFMA operand), then the pointwise
+    conv, its affine, the residual and its activation in float64.  -> (M, cout2)"""
+    mid = ref_tap_conv(x, w, stride, pad, scale, shift, act).to(torch.bfloat16).double()
+    return ref_pointwise(mid.reshape(-1, mid.shape[-1]), w2, scale2, shift2, act2, res=res)
