@@ -796,7 +796,8 @@ class StreamExpect:
     def group_of(self, m):
         return int(m if self.unit is None else self.unit[m]) // self.gvox
 
-    def where(self, m):
+    def where(self, m, c=None):
+        """Place of voxel m in the loop (c, the output channel, places nothing here: a group spans every channel of its split)."""
         g = self.group_of(m)
         return "voxel %d (clip %d, voxel %d of it), group g = %d, trip g // nchunks = %s" % (
             m, m // self.S, m % self.S, g, ", ".join("%d of nchunks %d" % (g // n, n) for n in self.nchunks))
@@ -823,11 +824,12 @@ class StreamExpect:
         m = int(per_voxel.argmax())
         err = per_voxel[m].item() / max(self.want.abs().max().item(), 1e-6)
         assert err <= self.tol, "%s: error %.3e of the reference abs-max > %.1e, worst at %s, channel %d" % (
-            what, err, self.tol, self.where(m), int(diff[m].argmax()))
+            what, err, self.tol, self.where(m, int(diff[m].argmax())), int(diff[m].argmax()))
         pads = r[:, self.c_off + self.C:self.c_off + self.written]
         if pads.numel() and (pads != 0).any():
             m = int((pads != 0).any(1).nonzero()[0])
-            raise AssertionError("%s: %d padding channels are not zero, first at %s" % (what, (pads != 0).sum().item(), self.where(m)))
+            raise AssertionError("%s: %d padding channels are not zero, first at %s" % (
+                what, (pads != 0).sum().item(), self.where(m, self.C + int((pads[m] != 0).nonzero()[0]))))
         rest_got, rest_before = r.clone(), self.rows(self.before).clone()
         rest_got[:, self.c_off:self.c_off + self.written] = 0
         rest_before[:, self.c_off:self.c_off + self.written] = 0
@@ -851,8 +853,9 @@ class StreamExpect:
         c = int(ne[m].nonzero()[0])
         raise AssertionError("%s: the large launch and the one-trip sub-launches differ in %d elements of %d voxels; first at %s, "
                              "column %d of the row: %r against %r; last at %s" % (
-                                 what, ne.sum().item(), len(voxels), self.where(m), c, self.rows(got)[m, c].item(),
-                                 self.rows(pieces)[m, c].item(), self.where(int(voxels[-1]))))
+                                 what, ne.sum().item(), len(voxels), self.where(m, c - self.c_off), c, self.rows(got)[m, c].item(),
+                                 self.rows(pieces)[m, c].item(),
+                                 self.where(int(voxels[-1]), int(ne[int(voxels[-1])].nonzero()[-1]) - self.c_off)))
 
 
 def ref_pointwise(x, w, scale, shift, act, gate=None, a_act=0, clip=None, res=None, x2=None, w2=None, scale2=None):
@@ -877,10 +880,10 @@ def ref_tap_conv(x, w, stride, pad, scale=None, shift=None, act=0):
     tap at a time; w (cout, cin, kt, kh, kw).  -> (B, To, Ho, Wo, cout)"""
     B, T, H, W, cin = x.shape
     cout, _, kt, kh, kw = w.shape
-    xp = torch.zeros(B, T + 2 * pad[0], H + 2 * pad[1], W + 2 * pad[2], cin, dtype=torch.float64)
+    xp = torch.zeros(B, T + 2 * pad[0], H + 2 * pad[1], W + 2 * pad[2], cin, dtype=torch.float64, device=x.device)
     xp[:, pad[0]:pad[0] + T, pad[1]:pad[1] + H, pad[2]:pad[2] + W] = x
     To, Ho, Wo = ((n + 2 * p - k) // s + 1 for n, p, k, s in zip((T, H, W), pad, (kt, kh, kw), stride))
-    out = torch.zeros(B * To * Ho * Wo, cout, dtype=torch.float64)
+    out = torch.zeros(B * To * Ho * Wo, cout, dtype=torch.float64, device=x.device)
     wd = w.double()
     for dt in range(kt):
         for dh in range(kh):
@@ -900,3 +903,94 @@ def ref_tap_pw2(x, w, stride, pad, scale, shift, act, w2, scale2, shift2, act2, 
     conv, its affine, the residual and its activation in float64.  -> (M, cout2)"""
     mid = ref_tap_conv(x, w, stride, pad, scale, shift, act).to(torch.bfloat16).double()
     return ref_pointwise(mid.reshape(-1, mid.shape[-1]), w2, scale2, shift2, act2, res=res)
+
+
+# ------------------------------------------------------------------ dense GEMM family (pv_gemm.hip, pv_gemm8.hip, pv_gemm9.hip, pv_gemm9h.hip)
+# gemm_glds_kernel, gemm8_kernel, gemm_quad_kernel and gemm_quad_half_kernel are persistent: the launcher starts
+# min(total_tiles, R) workgroups (R = 512 for gemm_glds_kernel, 256 for the others) and workgroup w walks the work items
+# it = w, w + R, w + 2 R, ... of the XCD-aware tile order of pv_gemm_tile.h.  The mirror of that order and GemmExpect serve
+# tests/test_gpu_gemm_kernels.py, whose cases run more than two trips of that loop; tests/test_gemm_kernel_checks.py feeds the
+# checks their own reference and defective copies of it on the CPU.  The float64 references are ref_pointwise and ref_tap_conv.
+def gemm_tile_of(it, total_tiles):
+    """PvTileOrder (pv_gemm_tile.h): work item -> tile.  Works on ints and on integer arrays / tensors alike."""
+    xcd, slot = it & 7, it >> 3
+    qn, rn = total_tiles >> 3, total_tiles & 7
+    lo, hi = xcd * (qn + 1), rn * (qn + 1) + (xcd - rn) * qn
+    return (xcd < rn) * lo + (xcd >= rn) * hi + slot
+
+
+def gemm_origin_of(it, total_tiles, tiles_n, BM, BN):
+    """work item -> (m0, n0), the first voxel row and the first channel of its BM x BN tile"""
+    tile = gemm_tile_of(it, total_tiles)
+    return (tile // tiles_n) * BM, (tile % tiles_n) * BN
+
+
+def gemm_item_of(tile, total_tiles):
+    """The inverse of gemm_tile_of: tile -> work item.  XCD x owns the tiles [start(x), start(x) + qn + (x < rn))."""
+    qn, rn = total_tiles >> 3, total_tiles & 7
+    big = rn * (qn + 1)                                   # tiles of the XCDs that own one more
+    if tile < big:
+        xcd, slot = tile // (qn + 1), tile % (qn + 1)
+    else:
+        xcd, slot = rn + (tile - big) // qn, (tile - big) % qn
+    return slot * 8 + xcd
+
+
+def gemm_place(m, c, total_tiles, tiles_n, BM, BN, R):
+    """(voxel row, channel) -> dict(tile, m0, n0, item, workgroup, trip) under a grid of R workgroups"""
+    tile = (m // BM) * tiles_n + c // BN
+    it = gemm_item_of(tile, total_tiles)
+    grid = min(total_tiles, R)
+    return dict(tile=tile, m0=m // BM * BM, n0=c // BN * BN, item=it, workgroup=it % grid, trip=it // grid)
+
+
+def gemm_trip_conditions(M, S, cout, BM, BN, R, rotation=False):
+    """The conditions on the INPUTS of a multi-trip GEMM case, asserted before anything is launched -> (tiles_m, tiles_n, total).
+    More than two whole trips, a ragged last one, a remainder branch in the XCD order (total % 8 != 0), an M tail, and tiles
+    that straddle clips.  A rotation case cannot have the last two: the launchers rotate only where a frame is a whole number
+    of tiles (Ho Wo % BM == 0), so a clip and M are whole numbers of tiles as well; it asserts exactly that instead."""
+    tiles_m, tiles_n = cdiv(M, BM), cdiv(round_up8(cout), BN)
+    total = tiles_m * tiles_n
+    assert_trips(total, [R])
+    assert total % 8 != 0, "total %d takes no remainder branch of the XCD order" % total
+    if rotation:
+        assert S % BM == 0 and M % BM == 0, "a rotated clip of %d voxels is no whole number of %d-voxel tiles" % (S, BM)
+    else:
+        assert M % BM != 0, "M %d is a multiple of the tile's %d voxels" % (M, BM)
+        assert S % BM != 0, "clips of %d voxels: no tile straddles two clips" % S
+    return tiles_m, tiles_n, total
+
+
+def gemm_sub_clips(S, tiles_n, BM, R):
+    """Most whole clips a sub-launch may take so that it is at most R tiles: one trip of the loop"""
+    n = (R // tiles_n) * BM // S
+    assert n >= 1 and cdiv(n * S, BM) * tiles_n <= R
+    return n
+
+
+class GemmExpect(StreamExpect):
+    """What one launch of a dense GEMM kernel must leave in its output allocation (stream_buf): StreamExpect's duties -- the
+    float64 reference under `tol` relative to its abs-max, padding channels [cout, round_up(cout, 8)) exact zeros, canaries
+    untouched, check_trips' bit equality with one-trip sub-launches -- with a failure placed by TILE: voxel, clip, channel,
+    tile, work item, workgroup and trip of the persistent loop under a grid of R workgroups."""
+
+    def __init__(self, want, before, ld, S, BM, BN, R, tol, guard=STREAM_GUARD):
+        super().__init__(want, before, ld, S, BM, [R], tol, guard=guard)
+        self.BM, self.BN, self.R = BM, BN, R
+        self.tiles_n = cdiv(self.written, BN)
+        self.total = cdiv(self.M, BM) * self.tiles_n
+
+    def place(self, m, c):
+        c = min(max(int(c), 0), self.tiles_n * self.BN - 1)            # a column of the row outside the launch's slice
+        return gemm_place(int(m), c, self.total, self.tiles_n, self.BM, self.BN, self.R)
+
+    def where(self, m, c=0):
+        p = self.place(m, c)
+        return ("voxel %d (clip %d, voxel %d of it), channel %d, tile %d (voxels from %d, channels from %d), work item %d = "
+                "workgroup %d on trip %d of %d workgroups" % (m, m // self.S, m % self.S, c, p["tile"], p["m0"], p["n0"], p["item"],
+                                                               p["workgroup"], p["trip"], min(self.total, self.R)))
+
+    def tile_block(self, tile):
+        """(row slice, channel slice) of a tile inside the (M, cout) reference"""
+        m0, n0 = (tile // self.tiles_n) * self.BM, (tile % self.tiles_n) * self.BN
+        return slice(m0, min(m0 + self.BM, self.M)), slice(n0, min(n0 + self.BN, self.C))
