@@ -994,3 +994,394 @@ class GemmExpect(StreamExpect):
         """(row slice, channel slice) of a tile inside the (M, cout) reference"""
         m0, n0 = (tile // self.tiles_n) * self.BM, (tile % self.tiles_n) * self.BN
         return slice(m0, min(m0 + self.BM, self.M)), slice(n0, min(n0 + self.BN, self.C))
+
+
+# ------------------------------------------------------------------ pv_mlp.hip: mlp_rows16_kernel and ln_linear_rows_kernel
+# Float64 references, operands, case tables and the checker of tests/test_gpu_mlp_kernels.py.  tests/test_mlp_kernel_checks.py
+# feeds the checker its own reference and defective copies of it and checks, on the CPU, every claim the tables make.
+#
+# An output is a (rows, ld) tensor: a launch owns channels [0, width) of the rows [r0, M) (r0 > 0: a sub-launch through offset
+# pointers); the pad columns [width, ld), the rows below r0 and the MLP_EXTRA_ROWS rows behind M hold the canary.
+WG_ROWS = 128                              # rows per workgroup, both kernels
+MLP_WAVE_ROWS, LNL_WAVE_ROWS = 16, 32      # rows per wave: 512 threads on 16-row MFMA tiles, 256 threads on 32-row tiles
+MLP_EXTRA_ROWS = 3
+MLP_FORMS = {(96, 96): (3, 6), (96, 192): (3, 12), (192, 192): (6, 12), (192, 384): (6, 24), (384, 384): (12, 24)}   # (C, Cout) -> launch16<KS2, NOB16>
+LNL_FORMS = {96: (6, 2), 192: (12, 2), 384: (24, 2), 768: (48, 1)}                                                    # C -> launch_ln_linear<KS, MINW>
+MLP_LN_PAIRS = [p for p in MLP_FORMS if p[0] == p[1]]
+BRANCH_TOL = TOL[torch.bfloat16]           # the project's bf16 bound, applied to the MLP branch alone
+
+
+def row_place(m, wave_rows):
+    """(workgroup, wave, row inside the wave) of row m of a launch"""
+    return m // WG_ROWS, m % WG_ROWS // wave_rows, m % wave_rows
+
+
+def row_layout(M, wave_rows):
+    """-> (workgroups, rows held by each wave of the last workgroup)"""
+    wgs = cdiv(M, WG_ROWS)
+    last = M - (wgs - 1) * WG_ROWS
+    return wgs, [min(max(last - w * wave_rows, 0), wave_rows) for w in range(WG_ROWS // wave_rows)]
+
+
+def bf16_of(t):
+    return t.to(torch.bfloat16).double()
+
+
+def ref_ln64(x, gamma, beta, eps):
+    x = x.double()
+    mu = x.mean(-1, keepdim=True)
+    var = ((x - mu) ** 2).mean(-1, keepdim=True)
+    return (x - mu) / torch.sqrt(var + eps) * gamma.double() + beta.double()
+
+
+def ref_mlp_rows(o, act, edit_hidden=None, **changed):
+    """pv_mlp_rows in float64 on operands `o` (make_mlp_*; `changed` replaces entries): weights rounded to bf16, xn the bf16
+    operand or float64 LayerNorm rounded to bf16, hidden values ref_act in float64 rounded to bf16 (edit_hidden: a defect on them).
+    -> (base, branch): base = residual + b2 (LayerNorm mode: x + b2), branch = W2 . hidden."""
+    o = dict(o, **changed)
+    if o["ln"]:
+        xn = bf16_of(ref_ln64(o["x"], o["gamma"], o["beta"], o["eps"]))
+        base = o["x"].double().clone()
+    else:
+        xn = o["x"].to(torch.bfloat16).double()
+        base = o["res"].double().clone() if o["res"] is not None else torch.zeros(xn.shape[0], o["w2"].shape[0], dtype=torch.float64)
+    if o["b2"] is not None:
+        base += o["b2"].double()
+    pre = xn @ bf16_of(o["w1"]).t()
+    if o["b1"] is not None:
+        pre = pre + o["b1"].double()
+    hid = bf16_of(ref_act(pre, act))
+    if edit_hidden is not None:
+        hid = edit_hidden(hid)
+    return base, hid @ bf16_of(o["w2"]).t()
+
+
+def ref_ln_linear(o, act, **changed):
+    """pv_ln_linear_rows in float64: LayerNorm rounded to bf16, the Linear on bf16-rounded weights, ref_act."""
+    o = dict(o, **changed)
+    y = bf16_of(ref_ln64(o["x"], o["gamma"], o["beta"], o["eps"])) @ bf16_of(o["w"]).t()
+    if o["b"] is not None:
+        y = y + o["b"].double()
+    return ref_act(y, act)
+
+
+def _gelu_as_f32(x):
+    """pv_gelu_fast2's operations in fp32 (Abramowitz & Stegun 7.1.25)"""
+    ax = x.abs()
+    t = 1.0 / ((ax * 0.70710678118654752440) * 0.47047 + 1.0)
+    poly = t * (0.3480242 + t * (-0.0958798 + t * 0.7478556))
+    e = torch.exp2((x * x) * -0.72134752044448170368)
+    return (x + ax * (1.0 - poly * e)) * 0.5
+
+
+def f32_scalar(v):
+    return torch.tensor(v, dtype=torch.float32)
+
+
+def replay_mlp_rows(o, act):
+    """What an fp32 machine with mlp_rows16_kernel's rounding points leaves in y: LayerNorm from the mean and the centred squares,
+    xn and the hidden values rounded to bf16, the A&S erf for GELU, fp32 sums on top of residual + b2 (LayerNorm mode: b2 last).
+    It says how far the float64 reference itself stands from any fp32 implementation; no kernel is involved."""
+    f = torch.float32
+    if o["ln"]:
+        x = o["x"].to(f)
+        mean = x.sum(-1, keepdim=True) * f32_scalar(1.0 / x.shape[1])
+        var = ((x - mean) ** 2).sum(-1, keepdim=True) * f32_scalar(1.0 / x.shape[1])
+        xn = ((x - mean) * torch.rsqrt(var + f32_scalar(o["eps"])) * o["gamma"].to(f) + o["beta"].to(f)).to(torch.bfloat16).to(f)
+        y = x.clone()
+    else:
+        xn = o["x"].to(torch.bfloat16).to(f)
+        y = o["res"].to(f).clone() if o["res"] is not None else torch.zeros(xn.shape[0], o["w2"].shape[0], dtype=f)
+        if o["b2"] is not None:
+            y += o["b2"].to(f)
+    pre = xn @ o["w1"].to(torch.bfloat16).to(f).t()
+    if o["b1"] is not None:
+        pre = pre + o["b1"].to(f)
+    if act == L.ACT_GELU:
+        hid = _gelu_as_f32(pre)
+    elif act == L.ACT_RELU:
+        hid = pre.clamp_min(0)
+    elif act == L.ACT_SWISH:
+        hid = pre * torch.sigmoid(pre)
+    elif act == L.ACT_SIGMOID:
+        hid = torch.sigmoid(pre)
+    else:
+        hid = pre
+    y = y + hid.to(torch.bfloat16).to(f) @ o["w2"].to(torch.bfloat16).to(f).t()
+    if o["ln"]:
+        y = y + o["b2"].to(f)
+    return y
+
+
+def _mlp_float_operands(C, H, Cout, M, seed):
+    g = torch.Generator().manual_seed(seed)
+    o = dict(C=C, H=H, Cout=Cout, M=M, eps=1e-6)
+    o["w1"] = (torch.randn(H, C, generator=g) * C ** -0.5).bfloat16().float()
+    o["w2"] = (torch.randn(Cout, H, generator=g) * H ** -0.5).bfloat16().float()
+    o["b1"], o["b2"] = torch.randn(H, generator=g) * 0.3, torch.randn(Cout, generator=g) * 0.3
+    o["gamma"], o["beta"] = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2
+    o["x32"] = torch.randn(M, C, generator=g) * 2.0 + 3.0 * torch.randn(M, 1, generator=g)      # rows with a large mean
+    o["r32"] = torch.randn(M, Cout, generator=g)
+    o["nn_gamma"], o["nn_beta"] = torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.2
+    return o
+
+
+def make_mlp_float(C, H, Cout, ln, res, M, seed=77):
+    """Seeded normal operands, drawn as tests/test_gpu_kernels.py::test_fused_mlp_rows draws them."""
+    o = _mlp_float_operands(C, H, Cout, M, seed)
+    x32, r32 = o.pop("x32"), o.pop("r32")
+    o.update(ln=ln, x=x32 if ln else x32.bfloat16(), res=r32 if (res and not ln) else None)
+    return o
+
+
+def make_mlp_int(C, H, Cout, ln, M, seed=1301):
+    """Operands under which every value of the launch is an integer that its format holds exactly (mlp_int_conditions): the
+    output equals the float64 reference bit for bit in any summation order."""
+    g = torch.Generator().manual_seed(seed + C + 7 * H + 13 * Cout)
+    ri = lambda lo, hi, shape: torch.randint(lo, hi + 1, shape, generator=g)
+    o = dict(C=C, H=H, Cout=Cout, M=M, ln=ln, eps=1e-6)
+    p0 = ri(0, C - 1, (H,))
+    p1 = (p0 + ri(1, C - 1, (H,))) % C                                   # a second, different channel
+    w1 = torch.zeros(H, C)
+    w1[torch.arange(H), p0] = (2 * ri(0, 1, (H,)) - 1).float()
+    w1[torch.arange(H), p1] = (2 * ri(0, 1, (H,)) - 1).float()
+    o["w1"], o["w2"] = w1, ri(-2, 2, (Cout, H)).float()
+    o["b1"], o["b2"] = 16.0 * ri(-3, 3, (H,)), 16.0 * ri(-3, 3, (Cout,))
+    if ln:
+        # gamma = 0: xn is beta for every row, whatever the statistics; 193 is prime, so channels 8, 16 or 32 apart differ
+        o["gamma"], o["beta"] = torch.zeros(C), 16.0 * ((torch.arange(C) * 37 + seed) % 193 - 96)
+        o["x"], o["res"] = ri(-64, 64, (M, C)).float(), None             # the residual: another integer row per token
+    else:
+        o["gamma"] = o["beta"] = None
+        o["x"], o["res"] = (16.0 * ri(-8, 8, (M, C))).bfloat16(), 16.0 * ri(-8, 8, (M, Cout))
+    o["nn_gamma"], o["nn_beta"] = torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.2
+    return o
+
+
+def mlp_int_conditions(o, acts):
+    """The conditions under which an integer case is exact, asserted on its operands: xn exact in bf16; every pre-activation a
+    multiple of 16 (pv_gelu_fast2 is exact at 0 and from |x| = 16 on: exp2f(-0.7213 * 256) is 0, what is left is (x + |x|) / 2);
+    hidden values at most 256 * 16, exact in bf16; every partial sum below 2^24 in magnitude, exact in fp32."""
+    xn = (o["beta"].expand(o["M"], -1) if o["ln"] else o["x"]).double()
+    assert o["ln"] is False or not o["gamma"].any()
+    assert torch.equal(bf16_of(xn), xn) and torch.equal(bf16_of(o["w1"]), o["w1"].double()) and torch.equal(bf16_of(o["w2"]), o["w2"].double())
+    assert ((o["w1"] != 0).sum(1) == 2).all() and (o["w1"].abs() <= 1).all() and (o["w2"].abs() <= 2).all()
+    pre = xn @ o["w1"].double().t() + o["b1"].double()
+    assert (pre % 16 == 0).all() and (xn.abs() @ o["w1"].abs().double().t() + o["b1"].abs().double()).max() < 2 ** 24
+    worst = 0.0
+    for act in acts:
+        assert act in (L.ACT_NONE, L.ACT_RELU, L.ACT_GELU)
+        hid = ref_act(pre, act)
+        assert torch.equal(hid, pre if act == L.ACT_NONE else pre.clamp_min(0)), "the float64 activation is not exact here"
+        assert hid.abs().max() <= 256 * 16 and torch.equal(bf16_of(hid), hid)
+        base, _ = ref_mlp_rows(o, act)
+        total = (hid.abs() @ o["w2"].abs().double().t() + (o["x"].abs().double() if o["ln"] else o["res"].abs().double())
+                 + o["b2"].abs().double()).max().item()
+        assert total < 2 ** 24 and (base % 1 == 0).all()
+        worst = max(worst, total)
+    return worst
+
+
+# A2: name -> (C, H, Cout, LayerNorm mode, residual, activation, M).  All five (C, Cout) pairs in operand mode and the three
+# C == Cout pairs in LayerNorm mode with GELU (the instantiations MViT launches), SWISH and SIGMOID through the runtime-activation
+# instantiation; H = 32, 96, 160 (1, 3, 5 hidden blocks) and M = 1, 15, 17, 127, 128, 129, 273 spread over them.
+MLP_A2 = {
+    "op_96_96": (96, 32, 96, False, True, L.ACT_GELU, 1),
+    "op_96_192": (96, 96, 192, False, True, L.ACT_GELU, 273),
+    "op_192_192": (192, 160, 192, False, False, L.ACT_GELU, 17),
+    "op_192_384": (192, 32, 384, False, True, L.ACT_GELU, 127),
+    "op_384_384": (384, 96, 384, False, False, L.ACT_GELU, 128),
+    "ln_96": (96, 160, 96, True, False, L.ACT_GELU, 129),
+    "ln_192": (192, 32, 192, True, False, L.ACT_GELU, 273),
+    "ln_384": (384, 96, 384, True, False, L.ACT_GELU, 273),
+    "op_192_384_swish": (192, 160, 384, False, True, L.ACT_SWISH, 15),
+    "ln_384_sigmoid": (384, 160, 384, True, False, L.ACT_SIGMOID, 129),
+}
+MLP_A1_H = (32, 64, 96, 160, 224)          # 1, 2, 3, 5, 7 hidden blocks: the ring wraps at 3; at 7 every buffer has been reused twice
+MLP_A1_M = 273                             # two full workgroups, then wave 0 full, wave 1 with one row, waves 2-7 empty
+MLP_A1_ACTS = (L.ACT_GELU, L.ACT_NONE, L.ACT_RELU)
+MLP_A3_ROWS = {0: "constant", 5: "variance_eps", 16: "outlier_first", 20: "outlier_last"}   # row of the launch -> edge; M = 21
+MLP_A3_M = 21
+MLP_RANGES = (1, 129, 256 + 16)            # A6: the launches of rows [r0, M)
+LNL_RANGES = (1, 129)
+LNL_B1_N = (32, 64, 96, 160)               # 1, 2, 3, 5 output blocks
+LNL_B4_M = (1, 31, 33, 97, 128, 129, 161, 193)
+LNL_ACTS = (L.ACT_NONE, L.ACT_RELU, L.ACT_SWISH, L.ACT_GELU, L.ACT_SIGMOID)
+
+
+def ln_edge_row(kind, C, seed=5):
+    """The LayerNorm edge rows: a constant row (variance 0); a row of +-1e-3 (variance 1e-6, the size of ln_eps); a normal row
+    with one outlier of 1e3 in channel 0 (ln_linear_rows_kernel's shift) or in the last channel."""
+    g = torch.Generator().manual_seed(seed + C)
+    if kind == "constant":
+        return torch.full((C,), 3.5)
+    if kind == "variance_eps":
+        sign = torch.ones(C)
+        sign[torch.randperm(C, generator=g)[:C // 2]] = -1.0
+        return 1e-3 * sign
+    row = torch.randn(C, generator=g)
+    row[0 if kind == "outlier_first" else C - 1] = 1e3
+    return row
+
+
+def make_mlp_edges(C, H, eps, seed=79):
+    """A3: LayerNorm mode, C = Cout, normal rows with the edge rows of MLP_A3_ROWS among them."""
+    o = make_mlp_float(C, H, C, True, False, MLP_A3_M, seed)
+    for m, kind in MLP_A3_ROWS.items():
+        o["x"][m] = ln_edge_row(kind, C)
+    o["eps"] = eps
+    return o
+
+
+def make_lnl_float(C, N, M, seed=78):
+    """Seeded normal operands, drawn as test_layernorm_fused_into_the_qkv_linear draws them."""
+    g = torch.Generator().manual_seed(seed)
+    o = dict(C=C, N=N, M=M, eps=1e-6)
+    o["w"] = (torch.randn(N, C, generator=g) * C ** -0.5).bfloat16().float()
+    o["b"] = torch.randn(N, generator=g) * 0.3
+    o["gamma"], o["beta"] = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2
+    o["x"] = torch.randn(M, C, generator=g) * 2.0 + 5.0 * torch.randn(M, 1, generator=g)
+    return o
+
+
+def make_lnl_int(C, N, M, seed=1401):
+    """B1: gamma = 0 and an integer beta (period 97, a prime: channels 8, 16 or 32 apart differ), W in {-1, 0, 1} with at most four
+    non-zeros per row, an integer bias: every output is an integer of magnitude <= 4 * 48 + 60 <= 256, exact in bf16."""
+    o = make_lnl_float(C, N, M, seed)
+    g = torch.Generator().manual_seed(seed + C + 3 * N)
+    ri = lambda lo, hi, shape: torch.randint(lo, hi + 1, shape, generator=g)
+    o["gamma"], o["beta"] = torch.zeros(C), ((torch.arange(C) * 37 + seed) % 97 - 48).float()
+    w = torch.zeros(N, C)
+    for _ in range(4):
+        w[torch.arange(N), ri(0, C - 1, (N,))] = (2 * ri(0, 1, (N,)) - 1).float()
+    o["w"], o["b"] = w, ri(-60, 60, (N,)).float()
+    return o
+
+
+def lnl_int_conditions(o):
+    assert not o["gamma"].any() and torch.equal(bf16_of(o["beta"]), o["beta"].double())
+    nz = (o["w"] != 0).sum(1)
+    assert (nz >= 1).all() and (nz <= 4).all() and (o["w"].abs() <= 1).all() and (o["b"] % 1 == 0).all()
+    want = ref_ln_linear(o, L.ACT_NONE)
+    assert (want % 1 == 0).all() and want.abs().max() <= 256 and torch.equal(bf16_of(want), want)
+    assert (o["beta"].abs().double() @ o["w"].abs().double().t() + o["b"].abs().double()).max() <= 256
+    return want.abs().max().item()
+
+
+def make_lnl_select(C, M, seed=1501):
+    """B2: W one-hot under a seeded permutation sigma (N = C), no bias, gamma = 1, beta = 0: y[m][n] is the normalised channel
+    sigma(n) of row m.  The rows are normal rows with a large mean and the LayerNorm edge rows at 0, 33 (wave 1), M - 2, M - 1."""
+    o = make_lnl_float(C, C, M, seed)
+    g = torch.Generator().manual_seed(seed + C)
+    o["sigma"] = torch.randperm(C, generator=g)
+    w = torch.zeros(C, C)
+    w[torch.arange(C), o["sigma"]] = 1.0
+    o["w"], o["b"], o["gamma"], o["beta"] = w, None, torch.ones(C), torch.zeros(C)
+    o["edges"] = {0: "outlier_first", 33: "constant", M - 2: "variance_eps", M - 1: "outlier_last"}
+    for m, kind in o["edges"].items():
+        o["x"][m] = ln_edge_row(kind, C)
+    return o
+
+
+def _explain_by_hidden(d, w2):
+    """Integer cases: the error row d (Cout,) of one token is W2 times the error of its hidden values.  Name the hidden unit, or
+    the hidden block, whose columns of W2 span it."""
+    w2, d = w2.double(), d.double()
+    alpha = (d @ w2) / (w2 * w2).sum(0).clamp_min(1.0)
+    resid = (d[:, None] - w2 * alpha[None, :]).abs().max(0).values
+    u = int(resid.argmin())
+    if resid[u] < 1e-6 and alpha[u] != 0:
+        return "explained by hidden unit %d alone (hidden block %d, unit %d of it) being off by %g" % (u, u // 32, u % 32, alpha[u])
+    for hb in range(w2.shape[1] // 32):
+        a = w2[:, 32 * hb:32 * hb + 32]
+        sol = torch.linalg.lstsq(a, d[:, None]).solution
+        if (a @ sol - d[:, None]).abs().max() < 1e-6 * max(1.0, d.abs().max().item()):
+            return "explained by the units of hidden block %d alone" % hb
+    return "not explained by the units of any single hidden block"
+
+
+class MlpExpect:
+    """What one launch of mlp_rows16_kernel (wave_rows 16) or ln_linear_rows_kernel (wave_rows 32, base None) must leave in its
+    output, on the Expect pattern: a buffer with canaries, the owned rows [r0, M), the written width.
+
+    base, branch  (M, width) float64: the launch must leave base + branch, and the error is measured on got - base against the
+                  branch ALONE, relative to the branch's abs-max (a residual stream many times the branch hides it otherwise)
+    before        the (rows, ld) buffer as it was handed to the launch
+    tol           bound on max|got - base - branch| / max|branch|; None (and no per_elem): bit-equal to base + branch in the
+                  buffer's dtype
+    per_elem      (rel, floor) instead: |got - base - branch| <= rel * |branch| + floor * max|branch| for every element
+    w2            integer cases: the failure also names the hidden unit or block that explains the worst row's error
+    """
+
+    def __init__(self, base, branch, before, ld, M, r0=0, wave_rows=MLP_WAVE_ROWS, tol=None, per_elem=None, w2=None):
+        self.branch = branch.cpu().double()
+        self.base = torch.zeros_like(self.branch) if base is None else base.cpu().double()
+        self.before, self.ld, self.M, self.r0, self.wave_rows = before.cpu().clone(), ld, M, r0, wave_rows
+        self.tol, self.per_elem, self.w2 = tol, per_elem, w2
+        self.width = self.branch.shape[1]
+        assert self.branch.shape == self.base.shape == (M, self.width) and 0 <= r0 < M
+        assert self.before.dim() == 2 and self.before.shape[0] >= M and self.before.shape[1] == ld >= self.width
+
+    def where(self, m, c):
+        wg, wave, row = row_place(m - self.r0, self.wave_rows)
+        return "row %d (workgroup %d, wave %d, lane row %d of the launch from row %d), channel %d" % (m, wg, wave, row, self.r0, c)
+
+    def ideal(self, base=None, branch=None):
+        """The buffer a kernel that computes the reference exactly leaves (or `base` + `branch` in its place)."""
+        buf = self.before.clone()
+        want = (self.base if base is None else base) + (self.branch if branch is None else branch)
+        buf[self.r0:self.M, :self.width] = want[self.r0:].to(buf.dtype)
+        return buf
+
+    def check(self, got, what=""):
+        """-> the error of the branch relative to its abs-max"""
+        got = got.detach().cpu()
+        assert got.shape == self.before.shape and got.dtype == self.before.dtype, what
+        rows = slice(self.r0, self.M)
+        data, base, branch = got[rows, :self.width], self.base[rows], self.branch[rows]
+        diff = (data.double() - base - branch).abs()
+        diff = torch.where(torch.isnan(diff), torch.full_like(diff, float("inf")), diff)
+        scale = max(branch.abs().max().item(), 1e-6)
+        err = diff.max().item() / scale
+        if self.per_elem is not None:
+            over = diff - (self.per_elem[0] * branch.abs() + self.per_elem[1] * scale)
+            bad, reason = over > 0, "beyond %g |want| + %g max|want|" % self.per_elem
+            diff = over
+        elif self.tol is not None:
+            bad, reason = diff > self.tol * scale, "error %.3e of the branch abs-max > %.1e" % (err, self.tol)
+        else:
+            bad, reason = data != (base + branch).to(got.dtype), "must be bit-equal to the reference"
+        if bad.any():
+            flat = int(torch.where(bad, diff, torch.full_like(diff, -1.0)).argmax())
+            m, c = self.r0 + flat // self.width, flat % self.width
+            msg = "%s: %d elements of %d rows %s; worst at %s: %r against %r" % (
+                what, bad.sum().item(), bad.any(1).sum().item(), reason, self.where(m, c), got[m, c].item(),
+                (self.base[m, c] + self.branch[m, c]).item())
+            if self.w2 is not None:
+                msg += "; the row's error is " + _explain_by_hidden(got[m, :self.width].double() - self.base[m] - self.branch[m], self.w2)
+            raise AssertionError(msg)
+        rest_got, rest_before = got.clone(), self.before.clone()
+        rest_got[rows, :self.width] = 0
+        rest_before[rows, :self.width] = 0
+        ne = rest_got != rest_before
+        if ne.any():
+            m, c = (int(v) for v in ne.nonzero()[0])
+            kind = "a pad column" if c >= self.width else ("a row at or behind M = %d" % self.M if m >= self.M else "a row below the launch's first")
+            raise AssertionError("%s: %d elements the launch does not own changed, first at row %d, column %d (%s)" % (
+                what, ne.sum().item(), m, c, kind))
+        return err
+
+    def same_bits(self, a, b, what="", r0_b=None):
+        """The owned part of two outputs of the same rows, bit for bit (b a launch from row r0_b: its rows sit in other lanes,
+        waves and workgroups).  A row's value comes from the same instructions in the same order wherever it sits."""
+        a, b = a.detach().cpu(), b.detach().cpu()
+        r0_b = self.r0 if r0_b is None else r0_b
+        lo = max(self.r0, r0_b)
+        ne = a[lo:self.M, :self.width] != b[lo:self.M, :self.width]
+        if ne.any():
+            m = lo + int(ne.any(1).nonzero()[0])
+            c = int(ne[m - lo].nonzero()[0])
+            pa, pb = row_place(m - self.r0, self.wave_rows), row_place(m - r0_b, self.wave_rows)
+            raise AssertionError("%s: %d elements of %d rows differ; first at row %d, channel %d: %r as (workgroup, wave, lane row) "
+                                 "%r against %r as %r" % (what, ne.sum().item(), ne.any(1).sum().item(), m, c, a[m, c].item(), pa,
+                                                          b[m, c].item(), pb))

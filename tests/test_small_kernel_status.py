@@ -1,4 +1,4 @@
-"""Statuses of the row, pooling, layout and SE-gate entries for descriptors they reject before any launch: one table of
+"""Statuses of the row, pooling, layout, SE-gate, fused-MLP and LayerNorm + Linear entries for descriptors they reject before any launch: one table of
 (entry, change to a valid descriptor, status).  PV_ERR_INVALID is a descriptor that contradicts itself, PV_ERR_UNSUPPORTED
 one that is consistent but has no kernel; callers tell them apart, so the table pins which of the two each case gets.
 No compute, runs without a GPU: the pointers are addresses of a host buffer that no entry dereferences."""
@@ -33,6 +33,14 @@ BASE["pv_mean_rows"] = (L.RowsDesc, dict(_ROWS, rows_per_batch=5))
 BASE["pv_add_posenc"] = (L.PosencDesc, dict(x=P, pos_spatial=P, B=1, T=2, HW=4, C=20, ld=24, dtype=L.PV_F32))
 BASE["pv_add_act"] = (L.AddDesc, dict(a=P, b=P, y=P, rows=5, C=20, lda=24, ldb=24, ldy=24, dtype=L.PV_F32))
 BASE["pv_ensemble_scores"] = (L.EnsembleDesc, dict(logits=P, video_index=P, accum=P, counts=P, N=3, C=10, ld=16, V=2, mode=0))
+# csrc/pv_mlp.hip: operand mode (bf16 x, residual, b2), LayerNorm mode (fp32 x, C == Cout, no residual), operand mode with yn
+_MLP = dict(x=P, w12=P, y=P, b2=P, M=10, C=96, H=64, Cout=192, ldx=96, ldy=192, act=L.ACT_GELU, dtype=L.PV_BF16)
+BASE["pv_mlp_rows"] = (L.MlpDesc, dict(_MLP, residual=P, ldr=192))
+BASE["pv_mlp_rows/ln"] = (L.MlpDesc, dict(_MLP, Cout=96, ldy=96, ln_gamma=P, ln_beta=P, ln_eps=1e-6))
+BASE["pv_mlp_rows/yn"] = (L.MlpDesc, dict(_MLP, yn=P, nn_gamma=P, nn_beta=P, ldyn=192, nn_eps=1e-6))
+BASE["pv_ln_linear_rows"] = (L.LnLinearDesc, dict(x=P, wb=P, y=P, ln_gamma=P, ln_beta=P, M=10, C=96, N=64, ldx=96, ldy=64,
+                                                  dtype=L.PV_BF16, ln_eps=1e-6))
+SUPPORTED = {"pv_mlp_rows": "pv_mlp_rows_supported", "pv_ln_linear_rows": "pv_ln_linear_rows_supported"}
 
 
 def _each(entry, status, **values):
@@ -97,6 +105,29 @@ TABLE = (
     # ---- pv_ensemble_scores
     + _each("pv_ensemble_scores", INVALID, logits=None, video_index=None, accum=None, counts=None, N=0, C=0, V=0, ld=8,
             mode=(2, -1))
+    # ---- pv_mlp_rows (check() of csrc/pv_mlp.hip, then the (C, Cout) table of the entry)
+    + _each("pv_mlp_rows", INVALID, x=None, w12=None, y=None, M=(0, -1, 0x80000000),
+            ldx=(88, 100), ldy=(184, 194), ldr=(184, 194))                # too small; bf16 rows of 8, fp32 rows of 4 elements
+    + _each("pv_mlp_rows", UNSUPPORTED, dtype=(NO_DTYPE, L.PV_F32), C=(0, 80), H=(0, 48), Cout=(0, 200))
+    + [("pv_mlp_rows", dict(C=768, ldx=768), UNSUPPORTED),                # consistent, but no (C, Cout) instantiation
+       ("pv_mlp_rows", dict(C=384, ldx=384), UNSUPPORTED),
+       ("pv_mlp_rows", dict(C=128, ldx=128), UNSUPPORTED),
+       ("pv_mlp_rows", dict(x=None, dtype=NO_DTYPE), INVALID)]            # the pointers are checked before the dtype
+    # LayerNorm mode: beta and b2 required, C == Cout, the residual is x itself; fp32 rows of 4 elements
+    + _each("pv_mlp_rows/ln", INVALID, ln_beta=None, b2=None, residual=P, ldx=(92, 98), ldy=(88, 98))
+    + [("pv_mlp_rows/ln", dict(Cout=192, ldy=192), INVALID),
+       ("pv_mlp_rows/ln", dict(C=128, Cout=128, ldx=128, ldy=128), UNSUPPORTED),
+       ("pv_mlp_rows/ln", dict(C=768, Cout=768, ldx=768, ldy=768), UNSUPPORTED),
+       ("pv_mlp_rows/ln", dict(dtype=L.PV_F32), UNSUPPORTED)]
+    # yn needs its parameters and a bf16 row of 8 elements
+    + _each("pv_mlp_rows/yn", INVALID, nn_gamma=None, nn_beta=None, ldyn=(0, 184, 196))
+    # ---- pv_ln_linear_rows (check_ln_linear(), then the C switch of the entry)
+    + _each("pv_ln_linear_rows", INVALID, x=None, wb=None, y=None, M=(0, -1, 0x80000000), ln_gamma=None, ln_beta=None,
+            ldx=(92, 98), ldy=(56, 68))
+    + _each("pv_ln_linear_rows", UNSUPPORTED, dtype=(NO_DTYPE, L.PV_F32), C=(0, 80), N=(0, 48))
+    + [("pv_ln_linear_rows", dict(C=128, ldx=128), UNSUPPORTED),
+       ("pv_ln_linear_rows", dict(C=1536, ldx=1536), UNSUPPORTED),
+       ("pv_ln_linear_rows", dict(ln_gamma=None, dtype=NO_DTYPE), UNSUPPORTED)]   # the dtype is checked before the parameters
 )
 
 
@@ -109,3 +140,23 @@ def test_every_rejected_descriptor_gets_its_status(pv_lib):
         if got != status:
             wrong.append("%s %s: status %d, expected %d" % (entry, change, got, status))
     assert not wrong, "\n".join(wrong)
+
+
+def test_the_supported_queries_are_zero_exactly_where_the_launch_declines(pv_lib):
+    """pv_mlp_rows_supported / pv_ln_linear_rows_supported: 1 for the descriptors the entries would launch, 0 for every row of
+    the table (whichever of the two statuses the launch gives) and for no descriptor at all."""
+    wrong = []
+    for entry, (cls, base) in BASE.items():
+        if entry.split("/")[0] in SUPPORTED and getattr(pv_lib, SUPPORTED[entry.split("/")[0]])(C.byref(cls(**base))) != 1:
+            wrong.append("%s: its base descriptor is not supported" % entry)
+    rows = 0
+    for entry, change, status in TABLE:
+        if entry.split("/")[0] not in SUPPORTED:
+            continue
+        cls, base = BASE[entry]
+        q = getattr(pv_lib, SUPPORTED[entry.split("/")[0]])
+        got = q(None) if change is None else q(C.byref(cls(**dict(base, **change))))
+        rows += 1
+        if got != 0 or status >= 0:
+            wrong.append("%s %s: supported says %d, the launch status is %d" % (entry, change, got, status))
+    assert rows > 60 and not wrong, "\n".join(wrong)
