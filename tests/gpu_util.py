@@ -1,5 +1,6 @@
 """Helpers for the -m gpu tests: raw C-ABI calls on torch-owned device memory."""
 import ctypes as C
+import math
 
 import torch
 
@@ -1385,3 +1386,452 @@ class MlpExpect:
             raise AssertionError("%s: %d elements of %d rows differ; first at row %d, channel %d: %r as (workgroup, wave, lane row) "
                                  "%r against %r as %r" % (what, ne.sum().item(), ne.any(1).sum().item(), m, c, a[m, c].item(), pa,
                                                           b[m, c].item(), pb))
+
+
+# ------------------------------------------------------------------ csrc/pv_attn.hip, pv_attn64.hip (pv_attention)
+# Float64 references, operand families, the mirror of the deferred-rescale rule, an fp32 replay of the kernels' arithmetic and
+# the checker of tests/test_gpu_attention_kernels.py.  tests/test_attention_kernel_checks.py feeds the checker its own reference
+# and defective replays and checks, on the CPU, every claim the families make.
+#
+# Operands are (B, N, heads, D) tensors of values the storage type holds exactly.  AttnLayout says where they lie: every
+# operand is a flat buffer, item b of operand x starts at off[x] + b * bs[x], row n of it at + n * ld[x], head h at + h * D.
+ATTN_WG_ROWS, ATTN_WAVE_ROWS = 128, 32     # kQB / kRowsWG; one 32-row block per wave
+ATTN_DEFER = 8.0                           # kDefer
+ATTN_LOG2E_F32 = 1.44269504088896340736    # the literal the kernels multiply d.scale by (as fp32)
+ATTN_INT_SCALE = 0.08664339780807495       # families A and B: fp32(scale) * fp32(log2 e) == 0.125 exactly
+ATTN_GUARD_TILES = 6                       # NaN rows behind the last item of Q, K and V, in key tiles
+ATTN_ROUTES = {                            # (dtype, head_dim) -> (routed symbol, instantiation)
+    (torch.bfloat16, 96): ("attn_w64_kernel", "attn_w64_kernel"),
+    (torch.bfloat16, 64): ("attn_pipe_kernel", "attn_pipe_kernel<64>"),
+    (torch.bfloat16, 32): ("attn_pipe_kernel", "attn_pipe_kernel<32>"),
+    (torch.bfloat16, 128): ("attn_kernel", "attn_kernel<bf16_t, 128>"),
+    (torch.float32, 32): ("attn_kernel", "attn_kernel<float, 32>"),
+    (torch.float32, 64): ("attn_kernel", "attn_kernel<float, 64>"),
+    (torch.float32, 96): ("attn_kernel", "attn_kernel<float, 96>"),
+    (torch.float32, 128): ("attn_kernel", "attn_kernel<float, 128>"),
+}
+ATTN_NOT_LAUNCHED = ("attn_kernel<bf16_t, 32>", "attn_kernel<bf16_t, 64>", "attn_kernel<bf16_t, 96>")   # K / V beyond 2 GiB only
+# 1, 1, 1, 1, 2, 2, 3, 4, 7, 8 (ragged), 8 tiles: both tail forms of the loop unrolled by two, two trips of it, every
+# (t & 1, t % 3) pair in a `more` step (t = 0 .. 6)
+ATTN_NK = {64: (1, 3, 37, 64, 65, 128, 192, 256, 448, 485, 512), 32: (1, 3, 19, 32, 33, 64, 96, 128, 224, 243, 256)}
+ATTN_TILES = (1, 1, 1, 1, 2, 2, 3, 4, 7, 8, 8)
+
+
+def attn_kt(dtype):
+    return 64 if dtype == torch.bfloat16 else 32
+
+
+def attn_step_form(t, Nk, KT):
+    """The form of the tile step that consumes key tile t (pv_attn64.hip / attn_pipe_kernel; attn_kernel has one loop body, for
+    which the same words name the tile's place in it)."""
+    nt = cdiv(Nk, KT)
+    if t + 1 < nt:
+        form = "`more` step, parity %d, V slot %d" % (t & 1, t % 3)
+    else:
+        form = "ragged last step" if Nk % KT else "last step"
+    return form + (", scores from the prologue" if t == 0 else "")
+
+
+def attn_log2_scale(scale):
+    """The factor of the exp2 domain as the kernels form it: fp32(scale) * fp32(log2 e), one fp32 rounding."""
+    f = torch.tensor(scale, dtype=torch.float32) * torch.tensor(ATTN_LOG2E_F32, dtype=torch.float32)
+    return float(f)
+
+
+def ref_attention(q, k, v, log2_scale, residual_q):
+    """float64 softmax attention in the exp2 domain: weights 2^(log2_scale * q.k).  -> ((B, Nq, H, D) output, (B, H, Nq) index of
+    each row's dominant key)"""
+    q, k, v = q.double(), k.double(), v.double()
+    s = torch.einsum("bqhd,bkhd->bhqk", q, k) * log2_scale
+    p = torch.exp2(s - s.max(-1, keepdim=True).values)
+    o = torch.einsum("bhqk,bkhd->bqhd", p / p.sum(-1, keepdim=True), v)
+    return (o + q if residual_q else o), s.argmax(-1)
+
+
+def _attn_pad_rows(x, w64):
+    """Rows of one (batch, head) filled up to whole waves the way the kernels fill their idle lanes: attn_w64_kernel repeats row
+    Nq - 1, the others hold zeros."""
+    n = x.shape[0]
+    pad = cdiv(n, ATTN_WAVE_ROWS) * ATTN_WAVE_ROWS - n
+    if not pad:
+        return x
+    fill = x[-1:].expand(pad, -1) if w64 else torch.zeros(pad, x.shape[1], dtype=x.dtype)
+    return torch.cat([x, fill])
+
+
+def attn_mirror(args, KT, w64):
+    """The deferred-rescale rule alone, on the (Nq, Nk) exponent arguments of one (batch, head): per wave of 32 rows, m_run from
+    a full first tile for attn_w64_kernel and from -1e30 otherwise, advanced where __any(mx > m_run + kDefer).  Coverage only --
+    no expected value comes from here.  -> list of events dict(wave, t, rescaled, rise (per lane, above the held maximum; None
+    before the first finite maximum), stale (largest argument above the maximum held AFTER the decision))"""
+    Nq, Nk = args.shape
+    a = _attn_pad_rows(args.double(), w64)
+    nt, ev = cdiv(Nk, KT), []
+    for w in range(a.shape[0] // ATTN_WAVE_ROWS):
+        rows = a[w * ATTN_WAVE_ROWS:(w + 1) * ATTN_WAVE_ROWS]
+        m = torch.full((ATTN_WAVE_ROWS,), -1e30, dtype=torch.float64)
+        if w64 and KT <= Nk:
+            m = rows[:, :KT].max(1).values
+        for t in range(nt):
+            mx = rows[:, t * KT:min((t + 1) * KT, Nk)].max(1).values
+            started = bool((m > -1e29).all())
+            rise = mx - m
+            trip = bool((mx > m + ATTN_DEFER).any())
+            if trip:
+                m = torch.maximum(m, mx)
+            ev.append(dict(wave=w, t=t, rescaled=trip, rise=rise if started else None, stale=float((mx - m).max())))
+    return ev
+
+
+def attn_mirror_coverage(events, Nk, KT):
+    """What a list of mirror events contains, as a set of names (the list family B must cover per route)."""
+    nt, got = cdiv(Nk, KT), set()
+    for e in events:
+        if e["rise"] is None:
+            continue
+        top = float(e["rise"].max())
+        if not e["rescaled"] and top == ATTN_DEFER:
+            got.add("no rescale at a rise of exactly 8")
+        if e["rescaled"] and top == ATTN_DEFER + 1:
+            got.add("rescale at a rise of 9")
+        if e["stale"] == ATTN_DEFER:
+            got.add("stale P of 2^8")
+        if e["rescaled"]:
+            over = e["rise"] > ATTN_DEFER
+            if over.sum() == 1 and ((e["rise"] > 0) & ~over).sum() >= 8:
+                got.add("one-lane rescale")
+            if top <= 12:     # a moderate alpha, 2^-1 .. 2^-12 on the lane that rose most
+                got.add(("rescale in a " + attn_step_form(e["t"], Nk, KT)).split(", V slot")[0].split(", scores")[0])
+    return got
+
+
+ATTN_B_COVER = {"no rescale at a rise of exactly 8", "rescale at a rise of 9", "stale P of 2^8", "one-lane rescale",
+                "rescale in a `more` step, parity 0", "rescale in a `more` step, parity 1", "rescale in a last step",
+                "rescale in a ragged last step"}
+ATTN_DEFECTS = ("swap_v", "stale_v", "alpha_l", "pair_l", "mask_short", "mask_long", "halves", "head")
+
+
+def replay_attention(q, k, v, log2_scale, residual_q, dtype, w64, defect=None):
+    """fp32 replay of the kernels' arithmetic: KT-key tiles, online softmax in the exp2 domain with the deferred rescale decided
+    per 32-row wave, P rounded to bf16 for the PV product (bf16 routes), l from the unrounded p, one rounding at the end.
+    defect: one of ATTN_DEFECTS --
+      swap_v      keys 5 and 6 of every 16-key slot read each other's V row
+      stale_v     from tile 3 on a tile's V comes from three tiles earlier (a V ring slot not rewritten)
+      alpha_l     alpha not applied to l in any rescale after a row's first
+      pair_l      the first pair of p of every tile missing from l
+      mask_short  key Nk - 1 masked too;  mask_long  key Nk (a zero row, score 0) not masked
+      halves      the two lane halves (keys with bit 2 clear / set) each keep their own running maximum
+      head        head h reads K and V of head h + 1 (the last one of head 0)
+    -> (B, Nq, H, D) in `dtype`"""
+    f32 = torch.float32
+    bf16 = dtype == torch.bfloat16
+    KT = attn_kt(dtype)
+    B, Nq, H, D = q.shape
+    Nk = k.shape[1]
+    nt = cdiv(Nk, KT)
+    sc = torch.tensor(log2_scale, dtype=f32)
+    out = torch.empty(B, Nq, H, D, dtype=dtype)
+    half_of_key = ((torch.arange(KT) >> 2) & 1).bool()            # crow(r, hi): the keys of lane half 1 have bit 2 set
+    half_of_chan = ((torch.arange(D) >> 2) & 1).bool()            # d0 = db * 32 + 8 g + 4 hi
+    for b in range(B):
+        for h in range(H):
+            hk = (h + 1) % H if defect == "head" else h
+            qq = _attn_pad_rows(q[b, :, h].to(f32), w64)
+            R = qq.shape[0]
+            kk = torch.zeros(nt * KT, D, dtype=f32)
+            vv = torch.zeros(nt * KT, D, dtype=f32)
+            kk[:Nk], vv[:Nk] = k[b, :, hk].to(f32), v[b, :, hk].to(f32)
+            valid = torch.arange(nt * KT) < (Nk - 1 if defect == "mask_short" else Nk + 1 if defect == "mask_long" else Nk)
+            nh = 2 if defect == "halves" else 1
+            m = torch.full((R, nh), -1e30, dtype=f32)
+            if w64 and KT <= Nk:
+                s0 = (qq @ kk[:KT].T) * sc
+                m = torch.stack([s0[:, ~half_of_key].max(1).values, s0[:, half_of_key].max(1).values], 1) if nh == 2 \
+                    else s0.max(1, keepdim=True).values
+            l = torch.zeros(R, nh, dtype=f32)
+            o = torch.zeros(R, D, dtype=f32)
+            first = torch.ones(R, dtype=torch.bool)
+            for t in range(nt):
+                ks = slice(t * KT, (t + 1) * KT)
+                s = qq @ kk[ks].T
+                s = torch.where(valid[ks][None, :], s, torch.full_like(s, -1e30))
+                if nh == 2:
+                    mx = torch.stack([s[:, ~half_of_key].max(1).values, s[:, half_of_key].max(1).values], 1) * sc
+                else:
+                    mx = s.max(1, keepdim=True).values * sc
+                trip = (mx > m + ATTN_DEFER).any(1).view(-1, ATTN_WAVE_ROWS).any(1).repeat_interleave(ATTN_WAVE_ROWS)
+                m_new = torch.where(trip[:, None], torch.maximum(m, mx), m)
+                alpha = torch.exp2(m - m_new)
+                m = m_new
+                l = l * (torch.where(first[:, None], alpha, torch.ones_like(alpha)) if defect == "alpha_l" else alpha)
+                first = first & ~trip
+                o = o * (torch.where(half_of_chan[None, :], alpha[:, 1:2], alpha[:, 0:1]) if nh == 2 else alpha)
+                mk = torch.where(half_of_key[None, :], m[:, 1:2], m[:, 0:1]) if nh == 2 else m
+                p = torch.exp2(s * sc - mk)
+                pl = p.clone()
+                if defect == "pair_l":
+                    pl[:, :2] = 0
+                if nh == 2:
+                    l = l + torch.stack([pl[:, ~half_of_key].sum(1), pl[:, half_of_key].sum(1)], 1)
+                else:
+                    l = l + pl.sum(1, keepdim=True)
+                vt = vv[slice((t - 3) * KT, (t - 2) * KT) if defect == "stale_v" and t >= 3 else ks]
+                if defect == "swap_v":
+                    idx = torch.arange(KT)
+                    idx[5::16], idx[6::16] = torch.arange(6, KT, 16), torch.arange(5, KT, 16)
+                    vt = vt[idx]
+                o = o + (p.to(torch.bfloat16).to(f32) if bf16 else p) @ vt
+            res = o * (1.0 / l.sum(1, keepdim=True))
+            if residual_q:
+                res = res + qq
+            out[b, :, h] = res[:Nq].to(dtype)
+    return out
+
+
+class AttnLayout:
+    """Where the operands of one pv_attention case lie.
+      packed  ld = heads * D, items back to back, one buffer per operand
+      wide    ldq, ldk, ldv, ldo all different and wider than heads * D, three spare rows and a different odd gap behind every item
+      fused   q, k and v are channel slices of ONE buffer of rows 3 * heads * D + 8 wide; o as in `wide`
+    Every element of Q, K and V that is not an operand value is NaN: the channels past the width, the rows between items and
+    ATTN_GUARD_TILES key tiles of rows behind the last item.  Every element of O is the canary."""
+
+    def __init__(self, kind, B, H, D, Nq, Nk, dtype):
+        self.kind, self.B, self.H, self.D, self.Nq, self.Nk, self.dtype = kind, B, H, D, Nq, Nk, dtype
+        W, guard = H * D, ATTN_GUARD_TILES * attn_kt(dtype)
+        n = dict(q=Nq, k=Nk, v=Nk, o=Nq)
+        self.off = dict(q=0, k=0, v=0, o=0)
+        if kind == "packed":
+            self.ld = dict.fromkeys("qkvo", W)
+            self.bs = {x: n[x] * W for x in "qkvo"}
+        else:
+            self.ld = dict(q=W + 8, k=W + 16, v=W + 24, o=W + 32)
+            self.bs = {x: (n[x] + 3) * self.ld[x] + 8 * (i + 1) for i, x in enumerate("qkvo")}
+            if kind == "fused":
+                ld = 3 * W + 8
+                self.ld.update(q=ld, k=ld, v=ld)
+                self.bs.update(dict.fromkeys("qkv", (max(Nq, Nk) + 3) * ld + 8))
+                self.off.update(k=W, v=2 * W)
+        rows = {x: (max(Nq, Nk) if kind == "fused" and x != "o" else n[x]) + (3 if x == "o" else guard) for x in "qkvo"}
+        self.size = {x: (B - 1) * self.bs[x] + rows[x] * self.ld[x] for x in "qkvo"}
+
+    def view(self, buf, x, b=None, h=None, rows=None):
+        """the (items, rows, heads, D) elements of operand x inside its flat buffer (a strided view)"""
+        b, h = b or (0, self.B), h or (0, self.H)
+        rows = rows or (0, self.Nq if x in "qo" else self.Nk)
+        off = self.off[x] + b[0] * self.bs[x] + rows[0] * self.ld[x] + h[0] * self.D
+        return buf.as_strided((b[1] - b[0], rows[1] - rows[0], h[1] - h[0], self.D), (self.bs[x], self.ld[x], self.D, 1), off)
+
+    def inputs(self, q, k, v):
+        """-> {"q", "k", "v"}: flat NaN-filled buffers holding the operands (one shared buffer when fused)"""
+        nan = float("nan")
+        if self.kind == "fused":
+            one = torch.full((self.size["q"],), nan, dtype=self.dtype)
+            bufs = dict(q=one, k=one, v=one)
+        else:
+            bufs = {x: torch.full((self.size[x],), nan, dtype=self.dtype) for x in "qkv"}
+        for x, t in (("q", q), ("k", k), ("v", v)):
+            assert (t.to(self.dtype).double() == t.double()).all(), "operand %s is not exact in %s" % (x, self.dtype)
+            self.view(bufs[x], x).copy_(t.to(self.dtype))
+        return bufs
+
+    def output(self):
+        return torch.full((self.size["o"],), CANARY, dtype=self.dtype)
+
+
+class AttnExpect:
+    """What one launch of pv_attention must leave in its output buffer.
+
+    want    (B, Nq, H, D) float64 reference;  dom  (B, H, Nq) the dominant key of every row (ref_attention gives both)
+    lay     the AttnLayout;  route  the routed symbol
+    mode    "bits": bit-equal to want in the buffer's dtype;  "elem": |got - want| <= bound |want| per element;
+            "row": max|got - want| over a query row / max|want| over that row <= bound
+    b, h, rows  the sub-range the launch owns (default everything): every other element of O keeps the canary
+    A failure names batch item, head, query row, workgroup, wave and lane, channel and channel block, and the key tile and step
+    form the row's dominant key lies in."""
+
+    def __init__(self, want, dom, lay, route, mode, bound=None, b=None, h=None, rows=None):
+        self.want, self.dom, self.lay, self.route, self.mode, self.bound = want.double(), dom, lay, route, mode, bound
+        self.b, self.h, self.rows = b or (0, lay.B), h or (0, lay.H), rows or (0, lay.Nq)
+        assert mode in ("bits", "elem", "row") and (bound is None) == (mode == "bits")
+        assert self.want.shape == (lay.B, lay.Nq, lay.H, lay.D) and self.rows[0] % ATTN_WG_ROWS == 0
+
+    def _own(self, t):
+        return t[self.b[0]:self.b[1], self.rows[0]:self.rows[1], self.h[0]:self.h[1]]
+
+    def where(self, b, m, h, c):
+        lay, KT = self.lay, attn_kt(self.lay.dtype)
+        r = m - self.rows[0]
+        j = int(self.dom[b, h, m])
+        nqb = cdiv(self.rows[1] - self.rows[0], ATTN_WG_ROWS)
+        item = ((b - self.b[0]) * (self.h[1] - self.h[0]) + h - self.h[0]) * nqb + r // ATTN_WG_ROWS
+        hi = (c >> 2) & 1
+        return ("batch item %d, head %d, query row %d (work item %d of the launch, query block %d, wave %d, lane %d), channel %d "
+                "(channel block %d, lane half %d); %s, Nk = %d: the row's dominant key %d is in key tile %d (16-key slot %d, "
+                "lane half %d), consumed by the %s" % (
+                    b, h, m, item, r // ATTN_WG_ROWS, r % ATTN_WG_ROWS // ATTN_WAVE_ROWS, r % ATTN_WAVE_ROWS + 32 * hi, c,
+                    c // 32, hi, self.route, lay.Nk, j, j // KT, j % KT // 16, (j >> 2) & 1, attn_step_form(j // KT, lay.Nk, KT)))
+
+    def ideal(self, values=None):
+        """The buffer a kernel that computes the reference (or `values`, (B, Nq, H, D)) exactly leaves."""
+        buf = self.lay.output()
+        self.lay.view(buf, "o", self.b, self.h, self.rows).copy_(self._own(self.want if values is None else values).to(buf.dtype))
+        return buf
+
+    def values(self, buf):
+        return self.lay.view(buf.detach().cpu(), "o", self.b, self.h, self.rows).clone()
+
+    def check(self, got, what=""):
+        """-> the worst error in the mode's own metric (0 for "bits")"""
+        got = got.detach().cpu()
+        assert got.shape == (self.lay.size["o"],) and got.dtype == self.lay.dtype, what
+        data, want = self.values(got), self._own(self.want)
+        diff = (data.double() - want).abs()
+        diff = torch.where(torch.isnan(diff), torch.full_like(diff, float("inf")), diff)
+        if self.mode == "bits":
+            over, reason = (data != want.to(got.dtype)).double(), "must be bit-equal to the reference"
+            err = 0.0
+        elif self.mode == "elem":
+            rel = diff / want.abs().clamp_min(1e-300)
+            over, err = diff - self.bound * want.abs(), rel.max().item()
+            reason = "beyond %.3e |want| (worst %.3e)" % (self.bound, err)
+        else:
+            rel = diff.max(-1, keepdim=True).values / want.abs().max(-1, keepdim=True).values.clamp_min(1e-30)
+            over, err = (rel - self.bound).expand_as(diff) * (diff == diff.max(-1, keepdim=True).values), rel.max().item()
+            reason = "are the worst of a query row beyond %.1e of the row's own abs-max (worst row %.3e)" % (self.bound, err)
+        bad = over > 0
+        if bad.any():
+            flat = int(torch.where(bad, over, torch.full_like(over, -1.0)).argmax())
+            nb, nr, nh, D = data.shape
+            b, m, h, c = flat // (nr * nh * D), flat // (nh * D) % nr, flat // D % nh, flat % D
+            raise AssertionError("%s: %d elements of %d rows %s; worst at %s: %r against %r" % (
+                what, bad.sum().item(), bad.any(-1).sum().item(), reason,
+                self.where(b + self.b[0], m + self.rows[0], h + self.h[0], c), data[b, m, h, c].item(), want[b, m, h, c].item()))
+        rest = got.clone()
+        self.lay.view(rest, "o", self.b, self.h, self.rows).fill_(CANARY)
+        ne = rest != CANARY
+        if ne.any():
+            raise AssertionError("%s: %d elements of O the launch does not own changed (pad channels, rows behind Nq, gaps between "
+                                 "items, other heads / rows / items of a sub-launch), first at buffer offset %d" % (
+                                     what, ne.sum().item(), int(ne.nonzero()[0])))
+        return err
+
+    def same_bits(self, full, part, what=""):
+        """The owned sub-range of `part` (this launch) against the same rows of `full` (the launch of everything), bit for bit."""
+        a, b_ = self.lay.view(full.detach().cpu(), "o", self.b, self.h, self.rows), self.values(part)
+        ne = a != b_
+        if ne.any():
+            b, m, h, c = (int(x) for x in ne.nonzero()[0])
+            raise AssertionError("%s: %d elements of %d rows differ between the full launch and the sub-launch; first at %s: %r "
+                                 "against %r" % (what, ne.sum().item(), ne.any(-1).sum().item(),
+                                                 self.where(b + self.b[0], m + self.rows[0], h + self.h[0], c),
+                                                 a[b, m, h, c].item(), b_[b, m, h, c].item()))
+
+
+# ---- family A: selection.  K rows are +-1 codes, q_i = 64 k_t(i), t(i) = (a i + b0) mod Nk: with ATTN_INT_SCALE the selected
+#      exponent argument is 8 D, every other one 8 dot(k_t, k_j)
+ATTN_A_GAP = 40.0
+
+
+def attn_select_nq(Nk):
+    return Nk + ATTN_WG_ROWS + 5            # every key selected, from more than one wave; a ragged last workgroup
+
+
+def make_attn_select(B, H, D, Nq, Nk, seed=1601):
+    g = torch.Generator().manual_seed(seed + 7 * D + Nk)
+    k = (torch.randint(0, 2, (B, Nk, H, D), generator=g) * 2 - 1).double()
+    pool = torch.tensor([x for x in range(-100, 101) if x not in (0, 64, -64)], dtype=torch.float64)   # v and v + q never zero:
+    v = pool[torch.randint(0, len(pool), (B, Nk, H, D), generator=g)]                                  # a relative bound means something
+    a = next(x for x in (37, 29, 23, 19, 17, 13, 11, 7, 5, 3, 1) if x < max(Nk, 2) and math.gcd(x, Nk) == 1)
+    i = torch.arange(Nq)
+    sel = torch.stack([torch.stack([(a * i + 11 * b + 5 * h) % Nk for h in range(H)]) for b in range(B)])    # (B, H, Nq)
+    q = torch.stack([torch.stack([64.0 * k[b, sel[b, h], h] for h in range(H)], 1) for b in range(B)])         # (B, Nq, H, D)
+    return dict(q=q, k=k, v=v, sel=sel, a=a, scale=ATTN_INT_SCALE)
+
+
+def attn_select_conditions(o):
+    """Asserted on the CPU before any launch: every non-selected argument at least ATTN_A_GAP below the selected one, no two rows
+    of V equal, every key selected, the selected argument 8 D.  -> the smallest gap"""
+    q, k, v, sel = o["q"], o["k"], o["v"], o["sel"]
+    B, Nk, H, D = k.shape
+    assert attn_log2_scale(o["scale"]) == 0.125
+    args = torch.einsum("bqhd,bkhd->bhqk", q, k) * 0.125
+    top = args.gather(-1, sel[..., None])[..., 0]
+    assert (top == 8 * D).all()
+    rest = args.scatter(-1, sel[..., None], -1e9).max(-1).values
+    gap = (top - rest).min().item() if Nk > 1 else float("inf")
+    assert gap >= ATTN_A_GAP, "selection gap %g < %g" % (gap, ATTN_A_GAP)
+    for b in range(B):
+        for h in range(H):
+            assert len({tuple(r.tolist()) for r in v[b, :, h]}) == Nk, "two rows of V are equal"
+            assert len(set(sel[b, h].tolist())) == Nk, "a key is never selected"
+            both = v[b, sel[b, h], h] + q[b, :, h]              # residual_q: integers of magnitude <= 164, bf16 values, never zero
+            assert (both.abs() <= 164).all() and (both != 0).all() and (both.bfloat16().double() == both).all()
+    assert (v != 0).all()
+    return gap
+
+
+# ---- family B: integer score levels.  k[:, 0] = 8 n_j, k[:, 1] = 8 u_j, q_i = (1, r_i, 0, ...): with ATTN_INT_SCALE the exponent
+#      arguments are the integers n_j + r_i u_j; V holds integers in [1, 8]
+ATTN_B_SCHEDULES = ("flat", "plus7", "plus8", "plus9", "falling", "saw", "one_lane")
+ATTN_SAW = (0, 12, 3, 20, 5, 9, 30)
+
+
+def attn_levels(schedule, nt):
+    if schedule in ("flat", "one_lane"):
+        return [40] * nt
+    if schedule == "falling":
+        return [100 - 9 * t for t in range(nt)]
+    if schedule == "saw":
+        return [40 + ATTN_SAW[t % len(ATTN_SAW)] + 40 * (t // len(ATTN_SAW)) for t in range(nt)]
+    return [20 + {"plus7": 7, "plus8": 8, "plus9": 9}[schedule] * t for t in range(nt)]
+
+
+def make_attn_levels(schedule, B, H, D, Nq, Nk, KT, seed=1701):
+    g = torch.Generator().manual_seed(seed + Nk + D)
+    nt = cdiv(Nk, KT)
+    n = torch.empty(B, Nk, H, dtype=torch.float64)
+    for t, lev in enumerate(attn_levels(schedule, nt)):
+        lo, hi = t * KT, min((t + 1) * KT, Nk)
+        n[:, lo:hi] = lev - torch.randint(1, 7, (B, hi - lo, H), generator=g).double()
+        pos = torch.randint(0, hi - lo, (B, H), generator=g)                # the tile maximum at a drawn position
+        for b in range(B):
+            for h in range(H):
+                n[b, lo + pos[b, h], h] = lev
+    k = torch.zeros(B, Nk, H, D, dtype=torch.float64)
+    q = torch.zeros(B, Nq, H, D, dtype=torch.float64)
+    k[..., 0], q[..., 0] = 8 * n, 1.0
+    if schedule == "one_lane":
+        # one late key 5 above the flat level for everyone (no lane trips on it alone) and 10 above for the ONE query per wave
+        # whose r is 1: that lane trips __any, its 31 neighbours advance by 5
+        j = min(Nk - 1, (nt - 1) * KT + 2) if nt > 1 else Nk - 1
+        k[:, j, :, 0] = 8 * (40 + 5)
+        k[:, j, :, 1] = 8 * 5
+        q[:, 13::ATTN_WAVE_ROWS, :, 1] = 1.0
+    v = torch.randint(1, 9, (B, Nk, H, D), generator=g).double()
+    return dict(q=q, k=k, v=v, scale=ATTN_INT_SCALE, schedule=schedule)
+
+
+def attn_level_args(o, b=0, h=0):
+    """the integer exponent arguments of one (batch, head), (Nq, Nk)"""
+    a = (o["q"][b, :, h] @ o["k"][b, :, h].T) * 0.125
+    assert (a == a.round()).all()
+    return a
+
+
+def attn_level_bound(dtype, Nk):
+    """bf16: one bf16 ulp; fp32: the worst-case summation bound for positive terms, numerator and denominator"""
+    return 2.0 ** -7 if dtype == torch.bfloat16 else 2.0 * (Nk + 8) * 2.0 ** -24
+
+
+# ---- family C: normal operands at three logit scales, judged per query row
+ATTN_C_VARIANCES = (1, 4, 12)
+ATTN_C_NK = {64: (65, 197, 485), 32: (33, 101, 243)}
+ATTN_C_NQ = 165
+
+
+def make_attn_float(B, H, D, Nq, Nk, variance, dtype, seed=1801):
+    std = float(variance) ** 0.5
+    f = std ** 0.5                          # q and k each by sqrt(std): the scores' standard deviation is std
+    mk = lambda n, s, by: (randn((B, n, H, D), seed + s + Nk + D) * by).to(dtype).double()
+    return dict(q=mk(Nq, 1, f), k=mk(Nk, 2, f), v=mk(Nk, 3, 1.0), scale=D ** -0.5, variance=variance)

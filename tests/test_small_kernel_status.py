@@ -1,4 +1,4 @@
-"""Statuses of the row, pooling, layout, SE-gate, fused-MLP and LayerNorm + Linear entries for descriptors they reject before any launch: one table of
+"""Statuses of the row, pooling, layout, SE-gate, fused-MLP, LayerNorm + Linear and attention entries for descriptors they reject before any launch: one table of
 (entry, change to a valid descriptor, status).  PV_ERR_INVALID is a descriptor that contradicts itself, PV_ERR_UNSUPPORTED
 one that is consistent but has no kernel; callers tell them apart, so the table pins which of the two each case gets.
 No compute, runs without a GPU: the pointers are addresses of a host buffer that no entry dereferences."""
@@ -40,6 +40,11 @@ BASE["pv_mlp_rows/ln"] = (L.MlpDesc, dict(_MLP, Cout=96, ldy=96, ln_gamma=P, ln_
 BASE["pv_mlp_rows/yn"] = (L.MlpDesc, dict(_MLP, yn=P, nn_gamma=P, nn_beta=P, ldyn=192, nn_eps=1e-6))
 BASE["pv_ln_linear_rows"] = (L.LnLinearDesc, dict(x=P, wb=P, y=P, ln_gamma=P, ln_beta=P, M=10, C=96, N=64, ldx=96, ldy=64,
                                                   dtype=L.PV_BF16, ln_eps=1e-6))
+# csrc/pv_attn.hip: 2 items x 7 rows of 2 heads x 32 channels; K / V 5 rows
+_ATTN = dict(q=P, k=P, v=P, o=P, B=2, heads=2, head_dim=32, Nq=7, Nk=5, ldq=64, ldk=64, ldv=64, ldo=64, q_bs=448, k_bs=320, v_bs=320,
+             o_bs=448, scale=0.125)
+BASE["pv_attention"] = (L.AttentionDesc, dict(_ATTN, dtype=L.PV_BF16))
+BASE["pv_attention/f32"] = (L.AttentionDesc, dict(_ATTN, dtype=L.PV_F32))
 SUPPORTED = {"pv_mlp_rows": "pv_mlp_rows_supported", "pv_ln_linear_rows": "pv_ln_linear_rows_supported"}
 
 
@@ -128,6 +133,23 @@ TABLE = (
     + [("pv_ln_linear_rows", dict(C=128, ldx=128), UNSUPPORTED),
        ("pv_ln_linear_rows", dict(C=1536, ldx=1536), UNSUPPORTED),
        ("pv_ln_linear_rows", dict(ln_gamma=None, dtype=NO_DTYPE), UNSUPPORTED)]   # the dtype is checked before the parameters
+    # ---- pv_attention: pointers, counts, alignment (rows of 8 bf16 / 4 fp32 elements), scale, row width; then head_dim and dtype
+    + [(e, {k: v}, INVALID) for e in ("pv_attention", "pv_attention/f32")
+       for k, vs in dict(q=None, k=None, v=None, o=None, B=(0, -1), heads=(0, -1), head_dim=(0, -32), Nq=(0, -1), Nk=(0, -1),
+                         ldq=56, ldk=56, ldv=56, ldo=56,                  # < heads * head_dim
+                         scale=(0.0, -0.125, float("inf"), float("nan"))).items()
+       for v in (vs if isinstance(vs, tuple) else (vs,))]
+    + _each("pv_attention", INVALID, ldq=68, ldk=68, ldv=68, ldo=68, q_bs=452, k_bs=324, v_bs=324, o_bs=452)       # % 8
+    + _each("pv_attention/f32", INVALID, ldq=66, ldk=66, ldv=66, ldo=66, q_bs=450, k_bs=322, v_bs=322, o_bs=450)   # % 4
+    + [("pv_attention", dict(head_dim=40, ldq=80, ldk=80, ldv=80, ldo=80), UNSUPPORTED),
+       ("pv_attention/f32", dict(head_dim=40, ldq=80, ldk=80, ldv=80, ldo=80), UNSUPPORTED),
+       ("pv_attention", dict(dtype=NO_DTYPE), UNSUPPORTED),
+       ("pv_attention", dict(dtype=L.PV_U8), UNSUPPORTED),
+       ("pv_attention", dict(dtype=NO_DTYPE, ldq=68), UNSUPPORTED),       # an unknown dtype is held to rows of 4 elements ...
+       ("pv_attention", dict(dtype=NO_DTYPE, ldq=66), INVALID),           # ... and the alignment is checked before the dtype
+       ("pv_attention", dict(head_dim=40), INVALID),                      # the row width (ld 64 < 2 * 40) before the head_dim
+       ("pv_attention", dict(dtype=NO_DTYPE, scale=0.0), INVALID),
+       ("pv_attention", dict(q=None, head_dim=40), INVALID)]
 )
 
 
