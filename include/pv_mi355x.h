@@ -150,6 +150,16 @@ typedef struct pv_conv3d_desc {
    * NULL: no slot (the 4-channel layout only). */
   const void* x_src_slot;
   int32_t x_src_c;        /* channel planes of the caller's clip, 1..4 (planes beyond them read as 0) */
+  /* GROUPED convolution with 16 or 32 channels per group (create_resnet / create_slowfast(stage_conv_b_num_groups=...),
+   * models/resnet.py:98-132; create_csn(stage_conv_b_width_per_group=...), models/csn.py:34,169 -> nn.Conv3d(C, C,
+   * groups = G)): 0 / 1 = dense.  Otherwise cin == round_up(C, 8), cout == C, C % groups == 0 and the weights are the
+   * compact [cout][taps][gw] (gw = C / groups) in `dtype`: w[co][tap][j] multiplies input channel (co / gw) * gw + j.
+   * Runs where pv_conv3d_grouped_supported(d) is 1 (csrc/pv_gconv.hip), PV_ERR_UNSUPPORTED elsewhere: bf16, gw 16 or 32,
+   * at most 27 taps, strides 1 / 2, dilation 1, scale / shift / act only (no residual, gate, fp32 output, second
+   * operand or fused neighbour, not the 4-channel layout).  The field occupies what was tail padding of the struct and the
+   * ABI version did not change with it: callers must zero-initialise the descriptor (as every field added since version 1
+   * assumes), or a caller built against an older header passes garbage here. */
+  int32_t groups;
 } pv_conv3d_desc;
 int pv_conv3d(const pv_conv3d_desc* d, pv_stream_t stream);
 /* 1 if this geometry (pointers are ignored) can run with the fused temporal conv, else 0 */
@@ -160,6 +170,9 @@ int pv_conv3d_ncdhw_supported(const pv_conv3d_desc* d);
 int pv_conv3d_x2_supported(const pv_conv3d_desc* d);
 /* 1 if this geometry (pointers are ignored; pw2_cout > 0) can run with the pointwise conv behind it, else 0 */
 int pv_conv3d_pw2_supported(const pv_conv3d_desc* d);
+/* 1 if this descriptor (groups > 1; data pointers are not dereferenced, fused operands must be unset) can run as a
+ * grouped conv, else 0 */
+int pv_conv3d_grouped_supported(const pv_conv3d_desc* d);
 
 /* ---- development knobs ---------------------------------------------------------------------
  * Kernel-routing choices that were settled by A/B measurements on the MI355X stay overridable for the tools

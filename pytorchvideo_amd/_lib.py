@@ -42,7 +42,7 @@ Conv3dDesc = _struct("Conv3dDesc", [
     + _ints("dil_t", "dil_h", "dil_w")
     + [("x2", _p), ("x2_scale", _p), ("x2_bs", _i64)] + _ints("x2_ld", "x2_cin", "x2_Hi", "x2_Wi", "x2_st", "x2_sh", "x2_sw")
     + [("pw2_w", _p), ("pw2_scale", _p), ("pw2_shift", _p)] + _ints("pw2_cout", "pw2_act")
-    + [("x_src_slot", _p)] + _ints("x_src_c"))
+    + [("x_src_slot", _p)] + _ints("x_src_c", "groups"))
 
 DwConv3dDesc = _struct("DwConv3dDesc", [
     ("x", _p), ("w", _p), ("y", _p), ("scale", _p), ("shift", _p), ("psum", _p),
@@ -195,6 +195,7 @@ _SYMBOLS = [
     ("pv_conv3d_ncdhw_supported", C.c_int, [C.POINTER(Conv3dDesc)]),
     ("pv_conv3d_x2_supported", C.c_int, [C.POINTER(Conv3dDesc)]),
     ("pv_conv3d_pw2_supported", C.c_int, [C.POINTER(Conv3dDesc)]),
+    ("pv_conv3d_grouped_supported", C.c_int, [C.POINTER(Conv3dDesc)]),
     ("pv_dwconv3d", C.c_int, [C.POINTER(DwConv3dDesc), _p]),
     ("pv_dwconv3d_psum_blocks", C.c_int, [C.POINTER(DwConv3dDesc)]),
     ("pv_dwconv3d_pw_supported", C.c_int, [C.POINTER(DwConv3dDesc)]),

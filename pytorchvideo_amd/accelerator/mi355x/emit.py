@@ -95,9 +95,10 @@ def check_conv3d(conv):
     if depthwise and tuple(conv.dilation) != (1, 1, 1):
         raise Unsupported("dilated depthwise conv")
     # channel-wise grouped conv with 2 / 4 / 8 channels per group (create_csn(stage_conv_b_width_per_group=...),
-    # reference models/csn.py:34,169) rides in the depthwise kernel (pv_dwconv3d_desc.gw); every other grouping is
-    # evaluated as a dense conv with block-diagonal weights (emit_conv) -- slower than a grouped kernel would be,
-    # but on the HIP path like the rest of the deployed model
+    # reference models/csn.py:34,169) rides in the depthwise kernel (pv_dwconv3d_desc.gw); 16 / 32 channels per group
+    # (ResNeXt-3D conv_b, the wide-group CSN variants) go to the grouped MFMA kernel in a bf16 session
+    # (pv_conv3d_desc.groups, csrc/pv_gconv.hip); every other grouping is evaluated as a dense conv with block-diagonal
+    # weights (emit_conv), on the HIP path like the rest of the deployed model
     return depthwise or group_width(conv) > 1
 
 
@@ -190,7 +191,17 @@ def emit_conv(sess, conv, x, norm=None, act=L.ACT_NONE, residual=None, a_gate=No
         raise RuntimeError("conv output buffer geometry mismatch")
     # pack [cout][taps][cin_p]
     w = conv.weight.detach().float().cpu()  # [cout, cin / groups, kt, kh, kw]
-    if conv.groups > 1:   # grouped, not channel-wise: block-diagonal dense weights
+    grouped = 0
+    if (conv.groups > 1 and tuning.get("grouped_conv") and sess.itemsize == 2 and not x.f32 and not c4 and dil == (1, 1, 1)
+            and conv.in_channels == cout and residual is None and a_gate is None and a_act == L.ACT_NONE and not y_f32
+            and dwt is None and pos is None and shortcut is None):
+        # 16 / 32 channels per group: the grouped kernel takes the compact weights; decided by the library from the geometry
+        d = L.Conv3dDesc(B=x.B, Ti=x.T, Hi=x.H, Wi=x.W, cin=cin_p, To=To, Ho=Ho, Wo=Wo, cout=cout, kt=kt, kh=kh, kw=kw,
+                         st=st, sh=sh, sw=sw, pt=pt, ph=ph, pw=pw, act=act, dtype=sess.pv_dtype, x_bs=x.bs, y_bs=y.bs,
+                         ldx=x.ld, ldy=y.ld, groups=conv.groups)
+        if L.lib().pv_conv3d_grouped_supported(C.byref(d)) == 1:
+            grouped = conv.groups
+    if conv.groups > 1 and not grouped:   # grouped, not channel-wise: block-diagonal dense weights
         cg_in, cg_out = conv.in_channels // conv.groups, cout // conv.groups
         wd = torch.zeros((cout, conv.in_channels) + tuple(w.shape[2:]), dtype=w.dtype)
         for g in range(conv.groups):
@@ -209,6 +220,8 @@ def emit_conv(sess, conv, x, norm=None, act=L.ACT_NONE, residual=None, a_gate=No
         wp = torch.zeros(cout, kt, kh, (kw + 1) // 2 * 2, 4, dtype=torch.float32)
         wp[:, :, :, :kw, : x.C] = w.permute(0, 2, 3, 4, 1)
         wp = wp.reshape(cout, -1)
+    elif grouped:   # compact [cout][taps][gw]
+        wp = w.permute(0, 2, 3, 4, 1).reshape(cout, kt * kh * kw, cout // grouped).contiguous()
     else:
         wp = torch.zeros(cout, kt * kh * kw, cin_p, dtype=torch.float32)
         wp[:, :, : x.C] = w.permute(0, 2, 3, 4, 1).reshape(cout, kt * kh * kw, x.C)
@@ -249,7 +262,7 @@ def emit_conv(sess, conv, x, norm=None, act=L.ACT_NONE, residual=None, a_gate=No
         kt=kt, kh=kh, kw=kw, st=st, sh=sh, sw=sw, pt=pt, ph=ph, pw=pw,
         act=act, a_act=a_act, dtype=L.PV_F32 if f32_op else sess.pv_dtype, y_f32=1 if (y_f32 and not f32_op) else 0,
         r_f32=1 if (residual is not None and residual.f32 and not f32_op) else 0, c4_wpair=wpair,
-        dil_t=dil[0], dil_h=dil[1], dil_w=dil[2],
+        dil_t=dil[0], dil_h=dil[1], dil_w=dil[2], groups=grouped,
     )
     if x2 is not None:
         f.update(shift=sess.add_weight(shift), x2_scale=sess.add_weight(scale2) if has_affine2 else None,
@@ -289,6 +302,10 @@ def emit_conv(sess, conv, x, norm=None, act=L.ACT_NONE, residual=None, a_gate=No
     flops = 2 * vox_out * cout * taps * x.C
     detail = "|%dx%dx%dx%d c%d->%d k%dx%dx%d s%d%d%d%s" % (x.B, To, Ho, Wo, x.C, cout, kt, kh, kw, st, sh, sw,
                                                           " gate" if a_gate is not None else "")
+    if grouped:   # the grouped kernel reads the compact filter and multiplies no zeros
+        alg -= sess.itemsize * cout * taps * (cin_p - cout // grouped)
+        flops //= grouped
+        detail += " g%d" % grouped
     if dwt is not None:
         flops += 2 * vox_out * cout * dwt.kernel_size[0]
         detail += "+k%dx1x1" % dwt.kernel_size[0]

@@ -15,11 +15,15 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 INCLUDE = os.path.join(ROOT, "include")
 OUT_DIR = os.path.join(os.path.dirname(HERE), "_lib")
 LIB = os.path.join(OUT_DIR, "libpv_mi355x.so")
-SOURCES = ["pv_conv.hip", "pv_pwconv.hip", "pv_gemm.hip", "pv_gemm8.hip", "pv_gemm9.hip", "pv_gemm9h.hip", "pv_stem.hip", "pv_dwconv.hip", "pv_pwdw.hip", "pv_segate.hip", "pv_pool.hip", "pv_layout.hip", "pv_rows.hip", "pv_resample.hip", "pv_yuv.hip", "pv_batch.hip", "pv_frames.hip", "pv_frames16.hip", "pv_orient.hip", "pv_hdr.hip", "pv_region.hip", "pv_area.hip", "pv_packed.hip", "pv_yuv4.hip", "pv_yuyv.hip", "pv_boxes.hip", "pv_tokpool.hip", "pv_attn.hip", "pv_attn64.hip", "pv_roi.hip", "pv_lateral.hip", "pv_mlp.hip", "pv_block.hip", "pv_headgemm.hip", "pv_comm.hip", "pv_plan.hip"]
+SOURCES = ["pv_conv.hip", "pv_pwconv.hip", "pv_gemm.hip", "pv_gemm8.hip", "pv_gemm9.hip", "pv_gemm9h.hip", "pv_stem.hip", "pv_dwconv.hip", "pv_pwdw.hip", "pv_segate.hip", "pv_pool.hip", "pv_layout.hip", "pv_rows.hip", "pv_resample.hip", "pv_yuv.hip", "pv_batch.hip", "pv_frames.hip", "pv_frames16.hip", "pv_orient.hip", "pv_hdr.hip", "pv_region.hip", "pv_area.hip", "pv_packed.hip", "pv_yuv4.hip", "pv_yuyv.hip", "pv_boxes.hip", "pv_tokpool.hip", "pv_attn.hip", "pv_attn64.hip", "pv_roi.hip", "pv_lateral.hip", "pv_gconv.hip", "pv_mlp.hip", "pv_block.hip", "pv_headgemm.hip", "pv_comm.hip", "pv_plan.hip"]
 HEADERS = [os.path.join(HERE, "pv_common.h"), os.path.join(HERE, "pv_attn.h"), os.path.join(HERE, "pv_gemm_tile.h"), os.path.join(HERE, "pv_rs.h"), os.path.join(HERE, "pv_frames.h"), os.path.join(HERE, "pv_area.h"), os.path.join(INCLUDE, "pv_mi355x.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", HERE,
          "-Wno-unused-result"]
+# per-unit flags.  pv_gconv.hip has no packed-fp32 arithmetic of its own in the K loop; left to itself hipcc pairs the epilogue and
+# the index arithmetic into ~400 v_pk_*_f32 on 64-bit register pairs, which costs gconv_plane_kernel<16> 146 VGPRs (2 waves per
+# SIMD) against 124 (3 waves) without them, and <32> 142 against 113 (-Rpass-analysis=kernel-resource-usage, both ways)
+UNIT_FLAGS = {"pv_gconv.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _stale(target, deps):
@@ -54,7 +58,7 @@ def _compile(src, force, out_dir=None, extra=()):
     obj = os.path.join(out_dir, src.replace(".hip", ".o"))
     path = os.path.join(HERE, src)
     if force or _stale(obj, [path] + HEADERS):
-        flags = [f for f in FLAGS if not (extra and f == "-O3")] + list(extra)
+        flags = [f for f in FLAGS if not (extra and f == "-O3")] + UNIT_FLAGS.get(src, []) + list(extra)
         cmd = [HIPCC] + flags + ["-c", path, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:

@@ -27,6 +27,8 @@ int pv_stem_c4(const pv_conv3d_desc& d, hipStream_t s);                 // pv_st
 int pv_stem_dwt_supported(const pv_conv3d_desc& d);                     // pv_stem.hip
 int pv_stem_ncdhw_supported(const pv_conv3d_desc& d);                   // pv_stem.hip
 int pv_pwconv_x2_supported(const pv_conv3d_desc& d);                    // pv_pwconv.hip
+int pv_gconv_supported(const pv_conv3d_desc& d);                        // pv_gconv.hip
+int pv_gconv_try(const pv_conv3d_desc& d, hipStream_t s);               // pv_gconv.hip
 
 namespace {
 
@@ -556,6 +558,11 @@ extern "C" int pv_conv3d_x2_supported(const pv_conv3d_desc* d) {
   return pv_pwconv_x2_supported(*d);
 }
 
+extern "C" int pv_conv3d_grouped_supported(const pv_conv3d_desc* d) {
+  if (!d || d->groups <= 1) return 0;
+  return pv_gconv_supported(*d);
+}
+
 extern "C" int pv_conv3d(const pv_conv3d_desc* dp, pv_stream_t stream) {
   if (!dp) return PV_ERR_INVALID;
   const pv_conv3d_desc& d = *dp;
@@ -581,6 +588,11 @@ extern "C" int pv_conv3d(const pv_conv3d_desc* dp, pv_stream_t stream) {
   const bool pw = taps == 1 && d.st == 1 && d.sh == 1 && d.sw == 1 && d.pt == 0 && d.ph == 0 && d.pw == 0;
   if ((d.a_gate || d.a_act != PV_ACT_NONE) && !pw) return PV_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d.groups < 0) return PV_ERR_INVALID;
+  if (d.groups > 1) {   // compact grouped weights: the grouped kernel only, no fallback
+    if (d.cout % d.groups || d.cin != pv_round_up(d.cout, 8)) return PV_ERR_INVALID;
+    return pv_gconv_try(d, s);
+  }
   if (c4) return pv_stem_c4(d, s);
   if (d.dwt_w || d.pos_spatial || d.pos_temporal) return PV_ERR_UNSUPPORTED;   // first-layer layout only
   if (d.pw2_w) {   // a pointwise conv behind this one: the tap-streaming kernel only, no fallback
