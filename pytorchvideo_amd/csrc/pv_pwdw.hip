@@ -56,7 +56,12 @@ __global__ __launch_bounds__(kPlaneThreads) void pwdw_plane_kernel(const pv_dwco
   constexpr int TW = 4 * NW;               // tile width (outputs)
   constexpr int IH = (kPR - 1) * S + 3;
   constexpr int IW = (TW - 1) * S + 3;
-  constexpr bool kDeep = S == 1;           // small planes: keep two of them in flight
+  // Two planes in flight (plane p + 2 requested in front of the stencil of p, p + 1 converted from registers loaded a whole
+  // plane earlier) wherever the second operand set fits beside two waves per SIMD: every stride-1 form, and stride 2 at KS = 1
+  // (res2.0, res3.0: MT = 5 more registers of 4).  <2, 4, 2> (res4.0) stands at 256 registers with ONE plane in flight; 40 more
+  // would cost it the second wave per SIMD, which is worth more there than the depth.
+  constexpr bool kDeep = S == 1 || KS == 1;
+  constexpr bool kLoadAlways = S == 2 && kDeep;   // the deep stride-2 walk: its plane requests stand on every path (load_plane)
   constexpr int IWP = (IW + 1) & ~1;       // LDS row pitch (even: columns are pair-swapped)
   constexpr int NVOX = IH * IW;
   constexpr int NMT = (NVOX + 15) / 16;    // 16-voxel MFMA column tiles per plane
@@ -160,15 +165,28 @@ __global__ __launch_bounds__(kPlaneThreads) void pwdw_plane_kernel(const pv_dwco
   // Buffer addressing: the lane's loop-invariant offset is the VECTOR offset, ks * 64 the immediate and the plane's byte
   // offset the SCALAR offset.  The hardware range-checks vector offset + immediate against num_records and does NOT check the
   // scalar offset: a lane outside the image stays out of range by its vector offset alone (kOOB), and a plane past the clip
-  // is never addressed because of the explicit p >= d.Ti guard.
+  // is never addressed: the one-plane and the stride-1 walks skip its loads (p >= d.Ti), the deep stride-2 walk issues them
+  // against a resource of NO records, where every offset is out of range and a load returns zero without touching memory.
+  // That walk's loads then stand on every path through a trip, so the wait in front of a plane's conv_a can be counted
+  // (vmcnt = the MT loads of the younger plane, plus stores): behind a branch the compiler has to assume they were skipped,
+  // and waits for everything.  The choice of the resource is one scalar select.
   auto load_plane = [&](u32x4 (&reg)[MT][KS], int p) {
-    if (p >= d.Ti) return;   // wave-uniform
+    __amdgpu_buffer_rsrc_t r = rx;
+    if constexpr (kLoadAlways) {
+      r = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, p < d.Ti ? (int)(x_plane_bytes * (unsigned)d.Ti) : 0, 0x00020000);
+    } else {
+      if (p >= d.Ti) return;   // wave-uniform
+    }
+    // the requests stay where they are written, between the barrier and the stencil, as the branch kept them in the guarded
+    // form: free to move, the scheduler spreads them over the stencil and the kernel needs 278 registers, not 236
+    if constexpr (kLoadAlways) __builtin_amdgcn_sched_barrier(0);
     const unsigned pb = (unsigned)p * x_plane_bytes;
 #pragma unroll
     for (int i = 0; i < MT; ++i)   // column tiles past the plane read nothing (kOOB) and write the dump row
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
-        reg[i][ks] = __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(x_off[i] + ks * 64u), (int)pb, 0);
+        reg[i][ks] = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(x_off[i] + ks * 64u), (int)pb, 0);
+    if constexpr (kLoadAlways) __builtin_amdgcn_sched_barrier(0);
   };
   auto conv_a = [&](f32x4 (&c)[2], const u32x4 (&reg)[KS]) {
 #pragma unroll
@@ -193,14 +211,14 @@ __global__ __launch_bounds__(kPlaneThreads) void pwdw_plane_kernel(const pv_dwco
     for (int n = 0; n < NW; ++n) acc[a][n] = f32x2{0.f, 0.f};
   f32x2 ps = {0.f, 0.f};
 
-  unsigned y_off[NW];
-  float y_mask[NW];   // 1 for outputs that exist: the squeeze-excitation sums skip the ragged edge
+  unsigned y_off[NW];   // kOOB for outputs that do not exist (the store is dropped, the squeeze-excitation sums skip them)
+  float y_mask[kLoadAlways ? 1 : NW];   // 1 for outputs that exist (the deep stride-2 form makes it from y_off, see finalize)
 #pragma unroll
   for (int n = 0; n < NW; ++n) {
     const int wo = wo_first + n;
     const bool ok = ch_ok && ho < d.Ho && wo < d.Wo;
     y_off[n] = ok ? (unsigned)((ho * d.Wo + wo) * d.ldy + ch) * 2u : kOOB;
-    y_mask[n] = ok ? 1.f : 0.f;
+    if constexpr (!kLoadAlways) y_mask[n] = ok ? 1.f : 0.f;
   }
   // Stencil side: LDS byte offset of the lane's input columns in the first input row of a plane buffer.  Column i lies at
   // colperm(sx * NW * S + i) = sx * NW * S + (i ^ t), t = (sx + i / (NW * S)) & 1: the pair swap moves an even i up and an odd
@@ -225,8 +243,19 @@ __global__ __launch_bounds__(kPlaneThreads) void pwdw_plane_kernel(const pv_dwco
     for (int n = 0; n < NW; ++n) {
       float v0 = a[n].x * sc.x + sh.x, v1 = a[n].y * sc.y + sh.y;
       if (decltype(sums_c)::value) {
-        // one packed operation per pair; the mask is 0 or 1, so the product is exact whether it is fused or not
-        ps = __builtin_elementwise_fma(f32x2{v0, v1}, f32x2{y_mask[n], y_mask[n]}, ps);
+        // one packed operation per pair; the mask is 0 or 1, so the product is exact whether it is fused or not.  The deep
+        // stride-2 form makes it here from the sign bit of y_off (kOOB), three instructions per output, and does not keep it
+        // in NW registers across the walk: with those <2, 4, 1> and its second operand set stay inside the registers of the
+        // one-plane form (tests/test_pwdw_loop_isa.py).
+        float mask;
+        if constexpr (kLoadAlways) {
+          int oob;   // 0, or -1 for an output past the edge; volatile so that it is not hoisted back into registers
+          asm volatile("v_ashrrev_i32 %0, 31, %1" : "=v"(oob) : "v"(y_off[n]));
+          mask = (float)(oob + 1);
+        } else {
+          mask = y_mask[n];
+        }
+        ps = __builtin_elementwise_fma(f32x2{v0, v1}, f32x2{mask, mask}, ps);
       }
       if (ACT == PV_ACT_RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
       else if (ACT == PV_ACT_SWISH) { v0 *= pv_sigmoid(v0); v1 *= pv_sigmoid(v1); }
@@ -241,8 +270,12 @@ __global__ __launch_bounds__(kPlaneThreads) void pwdw_plane_kernel(const pv_dwco
   auto walk = [&](auto relu_c, auto psum_c) {
     // ReLU on the packed pair: a negative bf16 is a negative int16, so max(.,0) per 16-bit half clears it
     constexpr bool a_relu = decltype(relu_c)::value;
-    auto produce_plane = [&](const u32x4 (&reg)[MT][KS], int p) {
-      if (p >= d.Ti) return;
+    // first_c: plane 0 of the deep stride-2 walk, produced unconditionally (an empty clip's loads return zero and nothing
+    // reads the buffer).  Its wait then stands on the only path into the loop and retires every start-up load (taps, BatchNorm
+    // tables) with it; left behind a branch, those stay pending on the other path and the compiler waits for them at the first
+    // stencil of every trip, with the loads of the younger plane just issued in front of that wait.
+    auto produce_plane = [&](const u32x4 (&reg)[MT][KS], int p, auto first_c) {
+      if (!(kLoadAlways && decltype(first_c)::value) && p >= d.Ti) return;
       bf16_t* dst = &s_in[p & 1][0][0];
       // One column tile ahead: tile i + 1's MFMAs are issued before tile i's results are touched, and tile i's results are
       // released only once tile i - 1's packed output exists (mfma_after).  Every result is thus read at least one whole
@@ -321,20 +354,22 @@ __global__ __launch_bounds__(kPlaneThreads) void pwdw_plane_kernel(const pv_dwco
       }
     };
 
+    constexpr std::true_type first{};
+    constexpr std::false_type later{};
     load_plane(xa, 0);
     if (kDeep) load_plane(xb, 1);
-    produce_plane(xa, 0);
+    produce_plane(xa, 0, first);
     __syncthreads();
     if (kDeep) {
       for (int p = 0; p < d.Ti; p += 2) {
         load_plane(xa, p + 2);       // xb holds plane p+1
         plane(p);
-        produce_plane(xb, p + 1);
+        produce_plane(xb, p + 1, later);
         __syncthreads();
         if (p + 1 < d.Ti) {
           load_plane(xb, p + 3);     // xa holds plane p+2
           plane(p + 1);
-          produce_plane(xa, p + 2);
+          produce_plane(xa, p + 2, later);
           __syncthreads();
         }
       }
@@ -344,12 +379,12 @@ __global__ __launch_bounds__(kPlaneThreads) void pwdw_plane_kernel(const pv_dwco
       for (int p = 0; p < d.Ti; p += 2) {
         load_plane(xa, p + 1);
         plane(p);
-        produce_plane(xa, p + 1);
+        produce_plane(xa, p + 1, later);
         __syncthreads();
         if (p + 1 < d.Ti) {
           load_plane(xa, p + 2);
           plane(p + 1);
-          produce_plane(xa, p + 2);
+          produce_plane(xa, p + 2, later);
           __syncthreads();
         }
       }
