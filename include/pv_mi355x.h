@@ -1027,6 +1027,33 @@ typedef struct pv_attention_desc {
 } pv_attention_desc;
 int pv_attention(const pv_attention_desc* d, pv_stream_t stream);
 
+/* ---- wide-head attention of the non-local block -------------------------------------
+ * NonLocal.forward of layers/nonlocal_net.py between its 1x1x1 convs: one single-head attention over all T*H*W
+ * positions of a clip, the head Ci = dim_inner channels wide, the scores never stored (csrc/pv_nlattn.hip):
+ *   mode 0 (instantiation "softmax"):      o = softmax(scale * q k^T) v     (online over key tiles, fp32)
+ *   mode 1 (instantiation "dot_product"):  o = (q k^T) v * scale            (the caller passes scale = 1 / Nk)
+ * q (theta) is [B][Nq][Ci], k (phi) and v (g) are [B][Nk][Ci], o is [B][Nq][Ci]: token tensors, channels last, leading
+ * dimension and batch stride per operand (elements), so the operands may be channel slices of one wider buffer.
+ * bf16 in and out, fp32 accumulation; Ci a multiple of 64 in [64, 512]; any Nq, Nk >= 1 whose rows lie inside 32-bit byte
+ * offsets of their clip; leading dimensions and batch strides multiples of 8, pointers 16-byte aligned.
+ * PV_ERR_INVALID: a null descriptor or operand, B / Ci / Nq / Nk <= 0, mode outside 0..1, a scale that is not finite and > 0,
+ * reserved != 0, a misaligned or too narrow operand.  PV_ERR_UNSUPPORTED: any other dtype, Ci or extent.  Validation
+ * precedes every HIP call.
+ */
+typedef struct pv_nonlocal_attention_desc {
+  const void* q; const void* k; const void* v; void* o;
+  int64_t q_bs, k_bs, v_bs, o_bs;
+  int32_t ldq, ldk, ldv, ldo;
+  int32_t B, Ci, Nq, Nk;
+  float scale;          /* finite and > 0 (row maxima are taken before scaling) */
+  int32_t mode;         /* 0 = softmax, 1 = dot_product */
+  int32_t dtype;
+  int32_t reserved;     /* 0 */
+} pv_nonlocal_attention_desc;
+int pv_nonlocal_attention(const pv_nonlocal_attention_desc* d, pv_stream_t stream);
+/* 1 if this geometry (pointers are ignored) can run, else 0 */
+int pv_nonlocal_attention_supported(const pv_nonlocal_attention_desc* d);
+
 /* ---- video-level ensembling (the step right after the path) ---------------
  * pytorchvideo_trainer/module/video_classification.py:244-311: preds = softmax(logits) of every clip
  * (30 views per video in the model zoo's test protocol) are summed -- or max-ed -- into its video's
@@ -1201,7 +1228,7 @@ enum pv_op_kind {
   PV_OP_LAYERNORM = 5, PV_OP_SOFTMAX_ROWS = 6, PV_OP_MEAN_ROWS = 7, PV_OP_POSENC = 8,
   PV_OP_ATTENTION = 9, PV_OP_ADD_ACT = 10, PV_OP_INGEST = 11, PV_OP_EGRESS = 12, PV_OP_TOKEN_POOL = 13,
   PV_OP_ROI_ALIGN = 14, PV_OP_LATERAL = 15, PV_OP_AFFINE_ROWS = 16, PV_OP_MLP_ROWS = 17, PV_OP_LN_LINEAR = 18,
-  PV_OP_BOTTLENECK = 19
+  PV_OP_BOTTLENECK = 19, PV_OP_NONLOCAL = 20
 };
 typedef struct pv_plan pv_plan;
 pv_plan* pv_plan_create(void);

@@ -20,7 +20,7 @@ ACT_NONE, ACT_RELU, ACT_SWISH, ACT_GELU, ACT_SIGMOID = 0, 1, 2, 3, 4
 POOL_MAX, POOL_AVG = 0, 1
 (OP_CONV3D, OP_DWCONV3D, OP_SE_GATE, OP_POOL3D, OP_LAYERNORM, OP_SOFTMAX_ROWS, OP_MEAN_ROWS,
  OP_POSENC, OP_ATTENTION, OP_ADD_ACT, OP_INGEST, OP_EGRESS, OP_TOKEN_POOL, OP_ROI_ALIGN, OP_LATERAL,
- OP_AFFINE_ROWS, OP_MLP_ROWS, OP_LN_LINEAR, OP_BOTTLENECK) = range(1, 20)
+ OP_AFFINE_ROWS, OP_MLP_ROWS, OP_LN_LINEAR, OP_BOTTLENECK, OP_NONLOCAL) = range(1, 21)
 
 _p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -143,6 +143,13 @@ AttentionDesc = _struct("AttentionDesc", [
     + _ints("ldq", "ldk", "ldv", "ldo", "B", "heads", "head_dim", "Nq", "Nk")
     + [("scale", _f32)] + _ints("residual_q", "dtype"))
 
+NonLocalAttentionDesc = _struct("NonLocalAttentionDesc", [
+    ("q", _p), ("k", _p), ("v", _p), ("o", _p),
+    ("q_bs", _i64), ("k_bs", _i64), ("v_bs", _i64), ("o_bs", _i64)]
+    + _ints("ldq", "ldk", "ldv", "ldo", "B", "Ci", "Nq", "Nk")
+    + [("scale", _f32)] + _ints("mode", "dtype", "reserved"))
+NL_SOFTMAX, NL_DOT_PRODUCT = 0, 1
+
 AddDesc = _struct("AddDesc", [
     ("a", _p), ("b", _p), ("y", _p), ("rows", _i64)]
     + _ints("C", "lda", "ldb", "ldy", "act", "dtype"))
@@ -183,6 +190,7 @@ DESC_FOR_OP = {
     OP_ATTENTION: AttentionDesc, OP_ADD_ACT: AddDesc, OP_INGEST: LayoutDesc, OP_EGRESS: LayoutDesc,
     OP_TOKEN_POOL: TokenPoolDesc, OP_ROI_ALIGN: RoiAlignDesc, OP_LATERAL: LateralDesc, OP_AFFINE_ROWS: RowsDesc,
     OP_MLP_ROWS: MlpDesc, OP_LN_LINEAR: LnLinearDesc, OP_BOTTLENECK: BottleneckDesc,
+    OP_NONLOCAL: NonLocalAttentionDesc,
 }
 
 # every symbol the header declares: (name, restype, argtypes)
@@ -220,6 +228,8 @@ _SYMBOLS = [
     ("pv_mean_rows", C.c_int, [C.POINTER(RowsDesc), _p]),
     ("pv_add_posenc", C.c_int, [C.POINTER(PosencDesc), _p]),
     ("pv_attention", C.c_int, [C.POINTER(AttentionDesc), _p]),
+    ("pv_nonlocal_attention", C.c_int, [C.POINTER(NonLocalAttentionDesc), _p]),
+    ("pv_nonlocal_attention_supported", C.c_int, [C.POINTER(NonLocalAttentionDesc)]),
     ("pv_add_act", C.c_int, [C.POINTER(AddDesc), _p]),
     ("pv_token_pool", C.c_int, [C.POINTER(TokenPoolDesc), _p]),
     ("pv_roi_align", C.c_int, [C.POINTER(RoiAlignDesc), _p]),

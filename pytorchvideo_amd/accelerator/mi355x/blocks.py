@@ -18,17 +18,24 @@ from .session import Session
 class Mi355xBlock(EfficientBlockBase):
     """Generic single-input / single-output block (stem, res stage, res block, head, pool)."""
 
+    # what a block keeps beside the state it adopted (name -> initial value); original() leaves exactly these behind
+    _BLOCK_STATE = dict(_orig_cls=None, convert_flag=False, _sess=None, _in_ref=None, _out_ref=None, _op_range=None,
+                        _owns_session=False)
+
     def __init__(self, original: nn.Module):
         super().__init__()
         # adopt the original module's state wholesale: children, params, buffers, hooks, plain attrs
         self.__dict__.update(original.__dict__)
+        self.__dict__.update(self._BLOCK_STATE)
         self.__dict__["_orig_cls"] = type(original)
-        self.__dict__["convert_flag"] = False
-        self.__dict__["_sess"] = None
-        self.__dict__["_in_ref"] = None
-        self.__dict__["_out_ref"] = None
-        self.__dict__["_op_range"] = None
-        self.__dict__["_owns_session"] = False
+
+    def original(self):
+        """The adopted module again, an instance of its own class that shares this block's children, parameters and
+        buffers (an unconverted block only)."""
+        assert not self.convert_flag, "a converted block does not go back"
+        m = object.__new__(self._orig_cls)
+        m.__dict__.update({k: v for k, v in self.__dict__.items() if k not in self._BLOCK_STATE})
+        return m
 
     # name shown in reprs / logs
     def _get_name(self):
@@ -186,7 +193,7 @@ class Mi355xRoIHeadBlock(Mi355xBlock):
 
 
 # ------------------------------------------------------------------------- transmuters
-_SINGLE_IO = ("ResNetBasicStem", "ResStage", "ResBlock", "ResNetBasicHead")
+_SINGLE_IO = ("ResNetBasicStem", "ResStage", "ResBlock", "ResNetBasicHead", "NonLocal")
 
 
 def _probe(module):
@@ -207,7 +214,10 @@ def _probe(module):
                 return False
             return True
         if n == "ResStage":
-            return all(type(b).__name__ == "ResBlock" and _probe(b) for b in module.res_blocks)
+            return all(type(b).__name__ in ("ResBlock", "NonLocal") and _probe(b) for b in module.res_blocks)
+        if n == "NonLocal":
+            E.check_nonlocal(module)
+            return True
         if n == "ResBlock":
             if not E.is_add_fusion(module.branch_fusion) or type(module.branch2).__name__ != "BottleneckBlock":
                 return False

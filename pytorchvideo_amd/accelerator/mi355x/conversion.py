@@ -220,6 +220,7 @@ def convert_to_deployable_form(model: nn.Module, input_tensor, convert_for_quant
     if dtype is None:
         dtype = _default_dtype(input_tensor)
     L.lib()  # fail early and loudly when the HIP library is not built
+    model = _without_planned_nonlocal(model, dtype)
     lut = {}
     if not _is_fusable_net(model) and not _is_fusable_mvit(model, input_tensor):
         lut = _record_input_sizes(model, _one_clip(input_tensor))
@@ -256,6 +257,42 @@ def convert_to_deployable_form(model: nn.Module, input_tensor, convert_for_quant
     converted.__dict__["_pv_session"] = sess
     converted.__dict__["_pv_use_graph"] = use_graph
     return converted
+
+
+def _holds_planned_nonlocal(module):
+    from .blocks import Mi355xBlock
+    return any(isinstance(b, Mi355xBlock) and not b.convert_flag
+               and any(getattr(m, "_orig_cls", type(m)).__name__ == "NonLocal" for m in b.modules())
+               for b in module.modules())
+
+
+def _without_planned_nonlocal(model, dtype):
+    """The non-local kernel is bf16 only, and the transmuter does not know the dtype.  For an fp32 conversion: a copy of
+    `model` in which every MI355X block that holds a non-local block is back in the form it has with the tuning option
+    `nonlocal_block` off -- the block itself a torch module, the residual blocks around it converted one by one.  The
+    non-local modules are marked (`_pv_torch_only`), so the transmuter declines them whatever the option says.  A bf16
+    conversion, or a model without such a block, is returned as it is."""
+    if dtype == torch.bfloat16 or not _holds_planned_nonlocal(model):
+        return model
+    from ..model_transmuter import transmute_model
+    from .blocks import Mi355xBlock
+
+    def walk(parent):
+        for name, child in list(parent.named_children()):
+            if isinstance(child, Mi355xBlock):
+                if _holds_planned_nonlocal(child):
+                    orig = child.original()
+                    for m in orig.modules():
+                        if type(m).__name__ == "NonLocal":
+                            m.__dict__["_pv_torch_only"] = True
+                    parent._modules[name] = orig
+                    transmute_model(orig, "mi355x")      # its children, as if the block had been declined at the start
+            else:
+                walk(child)
+
+    model = deepcopy(model)
+    walk(model)
+    return model
 
 
 def _default_dtype(x):
@@ -345,6 +382,7 @@ def _convert_detection(model, inputs, dtype, use_graph, kwargs):
     if dtype is None:
         dtype = _default_dtype(x)
     L.lib()
+    model = _without_planned_nonlocal(model, dtype)
     fusable = _is_fusable_net(model.model) and isinstance(model.detection_head, Mi355xRoIHeadBlock)
     lut = {}
     if not fusable:

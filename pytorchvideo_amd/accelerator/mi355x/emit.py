@@ -880,15 +880,108 @@ def emit_res_block(sess, rb, x, out=None):
     return y
 
 
+NONLOCAL_WIDTHS = range(64, 513, 64)     # dim_inner of pv_nonlocal_attention (csrc/pv_nlattn.hip)
+
+
+def _is_pointwise(conv):
+    return isinstance(conv, nn.Conv3d) and conv.kernel_size == (1, 1, 1) and conv.stride == (1, 1, 1) \
+        and _triple(conv.padding) == (0, 0, 0) and conv.groups == 1 and tuple(conv.dilation) == (1, 1, 1) \
+        and conv.padding_mode == "zeros"
+
+
+def check_nonlocal(nl):
+    """Structure of a NonLocal (layers/nonlocal_net.py) the plan can hold, geometry aside; raises Unsupported otherwise."""
+    if not tuning.get("nonlocal_block") or getattr(nl, "_pv_torch_only", False):
+        raise Unsupported("nonlocal_block is off")     # (or an fp32 conversion marked the module: conversion.py)
+    convs = (nl.conv_theta, nl.conv_phi, nl.conv_g, nl.conv_out)
+    if not all(_is_pointwise(c) for c in convs):
+        raise Unsupported("non-local convs are not pointwise")
+    ci = nl.conv_theta.out_channels
+    if ci not in NONLOCAL_WIDTHS or {nl.conv_phi.out_channels, nl.conv_g.out_channels, nl.conv_out.in_channels} != {ci}:
+        raise Unsupported("non-local dim_inner %d" % ci)
+    if nl.conv_phi.in_channels != nl.conv_theta.in_channels or nl.conv_g.in_channels != nl.conv_theta.in_channels \
+            or nl.conv_out.out_channels != nl.conv_theta.in_channels:
+        raise Unsupported("non-local channel counts")
+    if nl.instantiation not in ("softmax", "dot_product"):
+        raise Unsupported("instantiation %s" % nl.instantiation)
+    if nl.norm is not None and not (isinstance(nl.norm, nn.BatchNorm3d) and nl.norm.running_mean is not None):
+        raise Unsupported("non-local norm %s" % _cls_name(nl.norm))
+    pool = nl.pool
+    if pool is not None:
+        k = _triple(pool.kernel_size) if isinstance(pool, nn.MaxPool3d) else None
+        if k is None or _triple(pool.stride if pool.stride is not None else k) != k or _triple(pool.padding) != (0, 0, 0) \
+                or pool.ceil_mode or _triple(pool.dilation) != (1, 1, 1) or pool.return_indices:
+            raise Unsupported("non-local pool")
+
+
+def _stacked_pointwise(convs):
+    """One pointwise conv that computes `convs` side by side (filters and biases concatenated along the output channels)."""
+    # (skip_init: no initialisation, so emitting a plan draws nothing from the caller's random generator)
+    cat = nn.utils.skip_init(nn.Conv3d, convs[0].in_channels, sum(c.out_channels for c in convs), kernel_size=1,
+                             bias=any(c.bias is not None for c in convs))
+    with torch.no_grad():
+        cat.weight.copy_(torch.cat([c.weight.detach().float().cpu() for c in convs], 0))
+        if cat.bias is not None:
+            cat.bias.copy_(torch.cat([c.bias.detach().float().cpu() if c.bias is not None else torch.zeros(c.out_channels)
+                                      for c in convs], 0))
+    return cat
+
+
+def emit_nonlocal(sess, nl, x, out=None):
+    """NonLocal.forward (layers/nonlocal_net.py): theta | phi | g as ONE pointwise conv (with a pool: theta on x, phi | g on
+    the pooled tensor), pv_nonlocal_attention on channel slices of its output -- the Nq x Nk matrix stays on the chip --
+    and conv_out with its bias, the folded BatchNorm and x as the residual in one epilogue.  bf16 plans only."""
+    check_nonlocal(nl)
+    if sess.itemsize != 2 or x.f32:
+        raise Unsupported("the non-local kernel is bf16 only: convert in bf16, or through convert_to_deployable_form, which "
+                          "leaves the block a torch module in an fp32 conversion")
+    if nl.norm is not None and nl.norm.training:
+        raise Unsupported("non-local norm in training mode")
+    if nl.conv_theta.in_channels != x.C:
+        raise RuntimeError("non-local block expects %d input channels, got %d" % (nl.conv_theta.in_channels, x.C))
+    ci = nl.conv_theta.out_channels
+    if nl.pool is None:
+        tpg = emit_conv(sess, _stacked_pointwise([nl.conv_theta, nl.conv_phi, nl.conv_g]), x, label="nl.theta_phi_g")
+        theta, phi, g = (tpg.channel_slice(i * ci, ci) for i in range(3))
+        owned = [tpg]
+    else:
+        theta = emit_conv(sess, nl.conv_theta, x, label="nl.theta")
+        xp = emit_pool(sess, nl.pool, x, label="nl.pool")
+        pg = emit_conv(sess, _stacked_pointwise([nl.conv_phi, nl.conv_g]), xp, label="nl.phi_g")
+        sess.release(xp)
+        phi, g = pg.channel_slice(0, ci), pg.channel_slice(ci, ci)
+        owned = [theta, pg]
+    nq, nk = theta.voxels, phi.voxels
+    softmax = nl.instantiation == "softmax"
+    o = sess.alloc_act(x.B, x.T, x.H, x.W, ci)
+    f = dict(q=theta.ptr, k=phi.ptr, v=g.ptr, o=o.ptr, q_bs=theta.bs, k_bs=phi.bs, v_bs=g.bs, o_bs=o.bs,
+             ldq=theta.ld, ldk=phi.ld, ldv=g.ld, ldo=o.ld, B=x.B, Ci=ci, Nq=nq, Nk=nk,
+             scale=float(ci) ** -0.5 if softmax else 1.0 / nk, mode=L.NL_SOFTMAX if softmax else L.NL_DOT_PRODUCT,
+             dtype=sess.pv_dtype)
+    d = L.NonLocalAttentionDesc(**{k: v for k, v in f.items() if not isinstance(v, Ptr)})
+    if L.lib().pv_nonlocal_attention_supported(C.byref(d)) != 1:
+        raise Unsupported("non-local attention %dx%d c%d" % (nq, nk, ci))
+    sess.add_op(L.OP_NONLOCAL, f, label="nl.attention|%dx%dx%d c%d %s" % (x.B, nq, nk, ci, nl.instantiation),
+                alg_bytes=sess.itemsize * x.B * ci * (2 * nq + 2 * nk), flops=4 * x.B * nq * nk * ci)
+    for r in owned:
+        sess.release(r)
+    y = emit_conv(sess, nl.conv_out, o, nl.norm, L.ACT_NONE, residual=x, out=out, label="nl.out")
+    sess.release(o)
+    return y
+
+
 def emit_res_stage(sess, stage, x, out=None):
     """ResStage.forward; `out` (optional) receives the last block's output, e.g. a channel
     slice of a wider buffer so that a later torch.cat costs nothing."""
     cur = x
     n = len(stage.res_blocks)
     for i, blk in enumerate(stage.res_blocks):
-        if _cls_name(blk) != "ResBlock":
+        if _cls_name(blk) == "NonLocal":
+            nxt = emit_nonlocal(sess, blk, cur, out=out if i == n - 1 else None)
+        elif _cls_name(blk) != "ResBlock":
             raise Unsupported("stage element %s" % _cls_name(blk))
-        nxt = emit_res_block(sess, blk, cur, out=out if i == n - 1 else None)
+        else:
+            nxt = emit_res_block(sess, blk, cur, out=out if i == n - 1 else None)
         if cur is not x:
             sess.release(cur)
         cur = nxt
@@ -1205,6 +1298,8 @@ def emit_module_out(sess, m, x, out):
         return emit_res_stage(sess, m, x, out=out)
     if n == "ResBlock":
         return emit_res_block(sess, m, x, out=out)
+    if n == "NonLocal":
+        return emit_nonlocal(sess, m, x, out=out)
     raise Unsupported("no out= emitter for %s" % n)
 
 
@@ -1249,6 +1344,8 @@ def emit_module(sess, m, x):
         return emit_res_stage(sess, m, x)
     if n == "ResBlock":
         return emit_res_block(sess, m, x)
+    if n == "NonLocal":
+        return emit_nonlocal(sess, m, x)
     if n == "ResNetBasicHead":
         return emit_res_head(sess, m, x)
     if _is_a(m, (nn.MaxPool3d, nn.AvgPool3d, nn.AdaptiveAvgPool3d)):

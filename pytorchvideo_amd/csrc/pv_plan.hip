@@ -103,6 +103,7 @@ size_t desc_size(int kind) {
     case PV_OP_MLP_ROWS: return sizeof(pv_mlp_desc);
     case PV_OP_LN_LINEAR: return sizeof(pv_ln_linear_desc);
     case PV_OP_BOTTLENECK: return sizeof(pv_bottleneck_desc);
+    case PV_OP_NONLOCAL: return sizeof(pv_nonlocal_attention_desc);
     default: return 0;
   }
 }
@@ -129,6 +130,7 @@ int run_op(const pv_plan::Op& op, pv_stream_t s) {
     case PV_OP_MLP_ROWS: return pv_mlp_rows(static_cast<const pv_mlp_desc*>(p), s);
     case PV_OP_LN_LINEAR: return pv_ln_linear_rows(static_cast<const pv_ln_linear_desc*>(p), s);
     case PV_OP_BOTTLENECK: return pv_bottleneck(static_cast<const pv_bottleneck_desc*>(p), s);
+    case PV_OP_NONLOCAL: return pv_nonlocal_attention(static_cast<const pv_nonlocal_attention_desc*>(p), s);
     default: return PV_ERR_INVALID;
   }
 }

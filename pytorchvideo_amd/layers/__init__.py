@@ -6,3 +6,4 @@ from .roi_align import RoIAlign, roi_align  # noqa
 from .utils import round_repeats, round_width, set_attributes  # noqa
 from .attention import Mlp, MultiScaleAttention, MultiScaleBlock  # noqa
 from .positional_encoding import SpatioTemporalClsPositionalEncoding  # noqa
+from .nonlocal_net import NonLocal, create_nonlocal  # noqa
