@@ -150,12 +150,12 @@ typedef struct pv_conv3d_desc {
    * NULL: no slot (the 4-channel layout only). */
   const void* x_src_slot;
   int32_t x_src_c;        /* channel planes of the caller's clip, 1..4 (planes beyond them read as 0) */
-  /* GROUPED convolution with 16 or 32 channels per group (create_resnet / create_slowfast(stage_conv_b_num_groups=...),
+  /* GROUPED convolution with 16, 32, 64 or 128 channels per group (create_resnet / create_slowfast(stage_conv_b_num_groups=...),
    * models/resnet.py:98-132; create_csn(stage_conv_b_width_per_group=...), models/csn.py:34,169 -> nn.Conv3d(C, C,
    * groups = G)): 0 / 1 = dense.  Otherwise cin == round_up(C, 8), cout == C, C % groups == 0 and the weights are the
    * compact [cout][taps][gw] (gw = C / groups) in `dtype`: w[co][tap][j] multiplies input channel (co / gw) * gw + j.
-   * Runs where pv_conv3d_grouped_supported(d) is 1 (csrc/pv_gconv.hip), PV_ERR_UNSUPPORTED elsewhere: bf16, gw 16 or 32,
-   * at most 27 taps, strides 1 / 2, dilation 1, scale / shift / act only (no residual, gate, fp32 output, second
+   * Runs where pv_conv3d_grouped_supported(d) is 1 (csrc/pv_gconv.hip for gw 16 / 32, csrc/pv_gconv_wide.hip for
+   * gw 64 / 128), PV_ERR_UNSUPPORTED elsewhere: bf16, one of these four group widths, at most 27 taps, strides 1 / 2, dilation 1, scale / shift / act only (no residual, gate, fp32 output, second
    * operand or fused neighbour, not the 4-channel layout).  The field occupies what was tail padding of the struct and the
    * ABI version did not change with it: callers must zero-initialise the descriptor (as every field added since version 1
    * assumes), or a caller built against an older header passes garbage here. */

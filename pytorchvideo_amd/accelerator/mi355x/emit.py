@@ -95,9 +95,9 @@ def check_conv3d(conv):
     if depthwise and tuple(conv.dilation) != (1, 1, 1):
         raise Unsupported("dilated depthwise conv")
     # channel-wise grouped conv with 2 / 4 / 8 channels per group (create_csn(stage_conv_b_width_per_group=...),
-    # reference models/csn.py:34,169) rides in the depthwise kernel (pv_dwconv3d_desc.gw); 16 / 32 channels per group
-    # (ResNeXt-3D conv_b, the wide-group CSN variants) go to the grouped MFMA kernel in a bf16 session
-    # (pv_conv3d_desc.groups, csrc/pv_gconv.hip); every other grouping is evaluated as a dense conv with block-diagonal
+    # reference models/csn.py:34,169) rides in the depthwise kernel (pv_dwconv3d_desc.gw); 16 / 32 / 64 / 128 channels per
+    # group (ResNeXt-3D conv_b up to 32x16d, the wide-group CSN variants) go to the grouped MFMA kernels in a bf16 session
+    # (pv_conv3d_desc.groups, csrc/pv_gconv.hip and csrc/pv_gconv_wide.hip); every other grouping is evaluated as a dense conv with block-diagonal
     # weights (emit_conv), on the HIP path like the rest of the deployed model
     return depthwise or group_width(conv) > 1
 
@@ -195,7 +195,7 @@ def emit_conv(sess, conv, x, norm=None, act=L.ACT_NONE, residual=None, a_gate=No
     if (conv.groups > 1 and tuning.get("grouped_conv") and sess.itemsize == 2 and not x.f32 and not c4 and dil == (1, 1, 1)
             and conv.in_channels == cout and residual is None and a_gate is None and a_act == L.ACT_NONE and not y_f32
             and dwt is None and pos is None and shortcut is None):
-        # 16 / 32 channels per group: the grouped kernel takes the compact weights; decided by the library from the geometry
+        # 16 / 32 / 64 / 128 channels per group: a grouped kernel takes the compact weights; decided by the library from the geometry
         d = L.Conv3dDesc(B=x.B, Ti=x.T, Hi=x.H, Wi=x.W, cin=cin_p, To=To, Ho=Ho, Wo=Wo, cout=cout, kt=kt, kh=kh, kw=kw,
                          st=st, sh=sh, sw=sw, pt=pt, ph=ph, pw=pw, act=act, dtype=sess.pv_dtype, x_bs=x.bs, y_bs=y.bs,
                          ldx=x.ld, ldy=y.ld, groups=conv.groups)

@@ -1,7 +1,8 @@
 // Grouped 3-D convolution with 16 or 32 channels per group (ResNeXt-3D conv_b, the wide-group CSN variants):
 //   nn.Conv3d(C, C, kernel, stride, padding, groups = C / gw, bias=False) [+ BatchNorm3d eval][+ ReLU | Swish],  gw = 16 | 32
 // (create_resnet / create_slowfast(stage_conv_b_num_groups=...), models/resnet.py:98-132; create_csn(
-// stage_conv_b_width_per_group=...), models/csn.py:34,169).  bf16 in, fp32 accumulation, bf16 out.
+// stage_conv_b_width_per_group=...), models/csn.py:34,169).  bf16 in, fp32 accumulation, bf16 out.  (gw = 64 | 128: the kernel
+// of pv_gconv_wide.hip, reached through the two entry points at the end of this file.)
 //
 // Per group the conv is an implicit GEMM with N = gw output channels and K = taps * gw: with gw = 16 one
 // v_mfma_f32_16x16x32_bf16 covers two taps of a group, with gw = 32 one tap.  27 * gw / (stride^2 + 1) FLOP/B sits around
@@ -287,11 +288,14 @@ __global__ __launch_bounds__(256) void gconv_plane_kernel(const GConv d) {
   }
 }
 
-// Geometry -> launch configuration; false where the kernel does not serve the shape.
-bool gconv_configure(const pv_conv3d_desc& d, GConv& g) {
+}  // namespace
+
+// The scope of the grouped kernels, whatever the group width (which each kernel checks for itself: 16 / 32 here, 64 / 128 in
+// pv_gconv_wide.hip).
+bool pv_gconv_in_scope(const pv_conv3d_desc& d) {
   if (d.dtype != PV_BF16 || d.groups <= 1 || d.cout <= 0 || d.cout % d.groups) return false;
   const int gw = d.cout / d.groups;
-  if ((gw != 16 && gw != 32) || d.cin != d.cout) return false;
+  if (d.cin != d.cout) return false;
   if (d.residual || d.a_gate || d.a_act != PV_ACT_NONE || d.y_f32 || d.dwt_w || d.x2 || d.x2_cin || d.pw2_w || d.pw2_cout ||
       d.pos_spatial || d.pos_temporal || d.x_src_slot || d.c4_wpair)
     return false;
@@ -309,6 +313,19 @@ bool gconv_configure(const pv_conv3d_desc& d, GConv& g) {
   const long x_clip = ((long)d.Ti * d.Hi * d.Wi * d.ldx) * 2, y_clip = ((long)d.To * d.Ho * d.Wo * d.ldy) * 2;
   const int taps = d.kt * d.kh * d.kw;
   if (x_clip >= 0x7fffffffL || y_clip >= 0x7fffffffL || (long)d.cout * taps * gw * 2 >= 0x7fffffffL) return false;
+  return true;
+}
+
+int pv_gconv_wide_supported(const pv_conv3d_desc& d);                 // pv_gconv_wide.hip
+int pv_gconv_wide_try(const pv_conv3d_desc& d, hipStream_t s);        // pv_gconv_wide.hip
+
+namespace {
+
+// Geometry -> launch configuration; false where the kernel does not serve the shape.
+bool gconv_configure(const pv_conv3d_desc& d, GConv& g) {
+  if (!pv_gconv_in_scope(d)) return false;
+  const int gw = d.cout / d.groups, taps = d.kt * d.kh * d.kw;
+  if (gw != 16 && gw != 32) return false;
 
   g = GConv{};
   g.x = d.x; g.w = d.w; g.y = d.y; g.scale = d.scale; g.shift = d.shift;
@@ -350,12 +367,17 @@ bool gconv_configure(const pv_conv3d_desc& d, GConv& g) {
 
 }  // namespace
 
+// 64 / 128 channels per group are the other kernel's (gconv_wide_kernel); the two ranges do not overlap
+static bool gconv_is_wide(const pv_conv3d_desc& d) { return d.groups > 1 && d.cout > 0 && d.cout % d.groups == 0 && d.cout / d.groups >= 64; }
+
 int pv_gconv_supported(const pv_conv3d_desc& d) {
+  if (gconv_is_wide(d)) return pv_gconv_wide_supported(d);
   GConv g;
   return gconv_configure(d, g) ? 1 : 0;
 }
 
 int pv_gconv_try(const pv_conv3d_desc& d, hipStream_t s) {
+  if (gconv_is_wide(d)) return pv_gconv_wide_try(d, s);
   GConv g;
   if (!gconv_configure(d, g)) return PV_ERR_UNSUPPORTED;
   const unsigned grid = (unsigned)((g.units + 7) / 8 * 8 * g.tiles_h * g.tiles_w);

@@ -1,9 +1,10 @@
-"""A/B of the grouped conv kernel (csrc/pv_gconv.hip) against the block-diagonal dense route, one op at a time.
+"""A/B of the grouped conv kernels (csrc/pv_gconv.hip, csrc/pv_gconv_wide.hip) against the block-diagonal dense route, one op
+at a time.
 
-    python tools/bench_gconv.py [--out FILE.md] [--iters 20] [--rounds 5] [--batch 16]
+    python tools/bench_gconv.py [--out FILE.md] [--iters 20] [--rounds 5] [--batch 16] [--min-gw 64]
 
 Every shape is emitted twice through emit_conv into a one-op bf16 Session -- tuning "grouped_conv" on (compact weights,
-gconv_plane_kernel) and off (block-diagonal weights on the dense GEMM route) -- and the two plans are profiled
+gconv_plane_kernel / gconv_wide_kernel) and off (block-diagonal weights on the dense GEMM route) -- and the two plans are profiled
 alternately in the same process (pv_plan_profile: HIP events around the op).  Times are the median over the rounds;
 TFLOP/s and TB/s are on the GROUPED FLOP count and the algorithmic bytes (each input voxel, the compact filter and each
 output voxel once) for both routes, so the columns compare like with like.  The outputs of the two routes are compared
@@ -20,7 +21,9 @@ from pytorchvideo_amd.accelerator.mi355x.session import Session
 
 #          C    gw  H=W  spatial stride
 SHAPES = [(512, 16, 14, 1), (512, 16, 28, 2), (1024, 32, 7, 1), (1024, 32, 14, 2),
-          (64, 16, 56, 1), (128, 16, 28, 1), (256, 16, 14, 1), (512, 16, 7, 1)]
+          (64, 16, 56, 1), (128, 16, 28, 1), (256, 16, 14, 1), (512, 16, 7, 1),
+          # ResNeXt-101 32x8d res5 / 32x16d res4 (2048 channels, 64 per group), 32x16d res5 (4096, 128 per group)
+          (2048, 64, 14, 1), (2048, 64, 14, 2), (2048, 64, 7, 1), (4096, 128, 14, 2), (4096, 128, 7, 1)]
 KERNELS = [(3, 3, 3), (1, 3, 3)]
 
 
@@ -42,12 +45,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--min-gw", type=int, default=0, help="only the shapes with at least this many channels per group")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_gconv needs the GPU: no timing is taken without one")
     rows = ["| C | gw | kernel | in -> out | grouped kernel | grouped ms | dense ms | dense / grouped | grouped TFLOP/s | grouped TB/s | dense TFLOP/s | max rel diff |",
             "|---|---|---|---|---|---|---|---|---|---|---|---|"]
-    for C, gw, hw, s in SHAPES:
+    for C, gw, hw, s in [sh for sh in SHAPES if sh[1] >= a.min_gw]:
         for k in KERNELS:
             torch.manual_seed(C + k[0])
             conv = nn.Conv3d(C, C, k, stride=(1, s, s), padding=tuple(v // 2 for v in k), groups=C // gw, bias=False)
