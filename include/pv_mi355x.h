@@ -112,8 +112,10 @@ typedef struct pv_conv3d_desc {
   const float* pos_spatial;
   const float* pos_temporal;
   /* Dilation of the taps (create_resnet's stage_conv_b_dilation, models/resnet.py:601-1003: the
-   * detection backbone of models/hub/resnet.py:72-88 dilates res5); 0 means 1.  Dense convs only,
-   * not the first-layer layout; kernel extent (k-1)*dilation+1 enters the output-size check. */
+   * detection backbone of models/hub/resnet.py:72-88 dilates res5); 0 means 1.  Dense convs in any
+   * dimension, grouped convs (`groups` below) in H / W up to 4 at stride 1 in the dilated dimension;
+   * not the first-layer layout; kernel extent (k-1)*dilation+1 enters the output-size check, and
+   * padding up to that extent is valid. */
   int32_t dil_t, dil_h, dil_w;
   /* Optional second operand concatenated along K -- the projection shortcut of a residual block
    * (models/resnet.py:428-438 built, :1179-1189 added) folded into conv_c:
@@ -155,7 +157,8 @@ typedef struct pv_conv3d_desc {
    * groups = G)): 0 / 1 = dense.  Otherwise cin == round_up(C, 8), cout == C, C % groups == 0 and the weights are the
    * compact [cout][taps][gw] (gw = C / groups) in `dtype`: w[co][tap][j] multiplies input channel (co / gw) * gw + j.
    * Runs where pv_conv3d_grouped_supported(d) is 1 (csrc/pv_gconv.hip for gw 16 / 32, csrc/pv_gconv_wide.hip for
-   * gw 64 / 128), PV_ERR_UNSUPPORTED elsewhere: bf16, one of these four group widths, at most 27 taps, strides 1 / 2, dilation 1, scale / shift / act only (no residual, gate, fp32 output, second
+   * gw 64 / 128), PV_ERR_UNSUPPORTED elsewhere: bf16, one of these four group widths, at most 27 taps, strides 1 / 2, dil_h / dil_w up to 4
+   * where that dimension's stride is 1 (a polyphase split: each phase of the outputs is an undilated conv) and no dil_t, scale / shift / act only (no residual, gate, fp32 output, second
    * operand or fused neighbour, not the 4-channel layout).  The field occupies what was tail padding of the struct and the
    * ABI version did not change with it: callers must zero-initialise the descriptor (as every field added since version 1
    * assumes), or a caller built against an older header passes garbage here. */

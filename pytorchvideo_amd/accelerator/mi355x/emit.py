@@ -97,8 +97,10 @@ def check_conv3d(conv):
     # channel-wise grouped conv with 2 / 4 / 8 channels per group (create_csn(stage_conv_b_width_per_group=...),
     # reference models/csn.py:34,169) rides in the depthwise kernel (pv_dwconv3d_desc.gw); 16 / 32 / 64 / 128 channels per
     # group (ResNeXt-3D conv_b up to 32x16d, the wide-group CSN variants) go to the grouped MFMA kernels in a bf16 session
-    # (pv_conv3d_desc.groups, csrc/pv_gconv.hip and csrc/pv_gconv_wide.hip); every other grouping is evaluated as a dense conv with block-diagonal
-    # weights (emit_conv), on the HIP path like the rest of the deployed model
+    # (pv_conv3d_desc.groups, csrc/pv_gconv.hip and csrc/pv_gconv_wide.hip), dilated in H / W up to 4 at stride 1 included (the
+    # res5 conv_b of a detection backbone); every other grouping -- other widths, 2 / 4 / 8 per group with a dilation, a temporal
+    # dilation, a strided dilated dimension -- is evaluated as a dense conv with block-diagonal weights (emit_conv), on the HIP
+    # path like the rest of the deployed model.  A dilated DEPTHWISE conv is still declined: pv_dwconv3d_desc has no dilation.
     return depthwise or group_width(conv) > 1
 
 
@@ -192,13 +194,15 @@ def emit_conv(sess, conv, x, norm=None, act=L.ACT_NONE, residual=None, a_gate=No
     # pack [cout][taps][cin_p]
     w = conv.weight.detach().float().cpu()  # [cout, cin / groups, kt, kh, kw]
     grouped = 0
-    if (conv.groups > 1 and tuning.get("grouped_conv") and sess.itemsize == 2 and not x.f32 and not c4 and dil == (1, 1, 1)
+    if (conv.groups > 1 and tuning.get("grouped_conv") and sess.itemsize == 2 and not x.f32 and not c4
+            and (dil == (1, 1, 1) or tuning.get("grouped_conv_dilated"))
             and conv.in_channels == cout and residual is None and a_gate is None and a_act == L.ACT_NONE and not y_f32
             and dwt is None and pos is None and shortcut is None):
-        # 16 / 32 / 64 / 128 channels per group: a grouped kernel takes the compact weights; decided by the library from the geometry
+        # 16 / 32 / 64 / 128 channels per group: a grouped kernel takes the compact weights; decided by the library from the
+        # geometry (dilation included: up to 4 in H / W at stride 1, none in T -- anything else stays on the dense route)
         d = L.Conv3dDesc(B=x.B, Ti=x.T, Hi=x.H, Wi=x.W, cin=cin_p, To=To, Ho=Ho, Wo=Wo, cout=cout, kt=kt, kh=kh, kw=kw,
                          st=st, sh=sh, sw=sw, pt=pt, ph=ph, pw=pw, act=act, dtype=sess.pv_dtype, x_bs=x.bs, y_bs=y.bs,
-                         ldx=x.ld, ldy=y.ld, groups=conv.groups)
+                         ldx=x.ld, ldy=y.ld, groups=conv.groups, dil_t=dil[0], dil_h=dil[1], dil_w=dil[2])
         if L.lib().pv_conv3d_grouped_supported(C.byref(d)) == 1:
             grouped = conv.groups
     if conv.groups > 1 and not grouped:   # grouped, not channel-wise: block-diagonal dense weights

@@ -11,7 +11,8 @@ OPTIONS = {
     "fuse_block": True,          # a whole X3D residual block without squeeze-excitation as ONE launch (pv_bottleneck, round 6)  (emit.can_fuse_bottleneck)
     "fuse_bc": True,             # conv_b (narrow dense conv) -> pointwise conv_c of a ResNet / SlowFast bottleneck as ONE launch (pv_conv3d pw2_*, round 6)  (emit.can_fuse_conv_bc)
     "grouped_conv": True,        # grouped conv with 16 / 32 / 64 / 128 channels per group on the grouped MFMA kernels instead of block-diagonal dense weights  (emit.emit_conv)
-    "nonlocal_block": True,      # NonLocal (layers/nonlocal_net.py) inside a bf16 plan, its attention on pv_nonlocal_attention; off: the block stays a torch module between converted blocks  (emit.emit_nonlocal, blocks._probe)
+    "grouped_conv_dilated": True,  # ... also where the conv is dilated in H / W (polyphase form of the same kernels); off: dilated grouped convs keep the block-diagonal dense route  (emit.emit_conv)
+    "nonlocal_block": True,     # NonLocal (layers/nonlocal_net.py) inside a bf16 plan, its attention on pv_nonlocal_attention; off: the block stays a torch module between converted blocks  (emit.emit_nonlocal, blocks._probe)
     "fuse_stem": True,           # X3D stem (conv_xy + temporal depthwise + BN + ReLU) in one launch
     "stem_ncdhw": True,          # ... that reads the caller's bf16 NCDHW clip itself: no ingest launch (round 7)  (emit.emit_conv)
     "fuse_kv_pool": True,        # MViT pool_k + pool_v as one depthwise launch                   (emit_mvit)

@@ -144,6 +144,36 @@ __host__ __device__ __forceinline__ int pv_round_up(int v, int m) { return (v + 
 __host__ __device__ __forceinline__ long pv_ceil_div(long a, long b) { return (a + b - 1) / b; }
 inline unsigned pv_blocks(long total, int threads) { return (unsigned)pv_ceil_div(total, threads); }
 
+// ---- polyphase split of a conv dilated by (dh, dw) at stride 1 (pv_gconv.hip, pv_gconv_wide.hip) ----
+// Output voxels with h = i dh + rh, w = j dw + rw form phase (rh, rw): an UNDILATED conv on the input voxels of one residue.
+// Phase r of an axis of n outputs has ceil((n - r) / dil) of them (none where n <= r), tiled on its own; a unit's tiles are
+// numbered phase-major (rh, then rw, then the tile inside the phase), so the phases of a slab -- same filter -- are neighbours.
+__host__ __device__ __forceinline__ int pv_phase_extent(int n, int dil, int r) { return n > r ? (n - r + dil - 1) / dil : 0; }
+__host__ __device__ __forceinline__ int pv_phase_tiles(int n, int dil, int tile) {   // tiles of all phases of one axis
+  int t = 0;
+  for (int r = 0; r < dil; ++r) t += (pv_phase_extent(n, dil, r) + tile - 1) / tile;
+  return t;
+}
+struct PvPhaseTile { int rh, rw, Hop, Wop, ho0, wo0; };   // phase, its extent, first output (phase coordinates) of the tile
+__device__ __forceinline__ PvPhaseTile pv_phase_tile(int t, int Ho, int Wo, int dh, int dw, int TH, int TW) {
+  const int row = pv_phase_tiles(Wo, dw, TW);               // tiles of one tile row of all W phases
+  PvPhaseTile p{0, 0, 0, 0, 0, 0};
+  int th = 0, tw = 0;
+  for (;; ++p.rh) {                                         // t < the unit's tile count: both walks end on a phase with tiles
+    p.Hop = pv_phase_extent(Ho, dh, p.rh); th = (p.Hop + TH - 1) / TH;
+    if (t < th * row || p.rh == dh - 1) break;
+    t -= th * row;
+  }
+  for (;; ++p.rw) {
+    p.Wop = pv_phase_extent(Wo, dw, p.rw); tw = (p.Wop + TW - 1) / TW;
+    if (t < th * tw || p.rw == dw - 1) break;
+    t -= th * tw;
+  }
+  tw = tw > 0 ? tw : 1;
+  p.ho0 = (t / tw) * TH; p.wo0 = (t % tw) * TW;
+  return p;
+}
+
 // ---- host side: from a descriptor's dtype code to the element type ----
 // Calls f(PvType<T>()) with T = float | bf16_t (U8: | unsigned char, the sources of the layout kernels) and returns its
 // status; PV_ERR_UNSUPPORTED for every other code.  f is a generic lambda that launches its kernel<T> through PV_LAUNCH

@@ -24,6 +24,13 @@
 //   * epilogue: fp32 scale / shift / activation, one rounding, 16-byte stores.  gw = 32: the two row tiles of the group are
 //     interleaved in groups of 4 rows (as in pv_lateral.hip), so a lane's accumulators are 8 consecutive channels.  gw = 16: a
 //     row tile is one group, so lanes q and q ^ 1 trade halves of their two voxel tiles instead (4 cross-lane moves).
+//   * dilation (1, dh, dw), dh, dw <= 4, at stride 1 where dilated (the res5 conv_b of a detection backbone: DIL = true): a
+//     polyphase split, not a wider halo.  The outputs with h = i dh + rh, w = j dw + rw are an undilated conv of the inputs of one
+//     residue, so a workgroup owns (clip, slab, PHASE (rh, rw), tile of that phase's outputs) and only the two places that form
+//     a global address know: halo row hr of the tile is image row (ho0 + hr) dh + rh - ph, output (i, j) is stored at
+//     ((ho0 + i) dh + rh, (wo0 + j) dw + rw).  Ring, voxel stride, tap table, operand reads and the K loop are the undilated
+//     kernel's; the halo stays (TH - 1) + kh rows.  Phases are tiled on their own extents (pv_phase_tile, pv_common.h); all
+//     tiles of all phases of a (clip, slab) sit on one XCD residue, phase-major.
 #include "pv_common.h"
 
 namespace {
@@ -50,10 +57,13 @@ struct GConv {
   int hcols;                   // halo columns that exist: (TW - 1) * sw + kw
   int vs, plane_bytes, ksteps; // LDS voxel stride (bytes), bytes of a ring slot, K steps
   int lds;
+  // dilated form only (DIL): dilation in H / W, tiles of all phases of one unit
+  int dh, dw, ptiles;
 };
 
-// GW: channels per group.  NG x TPG 16-row MFMA tiles per slab: 4 groups x 1 tile, or 1 group x 2 tiles.
-template <int GW>
+// GW: channels per group.  NG x TPG 16-row MFMA tiles per slab: 4 groups x 1 tile, or 1 group x 2 tiles.  DIL: the workgroup's
+// tile is a tile of one phase of the dilated conv.
+template <int GW, bool DIL>
 __global__ __launch_bounds__(256) void gconv_plane_kernel(const GConv d) {
   constexpr int NG = GW == 16 ? 4 : 1, TPG = GW / 16, MT = NG * TPG, NTW = 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -69,12 +79,14 @@ __global__ __launch_bounds__(256) void gconv_plane_kernel(const GConv d) {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n16 = lane & 15, q = lane >> 4;
   // the tiles of one (clip, slab) share halos: they are consecutive slots of ONE residue mod 8 (one XCD)
-  const int ntile = d.tiles_h * d.tiles_w;
+  const int ntile = DIL ? d.ptiles : d.tiles_h * d.tiles_w;
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
   const int unit = (slot / ntile) * 8 + xcd, tile = slot % ntile;
   if (unit >= d.units) return;                             // the grid is padded to 8 units
   const int b = unit / d.nslabs, c0 = (unit % d.nslabs) * d.CS;
-  const int ho0 = (tile / d.tiles_w) * d.TH, wo0 = (tile % d.tiles_w) * d.TW;
+  PvPhaseTile pp{0, 0, d.Ho, d.Wo, (tile / d.tiles_w) * d.TH, (tile % d.tiles_w) * d.TW};
+  if constexpr (DIL) pp = pv_phase_tile(tile, d.Ho, d.Wo, d.dh, d.dw, d.TH, d.TW);
+  const int ho0 = pp.ho0, wo0 = pp.wo0;                    // DIL: in the coordinates of phase (pp.rh, pp.rw)
   const int live = (min(d.CS, d.C - c0)) / GW;             // groups of this slab that exist
 
   const bf16_t* xb = static_cast<const bf16_t*>(d.x) + (long)b * d.x_bs;
@@ -96,7 +108,9 @@ __global__ __launch_bounds__(256) void gconv_plane_kernel(const GConv d) {
     const int v = id / nch, ch = id - v * nch;
     const int hr = v / d.HTW, sl = v - hr * d.HTW;
     const int hc = d.sw == 2 ? (sl % d.HTWh) * 2 + sl / d.HTWh : sl;   // even columns first, odd columns second
-    const int h = ho0 * d.sh - d.ph + hr, w = wo0 * d.sw - d.pw + hc;
+    // DIL: halo voxel (hr, hc) of the phase is image voxel ((.) dh + rh, (.) dw + rw); the stride is 1 wherever dh / dw is not
+    const int h = DIL ? (ho0 * d.sh + hr) * d.dh + pp.rh - d.ph : ho0 * d.sh - d.ph + hr;
+    const int w = DIL ? (wo0 * d.sw + hc) * d.dw + pp.rw - d.pw : wo0 * d.sw - d.pw + hc;
     const bool ok = id < stage_total && hc < d.hcols && (unsigned)h < (unsigned)d.Hi && (unsigned)w < (unsigned)d.Wi && c0 + ch * 8 < d.C;
     soff[j] = ok ? (((unsigned)h * d.Wi + w) * (unsigned)d.ldx + c0 + ch * 8) * 2u : kGcOob;
     sdst[j] = id < stage_total ? v * d.vs + ch * 16 : -1;
@@ -179,7 +193,11 @@ __global__ __launch_bounds__(256) void gconv_plane_kernel(const GConv d) {
     const int r = m / d.TW, c = m - r * d.TW;
     vb[i] = (r * d.sh * d.HTW + c) * d.vs + (GW == 16 ? (q & 1) * 16 : q * 16);
     const int ho = ho0 + r, wo = wo0 + c;
-    yo[i] = (ho < d.Ho && wo < d.Wo) ? (((unsigned)ho * d.Wo + wo) * (unsigned)d.ldy + c0) * 2u : kGcOob;
+    if constexpr (DIL)
+      yo[i] = (ho < pp.Hop && wo < pp.Wop)
+                  ? (((unsigned)(ho * d.dh + pp.rh) * d.Wo + (wo * d.dw + pp.rw)) * (unsigned)d.ldy + c0) * 2u : kGcOob;
+    else
+      yo[i] = (ho < d.Ho && wo < d.Wo) ? (((unsigned)ho * d.Wo + wo) * (unsigned)d.ldy + c0) * 2u : kGcOob;
   }
   const unsigned y_plane = (unsigned)d.Ho * d.Wo * (unsigned)d.ldy * 2u;
   const int ring_bytes = R * d.plane_bytes;
@@ -299,14 +317,18 @@ bool pv_gconv_in_scope(const pv_conv3d_desc& d) {
   if (d.residual || d.a_gate || d.a_act != PV_ACT_NONE || d.y_f32 || d.dwt_w || d.x2 || d.x2_cin || d.pw2_w || d.pw2_cout ||
       d.pos_spatial || d.pos_temporal || d.x_src_slot || d.c4_wpair)
     return false;
-  if (d.dil_t > 1 || d.dil_h > 1 || d.dil_w > 1) return false;
+  // dilation in H / W up to 4 as a polyphase split (DIL): stride 1 in a dilated dimension, none in T
+  const int dh = d.dil_h > 1 ? d.dil_h : 1, dw = d.dil_w > 1 ? d.dil_w : 1;
+  if (d.dil_t > 1 || d.dil_t < 0 || d.dil_h < 0 || d.dil_w < 0 || dh > 4 || dw > 4) return false;
+  const int eh = (d.kh - 1) * dh + 1, ew = (d.kw - 1) * dw + 1;   // kernel extents
   if (d.act != PV_ACT_NONE && d.act != PV_ACT_RELU && d.act != PV_ACT_SWISH) return false;
   if (d.B <= 0 || d.Ti <= 0 || d.Hi <= 0 || d.Wi <= 0 || d.To <= 0 || d.Ho <= 0 || d.Wo <= 0) return false;
   if (d.kt < 1 || d.kh < 1 || d.kw < 1 || d.kt > 27 || d.kh > 27 || d.kw > 27 || d.kt * d.kh * d.kw > 27) return false;
   if (d.st < 1 || d.st > 2 || d.sh < 1 || d.sh > 2 || d.sw < 1 || d.sw > 2) return false;
-  if (d.pt < 0 || d.ph < 0 || d.pw < 0 || d.pt > d.kt || d.ph > d.kh || d.pw > d.kw) return false;
-  if ((d.Ti + 2 * d.pt - d.kt) / d.st + 1 != d.To || (d.Hi + 2 * d.ph - d.kh) / d.sh + 1 != d.Ho ||
-      (d.Wi + 2 * d.pw - d.kw) / d.sw + 1 != d.Wo || d.Ti + 2 * d.pt < d.kt || d.Hi + 2 * d.ph < d.kh || d.Wi + 2 * d.pw < d.kw)
+  if ((dh > 1 && d.sh != 1) || (dw > 1 && d.sw != 1)) return false;
+  if (d.pt < 0 || d.ph < 0 || d.pw < 0 || d.pt > d.kt || d.ph > eh || d.pw > ew) return false;
+  if ((d.Ti + 2 * d.pt - d.kt) / d.st + 1 != d.To || (d.Hi + 2 * d.ph - eh) / d.sh + 1 != d.Ho ||
+      (d.Wi + 2 * d.pw - ew) / d.sw + 1 != d.Wo || d.Ti + 2 * d.pt < d.kt || d.Hi + 2 * d.ph < eh || d.Wi + 2 * d.pw < ew)
     return false;
   if (d.ldx < d.cout || d.ldy < d.cout || d.ldx % 8 || d.ldy % 8 || d.x_bs % 8 || d.y_bs % 8) return false;
   // 32-bit byte offsets inside a clip, and a grid that fits
@@ -334,6 +356,8 @@ bool gconv_configure(const pv_conv3d_desc& d, GConv& g) {
   g.kt = d.kt; g.kh = d.kh; g.kw = d.kw; g.st = d.st; g.sh = d.sh; g.sw = d.sw; g.pt = d.pt; g.ph = d.ph; g.pw = d.pw;
   g.act = d.act;
   g.ksteps = gw == 16 ? (taps + 1) / 2 : taps;
+  g.dh = d.dil_h > 1 ? d.dil_h : 1; g.dw = d.dil_w > 1 ? d.dil_w : 1;
+  const int Wop = pv_phase_extent(d.Wo, g.dw, 0);    // columns of the widest phase (Wo itself where undilated)
   // Tiles, widest first; planes of at most 8 columns take the square tile.  The first one whose filter slab, kt + 1 halo
   // planes and staging registers fit is taken; at gw = 16 a 32-channel slab is the fallback of a 64-channel one.
   static const int kTiles[3][3] = {{8, 16, 4}, {4, 16, 2}, {8, 8, 2}};
@@ -342,7 +366,7 @@ bool gconv_configure(const pv_conv3d_desc& d, GConv& g) {
   for (int k = 0; k < (cs_max > 32 ? 2 : 1); ++k) {
     const int cs = slabs[k];
     for (int t = 0; t < 3; ++t) {
-      const int* tl = kTiles[d.Wo <= 8 ? (t + 2) % 3 : t];
+      const int* tl = kTiles[Wop <= 8 ? (t + 2) % 3 : t];
       g.TH = tl[0]; g.TW = tl[1]; g.nwaves = tl[2]; g.CS = cs;
       g.hcols = (g.TW - 1) * d.sw + d.kw;
       g.HTH = (g.TH - 1) * d.sh + d.kh;
@@ -357,12 +381,22 @@ bool gconv_configure(const pv_conv3d_desc& d, GConv& g) {
       g.tiles_h = (d.Ho + g.TH - 1) / g.TH; g.tiles_w = (d.Wo + g.TW - 1) / g.TW;
       g.nslabs = (d.cout + cs - 1) / cs;
       const long units = (long)d.B * g.nslabs;
-      if ((units + 7) / 8 * 8 * g.tiles_h * g.tiles_w > 0x7fffffffL) return false;
+      g.ptiles = pv_phase_tiles(d.Ho, g.dh, g.TH) * pv_phase_tiles(d.Wo, g.dw, g.TW);   // = tiles_h * tiles_w where undilated
+      if ((units + 7) / 8 * 8 * g.ptiles > 0x7fffffffL) return false;
       g.units = (int)units;
       return true;
     }
   }
   return false;
+}
+
+template <int GW, bool DIL> int gconv_launch(const GConv& g, hipStream_t s) {
+  const unsigned grid = (unsigned)((g.units + 7) / 8 * 8 * g.ptiles);
+  if (g.lds > 64 * 1024)
+    PV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gconv_plane_kernel<GW, DIL>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
+  PV_LAUNCH((gconv_plane_kernel<GW, DIL>), dim3(grid), dim3(g.nwaves * 64), (size_t)g.lds, s, g);
+  return pv_launch_status();
 }
 
 }  // namespace
@@ -380,20 +414,6 @@ int pv_gconv_try(const pv_conv3d_desc& d, hipStream_t s) {
   if (gconv_is_wide(d)) return pv_gconv_wide_try(d, s);
   GConv g;
   if (!gconv_configure(d, g)) return PV_ERR_UNSUPPORTED;
-  const unsigned grid = (unsigned)((g.units + 7) / 8 * 8 * g.tiles_h * g.tiles_w);
-  auto launch = [&](auto kern) -> int {
-    if (g.lds > 64 * 1024)
-      PV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
-    return PV_OK;
-  };
-  if (d.cout / d.groups == 16) {
-    const int r = launch(gconv_plane_kernel<16>);
-    if (r != PV_OK) return r;
-    PV_LAUNCH(gconv_plane_kernel<16>, dim3(grid), dim3(g.nwaves * 64), (size_t)g.lds, s, g);
-  } else {
-    const int r = launch(gconv_plane_kernel<32>);
-    if (r != PV_OK) return r;
-    PV_LAUNCH(gconv_plane_kernel<32>, dim3(grid), dim3(g.nwaves * 64), (size_t)g.lds, s, g);
-  }
-  return pv_launch_status();
+  return d.cout / d.groups == 16 ? (g.dh * g.dw > 1 ? gconv_launch<16, true>(g, s) : gconv_launch<16, false>(g, s))
+                                 : (g.dh * g.dw > 1 ? gconv_launch<32, true>(g, s) : gconv_launch<32, false>(g, s));
 }

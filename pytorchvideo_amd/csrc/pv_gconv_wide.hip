@@ -19,6 +19,10 @@
 //     second barrier separates the MFMAs from the write of plane p + 1; the request is still in flight under the MFMAs.
 //   * B operand: one ds_read_b128 per lane and K step -- lane (n, h) reads channels 16 s + 8 h of output voxel n displaced by
 //     the tap; it feeds a 32-row tile.  Voxel stride gw * 2 + 16 bytes (16 B x odd), stride-2 columns even-first / odd-second.
+//   * dilation (1, dh, dw) (DIL = true): the polyphase split of gconv_plane_kernel -- the workgroup's tile is a tile of ONE
+//     phase (rh, rw) of the outputs, and the phase enters only the image address of a staged voxel row and the store address.
+//     The filter stream does not depend on the phase; the dh dw phases of a group are neighbours in the grid, so the rows they
+//     all stream stay in one XCD's L2.
 #include "pv_common.h"
 
 bool pv_gconv_in_scope(const pv_conv3d_desc& d);   // pv_gconv.hip: everything gconv_configure demands but the group width
@@ -43,10 +47,12 @@ struct GWide {
   int tiles_h, tiles_w, groups, units;   // units = B * groups
   int HTH, HTW, HTWh, hcols;   // halo rows, column slots per row, slots per column parity (sw = 2), halo columns that exist
   int vs, plane_bytes, lds;    // LDS voxel stride (bytes), bytes of a ring slot, dynamic LDS
+  // dilated form only (DIL): dilation in H / W, tiles of all phases of one unit
+  int dh, dw, ptiles;
 };
 
-// GW: channels per group; NT: 32-voxel column tiles of a wave.
-template <int GW, int NT>
+// GW: channels per group; NT: 32-voxel column tiles of a wave; DIL: the tile is a tile of one phase of the dilated conv.
+template <int GW, int NT, bool DIL>
 __global__ __launch_bounds__(256) void gconv_wide_kernel(const GWide d) {
   constexpr int RT = GW / 32, KS = GW / 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -61,12 +67,14 @@ __global__ __launch_bounds__(256) void gconv_wide_kernel(const GWide d) {
   const int n32 = lane & 31, h = lane >> 5;
   const int rt = wave % RT, vsp = wave / RT;               // the wave's row tile, its share of the tile's voxels
   // the tiles of one (clip, group) share halos: they are consecutive slots of ONE residue mod 8 (one XCD)
-  const int ntile = d.tiles_h * d.tiles_w;
+  const int ntile = DIL ? d.ptiles : d.tiles_h * d.tiles_w;
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
   const int unit = (slot / ntile) * 8 + xcd, tile = slot % ntile;
   if (unit >= d.units) return;                             // the grid is padded to 8 units
   const int b = unit / d.groups, c0 = (unit % d.groups) * GW;
-  const int ho0 = (tile / d.tiles_w) * d.TH, wo0 = (tile % d.tiles_w) * d.TW;
+  PvPhaseTile pp{0, 0, d.Ho, d.Wo, (tile / d.tiles_w) * d.TH, (tile % d.tiles_w) * d.TW};
+  if constexpr (DIL) pp = pv_phase_tile(tile, d.Ho, d.Wo, d.dh, d.dw, d.TH, d.TW);
+  const int ho0 = pp.ho0, wo0 = pp.wo0;                    // DIL: in the coordinates of phase (pp.rh, pp.rw)
 
   const bf16_t* xb = static_cast<const bf16_t*>(d.x) + (long)b * d.x_bs;
   bf16_t* yb = static_cast<bf16_t*>(d.y) + (long)b * d.y_bs;
@@ -99,7 +107,9 @@ __global__ __launch_bounds__(256) void gconv_wide_kernel(const GWide d) {
     const int v = id / nch, ch = id - v * nch;
     const int hr = v / d.HTW, sl = v - hr * d.HTW;
     const int hc = d.sw == 2 ? (sl % d.HTWh) * 2 + sl / d.HTWh : sl;   // even columns first, odd columns second
-    const int hh = ho0 * d.sh - d.ph + hr, ww = wo0 * d.sw - d.pw + hc;
+    // DIL: halo voxel (hr, hc) of the phase is image voxel ((.) dh + rh, (.) dw + rw); the stride is 1 wherever dh / dw is not
+    const int hh = DIL ? (ho0 * d.sh + hr) * d.dh + pp.rh - d.ph : ho0 * d.sh - d.ph + hr;
+    const int ww = DIL ? (wo0 * d.sw + hc) * d.dw + pp.rw - d.pw : wo0 * d.sw - d.pw + hc;
     const bool ok = id < stage_total && hc < d.hcols && (unsigned)hh < (unsigned)d.Hi && (unsigned)ww < (unsigned)d.Wi;
     soff[j] = ok ? (((unsigned)hh * d.Wi + ww) * (unsigned)d.ldx + c0 + ch * 8) * 2u : kGwOob;
     sdst[j] = id < stage_total ? v * d.vs + ch * 16 : -1;
@@ -150,7 +160,11 @@ __global__ __launch_bounds__(256) void gconv_wide_kernel(const GWide d) {
     const int r = m / d.TW, c = m - r * d.TW;
     vb[i] = (r * d.sh * d.HTW + c) * d.vs + h * 16;
     const int ho = ho0 + r, wo = wo0 + c;
-    yo[i] = (ho < d.Ho && wo < d.Wo) ? (((unsigned)ho * d.Wo + wo) * (unsigned)d.ldy + c0 + rt * 32 + h * 16) * 2u : kGwOob;
+    if constexpr (DIL)
+      yo[i] = (ho < pp.Hop && wo < pp.Wop)
+                  ? (((unsigned)(ho * d.dh + pp.rh) * d.Wo + (wo * d.dw + pp.rw)) * (unsigned)d.ldy + c0 + rt * 32 + h * 16) * 2u : kGwOob;
+    else
+      yo[i] = (ho < d.Ho && wo < d.Wo) ? (((unsigned)ho * d.Wo + wo) * (unsigned)d.ldy + c0 + rt * 32 + h * 16) * 2u : kGwOob;
   }
   const unsigned y_plane = (unsigned)d.Ho * d.Wo * (unsigned)d.ldy * 2u;
   const int ring_bytes = R * d.plane_bytes;
@@ -246,6 +260,8 @@ bool gwide_configure(const pv_conv3d_desc& d, GWide& g) {
   g.kt = d.kt; g.kh = d.kh; g.kw = d.kw; g.st = d.st; g.sh = d.sh; g.sw = d.sw; g.pt = d.pt; g.ph = d.ph; g.pw = d.pw;
   g.act = d.act;
   g.groups = d.groups;
+  g.dh = d.dil_h > 1 ? d.dil_h : 1; g.dw = d.dil_w > 1 ? d.dil_w : 1;
+  const int Wop = pv_phase_extent(d.Wo, g.dw, 0);    // columns of the widest phase (Wo itself where undilated)
   // Tiles, largest first (a larger tile streams the filter less often per output voxel); planes of at most 8 columns take the
   // 8-column tiles only.  The first tile whose ring of kt + 1 halo planes and staging registers fit is taken; if none does,
   // the first that fits with kt planes.
@@ -253,7 +269,7 @@ bool gwide_configure(const pv_conv3d_desc& d, GWide& g) {
   static const GwTile kTiles128[4] = {{8, 16, 4, 4}, {4, 16, 2, 4}, {8, 8, 2, 4}, {4, 8, 1, 4}};
   const GwTile* tiles = gw == 64 ? kTiles64 : kTiles128;
   for (int R = d.kt + 1; R >= d.kt; --R) {
-    for (int t = d.Wo <= 8 ? 2 : 0; t < 4; ++t) {
+    for (int t = Wop <= 8 ? 2 : 0; t < 4; ++t) {
       g.TH = tiles[t].th; g.TW = tiles[t].tw; g.NT = tiles[t].nt; g.nwaves = tiles[t].nwaves; g.R = R;
       g.hcols = (g.TW - 1) * d.sw + d.kw;
       g.HTH = (g.TH - 1) * d.sh + d.kh;
@@ -267,7 +283,8 @@ bool gwide_configure(const pv_conv3d_desc& d, GWide& g) {
       g.lds = (int)lds;
       g.tiles_h = (d.Ho + g.TH - 1) / g.TH; g.tiles_w = (d.Wo + g.TW - 1) / g.TW;
       const long units = (long)d.B * d.groups;
-      if ((units + 7) / 8 * 8 * g.tiles_h * g.tiles_w > 0x7fffffffL) return false;
+      g.ptiles = pv_phase_tiles(d.Ho, g.dh, g.TH) * pv_phase_tiles(d.Wo, g.dw, g.TW);   // = tiles_h * tiles_w where undilated
+      if ((units + 7) / 8 * 8 * g.ptiles > 0x7fffffffL) return false;
       g.units = (int)units;
       return true;
     }
@@ -275,13 +292,17 @@ bool gwide_configure(const pv_conv3d_desc& d, GWide& g) {
   return false;
 }
 
-template <int GW, int NT> int gwide_launch(const GWide& g, hipStream_t s) {
-  const unsigned grid = (unsigned)((g.units + 7) / 8 * 8 * g.tiles_h * g.tiles_w);
+template <int GW, int NT, bool DIL> int gwide_launch_as(const GWide& g, hipStream_t s) {
+  const unsigned grid = (unsigned)((g.units + 7) / 8 * 8 * g.ptiles);
   if (g.lds > 64 * 1024)
-    PV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gconv_wide_kernel<GW, NT>),
+    PV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gconv_wide_kernel<GW, NT, DIL>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, g.lds));
-  PV_LAUNCH((gconv_wide_kernel<GW, NT>), dim3(grid), dim3(g.nwaves * 64), (size_t)g.lds, s, g);
+  PV_LAUNCH((gconv_wide_kernel<GW, NT, DIL>), dim3(grid), dim3(g.nwaves * 64), (size_t)g.lds, s, g);
   return pv_launch_status();
+}
+
+template <int GW, int NT> int gwide_launch(const GWide& g, hipStream_t s) {
+  return g.dh * g.dw > 1 ? gwide_launch_as<GW, NT, true>(g, s) : gwide_launch_as<GW, NT, false>(g, s);
 }
 
 }  // namespace
