@@ -230,6 +230,17 @@ typedef struct pv_dwconv3d_desc {
   int32_t dtype;
   int32_t n_prefix;          /* rows before the grid in each batch item (the cls    */
                              /* token of layers/attention.py:185-186) copied verbatim */
+  /* Dilation of the taps (create_resnet's stage_conv_b_dilation on a depthwise or channel-wise grouped conv_b: the res5 of an
+   * ir-CSN / X3D-style detection backbone, stride 1 and dilation (1, 2, 2)); 0 means 1, a negative value is PV_ERR_INVALID.
+   * dil_t here, dil_h / dil_w behind `gw`: the three fields occupy what were the two padding holes of the struct (offsets 156
+   * and 196), its size (200 bytes) and the ABI version did not change with them: callers must zero-initialise the descriptor
+   * (as every field added since version 1 assumes), or a caller built against an older header passes garbage here.
+   * The kernel extent (k-1)*dilation+1 enters the output-size check, and padding up to that extent is valid.  Any dilation,
+   * stride, tap count and dtype runs in the generic kernel; bf16 3x3x3 at stride 1 with dil_t 1, dil_h / dil_w up to 4 and
+   * "same" padding (pt 1, ph = dil_h, pw = dil_w) runs in the plane-streaming kernel as a polyphase split (each phase
+   * ho = i dil_h + rh, wo = j dil_w + rw of the outputs is an undilated conv; psum blocks are numbered phase-major).
+   * Not with n_prefix, w_mod or pw_w (PV_ERR_UNSUPPORTED): token pooling convs and the fused producer are never dilated. */
+  int32_t dil_t;
   /* Optional fused pointwise producer -- conv_a + norm_a + act_a of an X3D / ir-CSN bottleneck
    * (models/x3d.py:169-189, models/resnet.py:1345-1352): when pw_w is set, x is the 1x1x1 conv's
    * INPUT (pw_cin channels, row stride ldx) and the depthwise conv consumes
@@ -244,6 +255,7 @@ typedef struct pv_dwconv3d_desc {
    * channel's own 8-channel chunk.  0 / 1 = depthwise.  Weights [taps][gw][round_up(C,8)] fp32: w[t][j][c]
    * multiplies input channel (c / gw) * gw + j.  No w_mod, no fused producer, C % gw == 0. */
   int32_t gw;
+  int16_t dil_h, dil_w;      /* see dil_t */
 } pv_dwconv3d_desc;
 int pv_dwconv3d(const pv_dwconv3d_desc* d, pv_stream_t stream);
 int pv_dwconv3d_psum_blocks(const pv_dwconv3d_desc* d);

@@ -92,15 +92,18 @@ def check_conv3d(conv):
     if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
         raise Unsupported("padding mode")
     depthwise = conv.groups == conv.in_channels == conv.out_channels and conv.groups > 1
-    if depthwise and tuple(conv.dilation) != (1, 1, 1):
+    if depthwise and tuple(conv.dilation) != (1, 1, 1) and not tuning.get("dwconv_dilated"):
         raise Unsupported("dilated depthwise conv")
     # channel-wise grouped conv with 2 / 4 / 8 channels per group (create_csn(stage_conv_b_width_per_group=...),
     # reference models/csn.py:34,169) rides in the depthwise kernel (pv_dwconv3d_desc.gw); 16 / 32 / 64 / 128 channels per
     # group (ResNeXt-3D conv_b up to 32x16d, the wide-group CSN variants) go to the grouped MFMA kernels in a bf16 session
     # (pv_conv3d_desc.groups, csrc/pv_gconv.hip and csrc/pv_gconv_wide.hip), dilated in H / W up to 4 at stride 1 included (the
-    # res5 conv_b of a detection backbone); every other grouping -- other widths, 2 / 4 / 8 per group with a dilation, a temporal
-    # dilation, a strided dilated dimension -- is evaluated as a dense conv with block-diagonal weights (emit_conv), on the HIP
-    # path like the rest of the deployed model.  A dilated DEPTHWISE conv is still declined: pv_dwconv3d_desc has no dilation.
+    # res5 conv_b of a detection backbone); every other grouping -- other widths, 16+ per group with a temporal dilation or a
+    # strided dilated dimension -- is evaluated as a dense conv with block-diagonal weights (emit_conv), on the HIP path like the
+    # rest of the deployed model.  A dilated depthwise or 2 / 4 / 8-per-group conv (the res5 conv_b of an ir-CSN / X3D-style
+    # detection backbone) is a pv_dwconv3d like the undilated one (pv_dwconv3d_desc.dil_t / dil_h / dil_w): the plane kernel's
+    # polyphase form for bf16 3x3x3 "same" convs dilated in H / W, the generic kernel for everything else.  tuning
+    # "dwconv_dilated" off restores what came before: the depthwise conv is declined, the narrow groups take the dense route.
     return depthwise or group_width(conv) > 1
 
 
@@ -111,7 +114,7 @@ def group_width(conv):
     gw = conv.in_channels // conv.groups
     if gw == 1:
         return 1
-    return gw if gw in (2, 4, 8) and tuple(conv.dilation) == (1, 1, 1) else 0
+    return gw if gw in (2, 4, 8) and (tuple(conv.dilation) == (1, 1, 1) or tuning.get("dwconv_dilated")) else 0
 
 
 def is_add_fusion(fn):
@@ -361,11 +364,13 @@ def can_fuse_pointwise_into_dw(sess, conv_a, conv_b, x):
     kt, kh, kw = conv_b.kernel_size
     st, sh, sw = conv_b.stride
     pt, ph, pw = _triple(conv_b.padding)
+    dil = tuple(int(v) for v in conv_b.dilation)     # the library declines a dilated conv_b: the pair of launches is emitted
     d = L.DwConv3dDesc()
     d.ldx, d.ldy = x.ld, pad8(conv_b.out_channels)
     d.B, d.Ti, d.Hi, d.Wi, d.C = x.B, x.T, x.H, x.W, conv_b.out_channels
-    d.To, d.Ho, d.Wo = _conv_out(x.T, kt, st, pt), _conv_out(x.H, kh, sh, ph), _conv_out(x.W, kw, sw, pw)
+    d.To, d.Ho, d.Wo = _conv_out(x.T, kt, st, pt, dil[0]), _conv_out(x.H, kh, sh, ph, dil[1]), _conv_out(x.W, kw, sw, pw, dil[2])
     d.kt, d.kh, d.kw, d.st, d.sh, d.sw, d.pt, d.ph, d.pw = kt, kh, kw, st, sh, sw, pt, ph, pw
+    d.dil_t, d.dil_h, d.dil_w = dil
     d.dtype, d.pw_cin = sess.pv_dtype, x.C
     return min(d.To, d.Ho, d.Wo) > 0 and L.lib().pv_dwconv3d_pw_supported(C.byref(d)) == 1
 
@@ -404,10 +409,13 @@ def emit_dwconv(sess, conv, x, norm=None, act=L.ACT_NONE, want_psum=False, out=N
     kt, kh, kw = conv.kernel_size
     st, sh, sw = conv.stride
     pt, ph, pw = _triple(conv.padding)
+    dil = tuple(int(v) for v in conv.dilation)
+    if dil != (1, 1, 1) and (w_mod or grid is not None or n_prefix or producer is not None or max(dil) > 32767):
+        raise Unsupported("dilated token pooling conv / fused producer")     # pv_dwconv3d refuses them
     Ti, Hi, Wi = grid if grid is not None else (x.T, x.H, x.W)
     if grid is not None and x.voxels != n_prefix + Ti * Hi * Wi:
         raise RuntimeError("token count %d does not match grid %s" % (x.voxels, (Ti, Hi, Wi)))
-    To, Ho, Wo = _conv_out(Ti, kt, st, pt), _conv_out(Hi, kh, sh, ph), _conv_out(Wi, kw, sw, pw)
+    To, Ho, Wo = _conv_out(Ti, kt, st, pt, dil[0]), _conv_out(Hi, kh, sh, ph, dil[1]), _conv_out(Wi, kw, sw, pw, dil[2])
     if min(To, Ho, Wo) <= 0:
         raise RuntimeError("conv output would be empty")
     Cc = x.C if producer is None else conv.in_channels
@@ -439,6 +447,8 @@ def emit_dwconv(sess, conv, x, norm=None, act=L.ACT_NONE, want_psum=False, out=N
         kt=kt, kh=kh, kw=kw, st=st, sh=sh, sw=sw, pt=pt, ph=ph, pw=pw,
         w_mod=w_mod, act=act, dtype=sess.pv_dtype, n_prefix=n_prefix, gw=gw if gw > 1 else 0,
     )
+    if dil != (1, 1, 1):      # (an undilated op keeps the fields it always had)
+        f.update(dil_t=dil[0], dil_h=dil[1], dil_w=dil[2])
     if producer is not None:
         f.update(_pointwise_producer_fields(sess, producer, x, Cc))
     psum = nblk = None
@@ -1012,7 +1022,8 @@ def can_fuse_temporal_dw(sess, first, second, mid_norm, mid_act, x, act):
     k = second.kernel_size
     if first.bias is not None or first.out_channels != second.in_channels or second.in_channels != second.out_channels:
         return False
-    if k[1:] != (1, 1) or second.stride != (1, 1, 1) or _triple(second.padding) != (k[0] // 2, 0, 0) or k[0] % 2 == 0:
+    if k[1:] != (1, 1) or second.stride != (1, 1, 1) or _triple(second.padding) != (k[0] // 2, 0, 0) or k[0] % 2 == 0 \
+            or tuple(second.dilation) != (1, 1, 1):
         return False
     kt, kh, kw = first.kernel_size
     st, sh, sw = first.stride

@@ -247,7 +247,8 @@ def emit_attention_pool_kv(sess, ap_k, ap_v, xkv, heads, label):
     dim = xkv.C // 2
     hd = dim // heads
     same = ("kernel_size", "stride", "padding", "dilation", "groups", "in_channels", "out_channels", "padding_mode")
-    if any(getattr(pk, a) != getattr(pv, a) for a in same) or pk.bias is not None or pv.bias is not None:
+    if any(getattr(pk, a) != getattr(pv, a) for a in same) or pk.bias is not None or pv.bias is not None \
+            or tuple(pk.dilation) != (1, 1, 1):
         return None
     if pk.groups != pk.in_channels or pk.in_channels != hd or hd % 8 or 2 * heads > 16 or 16 % (2 * heads):
         return None

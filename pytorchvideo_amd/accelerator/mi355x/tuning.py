@@ -12,6 +12,7 @@ OPTIONS = {
     "fuse_bc": True,             # conv_b (narrow dense conv) -> pointwise conv_c of a ResNet / SlowFast bottleneck as ONE launch (pv_conv3d pw2_*, round 6)  (emit.can_fuse_conv_bc)
     "grouped_conv": True,        # grouped conv with 16 / 32 / 64 / 128 channels per group on the grouped MFMA kernels instead of block-diagonal dense weights  (emit.emit_conv)
     "grouped_conv_dilated": True,  # ... also where the conv is dilated in H / W (polyphase form of the same kernels); off: dilated grouped convs keep the block-diagonal dense route  (emit.emit_conv)
+    "dwconv_dilated": True,      # dilated depthwise / 2-4-8-per-group conv as a pv_dwconv3d (plane kernel's polyphase form or the generic kernel); off: the depthwise conv is declined, the narrow groups take the block-diagonal dense route  (emit.check_conv3d, emit.group_width)
     "nonlocal_block": True,     # NonLocal (layers/nonlocal_net.py) inside a bf16 plan, its attention on pv_nonlocal_attention; off: the block stays a torch module between converted blocks  (emit.emit_nonlocal, blocks._probe)
     "fuse_stem": True,           # X3D stem (conv_xy + temporal depthwise + BN + ReLU) in one launch
     "stem_ncdhw": True,          # ... that reads the caller's bf16 NCDHW clip itself: no ingest launch (round 7)  (emit.emit_conv)

@@ -7,12 +7,21 @@
 // fp32.  The folded-BN affine, the activation and (optionally) the per-block partial sums
 // for the squeeze-excitation mean are fused into the epilogue; partial sums are written
 // per block (no atomics) so the result is run-to-run deterministic.
+#include <cstddef>
 #include <type_traits>
 #include "pv_common.h"
+
+// dil_t and dil_h / dil_w live in what were the two padding holes of the descriptor: no field moved, the size is unchanged
+static_assert(sizeof(pv_dwconv3d_desc) == 200, "pv_dwconv3d_desc grew");
+static_assert(offsetof(pv_dwconv3d_desc, pw_w) == 160 && offsetof(pv_dwconv3d_desc, gw) == 192, "pv_dwconv3d_desc fields moved");
 
 namespace {
 
 constexpr int kThreads = 256;
+
+// descriptor dilation: 0 means 1 (negative values never get past validate / the support queries)
+__host__ __device__ __forceinline__ int dil1(int v) { return v > 1 ? v : 1; }
+__host__ __device__ __forceinline__ bool dilated(const pv_dwconv3d_desc& d) { return d.dil_t > 1 || d.dil_h > 1 || d.dil_w > 1; }
 
 // one tap of a channel-wise grouped conv: output channel c of the chunk sums GW inputs of its own group
 template <int GW> __device__ __forceinline__ void grouped_taps(float (&acc)[8], const float (&f)[8], const float* wp, int w_p) {
@@ -72,16 +81,18 @@ __global__ __launch_bounds__(kThreads) void dwconv_kernel(const pv_dwconv3d_desc
     const T* __restrict__ X = static_cast<const T*>(d.x) + (long)b * d.x_bs + (long)d.n_prefix * d.ldx + c0;
     const int t0 = to * d.st - d.pt, h0 = ho * d.sh - d.ph;
     if constexpr (KW == 0) {
+      // the runtime variant is also the one that takes every dilated descriptor the plane kernel does not: taps step by the dilation
       const int w0 = wo0 * d.sw - d.pw;
+      const int dil_t = dil1(d.dil_t), dil_h = dil1(d.dil_h), dil_w = dil1(d.dil_w);
       for (int dt = 0; dt < d.kt; ++dt) {
-        const int ti = t0 + dt;
+        const int ti = t0 + dt * dil_t;
         if ((unsigned)ti >= (unsigned)d.Ti) continue;
         for (int dh = 0; dh < d.kh; ++dh) {
-          const int hi = h0 + dh;
+          const int hi = h0 + dh * dil_h;
           if ((unsigned)hi >= (unsigned)d.Hi) continue;
           const T* row = X + (long)(ti * d.Hi + hi) * d.Wi * d.ldx;
           for (int dw = 0; dw < d.kw; ++dw) {
-            const int wi = w0 + dw;
+            const int wi = w0 + dw * dil_w;
             if ((unsigned)wi >= (unsigned)d.Wi) continue;
             Chunk8<T> c;
             c.load(row + (long)wi * d.ldx);
@@ -222,13 +233,23 @@ __global__ void dw_prefix_kernel(const pv_dwconv3d_desc d) {
 //   * output plane t-1 is finished after input plane t: folded BN, activation, store (16 lanes
 //     cover 64 contiguous bytes of a voxel), and -- for squeeze-excitation -- lane-private
 //     partial sums reduced once per workgroup (no atomics: bitwise reproducible).
+//
+// DIL (S = 1 only): the conv is dilated by (dil_h, dil_w) <= 4 in H / W with "same" padding (ph = dil_h, pw = dil_w) -- the
+// res5 conv_b of an ir-CSN / X3D-style detection backbone.  Outputs ho = i dil_h + rh, wo = j dil_w + rw form phase (rh, rw),
+// and a phase is an UNDILATED 3x3x3 pad-1 conv of the input voxels of the same residue (pv_common.h, polyphase split).  A
+// workgroup owns a tile of ONE phase in phase coordinates: only the image address of a staged voxel (st_off) and of a stored
+// output (y_off) are scaled by the dilation; LDS layout, colperm, register taps, the three rolling accumulator sets, the
+// double-buffered plane loop and the epilogue are the undilated kernel's, and so are LDS reads and FMAs per output.  Phases are
+// tiled on their own extents and numbered phase-major (pv_phase_tile), empty phases get no workgroups, and the psum block of a
+// tile is that number: a fixed order, so the squeeze-excitation mean stays bit-reproducible.
 constexpr int kPlaneThreads = 256;  // 4 waves = 4 output rows
 constexpr int kPR = kPlaneThreads / 64;
 
 // (A four-waves-per-SIMD build of the narrow tile -- <= 128 registers, no second plane in flight, so that res4's 1792
 // workgroups are 2 rounds instead of 3 -- measured -1.8 % on X3D-M in the two-branch form in round 4 and is gone.)
-template <int S, int NW, int ACT>
+template <int S, int NW, int ACT, bool DIL = false>
 __global__ __launch_bounds__(kPlaneThreads, 1) void dw3_plane_kernel(const pv_dwconv3d_desc d, int ntiles, int ngroups) {
+  static_assert(!DIL || S == 1, "the polyphase form is a stride-1 conv");
   constexpr int TW = 4 * NW;               // tile width (outputs)
   constexpr int IH = (kPR - 1) * S + 3;
   constexpr int IW = (TW - 1) * S + 3;
@@ -258,10 +279,19 @@ __global__ __launch_bounds__(kPlaneThreads, 1) void dw3_plane_kernel(const pv_dw
   const int cbase = grp * 32;
   const int ch = cbase + cp * 2;           // first of this lane's two channels
   const bool ch_ok = ch < c_p;
-  const int tiles_w = (d.Wo + TW - 1) / TW;
-  const int th = tile_id / tiles_w, tw = tile_id - th * tiles_w;
   const int b = (int)(tb / ntiles);
-  const int ho0 = th * kPR, wo0 = tw * TW;
+  // DIL: tile, rows and columns below are in the coordinates of this workgroup's phase; dil_h / dil_w / pz map them to the image
+  const int dil_h = DIL ? dil1(d.dil_h) : 1, dil_w = DIL ? dil1(d.dil_w) : 1;
+  PvPhaseTile pz{0, 0, d.Ho, d.Wo, 0, 0};
+  if constexpr (DIL) {
+    pz = pv_phase_tile(tile_id, d.Ho, d.Wo, dil_h, dil_w, kPR, TW);
+  } else {
+    const int tiles_w = (d.Wo + TW - 1) / TW;
+    const int th = tile_id / tiles_w, tw = tile_id - th * tiles_w;
+    pz.ho0 = th * kPR;
+    pz.wo0 = tw * TW;
+  }
+  const int ho0 = pz.ho0, wo0 = pz.wo0;
   const int ho = ho0 + row, wo_first = wo0 + sx * NW;
   const int hi0 = ho0 * S - 1, wi0 = wo0 * S - 1;
 
@@ -306,7 +336,8 @@ __global__ __launch_bounds__(kPlaneThreads, 1) void dw3_plane_kernel(const pv_dw
     const int id = tid + i * kPlaneThreads;
     const int v = id >> 2, c = id & 3;
     const int ih = v / IW, iw = v - ih * IW;
-    const int hi = hi0 + ih, wi = wi0 + iw;
+    // DIL: phase voxel (hi0 + ih, wi0 + iw) is image voxel (.. * dil + r); phase coordinate -1 (the halo) stays negative
+    const int hi = DIL ? (hi0 + ih) * dil_h + pz.rh : hi0 + ih, wi = DIL ? (wi0 + iw) * dil_w + pz.rw : wi0 + iw;
     const bool ok = id < NITEM && (unsigned)hi < (unsigned)d.Hi && (unsigned)wi < (unsigned)d.Wi &&
                     (cbase + c * 8) < c_p;
     st_off[i] = ok ? (unsigned)((hi * d.Wi + wi) * d.ldx + cbase + c * 8) * 2u : kOOB;
@@ -343,8 +374,9 @@ __global__ __launch_bounds__(kPlaneThreads, 1) void dw3_plane_kernel(const pv_dw
 #pragma unroll
   for (int n = 0; n < NW; ++n) {
     const int wo = wo_first + n;
-    const bool ok = ch_ok && ho < d.Ho && wo < d.Wo;
-    y_off[n] = ok ? (unsigned)((ho * d.Wo + wo) * d.ldy + ch) * 2u : kOOB;
+    const bool ok = ch_ok && ho < pz.Hop && wo < pz.Wop;   // (the phase's extent; undilated: Ho, Wo)
+    const int ho_y = DIL ? ho * dil_h + pz.rh : ho, wo_y = DIL ? wo * dil_w + pz.rw : wo;
+    y_off[n] = ok ? (unsigned)((ho_y * d.Wo + wo_y) * d.ldy + ch) * 2u : kOOB;
     y_mask[n] = ok ? 1.f : 0.f;
   }
   const bool has_psum = d.psum != nullptr;
@@ -442,8 +474,13 @@ __global__ __launch_bounds__(kPlaneThreads, 1) void dw3_plane_kernel(const pv_dw
 // which layers the plane-streaming kernel takes, and with how many outputs per lane
 int plane_variant(const pv_dwconv3d_desc& d) {
   if (d.dtype != PV_BF16 || (d.n_prefix != 0 && d.psum) || d.gw > 1) return 0;
-  if (d.kt != 3 || d.kh != 3 || d.kw != 3 || d.st != 1 || d.pt != 1 || d.ph != 1 || d.pw != 1) return 0;
+  if (d.dil_t < 0 || d.dil_h < 0 || d.dil_w < 0 || d.dil_t > 1) return 0;
+  const int dh = dil1(d.dil_h), dw = dil1(d.dil_w);   // "same" padding: ph = dil_h, pw = dil_w (undilated: 1)
+  if (d.kt != 3 || d.kh != 3 || d.kw != 3 || d.st != 1 || d.pt != 1 || d.ph != dh || d.pw != dw) return 0;
   if (d.sh != d.sw || (d.sw != 1 && d.sw != 2)) return 0;
+  // the polyphase form (dw3_plane_kernel<1, NW, ACT, true>): stride 1, dilation up to 4, a plain conv_b
+  const bool dil = dh > 1 || dw > 1;
+  if (dil && (dh > 4 || dw > 4 || d.sw != 1 || d.n_prefix != 0 || d.w_mod != 0 || d.pw_w != nullptr || d.pw_cin > 0)) return 0;
   if (d.act != PV_ACT_NONE && d.act != PV_ACT_RELU && d.act != PV_ACT_SWISH) return 0;
   if ((long)d.Ti * d.Hi * d.Wi * d.ldx > 0x3fffffffL || (long)d.To * d.Ho * d.Wo * d.ldy > 0x3fffffffL)
     return 0;   // 31-bit byte offsets inside a clip (buffer addressing)
@@ -451,12 +488,16 @@ int plane_variant(const pv_dwconv3d_desc& d) {
   // The plain kernel lives on the number of waves with loads in flight: narrow tiles win on every grid measured (X3D-M 14^2, MViT 56^2 pool_q)
   // (X3D-M res4 conv_b: -7 %); the fused conv_a producer (pw_cin > 0) recomputes its halo, so it keeps the wide tile.
   const bool fused = d.pw_w != nullptr || d.pw_cin > 0;
-  return d.Wo >= (fused ? 12 : pv_tune("dw_wide_min_wo", 64)) ? 4 : 2;
+  // (dilated: a phase is the plane that is tiled, so its width -- phase 0 is the widest -- takes the place of Wo)
+  return pv_phase_extent(d.Wo, dw, 0) >= (fused ? 12 : pv_tune("dw_wide_min_wo", 64)) ? 4 : 2;
 }
 
-int plane_tiles(const pv_dwconv3d_desc& d, int nw) { return ((d.Ho + kPR - 1) / kPR) * ((d.Wo + 4 * nw - 1) / (4 * nw)); }
+// tiles of one clip = psum blocks: every phase tiled on its own extent (undilated: one phase, ceil(Ho / 4) * ceil(Wo / 4 NW))
+int plane_tiles(const pv_dwconv3d_desc& d, int nw) {
+  return pv_phase_tiles(d.Ho, dil1(d.dil_h), kPR) * pv_phase_tiles(d.Wo, dil1(d.dil_w), 4 * nw);
+}
 
-template <int S, int NW> int launch_plane(const pv_dwconv3d_desc& d, hipStream_t s) {
+template <int S, int NW, bool DIL = false> int launch_plane(const pv_dwconv3d_desc& d, hipStream_t s) {
   const int c_p = pv_round_up(d.C, 8);
   const int ntiles = plane_tiles(d, NW), ngroups = (c_p + 31) / 32;
   const long blocks = pv_ceil_div((long)ntiles * d.B, 8) * 8 * ngroups;
@@ -467,9 +508,9 @@ template <int S, int NW> int launch_plane(const pv_dwconv3d_desc& d, hipStream_t
     PV_LAUNCH(dw_prefix_kernel<bf16_t>, dim3((unsigned)pv_ceil_div(total, kThreads)), dim3(kThreads), 0, s, d);
     PV_LAUNCH_CHECK();
   }
-  if (d.act == PV_ACT_NONE) PV_LAUNCH((dw3_plane_kernel<S, NW, PV_ACT_NONE>), grid, block, 0, s, d, ntiles, ngroups);
-  else if (d.act == PV_ACT_RELU) PV_LAUNCH((dw3_plane_kernel<S, NW, PV_ACT_RELU>), grid, block, 0, s, d, ntiles, ngroups);
-  else PV_LAUNCH((dw3_plane_kernel<S, NW, PV_ACT_SWISH>), grid, block, 0, s, d, ntiles, ngroups);
+  if (d.act == PV_ACT_NONE) PV_LAUNCH((dw3_plane_kernel<S, NW, PV_ACT_NONE, DIL>), grid, block, 0, s, d, ntiles, ngroups);
+  else if (d.act == PV_ACT_RELU) PV_LAUNCH((dw3_plane_kernel<S, NW, PV_ACT_RELU, DIL>), grid, block, 0, s, d, ntiles, ngroups);
+  else PV_LAUNCH((dw3_plane_kernel<S, NW, PV_ACT_SWISH, DIL>), grid, block, 0, s, d, ntiles, ngroups);
   PV_LAUNCH_CHECK();
   return PV_OK;
 }
@@ -489,7 +530,7 @@ bool geom(const pv_dwconv3d_desc& d, DwGeom* g) {
   const int c_p = pv_round_up(d.C, 8);
   const int CG = c_p / 8;
   if (CG > kThreads) return false;
-  g->nw = d.gw > 1 ? 1 : variant_nw(d);
+  g->nw = (d.gw > 1 || dilated(d)) ? 1 : variant_nw(d);
   g->gpb = kThreads / CG;
   g->wgroups = (d.Wo + g->nw - 1) / g->nw;
   const long upb = (long)d.To * d.Ho * g->wgroups;
@@ -525,7 +566,7 @@ template <typename T> int launch_dw(const pv_dwconv3d_desc& d, const DwGeom& g, 
     PV_LAUNCH(dw_prefix_kernel<T>, dim3((unsigned)pv_ceil_div(total, kThreads)), dim3(kThreads), 0, s, d);
     PV_LAUNCH_CHECK();
   }
-  if (d.gw > 1) return launch_variant<T, 0, 1, 1>(d, g, s);   // channel-wise grouped: the runtime variant
+  if (d.gw > 1 || dilated(d)) return launch_variant<T, 0, 1, 1>(d, g, s);   // channel-wise grouped, dilated: the runtime variant
   if (d.kw == 3 && d.sw == 1) return launch_variant<T, 3, 1, 4>(d, g, s);
   if (d.kw == 3 && d.sw == 2) return launch_variant<T, 3, 2, 4>(d, g, s);
   if (d.kw == 1 && d.sw == 1) return launch_variant<T, 1, 1, 4>(d, g, s);
@@ -534,13 +575,21 @@ template <typename T> int launch_dw(const pv_dwconv3d_desc& d, const DwGeom& g, 
 
 int validate(const pv_dwconv3d_desc& d) {
   if (!d.x || !d.w || !d.y) return PV_ERR_INVALID;
+  if (d.dil_t < 0 || d.dil_h < 0 || d.dil_w < 0) return PV_ERR_INVALID;   // before anything below reads a dilation
   if (d.B <= 0 || d.C <= 0 || d.To <= 0 || d.Ho <= 0 || d.Wo <= 0) return PV_ERR_INVALID;
   if (d.ldx % 8 || d.ldy % 8 || d.x_bs % 8 || d.y_bs % 8) return PV_ERR_INVALID;
   if (d.kt < 1 || d.kh < 1 || d.kw < 1 || d.st < 1 || d.sh < 1 || d.sw < 1) return PV_ERR_INVALID;
   if (d.w_mod < 0 || (d.w_mod > 0 && d.w_mod % 8)) return PV_ERR_UNSUPPORTED;
-  if ((d.Ti + 2 * d.pt - d.kt) / d.st + 1 != d.To || (d.Hi + 2 * d.ph - d.kh) / d.sh + 1 != d.Ho ||
-      (d.Wi + 2 * d.pw - d.kw) / d.sw + 1 != d.Wo)
+  // nn.Conv3d's output size on the kernel extent (k - 1) * dilation + 1 (64-bit: any field may hold any int32)
+  const long et = (long)(d.kt - 1) * dil1(d.dil_t) + 1, eh = (long)(d.kh - 1) * dil1(d.dil_h) + 1, ew = (long)(d.kw - 1) * dil1(d.dil_w) + 1;
+  if ((d.Ti + 2L * d.pt - et) / d.st + 1 != d.To || (d.Hi + 2L * d.ph - eh) / d.sh + 1 != d.Ho ||
+      (d.Wi + 2L * d.pw - ew) / d.sw + 1 != d.Wo)
     return PV_ERR_INVALID;
+  if (dilated(d)) {
+    if (et > d.Ti + 2L * d.pt || eh > d.Hi + 2L * d.ph || ew > d.Wi + 2L * d.pw) return PV_ERR_INVALID;   // extent beyond the padded input
+    // token pooling convs (cls rows, a filter shared over heads) and the fused producer are never dilated
+    if (d.n_prefix > 0 || d.w_mod > 0 || d.pw_w != nullptr) return PV_ERR_UNSUPPORTED;
+  }
   if (d.B > 65535) return PV_ERR_UNSUPPORTED;
   if (d.n_prefix < 0 || (d.n_prefix > 0 && d.psum)) return PV_ERR_INVALID;
   if (d.gw < 0 || (d.gw > 1 && d.gw != 2 && d.gw != 4 && d.gw != 8)) return PV_ERR_UNSUPPORTED;
@@ -557,12 +606,14 @@ int pv_pwdw_launch(const pv_dwconv3d_desc& d, hipStream_t s);  // pv_pwdw.hip
 
 extern "C" int pv_dwconv3d_pw_supported(const pv_dwconv3d_desc* d) {
   if (!d || d->B <= 0 || d->C <= 0 || d->To <= 0 || d->Ho <= 0 || d->Wo <= 0) return 0;
+  if (d->dil_t < 0 || d->dil_h < 0 || d->dil_w < 0 || dilated(*d)) return 0;   // the fused producer is never dilated
   return pv_pwdw_supported(*d);
 }
 
 extern "C" int pv_dwconv3d_psum_blocks(const pv_dwconv3d_desc* d) {
   if (!d) return PV_ERR_INVALID;
   if (d->B <= 0 || d->C <= 0 || d->To <= 0 || d->Ho <= 0 || d->Wo <= 0) return PV_ERR_INVALID;
+  if (d->dil_t < 0 || d->dil_h < 0 || d->dil_w < 0) return PV_ERR_INVALID;
   if (const int nw = plane_variant(*d)) return plane_tiles(*d, nw);  // pointers are not needed for the count
   DwGeom g;
   if (!geom(*d, &g)) return PV_ERR_UNSUPPORTED;
@@ -577,6 +628,7 @@ extern "C" int pv_dwconv3d(const pv_dwconv3d_desc* dp, pv_stream_t stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d.pw_w) return pv_pwdw_launch(d, s);   // fused conv_a -> conv_b; no unfused fallback inside the library
   if (const int nw = plane_variant(d)) {
+    if (d.dil_h > 1 || d.dil_w > 1) return nw == 4 ? launch_plane<1, 4, true>(d, s) : launch_plane<1, 2, true>(d, s);
     if (d.sw == 1) return nw == 4 ? launch_plane<1, 4>(d, s) : launch_plane<1, 2>(d, s);
     return nw == 4 ? launch_plane<2, 4>(d, s) : launch_plane<2, 2>(d, s);
   }
